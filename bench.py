@@ -2,6 +2,7 @@
 """bench.py — accepted tokens/sec + acceptance rate of the draft-then-verify loop.
 
     python bench.py --gpus 1 --steps 40 --warmup 5
+    python bench.py --gpus 1 --steps 40 --warmup 5 --full [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: bench.py starts the N ranks itself, see launch_ranks)
@@ -16,13 +17,19 @@ With N > 1 every rank decodes its own prompts on its own GPU (data parallel over
 weak scaling, no collective in the data path) and the per-rank stats are all-gathered
 once over RCCL.
 
-One JSON line is printed by rank 0. Besides the contract keys it carries
+One JSON line is printed by rank 0. A plain run sets up, warms up, times the steps and prints
+it; besides the contract keys it carries
+  step_roofline_frac — (K*W_draft + W_target bytes) / step time / 8 TB/s for the whole step
+With --full the line also carries the measurements that take runs of their own:
   roofline     — the dominant kernel (fused norm + gate/up + SwiGLU GEMV of the target at
                  T = K+1 tokens) priced against HBM: algorithmic bytes N*K*2 per launch over
                  its average launch duration, timed here with HIP events on the launch stream
   cpu_baseline — the oracle's reference-faithful loop (2K full-prefix forwards per step, as
                  the reference with KV append off) on the host cores, bounded sample
-  step_roofline_frac — (K*W_draft + W_target bytes) / step time / 8 TB/s for the whole step
+  h2d_prompt_us / value_pcie_inclusive — the pinned host -> device copy of the prompt ids
+--dump-outputs DIR writes what the last timed step returned to its caller (the step record:
+accept_len, n_new, cur_len, new_tokens, draft_tokens, target_ids) and every row's generated
+tokens so far as DIR/<name>.npy (float64, rows padded with -1); ranks > 0 add _rank<r>.
 """
 
 from __future__ import annotations
@@ -59,8 +66,8 @@ def parse():
     ap.add_argument("--draft", default="llama-3.2-1b")
     ap.add_argument("--flip", type=float, default=0.2, help="fraction of tokens whose draft successor differs")
     ap.add_argument("--cpu-baseline-steps", type=int, default=4,
-                    help="steps per timed repeat of the CPU baseline leg (1 warm-up step + 3 repeats); 0 disables the leg")
-    ap.add_argument("--no-probe", action="store_true")
+                    help="steps per timed repeat of the CPU baseline leg of --full (1 warm-up step + 3 repeats); 0 disables the leg")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the roofline probe")
     ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: both models stream an OCP e4m3 copy of their Linear weights (per-row scales, bf16 activations and "
                          "MFMA); not the headline configuration (BASELINE config 2 is bf16), CPU parity leg uses the dequantised weights")
@@ -75,7 +82,16 @@ def parse():
     ap.add_argument("--do-sample", action="store_true",
                     help="sampled bonus token (T=0.7, top_k=50, top_p=0.9: the reference's default sampler) instead of greedy; "
                          "not the headline configuration (SPECDEC_DETERMINISTIC is greedy), no CPU parity leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the roofline probe (every weight-streaming "
+                         "kernel timed live; --no-probe drops it), the CPU baseline with its parity check (--cpu-baseline-steps) and the "
+                         "pinned H2D copy of the prompt ids; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's record and every row's generated tokens as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build_models(args, device):
@@ -392,6 +408,24 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, rec, rows, rank):
+    """--dump-outputs: what the last timed step handed its caller (the StepRecord the host rules consumed) and the tokens every
+    row has emitted so far, as float64 .npy files (token ids are exact in float64; ragged rows are padded with -1)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: getattr(rec, name) for name in ("accept_len", "n_new", "cur_len", "new_tokens", "draft_tokens", "target_ids")}
+    width = max(len(r) for r in rows)
+    gen = np.full((len(rows), width), -1, dtype=np.float64)
+    for b, r in enumerate(rows):
+        gen[b, :len(r)] = r
+    arrays["generated_tokens"] = gen
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -477,16 +511,18 @@ def main():
     p0, a0 = sess.stats["proposed"], sum(r.accepted for r in sess.rows)
     import gc
 
-    # PCIe-inclusive figure (contract: inputs are resident when the timed region starts; what a caller with HOST prompt
-    # buffers pays on top is this one copy per request): B x PROMPT_LEN int32 ids, pinned host -> device
-    h_ids = torch.tensor(prompts, dtype=torch.int32).pin_memory()
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    for _ in range(20):
-        d_ids = h_ids.to(device, non_blocking=True)
+    h2d_s = None
+    if args.full:
+        # PCIe-inclusive figure (contract: inputs are resident when the timed region starts; what a caller with HOST prompt
+        # buffers pays on top is this one copy per request): B x PROMPT_LEN int32 ids, pinned host -> device
+        h_ids = torch.tensor(prompts, dtype=torch.int32).pin_memory()
         torch.cuda.synchronize()
-    h2d_s = (time.perf_counter() - th) / 20
-    del d_ids
+        th = time.perf_counter()
+        for _ in range(20):
+            d_ids = h_ids.to(device, non_blocking=True)
+            torch.cuda.synchronize()
+        h2d_s = (time.perf_counter() - th) / 20
+        del d_ids
     gc.collect()
     gc.disable()            # no collector pauses between graph launches inside the timed region
     barrier()
@@ -497,7 +533,10 @@ def main():
     dt_local = time.perf_counter() - t0
     gc.enable()
     barrier()
+    last_rec = sess.last_record        # the record of the last timed step (steps launched ahead of it are drained below)
     sess.finish()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_rec, [list(r.generated) for r in sess.rows], rank)
     n_tok = sum(len(r.generated) for r in sess.rows) - n0
     proposed = sess.stats["proposed"] - p0
     accepted_ref = sum(r.accepted for r in sess.rows) - a0          # reference definition (bonus counted)
@@ -545,16 +584,17 @@ def main():
         "ranks": {"ms_per_step_min": min(job.column("wall_ns")) / 1e6 / args.steps, "ms_per_step_max": max(job.column("wall_ns")) / 1e6 / args.steps,
                   "numa_node": job.column("numa_node"), "cpus": job.column("cpus")},
         "rank0_numa": numa, "collective_backend": ("gloo (rehearsal: all ranks on cuda:0)" if rehearsal else "nccl (RCCL)") if world > 1 else None,
-        # one-off H2D of the prompt ids of this rank's rows, measured, and the rate with it added to the timed region
-        "h2d_prompt_us": h2d_s * 1e6,
-        "value_pcie_inclusive": tokens / (t_max + h2d_s),
     }
+    if h2d_s is not None:
+        # one-off H2D of the prompt ids of this rank's rows, measured, and the rate with it added to the timed region
+        out["h2d_prompt_us"] = h2d_s * 1e6
+        out["value_pcie_inclusive"] = tokens / (t_max + h2d_s)
     log(f"timed region: {ms_per_step:.3f} ms/step, {value:.1f} tok/s")
-    # ---- roofline of the dominant kernel, timed live with HIP events --------------------
-    if not args.no_probe:
+    # ---- roofline of the dominant kernel, timed live with HIP events (--full) ------------
+    if args.full and not args.no_probe:
         out["roofline"] = roofline_leg(sess, B, K, wd, medusa or heads is not None)
-    # ---- CPU baseline (rank 0, N = 1 only) ---------------------------------------------------
-    if world == 1 and args.cpu_baseline_steps > 0:
+    # ---- CPU baseline (rank 0, N = 1 only; --full) ----------------------------------------
+    if args.full and world == 1 and args.cpu_baseline_steps > 0:
         gpu_rows = [list(r.generated) for r in sess.rows]
         cb, same = cpu_baseline(drf, tgt, prompts, K, gpu_rows, wd, seg_steps=args.cpu_baseline_steps, gpu_counters=list(sess.rows[0].counters))
         out["cpu_baseline"] = cb

@@ -3,7 +3,7 @@
 tag=${1:-final}
 export TMPDIR=/tmp
 O=$PWD/gpurun_out
-python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -20 $O/${tag}_bench.err; exit 1; }
+python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -20 $O/${tag}_bench.err; exit 1; }
 echo "bench done"; tail -c 600 $O/${tag}_bench.json; echo
 B="python3 bench.py --steps 30 --warmup 5 --cpu-baseline-steps 0 --no-probe"
 P="python3 bench.py --steps 10 --warmup 2 --cpu-baseline-steps 0 --no-probe"   # counter passes serialise the kernels: fewer steps

@@ -29,7 +29,7 @@ profile() {   # profile <name> <workload string> <bench flags...>
 for part in $parts; do
   case $part in
     headline)
-      python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+      python3 bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
       echo "bench done"; tail -c 400 $O/bench.json; echo
       profile headline "llama-3.2-3b+llama-3.2-1b K=4 B=1" ;;
     b8) profile batch8 "llama-3.2-3b+llama-3.2-1b K=4 B=8" --batch 8 ;;

@@ -542,7 +542,11 @@ def gen_fake():
     fed ids; the token function hashes a tuple of ints, which CPython does not randomise."""
     SpeculativePipeline = _reference_pipeline_class()
     cfg = os.path.join(REF, "configs", "specdec.yaml")
-    out = {"config": "configs/specdec.yaml of the reference, unchanged", "runs": [], "token_function": []}
+    import yaml
+
+    with open(cfg) as f:
+        values = yaml.safe_load(f)
+    out = {"config": "configs/specdec.yaml of the reference, unchanged", "config_values": values, "runs": [], "token_function": []}
     for prompt, n in (("Hello world", 8), ("The quick brown fox", 12), ("a", 5)):
         pipe = SpeculativePipeline(config_path=cfg)
         ids = [int(x) for x in pipe.base_lm.encode(prompt)[0].tolist()]

@@ -50,3 +50,37 @@ def test_world_size_must_equal_gpus():
     env = dict(_env(), WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     res = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--dry-run"], env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "WORLD_SIZE=2" in res.stderr
+
+
+def test_steps_must_be_at_least_one():
+    res = subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-run"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert res.returncode == 2 and "--steps must be >= 1" in res.stderr
+
+
+def test_dump_outputs_writes_the_step_record_as_float64(tmp_path):
+    """--dump-outputs: one float64 .npy per field of the last step's record plus every row's tokens (ragged rows padded with -1);
+    ranks > 0 write the same names with a _rank<r> suffix."""
+    import importlib.util
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    i32 = np.int32
+    rec = SimpleNamespace(accept_len=np.array([4, 1], i32), n_new=np.array([5, 2], i32), cur_len=np.array([40, 37], i32),
+                          new_tokens=np.array([[7, 8, 9, 10, 128000], [11, 12, 0, 0, 0]], i32),
+                          draft_tokens=np.array([[7, 8, 9, 10], [11, 3, 4, 5]], i32),
+                          target_ids=np.array([[7, 8, 9, 10, 128000], [11, 12, 1, 1, 1]], i32))
+    rows = [[5, 6, 7, 8, 9, 10, 128000], [11, 12]]
+    bench.dump_outputs(str(tmp_path), rec, rows, 0)
+    bench.dump_outputs(str(tmp_path), rec, rows, 1)
+    fields = ["accept_len", "n_new", "cur_len", "new_tokens", "draft_tokens", "target_ids"]
+    assert sorted(os.listdir(tmp_path)) == sorted([f"{n}{s}.npy" for n in fields + ["generated_tokens"] for s in ("", "_rank1")])
+    for n in fields:
+        a = np.load(tmp_path / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, getattr(rec, n))
+    g = np.load(tmp_path / "generated_tokens_rank1.npy")
+    assert g.dtype == np.float64 and g.shape == (2, 7)
+    assert g[0].tolist() == rows[0] and g[1].tolist() == [11, 12] + [-1] * 5
