@@ -336,6 +336,30 @@ int sd_model_set_length_hint(sd_model* m, int max_len);
 /* 1 when a pass of T tokens of one row would run as the persistent launch right now, else 0. */
 int sd_model_persist_active(const sd_model* m, int T);
 
+/* Prompt prefill: how a pass of >= 96 positions per row (a prompt being absorbed into the KV cache) is computed.
+ *   SD_PREFILL_AUTO     the default after every bind: rocBLAS GEMMs for a Llama model with bf16 row-major weights and dense
+ *                       KV when the library can be opened (and SPECDEC_NO_GEMM_PREFILL is unset), else the 128-token passes
+ *   SD_PREFILL_PASSES   always the decode-shaped 128-token passes
+ *   SD_PREFILL_ROCBLAS  rocBLAS GEMMs over the HF-layout bf16 weights (Llama, bf16 storage, dense KV)
+ *   SD_PREFILL_NATIVE   this library's MFMA GEMM over the packed weights (Llama, bf16 or fp8 storage, dense or paged KV)
+ * Under every backend a pass that asks for logits, runs under stream capture or is gated by adaptive K takes the passes. */
+enum sd_prefill_backend { SD_PREFILL_AUTO = 0, SD_PREFILL_PASSES = 1, SD_PREFILL_ROCBLAS = 2, SD_PREFILL_NATIVE = 3 };
+
+/* 1 when `backend` can be used in this process (ROCBLAS: the library opens), else 0. */
+int sd_prefill_backend_available(int backend);
+
+/* Select the prefill backend of `m` until the next bind. Nonzero (with sd_last_error) for an unknown value; ROCBLAS when the
+ * library is missing or the model is fp8, paged or GPT-2; NATIVE for GPT-2, for a model without packed weights
+ * (SPECDEC_NO_PACK) or with d_model, Hq*D or d_ff not a multiple of 64. A choice is never replaced by another GEMM backend. */
+int sd_model_set_prefill_backend(sd_model* m, int backend);
+
+/* The configured backend (enum sd_prefill_backend). */
+int sd_model_prefill_backend(const sd_model* m);
+
+/* Prompt rows absorbed by SD_PREFILL_PASSES, _ROCBLAS or _NATIVE since the bind: one per row of a forward call with >= 96
+ * positions per row. -1 for another value. */
+int64_t sd_model_prefill_count(const sd_model* m, int backend);
+
 /* Rows [row0, row0+n) of one of the workspace buffers the last pass left behind (bf16, asynchronous copy on `stream`):
  * which = 0 residual stream [d_model] (= sd_model_hidden_rows), 1 q after RoPE [Hq*D], 2 attention rows [Hq*D],
  * 3 MLP activation [d_ff]; all of the LAST layer. For stage-by-stage checks of the persistent launch against the

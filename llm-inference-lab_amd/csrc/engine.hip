@@ -66,6 +66,9 @@ struct sd_model {
   unsigned* p_sync = nullptr;              // [0] launch counter, [1] status
   unsigned long long* p_debug = nullptr;   // optional timeline (sd_model_probe_persist)
   void* prefill_ws = nullptr;              // lazily allocated workspace of the GEMM prefill path (csrc/prefill_gemm.hip)
+  int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
+  int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
+  sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
   unsigned* host_status = nullptr;         // pinned host word: a persistent launch that gives up stores its reason here as well
   int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
   int len_hint = 0;                        // caller's bound on the rows' current lengths (sd_model_set_length_hint; default Lmax)
@@ -73,6 +76,7 @@ struct sd_model {
   ~sd_model() {
     if (host_status) (void)hipHostFree(host_status);
     if (prefill_ws) (void)hipFree(prefill_ws);
+    sd::native_plan_free(native_plan);
   }
 };
 
@@ -410,17 +414,44 @@ static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, con
   SD_REQUIRE(!logits_out || logits_dtype == SD_F32 || logits_dtype == SD_BF16, "forward: logits dtype %d", logits_dtype);
   const int V = m->cfg.vocab;
   const int cap = (B * M <= m->small_t) ? m->small_t : m->max_t;  // tokens per pass
-  // A prompt (M >= 96 positions per row, whatever the pass size of the decode-shaped kernels). A prompt of a Llama model with bf16 row-major weights and dense KV is absorbed as GEMMs (csrc/prefill_gemm.hip:
-  // <= 512 positions per chunk, every matrix product one library GEMM, this repo's norm / epilogue / attention kernels around them) when
-  // the caller wants no logits of the prompt positions (skip_head, or ids only — the head then runs over the LAST chunk's rows below).
+  // A prompt (M >= 96 positions per row, whatever the pass size of the decode-shaped kernels) is absorbed as GEMMs (csrc/prefill_gemm.hip:
+  // <= 512 positions per chunk, every matrix product one GEMM, this repo's norm / epilogue / attention kernels around them) when the
+  // caller wants no logits of the prompt positions (skip_head, or ids only — the head then runs over the LAST chunk's rows below), the
+  // pass is not being captured and no adaptive-K word gates it. Which GEMM (sd_model_set_prefill_backend): SD_PREFILL_AUTO = rocBLAS for a
+  // Llama model with bf16 row-major weights and dense KV when the library opens, else the passes; SD_PREFILL_ROCBLAS / _NATIVE = that
+  // GEMM (validated when it was set); SD_PREFILL_PASSES = never a GEMM.
   static const int prefill_min = getenv(debug_env::kPrefillMinTokens) ? atoi(getenv(debug_env::kPrefillMinTokens)) : kPrefillMinTokens;
-  if (M >= prefill_min && m->cfg.arch == SD_ARCH_LLAMA && !m->w8() && !m->block_table && !logits_out && m->cfg.weight_dtype == SD_BF16 &&
-      !getenv(debug_env::kNoGemmPrefill) && !m->skip_k && prefill_gemm_available()) {
-    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap_st);
-    if (cap_st == hipStreamCaptureStatusNone) {
+  if (M >= prefill_min) {
+    int backend = SD_PREFILL_PASSES;
+    const bool gemm_ok = m->cfg.arch == SD_ARCH_LLAMA && !logits_out && !m->skip_k;
+    if (m->prefill_backend == SD_PREFILL_AUTO) {
+      if (gemm_ok && !m->w8() && !m->block_table && m->cfg.weight_dtype == SD_BF16 && !getenv(debug_env::kNoGemmPrefill) && prefill_gemm_available())
+        backend = SD_PREFILL_ROCBLAS;
+    } else if (m->prefill_backend != SD_PREFILL_PASSES && gemm_ok) {
+      backend = m->prefill_backend;
+    }
+    if (backend != SD_PREFILL_PASSES) {
+      hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+      (void)hipStreamIsCapturing(st, &cap_st);
+      if (cap_st != hipStreamCaptureStatusNone) backend = SD_PREFILL_PASSES;
+    }
+    if (backend == SD_PREFILL_PASSES) {
+      m->prefill_count[SD_PREFILL_PASSES] += B;
+    } else {
       if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(m->cfg)));
       PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
+      pm.block_table = m->block_table;
+      pm.page_shift = m->page_shift;
+      pm.max_pages = m->max_pages;
+      pm.n_pages = m->n_pages;
+      if (backend == SD_PREFILL_NATIVE) {
+        if (!m->native_plan.buf)
+          if (int rc = native_plan_build(m->cfg, m->native_plan)) return rc;
+        pm.gemm = PREFILL_GEMM_NATIVE;
+        pm.packed = m->packed.data();
+        pm.scales = m->w8() ? m->scales.data() : nullptr;
+        pm.plan = &m->native_plan;
+      }
       for (int b0 = 0; b0 < B; ++b0) {
         for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
           const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
@@ -441,6 +472,7 @@ static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, con
           }
         }
       }
+      m->prefill_count[backend] += B;
       return 0;
     }
   }
@@ -586,6 +618,8 @@ extern "C" int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, i
   m->Lmax = Lmax;
   m->block_table = nullptr;
   m->page_shift = m->max_pages = m->n_pages = 0;
+  m->prefill_backend = SD_PREFILL_AUTO;
+  for (int64_t& n : m->prefill_count) n = 0;
   return carve_workspace(m, workspace);
 }
 
@@ -616,6 +650,8 @@ extern "C" int sd_model_bind_paged(sd_model* m, void* k_pool, void* v_pool, int 
   m->page_shift = shift;
   m->max_pages = max_pages_per_row;
   m->n_pages = n_pages;
+  m->prefill_backend = SD_PREFILL_AUTO;
+  for (int64_t& n : m->prefill_count) n = 0;
   return carve_workspace(m, workspace);
 }
 
@@ -718,6 +754,38 @@ extern "C" int sd_model_set_length_hint(sd_model* m, int max_len) {
   SD_REQUIRE(m && m->x, "set_length_hint: NULL argument / model not bound");
   m->len_hint = (max_len <= 0 || max_len > m->Lmax) ? m->Lmax : max_len;
   return 0;
+}
+
+extern "C" int sd_prefill_backend_available(int backend) {
+  if (backend == SD_PREFILL_ROCBLAS) return prefill_gemm_library_present() ? 1 : 0;
+  return (backend == SD_PREFILL_AUTO || backend == SD_PREFILL_PASSES || backend == SD_PREFILL_NATIVE) ? 1 : 0;
+}
+
+extern "C" int sd_model_set_prefill_backend(sd_model* m, int backend) {
+  clear_error();
+  SD_REQUIRE(m, "set_prefill_backend: NULL model");
+  SD_REQUIRE(backend >= SD_PREFILL_AUTO && backend <= SD_PREFILL_NATIVE, "set_prefill_backend: unknown backend %d", backend);
+  const bool gpt2 = m->cfg.arch == SD_ARCH_GPT2;
+  if (backend == SD_PREFILL_ROCBLAS) {
+    SD_REQUIRE(!gpt2, "set_prefill_backend: rocBLAS prefill serves Llama models only (this model is GPT-2)");
+    SD_REQUIRE(!m->w8() && m->cfg.weight_dtype == SD_BF16,
+               "set_prefill_backend: rocBLAS prefill multiplies the bf16 HF-layout weights, not this model's fp8 storage");
+    SD_REQUIRE(!m->block_table, "set_prefill_backend: rocBLAS prefill serves dense KV only (this model is bound to a paged cache)");
+    SD_REQUIRE(prefill_gemm_available(), "set_prefill_backend: rocBLAS could not be opened");
+  } else if (backend == SD_PREFILL_NATIVE) {
+    SD_REQUIRE(!gpt2, "set_prefill_backend: native prefill serves Llama models only (this model is GPT-2)");
+    SD_REQUIRE(m->is_packed(), "set_prefill_backend: native prefill reads the packed weights (this model has none: SPECDEC_NO_PACK)");
+    SD_REQUIRE(prefill_native_shapes_ok(m->cfg), "set_prefill_backend: native prefill needs d_model, Hq*D and d_ff multiples of 64");
+  }
+  m->prefill_backend = backend;
+  return 0;
+}
+
+extern "C" int sd_model_prefill_backend(const sd_model* m) { return m ? m->prefill_backend : -1; }
+
+extern "C" int64_t sd_model_prefill_count(const sd_model* m, int backend) {
+  if (!m || backend < SD_PREFILL_PASSES || backend > SD_PREFILL_NATIVE) return -1;
+  return m->prefill_count[backend];
 }
 
 extern "C" int sd_model_persist_active(const sd_model* m, int T) {

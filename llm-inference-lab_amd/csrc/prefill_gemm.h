@@ -11,16 +11,46 @@ constexpr int kPrefillChunk = 512;   // positions per GEMM chunk (workspace: ~11
 // (profiles/round4_context_scaling.md): they cross below 96.
 constexpr int kPrefillMinTokens = 96;
 
+// ---- the native GEMM over the packed tile streams (csrc/prefill_mfma.hip) ----------------------------------------------------
+struct NativeMat {          // one matrix shape of a layer, split into row blocks of whole packed tiles
+  const int4* tiles;        // device: {first row in its block, pairs, first pair, 0} per tile
+  const int2* blocks;       // device: {first tile, tiles} per row block
+  int n_blocks, rb;         // row blocks; rows per block (128 or 64)
+  int N, K, n_pairs, epi;
+};
+struct NativePlan {
+  NativeMat mat[4][2];      // [qkv, out, gate / up, down][128-row blocks, 64-row blocks]
+  int head_dim = 0;
+  void* buf = nullptr;      // device tables of all eight
+};
+bool prefill_native_shapes_ok(const sd_model_config& c);     // Llama, every K a multiple of 64
+int native_plan_build(const sd_model_config& c, NativePlan& plan);
+void native_plan_free(NativePlan& plan);
+// Y[T][N] fp32 (HF row order) = X[T][K] x W^T, W = the packed stream of matrix `which` (0 qkv, 1 out, 2 gate / up, 3 down) of a layer
+int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const float* w_scale, bool w8, const uint16_t* X, int ldx, float* Y,
+                        int T, hipStream_t st);
+
+enum PrefillGemm { PREFILL_GEMM_ROCBLAS = 0, PREFILL_GEMM_NATIVE = 1 };
+
 struct PrefillModel {
   const sd_model_config* cfg;
-  uint16_t* k_cache;    // [layer][B][Hkv][Lmax][D]
-  uint16_t* v_cache;    // [layer][B][Hkv][D][Lmax]
+  uint16_t* k_cache;    // dense: [layer][B][Hkv][Lmax][D]; paged: page pools [layer][pages][Hkv][P][D]
+  uint16_t* v_cache;    // dense: [layer][B][Hkv][D][Lmax]; paged: [layer][pages][Hkv][D][P]
   int B, Lmax;
   float* attn_ws;       // split-KV workspace of the attention kernel
   unsigned* attn_cnt;
+  // paged KV (sd_model_bind_paged): null = dense rows
+  const int32_t* block_table = nullptr;   // [B][max_pages]
+  int page_shift = 0, max_pages = 0, n_pages = 0;
+  // matrix product: rocBLAS over the HF-layout bf16 weights, or the native GEMM over the packed streams
+  int gemm = PREFILL_GEMM_ROCBLAS;
+  const void* const* packed = nullptr;    // native: per matrix (4 per layer + lm_head, packing order)
+  const float* const* scales = nullptr;   // native, fp8 storage: fp32 row scales per matrix (else null)
+  const NativePlan* plan = nullptr;
 };
 
-bool prefill_gemm_available();                               // rocBLAS could be opened (dlopen at first use)
+bool prefill_gemm_available();                               // rocBLAS could be opened (dlopen at first use) and a handle created
+bool prefill_gemm_library_present();                         // rocBLAS could be opened (dlopen only: no device work)
 size_t prefill_gemm_workspace_bytes(const sd_model_config& c);
 int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int cache_row, int Mc, void* ws,
                        uint16_t** x_out, hipStream_t st);

@@ -16,9 +16,13 @@
 // Sums differ from the GEMV path in fp32 summation order only; tests/test_hip_prefill_gemm_gpu.py holds the chunked path against the
 // 128-token passes (next tokens, logits, K / V rows).
 //
-// rocBLAS is opened at first use (dlopen: the C-ABI library itself does not link it); when it is missing, or for GPT-2 models, fp8
-// storage or paged KV, prefill falls back to the 128-token passes. Llama, bf16 row-major weights (the caller's HF-layout tensors:
-// sd_layer_weights), dense KV.
+// The matrix product is one of two backends (PrefillModel::gemm):
+//   * rocBLAS, opened at first use (dlopen: the C-ABI library itself does not link it), over the caller's HF-layout bf16 tensors
+//     (sd_layer_weights): Llama, bf16 storage, dense KV. When it is missing, or for GPT-2 models, fp8 storage or paged KV, the
+//     default rule (SD_PREFILL_AUTO) sends the prompt through the 128-token passes.
+//   * the native GEMM (csrc/prefill_mfma.hip) over the packed tile streams of csrc/pack.hip, the one weight copy every model
+//     has in both storage dtypes: Llama, bf16 or fp8 storage, dense or paged KV. It writes Y in HF row order, so everything
+//     around it is the same as for rocBLAS.
 
 #include <dlfcn.h>
 
@@ -51,10 +55,10 @@ struct Blas {
 };
 Blas g_blas;
 
-bool blas_ready() {
+// the library and its five entry points (no device work: a handle is created by blas_ready)
+bool blas_open() {
   Blas& b = g_blas;
-  if (b.tried) return b.ok;
-  b.tried = true;
+  if (b.lib) return b.create && b.destroy && b.set_stream && b.gemm_ex;
   for (const char* name : {"librocblas.so.5", "librocblas.so", "/opt/rocm/lib/librocblas.so"}) {
     b.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
     if (b.lib) break;
@@ -64,7 +68,14 @@ bool blas_ready() {
   b.destroy = reinterpret_cast<rb_destroy_t>(dlsym(b.lib, "rocblas_destroy_handle"));
   b.set_stream = reinterpret_cast<rb_set_stream_t>(dlsym(b.lib, "rocblas_set_stream"));
   b.gemm_ex = reinterpret_cast<rb_gemm_ex_t>(dlsym(b.lib, "rocblas_gemm_ex"));
-  if (!b.create || !b.destroy || !b.set_stream || !b.gemm_ex) return false;
+  return b.create && b.destroy && b.set_stream && b.gemm_ex;
+}
+
+bool blas_ready() {
+  Blas& b = g_blas;
+  if (b.tried) return b.ok;
+  b.tried = true;
+  if (!blas_open()) return false;
   if (b.create(&b.h) != 0 || !b.h) return false;
   b.ok = true;
   return true;
@@ -136,6 +147,7 @@ int launch_epilogue_rows(GemvArgs a, const float* Y, int T, int out_elem_stride,
 }  // namespace
 
 bool prefill_gemm_available() { return blas_ready(); }
+bool prefill_gemm_library_present() { return blas_open(); }
 
 size_t prefill_gemm_workspace_bytes(const sd_model_config& c) {
   const size_t T = kPrefillChunk;
@@ -180,8 +192,21 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     e.x = x + static_cast<size_t>(s0) * d;
     if (int rc = launch_embed(e, st)) return rc;
   }
-  const size_t layer_kv = static_cast<size_t>(m.B) * Hkv * m.Lmax * D;
-  const size_t row_kv = static_cast<size_t>(cache_row) * Hkv * m.Lmax * D;
+  // dense: row cache_row of each layer's cache; paged: the layer's page pool, the row's pages through its block-table row
+  const bool paged = m.block_table != nullptr;
+  const size_t layer_kv = paged ? (static_cast<size_t>(m.n_pages) * Hkv * D << m.page_shift) : static_cast<size_t>(m.B) * Hkv * m.Lmax * D;
+  const size_t row_kv = paged ? 0 : static_cast<size_t>(cache_row) * Hkv * m.Lmax * D;
+  const int32_t* bt = paged ? m.block_table + static_cast<size_t>(cache_row) * m.max_pages : nullptr;
+  const bool native = m.gemm == PREFILL_GEMM_NATIVE;
+  SD_REQUIRE(!native || (m.packed && m.plan), "prefill: the native backend needs the packed weights");
+  SD_REQUIRE(native || !paged, "prefill: the rocBLAS backend serves dense KV only");
+  // one matrix product: Y[Mc][N] = X[Mc][K] x W^T (which: 0 qkv, 1 out, 2 gate / up, 3 down of layer l)
+  auto product = [&](int l, int which, const void* w_rows, const uint16_t* X, int N, int K, int ldx) -> int {
+    if (!native) return gemm_rows(w_rows, X, Y, Mc, N, K, ldx, st);
+    const int index = 4 * l + which;
+    const float* sc = m.scales ? m.scales[index] : nullptr;
+    return launch_prefill_mfma(*m.plan, which, m.packed[index], sc, sc != nullptr, X, ldx, Y, Mc, st);
+  };
   for (int l = 0; l < c.n_layers; ++l) {
     const sd_layer_weights& w = c.layers[l];
     uint16_t* kc = m.k_cache + l * layer_kv + row_kv;
@@ -197,12 +222,14 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     g.max_pos = c.max_pos;
     g.l_max = m.Lmax;
     g.out_dtype = SD_BF16;
+    g.block_table = bt;
+    g.page_shift = m.page_shift;
 
     // 1. norm, QKV product, RoPE + q store + in-place K / V^T append
     hipLaunchKernelGGL(rms_rows_kernel, dim3(Mc), dim3(256), 0, st, x, d, static_cast<const uint16_t*>(w.attn_norm_w), c.norm_eps, d, xn);
     SD_LAUNCH_CHECK();
     const int Nqkv = (Hq + 2 * Hkv) * D;
-    if (int rc = gemm_rows(w.wqkv, xn, Y, Mc, Nqkv, d, d, st)) return rc;
+    if (int rc = product(l, 0, w.wqkv, xn, Nqkv, d, d)) return rc;
     GemvArgs a1 = g;
     a1.N = Nqkv;
     a1.K = d;
@@ -235,11 +262,13 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
       at.split_ws = m.attn_ws;
       at.split_cnt = m.attn_cnt;
       at.split_slots = kAttnSplitSlots;
+      at.block_table = bt;
+      at.page_shift = m.page_shift;
       if (int rc = launch_attention(at, st)) return rc;
     }
 
     // 3. output projection + residual
-    if (int rc = gemm_rows(w.wo, attn, Y, Mc, d, HqD, HqD, st)) return rc;
+    if (int rc = product(l, 1, w.wo, attn, d, HqD, HqD)) return rc;
     GemvArgs a3 = g;
     a3.N = d;
     a3.K = HqD;
@@ -252,7 +281,7 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     // 4. norm, gate / up product, SwiGLU
     hipLaunchKernelGGL(rms_rows_kernel, dim3(Mc), dim3(256), 0, st, x, d, static_cast<const uint16_t*>(w.mlp_norm_w), c.norm_eps, d, xn);
     SD_LAUNCH_CHECK();
-    if (int rc = gemm_rows(w.w_up, xn, Y, Mc, 2 * ff, d, d, st)) return rc;
+    if (int rc = product(l, 2, w.w_up, xn, 2 * ff, d, d)) return rc;
     GemvArgs a4 = g;
     a4.N = 2 * ff;
     a4.K = d;
@@ -263,7 +292,7 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     if (int rc = launch_epilogue_rows<EPI_SWIGLU>(a4, Y, Mc, ff * 2, st)) return rc;
 
     // 5. down projection + residual
-    if (int rc = gemm_rows(w.w_down, act, Y, Mc, d, ff, ff, st)) return rc;
+    if (int rc = product(l, 3, w.w_down, act, d, ff, ff)) return rc;
     GemvArgs a5 = g;
     a5.N = d;
     a5.K = ff;

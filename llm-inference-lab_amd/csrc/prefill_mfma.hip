@@ -1,0 +1,331 @@
+// Prompt-prefill GEMM over the packed tile streams (the native backend of csrc/prefill_gemm.hip).
+//
+// Y[T][N] (fp32, row-major, true HF row order) = X[T][K] (bf16, rows ldx apart) x W^T, where W is ONE matrix's packed stream as
+// pack_one_matrix left it (csrc/pack.hip): bf16, or OCP fp8 e4m3 with fp32 row scales. These are the bytes the decode kernels
+// stream, so the prefill of an fp8 model multiplies the same dequantised values as its decode steps (the e4m3 values are widened
+// to bf16, which is exact, and row r's fp32 accumulator is multiplied by scale[r] before the store, as gemm_pipe.hip does).
+//
+// The stream is a sequence of tiles of 2 * np rows (np <= 8 pairs, irregular: the decode kernels' work split, gemv_geometry).
+// Each tile holds its whole K range contiguously, step after step: bf16 [32-k step][g = 0..3][row][16 B]; fp8 [64-k double
+// step][g][row][16 B] with a lane's 16 bytes holding its fragments of two consecutive 32-k steps. So one 64-k stage of a tile is
+// ONE contiguous piece of 2 * np * SB bytes (SB = 128 bf16, 64 fp8), and consecutive tiles' pieces concatenated are the
+// stage's weight rows in packed order.
+//
+// Decomposition: a workgroup (4 waves, 2 x 2) owns RB = 64 or 128 consecutive packed rows (whole tiles: a host table per
+// matrix shape, NativeMat) and 128 tokens. Per 64-k stage it copies the x tile (128 rows x 128 B, full lines, XOR-swizzled
+// 16-byte slots) and the weight pieces of its tiles into LDS with LDS-DMA (global_load_lds_dwordx4), two buffers deep, and
+// each wave runs 16 x 16 x 32 bf16 MFMAs over its 64 tokens x RB / 2 rows: A = x rows (tokens on the fragment's rows), B = W
+// rows (weight rows on the lanes), so each lane's results are 4 tokens of ONE weight row and the store maps that packed row to
+// its HF row once. No split-K: the host picks RB = 64 when 128-row blocks would leave most CUs idle.
+
+#include "gemv_device.h"
+#include "prefill_gemm.h"
+
+namespace sd {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kBT = 128;              // tokens per workgroup
+constexpr int kXBytes = kBT * 128;    // x stage: 128 tokens x 64 k (bf16)
+
+struct MfmaArgs {
+  const char* W;            // packed stream of the matrix
+  const float* w_scale;     // fp8: fp32 scale per HF row
+  const char* X;            // bf16 [T][ldx]
+  float* Y;                 // fp32 [T][N]
+  const int4* tiles;        // {first row in its block, pairs, first pair, 0}
+  const int2* blocks;       // {first tile, tiles}
+  int T, N, K, ldx;
+  int n_blocks, n_tb;       // row blocks, token blocks
+  int row_bytes;            // bytes of one packed row of the stream (K padded to 32 / 64)
+  int epi, head_dim, n_pairs;
+};
+
+__device__ __forceinline__ void glds16(const char* src, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16,
+                                   0, 0);
+}
+
+// HF row of packed row j (0 .. 2 np - 1) of the tile whose first pair is p0 (the rule of pack_pair_rows)
+__device__ __forceinline__ int hf_row(const MfmaArgs& a, int p0, int np, int j) {
+  const int second = j >= np ? 1 : 0;
+  const int p = p0 + j - second * np;
+  int r0, r1;
+  if (a.epi == EPI_QKV_ROPE) {
+    const int half = a.head_dim >> 1;
+    const int h = p / half, i = p - h * half;
+    r0 = h * a.head_dim + i;
+    r1 = r0 + half;
+  } else if (a.epi == EPI_SWIGLU) {
+    r0 = p;
+    r1 = p + a.n_pairs;
+  } else {
+    r0 = 2 * p;
+    r1 = 2 * p + 1;
+  }
+  return second ? r1 : r0;
+}
+
+template <int RF, bool W8>
+__global__ __launch_bounds__(kThreads, 2) void prefill_mfma_kernel(MfmaArgs a) {
+  constexpr int SB = W8 ? 64 : 128;              // bytes of one packed row per 64-k stage
+  constexpr int RB = 2 * RF * 16;                // weight rows per workgroup
+  constexpr int kWBytes = RB * SB;
+  constexpr int kBuf = kXBytes + kWBytes;
+  constexpr int XCH = kXBytes / 16 / kThreads;   // 16-byte x pieces per thread per stage
+  constexpr int WCH = kWBytes / 16 / kThreads;   // 16-byte weight pieces per thread per stage
+  static_assert(WCH >= 1 && XCH == 4, "stage geometry");
+  __shared__ __attribute__((aligned(16))) char smem[2 * kBuf];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int wt = wave & 1, wr = wave >> 1;       // token half, row half of the workgroup tile
+
+  // workgroup -> (row block, token block): the token blocks of one row block are consecutive on one XCD (dispatch is
+  // round-robin over the 8 XCDs), so a weight piece is fetched from HBM once and shared through that XCD's L2
+  const int G = a.n_blocks * a.n_tb;
+  int L = blockIdx.x;
+  if ((G & 7) == 0) L = (L & 7) * (G >> 3) + (L >> 3);
+  const int rb = L / a.n_tb, tb = L - rb * a.n_tb;
+  const int2 blk = a.blocks[rb];
+  const int t0 = tb * kBT;
+
+  // per lane: B-fragment offsets in the weight image and the HF row of each fragment column; sources of the weight pieces
+  int woff[RF], wstep[RF], hrow[RF];
+#pragma unroll
+  for (int f = 0; f < RF; ++f) { woff[f] = 0; wstep[f] = 0; hrow[f] = -1; }
+  uint32_t dsrc[WCH], dstr[WCH];
+  bool dval[WCH];
+#pragma unroll
+  for (int c = 0; c < WCH; ++c) { dsrc[c] = 0; dstr[c] = 0; dval[c] = false; }
+  for (int k = 0; k < blk.y; ++k) {
+    const int4 tl = a.tiles[blk.x + k];
+    const int rs = tl.x, np = tl.y, p0 = tl.z, nr = 2 * tl.y;
+#pragma unroll
+    for (int f = 0; f < RF; ++f) {
+      const int R = wr * RF * 16 + f * 16 + n;
+      if (R >= rs && R < rs + nr) {
+        const int j = R - rs;
+        woff[f] = rs * SB + (g * nr + j) * 16;
+        wstep[f] = nr * 64;
+        const int r = hf_row(a, p0, np, j);
+        hrow[f] = r < a.N ? r : -1;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < WCH; ++c) {
+      const int byte = ((c * 4 + wave) * 64 + lane) * 16;
+      const int row = byte / SB;
+      if (row >= rs && row < rs + nr) {
+        dsrc[c] = static_cast<uint32_t>(p0) * 2u * static_cast<uint32_t>(a.row_bytes) + static_cast<uint32_t>(byte - rs * SB);
+        dstr[c] = static_cast<uint32_t>(nr * SB);
+        dval[c] = true;
+      }
+    }
+  }
+  // x pieces: token row tr, 16-byte slot sl of the LDS image holds k-chunk sl ^ (tr & 7) (rows past T repeat row T - 1)
+  uint32_t xsrc[XCH];
+#pragma unroll
+  for (int c = 0; c < XCH; ++c) {
+    const int idx = (c * 4 + wave) * 64 + lane;
+    const int tr = idx >> 3, sl = idx & 7;
+    const int t = min(t0 + tr, a.T - 1);
+    xsrc[c] = static_cast<uint32_t>(t) * static_cast<uint32_t>(a.ldx) * 2u + static_cast<uint32_t>((sl ^ (tr & 7)) * 16);
+  }
+  const int xrow = (wt * 64 + n) * 128;
+  const int xo0 = (g ^ (n & 7)) * 16, xo1 = ((4 + g) ^ (n & 7)) * 16;
+
+  auto issue = [&](int s, int b) {
+    char* xb = smem + b * kBuf;
+    char* wb = xb + kXBytes;
+#pragma unroll
+    for (int c = 0; c < XCH; ++c) glds16(a.X + xsrc[c] + static_cast<uint32_t>(s) * 128u, xb + (c * 4 + wave) * 1024);
+#pragma unroll
+    for (int c = 0; c < WCH; ++c)
+      if (dval[c]) glds16(a.W + dsrc[c] + static_cast<uint32_t>(s) * dstr[c], wb + (c * 4 + wave) * 1024);
+  };
+
+  f32x4_t acc[4][RF];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int f = 0; f < RF; ++f) acc[q][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int S = a.K >> 6;
+  issue(0, 0);
+  for (int s = 0; s < S; ++s) {
+    __syncthreads();                       // stage s has landed (the wait for the DMA precedes the barrier); buffer s+1 is free
+    if (s + 1 < S) issue(s + 1, (s + 1) & 1);
+    const char* xb = smem + (s & 1) * kBuf;
+    const char* wb = xb + kXBytes;
+    u32x4 wf[2][RF];
+#pragma unroll
+    for (int f = 0; f < RF; ++f) {
+      if constexpr (W8) {
+        const u32x4 raw = *reinterpret_cast<const u32x4*>(wb + woff[f]);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          wf[0][f][2 * e] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[e], 1.0f, false));
+          wf[0][f][2 * e + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[e], 1.0f, true));
+          wf[1][f][2 * e] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[2 + e], 1.0f, false));
+          wf[1][f][2 * e + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[2 + e], 1.0f, true));
+        }
+      } else {
+        wf[0][f] = *reinterpret_cast<const u32x4*>(wb + woff[f]);
+        wf[1][f] = *reinterpret_cast<const u32x4*>(wb + woff[f] + wstep[f]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const u32x4 xa = *reinterpret_cast<const u32x4*>(xb + xrow + q * 16 * 128 + (u ? xo1 : xo0));
+#pragma unroll
+        for (int f = 0; f < RF; ++f)
+          acc[q][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, xa), __builtin_bit_cast(bf16x8_t, wf[u][f]),
+                                                              acc[q][f], 0, 0, 0);
+      }
+    }
+  }
+
+  // lane (n, g) holds tokens 4 g + e of its fragment row q, for weight row (fragment column) n of fragment f
+#pragma unroll
+  for (int f = 0; f < RF; ++f) {
+    const int r = hrow[f];
+    if (r < 0) continue;
+    const float sc = W8 ? a.w_scale[r] : 1.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int t = t0 + wt * 64 + q * 16 + 4 * g + e;
+        if (t < a.T) a.Y[static_cast<size_t>(t) * a.N + r] = acc[q][f][e] * sc;
+      }
+  }
+}
+
+// the four matrix shapes of a layer, in packing order (model_matrices, csrc/pack.hip)
+void layer_shapes(const sd_model_config& c, int shp[4][4]) {
+  const int d = c.d_model, HqD = c.n_heads * c.head_dim, Nqkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
+  const int v[4][4] = {{Nqkv, d, Nqkv / 2, EPI_QKV_ROPE}, {d, HqD, d / 2, EPI_RESID}, {2 * c.d_ff, d, c.d_ff, EPI_SWIGLU}, {d, c.d_ff, d / 2, EPI_RESID}};
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) shp[i][j] = v[i][j];
+}
+
+}  // namespace
+
+bool prefill_native_shapes_ok(const sd_model_config& c) {
+  return c.arch == SD_ARCH_LLAMA && c.d_model % 64 == 0 && (c.n_heads * c.head_dim) % 64 == 0 && c.d_ff % 64 == 0;
+}
+
+// Tiles of each matrix shape in stream order (the loop of pack_kernel: per workgroup share of ppw pairs, tiles of tile_pairs),
+// grouped into row blocks of whole tiles of <= 128 (and, separately, <= 64) rows.
+int native_plan_build(const sd_model_config& c, NativePlan& plan) {
+  SD_REQUIRE(prefill_native_shapes_ok(c), "prefill: the native backend needs a Llama model with d_model, Hq*D and d_ff multiples of 64");
+  int shp[4][4];
+  layer_shapes(c, shp);
+  std::vector<int4> tiles;
+  std::vector<int2> blocks;
+  struct Span { size_t tiles, blocks; int n_blocks; };
+  Span spans[4][2];
+  for (int i = 0; i < 4; ++i) {
+    const int n_pairs = shp[i][2], K = shp[i][1];
+    const GemvGeom q = gemv_geometry(n_pairs, K);
+    std::vector<int2> raw;   // {first pair, pairs}
+    for (int p_lo = 0; p_lo < n_pairs; p_lo += q.ppw) {
+      const int p_hi = std::min(p_lo + q.ppw, n_pairs);
+      for (int p0 = p_lo; p0 < p_hi; p0 += q.tile_pairs) raw.push_back(make_int2(p0, std::min(q.tile_pairs, p_hi - p0)));
+    }
+    for (int v = 0; v < 2; ++v) {
+      const int rb = v == 0 ? 128 : 64;
+      spans[i][v].tiles = tiles.size();
+      spans[i][v].blocks = blocks.size();
+      int first = 0, rows = 0;
+      for (size_t k = 0; k < raw.size(); ++k) {
+        const int nr = 2 * raw[k].y;
+        SD_REQUIRE(nr <= rb, "prefill: tile of %d rows", nr);
+        if (rows + nr > rb) {
+          blocks.push_back(make_int2(first, static_cast<int>(k) - first));
+          first = static_cast<int>(k);
+          rows = 0;
+        }
+        tiles.push_back(make_int4(rows, raw[k].y, raw[k].x, 0));
+        rows += nr;
+      }
+      blocks.push_back(make_int2(first, static_cast<int>(raw.size()) - first));
+      spans[i][v].n_blocks = static_cast<int>(blocks.size() - spans[i][v].blocks);
+    }
+    // block tile indices are relative to the span's first tile; made absolute below
+    for (int v = 0; v < 2; ++v)
+      for (int b = 0; b < spans[i][v].n_blocks; ++b) blocks[spans[i][v].blocks + b].x += static_cast<int>(spans[i][v].tiles);
+  }
+  const size_t tb = tiles.size() * sizeof(int4), bb = blocks.size() * sizeof(int2);
+  native_plan_free(plan);
+  SD_HIP_CHECK(hipMalloc(&plan.buf, tb + bb));
+  SD_HIP_CHECK(hipMemcpy(plan.buf, tiles.data(), tb, hipMemcpyHostToDevice));
+  SD_HIP_CHECK(hipMemcpy(static_cast<char*>(plan.buf) + tb, blocks.data(), bb, hipMemcpyHostToDevice));
+  const int4* dt = static_cast<const int4*>(plan.buf);
+  const int2* db = reinterpret_cast<const int2*>(static_cast<char*>(plan.buf) + tb);
+  for (int i = 0; i < 4; ++i)
+    for (int v = 0; v < 2; ++v) {
+      NativeMat& m = plan.mat[i][v];
+      m.tiles = dt;
+      m.blocks = db + spans[i][v].blocks;
+      m.n_blocks = spans[i][v].n_blocks;
+      m.rb = v == 0 ? 128 : 64;
+      m.N = shp[i][0];
+      m.K = shp[i][1];
+      m.n_pairs = shp[i][2];
+      m.epi = shp[i][3];
+    }
+  plan.head_dim = c.head_dim;
+  return 0;
+}
+
+void native_plan_free(NativePlan& plan) {
+  if (plan.buf) (void)hipFree(plan.buf);
+  plan = NativePlan{};
+}
+
+// which = 0 qkv, 1 out, 2 gate / up, 3 down
+int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const float* w_scale, bool w8, const uint16_t* X, int ldx, float* Y,
+                        int T, hipStream_t st) {
+  SD_REQUIRE(plan.buf && which >= 0 && which < 4, "prefill: native plan not built");
+  SD_REQUIRE(T >= 1 && T <= kPrefillChunk, "prefill: native GEMM of %d rows", T);
+  SD_REQUIRE(W && X && Y && (!w8 || w_scale), "prefill: native GEMM with a NULL operand");
+  const int n_tb = (T + kBT - 1) / kBT;
+  // 128-row blocks unless they would fill fewer than the CUs (one workgroup per CU, two resident)
+  const int v = plan.mat[which][0].n_blocks * n_tb >= 256 ? 0 : 1;
+  const NativeMat& m = plan.mat[which][v];
+  MfmaArgs a{};
+  a.W = static_cast<const char*>(W);
+  a.w_scale = w_scale;
+  a.X = reinterpret_cast<const char*>(X);
+  a.Y = Y;
+  a.tiles = m.tiles;
+  a.blocks = m.blocks;
+  a.T = T;
+  a.N = m.N;
+  a.K = m.K;
+  a.ldx = ldx;
+  a.n_blocks = m.n_blocks;
+  a.n_tb = n_tb;
+  a.row_bytes = w8 ? ((m.K + 63) & ~63) : ((m.K + 31) & ~31) * 2;
+  a.epi = m.epi;
+  a.head_dim = plan.head_dim;
+  a.n_pairs = m.n_pairs;
+  const dim3 grid(m.n_blocks * n_tb), block(kThreads);
+  if (w8) {
+    if (v == 0) hipLaunchKernelGGL((prefill_mfma_kernel<4, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((prefill_mfma_kernel<2, true>), grid, block, 0, st, a);
+  } else {
+    if (v == 0) hipLaunchKernelGGL((prefill_mfma_kernel<4, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((prefill_mfma_kernel<2, false>), grid, block, 0, st, a);
+  }
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace sd

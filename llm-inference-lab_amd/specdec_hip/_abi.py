@@ -24,6 +24,9 @@ LIB_PATH = PKG_DIR / "lib" / "libspecdec_hip.so"
 # enum sd_dtype (include/specdec_hip.h)
 SD_F32, SD_F16, SD_BF16, SD_I32, SD_I64, SD_U8, SD_FP8_E4M3 = range(7)
 SD_ABI_VERSION = 1
+# enum sd_prefill_backend
+SD_PREFILL_AUTO, SD_PREFILL_PASSES, SD_PREFILL_ROCBLAS, SD_PREFILL_NATIVE = range(4)
+PREFILL_BACKENDS = {"auto": SD_PREFILL_AUTO, "passes": SD_PREFILL_PASSES, "rocblas": SD_PREFILL_ROCBLAS, "native": SD_PREFILL_NATIVE}
 
 _c_void_p = ctypes.c_void_p
 _c_int = ctypes.c_int
@@ -88,6 +91,10 @@ SIGNATURES = {
     "sd_model_set_persist_tokens": (_c_int, [_c_void_p, _c_int]),
     "sd_model_set_length_hint": (_c_int, [_c_void_p, _c_int]),
     "sd_model_persist_active": (_c_int, [_c_void_p, _c_int]),
+    "sd_prefill_backend_available": (_c_int, [_c_int]),
+    "sd_model_set_prefill_backend": (_c_int, [_c_void_p, _c_int]),
+    "sd_model_prefill_backend": (_c_int, [_c_void_p]),
+    "sd_model_prefill_count": (_c_i64, [_c_void_p, _c_int]),
     "sd_model_debug_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "sd_model_probe_forward": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_double), _c_void_p, _c_size]),

@@ -58,17 +58,37 @@ class EngineGaveUp(_abi.HipLibraryError):
         self.status = status
 
 
+_PREFILL_NAMES = {v: k for k, v in _abi.PREFILL_BACKENDS.items()}
+
+
+def _prefill_backend_id(name: str) -> int:
+    """enum sd_prefill_backend of a backend name; raises before any device work"""
+    if name not in _abi.PREFILL_BACKENDS:
+        raise ValueError(f"prefill_backend={name!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
+    return _abi.PREFILL_BACKENDS[name]
+
+
+def prefill_backends_available() -> List[str]:
+    """names of the prefill backends this process can use"""
+    lib = _abi.load()
+    return [name for name, v in _abi.PREFILL_BACKENDS.items() if lib.sd_prefill_backend_available(v)]
+
+
 class HipModel:
     """A decoder (Llama or GPT-2 shaped) bound to its KV cache on one GPU."""
 
     def __init__(self, weights: ModelWeights, batch: int, l_max: int, device: Optional[torch.device] = None,
-                 weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None):
+                 weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None,
+                 prefill_backend: str = "auto"):
         """weight_dtype "fp8": the engine streams an OCP e4m3 copy of the Linear weights (per-output-row
         scales, quantised on the device at load); activations and the KV cache stay bf16.
         page_len (a power of two >= 32): paged KV — the rows share a pool of `n_pages` pages (default: enough for every
-        row to reach l_max) through a block table; `reserve(row, length)` / `release(row)` manage a row's pages."""
+        row to reach l_max) through a block table; `reserve(row, length)` / `release(row)` manage a row's pages.
+        prefill_backend: how prompts (>= 96 positions per row) are absorbed — "auto" (rocBLAS where it serves the model, else
+        the passes), "passes", "rocblas" or "native" (this library's GEMM over the packed weights); see set_prefill_backend."""
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype={weight_dtype!r} (bf16 or fp8)")
+        _prefill_backend_id(prefill_backend)
         self.weight_dtype = weight_dtype
         self.lib = _abi.load()
         self.cfg: ModelConfig = weights.config
@@ -122,7 +142,13 @@ class HipModel:
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):
             self._bind_paged(int(page_len or os.environ["SPECDEC_PAGED_KV"]), n_pages)
-            return
+        else:
+            self._bind_dense()
+        if prefill_backend != "auto":
+            self.set_prefill_backend(prefill_backend)
+
+    def _bind_dense(self) -> None:
+        dev = self.device
         kv_bytes = self.lib.sd_model_kv_bytes(self.handle, self.batch, self.l_max)
         with torch.cuda.device(dev):
             # [n_layers][B][Hkv][Lmax][D] bf16 — sized for 288 GB of HBM: no paging, no realign copies
@@ -253,6 +279,21 @@ class HipModel:
     def persist_active(self, tokens: int = 1) -> bool:
         """Would a pass of `tokens` tokens of one row run as the persistent launch right now (token limit, length hint, paging)?"""
         return bool(self.lib.sd_model_persist_active(self.handle, int(tokens)))
+
+    # ---- prompt prefill -------------------------------------------------------------------------------------------
+    def set_prefill_backend(self, name: str) -> None:
+        """"auto", "passes", "rocblas" or "native". Raises (ValueError) for an unknown name and (RuntimeError, with the
+        library's reason) for a backend that cannot serve this model: rocBLAS missing, or asked for fp8 / paged / GPT-2;
+        native asked for GPT-2 or a model without packed weights. A choice is never replaced by another GEMM."""
+        _abi.check(self.lib.sd_model_set_prefill_backend(self.handle, _prefill_backend_id(name)), "sd_model_set_prefill_backend")
+
+    @property
+    def prefill_backend(self) -> str:
+        return _PREFILL_NAMES[self.lib.sd_model_prefill_backend(self.handle)]
+
+    def prefill_counts(self) -> dict:
+        """Prompt rows absorbed per backend since the bind (one per row of a forward of >= 96 positions per row)."""
+        return {name: int(self.lib.sd_model_prefill_count(self.handle, _abi.PREFILL_BACKENDS[name])) for name in ("passes", "rocblas", "native")}
 
     def set_persist_tokens(self, max_tokens: int) -> None:
         """Tokens per pass the persistent launch takes from now on (0: launch path only; sd_model_set_persist_tokens). Loops that

@@ -103,6 +103,12 @@ def _backend_of(fn_name: str) -> str:
     return fn_name
 
 
+def _prefill_backends():
+    from specdec_hip.engine import prefill_backends_available
+
+    return prefill_backends_available()
+
+
 def get_kernel_info():
     """Backend names per op. Keys as the reference (kernels/__init__.py:116-156);
     the HIP ops report "hip" (the reference's own allowed set has no such name)."""
@@ -121,6 +127,7 @@ def get_kernel_info():
         "device": device,
         "library": str(_abi.lib_path()),
         "library_loaded": lib_ok,
+        "prefill_backends": _prefill_backends() if lib_ok else [],
     }
 
 

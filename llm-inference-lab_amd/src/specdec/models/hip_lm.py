@@ -18,6 +18,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
+from specdec_hip import _abi
 from specdec_hip import weights as W
 from specdec_hip.engine import EngineGaveUp, HipModel
 
@@ -80,7 +81,9 @@ def _draw(last: torch.Tensor, temperature: float, kwargs) -> torch.Tensor:
 class HipLM(LanguageModel):
     def __init__(self, weights: W.ModelWeights, tokenizer: Any = None, name: Optional[str] = None,
                  max_len: int = 1024, batch: int = 1, device: str = "cuda", weight_dtype: str = "bf16",
-                 kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None):
+                 kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto"):
+        if prefill_backend not in _abi.PREFILL_BACKENDS:
+            raise ValueError(f"prefill_backend={prefill_backend!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
         if not torch.cuda.is_available():
             raise RuntimeError("HipLM needs a GPU: this build has no CPU compute path")
         self._device = torch.device(device if device != "auto" else "cuda")
@@ -95,6 +98,8 @@ class HipLM(LanguageModel):
         # paged KV (sd_model_bind_paged): engines share a pool of kv_pages pages of kv_page_len positions instead of
         # owning l_max positions per row (kv_pages None: enough for every row to reach l_max)
         self.kv_page_len, self.kv_pages = kv_page_len, kv_pages
+        # how the engines absorb prompts (HipModel.set_prefill_backend): "auto", "passes", "rocblas" or "native"
+        self.prefill_backend = prefill_backend
         self._model: Optional[HipModel] = None
         self._cached: List[List[int]] = []
         self._last_generated_kv: Optional[KVCache] = None
@@ -103,7 +108,7 @@ class HipLM(LanguageModel):
     def new_engine(self, batch: int, l_max: int) -> HipModel:
         """A forward instance with its own KV cache over the shared weights."""
         return HipModel(self.weights, batch=batch, l_max=l_max, device=self._device, weight_dtype=self.weight_dtype,
-                        page_len=self.kv_page_len, n_pages=self.kv_pages)
+                        page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend)
 
     def _engine(self, batch: int, need_len: int) -> HipModel:
         m = self._model

@@ -43,6 +43,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--target-acceptance", type=float)
     ap.add_argument("--per-row-K", action="store_true",
                     help="adaptive controller: every batch row its own K, moved on the device inside the captured step (not in the reference)")
+    ap.add_argument("--prefill-backend", type=str, choices=["auto", "passes", "rocblas", "native"], default="auto",
+                    help="how prompts are absorbed into the KV cache: auto (rocBLAS where it serves the model, else the 128-token passes), "
+                         "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
     return ap.parse_args(argv)
 
 
@@ -69,6 +72,9 @@ def main(argv=None) -> int:
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,
                                    policy=args.policy, controller=controller, controller_params=cp, draft_mode=args.draft_mode,
                                    policy_params={k: v for k, v in (("tau", args.policy_tau), ("k", args.policy_k), ("p", args.policy_p)) if v is not None})
+        for lm in (pipe.base_lm, pipe.draft_lm):
+            if lm is not None and hasattr(lm, "prefill_backend"):
+                lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
     except Exception as e:  # the reference CLI reports and exits 1 (run_specdec.py:276-278)
         logging.error("Error: %s", e)
