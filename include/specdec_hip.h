@@ -362,8 +362,9 @@ int64_t sd_model_prefill_count(const sd_model* m, int backend);
 
 /* Rows [row0, row0+n) of one of the workspace buffers the last pass left behind (bf16, asynchronous copy on `stream`):
  * which = 0 residual stream [d_model] (= sd_model_hidden_rows), 1 q after RoPE [Hq*D], 2 attention rows [Hq*D],
- * 3 MLP activation [d_ff]; all of the LAST layer. For stage-by-stage checks of the persistent launch against the
- * launch-per-operator forward. (The draft model of an sd_specdec loop runs the persistent launch WITHOUT these stores unless
+ * 3 MLP activation [d_ff]; all of the LAST layer. After a prompt absorbed by a GEMM prefill backend (rocBLAS or native) the
+ * rows are those of the last chunk's last <= 128 positions, in position order: the same positions sd_model_hidden_rows returns.
+ * For stage-by-stage checks of every forward path against each other and against a plain reference. (The draft model of an sd_specdec loop runs the persistent launch WITHOUT these stores unless
  * SPECDEC_PERSIST_TAPS is set when the loop is created: its rows are then not updated by the loop's passes.) */
 int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void* out, void* stream);
 

@@ -455,18 +455,26 @@ static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, con
       for (int b0 = 0; b0 < B; ++b0) {
         for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
           const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
-          uint16_t* xr = nullptr;
+          PrefillRows rows;
           if (int rc = prefill_gemm_chunk(pm, tokens + static_cast<size_t>(b0) * tok_stride + m0, pos_base + b0, pos_off + m0, row0 + b0, mc,
-                                          m->prefill_ws, &xr, st))
+                                          m->prefill_ws, &rows, st))
             return rc;
-          // the residual rows of the chunk's last <= 128 positions go where every other pass leaves them (hidden rows, the head)
+          const uint16_t* xr = rows.x;
+          // the chunk's last <= 128 positions go where every other pass leaves them: the residual rows (hidden rows, the head) and
+          // the last layer's q, attention and activation rows (sd_model_debug_rows)
           const int keep = mc < 128 ? mc : 128;
-          SD_HIP_CHECK(hipMemcpyAsync(m->x, xr + static_cast<size_t>(mc - keep) * m->cfg.d_model, static_cast<size_t>(keep) * m->cfg.d_model * 2,
-                                      hipMemcpyDeviceToDevice, st));
+          const size_t HqD = static_cast<size_t>(m->cfg.n_heads) * m->cfg.head_dim;
+          const struct { uint16_t* dst; const uint16_t* src; size_t w; } taps[4] = {
+              {m->x, rows.x, static_cast<size_t>(m->cfg.d_model)}, {m->q, rows.q, HqD}, {m->attn, rows.attn, HqD},
+              {m->act, rows.act, static_cast<size_t>(m->cfg.d_ff)}};
+          for (const auto& tp : taps)
+            SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
+                                        hipMemcpyDeviceToDevice, st));
           if (!skip_head && ids_out) {
-            // ids of the prompt positions: the lm_head over the chunk's rows in groups of <= 128 (the decode-shaped head kernel)
-            for (int s0 = 0; s0 < mc; s0 += 128) {
-              const int n = (mc - s0 < 128) ? mc - s0 : 128;
+            // ids of the prompt positions: the lm_head over the chunk's rows in groups of at most the model's pass size (the
+            // decode-shaped head kernel covers no more: 64 rows for some fp8 heads)
+            for (int s0 = 0; s0 < mc; s0 += m->max_t) {
+              const int n = (mc - s0 < m->max_t) ? mc - s0 : m->max_t;
               if (int rc = head_pass(m, xr + static_cast<size_t>(s0) * m->cfg.d_model, n, ids_out + static_cast<size_t>(b0) * ids_stride + m0 + s0, st)) return rc;
             }
           }

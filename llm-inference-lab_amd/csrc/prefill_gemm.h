@@ -52,7 +52,15 @@ struct PrefillModel {
 bool prefill_gemm_available();                               // rocBLAS could be opened (dlopen at first use) and a handle created
 bool prefill_gemm_library_present();                         // rocBLAS could be opened (dlopen only: no device work)
 size_t prefill_gemm_workspace_bytes(const sd_model_config& c);
+// the chunk's rows of the last layer, left in the prefill workspace: residual stream [Mc][d_model], q after RoPE and attention
+// rows [Mc][Hq*D], MLP activation [Mc][d_ff]
+struct PrefillRows {
+  uint16_t* x = nullptr;
+  uint16_t* q = nullptr;
+  uint16_t* attn = nullptr;
+  uint16_t* act = nullptr;
+};
 int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int cache_row, int Mc, void* ws,
-                       uint16_t** x_out, hipStream_t st);
+                       PrefillRows* rows_out, hipStream_t st);
 
 }  // namespace sd

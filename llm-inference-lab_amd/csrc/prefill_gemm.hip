@@ -159,9 +159,10 @@ size_t prefill_gemm_workspace_bytes(const sd_model_config& c) {
 }
 
 // One chunk of Mc <= kPrefillChunk positions of row `row` (absolute cache row), positions pos_base[row] + pos_off + [0, Mc).
-// ws: prefill_gemm_workspace_bytes(c) bytes. Leaves the residual rows in ws (x) — the caller takes the hidden rows / runs the head.
+// ws: prefill_gemm_workspace_bytes(c) bytes. Leaves the last layer's rows in ws (*rows_out: residual stream, q, attention,
+// activation) — the caller takes the hidden rows / stage rows and runs the head.
 int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int cache_row, int Mc, void* ws,
-                       uint16_t** x_out, hipStream_t st) {
+                       PrefillRows* rows_out, hipStream_t st) {
   const sd_model_config& c = *m.cfg;
   SD_REQUIRE(Mc >= 1 && Mc <= kPrefillChunk, "prefill: chunk of %d positions", Mc);
   const int d = c.d_model, Hq = c.n_heads, Hkv = c.n_kv_heads, D = c.head_dim, ff = c.d_ff, HqD = Hq * D;
@@ -302,7 +303,10 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     a5.out_stride = d;
     if (int rc = launch_epilogue_rows<EPI_RESID>(a5, Y, Mc, d * 2, st)) return rc;
   }
-  *x_out = x;
+  rows_out->x = x;
+  rows_out->q = q;
+  rows_out->attn = attn;
+  rows_out->act = act;
   return 0;
 }
 
