@@ -281,6 +281,19 @@ int sd_model_forward(sd_model* m, const int32_t* tokens, int tok_stride,
  * final_norm(row). */
 int sd_model_hidden_rows(sd_model* m, int row0, int n, void* out, void* stream);
 
+/* Log-likelihood of tokens[0..n) appended to cache row `row` at positions pos0..pos0+n-1 (after the row's first pos0
+ * cached positions). logprob[i] = log p(tokens[i+1] | ...) for i < n-1 (fp32, may be NULL); greedy[i] = argmax id after
+ * position i for i < n (may be NULL; greedy[n-1] is the next token a forward would return). Leaves the KV cache as
+ * sd_model_forward(skip_head=1) over the same tokens does. tokens, logprob and greedy are device memory.
+ * The layers take the route sd_model_forward takes for one row of n tokens (the prefill backend for n >= 96, chunks of <= 512
+ * positions; else the passes) and count in sd_model_prefill_count the same way; the head is the native GEMM over the packed
+ * lm_head (csrc/score_head.hip) with a log-softmax / argmax epilogue, so no [n][V] logits are written. Each logit is the value a
+ * bf16 lm_head returns (fp32 product, x row scale for fp8, rounded once to bf16). Outputs are bit-identical run to run.
+ * Refused (nonzero + sd_last_error, before any device work): NULL model or tokens, n < 2, a model without packed weights,
+ * d_model not a multiple of 64, an unbound model, row / positions out of range, a capturing stream. */
+int sd_model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0,
+                   float* logprob, int32_t* greedy, void* stream);
+
 /* Measurement hook for bench.py's roofline leg: launches ONE of the forward's weight-
  * streaming GEMVs (which: 1 = attention out-proj, 2 = norm+gate/up+SwiGLU, 3 = down-proj,
  * 4 = final norm+lm_head+argmax) `iters` times, round-robin over the layers so the weights

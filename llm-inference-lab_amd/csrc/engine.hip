@@ -69,6 +69,7 @@ struct sd_model {
   int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
   int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
   sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
+  void* score_ws = nullptr;                // sd_model_score: normed rows, head partials, target logits, a zero word (first call)
   unsigned* host_status = nullptr;         // pinned host word: a persistent launch that gives up stores its reason here as well
   int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
   int len_hint = 0;                        // caller's bound on the rows' current lengths (sd_model_set_length_hint; default Lmax)
@@ -76,6 +77,7 @@ struct sd_model {
   ~sd_model() {
     if (host_status) (void)hipHostFree(host_status);
     if (prefill_ws) (void)hipFree(prefill_ws);
+    if (score_ws) (void)hipFree(score_ws);
     sd::native_plan_free(native_plan);
   }
 };
@@ -508,6 +510,97 @@ static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, con
   return 0;
 }
 
+// ---- sd_model_score: the layers as the forward runs them, the head as a log-softmax reduction (csrc/score_head.hip)
+struct ScoreWs {
+  uint16_t* xn;      // [kPrefillChunk][d_model] normed rows
+  float4* part;      // score_partial_bytes
+  float* tgt;        // [kPrefillChunk] target logits
+  int32_t* zero;     // position base of the row (pos0 goes in pos_off)
+};
+
+static int score_ws(sd_model* m, ScoreWs& w) {
+  const size_t xb = align_up(static_cast<size_t>(kPrefillChunk) * m->cfg.d_model * 2, 256);
+  const size_t pb = align_up(score_partial_bytes(m->native_plan), 256);
+  const size_t tb = align_up(kPrefillChunk * sizeof(float), 256);
+  if (!m->score_ws) {
+    SD_HIP_CHECK(hipMalloc(&m->score_ws, xb + pb + tb + 256));
+    SD_HIP_CHECK(hipMemset(static_cast<char*>(m->score_ws) + xb + pb + tb, 0, 256));
+  }
+  char* p = static_cast<char*>(m->score_ws);
+  w.xn = reinterpret_cast<uint16_t*>(p);
+  w.part = reinterpret_cast<float4*>(p + xb);
+  w.tgt = reinterpret_cast<float*>(p + xb + pb);
+  w.zero = reinterpret_cast<int32_t*>(p + xb + pb + tb);
+  return 0;
+}
+
+// the head over rows [m0, m0 + mc) of the sequence, left by the layers at x (rows ldx apart)
+static int score_chunk(sd_model* m, const ScoreWs& w, const uint16_t* x, int ldx, int mc, const int32_t* tokens, int n, int m0, float* logprob,
+                       int32_t* greedy, hipStream_t st) {
+  const int n_target = (n - 1 - m0 < mc) ? n - 1 - m0 : mc;   // token m0 + t predicts tokens[m0 + t + 1]
+  if (int rc = launch_final_norm_rows(m->cfg, x, ldx, mc, w.xn, st)) return rc;
+  return launch_score_head(m->native_plan, m->packed[4 * m->cfg.n_layers], m->scale(4 * m->cfg.n_layers), m->w8(), w.xn, mc, tokens + m0 + 1,
+                           n_target, w.part, w.tgt, logprob ? logprob + m0 : nullptr, greedy ? greedy + m0 : nullptr, st);
+}
+
+static int model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, hipStream_t st) {
+  if (!m->native_plan.buf)
+    if (int rc = native_plan_build(m->cfg, m->native_plan)) return rc;
+  ScoreWs w{};
+  if (int rc = score_ws(m, w)) return rc;
+  // the route of model_forward for B = 1, M = n, no logits (the stream is not capturing: refused by the caller)
+  static const int prefill_min = getenv(debug_env::kPrefillMinTokens) ? atoi(getenv(debug_env::kPrefillMinTokens)) : kPrefillMinTokens;
+  if (n >= prefill_min) {
+    int backend = SD_PREFILL_PASSES;
+    const bool gemm_ok = m->cfg.arch == SD_ARCH_LLAMA && !m->skip_k;
+    if (m->prefill_backend == SD_PREFILL_AUTO) {
+      if (gemm_ok && !m->w8() && !m->block_table && m->cfg.weight_dtype == SD_BF16 && !getenv(debug_env::kNoGemmPrefill) && prefill_gemm_available())
+        backend = SD_PREFILL_ROCBLAS;
+    } else if (m->prefill_backend != SD_PREFILL_PASSES && gemm_ok) {
+      backend = m->prefill_backend;
+    }
+    m->prefill_count[backend] += 1;
+    if (backend != SD_PREFILL_PASSES) {
+      if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(m->cfg)));
+      PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
+      pm.block_table = m->block_table;
+      pm.page_shift = m->page_shift;
+      pm.max_pages = m->max_pages;
+      pm.n_pages = m->n_pages;
+      if (backend == SD_PREFILL_NATIVE) {
+        pm.gemm = PREFILL_GEMM_NATIVE;
+        pm.packed = m->packed.data();
+        pm.scales = m->w8() ? m->scales.data() : nullptr;
+        pm.plan = &m->native_plan;
+      }
+      for (int m0 = 0; m0 < n; m0 += kPrefillChunk) {
+        const int mc = (n - m0 < kPrefillChunk) ? n - m0 : kPrefillChunk;
+        PrefillRows rows;
+        if (int rc = prefill_gemm_chunk(pm, tokens + m0, w.zero, pos0 + m0, row, mc, m->prefill_ws, &rows, st)) return rc;
+        // the taps of model_forward: the chunk's last <= 128 positions (sd_model_hidden_rows / sd_model_debug_rows)
+        const int keep = mc < 128 ? mc : 128;
+        const size_t HqD = static_cast<size_t>(m->cfg.n_heads) * m->cfg.head_dim;
+        const struct { uint16_t* dst; const uint16_t* src; size_t w; } taps[4] = {
+            {m->x, rows.x, static_cast<size_t>(m->cfg.d_model)}, {m->q, rows.q, HqD}, {m->attn, rows.attn, HqD},
+            {m->act, rows.act, static_cast<size_t>(m->cfg.d_ff)}};
+        for (const auto& tp : taps)
+          SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
+                                      hipMemcpyDeviceToDevice, st));
+        if (int rc = score_chunk(m, w, rows.x, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st)) return rc;
+      }
+      return 0;
+    }
+  }
+  // the passes: one pass when n fits, else chunks of `cap` positions in position order; the head over each pass's residual rows
+  const int cap = (n <= m->small_t) ? m->small_t : m->max_t;
+  for (int m0 = 0; m0 < n; m0 += cap) {
+    const int mc = (n - m0 < cap) ? n - m0 : cap;
+    if (int rc = forward_pass(m, tokens + m0, n, w.zero, pos0 + m0, row, 0, 1, mc, nullptr, mc, nullptr, SD_BF16, m->cfg.vocab, 1, st)) return rc;
+    if (int rc = score_chunk(m, w, m->x, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st)) return rc;
+  }
+  return 0;
+}
+
 }  // namespace sd
 
 // ============================================================================ C-ABI
@@ -825,6 +918,24 @@ extern "C" int sd_model_forward(sd_model* m, const int32_t* tokens, int tok_stri
   clear_error();
   return model_forward(m, tokens, tok_stride, pos_base, pos_off, row0, B, M, ids_out, ids_stride, logits_out,
                        logits_dtype, skip_head, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sd_model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, void* stream) {
+  clear_error();
+  SD_REQUIRE(m, "score: NULL model");
+  SD_REQUIRE(tokens, "score: NULL tokens");
+  SD_REQUIRE(n >= 2, "score: n=%d tokens (a log-likelihood needs at least 2)", n);
+  SD_REQUIRE(m->is_packed(), "score: the head reads the packed lm_head (this model has none: SPECDEC_NO_PACK)");
+  SD_REQUIRE(m->cfg.d_model % 64 == 0, "score: d_model=%d is not a multiple of 64 (the head GEMM's k stage)", m->cfg.d_model);
+  SD_REQUIRE(m->k_cache && m->x, "score: model not bound (sd_model_bind)");
+  SD_REQUIRE(row >= 0 && row < m->B, "score: row %d outside the bound batch of %d", row, m->B);
+  SD_REQUIRE(pos0 >= 0 && pos0 + n <= m->Lmax && pos0 + n <= m->cfg.max_pos, "score: positions [%d,%d) outside the cache rows (%d) / max_pos (%d)",
+             pos0, pos0 + n, m->Lmax, m->cfg.max_pos);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+  SD_HIP_CHECK(hipStreamIsCapturing(st, &cap_st));
+  SD_REQUIRE(cap_st == hipStreamCaptureStatusNone, "score: the stream is capturing (score allocates its workspace and picks its route on the host)");
+  return model_score(m, tokens, n, row, pos0, logprob, greedy, st);
 }
 
 extern "C" int sd_model_hidden_rows(sd_model* m, int row0, int n, void* out, void* stream) {

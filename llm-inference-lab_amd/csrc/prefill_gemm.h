@@ -19,16 +19,26 @@ struct NativeMat {          // one matrix shape of a layer, split into row block
   int N, K, n_pairs, epi;
 };
 struct NativePlan {
-  NativeMat mat[4][2];      // [qkv, out, gate / up, down][128-row blocks, 64-row blocks]
+  NativeMat mat[5][2];      // [qkv, out, gate / up, down, lm_head][128-row blocks, 64-row blocks]
+  bool layers = false;      // the four layer shapes are built (prefill_native_shapes_ok); the lm_head is built whenever d_model % 64 == 0
   int head_dim = 0;
-  void* buf = nullptr;      // device tables of all eight
+  void* buf = nullptr;      // device tables of all of them
 };
 bool prefill_native_shapes_ok(const sd_model_config& c);     // Llama, every K a multiple of 64
+// the layer shapes where prefill_native_shapes_ok, and the lm_head (N = vocab, K = d_model, pairs (2p, 2p + 1); either arch)
 int native_plan_build(const sd_model_config& c, NativePlan& plan);
 void native_plan_free(NativePlan& plan);
 // Y[T][N] fp32 (HF row order) = X[T][K] x W^T, W = the packed stream of matrix `which` (0 qkv, 1 out, 2 gate / up, 3 down) of a layer
 int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const float* w_scale, bool w8, const uint16_t* X, int ldx, float* Y,
                         int T, hipStream_t st);
+
+// ---- sd_model_score's head (csrc/score_head.hip): the lm_head of the native plan with a log-softmax / argmax epilogue ----------------
+// bytes of the partials of kPrefillChunk tokens (either row-block size)
+size_t score_partial_bytes(const NativePlan& plan);
+// Xn: T <= kPrefillChunk normed rows (bf16 [T][d_model]). target[t] (t < n_target): the row whose logit gives logprob[t] = l_target - lse;
+// greedy[t] = argmax row (either may be null). part / tgt_logit: score_partial_bytes / T floats of workspace.
+int launch_score_head(const NativePlan& plan, const void* W, const float* w_scale, bool w8, const uint16_t* Xn, int T, const int32_t* target,
+                      int n_target, float4* part, float* tgt_logit, float* logprob, int32_t* greedy, hipStream_t st);
 
 enum PrefillGemm { PREFILL_GEMM_ROCBLAS = 0, PREFILL_GEMM_NATIVE = 1 };
 
@@ -60,6 +70,9 @@ struct PrefillRows {
   uint16_t* attn = nullptr;
   uint16_t* act = nullptr;
 };
+// the final norm of the model over n residual rows (bf16, rows ldx apart) -> bf16 [n][d_model]: Llama RMSNorm with the rounding points
+// of the GEMV prologue (rms_rows_kernel), GPT-2 LayerNorm in fp32 rounded once (layernorm_pair)
+int launch_final_norm_rows(const sd_model_config& c, const uint16_t* x, int ldx, int n, uint16_t* out, hipStream_t st);
 int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int cache_row, int Mc, void* ws,
                        PrefillRows* rows_out, hipStream_t st);
 

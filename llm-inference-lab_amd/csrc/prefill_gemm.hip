@@ -114,6 +114,35 @@ __global__ __launch_bounds__(256) void rms_rows_kernel(const uint16_t* x, int x_
   for (int i = tid; i < np; i += 256) o[i] = rmsnorm_pair(row[i], rs, w2[i]);
 }
 
+// ---- GPT-2 LayerNorm of T rows (the final norm of sd_model_score): mean and rstd as the GEMV prologue forms them, layernorm_pair --------
+__global__ __launch_bounds__(256) void ln_rows_kernel(const uint16_t* x, int x_stride, const uint16_t* w, const uint16_t* b, float eps, int d,
+                                                     uint16_t* out) {
+  __shared__ float red[8];
+  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = reinterpret_cast<const uint32_t*>(x + static_cast<size_t>(t) * x_stride);
+  const uint32_t* w2 = reinterpret_cast<const uint32_t*>(w);
+  const uint32_t* b2 = reinterpret_cast<const uint32_t*>(b);
+  const int np = d >> 1;
+  f32x2_t s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
+  for (int i = tid; i < np; i += 256) {
+    const f32x2_t f = bf16x2_unpack(row[i]);
+    s1 += f;
+    s2 += f * f;
+  }
+  const float p1 = wave_reduce_sum(s1.x + s1.y), p2 = wave_reduce_sum(s2.x + s2.y);
+  if (lane == 0) {
+    red[wave] = p1;
+    red[4 + wave] = p2;
+  }
+  __syncthreads();
+  const float invK = 1.0f / static_cast<float>(d);
+  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) * invK;
+  const float sq = (red[4] + red[5]) + (red[6] + red[7]);
+  const float rs = rsqrtf(fmaxf(sq * invK - mean * mean, 0.f) + eps);
+  uint32_t* o = reinterpret_cast<uint32_t*>(out + static_cast<size_t>(t) * d);
+  for (int i = tid; i < np; i += 256) o[i] = layernorm_pair(row[i], mean, rs, w2[i], b2[i]);
+}
+
 // ---- the fused epilogues of the weight-streaming kernels, applied to fp32 products ---------------------------------------------------
 // Y: [T][N] fp32. GemvArgs carries token counts in 8-bit fields, so every group of 128 tokens gets its own view of the arguments
 // (pos_off and the token-indexed output moved on by 128 tokens) and the epilogue sees token indices below 128 — exactly what it
@@ -148,6 +177,17 @@ int launch_epilogue_rows(GemvArgs a, const float* Y, int T, int out_elem_stride,
 
 bool prefill_gemm_available() { return blas_ready(); }
 bool prefill_gemm_library_present() { return blas_open(); }
+
+int launch_final_norm_rows(const sd_model_config& c, const uint16_t* x, int ldx, int n, uint16_t* out, hipStream_t st) {
+  SD_REQUIRE(n >= 1 && x && out, "final norm: %d rows", n);
+  if (c.arch == SD_ARCH_LLAMA)
+    hipLaunchKernelGGL(rms_rows_kernel, dim3(n), dim3(256), 0, st, x, ldx, static_cast<const uint16_t*>(c.final_norm_w), c.norm_eps, c.d_model, out);
+  else
+    hipLaunchKernelGGL(ln_rows_kernel, dim3(n), dim3(256), 0, st, x, ldx, static_cast<const uint16_t*>(c.final_norm_w),
+                       static_cast<const uint16_t*>(c.final_norm_b), c.norm_eps, c.d_model, out);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
 
 size_t prefill_gemm_workspace_bytes(const sd_model_config& c) {
   const size_t T = kPrefillChunk;

@@ -18,177 +18,19 @@
 // rows (weight rows on the lanes), so each lane's results are 4 tokens of ONE weight row and the store maps that packed row to
 // its HF row once. No split-K: the host picks RB = 64 when 128-row blocks would leave most CUs idle.
 
-#include "gemv_device.h"
-#include "prefill_gemm.h"
+#include "prefill_mfma_device.h"
 
 namespace sd {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBT = 128;              // tokens per workgroup
-constexpr int kXBytes = kBT * 128;    // x stage: 128 tokens x 64 k (bf16)
-
-struct MfmaArgs {
-  const char* W;            // packed stream of the matrix
-  const float* w_scale;     // fp8: fp32 scale per HF row
-  const char* X;            // bf16 [T][ldx]
-  float* Y;                 // fp32 [T][N]
-  const int4* tiles;        // {first row in its block, pairs, first pair, 0}
-  const int2* blocks;       // {first tile, tiles}
-  int T, N, K, ldx;
-  int n_blocks, n_tb;       // row blocks, token blocks
-  int row_bytes;            // bytes of one packed row of the stream (K padded to 32 / 64)
-  int epi, head_dim, n_pairs;
-};
-
-__device__ __forceinline__ void glds16(const char* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16,
-                                   0, 0);
-}
-
-// HF row of packed row j (0 .. 2 np - 1) of the tile whose first pair is p0 (the rule of pack_pair_rows)
-__device__ __forceinline__ int hf_row(const MfmaArgs& a, int p0, int np, int j) {
-  const int second = j >= np ? 1 : 0;
-  const int p = p0 + j - second * np;
-  int r0, r1;
-  if (a.epi == EPI_QKV_ROPE) {
-    const int half = a.head_dim >> 1;
-    const int h = p / half, i = p - h * half;
-    r0 = h * a.head_dim + i;
-    r1 = r0 + half;
-  } else if (a.epi == EPI_SWIGLU) {
-    r0 = p;
-    r1 = p + a.n_pairs;
-  } else {
-    r0 = 2 * p;
-    r1 = 2 * p + 1;
-  }
-  return second ? r1 : r0;
-}
-
 template <int RF, bool W8>
 __global__ __launch_bounds__(kThreads, 2) void prefill_mfma_kernel(MfmaArgs a) {
-  constexpr int SB = W8 ? 64 : 128;              // bytes of one packed row per 64-k stage
-  constexpr int RB = 2 * RF * 16;                // weight rows per workgroup
-  constexpr int kWBytes = RB * SB;
-  constexpr int kBuf = kXBytes + kWBytes;
-  constexpr int XCH = kXBytes / 16 / kThreads;   // 16-byte x pieces per thread per stage
-  constexpr int WCH = kWBytes / 16 / kThreads;   // 16-byte weight pieces per thread per stage
-  static_assert(WCH >= 1 && XCH == 4, "stage geometry");
-  __shared__ __attribute__((aligned(16))) char smem[2 * kBuf];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 15, g = lane >> 4;
-  const int wt = wave & 1, wr = wave >> 1;       // token half, row half of the workgroup tile
-
-  // workgroup -> (row block, token block): the token blocks of one row block are consecutive on one XCD (dispatch is
-  // round-robin over the 8 XCDs), so a weight piece is fetched from HBM once and shared through that XCD's L2
-  const int G = a.n_blocks * a.n_tb;
-  int L = blockIdx.x;
-  if ((G & 7) == 0) L = (L & 7) * (G >> 3) + (L >> 3);
-  const int rb = L / a.n_tb, tb = L - rb * a.n_tb;
-  const int2 blk = a.blocks[rb];
-  const int t0 = tb * kBT;
-
-  // per lane: B-fragment offsets in the weight image and the HF row of each fragment column; sources of the weight pieces
-  int woff[RF], wstep[RF], hrow[RF];
-#pragma unroll
-  for (int f = 0; f < RF; ++f) { woff[f] = 0; wstep[f] = 0; hrow[f] = -1; }
-  uint32_t dsrc[WCH], dstr[WCH];
-  bool dval[WCH];
-#pragma unroll
-  for (int c = 0; c < WCH; ++c) { dsrc[c] = 0; dstr[c] = 0; dval[c] = false; }
-  for (int k = 0; k < blk.y; ++k) {
-    const int4 tl = a.tiles[blk.x + k];
-    const int rs = tl.x, np = tl.y, p0 = tl.z, nr = 2 * tl.y;
-#pragma unroll
-    for (int f = 0; f < RF; ++f) {
-      const int R = wr * RF * 16 + f * 16 + n;
-      if (R >= rs && R < rs + nr) {
-        const int j = R - rs;
-        woff[f] = rs * SB + (g * nr + j) * 16;
-        wstep[f] = nr * 64;
-        const int r = hf_row(a, p0, np, j);
-        hrow[f] = r < a.N ? r : -1;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < WCH; ++c) {
-      const int byte = ((c * 4 + wave) * 64 + lane) * 16;
-      const int row = byte / SB;
-      if (row >= rs && row < rs + nr) {
-        dsrc[c] = static_cast<uint32_t>(p0) * 2u * static_cast<uint32_t>(a.row_bytes) + static_cast<uint32_t>(byte - rs * SB);
-        dstr[c] = static_cast<uint32_t>(nr * SB);
-        dval[c] = true;
-      }
-    }
-  }
-  // x pieces: token row tr, 16-byte slot sl of the LDS image holds k-chunk sl ^ (tr & 7) (rows past T repeat row T - 1)
-  uint32_t xsrc[XCH];
-#pragma unroll
-  for (int c = 0; c < XCH; ++c) {
-    const int idx = (c * 4 + wave) * 64 + lane;
-    const int tr = idx >> 3, sl = idx & 7;
-    const int t = min(t0 + tr, a.T - 1);
-    xsrc[c] = static_cast<uint32_t>(t) * static_cast<uint32_t>(a.ldx) * 2u + static_cast<uint32_t>((sl ^ (tr & 7)) * 16);
-  }
-  const int xrow = (wt * 64 + n) * 128;
-  const int xo0 = (g ^ (n & 7)) * 16, xo1 = ((4 + g) ^ (n & 7)) * 16;
-
-  auto issue = [&](int s, int b) {
-    char* xb = smem + b * kBuf;
-    char* wb = xb + kXBytes;
-#pragma unroll
-    for (int c = 0; c < XCH; ++c) glds16(a.X + xsrc[c] + static_cast<uint32_t>(s) * 128u, xb + (c * 4 + wave) * 1024);
-#pragma unroll
-    for (int c = 0; c < WCH; ++c)
-      if (dval[c]) glds16(a.W + dsrc[c] + static_cast<uint32_t>(s) * dstr[c], wb + (c * 4 + wave) * 1024);
-  };
-
+  __shared__ __attribute__((aligned(16))) char smem[mfma_smem_bytes<RF, W8>()];
   f32x4_t acc[4][RF];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int f = 0; f < RF; ++f) acc[q][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int S = a.K >> 6;
-  issue(0, 0);
-  for (int s = 0; s < S; ++s) {
-    __syncthreads();                       // stage s has landed (the wait for the DMA precedes the barrier); buffer s+1 is free
-    if (s + 1 < S) issue(s + 1, (s + 1) & 1);
-    const char* xb = smem + (s & 1) * kBuf;
-    const char* wb = xb + kXBytes;
-    u32x4 wf[2][RF];
-#pragma unroll
-    for (int f = 0; f < RF; ++f) {
-      if constexpr (W8) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(wb + woff[f]);
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          wf[0][f][2 * e] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[e], 1.0f, false));
-          wf[0][f][2 * e + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[e], 1.0f, true));
-          wf[1][f][2 * e] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[2 + e], 1.0f, false));
-          wf[1][f][2 * e + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[2 + e], 1.0f, true));
-        }
-      } else {
-        wf[0][f] = *reinterpret_cast<const u32x4*>(wb + woff[f]);
-        wf[1][f] = *reinterpret_cast<const u32x4*>(wb + woff[f] + wstep[f]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x4 xa = *reinterpret_cast<const u32x4*>(xb + xrow + q * 16 * 128 + (u ? xo1 : xo0));
-#pragma unroll
-        for (int f = 0; f < RF; ++f)
-          acc[q][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, xa), __builtin_bit_cast(bf16x8_t, wf[u][f]),
-                                                              acc[q][f], 0, 0, 0);
-      }
-    }
-  }
+  int hrow[RF], t0, rb;
+  mfma_block_product<RF, W8>(a, smem, acc, hrow, t0, rb);
+  const int lane = threadIdx.x & 63, wt = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1, g = lane >> 4;
 
   // lane (n, g) holds tokens 4 g + e of its fragment row q, for weight row (fragment column) n of fragment f
 #pragma unroll
@@ -207,7 +49,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_mfma_kernel(MfmaArgs a) {
 }
 
 // the four matrix shapes of a layer, in packing order (model_matrices, csrc/pack.hip)
-void layer_shapes(const sd_model_config& c, int shp[4][4]) {
+void layer_shapes(const sd_model_config& c, int shp[][4]) {
   const int d = c.d_model, HqD = c.n_heads * c.head_dim, Nqkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
   const int v[4][4] = {{Nqkv, d, Nqkv / 2, EPI_QKV_ROPE}, {d, HqD, d / 2, EPI_RESID}, {2 * c.d_ff, d, c.d_ff, EPI_SWIGLU}, {d, c.d_ff, d / 2, EPI_RESID}};
   for (int i = 0; i < 4; ++i)
@@ -223,14 +65,17 @@ bool prefill_native_shapes_ok(const sd_model_config& c) {
 // Tiles of each matrix shape in stream order (the loop of pack_kernel: per workgroup share of ppw pairs, tiles of tile_pairs),
 // grouped into row blocks of whole tiles of <= 128 (and, separately, <= 64) rows.
 int native_plan_build(const sd_model_config& c, NativePlan& plan) {
-  SD_REQUIRE(prefill_native_shapes_ok(c), "prefill: the native backend needs a Llama model with d_model, Hq*D and d_ff multiples of 64");
-  int shp[4][4];
+  SD_REQUIRE(c.d_model % 64 == 0, "prefill: the native GEMM needs d_model a multiple of 64 (got %d)", c.d_model);
+  const bool layers = prefill_native_shapes_ok(c);
+  int shp[5][4];
   layer_shapes(c, shp);
+  const int head[4] = {c.vocab, c.d_model, (c.vocab + 1) / 2, EPI_ARGMAX};
+  for (int j = 0; j < 4; ++j) shp[4][j] = head[j];
   std::vector<int4> tiles;
   std::vector<int2> blocks;
   struct Span { size_t tiles, blocks; int n_blocks; };
-  Span spans[4][2];
-  for (int i = 0; i < 4; ++i) {
+  Span spans[5][2] = {};
+  for (int i = layers ? 0 : 4; i < 5; ++i) {
     const int n_pairs = shp[i][2], K = shp[i][1];
     const GemvGeom q = gemv_geometry(n_pairs, K);
     std::vector<int2> raw;   // {first pair, pairs}
@@ -268,7 +113,7 @@ int native_plan_build(const sd_model_config& c, NativePlan& plan) {
   SD_HIP_CHECK(hipMemcpy(static_cast<char*>(plan.buf) + tb, blocks.data(), bb, hipMemcpyHostToDevice));
   const int4* dt = static_cast<const int4*>(plan.buf);
   const int2* db = reinterpret_cast<const int2*>(static_cast<char*>(plan.buf) + tb);
-  for (int i = 0; i < 4; ++i)
+  for (int i = layers ? 0 : 4; i < 5; ++i)
     for (int v = 0; v < 2; ++v) {
       NativeMat& m = plan.mat[i][v];
       m.tiles = dt;
@@ -280,6 +125,7 @@ int native_plan_build(const sd_model_config& c, NativePlan& plan) {
       m.n_pairs = shp[i][2];
       m.epi = shp[i][3];
     }
+  plan.layers = layers;
   plan.head_dim = c.head_dim;
   return 0;
 }
@@ -292,7 +138,7 @@ void native_plan_free(NativePlan& plan) {
 // which = 0 qkv, 1 out, 2 gate / up, 3 down
 int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const float* w_scale, bool w8, const uint16_t* X, int ldx, float* Y,
                         int T, hipStream_t st) {
-  SD_REQUIRE(plan.buf && which >= 0 && which < 4, "prefill: native plan not built");
+  SD_REQUIRE(plan.buf && plan.layers && which >= 0 && which < 4, "prefill: native plan not built");
   SD_REQUIRE(T >= 1 && T <= kPrefillChunk, "prefill: native GEMM of %d rows", T);
   SD_REQUIRE(W && X && Y && (!w8 || w_scale), "prefill: native GEMM with a NULL operand");
   const int n_tb = (T + kBT - 1) / kBT;

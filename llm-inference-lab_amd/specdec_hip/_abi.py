@@ -82,6 +82,7 @@ SIGNATURES = {
         [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,
          _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p],
     ),
+    "sd_model_score": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "sd_model_probe_gemv": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p,
                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]),
     "sd_model_persist_tokens": (_c_int, [_c_void_p]),

@@ -246,6 +246,24 @@ class HipModel:
         _abi.check(rc, "sd_model_forward")
         return ids, logits
 
+    def score(self, tokens, row: int = 0, pos0: int = 0, stream: Optional[torch.cuda.Stream] = None):
+        """Log-likelihood of `tokens` (n >= 2 ids) appended to cache row `row` at positions pos0 .. pos0+n-1 (sd_model_score).
+        -> (logprob fp32 [n-1]: log p(tokens[i+1] | ...), greedy int32 [n]: the argmax id after position i), device tensors.
+        Leaves the cache as forward(skip_head=True) over the same tokens does; the [n][V] logits are never written."""
+        t = torch.as_tensor(tokens).reshape(-1).to(self.device, torch.int32).contiguous()
+        n = int(t.numel())
+        if self.health():
+            self.check_health("sd_model_score")
+        if self.page_len is not None and n >= 2 and 0 <= row < self.batch and pos0 >= 0:
+            self.reserve(int(row), int(pos0) + n, stream=stream)
+        logprob = torch.empty((max(n - 1, 0),), dtype=torch.float32, device=self.device)
+        greedy = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.sd_model_score(self.handle, t.data_ptr() if n else None, n, int(row), int(pos0), _ptr(logprob), _ptr(greedy),
+                                         _stream(stream, self.device))
+        _abi.check(rc, "sd_model_score")
+        return logprob, greedy
+
     def hidden_rows(self, n: int, row0: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
         """bf16 [n][d_model]: the residual-stream rows (before the final norm) of the last forward pass (sd_model_hidden_rows)."""
         out = torch.empty((n, self.cfg.d_model), dtype=torch.bfloat16, device=self.device)

@@ -128,6 +128,8 @@ def get_kernel_info():
         "library": str(_abi.lib_path()),
         "library_loaded": lib_ok,
         "prefill_backends": _prefill_backends() if lib_ok else [],
+        # sequence log-likelihood on the device (sd_model_score: lm_head GEMM with a log-softmax epilogue, csrc/score_head.hip)
+        "score_head": "hip" if lib_ok else "unavailable",
     }
 
 

@@ -14,6 +14,7 @@ launch per step."""
 from __future__ import annotations
 
 import logging
+import math
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -256,6 +257,30 @@ class HipLM(LanguageModel):
             var = ((x * x).mean(-1, keepdim=True) - mean * mean).clamp_min(0.0)
             h = bf((x - mean) * torch.rsqrt(var + self.config.norm_eps) * w.final_norm_w.float() + w.final_norm_b.float())
         return h.view(1, 1, -1)
+
+    def score(self, input_ids: Any) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(logprob fp32 [n-1], greedy int32 [n]) of one sequence of n >= 2 ids, scored on the device from position 0 of cache row 0
+        (HipModel.score). The row then caches the whole sequence, so a generate_tokens call on a prompt that extends it reuses it."""
+        return self._guarded("score", lambda: self._score(input_ids))
+
+    def _score(self, input_ids: Any) -> Tuple[torch.Tensor, torch.Tensor]:
+        ids = torch.as_tensor(input_ids).reshape(1, -1)
+        ids = validate_and_clamp_tokens(ids.long(), self.vocab_size, "score")
+        L = ids.shape[1]
+        if L < 2:
+            raise ValueError(f"score: {L} token(s); a log-likelihood needs at least 2")
+        m = self._engine(1, L + 1)
+        m.set_length_hint(max([L] + [len(c) for c in self._cached]) + 1)
+        self._cached[0] = []                      # the row is rewritten from position 0
+        logprob, greedy = m.score(ids[0].to(self._device, torch.int32), row=0, pos0=0)
+        self._cached[0] = ids[0].tolist()
+        return logprob, greedy
+
+    def perplexity(self, text_or_ids: Any) -> float:
+        """exp(mean(-log p(x_i | x_<i))) over positions 1..n-1: the `labels=input_ids` loss of a HF causal LM, exponentiated."""
+        ids = self.encode(text_or_ids) if isinstance(text_or_ids, str) else text_or_ids
+        logprob, _ = self.score(ids)
+        return math.exp(-float(logprob.double().mean()))
 
     def verify_tokens(self, input_ids: torch.Tensor, draft_tokens: torch.Tensor, row: Optional[int] = None, rows: int = 1):
         return self._guarded("verify_tokens", lambda: self._verify_tokens(input_ids, draft_tokens, row, rows))

@@ -12,6 +12,7 @@ from __future__ import annotations
 import argparse
 import json
 import logging
+import math
 import sys
 
 from .core.pipeline import SpeculativePipeline
@@ -46,7 +47,20 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--prefill-backend", type=str, choices=["auto", "passes", "rocblas", "native"], default="auto",
                     help="how prompts are absorbed into the KV cache: auto (rocBLAS where it serves the model, else the 128-token passes), "
                          "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
+    ap.add_argument("--eval-perplexity", action="store_true",
+                    help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     return ap.parse_args(argv)
+
+
+def generated_perplexity(lm, tokens):
+    """(perplexity, loss) of the generated ids under `lm` (HipLM.score); (inf, inf) for fewer than 2 tokens, as the reference's
+    evaluator reports a text it cannot score."""
+    ids = [int(t) for t in tokens]
+    if len(ids) < 2:
+        return float("inf"), float("inf")
+    logprob, _ = lm.score(ids)
+    loss = -float(logprob.double().mean())
+    return math.exp(loss), loss
 
 
 def main(argv=None) -> int:
@@ -76,11 +90,15 @@ def main(argv=None) -> int:
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
+        if args.eval_perplexity:
+            r["perplexity"], r["perplexity_loss"] = generated_perplexity(pipe.base_lm, r["generated_tokens"])
     except Exception as e:  # the reference CLI reports and exits 1 (run_specdec.py:276-278)
         logging.error("Error: %s", e)
         return 1
     keys = ("latency_ms", "proposed", "accepted", "acceptance_rate", "tokens_per_sec", "text", "impl", "device",
             "base_model", "draft_model", "draft_mode", "dtype")
+    if args.eval_perplexity:
+        keys += ("perplexity", "perplexity_loss")
     print(json.dumps({k: r[k] for k in keys}))
     return 0
 
