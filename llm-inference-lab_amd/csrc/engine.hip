@@ -113,6 +113,43 @@ static size_t workspace_bytes(const sd_model_config& c) {
   return n + 256;
 }
 
+// Matrix `index` (4 * layer + which; 4 * n_layers = the lm_head) as the forward launches it: weights, shape and bias, the fused
+// norm, and the workspace rows it reads and writes. The caller adds what belongs to the call: tokens, positions, caches, statistics.
+static GemvArgs matrix_args(const sd_model* m, int index) {
+  const sd_model_config& c = m->cfg;
+  const int which = matrix_which(c, index);
+  const MatShape sh = matrix_shape(c, which);
+  const MatWeights wt = matrix_weights(c, index);
+  GemvArgs a{};
+  a.W = m->mat(index, wt.w);
+  a.w_scale = m->scale(index);
+  a.packed = m->is_packed();
+  a.w8 = m->w8();
+  a.bias = wt.bias;
+  a.N = sh.N;
+  a.K = sh.K;
+  a.n_pairs = sh.n_pairs;
+  if (wt.norm_w) {
+    a.prologue = c.arch == SD_ARCH_LLAMA ? PRO_RMSNORM : PRO_LAYERNORM;
+    a.norm_w = wt.norm_w;
+    a.norm_b = wt.norm_b;
+    a.norm_eps = c.norm_eps;
+  }
+  const int d = c.d_model, HqD = c.n_heads * c.head_dim, ff = c.d_ff;
+  const struct { const uint16_t* x; int x_stride; uint16_t* out; int out_stride; } rows[5] = {
+      {m->x, d, m->q, HqD}, {m->attn, HqD, m->x, d}, {m->x, d, m->act, ff}, {m->act, ff, m->x, d}, {m->x, d, nullptr, 0}};
+  a.x = rows[which].x;
+  a.x_stride = rows[which].x_stride;
+  a.out = rows[which].out;
+  a.out_stride = rows[which].out_stride;
+  a.out_dtype = SD_BF16;
+  if (which == 4) {   // the head's argmax partials
+    a.part_val = m->part_val;
+    a.part_idx = m->part_idx;
+  }
+  return a;
+}
+
 // one pass: Bc rows x Mc tokens, Bc*Mc <= m->max_t
 static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base,
                         int pos_off, int row0, int b0, int Bc, int Mc, int32_t* ids_out, int ids_stride,
@@ -122,7 +159,6 @@ static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, cons
   const int T = Bc * Mc;
   const int d = c.d_model, Hq = c.n_heads, Hkv = c.n_kv_heads, D = c.head_dim, ff = c.d_ff;
   const bool llama = (c.arch == SD_ARCH_LLAMA);
-  const int pro = llama ? PRO_RMSNORM : PRO_LAYERNORM;
 
   // ---- the whole pass as ONE persistent launch (csrc/persist.hip): small passes of a dense-KV Llama model
   if (persist_pass_ok(m, T, Bc, Mc)) {
@@ -206,44 +242,28 @@ static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, cons
     }
   };
   for (int l = 0; l < c.n_layers; ++l) {
-    const sd_layer_weights& w = m->layers[l];
     uint16_t* kc = m->k_cache + l * layer_kv + row_kv;
     uint16_t* vc = m->v_cache + l * layer_kv + row_kv;
-
-    GemvArgs g{};
-    g.T = T;
-    g.M = Mc;
-    g.pos_base = pos_base + b0;
-    g.pos_off = pos_off;
-    g.head_dim = D;
-    g.n_q_heads = Hq;
-    g.n_kv_heads = Hkv;
-    g.max_pos = c.max_pos;
-    g.l_max = m->Lmax;
-    g.out_dtype = SD_BF16;
-    g.w8 = m->w8();
-    g.block_table = bt;
-    g.page_shift = m->page_shift;
-    g.skip_k = m->skip_k;
-    g.skip_i = m->skip_i;
+    auto layer_args = [&](int which) {
+      GemvArgs g = matrix_args(m, 4 * l + which);
+      g.T = T;
+      g.M = Mc;
+      g.pos_base = pos_base + b0;
+      g.pos_off = pos_off;
+      g.head_dim = D;
+      g.n_q_heads = Hq;
+      g.n_kv_heads = Hkv;
+      g.max_pos = c.max_pos;
+      g.l_max = m->Lmax;
+      g.block_table = bt;
+      g.page_shift = m->page_shift;
+      g.skip_k = m->skip_k;
+      g.skip_i = m->skip_i;
+      return g;
+    };
 
     // 1. norm + QKV projection + RoPE + in-place KV append
-    g.packed = m->is_packed();
-    GemvArgs a1 = g;
-    a1.W = m->mat(4 * l + 0, w.wqkv);
-    a1.w_scale = m->scale(4 * l + 0);
-    a1.bias = w.bqkv;
-    a1.N = (Hq + 2 * Hkv) * D;
-    a1.K = d;
-    a1.n_pairs = a1.N / 2;
-    a1.x = m->x;
-    a1.x_stride = d;
-    a1.prologue = pro;
-    a1.norm_w = w.attn_norm_w;
-    a1.norm_b = w.attn_norm_b;
-    a1.norm_eps = c.norm_eps;
-    a1.out = m->q;
-    a1.out_stride = Hq * D;
+    GemvArgs a1 = layer_args(0);
     a1.rope_cos = llama ? c.rope_cos : nullptr;
     a1.rope_sin = llama ? c.rope_sin : nullptr;
     a1.k_cache = kc;
@@ -276,89 +296,29 @@ static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, cons
     at.skip_i = m->skip_i;
     if (int rc = launch_attention(at, st)) return rc;
 
-    // 3. output projection + residual
-    GemvArgs a3 = g;
-    a3.W = m->mat(4 * l + 1, w.wo);
-    a3.w_scale = m->scale(4 * l + 1);
-    a3.bias = w.bo;
-    a3.N = d;
-    a3.K = Hq * D;
-    a3.n_pairs = d / 2;
-    a3.x = m->attn;
-    a3.x_stride = Hq * D;
-    a3.prologue = PRO_NONE;
-    a3.out = m->x;
-    a3.out_stride = d;
-
-    // 4. norm + up projection (+ gate) + activation
-    GemvArgs a4 = g;
-    a4.W = m->mat(4 * l + 2, w.w_up);
-    a4.w_scale = m->scale(4 * l + 2);
-    a4.bias = w.b_up;
-    a4.K = d;
-    a4.x = m->x;
-    a4.x_stride = d;
-    a4.prologue = pro;
-    a4.norm_w = w.mlp_norm_w;
-    a4.norm_b = w.mlp_norm_b;
-    a4.norm_eps = c.norm_eps;
-    a4.out = m->act;
-    a4.out_stride = ff;
+    // 3. output projection + residual, 4. norm + up projection (+ gate) + activation
+    GemvArgs a3 = layer_args(1);
+    GemvArgs a4 = layer_args(2);
     publish(a3);
     a4.xstat_in = stat_in;
     a4.xstat_n = stat_n;
-    if (llama) {
-      a4.N = 2 * ff;
-      a4.n_pairs = ff;
-      if (int rc = launch_gemv(a3, EPI_RESID, st)) return rc;
-      if (int rc = launch_gemv(a4, EPI_SWIGLU, st)) return rc;
-    } else {
-      a4.N = ff;
-      a4.n_pairs = ff / 2;
-      if (int rc = launch_gemv(a3, EPI_RESID, st)) return rc;
-      if (int rc = launch_gemv(a4, EPI_GELU, st)) return rc;
-    }
+    if (int rc = launch_gemv(a3, EPI_RESID, st)) return rc;
+    if (int rc = launch_gemv(a4, matrix_shape(c, 2).epi, st)) return rc;
 
     // 5. down projection + residual
-    GemvArgs a5 = g;
-    a5.W = m->mat(4 * l + 3, w.w_down);
-    a5.w_scale = m->scale(4 * l + 3);
-    a5.bias = w.b_down;
-    a5.N = d;
-    a5.K = ff;
-    a5.n_pairs = d / 2;
-    a5.x = m->act;
-    a5.x_stride = ff;
-    a5.prologue = PRO_NONE;
-    a5.out = m->x;
-    a5.out_stride = d;
+    GemvArgs a5 = layer_args(3);
     publish(a5);
     if (int rc = launch_gemv(a5, EPI_RESID, st)) return rc;
   }
   if (skip_head) return 0;
 
   // final norm + lm_head with the argmax fused into the epilogue
-  GemvArgs h{};
-  h.packed = m->is_packed();
-  h.w8 = m->w8();
-  h.w_scale = m->scale(4 * c.n_layers);
-  h.W = m->mat(4 * c.n_layers, c.lm_head);
-  h.N = c.vocab;
-  h.K = d;
-  h.n_pairs = (c.vocab + 1) / 2;
-  h.x = m->x;
-  h.x_stride = d;
+  GemvArgs h = matrix_args(m, 4 * c.n_layers);
   h.T = T;
   h.M = Mc;
-  h.prologue = pro;
-  h.norm_w = c.final_norm_w;
-  h.norm_b = c.final_norm_b;
-  h.norm_eps = c.norm_eps;
   h.out = logits_out;
   h.out_stride = logits_stride;
   h.out_dtype = logits_dtype;
-  h.part_val = m->part_val;
-  h.part_idx = m->part_idx;
   h.xstat_in = stat_in;
   h.xstat_n = stat_n;
   h.skip_k = m->skip_k;
@@ -376,31 +336,78 @@ static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, cons
 
 // final norm + lm_head + fused argmax over n <= 128 residual rows (bf16 [n][d_model]) -> ids[0..n)
 static int head_pass(sd_model* m, const uint16_t* xrows, int n, int32_t* ids, hipStream_t st) {
-  const sd_model_config& c = m->cfg;
-  GemvArgs h{};
-  h.packed = m->is_packed();
-  h.w8 = m->w8();
-  h.w_scale = m->scale(4 * c.n_layers);
-  h.W = m->mat(4 * c.n_layers, c.lm_head);
-  h.N = c.vocab;
-  h.K = c.d_model;
-  h.n_pairs = (c.vocab + 1) / 2;
+  GemvArgs h = matrix_args(m, 4 * m->cfg.n_layers);
   h.x = xrows;
-  h.x_stride = c.d_model;
   h.T = n;
   h.M = n;
-  h.prologue = (c.arch == SD_ARCH_LLAMA) ? PRO_RMSNORM : PRO_LAYERNORM;
-  h.norm_w = c.final_norm_w;
-  h.norm_b = c.final_norm_b;
-  h.norm_eps = c.norm_eps;
-  h.out = nullptr;
-  h.out_dtype = SD_BF16;
-  h.part_val = m->part_val;
-  h.part_idx = m->part_idx;
   int ks = 1;
   m->head_grid = gemv_grid(h, &ks);
   if (int rc = launch_gemv(h, EPI_ARGMAX, st)) return rc;
   return launch_argmax_finalize(m->part_val, m->part_idx, n, m->head_grid, n, n, ids, st);
+}
+
+// The route of a prompt. A prompt (M >= 96 positions per row, whatever the pass size of the decode-shaped kernels) is absorbed as GEMMs
+// (csrc/prefill_gemm.hip: <= 512 positions per chunk, every matrix product one GEMM, this repo's norm / epilogue / attention kernels
+// around them) when the caller wants no logits of the prompt positions (skip_head, or ids only: the head then runs over each chunk's
+// rows), the pass is not being captured and no adaptive-K word gates it. Which GEMM (sd_model_set_prefill_backend): SD_PREFILL_AUTO =
+// rocBLAS for a Llama model with bf16 row-major weights and dense KV when the library opens, else the passes; SD_PREFILL_ROCBLAS /
+// _NATIVE = that GEMM (validated when it was set); SD_PREFILL_PASSES = never a GEMM. Returns the backend, or -1 when M is below the
+// prefill minimum (the passes, not counted as a prompt).
+static int prefill_route(const sd_model* m, int M, bool logits, hipStream_t st) {
+  static const int prefill_min = getenv(debug_env::kPrefillMinTokens) ? atoi(getenv(debug_env::kPrefillMinTokens)) : kPrefillMinTokens;
+  if (M < prefill_min) return -1;
+  int backend = SD_PREFILL_PASSES;
+  const bool gemm_ok = m->cfg.arch == SD_ARCH_LLAMA && !logits && !m->skip_k;
+  if (m->prefill_backend == SD_PREFILL_AUTO) {
+    if (gemm_ok && !m->w8() && !m->block_table && m->cfg.weight_dtype == SD_BF16 && !getenv(debug_env::kNoGemmPrefill) && prefill_gemm_available())
+      backend = SD_PREFILL_ROCBLAS;
+  } else if (m->prefill_backend != SD_PREFILL_PASSES && gemm_ok) {
+    backend = m->prefill_backend;
+  }
+  if (backend != SD_PREFILL_PASSES) {
+    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap_st);
+    if (cap_st != hipStreamCaptureStatusNone) backend = SD_PREFILL_PASSES;
+  }
+  return backend;
+}
+
+// One row's prompt of M positions through the GEMM `backend` (prefill_route), in chunks of <= kPrefillChunk positions in position
+// order; on_chunk(m0, mc, x) runs the caller's head over each chunk's residual rows (bf16 [mc][d_model]).
+template <class OnChunk>
+static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int row, int M,
+                       hipStream_t st, OnChunk&& on_chunk) {
+  const sd_model_config& c = m->cfg;
+  if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(c)));
+  PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
+  pm.block_table = m->block_table;
+  pm.page_shift = m->page_shift;
+  pm.max_pages = m->max_pages;
+  pm.n_pages = m->n_pages;
+  if (backend == SD_PREFILL_NATIVE) {
+    if (!m->native_plan.buf)
+      if (int rc = native_plan_build(c, m->native_plan)) return rc;
+    pm.gemm = PREFILL_GEMM_NATIVE;
+    pm.packed = m->packed.data();
+    pm.scales = m->w8() ? m->scales.data() : nullptr;
+    pm.plan = &m->native_plan;
+  }
+  for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
+    const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
+    PrefillRows rows;
+    if (int rc = prefill_gemm_chunk(pm, tokens + m0, pos_base_row, pos_off + m0, row, mc, m->prefill_ws, &rows, st)) return rc;
+    // the chunk's last <= 128 positions go where every other pass leaves them: the residual rows (hidden rows, the head) and
+    // the last layer's q, attention and activation rows (sd_model_debug_rows)
+    const int keep = mc < 128 ? mc : 128;
+    const size_t HqD = static_cast<size_t>(c.n_heads) * c.head_dim;
+    const struct { uint16_t* dst; const uint16_t* src; size_t w; } taps[4] = {
+        {m->x, rows.x, static_cast<size_t>(c.d_model)}, {m->q, rows.q, HqD}, {m->attn, rows.attn, HqD}, {m->act, rows.act, static_cast<size_t>(c.d_ff)}};
+    for (const auto& tp : taps)
+      SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
+                                  hipMemcpyDeviceToDevice, st));
+    if (int rc = on_chunk(m0, mc, rows.x)) return rc;
+  }
+  return 0;
 }
 
 // rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are
@@ -416,75 +423,25 @@ static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, con
   SD_REQUIRE(!logits_out || logits_dtype == SD_F32 || logits_dtype == SD_BF16, "forward: logits dtype %d", logits_dtype);
   const int V = m->cfg.vocab;
   const int cap = (B * M <= m->small_t) ? m->small_t : m->max_t;  // tokens per pass
-  // A prompt (M >= 96 positions per row, whatever the pass size of the decode-shaped kernels) is absorbed as GEMMs (csrc/prefill_gemm.hip:
-  // <= 512 positions per chunk, every matrix product one GEMM, this repo's norm / epilogue / attention kernels around them) when the
-  // caller wants no logits of the prompt positions (skip_head, or ids only — the head then runs over the LAST chunk's rows below), the
-  // pass is not being captured and no adaptive-K word gates it. Which GEMM (sd_model_set_prefill_backend): SD_PREFILL_AUTO = rocBLAS for a
-  // Llama model with bf16 row-major weights and dense KV when the library opens, else the passes; SD_PREFILL_ROCBLAS / _NATIVE = that
-  // GEMM (validated when it was set); SD_PREFILL_PASSES = never a GEMM.
-  static const int prefill_min = getenv(debug_env::kPrefillMinTokens) ? atoi(getenv(debug_env::kPrefillMinTokens)) : kPrefillMinTokens;
-  if (M >= prefill_min) {
-    int backend = SD_PREFILL_PASSES;
-    const bool gemm_ok = m->cfg.arch == SD_ARCH_LLAMA && !logits_out && !m->skip_k;
-    if (m->prefill_backend == SD_PREFILL_AUTO) {
-      if (gemm_ok && !m->w8() && !m->block_table && m->cfg.weight_dtype == SD_BF16 && !getenv(debug_env::kNoGemmPrefill) && prefill_gemm_available())
-        backend = SD_PREFILL_ROCBLAS;
-    } else if (m->prefill_backend != SD_PREFILL_PASSES && gemm_ok) {
-      backend = m->prefill_backend;
-    }
-    if (backend != SD_PREFILL_PASSES) {
-      hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(st, &cap_st);
-      if (cap_st != hipStreamCaptureStatusNone) backend = SD_PREFILL_PASSES;
-    }
-    if (backend == SD_PREFILL_PASSES) {
-      m->prefill_count[SD_PREFILL_PASSES] += B;
-    } else {
-      if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(m->cfg)));
-      PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
-      pm.block_table = m->block_table;
-      pm.page_shift = m->page_shift;
-      pm.max_pages = m->max_pages;
-      pm.n_pages = m->n_pages;
-      if (backend == SD_PREFILL_NATIVE) {
-        if (!m->native_plan.buf)
-          if (int rc = native_plan_build(m->cfg, m->native_plan)) return rc;
-        pm.gemm = PREFILL_GEMM_NATIVE;
-        pm.packed = m->packed.data();
-        pm.scales = m->w8() ? m->scales.data() : nullptr;
-        pm.plan = &m->native_plan;
-      }
-      for (int b0 = 0; b0 < B; ++b0) {
-        for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
-          const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
-          PrefillRows rows;
-          if (int rc = prefill_gemm_chunk(pm, tokens + static_cast<size_t>(b0) * tok_stride + m0, pos_base + b0, pos_off + m0, row0 + b0, mc,
-                                          m->prefill_ws, &rows, st))
-            return rc;
-          const uint16_t* xr = rows.x;
-          // the chunk's last <= 128 positions go where every other pass leaves them: the residual rows (hidden rows, the head) and
-          // the last layer's q, attention and activation rows (sd_model_debug_rows)
-          const int keep = mc < 128 ? mc : 128;
-          const size_t HqD = static_cast<size_t>(m->cfg.n_heads) * m->cfg.head_dim;
-          const struct { uint16_t* dst; const uint16_t* src; size_t w; } taps[4] = {
-              {m->x, rows.x, static_cast<size_t>(m->cfg.d_model)}, {m->q, rows.q, HqD}, {m->attn, rows.attn, HqD},
-              {m->act, rows.act, static_cast<size_t>(m->cfg.d_ff)}};
-          for (const auto& tp : taps)
-            SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
-                                        hipMemcpyDeviceToDevice, st));
-          if (!skip_head && ids_out) {
-            // ids of the prompt positions: the lm_head over the chunk's rows in groups of at most the model's pass size (the
-            // decode-shaped head kernel covers no more: 64 rows for some fp8 heads)
-            for (int s0 = 0; s0 < mc; s0 += m->max_t) {
-              const int n = (mc - s0 < m->max_t) ? mc - s0 : m->max_t;
-              if (int rc = head_pass(m, xr + static_cast<size_t>(s0) * m->cfg.d_model, n, ids_out + static_cast<size_t>(b0) * ids_stride + m0 + s0, st)) return rc;
-            }
-          }
+  const int backend = prefill_route(m, M, logits_out != nullptr, st);
+  if (backend == SD_PREFILL_PASSES) {
+    m->prefill_count[SD_PREFILL_PASSES] += B;
+  } else if (backend >= 0) {
+    for (int b0 = 0; b0 < B; ++b0) {
+      // ids of the prompt positions: the lm_head over the chunk's rows in groups of at most the model's pass size (the decode-shaped
+      // head kernel covers no more: 64 rows for some fp8 heads)
+      auto head = [&](int m0, int mc, const uint16_t* xr) -> int {
+        if (skip_head || !ids_out) return 0;
+        for (int s0 = 0; s0 < mc; s0 += m->max_t) {
+          const int n = (mc - s0 < m->max_t) ? mc - s0 : m->max_t;
+          if (int rc = head_pass(m, xr + static_cast<size_t>(s0) * m->cfg.d_model, n, ids_out + static_cast<size_t>(b0) * ids_stride + m0 + s0, st)) return rc;
         }
-      }
-      m->prefill_count[backend] += B;
-      return 0;
+        return 0;
+      };
+      if (int rc = prefill_row(m, backend, tokens + static_cast<size_t>(b0) * tok_stride, pos_base + b0, pos_off, row0 + b0, M, st, head)) return rc;
     }
+    m->prefill_count[backend] += B;
+    return 0;
   }
   if (M <= cap) {
     const int Bc = cap / M;
@@ -549,48 +506,12 @@ static int model_score(sd_model* m, const int32_t* tokens, int n, int row, int p
   ScoreWs w{};
   if (int rc = score_ws(m, w)) return rc;
   // the route of model_forward for B = 1, M = n, no logits (the stream is not capturing: refused by the caller)
-  static const int prefill_min = getenv(debug_env::kPrefillMinTokens) ? atoi(getenv(debug_env::kPrefillMinTokens)) : kPrefillMinTokens;
-  if (n >= prefill_min) {
-    int backend = SD_PREFILL_PASSES;
-    const bool gemm_ok = m->cfg.arch == SD_ARCH_LLAMA && !m->skip_k;
-    if (m->prefill_backend == SD_PREFILL_AUTO) {
-      if (gemm_ok && !m->w8() && !m->block_table && m->cfg.weight_dtype == SD_BF16 && !getenv(debug_env::kNoGemmPrefill) && prefill_gemm_available())
-        backend = SD_PREFILL_ROCBLAS;
-    } else if (m->prefill_backend != SD_PREFILL_PASSES && gemm_ok) {
-      backend = m->prefill_backend;
-    }
-    m->prefill_count[backend] += 1;
-    if (backend != SD_PREFILL_PASSES) {
-      if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(m->cfg)));
-      PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
-      pm.block_table = m->block_table;
-      pm.page_shift = m->page_shift;
-      pm.max_pages = m->max_pages;
-      pm.n_pages = m->n_pages;
-      if (backend == SD_PREFILL_NATIVE) {
-        pm.gemm = PREFILL_GEMM_NATIVE;
-        pm.packed = m->packed.data();
-        pm.scales = m->w8() ? m->scales.data() : nullptr;
-        pm.plan = &m->native_plan;
-      }
-      for (int m0 = 0; m0 < n; m0 += kPrefillChunk) {
-        const int mc = (n - m0 < kPrefillChunk) ? n - m0 : kPrefillChunk;
-        PrefillRows rows;
-        if (int rc = prefill_gemm_chunk(pm, tokens + m0, w.zero, pos0 + m0, row, mc, m->prefill_ws, &rows, st)) return rc;
-        // the taps of model_forward: the chunk's last <= 128 positions (sd_model_hidden_rows / sd_model_debug_rows)
-        const int keep = mc < 128 ? mc : 128;
-        const size_t HqD = static_cast<size_t>(m->cfg.n_heads) * m->cfg.head_dim;
-        const struct { uint16_t* dst; const uint16_t* src; size_t w; } taps[4] = {
-            {m->x, rows.x, static_cast<size_t>(m->cfg.d_model)}, {m->q, rows.q, HqD}, {m->attn, rows.attn, HqD},
-            {m->act, rows.act, static_cast<size_t>(m->cfg.d_ff)}};
-        for (const auto& tp : taps)
-          SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
-                                      hipMemcpyDeviceToDevice, st));
-        if (int rc = score_chunk(m, w, rows.x, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st)) return rc;
-      }
-      return 0;
-    }
-  }
+  const int backend = prefill_route(m, n, false, st);
+  if (backend >= 0) m->prefill_count[backend] += 1;
+  if (backend > SD_PREFILL_PASSES)
+    return prefill_row(m, backend, tokens, w.zero, pos0, row, n, st, [&](int m0, int mc, const uint16_t* xr) {
+      return score_chunk(m, w, xr, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st);
+    });
   // the passes: one pass when n fits, else chunks of `cap` positions in position order; the head over each pass's residual rows
   const int cap = (n <= m->small_t) ? m->small_t : m->max_t;
   for (int m0 = 0; m0 < n; m0 += cap) {
@@ -641,13 +562,12 @@ extern "C" int sd_model_create(const sd_model_config* cfg, sd_model** out) {
   {
     // 64-token passes need every matrix of the model to be a shape gemm_skinny.hip covers
     const sd_model_config& c = m->cfg;
-    const bool llama = (c.arch == SD_ARCH_LLAMA);
     const int HqD = c.n_heads * c.head_dim;
     const bool w8 = cfg->weight_dtype == SD_FP8_E4M3;
     auto covers = [&](int T) {
-      return gemm_skinny_covers(T, (c.n_heads + 2 * c.n_kv_heads) * c.head_dim / 2, c.d_model, w8) &&
-             gemm_skinny_covers(T, c.d_model / 2, HqD, w8) && gemm_skinny_covers(T, llama ? c.d_ff : c.d_ff / 2, c.d_model, w8) &&
-             gemm_skinny_covers(T, c.d_model / 2, c.d_ff, w8) && gemm_skinny_covers(T, (c.vocab + 1) / 2, c.d_model, w8);
+      for (int i = 0; i < 5; ++i)
+        if (!gemm_skinny_covers(T, matrix_shape(c, i).n_pairs, matrix_shape(c, i).K, w8)) return false;
+      return true;
     };
     // the most tokens every matrix of the model can take in one pass: 128, 64 (x chunks of a pass must fit the LDS) ...
     int cover_t = 0;
@@ -665,15 +585,12 @@ extern "C" int sd_model_create(const sd_model_config* cfg, sd_model** out) {
   }
   if (cfg->weight_dtype == SD_FP8_E4M3) {
     // every matrix must split into whole 64-k steps per K slice
-    const sd_model_config& c = m->cfg;
-    const bool llama = (c.arch == SD_ARCH_LLAMA);
-    const int shapes[5][2] = {{(c.n_heads + 2 * c.n_kv_heads) * c.head_dim / 2, c.d_model}, {c.d_model / 2, c.n_heads * c.head_dim},
-                              {llama ? c.d_ff : c.d_ff / 2, c.d_model}, {c.d_model / 2, c.d_ff}, {(c.vocab + 1) / 2, c.d_model}};
-    for (const auto& sh : shapes) {
-      const GemvGeom q = gemv_geometry(sh[0], sh[1]);
-      if (sh[1] % 64 != 0 || q.kw % 64 != 0 || q.kw * q.ksplit != sh[1]) {
+    for (int i = 0; i < 5; ++i) {
+      const MatShape sh = matrix_shape(m->cfg, i);
+      const GemvGeom q = gemv_geometry(sh.n_pairs, sh.K);
+      if (sh.K % 64 != 0 || q.kw % 64 != 0 || q.kw * q.ksplit != sh.K) {
         delete m;
-        SD_REQUIRE(false, "model_create: fp8 storage does not cover a matrix with K=%d (K slice %d)", sh[1], q.kw);
+        SD_REQUIRE(false, "model_create: fp8 storage does not cover a matrix with K=%d (K slice %d)", sh.K, q.kw);
       }
     }
   }
@@ -681,8 +598,9 @@ extern "C" int sd_model_create(const sd_model_config* cfg, sd_model** out) {
     const char* base = static_cast<const char*>(cfg->packed);
     for (int i = 0; i <= 4 * cfg->n_layers; ++i) {
       m->packed.push_back(base + packed_offset(m->cfg, i));
-      if (cfg->weight_dtype == SD_FP8_E4M3)
-        m->scales.push_back(reinterpret_cast<const float*>(base + packed_offset(m->cfg, i) + packed_scale_offset(m->cfg, i)));
+      const MatShape sh = matrix_shape(m->cfg, matrix_which(m->cfg, i));
+      if (cfg->weight_dtype == SD_FP8_E4M3)   // the fp32 row scales follow the packed bytes
+        m->scales.push_back(reinterpret_cast<const float*>(base + packed_offset(m->cfg, i) + packed_fp8_weight_bytes(sh.n_pairs, sh.K)));
     }
   }
   *out = m;
@@ -800,30 +718,23 @@ static int carve_workspace(sd_model* m, void* workspace) {
     SD_HIP_CHECK(hipGetDevice(&dev));
     SD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     if (persist_model_ok(c, m->is_packed() != 0, m->w8() != 0, prop.multiProcessorCount)) {
-      const int HqD = c.n_heads * c.head_dim;
       std::vector<PersistOp> ops;
-      auto add = [&](int index, const void* norm_w, int n_pairs, int K, int kind, int layer) {
-        const GemvGeom q = gemv_geometry(n_pairs, K);
+      for (int i = 0; i <= 4 * c.n_layers; ++i) {
+        const int which = matrix_which(c, i);   // = PersistKind
+        const MatShape sh = matrix_shape(c, which);
+        const GemvGeom q = gemv_geometry(sh.n_pairs, sh.K);
         PersistOp o{};
-        o.W = m->packed[index];
-        o.norm_w = norm_w;
-        o.pair_bytes = static_cast<unsigned>(4 * K);
-        o.n_pairs = n_pairs;
+        o.W = m->packed[i];
+        o.norm_w = matrix_weights(c, i).norm_w;
+        o.pair_bytes = static_cast<unsigned>(4 * sh.K);
+        o.n_pairs = sh.n_pairs;
         o.ppw = q.ppw;
         o.tile_pairs = q.tile_pairs;
-        o.K = K;
-        o.kind = kind;
-        o.layer = layer;
+        o.K = sh.K;
+        o.kind = which;
+        o.layer = i >> 2;
         ops.push_back(o);
-      };
-      for (int l = 0; l < c.n_layers; ++l) {
-        const sd_layer_weights& w = m->layers[l];
-        add(4 * l + 0, w.attn_norm_w, (c.n_heads + 2 * c.n_kv_heads) * c.head_dim / 2, c.d_model, POP_QKV, l);
-        add(4 * l + 1, nullptr, c.d_model / 2, HqD, POP_OUT, l);
-        add(4 * l + 2, w.mlp_norm_w, c.d_ff, c.d_model, POP_GATEUP, l);
-        add(4 * l + 3, nullptr, c.d_model / 2, c.d_ff, POP_DOWN, l);
       }
-      add(4 * c.n_layers, c.final_norm_w, (c.vocab + 1) / 2, c.d_model, POP_HEAD, c.n_layers);
       SD_HIP_CHECK(hipMemcpy(m->p_ops, ops.data(), ops.size() * sizeof(PersistOp), hipMemcpyHostToDevice));
       // (a cache whose rows are not whole 8-key vectors cannot be walked by the launch's attention: launch path)
       m->persist_cap = persist_cache_ok(m->Lmax) ? persist_max_tokens(c) : 0;
@@ -956,9 +867,10 @@ extern "C" int sd_model_probe_gemv(sd_model* m, int which, int T, int iters, voi
   clear_error();
   SD_REQUIRE(m && m->x && avg_usec && bytes_per_launch, "probe_gemv: NULL argument / model not bound");
   SD_REQUIRE(T >= 1 && T <= kSkinnyMaxT && iters >= 1, "probe_gemv: T=%d iters=%d", T, iters);
+  SD_REQUIRE(which >= 0 && which <= 4, "probe_gemv: which=%d (0=qkv 1=o_proj 2=gate_up 3=down 4=lm_head)", which);
+  SD_REQUIRE(which != 0 || !m->block_table, "probe_gemv: the QKV probe writes dense cache rows (not available on a paged model)");
   const sd_model_config& c = m->cfg;
-  const bool llama = (c.arch == SD_ARCH_LLAMA);
-  const int d = c.d_model, ff = c.d_ff, Hq = c.n_heads, D = c.head_dim;
+  const MatShape sh = matrix_shape(c, which);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipEvent_t e0, e1;
   SD_HIP_CHECK(hipEventCreate(&e0));
@@ -976,67 +888,25 @@ extern "C" int sd_model_probe_gemv(sd_model* m, int which, int T, int iters, voi
   const bool use_xstat = T > kGemvMaxT && T <= 64 && !getenv(debug_env::kProbeNoXstat);
   auto launch = [&](int l) -> int {
     if (hot > 0) l %= hot;
-    const sd_layer_weights& w = m->layers[l % c.n_layers];
-    GemvArgs g{};
-    g.debug_ts = dbg;
-    g.packed = m->is_packed();
-    g.w8 = m->w8();
-    g.w_scale = m->scale(which == 4 ? 4 * c.n_layers : 4 * (l % c.n_layers) + which);
-    g.M = T;
     const int li = l % c.n_layers;
+    GemvArgs g = matrix_args(m, which == 4 ? 4 * c.n_layers : 4 * li + which);
+    g.debug_ts = dbg;
     g.T = T;
     g.M = T;
-    g.out_dtype = SD_BF16;
     g.norm_eps = c.norm_eps;
-    if (use_xstat && (which == 0 || which == 2 || which == 4)) { g.xstat_in = m->xstat; g.xstat_n = 256; }
-    switch (which) {
-      case 0: {  // norm + QKV projection + RoPE + in-place KV append (row 0 of the cache, positions 0..T-1)
-        SD_REQUIRE(!m->block_table, "probe_gemv: the QKV probe writes dense cache rows (not available on a paged model)");
-        const int Hkv = c.n_kv_heads;
-        g.W = m->mat(4 * li + 0, w.wqkv); g.bias = w.bqkv; g.N = (Hq + 2 * Hkv) * D; g.K = d; g.n_pairs = g.N / 2;
-        g.x = m->x; g.x_stride = d; g.prologue = llama ? PRO_RMSNORM : PRO_LAYERNORM; g.norm_w = w.attn_norm_w; g.norm_b = w.attn_norm_b;
-        g.out = m->q; g.out_stride = Hq * D; g.head_dim = D; g.n_q_heads = Hq; g.n_kv_heads = Hkv; g.max_pos = c.max_pos; g.l_max = m->Lmax;
-        g.rope_cos = llama ? c.rope_cos : nullptr; g.rope_sin = llama ? c.rope_sin : nullptr;
-        g.pos_base = m->probe_pos; g.pos_off = 0; g.M = T;
-        const size_t layer_kv = static_cast<size_t>(m->B) * Hkv * m->Lmax * D;
-        g.k_cache = m->k_cache + li * layer_kv; g.v_cache = m->v_cache + li * layer_kv;
-        return launch_gemv(g, EPI_QKV_ROPE, st);
-      }
-      case 1:  // attention output projection + residual
-        g.W = m->mat(4 * li + 1, w.wo); g.bias = w.bo; g.N = d; g.K = Hq * D; g.n_pairs = d / 2;
-        g.x = m->attn; g.x_stride = Hq * D; g.prologue = PRO_NONE; g.out = m->x; g.out_stride = d;
-        if (use_xstat && gemm_resid_publishes_stats(g)) g.xstat_out = m->xstat;
-        return launch_gemv(g, EPI_RESID, st);
-      case 2:  // norm + gate/up + SwiGLU (GELU for GPT-2)
-        g.W = m->mat(4 * li + 2, w.w_up); g.bias = w.b_up; g.K = d; g.x = m->x; g.x_stride = d;
-        g.prologue = llama ? PRO_RMSNORM : PRO_LAYERNORM; g.norm_w = w.mlp_norm_w; g.norm_b = w.mlp_norm_b;
-        g.out = m->act; g.out_stride = ff;
-        if (llama) { g.N = 2 * ff; g.n_pairs = ff; return launch_gemv(g, EPI_SWIGLU, st); }
-        g.N = ff; g.n_pairs = ff / 2;
-        return launch_gemv(g, EPI_GELU, st);
-      case 3:  // down projection + residual
-        g.W = m->mat(4 * li + 3, w.w_down); g.bias = w.b_down; g.N = d; g.K = ff; g.n_pairs = d / 2;
-        g.x = m->act; g.x_stride = ff; g.prologue = PRO_NONE; g.out = m->x; g.out_stride = d;
-        if (use_xstat && gemm_resid_publishes_stats(g)) g.xstat_out = m->xstat;
-        return launch_gemv(g, EPI_RESID, st);
-      case 4:  // final norm + lm_head + fused argmax
-        g.W = m->mat(4 * c.n_layers, c.lm_head); g.N = c.vocab; g.K = d; g.n_pairs = (c.vocab + 1) / 2; g.x = m->x; g.x_stride = d;
-        g.prologue = llama ? PRO_RMSNORM : PRO_LAYERNORM; g.norm_w = c.final_norm_w; g.norm_b = c.final_norm_b;
-        g.part_val = m->part_val; g.part_idx = m->part_idx;
-        return launch_gemv(g, EPI_ARGMAX, st);
-      default:
-        set_error("probe_gemv: which=%d (0=qkv 1=o_proj 2=gate_up 3=down 4=lm_head)", which);
-        return 1;
+    if (use_xstat && g.prologue != PRO_NONE) { g.xstat_in = m->xstat; g.xstat_n = 256; }
+    if (which == 0) {  // QKV: + RoPE + in-place KV append (row 0 of the cache, positions 0..T-1)
+      const int Hkv = c.n_kv_heads, D = c.head_dim;
+      g.head_dim = D; g.n_q_heads = c.n_heads; g.n_kv_heads = Hkv; g.max_pos = c.max_pos; g.l_max = m->Lmax;
+      g.rope_cos = c.arch == SD_ARCH_LLAMA ? c.rope_cos : nullptr; g.rope_sin = c.arch == SD_ARCH_LLAMA ? c.rope_sin : nullptr;
+      g.pos_base = m->probe_pos; g.pos_off = 0;
+      const size_t layer_kv = static_cast<size_t>(m->B) * Hkv * m->Lmax * D;
+      g.k_cache = m->k_cache + li * layer_kv; g.v_cache = m->v_cache + li * layer_kv;
     }
+    if (use_xstat && sh.epi == EPI_RESID && gemm_resid_publishes_stats(g)) g.xstat_out = m->xstat;
+    return launch_gemv(g, sh.epi, st);
   };
-  double bytes = 0;
-  switch (which) {
-    case 0: bytes = 2.0 * (Hq + 2 * c.n_kv_heads) * D * d; break;
-    case 1: bytes = 2.0 * d * Hq * D; break;
-    case 2: bytes = 2.0 * (llama ? 2 : 1) * ff * d; break;
-    case 3: bytes = 2.0 * d * ff; break;
-    default: bytes = 2.0 * c.vocab * d; break;
-  }
+  double bytes = 2.0 * sh.N * sh.K;
   if (m->w8()) bytes *= 0.5;  // one byte per weight
   for (int i = 0; i < 3; ++i)
     if (int rc = launch(i)) return rc;
@@ -1138,10 +1008,9 @@ extern "C" int sd_model_probe_forward(sd_model* m, int M, int pos0, int iters, i
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   *avg_usec = ms * 1000.0f / iters;
-  const bool llama = (c.arch == SD_ARCH_LLAMA);
-  double per_layer = 2.0 * ((c.n_heads + 2.0 * c.n_kv_heads) * c.head_dim * c.d_model + static_cast<double>(c.d_model) * c.n_heads * c.head_dim +
-                            (llama ? 3.0 : 2.0) * c.d_ff * c.d_model);
-  double bytes = per_layer * c.n_layers + (skip_head ? 0.0 : 2.0 * c.vocab * c.d_model);
+  double per_layer = 0;
+  for (int i = 0; i < 4; ++i) per_layer += 2.0 * matrix_shape(c, i).N * matrix_shape(c, i).K;
+  double bytes = per_layer * c.n_layers + (skip_head ? 0.0 : 2.0 * matrix_shape(c, 4).N * matrix_shape(c, 4).K);
   if (m->w8()) bytes *= 0.5;
   *bytes_per_forward = bytes;
   if (timeline && m->persist_t >= M) {
@@ -1217,25 +1086,12 @@ static int enqueue_medusa_heads(sd_specdec* s, hipStream_t st) {
   const sd_model_config& c = m->cfg;
   const int B = s->B, K = s->K;
   if (int rc = launch_medusa_rows(s->st, s->head_rows, st)) return rc;
-  GemvArgs h{};
+  GemvArgs h = matrix_args(m, 4 * c.n_layers);   // the lm_head's shape and final norm; the heads' own weights below
   h.packed = 1;
   h.w8 = s->head_scales.empty() ? 0 : 1;
-  h.N = c.vocab;
-  h.K = c.d_model;
-  h.n_pairs = (c.vocab + 1) / 2;
-  h.x = m->x;
-  h.x_stride = c.d_model;
   h.x_row = s->head_rows;
   h.T = B;
   h.M = 1;
-  h.prologue = (c.arch == SD_ARCH_LLAMA) ? PRO_RMSNORM : PRO_LAYERNORM;
-  h.norm_w = c.final_norm_w;
-  h.norm_b = c.final_norm_b;
-  h.norm_eps = c.norm_eps;
-  h.out = nullptr;
-  h.out_dtype = SD_BF16;
-  h.part_val = m->part_val;
-  h.part_idx = m->part_idx;
   if (B > m->small_t) {   // more rows than a GEMV pass: gather them (the attention-output buffer is free after the verify forward)
     if (int rc = launch_medusa_gather(m->x, s->head_rows, m->attn, B, c.d_model, st)) return rc;
     h.x = m->attn;
@@ -1274,23 +1130,13 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
     if (int rc = launch_eagle_extrapolate(m->x, s->eagle_H, s->eagle_prev, s->eagle_has, c.final_norm_w, c.final_norm_b, c.norm_eps,
                                           s->eagle_alpha, c.d_model, B, K, c.arch == SD_ARCH_LLAMA ? 1 : 0, st_t))
       return rc;
-    GemvArgs h{};
-    h.packed = m->is_packed();
-    h.w8 = m->w8();
-    h.w_scale = m->scale(4 * c.n_layers);
-    h.W = m->mat(4 * c.n_layers, c.lm_head);
-    h.N = c.vocab;
-    h.K = c.d_model;
-    h.n_pairs = (c.vocab + 1) / 2;
+    GemvArgs h = matrix_args(m, 4 * c.n_layers);
     h.x = s->eagle_H;
-    h.x_stride = c.d_model;
     h.T = B * K;
     h.M = K;
     h.prologue = PRO_NONE;     // the rows are final-norm outputs already
-    h.out = nullptr;
-    h.out_dtype = SD_BF16;
-    h.part_val = m->part_val;
-    h.part_idx = m->part_idx;
+    h.norm_w = h.norm_b = nullptr;
+    h.norm_eps = 0.f;
     int ppw = 1;
     const int grid = gemv_grid(h, &ppw);
     if (int rc = launch_gemv(h, EPI_ARGMAX, st_t)) return rc;
@@ -1661,9 +1507,8 @@ extern "C" int sd_specdec_set_medusa(sd_specdec* s, int n_heads, const void* con
     SD_REQUIRE(packed_heads[i], "specdec_set_medusa: head %d is NULL", i);
     s->heads.push_back(packed_heads[i]);
     if (weight_dtype == SD_FP8_E4M3) {
-      const size_t off = packed_any_matrix_bytes((c.vocab + 1) / 2, c.d_model, SD_FP8_E4M3) -
-                         ((static_cast<size_t>((c.vocab + 1) / 2) * 2 * 4 + 255) & ~static_cast<size_t>(255));
-      s->head_scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + off));
+      const MatShape h = matrix_shape(c, 4);   // the fp32 row scales follow the packed bytes (sd_pack_head)
+      s->head_scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + packed_fp8_weight_bytes(h.n_pairs, h.K)));
     }
   }
   s->head_stride = 0;

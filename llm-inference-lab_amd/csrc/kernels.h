@@ -112,11 +112,28 @@ struct GemvGeom {
   int grid, ppw, n_tiles, tile_pairs, ksplit, kw;
 };
 GemvGeom gemv_geometry(int n_pairs, int K);
+
+// ---- the model's matrices (pack.hip), in packing order: per layer qkv, out, gate / up, down; then the lm_head.
+// Matrix `index` = 4 * layer + which (which: 0 qkv, 1 out, 2 gate / up, 3 down); index 4 * n_layers (which 4) is the lm_head.
+struct MatShape {
+  int N, K, n_pairs, epi;   // rows, inputs, row pairs of the packed stream, GemvEpilogue
+};
+MatShape matrix_shape(const sd_model_config& c, int which);
+MatShape head_shape(int vocab, int d_model);   // a vocabulary-sized output matrix: the lm_head, a Medusa head
+inline int matrix_which(const sd_model_config& c, int index) { return index == 4 * c.n_layers ? 4 : index & 3; }
+struct MatWeights {
+  const void* w;        // bf16 HF-layout [N][K]
+  const void* bias;     // [N] or null
+  const void* norm_w;   // the normalisation fused in front of the product (qkv, gate / up, lm_head), else null
+  const void* norm_b;
+};
+MatWeights matrix_weights(const sd_model_config& c, int index);
+
 size_t packed_matrix_bytes(int n_pairs, int K);
+size_t packed_fp8_weight_bytes(int n_pairs, int K);                     // fp8: the packed bytes, before the row scales
 size_t packed_any_matrix_bytes(int n_pairs, int K, int weight_dtype);   // bf16 or fp8 (+ scales)
 int pack_one_matrix(const void* w_bf16, int N, int K, int n_pairs, int epi, int head_dim, int weight_dtype, void* dst, hipStream_t st);
-size_t packed_scale_offset(const sd_model_config& c, int index);  // fp8: row scales follow the packed bytes of a matrix
-size_t packed_offset(const sd_model_config& c, int index);  // index: 4*layer + {0 qkv,1 out,2 up,3 down}; 4*n_layers = lm_head
+size_t packed_offset(const sd_model_config& c, int index);  // byte offset of matrix `index` in the buffer of sd_pack_weights
 int gemv_grid(const GemvArgs& a, int* ppw_out);
 int gemv_max_tokens(int K);                                          // tokens gemv.hip can stage for rows of K elements (<= 9)
 int launch_gemv(const GemvArgs& a, int epi, hipStream_t st);          // T <= 9: gemv.hip, else gemm_skinny.hip

@@ -160,24 +160,29 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const uint16_t* __re
   }
 }
 
-// matrices of the model in packing order: per layer qkv, out, up, down; then lm_head
-struct MatDesc {
-  const void* w;
-  int N, K, n_pairs, epi;
-};
+// the model's matrices in packing order (kernels.h): the one place that knows their shapes
+MatShape head_shape(int vocab, int d_model) { return {vocab, d_model, (vocab + 1) / 2, EPI_ARGMAX}; }
 
-static void model_matrices(const sd_model_config& c, std::vector<MatDesc>& out) {
-  const bool llama = (c.arch == SD_ARCH_LLAMA);
-  const int d = c.d_model, Hq = c.n_heads, Hkv = c.n_kv_heads, D = c.head_dim, ff = c.d_ff;
-  for (int l = 0; l < c.n_layers; ++l) {
-    const sd_layer_weights& w = c.layers[l];
-    out.push_back({w.wqkv, (Hq + 2 * Hkv) * D, d, (Hq + 2 * Hkv) * D / 2, EPI_QKV_ROPE});
-    out.push_back({w.wo, d, Hq * D, d / 2, EPI_RESID});
-    if (llama) out.push_back({w.w_up, 2 * ff, d, ff, EPI_SWIGLU});
-    else out.push_back({w.w_up, ff, d, ff / 2, EPI_GELU});
-    out.push_back({w.w_down, d, ff, d / 2, EPI_RESID});
+MatShape matrix_shape(const sd_model_config& c, int which) {
+  const int d = c.d_model, HqD = c.n_heads * c.head_dim, Nqkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, ff = c.d_ff;
+  switch (which) {
+    case 0: return {Nqkv, d, Nqkv / 2, EPI_QKV_ROPE};
+    case 1: return {d, HqD, d / 2, EPI_RESID};
+    case 2: return c.arch == SD_ARCH_LLAMA ? MatShape{2 * ff, d, ff, EPI_SWIGLU} : MatShape{ff, d, ff / 2, EPI_GELU};
+    case 3: return {d, ff, d / 2, EPI_RESID};
+    default: return head_shape(c.vocab, d);
   }
-  out.push_back({c.lm_head, c.vocab, d, (c.vocab + 1) / 2, EPI_ARGMAX});
+}
+
+MatWeights matrix_weights(const sd_model_config& c, int index) {
+  if (index == 4 * c.n_layers) return {c.lm_head, nullptr, c.final_norm_w, c.final_norm_b};
+  const sd_layer_weights& w = c.layers[index >> 2];
+  switch (index & 3) {
+    case 0: return {w.wqkv, w.bqkv, w.attn_norm_w, w.attn_norm_b};
+    case 1: return {w.wo, w.bo, nullptr, nullptr};
+    case 2: return {w.w_up, w.b_up, w.mlp_norm_w, w.mlp_norm_b};
+    default: return {w.w_down, w.b_down, nullptr, nullptr};
+  }
 }
 
 size_t packed_matrix_bytes(int n_pairs, int K) {
@@ -193,24 +198,15 @@ size_t packed_fp8_weight_bytes(int n_pairs, int K) {
 static size_t packed_fp8_matrix_bytes(int n_pairs, int K) {
   return packed_fp8_weight_bytes(n_pairs, K) + ((static_cast<size_t>(n_pairs) * 2 * 4 + 255) & ~static_cast<size_t>(255));
 }
-static size_t matrix_bytes(const sd_model_config& c, const MatDesc& m) {
+static size_t matrix_bytes(const sd_model_config& c, int index) {
+  const MatShape m = matrix_shape(c, matrix_which(c, index));
   return c.weight_dtype == SD_FP8_E4M3 ? packed_fp8_matrix_bytes(m.n_pairs, m.K) : packed_matrix_bytes(m.n_pairs, m.K);
 }
 
-// byte offset of matrix `index` (same order as model_matrices) inside the packed buffer
 size_t packed_offset(const sd_model_config& c, int index) {
-  std::vector<MatDesc> mats;
-  model_matrices(c, mats);
   size_t off = 0;
-  for (int i = 0; i < index && i < static_cast<int>(mats.size()); ++i) off += matrix_bytes(c, mats[i]);
+  for (int i = 0; i < index && i <= 4 * c.n_layers; ++i) off += matrix_bytes(c, i);
   return off;
-}
-
-// offset of the fp32 row scales of matrix `index` from the start of its packed bytes
-size_t packed_scale_offset(const sd_model_config& c, int index) {
-  std::vector<MatDesc> mats;
-  model_matrices(c, mats);
-  return packed_fp8_weight_bytes(mats[index].n_pairs, mats[index].K);
 }
 
 size_t packed_any_matrix_bytes(int n_pairs, int K, int weight_dtype) {
@@ -240,7 +236,8 @@ using namespace sd;
 
 // A vocabulary-sized output matrix [V][d] outside a model (Medusa heads): same layout and quantiser as the lm_head.
 extern "C" size_t sd_packed_head_bytes(int vocab, int d_model, int weight_dtype) {
-  return packed_any_matrix_bytes((vocab + 1) / 2, d_model, weight_dtype);
+  const MatShape h = head_shape(vocab, d_model);
+  return packed_any_matrix_bytes(h.n_pairs, h.K, weight_dtype);
 }
 
 extern "C" int sd_pack_head(const void* w_bf16, int vocab, int d_model, int weight_dtype, void* dst, size_t dst_bytes, void* stream) {
@@ -248,45 +245,29 @@ extern "C" int sd_pack_head(const void* w_bf16, int vocab, int d_model, int weig
   SD_REQUIRE(weight_dtype == SD_BF16 || weight_dtype == SD_FP8_E4M3, "pack_head: weight_dtype %d", weight_dtype);
   SD_REQUIRE(dst_bytes >= sd_packed_head_bytes(vocab, d_model, weight_dtype), "pack_head: destination too small");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 255) == 0, "pack_head: destination must be 256-byte aligned");
-  return pack_one_matrix(w_bf16, vocab, d_model, (vocab + 1) / 2, EPI_ARGMAX, 0, weight_dtype, dst, static_cast<hipStream_t>(stream));
+  const MatShape h = head_shape(vocab, d_model);
+  return pack_one_matrix(w_bf16, h.N, h.K, h.n_pairs, h.epi, 0, weight_dtype, dst, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t sd_packed_bytes(const sd_model_config* cfg) {
   if (!cfg || !cfg->layers) return 0;
-  std::vector<MatDesc> mats;
-  model_matrices(*cfg, mats);
-  size_t n = 0;
-  for (const MatDesc& m : mats) n += matrix_bytes(*cfg, m);
-  return n;
+  return packed_offset(*cfg, 4 * cfg->n_layers + 1);
 }
 
 extern "C" int sd_pack_weights(const sd_model_config* cfg, void* dst, size_t dst_bytes, void* stream) {
   clear_error();
   SD_REQUIRE(cfg && cfg->layers && dst, "pack_weights: NULL argument");
   SD_REQUIRE(cfg->weight_dtype == SD_BF16 || cfg->weight_dtype == SD_FP8_E4M3, "pack_weights: weight_dtype %d (bf16 or fp8 e4m3)", cfg->weight_dtype);
-  const bool fp8 = cfg->weight_dtype == SD_FP8_E4M3;
   SD_REQUIRE(dst_bytes >= sd_packed_bytes(cfg), "pack_weights: destination too small");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 255) == 0, "pack_weights: destination must be 256-byte aligned");
-  std::vector<MatDesc> mats;
-  model_matrices(*cfg, mats);
-  hipStream_t st = static_cast<hipStream_t>(stream);
   char* p = static_cast<char*>(dst);
-  for (const MatDesc& m : mats) {
-    SD_REQUIRE(m.w, "pack_weights: NULL matrix");
+  for (int i = 0; i <= 4 * cfg->n_layers; ++i) {
+    const MatShape m = matrix_shape(*cfg, matrix_which(*cfg, i));
+    const void* w = matrix_weights(*cfg, i).w;
+    SD_REQUIRE(w, "pack_weights: NULL matrix");
     SD_REQUIRE(m.K % 8 == 0, "pack_weights: K=%d must be a multiple of 8", m.K);
-    const GemvGeom q = gemv_geometry(m.n_pairs, m.K);
-    PackJob j{static_cast<const uint16_t*>(m.w), reinterpret_cast<uint16_t*>(p), m.N, m.K, m.n_pairs, m.epi,
-              cfg->head_dim, q.ppw, q.tile_pairs};
-    if (fp8) {
-      float* scale = reinterpret_cast<float*>(p + packed_fp8_weight_bytes(m.n_pairs, m.K));
-      hipLaunchKernelGGL(row_scale_kernel, dim3(m.N), dim3(kWave), 0, st, static_cast<const uint16_t*>(m.w), m.N, m.K, scale);
-      SD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(pack_fp8_kernel, dim3(2048), dim3(256), 0, st, j, scale);
-    } else {
-      hipLaunchKernelGGL(pack_kernel, dim3(2048), dim3(256), 0, st, j);
-    }
-    SD_LAUNCH_CHECK();
-    p += matrix_bytes(*cfg, m);
+    if (int rc = pack_one_matrix(w, m.N, m.K, m.n_pairs, m.epi, cfg->head_dim, cfg->weight_dtype, p, static_cast<hipStream_t>(stream))) return rc;
+    p += matrix_bytes(*cfg, i);
   }
   return 0;
 }

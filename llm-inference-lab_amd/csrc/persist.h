@@ -6,7 +6,7 @@
 
 namespace sd {
 
-enum PersistKind { POP_QKV = 0, POP_OUT = 1, POP_GATEUP = 2, POP_DOWN = 3, POP_HEAD = 4 };
+enum PersistKind { POP_QKV = 0, POP_OUT = 1, POP_GATEUP = 2, POP_DOWN = 3, POP_HEAD = 4 };   // = matrix_which (kernels.h)
 
 // One matrix of the forward, in the order the weights are streamed (device array, read through the scalar cache).
 struct PersistOp {

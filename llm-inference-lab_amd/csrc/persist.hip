@@ -1350,14 +1350,15 @@ bool persist_model_ok(const sd_model_config& c, bool packed, bool w8, int n_cus)
     const sd_layer_weights& w = c.layers[l];
     if (w.bqkv || w.bo || w.b_up || w.b_down) return false;
   }
+  GemvGeom g[5];
+  for (int i = 0; i < 5; ++i) {
+    const MatShape sh = matrix_shape(c, i);
+    g[i] = gemv_geometry(sh.n_pairs, sh.K);
+    if (g[i].grid > kPersistCUs) return false;   // every matrix cut for <= 256 workgroups
+  }
   // QKV tiles (RoPE factors are staged per tile), even SwiGLU tiles (an activation granule holds two neighbouring pairs)
-  const GemvGeom gq = gemv_geometry((c.n_heads + 2 * c.n_kv_heads) * c.head_dim / 2, c.d_model);
-  if ((gq.ppw + gq.tile_pairs - 1) / gq.tile_pairs > kPersistMaxQkvTiles) return false;
-  const GemvGeom gu = gemv_geometry(c.d_ff, c.d_model);
-  if ((gu.ppw & 1) || (gu.tile_pairs & 1) || (c.d_ff & 1)) return false;
-  // every matrix cut for <= 256 workgroups
-  const GemvGeom go = gemv_geometry(c.d_model / 2, HqD), gd = gemv_geometry(c.d_model / 2, c.d_ff), gh = gemv_geometry((c.vocab + 1) / 2, c.d_model);
-  if (gq.grid > kPersistCUs || gu.grid > kPersistCUs || go.grid > kPersistCUs || gd.grid > kPersistCUs || gh.grid > kPersistCUs) return false;
+  if ((g[0].ppw + g[0].tile_pairs - 1) / g[0].tile_pairs > kPersistMaxQkvTiles) return false;
+  if ((g[2].ppw & 1) || (g[2].tile_pairs & 1) || (c.d_ff & 1)) return false;
   return persist_max_tokens(c) >= 1;
 }
 

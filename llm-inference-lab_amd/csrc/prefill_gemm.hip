@@ -242,9 +242,12 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
   SD_REQUIRE(!native || (m.packed && m.plan), "prefill: the native backend needs the packed weights");
   SD_REQUIRE(native || !paged, "prefill: the rocBLAS backend serves dense KV only");
   // one matrix product: Y[Mc][N] = X[Mc][K] x W^T (which: 0 qkv, 1 out, 2 gate / up, 3 down of layer l)
-  auto product = [&](int l, int which, const void* w_rows, const uint16_t* X, int N, int K, int ldx) -> int {
-    if (!native) return gemm_rows(w_rows, X, Y, Mc, N, K, ldx, st);
+  auto product = [&](int l, int which, const uint16_t* X, int ldx) -> int {
     const int index = 4 * l + which;
+    if (!native) {
+      const MatShape sh = matrix_shape(c, which);
+      return gemm_rows(matrix_weights(c, index).w, X, Y, Mc, sh.N, sh.K, ldx, st);
+    }
     const float* sc = m.scales ? m.scales[index] : nullptr;
     return launch_prefill_mfma(*m.plan, which, m.packed[index], sc, sc != nullptr, X, ldx, Y, Mc, st);
   };
@@ -265,19 +268,24 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     g.out_dtype = SD_BF16;
     g.block_table = bt;
     g.page_shift = m.page_shift;
+    // the epilogue of product `which`: its shape and bias, the rows it writes
+    auto epilogue_args = [&](int which, void* out, int out_stride) {
+      const MatShape sh = matrix_shape(c, which);
+      GemvArgs a = g;
+      a.N = sh.N;
+      a.K = sh.K;
+      a.n_pairs = sh.n_pairs;
+      a.bias = matrix_weights(c, 4 * l + which).bias;
+      a.out = out;
+      a.out_stride = out_stride;
+      return a;
+    };
 
     // 1. norm, QKV product, RoPE + q store + in-place K / V^T append
     hipLaunchKernelGGL(rms_rows_kernel, dim3(Mc), dim3(256), 0, st, x, d, static_cast<const uint16_t*>(w.attn_norm_w), c.norm_eps, d, xn);
     SD_LAUNCH_CHECK();
-    const int Nqkv = (Hq + 2 * Hkv) * D;
-    if (int rc = product(l, 0, w.wqkv, xn, Nqkv, d, d)) return rc;
-    GemvArgs a1 = g;
-    a1.N = Nqkv;
-    a1.K = d;
-    a1.n_pairs = Nqkv / 2;
-    a1.bias = w.bqkv;
-    a1.out = q;
-    a1.out_stride = HqD;
+    if (int rc = product(l, 0, xn, d)) return rc;
+    GemvArgs a1 = epilogue_args(0, q, HqD);
     a1.rope_cos = c.rope_cos;
     a1.rope_sin = c.rope_sin;
     a1.k_cache = kc;
@@ -309,39 +317,18 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     }
 
     // 3. output projection + residual
-    if (int rc = product(l, 1, w.wo, attn, d, HqD, HqD)) return rc;
-    GemvArgs a3 = g;
-    a3.N = d;
-    a3.K = HqD;
-    a3.n_pairs = d / 2;
-    a3.bias = w.bo;
-    a3.out = x;
-    a3.out_stride = d;
-    if (int rc = launch_epilogue_rows<EPI_RESID>(a3, Y, Mc, d * 2, st)) return rc;
+    if (int rc = product(l, 1, attn, HqD)) return rc;
+    if (int rc = launch_epilogue_rows<EPI_RESID>(epilogue_args(1, x, d), Y, Mc, d * 2, st)) return rc;
 
     // 4. norm, gate / up product, SwiGLU
     hipLaunchKernelGGL(rms_rows_kernel, dim3(Mc), dim3(256), 0, st, x, d, static_cast<const uint16_t*>(w.mlp_norm_w), c.norm_eps, d, xn);
     SD_LAUNCH_CHECK();
-    if (int rc = product(l, 2, w.w_up, xn, 2 * ff, d, d)) return rc;
-    GemvArgs a4 = g;
-    a4.N = 2 * ff;
-    a4.K = d;
-    a4.n_pairs = ff;
-    a4.bias = w.b_up;
-    a4.out = act;
-    a4.out_stride = ff;
-    if (int rc = launch_epilogue_rows<EPI_SWIGLU>(a4, Y, Mc, ff * 2, st)) return rc;
+    if (int rc = product(l, 2, xn, d)) return rc;
+    if (int rc = launch_epilogue_rows<EPI_SWIGLU>(epilogue_args(2, act, ff), Y, Mc, ff * 2, st)) return rc;
 
     // 5. down projection + residual
-    if (int rc = product(l, 3, w.w_down, act, d, ff, ff)) return rc;
-    GemvArgs a5 = g;
-    a5.N = d;
-    a5.K = ff;
-    a5.n_pairs = d / 2;
-    a5.bias = w.b_down;
-    a5.out = x;
-    a5.out_stride = d;
-    if (int rc = launch_epilogue_rows<EPI_RESID>(a5, Y, Mc, d * 2, st)) return rc;
+    if (int rc = product(l, 3, act, ff)) return rc;
+    if (int rc = launch_epilogue_rows<EPI_RESID>(epilogue_args(3, x, d), Y, Mc, d * 2, st)) return rc;
   }
   rows_out->x = x;
   rows_out->q = q;

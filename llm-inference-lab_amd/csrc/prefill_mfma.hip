@@ -48,14 +48,6 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_mfma_kernel(MfmaArgs a) {
   }
 }
 
-// the four matrix shapes of a layer, in packing order (model_matrices, csrc/pack.hip)
-void layer_shapes(const sd_model_config& c, int shp[][4]) {
-  const int d = c.d_model, HqD = c.n_heads * c.head_dim, Nqkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
-  const int v[4][4] = {{Nqkv, d, Nqkv / 2, EPI_QKV_ROPE}, {d, HqD, d / 2, EPI_RESID}, {2 * c.d_ff, d, c.d_ff, EPI_SWIGLU}, {d, c.d_ff, d / 2, EPI_RESID}};
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) shp[i][j] = v[i][j];
-}
-
 }  // namespace
 
 bool prefill_native_shapes_ok(const sd_model_config& c) {
@@ -67,17 +59,14 @@ bool prefill_native_shapes_ok(const sd_model_config& c) {
 int native_plan_build(const sd_model_config& c, NativePlan& plan) {
   SD_REQUIRE(c.d_model % 64 == 0, "prefill: the native GEMM needs d_model a multiple of 64 (got %d)", c.d_model);
   const bool layers = prefill_native_shapes_ok(c);
-  int shp[5][4];
-  layer_shapes(c, shp);
-  const int head[4] = {c.vocab, c.d_model, (c.vocab + 1) / 2, EPI_ARGMAX};
-  for (int j = 0; j < 4; ++j) shp[4][j] = head[j];
   std::vector<int4> tiles;
   std::vector<int2> blocks;
   struct Span { size_t tiles, blocks; int n_blocks; };
   Span spans[5][2] = {};
   for (int i = layers ? 0 : 4; i < 5; ++i) {
-    const int n_pairs = shp[i][2], K = shp[i][1];
-    const GemvGeom q = gemv_geometry(n_pairs, K);
+    const MatShape sh = matrix_shape(c, i);
+    const int n_pairs = sh.n_pairs;
+    const GemvGeom q = gemv_geometry(n_pairs, sh.K);
     std::vector<int2> raw;   // {first pair, pairs}
     for (int p_lo = 0; p_lo < n_pairs; p_lo += q.ppw) {
       const int p_hi = std::min(p_lo + q.ppw, n_pairs);
@@ -120,10 +109,11 @@ int native_plan_build(const sd_model_config& c, NativePlan& plan) {
       m.blocks = db + spans[i][v].blocks;
       m.n_blocks = spans[i][v].n_blocks;
       m.rb = v == 0 ? 128 : 64;
-      m.N = shp[i][0];
-      m.K = shp[i][1];
-      m.n_pairs = shp[i][2];
-      m.epi = shp[i][3];
+      const MatShape sh = matrix_shape(c, i);
+      m.N = sh.N;
+      m.K = sh.K;
+      m.n_pairs = sh.n_pairs;
+      m.epi = sh.epi;
     }
   plan.layers = layers;
   plan.head_dim = c.head_dim;
