@@ -94,6 +94,19 @@ int sd_sample_token(const void* logits, int logits_dtype, int64_t row_stride, in
                     int top_k, float top_p, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
                     const int32_t* stream_id, int32_t* out_ids, void* stream);
 
+/* Steps 3 and 4 of speculative sampling (sd_specdec_set_spec_sampling) on caller tensors: draft_logits [B][K][V] and
+ * target_logits [B][K+1][V], bf16 contiguous; draft_ids [B][K] int32 (the tokens drawn from q_i; clamped to [0, V)).
+ * Draw counter of row b = draw_counters[b] (then advanced by K + 1) or draw0 when draw_counters is NULL; rows with
+ * active[b] == 0 (nullable) are skipped: accept_len_out[b] = 0, nothing else written, no draws consumed. Outputs:
+ * accept_len_out [B], next_tok_out [B], ratios_out (nullable, float64 [B][K]: ratio_i of every position, NaN for a
+ * non-finite position). K in 1..63. workspace: sd_spec_sample_workspace(B, K) bytes of device scratch.
+ * Asynchronous on `stream`, no allocation, graph-capturable. */
+size_t sd_spec_sample_workspace(int B, int K);
+int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K, int V,
+                          float temperature, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
+                          const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
+                          double* ratios_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * kv_append (in place) — the KV-append path
  *   reference contract: kv_append_ref, src/kernels/reference.py:59-93
@@ -425,6 +438,29 @@ int sd_specdec_set_row(sd_specdec* s, int b, int seq_len, int prev_tok, int last
 int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperature, int top_k, float top_p,
                             uint64_t seed, void* logits_buf, size_t logits_bytes,
                             uint32_t* draw_counters, const int32_t* stream_ids);
+
+/* Speculative sampling inside the step (opt-in; generate_batch with policy="rejection", backend="device"): the third mode
+ * of the step next to greedy and sampled-bonus. Per row b and step, T = temperature > 0, every distribution is
+ * softmax(x / T) over the STORED bf16 logits in float64, c = draw_counters[b] at the start of the step, sid = stream_ids[b]
+ * or b, Philox4x32-10 keyed by seed:
+ *   1. draft forward i (i = 0..K-1) stores its last position's logits as row q_i of draft_logits_buf ([B][K][V] bf16);
+ *      d_{i+1} = Gumbel-max draw over q_i / T, counter (c + i, sid, element, Gumbel tag) — sd_sample_token's whole-row draw;
+ *   2. the verify forward stores p_0..p_K in target_logits_buf ([B][K+1][V] bf16; until then its first rows are scratch
+ *      for the draft forwards' logits);
+ *   3. u_i = the uniform of counter (c + i, sid, 0, CDF tag); ratio_i = exp((p_i[d]/T - lse(p_i/T)) - (q_i[d]/T - lse(q_i/T)))
+ *      with d = d_{i+1}; accept length a = number of leading i with u_i < ratio_i;
+ *   4. next token: a < K: Gumbel-max over log max(0, softmax(p_a/T) - softmax(q_a/T)) on its support (empty support, q == p:
+ *      over p_a / T); a == K: Gumbel-max over p_K / T; counter (c + K, sid, element, Gumbel tag);
+ *   5. emitted: d_1..d_a + the next token (the accepted tokens are the DRAFT's ids; the record's target-argmax slots keep the
+ *      target's argmax); draw_counters[b] += K + 1; rows with active == 0 consume no draws.
+ * The emitted sequence is distributed as sampling from softmax(target bf16 logits / T), whatever the draft is. Non-finite
+ * logits: a position whose p or q row holds a NaN or has a non-finite maximum is rejected and redrawn from p_i / T alone
+ * (NaN-first ordering of sd_sample_token). Refused: SD_EMIT_DRAFT, loops without a draft model (self-draft, Medusa heads,
+ * EAGLE), adaptive K, the sampled-bonus mode being on, temperature <= 0 or NaN, short or misaligned (16 B) buffers; top-k /
+ * top-p shaping of p and q is not part of the mode. Both calls (enable / disable) drop the captured graph. */
+int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float temperature, uint64_t seed, void* draft_logits_buf,
+                                 size_t draft_logits_bytes, void* target_logits_buf, size_t target_logits_bytes,
+                                 uint32_t* draw_counters, const int32_t* stream_ids);
 
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,

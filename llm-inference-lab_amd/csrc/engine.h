@@ -61,4 +61,11 @@ struct SampleArgs;
 int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
                        uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st);
 
+
+// csrc/spec_sample.hip: speculative sampling inside the step
+int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
+                           float temperature, uint64_t seed, const uint32_t* draw, const int32_t* stream_id, hipStream_t st);
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
+                     uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
+
 }  // namespace sd

@@ -1060,6 +1060,13 @@ struct sd_specdec {
   void* logits = nullptr;          // [B][K+1][V] bf16
   uint32_t* draw = nullptr;        // [B]
   const int32_t* stream_id = nullptr;
+  // speculative sampling (sd_specdec_set_spec_sampling): draft tokens drawn from q, accept by p/q, residual redraw. Shares
+  // temperature / seed / draw / stream_id with the sampled-bonus mode (the two are mutually exclusive).
+  int spec = 0;
+  void* spec_q = nullptr;          // [B][K][V] bf16 draft logits, caller-owned
+  void* spec_p = nullptr;          // [B][K+1][V] bf16 target logits, caller-owned; until the verify forward overwrites it, its first
+                                   // rows are where each draft forward leaves the logits of its pass ([B][M][V])
+  int32_t* spec_flags = nullptr;   // [2][B][K+1] device: accept flags, candidate next tokens
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -1170,7 +1177,11 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
       return launch_draft_finalize(s->draft->part_val, s->draft->part_idx, s->draft->head_grid, M, i, ids, s->st, skip_k, skip_i, st_d);
     return 0;
   };
-  int32_t* const ids_d = one_pass_d ? nullptr : s->st.draft_ids;
+  // speculative sampling: every draft forward stores its logits, d_{i+1} is DRAWN from the last position's row (no argmax ids)
+  const bool spec = s->spec != 0;
+  const int V = s->target->cfg.vocab;
+  uint16_t* const q_pass = spec ? static_cast<uint16_t*>(s->spec_p) : nullptr;
+  int32_t* const ids_d = (one_pass_d || spec) ? nullptr : s->st.draft_ids;
   for (int i = 0; s->draft && i < K; ++i) {
     const int M = (i == 0) ? 2 : 1;
     const int32_t* toks = (i == 0) ? s->st.tok2 : s->st.next_tok;
@@ -1184,21 +1195,26 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
       // 1-token pass over `last` alone, whose id lands where the 2-token pass leaves its second one
       s->draft->skip_k = s->st.fwd0_w;
       s->draft->skip_i = 1;
-      rc_f = model_forward(s->draft, toks, 2, s->st.cur_len, -1, 0, B, 2, ids_d, 2, nullptr, SD_BF16, 0, st_d);
-      if (!rc_f) rc_f = finalize(2, 0, s->st.draft_ids, s->st.fwd0_w, 1);
+      rc_f = model_forward(s->draft, toks, 2, s->st.cur_len, -1, 0, B, 2, ids_d, 2, q_pass, SD_BF16, 0, st_d);
+      if (!rc_f && !spec) rc_f = finalize(2, 0, s->st.draft_ids, s->st.fwd0_w, 1);
       if (!rc_f) {
         s->draft->skip_k = s->st.fwd0_w + 1;
-        rc_f = model_forward(s->draft, toks + 1, 2, s->st.cur_len, 0, 0, B, 1, ids_d ? ids_d + 1 : nullptr, 2, nullptr, SD_BF16, 0, st_d);
+        // (the 1-token form's logits row lands where the 2-token form leaves its second one, as its id does)
+        rc_f = model_forward(s->draft, toks + 1, 2, s->st.cur_len, 0, 0, B, 1, ids_d ? ids_d + 1 : nullptr, 2, spec ? q_pass + V : nullptr,
+                             SD_BF16, 0, st_d);
       }
-      if (!rc_f) rc_f = finalize(1, 0, s->st.draft_ids + 1, s->st.fwd0_w + 1, 1);
+      if (!rc_f && !spec) rc_f = finalize(1, 0, s->st.draft_ids + 1, s->st.fwd0_w + 1, 1);
     } else {
-      rc_f = model_forward(s->draft, toks, M, s->st.cur_len, off, 0, B, M, ids_d, 2, nullptr, SD_BF16, 0, st_d);
-      if (!rc_f) rc_f = finalize(M, i, s->st.draft_ids, s->draft->skip_k, i);
+      rc_f = model_forward(s->draft, toks, M, s->st.cur_len, off, 0, B, M, ids_d, 2, q_pass, SD_BF16, 0, st_d);
+      if (!rc_f && !spec) rc_f = finalize(M, i, s->st.draft_ids, s->draft->skip_k, i);
     }
     s->draft->skip_k = nullptr;
     if (rc_f) return rc_f;
-    if (!one_pass_d)
+    if (spec) {   // exactly one form of forward 0 ran: one draw launch serves both
+      if (int rc = launch_spec_draft_draw(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->seed, s->draw, s->stream_id, st_d)) return rc;
+    } else if (!one_pass_d) {
       if (int rc = launch_draft_next(M, i, s->st, st_d)) return rc;
+    }
   }
   if (two) {
     SD_HIP_CHECK(hipEventRecord(s->ev_join, st_d));
@@ -1209,9 +1225,9 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
   // lm_head's partials (verify_tail_kernel) instead of three
   const unsigned* const st_word_d = (s->draft && s->draft->p_sync) ? s->draft->p_sync + 1 : nullptr;
   const unsigned* const st_word_t = s->target->p_sync ? s->target->p_sync + 1 : nullptr;
-  const bool tail = !s->sample && verify_tail_fits(s->st) && B * (K + 1) <= s->target->max_t;
+  const bool tail = !s->sample && !spec && verify_tail_fits(s->st) && B * (K + 1) <= s->target->max_t;
   if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, K + 1, tail ? nullptr : s->st.target_ids,
-                             K + 1, s->sample ? s->logits : nullptr, SD_BF16, 0, st_t))
+                             K + 1, s->sample ? s->logits : (spec ? s->spec_p : nullptr), SD_BF16, 0, st_t))
     return rc;
   if (tail) {
     if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
@@ -1228,7 +1244,13 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
                                     s->draw, s->stream_id, st_t))
       return rc;
   }
-  if (int rc = launch_accept(s->st, s->mode, s->sample, st_t)) return rc;
+  if (spec) {
+    // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
+    if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, s->seed, s->draw, s->stream_id, s->spec_flags,
+                                  s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
+      return rc;
+  }
+  if (int rc = launch_accept(s->st, s->mode, spec ? 2 : s->sample, st_t)) return rc;
   if (int rc = launch_pack_record(s->st, s->host_record, s->rec, s->step_counter, st_word_d, st_word_t, st_t)) return rc;
   // persistent Medusa heads: the proposals of the next step, after the record of this one has left
   if (!s->heads.empty())
@@ -1324,6 +1346,7 @@ extern "C" int sd_specdec_destroy(sd_specdec* s) {
   if (s->host_stage) (void)hipHostFree(s->host_stage);
   if (s->dev_block) (void)hipFree(s->dev_block);
   if (s->head_rows) (void)hipFree(s->head_rows);
+  if (s->spec_flags) (void)hipFree(s->spec_flags);
   delete s;
   return 0;
 }
@@ -1378,6 +1401,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(step_size >= 1, "specdec_set_adaptive: step_size %d", step_size);
   SD_REQUIRE(target_rate == target_rate, "specdec_set_adaptive: target rate is NaN");
   SD_REQUIRE(s->heads.empty() && !s->eagle, "specdec_set_adaptive: stateful draft modes keep a fixed K");
+  SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -1434,6 +1458,7 @@ extern "C" int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperat
     return 0;
   }
   SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_sampling: only the bonus-token emit mode (generate_batch) samples");
+  SD_REQUIRE(!s->spec, "specdec_set_sampling: speculative sampling is enabled (sd_specdec_set_spec_sampling); the two modes are mutually exclusive");
   SD_REQUIRE(logits_buf && draw_counters, "specdec_set_sampling: NULL logits buffer / draw counters");
   const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * s->target->cfg.vocab * 2;
   SD_REQUIRE(logits_bytes >= need, "specdec_set_sampling: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need);
@@ -1445,6 +1470,50 @@ extern "C" int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperat
   s->top_p = top_p;
   s->seed = seed;
   s->logits = logits_buf;
+  s->draw = draw_counters;
+  s->stream_id = stream_ids;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float temperature, uint64_t seed, void* draft_logits_buf,
+                                            size_t draft_logits_bytes, void* target_logits_buf, size_t target_logits_bytes,
+                                            uint32_t* draw_counters, const int32_t* stream_ids) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_spec_sampling: NULL");
+  if (!enable) {
+    if (s->spec && s->exec) {
+      (void)hipGraphExecDestroy(s->exec);
+      (void)hipGraphDestroy(s->graph);
+      s->exec = nullptr;
+      s->graph = nullptr;
+    }
+    s->spec = 0;
+    return 0;
+  }
+  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_spec_sampling: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
+  SD_REQUIRE(s->draft, "specdec_set_spec_sampling: needs a draft model (self-draft, Medusa heads and EAGLE loops propose without a distribution q)");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_spec_sampling: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->sample, "specdec_set_spec_sampling: the sampled-bonus mode is enabled (sd_specdec_set_sampling); the two modes are mutually exclusive");
+  SD_REQUIRE(temperature == temperature && temperature > 0.f, "specdec_set_spec_sampling: temperature %g (must be > 0)", temperature);
+  SD_REQUIRE(draft_logits_buf && target_logits_buf && draw_counters, "specdec_set_spec_sampling: NULL logits buffer / draw counters");
+  const size_t V = static_cast<size_t>(s->target->cfg.vocab);
+  const size_t need_q = static_cast<size_t>(s->B) * s->K * V * 2, need_p = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
+  SD_REQUIRE(draft_logits_bytes >= need_q, "specdec_set_spec_sampling: draft logits buffer %zu B < %zu B ([B][K][V] bf16)", draft_logits_bytes, need_q);
+  SD_REQUIRE(target_logits_bytes >= need_p, "specdec_set_spec_sampling: target logits buffer %zu B < %zu B ([B][K+1][V] bf16)", target_logits_bytes, need_p);
+  SD_REQUIRE(((reinterpret_cast<uintptr_t>(draft_logits_buf) | reinterpret_cast<uintptr_t>(target_logits_buf)) & 15) == 0,
+             "specdec_set_spec_sampling: logits buffers must be 16-byte aligned");
+  if (!s->spec_flags) SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->spec_flags), sizeof(int32_t) * 2 * s->B * (s->K + 1)));
+  if (s->exec) {  // the captured step holds the other mode's launches, or this mode's parameters
+    (void)hipGraphExecDestroy(s->exec);
+    (void)hipGraphDestroy(s->graph);
+    s->exec = nullptr;
+    s->graph = nullptr;
+  }
+  s->spec = 1;
+  s->temperature = temperature;
+  s->seed = seed;
+  s->spec_q = draft_logits_buf;
+  s->spec_p = target_logits_buf;
   s->draw = draw_counters;
   s->stream_id = stream_ids;
   return 0;

@@ -333,7 +333,10 @@ __global__ __launch_bounds__(kWave) void accept_len_kernel(SpecState s) {
 // one wave, one row: my_t = the target's id at verify position `lane` (lanes 0..K)
 __device__ __forceinline__ void accept_row(const SpecState& s, int b, int lane, int my_t, int mode, int use_sampled) {
   const int K = s.K, M = K + 1;
-  const int a = accept_scan(s, b, lane, my_t);
+  // use_sampled == 2 (speculative sampling, csrc/spec_sample.hip): the accept length is given, the accepted tokens are the
+  // DRAFT's ids (under greedy they equal the target's), the token after them is the redrawn / bonus token in s.sampled
+  const int a = use_sampled == 2 ? s.accept_len[b] : accept_scan(s, b, lane, my_t);
+  if (use_sampled == 2 && lane < a) my_t = s.draft_tok[b * K + lane];
   // sampled bonus token (pipeline.py:3140-3160 / :3351-3361): the token after the accepted prefix
   // is drawn from the target distribution at that position instead of its argmax
   if (use_sampled && lane == a && s.active[b]) my_t = s.sampled[b];

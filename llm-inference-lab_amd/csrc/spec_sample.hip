@@ -1,0 +1,389 @@
+// Speculative sampling inside the step: the draft's tokens are DRAWN from the draft's distribution, the target accepts
+// d_{i+1} with probability min(1, p_i(d_{i+1}) / q_i(d_{i+1})), the first rejected position is redrawn from
+// normalise(max(0, p - q)) and a full acceptance draws the bonus token from p_K (Leviathan et al. 2023, Chen et al. 2023).
+// The emitted sequence is then distributed exactly as sampling from softmax(target bf16 logits / T), whatever the draft is.
+//
+// All distributions are softmax(x / T) over the STORED bf16 logits of the respective forward, in float64 (x / T with T the
+// float32 temperature widened to double; no division when T == 1, as csrc/sample.hip). Draw schedule of row b in a step
+// that starts with draw counter c (Philox4x32-10, key = seed, stream sid = stream_ids[b] or b), restated on the CPU in
+// tests/spec_sample_ref.py:
+//   d_{i+1}, i = 0..K-1 : Gumbel-max over q_i / T, counter (c + i, sid, element, kTagGumbel)   (= sample_gumbel_kernel)
+//   u_i,     i = 0..K-1 : counter (c + i, sid, 0, kTagCdf), u = r0 * 2^-32                       (= draw_uniform)
+//   next token          : Gumbel-max over log-weights, counter (c + K, sid, element, kTagGumbel)
+//   the row's counter advances by K + 1; rows with active[b] == 0 consume nothing.
+// The three kinds are independent: different tags (uniform / Gumbel) or different counters (c + i, i < K / c + K).
+//   ratio_i = exp((p_i[d]/T - lse(p_i/T)) - (q_i[d]/T - lse(q_i/T))),  lse(v) = max v + log(sum exp(v - max v))
+//   a       = number of leading i with u_i < ratio_i
+//   next    = a < K: Gumbel-max over log(r_v), r_v = exp(p_a[v]/T - lse p) - exp(q_a[v]/T - lse q), over the v with r_v > 0
+//                    (no such v — q == p: over p_a[v]/T);  a == K: Gumbel-max over p_K[v]/T.
+// The sums of the two log-sum-exps are the only order-dependent quantities; p and q of a position go through the same
+// code in the same order, so bitwise equal rows give ratio exactly 1 and an all-zero residual.
+// Non-finite logits: a position whose p or q row holds a NaN, or whose row maximum is not finite (+inf present, or every
+// entry -inf), is REJECTED (ratio = NaN) and its candidate is the plain Gumbel-max over p_i / T with the ordering of
+// sample_gumbel_kernel (NaN scores first, then value, then lowest index). -inf entries of otherwise finite rows have
+// probability 0 on either side.
+//
+// Three kernels, ordinary stream order between them, no allocation, graph-capturable:
+//   spec_draft_draw_kernel  one 1024-thread workgroup per row: reads the logits row the draft's lm_head has just stored,
+//                           keeps it as row q_i of the [B][K][V] buffer, draws d_{i+1}, hands it to the next draft
+//                           forward and to the verify input (the sampled counterpart of draft_finalize_kernel)
+//   spec_stats_kernel       grid (K+1, B): position i of row b, independent of the accept length — the two log-sum-exps,
+//                           ratio_i and the flag u_i < ratio_i, then the candidate next token of position i
+//   spec_accept_kernel      one wave per row: accept length = leading flags, next token = candidate of that position
+
+#include "engine.h"
+#include "sample_device.h"
+
+namespace sd {
+
+constexpr int kSpecWaves = kSampleThreads / kWave;
+
+__device__ __forceinline__ double gumbel_noise(uint32_t c, uint32_t sid, int i, uint32_t seed_lo, uint32_t seed_hi) {
+  uint32_t r0;
+  philox4x32_10(c, sid, static_cast<uint32_t>(i), kTagGumbel, seed_lo, seed_hi, r0);
+  const double u = (static_cast<double>(r0) + 0.5) * 2.3283064365386963e-10;  // 2^-32
+  return -log(-log(u));
+}
+
+// f(p value, q value, index) over two bf16 rows of V elements, 16-byte loads when both allow it
+template <typename F>
+__device__ __forceinline__ void for_each_pair(const uint16_t* rp, const uint16_t* rq, int V, int tid, F&& f) {
+  const bool aligned = ((reinterpret_cast<uintptr_t>(rp) | reinterpret_cast<uintptr_t>(rq)) & 15) == 0;
+  if (aligned && (V & 7) == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(rp);
+    const uint4* q = reinterpret_cast<const uint4*>(rq);
+    for (int v = tid; v < (V >> 3); v += kSampleThreads) {
+      const uint4 a = p[v], b = q[v];
+      const uint32_t wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        f(__uint_as_float(wa[j] << 16), __uint_as_float(wb[j] << 16), 8 * v + 2 * j);
+        f(__uint_as_float(wa[j] & 0xffff0000u), __uint_as_float(wb[j] & 0xffff0000u), 8 * v + 2 * j + 1);
+      }
+    }
+  } else {
+    for (int i = tid; i < V; i += kSampleThreads) f(bf16_bits_to_float(rp[i]), bf16_bits_to_float(rq[i]), i);
+  }
+}
+
+// workgroup-wide reductions; every thread gets the result. Fixed order: xor tree inside a wave, then the waves in order.
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < kSpecWaves; ++w) r += sh[w];
+  return r;
+}
+
+__device__ __forceinline__ double block_max(double v, double* sh) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < kSpecWaves; ++w) r = fmax(r, sh[w]);
+  return r;
+}
+
+// best (score, index) of the workgroup under better_d; valid in thread 0
+__device__ __forceinline__ void block_best(double& bv, int& bi, double* sv, int* si) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(bv, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (better_d(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kSpecWaves; ++w)
+      if (better_d(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+}
+
+__device__ __forceinline__ bool is_finite_d(double v) { return v - v == 0.0; }
+
+// ---------------------------------------------------------------------------------------------- draft draw + hand-over
+struct SpecDrawArgs {
+  const uint16_t* src;   // logits rows of the draft forward just run: entry b's row is b * src_rows_per_b + src_row
+  int src_rows_per_b, src_row;
+  uint16_t* q;           // [B][K][V]: row (b, i) receives a copy
+  int i, V;
+  float temperature;
+  uint32_t seed_lo, seed_hi;
+  const uint32_t* draw;  // [B] counters at the start of the step (read only here)
+  const int32_t* stream_id;
+};
+
+__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const SpecDrawArgs a, SpecState s) {
+  __shared__ double sv[kSpecWaves];
+  __shared__ int si[kSpecWaves];
+  const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+  const uint16_t* src = a.src + (static_cast<size_t>(b) * a.src_rows_per_b + a.src_row) * V;
+  uint16_t* dst = a.q + (static_cast<size_t>(b) * s.K + a.i) * V;
+  const double T = static_cast<double>(a.temperature);
+  const bool scale = a.temperature != 1.0f;
+  const uint32_t c = a.draw[b] + static_cast<uint32_t>(a.i);
+  const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
+  double bv = -INFINITY;
+  int bi = 0x7fffffff;
+  auto visit = [&](float x, int i) {
+    double v = static_cast<double>(x);
+    if (scale) v = v / T;
+    const double sc = v + gumbel_noise(c, sid, i, a.seed_lo, a.seed_hi);
+    if (better_d(sc, i, bv, bi)) { bv = sc; bi = i; }
+  };
+  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  if (aligned && (V & 7) == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(src);
+    uint4* o = reinterpret_cast<uint4*>(dst);
+    for (int v = tid; v < (V >> 3); v += kSampleThreads) {
+      const uint4 w4 = p[v];
+      o[v] = w4;
+      const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        visit(__uint_as_float(w[j] << 16), 8 * v + 2 * j);
+        visit(__uint_as_float(w[j] & 0xffff0000u), 8 * v + 2 * j + 1);
+      }
+    }
+  } else {
+    for (int i = tid; i < V; i += kSampleThreads) {
+      const uint16_t w = src[i];
+      dst[i] = w;
+      visit(bf16_bits_to_float(w), i);
+    }
+  }
+  block_best(bv, bi, sv, si);
+  if (tid == 0) {
+    const int d = bi;   // always a valid index: V >= 1 and the first element visited beats the initial (-inf, INT_MAX)
+    s.draft_tok[b * s.K + a.i] = d;
+    s.verify_tok[b * (s.K + 1) + a.i + 1] = d;
+    s.next_tok[b] = d;
+  }
+}
+
+int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
+                           float temperature, uint64_t seed, const uint32_t* draw, const int32_t* stream_id, hipStream_t st) {
+  SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
+  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
+             "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+  SpecDrawArgs a{};
+  a.src = static_cast<const uint16_t*>(src);
+  a.src_rows_per_b = src_rows_per_b;
+  a.src_row = src_row;
+  a.q = static_cast<uint16_t*>(q);
+  a.i = i;
+  a.V = V;
+  a.temperature = temperature;
+  a.seed_lo = static_cast<uint32_t>(seed);
+  a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.draw = draw;
+  a.stream_id = stream_id;
+  hipLaunchKernelGGL(spec_draft_draw_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, s);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------- per-position statistics and candidate
+struct SpecStatArgs {
+  const uint16_t* P;          // [B][K+1][V] target logits
+  const uint16_t* Q;          // [B][K][V] draft logits
+  const int32_t* draft_ids;   // [B][K]
+  int K, V;
+  float temperature;
+  uint32_t seed_lo, seed_hi;
+  const uint32_t* draw;       // nullable: [B] counters at the start of the step
+  uint32_t draw0;
+  const int32_t* stream_id;
+  const int32_t* active;
+  int32_t* flag;              // [B][K+1] (slot K unused)
+  int32_t* cand;              // [B][K+1]
+  double* ratios;             // nullable [B][K]
+};
+
+__global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecStatArgs a) {
+  __shared__ double sh[kSpecWaves];
+  __shared__ double sv[kSpecWaves];
+  __shared__ int si[kSpecWaves];
+  const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, K = a.K, V = a.V;
+  if (a.active && a.active[b] == 0) return;
+  const uint16_t* rp = a.P + (static_cast<size_t>(b) * (K + 1) + i) * V;
+  const uint16_t* rq = i < K ? a.Q + (static_cast<size_t>(b) * K + i) * V : rp;   // position K has no q row
+  const double T = static_cast<double>(a.temperature);
+  const bool scale = a.temperature != 1.0f;
+  const uint32_t c0 = a.draw ? a.draw[b] : a.draw0;
+  const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
+  auto scaled = [&](float x) {
+    const double v = static_cast<double>(x);
+    return scale ? v / T : v;
+  };
+
+  // ---- pass 1: maxima and log-sum-exps of both rows, the ratio, the flag
+  bool residual = false;
+  double lse_p = 0.0, lse_q = 0.0;
+  if (i < K) {
+    double mp = -INFINITY, mq = -INFINITY;
+    int nan = 0;
+    for_each_pair(rp, rq, V, tid, [&](float xp, float xq, int) {
+      const double vp = scaled(xp), vq = scaled(xq);
+      nan |= (vp != vp) | (vq != vq);
+      mp = fmax(mp, vp);
+      mq = fmax(mq, vq);
+    });
+    mp = block_max(mp, sh);
+    mq = block_max(mq, sh);
+    const bool bad = __syncthreads_or(nan) || !is_finite_d(mp) || !is_finite_d(mq);
+    if (!bad) {
+      double sp = 0.0, sq = 0.0;
+      for_each_pair(rp, rq, V, tid, [&](float xp, float xq, int) {
+        sp += exp(scaled(xp) - mp);
+        sq += exp(scaled(xq) - mq);
+      });
+      sp = block_sum(sp, sh);
+      sq = block_sum(sq, sh);
+      lse_p = mp + log(sp);
+      lse_q = mq + log(sq);
+      residual = true;
+    }
+    if (tid == 0) {
+      int d = a.draft_ids[b * K + i];
+      d = d < 0 ? 0 : (d >= V ? V - 1 : d);
+      double ratio = NAN;
+      if (!bad) ratio = exp((scaled(bf16_bits_to_float(rp[d])) - lse_p) - (scaled(bf16_bits_to_float(rq[d])) - lse_q));
+      uint32_t r0;
+      philox4x32_10(c0 + static_cast<uint32_t>(i), sid, 0u, kTagCdf, a.seed_lo, a.seed_hi, r0);
+      const double u = static_cast<double>(r0) * 2.3283064365386963e-10;  // 2^-32
+      a.flag[b * (K + 1) + i] = (u < ratio) ? 1 : 0;
+      if (a.ratios) a.ratios[b * K + i] = ratio;
+    }
+  }
+
+  // ---- pass 2: the candidate next token of this position
+  const uint32_t cn = c0 + static_cast<uint32_t>(K);
+  double rv = -INFINITY, pv = -INFINITY;
+  int ri = 0x7fffffff, pi = 0x7fffffff;
+  for_each_pair(rp, rq, V, tid, [&](float xp, float xq, int idx) {
+    const double vp = scaled(xp);
+    const double g = gumbel_noise(cn, sid, idx, a.seed_lo, a.seed_hi);
+    const double s_p = vp + g;
+    if (better_d(s_p, idx, pv, pi)) { pv = s_p; pi = idx; }
+    if (residual) {
+      const double r = exp(vp - lse_p) - exp(scaled(xq) - lse_q);
+      if (r > 0.0) {
+        const double s_r = log(r) + g;
+        if (better_d(s_r, idx, rv, ri)) { rv = s_r; ri = idx; }
+      }
+    }
+  });
+  block_best(pv, pi, sv, si);
+  if (residual) block_best(rv, ri, sv, si);   // (workgroup-uniform)
+  if (tid == 0) a.cand[b * (K + 1) + i] = (residual && ri != 0x7fffffff) ? ri : pi;
+}
+
+// ------------------------------------------------------------------------------------------------------------- accept
+struct SpecAcceptArgs {
+  const int32_t* flag;
+  const int32_t* cand;
+  int K;
+  const int32_t* active;
+  uint32_t* draw;          // nullable: advanced by K + 1 for active rows
+  int32_t* accept_len;     // [B]
+  int32_t* next_tok;       // [B]
+};
+
+__global__ __launch_bounds__(kWave) void spec_accept_kernel(const SpecAcceptArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, K = a.K;
+  if (a.active && a.active[b] == 0) {   // the row's step does not count: nothing accepted, nothing drawn
+    if (lane == 0) a.accept_len[b] = 0;
+    return;
+  }
+  const bool ok = (lane < K) && a.flag[b * (K + 1) + lane] != 0;
+  const unsigned long long m64 = __ballot(ok);
+  const unsigned long long valid = (1ull << K) - 1ull;
+  const unsigned long long miss = (~m64) & valid;
+  const int acc = miss ? __builtin_ctzll(miss) : K;
+  if (lane == 0) {
+    a.accept_len[b] = acc;
+    a.next_tok[b] = a.cand[b * (K + 1) + acc];
+    if (a.draw) a.draw[b] = a.draw[b] + static_cast<uint32_t>(K + 1);
+  }
+}
+
+static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, hipStream_t st) {
+  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1, "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+  SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
+  hipLaunchKernelGGL(spec_stats_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa);
+  SD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+// the step's statistics + accept: accept length -> s.accept_len, next token -> s.sampled, counters advanced
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
+                     uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st) {
+  SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
+  SpecStatArgs sa{};
+  sa.P = static_cast<const uint16_t*>(target_logits);
+  sa.Q = static_cast<const uint16_t*>(draft_logits);
+  sa.draft_ids = s.draft_tok;
+  sa.K = s.K;
+  sa.V = V;
+  sa.temperature = temperature;
+  sa.seed_lo = static_cast<uint32_t>(seed);
+  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
+  sa.draw = draw;
+  sa.stream_id = stream_id;
+  sa.active = s.active;
+  sa.flag = flag;
+  sa.cand = cand;
+  SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
+  return launch_spec_kernels(sa, aa, s.B, st);
+}
+
+}  // namespace sd
+
+using namespace sd;
+
+extern "C" size_t sd_spec_sample_workspace(int B, int K) {
+  if (B <= 0 || K <= 0) return 0;
+  return static_cast<size_t>(B) * (K + 1) * 2 * sizeof(int32_t);
+}
+
+extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
+                                     int V, float temperature, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
+                                     const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
+                                     double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "spec_sample_accept: NULL argument");
+  SD_REQUIRE(B >= 1 && K >= 1, "spec_sample_accept: B=%d K=%d", B, K);
+  SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "spec_sample_accept: workspace %zu B < %zu B", workspace_bytes,
+             sd_spec_sample_workspace(B, K));
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && (!ratios_out || (reinterpret_cast<uintptr_t>(ratios_out) & 7) == 0),
+             "spec_sample_accept: misaligned workspace / ratios");
+  int32_t* flag = static_cast<int32_t*>(workspace);
+  int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
+  SpecStatArgs sa{};
+  sa.P = static_cast<const uint16_t*>(target_logits);
+  sa.Q = static_cast<const uint16_t*>(draft_logits);
+  sa.draft_ids = draft_ids;
+  sa.K = K;
+  sa.V = V;
+  sa.temperature = temperature;
+  sa.seed_lo = static_cast<uint32_t>(seed);
+  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
+  sa.draw = draw_counters;
+  sa.draw0 = draw0;
+  sa.stream_id = stream_ids;
+  sa.active = active;
+  sa.flag = flag;
+  sa.cand = cand;
+  sa.ratios = ratios_out;
+  SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
+  return launch_spec_kernels(sa, aa, B, static_cast<hipStream_t>(stream));
+}

@@ -448,6 +448,9 @@ class HipSpecDec:
         with torch.cuda.device(self.device):
             self.stream_t = torch.cuda.Stream(self.device)
             self.stream_d = torch.cuda.Stream(self.device)
+        # sampling modes (set_sampling / set_spec_sampling): off; their buffers are allocated at first use and kept
+        self.sampling = self.spec_sampling = False
+        self._logits = self._draft_logits = self._draw = self._stream_ids = None
         self.rec_ints = self.lib.sd_specdec_record_ints(self.handle)
         ptr = self.lib.sd_specdec_record(self.handle)
         self._record = np.ctypeslib.as_array(ptr, shape=(2, self.B, self.rec_ints))   # slot = launch index & 1
@@ -531,7 +534,7 @@ class HipSpecDec:
                 self.sampling = False
                 return
             V = self.target.weights.config.vocab
-            if getattr(self, "_logits", None) is None:
+            if self._logits is None:
                 self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
             self._draw = torch.tensor(list(draw_counts) if draw_counts is not None else [0] * self.B, dtype=torch.int32,
                                       device=self.device)
@@ -544,9 +547,54 @@ class HipSpecDec:
                 self._stream_ids.data_ptr()), "sd_specdec_set_sampling")
             self.sampling = True
 
+    def set_spec_sampling(self, enable: bool, temperature: float = 1.0, seed: int = 0, stream_ids: Optional[Sequence[int]] = None,
+                          draw_counts: Optional[Sequence[int]] = None):
+        """Speculative sampling inside the step (sd_specdec_set_spec_sampling): draft tokens drawn from the draft's
+        distribution, accepted with probability min(1, p/q), the first rejection redrawn from the residual — the output is
+        distributed as the target's own sampling at `temperature`. The loop owns the two logits buffers (`spec_draft_logits`
+        [B][K][V], `step_logits` [B][K+1][V]) and the draw counters (K + 1 per row and step; start at `draw_counts`)."""
+        with torch.cuda.device(self.device):
+            if not enable:
+                _abi.check(self.lib.sd_specdec_set_spec_sampling(self.handle, 0, 1.0, 0, None, 0, None, 0, None, None),
+                           "sd_specdec_set_spec_sampling")
+                self.spec_sampling = False
+                return
+            V = self.target.weights.config.vocab
+            if self._logits is None:
+                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+            if self._draft_logits is None:
+                self._draft_logits = torch.empty((self.B, self.K, V), dtype=torch.bfloat16, device=self.device)
+            self._draw = torch.tensor(list(draw_counts) if draw_counts is not None else [0] * self.B, dtype=torch.int32,
+                                      device=self.device)
+            sid = list(stream_ids) if stream_ids is not None else list(range(self.B))
+            self._stream_ids = torch.tensor(sid, dtype=torch.int32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+            _abi.check(self.lib.sd_specdec_set_spec_sampling(
+                self.handle, 1, float(temperature), int(seed) & (2 ** 64 - 1), self._draft_logits.data_ptr(),
+                self._draft_logits.numel() * 2, self._logits.data_ptr(), self._logits.numel() * 2, self._draw.data_ptr(),
+                self._stream_ids.data_ptr()), "sd_specdec_set_spec_sampling")
+            self.spec_sampling = True
+
+    def set_draw_counts(self, draw_counts: Sequence[int]) -> None:
+        """Rewrite the rows' draw counters (sampling modes) on the loop's target stream: the host's in-order view after steps
+        that were launched ahead turned out void for a row. The captured step is kept."""
+        host = torch.tensor([int(x) & 0xFFFFFFFF for x in draw_counts], dtype=torch.int64).to(torch.int32)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream_t):
+            self._draw.copy_(host.to(self.device))
+
+    @property
+    def draw_counts(self) -> List[int]:
+        """The device's draw counters (synchronises)."""
+        return [int(x) & 0xFFFFFFFF for x in self._draw.cpu().tolist()]
+
+    @property
+    def spec_draft_logits(self) -> torch.Tensor:
+        """[B][K][V] bf16: row (b, i) = the logits d_{i+1} was drawn from in the last step (speculative sampling only)."""
+        return self._draft_logits
+
     @property
     def step_logits(self) -> torch.Tensor:
-        """[B][K+1][V] bf16 logits of the last verify forward (sampling mode only)."""
+        """[B][K+1][V] bf16 logits of the last verify forward (sampling modes only)."""
         return self._logits
 
     def step(self, use_graph: bool = True, two_streams: bool = True):

@@ -346,6 +346,42 @@ def sample_token_hip(logits: torch.Tensor, temperature: float, top_k: Optional[i
     return out
 
 
+def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor, temperature: float,
+                           seed: int = 0, draw: int = 0, draw_counters: Optional[torch.Tensor] = None,
+                           stream_ids: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                           return_ratios: bool = False):
+    """Acceptance and next token of speculative sampling (sd_spec_sample_accept) on caller tensors.
+
+    draft_logits bf16 [B, K, V] (q_i), target_logits bf16 [B, K+1, V] (p_i), draft_ids int32 [B, K] (the tokens drawn from
+    q_i). Returns (accept_len int32 [B], next_tok int32 [B]) and, with return_ratios, the float64 [B, K] ratios
+    p_i(d)/q_i(d). Row b's draws use counter `draw` (or the int32 `draw_counters`, advanced by K + 1 on the device) and
+    Philox stream stream_ids[b] (default b); see include/specdec_hip.h for the schedule."""
+    lib = _abi.load()
+    dev = _require_device("spec_sample_accept", draft_logits, target_logits, draft_ids)
+    if draft_logits.dim() != 3 or target_logits.dim() != 3 or draft_ids.dim() != 2:
+        raise ValueError("spec_sample_accept: need draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]")
+    B, K, V = draft_logits.shape
+    if tuple(target_logits.shape) != (B, K + 1, V) or tuple(draft_ids.shape) != (B, K):
+        raise ValueError(f"spec_sample_accept: shapes {tuple(draft_logits.shape)} / {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
+    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16 or draft_ids.dtype != torch.int32:
+        raise TypeError("spec_sample_accept: logits must be bfloat16 and draft_ids int32")
+    draft_logits, target_logits, draft_ids = draft_logits.contiguous(), target_logits.contiguous(), draft_ids.contiguous()
+    for name, t in (("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"spec_sample_accept: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    accept = torch.zeros(B, dtype=torch.int32, device=dev)
+    nxt = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
+    ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_spec_sample_accept(draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V,
+                                             float(temperature), int(seed) & (2 ** 64 - 1), ptr(draw_counters), int(draw) & 0xFFFFFFFF,
+                                             ptr(stream_ids), ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios),
+                                             ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "sd_spec_sample_accept")
+    return (accept, nxt, ratios) if return_ratios else (accept, nxt)
+
+
 def quantize_fp8_rows_hip(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(q float8_e4m3fn [N][K], scales float32 [N]) of a bf16 matrix: the per-output-row quantiser of the
     engine's fp8 weight storage (sd_quantize_fp8_rows)."""

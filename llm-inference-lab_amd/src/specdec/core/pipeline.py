@@ -171,6 +171,18 @@ class SpeculativePipeline:
         # what the base model generates by itself from the same prefix, which a parallel pass over the DRAFT tokens does
         # not give once a non-argmax draft token is accepted.
         self.policy_name = policy
+        # policy="rejection": backend "host" (default) is the host loop (_decode_rejection); "device" runs speculative sampling
+        # inside the captured step (csrc/spec_sample.hip, sd_specdec_set_spec_sampling) with the policy's temperature and seed
+        self.rejection_backend = str((policy_params or {}).get("backend", "host"))
+        if self.rejection_backend not in ("host", "device"):
+            raise ValueError(f"policy_params['backend']={self.rejection_backend!r} (one of 'host', 'device')")
+        if self.rejection_backend == "device":
+            if policy != "rejection":
+                raise ValueError("policy_params['backend']='device' belongs to policy='rejection'")
+            if self._fake:
+                raise NotImplementedError("policy='rejection' with backend='device' needs the HIP engine (implementation='hip')")
+            if not float((policy_params or {}).get("temperature", 1.0)) > 0:
+                raise ValueError("policy='rejection' with backend='device' needs temperature > 0")
         if policy != "longest_prefix" and (mode != "vanilla" or medusa_heads is not None):
             raise NotImplementedError(f"policy={policy!r} drafts with the draft model (draft_mode='vanilla')")
         self.controller = create_controller(controller, **(controller_params or {}))
@@ -522,6 +534,18 @@ class SpeculativePipeline:
         return {"temperature": float(temperature), "top_k": int(top_k) if top_k else None,
                 "top_p": None if top_p is None else float(top_p), "seed": int(kwargs.get("seed", self.config.get("seed") or 0))}
 
+    def _spec_sampling_config(self, kwargs: Dict[str, Any]) -> Dict[str, Any]:
+        """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature and
+        seed. What the mode does not do is refused, not approximated."""
+        from ..policies.controllers import FixedKController
+
+        if kwargs.get("top_k") or (kwargs.get("top_p") is not None and float(kwargs["top_p"]) < 1.0):
+            raise NotImplementedError("policy='rejection' (backend='device'): top-k / top-p shaping of the two distributions is not supported")
+        if not isinstance(self.controller, FixedKController):
+            raise NotImplementedError("policy='rejection' (backend='device') keeps a fixed K (controller='fixed'): adaptive K is not supported")
+        return {"spec": True, "temperature": float(self.policy.temperature), "top_k": None, "top_p": None,
+                "seed": int(kwargs.get("seed", self.policy.seed))}
+
     def generate(self, prompt: PromptLike, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  do_sample: Optional[bool] = None, **kwargs) -> Dict[str, Any]:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
@@ -586,7 +610,9 @@ class SpeculativePipeline:
         if self.draft_lm is None and not heads:
             raise ValueError("generate_batch drafts with the draft model (the reference ignores draft_mode there): pass draft_lm / draft_model")
         ids = [self._encode(p) for p in prompts]
-        if self.policy_name == "rejection":
+        if self.policy_name == "rejection" and self.rejection_backend == "device":
+            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs))
+        elif self.policy_name == "rejection":
             rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
         elif self.policy_name != "longest_prefix":
             if sampling is not None:
@@ -714,6 +740,8 @@ class DecodeSession:
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
         self.self_draft = self_draft
         self.sampling = sampling
+        # speculative sampling (policy="rejection", backend="device"): the step's third mode instead of the sampled bonus token
+        self._spec = bool(sampling and sampling.get("spec"))
         self.step_limit = step_limit
         if sampling is not None and emit_mode != HipSpecDec.EMIT_BONUS:
             raise ValueError("sampling is a generate_batch (bonus-token) feature")
@@ -768,7 +796,9 @@ class DecodeSession:
 
         # (persistent Medusa heads / EAGLE-lite: a void step would replace the next proposals with ones derived from stale
         # state — harmless for the tokens, but the counters would no longer be those of the in-order loop)
-        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and sampling is None
+        # (speculative sampling advances a row's draw counter on the device by K + 1 per step, void steps included: the host's
+        # in-order counters are written back whenever a row is repaired, so its steps can be queued ahead like greedy ones)
+        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and (sampling is None or self._spec)
                        and not self._stateful_draft
                        and os.environ.get("SPECDEC_EARLY_LAUNCH", "1") != "0")
         self._depth = 2 if self._early else 1
@@ -807,12 +837,22 @@ class DecodeSession:
     def _apply_sampling(self) -> None:
         """Loops are cached per (batch, K): (re)configure the one in use for this run."""
         sp = self.sampling
+        spec = self._spec
+        if self.loop.spec_sampling and not spec:
+            self.loop.sync()
+            self.loop.set_spec_sampling(False)
+        if self.loop.sampling and (sp is None or spec):
+            self.loop.sync()
+            self.loop.set_sampling(False)
         if sp is None:
-            if getattr(self.loop, "sampling", False):
-                self.loop.sync()
-                self.loop.set_sampling(False)
             return
         self.loop.sync()
+        if spec:
+            if self.per_row or self.self_draft:
+                raise NotImplementedError("speculative sampling needs a draft model and a fixed K")
+            self.loop.set_spec_sampling(True, sp["temperature"], sp["seed"], stream_ids=list(range(len(self.rows))),
+                                        draw_counts=[r.draws for r in self.rows])
+            return
         self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
                                stream_ids=list(range(len(self.rows))), draw_counts=[r.draws for r in self.rows])
 
@@ -845,6 +885,8 @@ class DecodeSession:
             if self.per_row:                       # the device counted steps the host voided: hand it the in-order view
                 m = self.row_ctl[b]
                 loop.set_adaptive_row(b, m.current_k, r.strict_acc, r.strict_prop, m.acceptance_history[-4:])
+        if self._flagged and self._spec and loop.spec_sampling:
+            loop.set_draw_counts([r.draws for r in self.rows])   # void steps drew for the flagged rows: back to the in-order view
         self._flagged.clear()
 
     def _recover(self, err: Exception) -> None:
@@ -974,14 +1016,20 @@ class DecodeSession:
                 r.strict_acc += a
                 r.strict_prop += k
                 m.get_k(r.steps + 2, {"step": r.steps + 2, "acceptance_rate": r.strict_acc / max(r.strict_prop, 1)})
-            if self.sampling is not None:
+            if self._spec:
+                # speculative sampling: the accepted tokens are the DRAFT's ids, then the redrawn / bonus token. An accepted EOS
+                # ends the row by the rule as it stands for greedy steps: the accepted tokens are cut BEFORE the EOS, then the
+                # rule appends t[pos] — a < k: pos = a, the token redrawn after the accepted prefix (the EOS itself is dropped);
+                # a == k: pos = length of the cut, which is the EOS (it stays as the last token)
+                t = [int(x) for x in rec.new_tokens[b]]
+            elif self.sampling is not None:
                 t[a] = int(rec.new_tokens[b][a])       # the token the device sampled at position a
             assumed = before + t[: int(rec.n_new[b])]  # what the device advanced to
             if self.emit_mode == HipSpecDec.EMIT_BONUS:
                 pipe._rules_batch(r, k, a, t, self.max_tokens, self.eos,
-                                  self._resampler(b, r) if self.sampling is not None else None)
+                                  self._resampler(b, r) if (self.sampling is not None and not self._spec) else None)
                 if self.sampling is not None:
-                    r.draws += 1
+                    r.draws += (k + 1) if self._spec else 1
             else:
                 pipe._rules_single(r, k, a, d, t, self.max_tokens, self.eos)
             r.steps += 1

@@ -36,6 +36,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--policy-tau", type=float, help="conf_threshold: tau")
     ap.add_argument("--policy-k", type=int, help="topk_agree: k")
     ap.add_argument("--policy-p", type=float, help="typical: p")
+    ap.add_argument("--spec-sampling", action="store_true",
+                    help="speculative sampling inside the captured step (policy 'rejection', backend 'device'): the output is "
+                         "distributed as the target's own sampling at --temperature; drawn with --seed; fixed K, draft-model mode")
     ap.add_argument("--controller", type=str, choices=["fixed", "adaptive"], default="fixed")
     ap.add_argument("--K", type=int, default=4, help="K of the fixed controller")
     ap.add_argument("--adaptive-K", action="store_true")
@@ -81,15 +84,27 @@ def main(argv=None) -> int:
             cp["initial_k"] = max(lo, min(4, hi))
     else:
         controller, cp = "fixed", {"k": args.K}
+    policy, pp = args.policy, {k: v for k, v in (("tau", args.policy_tau), ("k", args.policy_k), ("p", args.policy_p)) if v is not None}
+    if args.spec_sampling:
+        if args.policy != "longest_prefix":
+            logging.error("Cannot specify both --policy and --spec-sampling")
+            return 1
+        policy, pp = "rejection", {"backend": "device", "temperature": 0.7 if args.temperature is None else args.temperature,
+                               "seed": 0 if args.seed is None else args.seed}   # (the pipeline refuses a temperature <= 0)
     try:
         pipe = SpeculativePipeline(config_path=args.config, base_model=args.base_model, draft_model=args.draft_model,
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,
-                                   policy=args.policy, controller=controller, controller_params=cp, draft_mode=args.draft_mode,
-                                   policy_params={k: v for k, v in (("tau", args.policy_tau), ("k", args.policy_k), ("p", args.policy_p)) if v is not None})
+                                   policy=policy, controller=controller, controller_params=cp, draft_mode=args.draft_mode,
+                                   policy_params=pp)
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
-        r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
+        if args.spec_sampling:      # a generate_batch mode (a correction / bonus token every step): a batch of one
+            r = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens)[0]
+            r = {**pipe._sysinfo(), **r, "latency_ms": r["total_time_ms"],
+                 "acceptance_rate": r["accepted"] / max(r["proposed"], 1)}
+        else:
+            r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
         if args.eval_perplexity:
             r["perplexity"], r["perplexity_loss"] = generated_perplexity(pipe.base_lm, r["generated_tokens"])
     except Exception as e:  # the reference CLI reports and exits 1 (run_specdec.py:276-278)

@@ -42,10 +42,15 @@ def cmd_bench(args: argparse.Namespace) -> int:
 
 
 def cmd_run(args: argparse.Namespace) -> int:
+    spec = getattr(args, "spec_sampling", False)
+    extra = {"policy": "rejection", "policy_params": {"backend": "device", "temperature": args.temperature, "seed": args.seed}} if spec else {}
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
-                               draft_mode="vanilla")
-    res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample)
+                               draft_mode="vanilla", **extra)
+    if spec:   # speculative sampling inside the captured step: a generate_batch mode, here a batch of one
+        res = {**pipe._sysinfo(), **pipe.generate_batch([args.prompt], max_tokens=args.max_tokens)[0]}
+    else:
+        res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample)
     kinfo = get_kernel_info()
     print(f"Device: {res.get('device')} | Dtype: {res.get('dtype')} | "
           f"Backends: verify={kinfo.get('verify_backend')}, kv_append={kinfo.get('kv_append_backend')}")
@@ -75,6 +80,9 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--device", choices=["auto", "cuda"], default="auto")
     pr.add_argument("--temperature", type=float, default=0.7)
     pr.add_argument("--do-sample", action="store_true")
+    pr.add_argument("--spec-sampling", action="store_true",
+                    help="speculative sampling on the device (policy 'rejection', backend 'device') at --temperature, drawn with --seed")
+    pr.add_argument("--seed", type=int, default=0)
     pr.add_argument("prompt", type=str)
     pr.set_defaults(func=cmd_run)
     return p
