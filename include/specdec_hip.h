@@ -107,6 +107,17 @@ int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, c
                           const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
                           double* ratios_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same steps for the SHAPED mode (sd_specdec_set_spec_shaping): sd_spec_sample_accept's arguments plus top_k (1..1024,
+ * clamped to V) and top_p (> 0; >= 1: no nucleus cut); the same workspace function. Steps 2-4 of the shaped definition below:
+ * the acceptance uniform of position i is the Philox value of counter (c + i, sid, 0, 0x5EED0003), the next token inverts the
+ * uniform of counter (c + K, sid, 0, CDF tag). ratios_out: (e_p(d)/Z_p) / (e_q(d)/Z_q); 0 when d is outside the target's kept
+ * set, NaN (rejected) when d is outside the draft's. Refused: top_k <= 0 (top_p without top_k, the full-vocabulary nucleus, is
+ * not supported; the unshaped op is sd_spec_sample_accept), top_k > 1024, top_p <= 0 or NaN. */
+int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K, int V,
+                                 float temperature, int top_k, float top_p, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
+                                 const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
+                                 double* ratios_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * kv_append (in place) — the KV-append path
  *   reference contract: kv_append_ref, src/kernels/reference.py:59-93
@@ -456,11 +467,35 @@ int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperature, int to
  * The emitted sequence is distributed as sampling from softmax(target bf16 logits / T), whatever the draft is. Non-finite
  * logits: a position whose p or q row holds a NaN or has a non-finite maximum is rejected and redrawn from p_i / T alone
  * (NaN-first ordering of sd_sample_token). Refused: SD_EMIT_DRAFT, loops without a draft model (self-draft, Medusa heads,
- * EAGLE), adaptive K, the sampled-bonus mode being on, temperature <= 0 or NaN, short or misaligned (16 B) buffers; top-k /
- * top-p shaping of p and q is not part of the mode. Both calls (enable / disable) drop the captured graph. */
+ * EAGLE), adaptive K, the sampled-bonus mode being on, temperature <= 0 or NaN, short or misaligned (16 B) buffers. Top-k /
+ * top-p shaping of p and q is sd_specdec_set_spec_shaping below; without it the mode samples the whole vocabulary. Both calls
+ * (enable / disable) drop the captured graph. */
 int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float temperature, uint64_t seed, void* draft_logits_buf,
                                  size_t draft_logits_bytes, void* target_logits_buf, size_t target_logits_bytes,
                                  uint32_t* draw_counters, const int32_t* stream_ids);
+
+/* Top-k / top-p shape of speculative sampling: with top_k in 1..1024 (clamped to V) both distributions of every position are
+ * the temperature -> top-k -> top-p distribution of their row exactly as sd_sample_token defines it, and the emitted tokens
+ * are distributed as the target's own sd_sample_token(temperature, top_k, top_p) sampling, whatever the draft is.
+ * For a bf16 row x, S(x) = the kept ids in sorted order (value descending, index ascending), float64 weights
+ * e_j = exp(x_j/T - max), Z = their sum added sequentially in sorted order; a row whose top value is not finite is the point
+ * mass on its first id (no position is "rejected as non-finite" in this mode). x'(v) = e(v)/Z on the kept set, 0 elsewhere.
+ * Per row b and step (c, sid, seed as above; Philox counter words are (draw, stream, element, tag)):
+ *   1. d_{i+1}, i = 0..K-1: the uniform of counter (c + i, sid, 0, CDF tag) inverted through S(q_i) in sorted order — exactly
+ *      the token sd_sample_token draws from q_i with draw index c + i; the logits row is stored as q_i as in the unshaped mode;
+ *   2. u_i: counter (c + i, sid, 0, 0x5EED0003) — a tag of its own, the CDF-tag block of (c + i) being the draw of step 1;
+ *   3. ratio_i = (e_p(d)/Z_p) / (e_q(d)/Z_q), d = d_{i+1}; e_p(d) = 0 when d is outside the target's kept set (rejected).
+ *      p and q go through the same code in the same order: bitwise equal rows give exactly 1.0. a = leading i with u_i < ratio_i;
+ *   4. next token, uniform u_n of counter (c + K, sid, 0, CDF tag): a < K: weights r_j = max(0, p'_a(id_j) - q'_a(id_j)) over
+ *      the TARGET's kept ids in the target's sorted order, Z_r summed sequentially, the first j with u_n Z_r < cum_j (the last
+ *      kept id otherwise); Z_r == 0 (q' >= p' on p's support): the same inversion through e_p, i.e. sd_sample_token on p_a with
+ *      draw c + K; a == K: sd_sample_token on p_K with draw c + K;
+ *   5. as step 5 above.
+ * top_k <= 0 with top_p >= 1 returns to the unshaped mode (the default). Legal before or after
+ * sd_specdec_set_spec_sampling(enable = 1); the shape is kept while the mode is switched off and on. Drops the captured graph.
+ * Refused: top_k > 1024; top_k <= 0 with top_p < 1 (top_p without top_k, the full-vocabulary nucleus: it needs the rank-block
+ * walk of sd_sample_token on two rows at once); top_p <= 0 or NaN. */
+int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p);
 
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,

@@ -67,5 +67,12 @@ int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per
                            float temperature, uint64_t seed, const uint32_t* draw, const int32_t* stream_id, hipStream_t st);
 int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
                      uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
+// the same two with both distributions shaped by top-k / top-p (top_k in 1..1024)
+int launch_spec_draft_draw_shaped(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
+                                  float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw,
+                                  const int32_t* stream_id, hipStream_t st);
+int launch_spec_step_shaped(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
+                            int top_k, float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag,
+                            int32_t* cand, hipStream_t st);
 
 }  // namespace sd

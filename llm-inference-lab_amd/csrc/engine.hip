@@ -1067,6 +1067,8 @@ struct sd_specdec {
   void* spec_p = nullptr;          // [B][K+1][V] bf16 target logits, caller-owned; until the verify forward overwrites it, its first
                                    // rows are where each draft forward leaves the logits of its pass ([B][M][V])
   int32_t* spec_flags = nullptr;   // [2][B][K+1] device: accept flags, candidate next tokens
+  int spec_top_k = 0;              // sd_specdec_set_spec_shaping: > 0 = both distributions shaped by top-k / top-p
+  float spec_top_p = 1.0f;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -1210,7 +1212,11 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
     }
     s->draft->skip_k = nullptr;
     if (rc_f) return rc_f;
-    if (spec) {   // exactly one form of forward 0 ran: one draw launch serves both
+    if (spec && s->spec_top_k > 0) {
+      if (int rc = launch_spec_draft_draw_shaped(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->spec_top_k, s->spec_top_p,
+                                                 s->seed, s->draw, s->stream_id, st_d))
+        return rc;
+    } else if (spec) {   // exactly one form of forward 0 ran: one draw launch serves both
       if (int rc = launch_spec_draft_draw(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->seed, s->draw, s->stream_id, st_d)) return rc;
     } else if (!one_pass_d) {
       if (int rc = launch_draft_next(M, i, s->st, st_d)) return rc;
@@ -1244,7 +1250,11 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
                                     s->draw, s->stream_id, st_t))
       return rc;
   }
-  if (spec) {
+  if (spec && s->spec_top_k > 0) {
+    if (int rc = launch_spec_step_shaped(s->st, s->spec_p, s->spec_q, V, s->temperature, s->spec_top_k, s->spec_top_p, s->seed, s->draw,
+                                         s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
+      return rc;
+  } else if (spec) {
     // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
     if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, s->seed, s->draw, s->stream_id, s->spec_flags,
                                   s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
@@ -1516,6 +1526,24 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   s->spec_p = target_logits_buf;
   s->draw = draw_counters;
   s->stream_id = stream_ids;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p) {
+  clear_error();
+  SD_REQUIRE(top_p == top_p && top_p > 0.f, "specdec_set_spec_shaping: top_p %g (must be > 0)", top_p);
+  SD_REQUIRE(top_k > 0 || top_p >= 1.0f, "specdec_set_spec_shaping: top_p = %g without top_k (the full-vocabulary nucleus) is not supported; "
+             "give a top_k in 1..1024", top_p);
+  SD_REQUIRE(top_k <= 1024, "specdec_set_spec_shaping: top_k=%d > 1024 is not supported", top_k);
+  SD_REQUIRE(s, "specdec_set_spec_shaping: NULL");
+  if (s->exec) {  // the captured step holds the launches of the other shape
+    (void)hipGraphExecDestroy(s->exec);
+    (void)hipGraphDestroy(s->graph);
+    s->exec = nullptr;
+    s->graph = nullptr;
+  }
+  s->spec_top_k = top_k > 0 ? top_k : 0;
+  s->spec_top_p = top_k > 0 ? top_p : 1.0f;
   return 0;
 }
 

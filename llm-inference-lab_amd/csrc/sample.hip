@@ -29,10 +29,6 @@
 
 namespace sd {
 
-constexpr int kSampleMaxK = 1024;     // top_k limit
-constexpr int kSampleCap = 2048;      // bucket size at which the radix passes stop
-constexpr int kSampleSort = 4096;     // >= kSampleMaxK + kSampleCap, power of two
-
 struct SampleArgs {
   const void* logits;
   int dtype;               // SD_F32 / SD_BF16 / SD_F16
@@ -52,179 +48,18 @@ struct SampleArgs {
 };
 
 __global__ __launch_bounds__(kSampleThreads) void sample_topk_kernel(const SampleArgs a) {
-  __shared__ uint32_t hist[2048];
-  __shared__ uint64_t sel[kSampleSort];
-  __shared__ double ev[kSampleMaxK];
-  __shared__ uint32_t s_cnt, s_digit, s_above, s_bucket;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ SurvivorLds L;
+  const int b = blockIdx.x, tid = threadIdx.x;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
-  const int V = a.V;
-  const int k = min(a.top_k, V);
-
-  // gather every element whose composite key, shifted right by `shift`, is >= `bound`
-  auto gather = [&](uint64_t bound, int shift) {
-    if (tid == 0) s_cnt = 0;
-    for (int i = tid; i < kSampleSort; i += kSampleThreads) sel[i] = 0;
-    __syncthreads();
-    for_each_logit(row, a.dtype, V, tid, [&](float x, int i) {
-      const uint64_t c = composite_key(x, i);
-      if ((c >> shift) >= bound) {
-        const uint32_t slot = atomicAdd(&s_cnt, 1u);
-        if (slot < static_cast<uint32_t>(kSampleSort)) sel[slot] = c + 1;  // 0 stays "empty" and sorts last
-      }
-    });
-    __syncthreads();
-  };
-  // descending bitonic sort of sel[0, n), n a power of two
-  auto sort_desc = [&](int n) {
-    for (int size = 2; size <= n; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < n / 2; t += kSampleThreads) {
-          const int lo = 2 * t - (t & (stride - 1));
-          const int hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const uint64_t x = sel[lo], y = sel[hi];
-          if ((x < y) == desc) { sel[lo] = y; sel[hi] = x; }
-        }
-        __syncthreads();
-      }
-    }
-  };
-
-  // ---- 1a. fast path: the k-th largest thread maximum bounds the k-th largest element from below
-  {
-    uint64_t best = 0;
-    for_each_logit(row, a.dtype, V, tid, [&](float x, int i) {
-      const uint64_t c = composite_key(x, i);
-      best = c > best ? c : best;
-    });
-    sel[tid] = best;  // threads without an element hold 0: below every real key
-    __syncthreads();
-    sort_desc(kSampleThreads);
-    const uint64_t tau = sel[k - 1];  // k <= min(1024, V): at least k threads saw an element
-    __syncthreads();
-    gather(tau, 0);
-  }
-
-  // ---- 1b. fallback: radix select on the composite key, most significant digits first
-  if (s_cnt > static_cast<uint32_t>(kSampleSort)) {
-    const int widths[5] = {11, 11, 10, 10, 10};
-    uint64_t prefix = 0;       // decided high bits (right-aligned)
-    int decided = 0;           // number of decided bits (of 52)
-    int need = k;              // rank of the wanted element inside the current bucket (1-based from the top)
-    for (int p = 0; p < 5; ++p) {
-      const int w = widths[p];
-      const int shift = 52 - decided - w;
-      for (int i = tid; i < 2048; i += kSampleThreads) hist[i] = 0;
-      __syncthreads();
-      for_each_logit(row, a.dtype, V, tid, [&](float x, int i) {
-        const uint64_t c = composite_key(x, i);
-        if ((c >> (shift + w)) == prefix) atomicAdd(&hist[(c >> shift) & ((1u << w) - 1u)], 1u);
-      });
-      __syncthreads();
-      if (wave == 0) {
-        // lane l owns digits [32 l, 32 l + 32); scan from the top digit down
-        const int nb = 1 << w;
-        uint32_t local = 0;
-        for (int j = 0; j < 32; ++j) {
-          const int d = lane * 32 + j;
-          if (d < nb) local += hist[d];
-        }
-        uint32_t incl = local;  // suffix sum over lanes >= this one
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const uint32_t o = __shfl_down(incl, off, 64);
-          if (lane + off < 64) incl += o;
-        }
-        uint32_t above = incl - local;
-        if (above < static_cast<uint32_t>(need) && incl >= static_cast<uint32_t>(need)) {
-          for (int j = 31; j >= 0; --j) {
-            const int d = lane * 32 + j;
-            if (d >= nb) continue;
-            const uint32_t h = hist[d];
-            if (above + h >= static_cast<uint32_t>(need)) {
-              s_digit = d;
-              s_above = above;
-              s_bucket = h;
-              break;
-            }
-            above += h;
-          }
-        }
-      }
-      __syncthreads();
-      prefix = (prefix << w) | s_digit;
-      decided += w;
-      need -= static_cast<int>(s_above);
-      const uint32_t bucket = s_bucket;
-      __syncthreads();
-      if (bucket <= static_cast<uint32_t>(kSampleCap)) break;
-    }
-    gather(prefix, 52 - decided);
-  }
-
-  // ---- 2. sort the candidates (>= k of them, the k largest among them) descending
-  int n_sort = 2;  // next power of two >= gathered count (workgroup-uniform)
-  while (n_sort < static_cast<int>(s_cnt)) n_sort <<= 1;
-  sort_desc(n_sort);
-
-  // ---- 3. the k survivors in sorted order: weights in float64
-  const double T = static_cast<double>(a.temperature);
-  const bool scale = (a.temperature > 0.f) && (a.temperature != 1.0f);
-  int my_idx = 0;
-  if (tid < k) {
-    const uint64_t c = sel[tid] - 1;
-    my_idx = static_cast<int>(((1u << kIdxBits) - 1u) - static_cast<uint32_t>(c & ((1u << kIdxBits) - 1u)));
-    double v = static_cast<double>(load_logit(row, a.dtype, my_idx));
-    if (scale) v = v / T;
-    ev[tid] = v;
-  }
-  __syncthreads();
-  const double m = ev[0];
-  __syncthreads();
-  if (tid < k) {
-    double e = exp(ev[tid] - m);
-    if (e != e) e = 0.0;
-    ev[tid] = e;
-  }
-  // sel[] is reused for the token ids of the survivors
-  __syncthreads();
-  if (tid < k) sel[tid] = static_cast<uint64_t>(my_idx);
-  __syncthreads();
+  // steps 1-3: the kept set, its weights and their sum (sample_device.h)
+  row_survivors(L, row, a.dtype, a.V, min(a.top_k, a.V), a.temperature, a.top_p);
   if (tid == 0) {
-    int pick = 0;
-    const bool finite = (m == m) && (m - m == 0.0);
-    if (finite) {
-      int n_keep = k;
-      if (a.top_p < 1.0f) {
-        const double tp = static_cast<double>(a.top_p);
-        double z = 0.0;
-        for (int i = 0; i < k; ++i) z += ev[i];
-        double cum = 0.0;
-        n_keep = 0;
-        for (int i = 0; i < k; ++i) {
-          cum += ev[i] / z;
-          if (i == 0 || !(cum > tp)) n_keep = i + 1;
-          else break;
-        }
-      }
-      double z2 = 0.0;
-      for (int i = 0; i < n_keep; ++i) z2 += ev[i];
-      const uint32_t d = a.draw ? a.draw[b] : a.draw0;
-      const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
-      uint32_t r0;
-      philox4x32_10(d, sid, 0u, kTagCdf, a.seed_lo, a.seed_hi, r0);
-      const double target = static_cast<double>(r0) * 2.3283064365386963e-10 * z2;  // 2^-32
-      pick = n_keep - 1;
-      double c = 0.0;
-      for (int i = 0; i < n_keep; ++i) {
-        c += ev[i];
-        if (target < c) { pick = i; break; }
-      }
-    }
-    a.out[b] = static_cast<int32_t>(sel[pick]);
+    const uint32_t d = a.draw ? a.draw[b] : a.draw0;
+    const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
+    const int pick = invert_weights(L.ev, L.n_keep, L.z, philox_uniform(d, sid, kTagCdf, a.seed_lo, a.seed_hi));
+    a.out[b] = static_cast<int32_t>(L.sel[pick]);
     if (a.draw) a.draw[b] = a.draw[b] + 1u;
   }
 }

@@ -1,5 +1,6 @@
 // Device building blocks shared by the samplers (csrc/sample.hip, csrc/spec_sample.hip): the Philox4x32-10 draw, the
-// row walkers and the total order of Gumbel scores. Arithmetic as oracle/sampling_ref.py.
+// row walkers, the total order of Gumbel scores and the kept set of a temperature -> top-k -> top-p shaped row
+// (row_survivors: the ONE definition of "tie at the cut"). Arithmetic as oracle/sampling_ref.py.
 #pragma once
 
 #include <hip/hip_fp16.h>
@@ -11,6 +12,10 @@ namespace sd {
 constexpr int kSampleThreads = 1024;
 constexpr int kIdxBits = 20;
 constexpr uint32_t kTagCdf = 0x5EED0001u, kTagGumbel = 0x5EED0002u;
+constexpr uint32_t kTagAccept = 0x5EED0003u;   // acceptance uniform of shaped speculative sampling (csrc/spec_sample.hip)
+constexpr int kSampleMaxK = 1024;     // top_k limit
+constexpr int kSampleCap = 2048;      // bucket size at which the radix passes stop
+constexpr int kSampleSort = 4096;     // >= kSampleMaxK + kSampleCap, power of two
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t& r0) {
@@ -81,6 +86,202 @@ __device__ __forceinline__ bool better_d(double v, int i, double bv, int bi) {
     return vn;
   }
   return (v > bv) | ((v == bv) & (i < bi));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The kept set of a row under temperature -> top-k -> top-p (oracle/sampling_ref.py: filtered_distribution), by one
+// 1024-thread workgroup; the steps are described at the top of csrc/sample.hip. On return (after a barrier) the LDS block
+// holds, in sorted order (value descending, index ascending):
+//   sel[j] = token id, ev[j] = float64 weight exp(x_j / T - max), j < n_keep;  z = their sum, added sequentially.
+// A row whose top value is not finite is the point mass on its first id: n_keep = 1, ev[0] = 1, z = 1.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SurvivorLds {
+  uint64_t sel[kSampleSort];
+  double ev[kSampleMaxK];
+  uint32_t hist[2048];
+  double z;
+  uint32_t cnt, digit, above, bucket;
+  int n_keep;
+};
+
+// k = min(top_k, V) in 1..kSampleMaxK; every thread of the workgroup calls it (barriers inside)
+__device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, int dtype, int V, int k, float temperature, float top_p) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // gather every element whose composite key, shifted right by `shift`, is >= `bound`
+  auto gather = [&](uint64_t bound, int shift) {
+    if (tid == 0) L.cnt = 0;
+    for (int i = tid; i < kSampleSort; i += kSampleThreads) L.sel[i] = 0;
+    __syncthreads();
+    for_each_logit(row, dtype, V, tid, [&](float x, int i) {
+      const uint64_t c = composite_key(x, i);
+      if ((c >> shift) >= bound) {
+        const uint32_t slot = atomicAdd(&L.cnt, 1u);
+        if (slot < static_cast<uint32_t>(kSampleSort)) L.sel[slot] = c + 1;  // 0 stays "empty" and sorts last
+      }
+    });
+    __syncthreads();
+  };
+  // descending bitonic sort of sel[0, n), n a power of two
+  auto sort_desc = [&](int n) {
+    for (int size = 2; size <= n; size <<= 1) {
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = tid; t < n / 2; t += kSampleThreads) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool desc = ((lo & size) == 0);
+          const uint64_t x = L.sel[lo], y = L.sel[hi];
+          if ((x < y) == desc) { L.sel[lo] = y; L.sel[hi] = x; }
+        }
+        __syncthreads();
+      }
+    }
+  };
+
+  // ---- 1a. fast path: the k-th largest thread maximum bounds the k-th largest element from below
+  {
+    uint64_t best = 0;
+    for_each_logit(row, dtype, V, tid, [&](float x, int i) {
+      const uint64_t c = composite_key(x, i);
+      best = c > best ? c : best;
+    });
+    L.sel[tid] = best;  // threads without an element hold 0: below every real key
+    __syncthreads();
+    sort_desc(kSampleThreads);
+    const uint64_t tau = L.sel[k - 1];  // k <= min(1024, V): at least k threads saw an element
+    __syncthreads();
+    gather(tau, 0);
+  }
+
+  // ---- 1b. fallback: radix select on the composite key, most significant digits first
+  if (L.cnt > static_cast<uint32_t>(kSampleSort)) {
+    const int widths[5] = {11, 11, 10, 10, 10};
+    uint64_t prefix = 0;       // decided high bits (right-aligned)
+    int decided = 0;           // number of decided bits (of 52)
+    int need = k;              // rank of the wanted element inside the current bucket (1-based from the top)
+    for (int p = 0; p < 5; ++p) {
+      const int w = widths[p];
+      const int shift = 52 - decided - w;
+      for (int i = tid; i < 2048; i += kSampleThreads) L.hist[i] = 0;
+      __syncthreads();
+      for_each_logit(row, dtype, V, tid, [&](float x, int i) {
+        const uint64_t c = composite_key(x, i);
+        if ((c >> (shift + w)) == prefix) atomicAdd(&L.hist[(c >> shift) & ((1u << w) - 1u)], 1u);
+      });
+      __syncthreads();
+      if (wave == 0) {
+        // lane l owns digits [32 l, 32 l + 32); scan from the top digit down
+        const int nb = 1 << w;
+        uint32_t local = 0;
+        for (int j = 0; j < 32; ++j) {
+          const int d = lane * 32 + j;
+          if (d < nb) local += L.hist[d];
+        }
+        uint32_t incl = local;  // suffix sum over lanes >= this one
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const uint32_t o = __shfl_down(incl, off, 64);
+          if (lane + off < 64) incl += o;
+        }
+        uint32_t above = incl - local;
+        if (above < static_cast<uint32_t>(need) && incl >= static_cast<uint32_t>(need)) {
+          for (int j = 31; j >= 0; --j) {
+            const int d = lane * 32 + j;
+            if (d >= nb) continue;
+            const uint32_t h = L.hist[d];
+            if (above + h >= static_cast<uint32_t>(need)) {
+              L.digit = d;
+              L.above = above;
+              L.bucket = h;
+              break;
+            }
+            above += h;
+          }
+        }
+      }
+      __syncthreads();
+      prefix = (prefix << w) | L.digit;
+      decided += w;
+      need -= static_cast<int>(L.above);
+      const uint32_t bucket = L.bucket;
+      __syncthreads();
+      if (bucket <= static_cast<uint32_t>(kSampleCap)) break;
+    }
+    gather(prefix, 52 - decided);
+  }
+
+  // ---- 2. sort the candidates (>= k of them, the k largest among them) descending
+  int n_sort = 2;  // next power of two >= gathered count (workgroup-uniform)
+  while (n_sort < static_cast<int>(L.cnt)) n_sort <<= 1;
+  sort_desc(n_sort);
+
+  // ---- 3. the k survivors in sorted order: weights in float64
+  const double T = static_cast<double>(temperature);
+  const bool scale = (temperature > 0.f) && (temperature != 1.0f);
+  int my_idx = 0;
+  if (tid < k) {
+    const uint64_t c = L.sel[tid] - 1;
+    my_idx = static_cast<int>(((1u << kIdxBits) - 1u) - static_cast<uint32_t>(c & ((1u << kIdxBits) - 1u)));
+    double v = static_cast<double>(load_logit(row, dtype, my_idx));
+    if (scale) v = v / T;
+    L.ev[tid] = v;
+  }
+  __syncthreads();
+  const double m = L.ev[0];
+  __syncthreads();
+  if (tid < k) {
+    double e = exp(L.ev[tid] - m);
+    if (e != e) e = 0.0;
+    L.ev[tid] = e;
+  }
+  // sel[] is reused for the token ids of the survivors
+  __syncthreads();
+  if (tid < k) L.sel[tid] = static_cast<uint64_t>(my_idx);
+  __syncthreads();
+  if (tid == 0) {
+    int n_keep = 1;
+    double z2 = 1.0;
+    const bool finite = (m == m) && (m - m == 0.0);
+    if (finite) {
+      n_keep = k;
+      if (top_p < 1.0f) {
+        const double tp = static_cast<double>(top_p);
+        double z = 0.0;
+        for (int i = 0; i < k; ++i) z += L.ev[i];
+        double cum = 0.0;
+        n_keep = 0;
+        for (int i = 0; i < k; ++i) {
+          cum += L.ev[i] / z;
+          if (i == 0 || !(cum > tp)) n_keep = i + 1;
+          else break;
+        }
+      }
+      z2 = 0.0;
+      for (int i = 0; i < n_keep; ++i) z2 += L.ev[i];
+    } else {
+      L.ev[0] = 1.0;   // -inf / NaN / +inf on top: the point mass on the first id
+    }
+    L.n_keep = n_keep;
+    L.z = z2;
+  }
+  __syncthreads();
+}
+
+// index of the weight a uniform u in [0, 1) lands on: the first j with u * z < w[0] + .. + w[j] (sequential), else the last
+__device__ __forceinline__ int invert_weights(const double* w, int n, double z, double u) {
+  const double target = u * z;
+  double c = 0.0;
+  for (int i = 0; i < n; ++i) {
+    c += w[i];
+    if (target < c) return i;
+  }
+  return n - 1;
+}
+
+// the uniform r0 * 2^-32 of Philox counter (draw, stream, 0, tag)
+__device__ __forceinline__ double philox_uniform(uint32_t draw, uint32_t sid, uint32_t tag, uint32_t seed_lo, uint32_t seed_hi) {
+  uint32_t r0;
+  philox4x32_10(draw, sid, 0u, tag, seed_lo, seed_hi, r0);
+  return static_cast<double>(r0) * 2.3283064365386963e-10;  // 2^-32
 }
 
 }  // namespace sd

@@ -30,6 +30,34 @@
 //   spec_stats_kernel       grid (K+1, B): position i of row b, independent of the accept length — the two log-sum-exps,
 //                           ratio_i and the flag u_i < ratio_i, then the candidate next token of position i
 //   spec_accept_kernel      one wave per row: accept length = leading flags, next token = candidate of that position
+//
+// SHAPED variant (sd_specdec_set_spec_shaping, sd_spec_sample_accept_shaped): both distributions of every position are the
+// temperature -> top-k -> top-p distribution of their row, exactly as sd_sample_token / oracle/sampling_ref.py:
+// filtered_distribution define it, and the emitted tokens are distributed as the target's own
+// sd_sample_token(temperature, top_k, top_p) sampling, whatever the draft is. top_k in 1..1024 (clamped to V), with or without
+// top_p < 1; top_p WITHOUT top_k (the full-vocabulary nucleus) is refused. Restated on the CPU in tests/spec_shape_ref.py.
+// For a bf16 row x, S(x) = the kept ids in sorted order (value descending, index ascending: the 52-bit composite key), float64
+// weights e_j = exp(x_j / T - max), Z = their sum added sequentially in sorted order; a row whose top value is not finite is
+// the point mass on its first id (so the shaped mode has no "rejected non-finite position" path). x'(v) = e(v) / Z on the kept
+// set, 0 elsewhere. Row b, draw counter c at the start of the step, Philox counter words (draw, stream, element, tag):
+//   1. d_{i+1}, i = 0..K-1 : the uniform of counter (c + i, sid, 0, kTagCdf) inverted through S(q_i) in sorted order — exactly
+//                            the token sd_sample_token draws from q_i with draw index c + i
+//   2. u_i,     i = 0..K-1 : counter (c + i, sid, 0, kTagAccept) — a tag of its own: (c + i, .., kTagCdf) is the draw of 1.
+//   3. ratio_i = (e_p(d) / Z_p) / (e_q(d) / Z_q), d = d_{i+1}; e_p(d) = 0 when d is outside the target's kept set (ratio 0:
+//      rejected). p and q go through the same code in the same order: bitwise equal rows give ratio exactly 1.0. A d outside
+//      q's kept set can only come from a caller of the stand-alone op: ratio NaN, rejected. a = leading i with u_i < ratio_i
+//   4. next token, uniform u_n of counter (c + K, sid, 0, kTagCdf):
+//        a < K : weights r_j = max(0, p'_a(id_j) - q'_a(id_j)) over the TARGET's kept ids in the target's sorted order, Z_r
+//                summed sequentially, the first j with u_n * Z_r < cum_j (the last kept id otherwise); Z_r == 0 (q' >= p' on
+//                p's support, i.e. equal): the same inversion through e_p — sd_sample_token on p_a with draw c + K
+//        a == K: sd_sample_token on p_K with draw c + K
+//   5. emitted d_1..d_a + the next token; the counter advances by K + 1; inactive rows consume nothing.
+// No launch of the shaped step evaluates a Philox block or a logarithm per vocabulary element:
+//   spec_draft_draw_shaped_kernel  one workgroup per row: copies the row to q[b][i], row_survivors (sample_device.h — the kept
+//                                  set sample_topk_kernel uses), inverts the uniform of 1., hands d_{i+1} over
+//   spec_stats_shaped_kernel       grid (K+1, B): the kept sets of q_i (re-selected from the stored row) and p_i, the lookup
+//                                  of d in both, ratio and flag, q' looked up for each of p's <= 1024 ids, the residual walk
+//   spec_accept_kernel             unchanged
 
 #include "engine.h"
 #include "sample_device.h"
@@ -346,6 +374,169 @@ int launch_spec_step(const SpecState& s, const void* target_logits, const void* 
   return launch_spec_kernels(sa, aa, s.B, st);
 }
 
+// ------------------------------------------------------------------------------------------ shaped variant (top-k / top-p)
+struct SpecShape {
+  int top_k;      // 1..kSampleMaxK after the clamp to V
+  float top_p;    // >= 1: no nucleus cut
+};
+
+static int check_spec_shape(const char* who, int top_k, float top_p) {
+  SD_REQUIRE(top_p == top_p && top_p > 0.f, "%s: top_p %g (must be > 0)", who, top_p);
+  SD_REQUIRE(top_k > 0, "%s: top_p = %g without top_k (the full-vocabulary nucleus) is not supported; give a top_k in 1..%d", who,
+             top_p, kSampleMaxK);
+  SD_REQUIRE(top_k <= kSampleMaxK, "%s: top_k=%d > %d is not supported", who, top_k, kSampleMaxK);
+  return 0;
+}
+
+__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(const SpecDrawArgs a, const SpecShape sh, SpecState s) {
+  __shared__ SurvivorLds L;
+  const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+  const uint16_t* src = a.src + (static_cast<size_t>(b) * a.src_rows_per_b + a.src_row) * V;
+  uint16_t* dst = a.q + (static_cast<size_t>(b) * s.K + a.i) * V;
+  if ((((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) && (V & 7) == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(src);
+    uint4* o = reinterpret_cast<uint4*>(dst);
+    for (int v = tid; v < (V >> 3); v += kSampleThreads) o[v] = p[v];
+  } else {
+    for (int i = tid; i < V; i += kSampleThreads) dst[i] = src[i];
+  }
+  row_survivors(L, src, SD_BF16, V, min(sh.top_k, V), a.temperature, sh.top_p);
+  if (tid == 0) {
+    const uint32_t c = a.draw[b] + static_cast<uint32_t>(a.i);
+    const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
+    const int d = static_cast<int>(L.sel[invert_weights(L.ev, L.n_keep, L.z, philox_uniform(c, sid, kTagCdf, a.seed_lo, a.seed_hi))]);
+    s.draft_tok[b * s.K + a.i] = d;
+    s.verify_tok[b * (s.K + 1) + a.i + 1] = d;
+    s.next_tok[b] = d;
+  }
+}
+
+int launch_spec_draft_draw_shaped(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
+                                  float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw,
+                                  const int32_t* stream_id, hipStream_t st) {
+  SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
+  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
+             "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+  if (int rc = check_spec_shape("spec_draft_draw", top_k, top_p)) return rc;
+  SpecDrawArgs a{};
+  a.src = static_cast<const uint16_t*>(src);
+  a.src_rows_per_b = src_rows_per_b;
+  a.src_row = src_row;
+  a.q = static_cast<uint16_t*>(q);
+  a.i = i;
+  a.V = V;
+  a.temperature = temperature;
+  a.seed_lo = static_cast<uint32_t>(seed);
+  a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.draw = draw;
+  a.stream_id = stream_id;
+  hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{top_k, top_p}, s);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+// position i of row b: flag + ratio (i < K) and the candidate next token. Static LDS: the survivor block (48 KB) + q's kept set
+// (12 KB); q's weights are overwritten by the residual once every lookup of q' has been made.
+__global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const SpecStatArgs a, const SpecShape sh) {
+  __shared__ SurvivorLds L;
+  __shared__ double qe[kSampleMaxK];
+  __shared__ int qi[kSampleMaxK];
+  __shared__ double s_ep, s_eq;
+  __shared__ int s_in_q;
+  const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, K = a.K, V = a.V;
+  if (a.active && a.active[b] == 0) return;
+  const uint16_t* rp = a.P + (static_cast<size_t>(b) * (K + 1) + i) * V;
+  const int k = min(sh.top_k, V);
+  const uint32_t c0 = a.draw ? a.draw[b] : a.draw0;
+  const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
+  int nq = 0;
+  double zq = 1.0;
+  if (i < K) {   // (workgroup-uniform) the kept set of q_i, parked in qi / qe
+    row_survivors(L, a.Q + (static_cast<size_t>(b) * K + i) * V, SD_BF16, V, k, a.temperature, sh.top_p);
+    nq = L.n_keep;
+    zq = L.z;
+    if (tid < nq) {
+      qi[tid] = static_cast<int>(L.sel[tid]);
+      qe[tid] = L.ev[tid];
+    }
+    if (tid == 0) { s_ep = 0.0; s_eq = 0.0; s_in_q = 0; }
+    __syncthreads();
+  }
+  row_survivors(L, rp, SD_BF16, V, k, a.temperature, sh.top_p);   // the kept set of p_i stays in L
+  const int np = L.n_keep;
+  const double zp = L.z;
+  if (i < K) {
+    // the drawn token in both kept sets (ids are unique inside a set: at most one thread writes each word)
+    const int d = a.draft_ids[b * K + i];
+    if (tid < np && static_cast<int>(L.sel[tid]) == d) s_ep = L.ev[tid];
+    if (tid < nq && qi[tid] == d) { s_eq = qe[tid]; s_in_q = 1; }
+    // residual weight of the target's j-th kept id
+    double r = 0.0;
+    if (tid < np) {
+      const int id = static_cast<int>(L.sel[tid]);
+      double eq = 0.0;
+      for (int t = 0; t < nq; ++t)
+        if (qi[t] == id) { eq = qe[t]; break; }
+      r = L.ev[tid] / zp - eq / zq;
+      r = r > 0.0 ? r : 0.0;
+    }
+    __syncthreads();
+    if (tid < np) qe[tid] = r;
+    if (tid == 0) {
+      const double ratio = s_in_q ? (s_ep / zp) / (s_eq / zq) : NAN;
+      const double u = philox_uniform(c0 + static_cast<uint32_t>(i), sid, kTagAccept, a.seed_lo, a.seed_hi);
+      a.flag[b * (K + 1) + i] = (u < ratio) ? 1 : 0;
+      if (a.ratios) a.ratios[b * K + i] = ratio;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double un = philox_uniform(c0 + static_cast<uint32_t>(K), sid, kTagCdf, a.seed_lo, a.seed_hi);
+    int pick = -1;
+    if (i < K) {
+      double zr = 0.0;
+      for (int j = 0; j < np; ++j) zr += qe[j];
+      if (zr > 0.0) pick = invert_weights(qe, np, zr, un);
+    }
+    if (pick < 0) pick = invert_weights(L.ev, np, zp, un);   // position K, or q' == p' on p's support: the target's own draw
+    a.cand[b * (K + 1) + i] = static_cast<int32_t>(L.sel[pick]);
+  }
+}
+
+static int launch_spec_kernels_shaped(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st) {
+  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && sa.V <= (1 << kIdxBits),
+             "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+  SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
+  if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
+  hipLaunchKernelGGL(spec_stats_shaped_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, SpecShape{top_k, top_p});
+  SD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_spec_step_shaped(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
+                            int top_k, float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag,
+                            int32_t* cand, hipStream_t st) {
+  SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
+  SpecStatArgs sa{};
+  sa.P = static_cast<const uint16_t*>(target_logits);
+  sa.Q = static_cast<const uint16_t*>(draft_logits);
+  sa.draft_ids = s.draft_tok;
+  sa.K = s.K;
+  sa.V = V;
+  sa.temperature = temperature;
+  sa.seed_lo = static_cast<uint32_t>(seed);
+  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
+  sa.draw = draw;
+  sa.stream_id = stream_id;
+  sa.active = s.active;
+  sa.flag = flag;
+  sa.cand = cand;
+  SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
+  return launch_spec_kernels_shaped(sa, aa, s.B, top_k, top_p, st);
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -386,4 +577,42 @@ extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* targe
   sa.ratios = ratios_out;
   SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
   return launch_spec_kernels(sa, aa, B, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
+                                            int V, float temperature, int top_k, float top_p, uint64_t seed, uint32_t* draw_counters,
+                                            uint32_t draw0, const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out,
+                                            int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  clear_error();
+  SD_REQUIRE(top_p == top_p && top_p > 0.f, "spec_sample_accept_shaped: top_p %g (must be > 0)", top_p);
+  SD_REQUIRE(top_k > 0, "spec_sample_accept_shaped: top_k=%d with top_p=%g: the shaped op needs a top_k in 1..1024 (top_p without top_k, "
+             "the full-vocabulary nucleus, is not supported; the unshaped op is sd_spec_sample_accept)", top_k, top_p);
+  SD_REQUIRE(top_k <= kSampleMaxK, "spec_sample_accept_shaped: top_k=%d > %d is not supported", top_k, kSampleMaxK);
+  SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "spec_sample_accept_shaped: NULL argument");
+  SD_REQUIRE(B >= 1 && K >= 1, "spec_sample_accept_shaped: B=%d K=%d", B, K);
+  SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "spec_sample_accept_shaped: workspace %zu B < %zu B", workspace_bytes,
+             sd_spec_sample_workspace(B, K));
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && (!ratios_out || (reinterpret_cast<uintptr_t>(ratios_out) & 7) == 0),
+             "spec_sample_accept_shaped: misaligned workspace / ratios");
+  int32_t* flag = static_cast<int32_t*>(workspace);
+  int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
+  SpecStatArgs sa{};
+  sa.P = static_cast<const uint16_t*>(target_logits);
+  sa.Q = static_cast<const uint16_t*>(draft_logits);
+  sa.draft_ids = draft_ids;
+  sa.K = K;
+  sa.V = V;
+  sa.temperature = temperature;
+  sa.seed_lo = static_cast<uint32_t>(seed);
+  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
+  sa.draw = draw_counters;
+  sa.draw0 = draw0;
+  sa.stream_id = stream_ids;
+  sa.active = active;
+  sa.flag = flag;
+  sa.cand = cand;
+  sa.ratios = ratios_out;
+  SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
+  return launch_spec_kernels_shaped(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
 }

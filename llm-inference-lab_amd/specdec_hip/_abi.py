@@ -54,6 +54,11 @@ SIGNATURES = {
         [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p, ctypes.c_uint32,
          _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
     ),
+    "sd_spec_sample_accept_shaped": (
+        _c_int,
+        [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_float, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p,
+         ctypes.c_uint32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
+    ),
     "sd_kv_append": (
         _c_int,
         [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
@@ -112,6 +117,7 @@ SIGNATURES = {
                                          _c_void_p, _c_size, _c_void_p, _c_void_p]),
     "sd_specdec_set_spec_sampling": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p, _c_size,
                                               _c_void_p, _c_size, _c_void_p, _c_void_p]),
+    "sd_specdec_set_spec_shaping": (_c_int, [_c_void_p, _c_int, ctypes.c_float]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),

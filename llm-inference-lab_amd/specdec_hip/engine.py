@@ -450,6 +450,7 @@ class HipSpecDec:
             self.stream_d = torch.cuda.Stream(self.device)
         # sampling modes (set_sampling / set_spec_sampling): off; their buffers are allocated at first use and kept
         self.sampling = self.spec_sampling = False
+        self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
         self.rec_ints = self.lib.sd_specdec_record_ints(self.handle)
         ptr = self.lib.sd_specdec_record(self.handle)
@@ -548,17 +549,23 @@ class HipSpecDec:
             self.sampling = True
 
     def set_spec_sampling(self, enable: bool, temperature: float = 1.0, seed: int = 0, stream_ids: Optional[Sequence[int]] = None,
-                          draw_counts: Optional[Sequence[int]] = None):
+                          draw_counts: Optional[Sequence[int]] = None, top_k: Optional[int] = None, top_p: Optional[float] = None):
         """Speculative sampling inside the step (sd_specdec_set_spec_sampling): draft tokens drawn from the draft's
         distribution, accepted with probability min(1, p/q), the first rejection redrawn from the residual — the output is
         distributed as the target's own sampling at `temperature`. The loop owns the two logits buffers (`spec_draft_logits`
-        [B][K][V], `step_logits` [B][K+1][V]) and the draw counters (K + 1 per row and step; start at `draw_counts`)."""
+        [B][K][V], `step_logits` [B][K+1][V]) and the draw counters (K + 1 per row and step; start at `draw_counts`).
+        `top_k` (1..1024), optionally with `top_p` < 1, shapes BOTH distributions as sd_sample_token does
+        (sd_specdec_set_spec_shaping): the output is then distributed as the target's own top-k / top-p sampling. Without
+        them the mode samples the whole vocabulary; `top_p` without `top_k` is refused."""
         with torch.cuda.device(self.device):
             if not enable:
                 _abi.check(self.lib.sd_specdec_set_spec_sampling(self.handle, 0, 1.0, 0, None, 0, None, 0, None, None),
                            "sd_specdec_set_spec_sampling")
                 self.spec_sampling = False
                 return
+            _abi.check(self.lib.sd_specdec_set_spec_shaping(self.handle, int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p)),
+                       "sd_specdec_set_spec_shaping")
+            self.spec_shape = (int(top_k), 1.0 if top_p is None else float(top_p)) if top_k else None
             V = self.target.weights.config.vocab
             if self._logits is None:
                 self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)

@@ -349,8 +349,11 @@ def sample_token_hip(logits: torch.Tensor, temperature: float, top_k: Optional[i
 def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor, temperature: float,
                            seed: int = 0, draw: int = 0, draw_counters: Optional[torch.Tensor] = None,
                            stream_ids: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
-                           return_ratios: bool = False):
-    """Acceptance and next token of speculative sampling (sd_spec_sample_accept) on caller tensors.
+                           return_ratios: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None):
+    """Acceptance and next token of speculative sampling (sd_spec_sample_accept) on caller tensors. With `top_k` (1..1024),
+    optionally `top_p` < 1, both distributions are shaped as sd_sample_token shapes them (sd_spec_sample_accept_shaped: the
+    draft ids are then draws of sample_token_hip(q_i, top_k, top_p), the next token an inversion draw); `top_p` without
+    `top_k` is refused by the library.
 
     draft_logits bf16 [B, K, V] (q_i), target_logits bf16 [B, K+1, V] (p_i), draft_ids int32 [B, K] (the tokens drawn from
     q_i). Returns (accept_len int32 [B], next_tok int32 [B]) and, with return_ratios, the float64 [B, K] ratios
@@ -374,6 +377,14 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
     ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    if top_k or (top_p is not None and float(top_p) < 1.0):
+        with torch.cuda.device(dev):
+            _abi.check(lib.sd_spec_sample_accept_shaped(
+                draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V, float(temperature),
+                int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p), int(seed) & (2 ** 64 - 1), ptr(draw_counters),
+                int(draw) & 0xFFFFFFFF, ptr(stream_ids), ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios), ws.data_ptr(),
+                ws.numel(), _stream_ptr(dev)), "sd_spec_sample_accept_shaped")
+        return (accept, nxt, ratios) if return_ratios else (accept, nxt)
     with torch.cuda.device(dev):
         _abi.check(lib.sd_spec_sample_accept(draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V,
                                              float(temperature), int(seed) & (2 ** 64 - 1), ptr(draw_counters), int(draw) & 0xFFFFFFFF,

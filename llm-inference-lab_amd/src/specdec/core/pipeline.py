@@ -183,6 +183,18 @@ class SpeculativePipeline:
                 raise NotImplementedError("policy='rejection' with backend='device' needs the HIP engine (implementation='hip')")
             if not float((policy_params or {}).get("temperature", 1.0)) > 0:
                 raise ValueError("policy='rejection' with backend='device' needs temperature > 0")
+            # the policy shapes the mode: top_k (1..1024), optionally with top_p, as sd_sample_token defines them
+            tk, tp = self.policy.top_k, self.policy.top_p
+            if tk is not None and not 1 <= tk <= 1024:
+                raise NotImplementedError(f"policy='rejection' (backend='device'): top_k={tk} is outside 1..1024")
+            if tp is not None and not tp > 0:
+                raise ValueError(f"policy='rejection' (backend='device'): top_p={tp} (must be > 0)")
+            if tk is None and tp is not None and tp < 1.0:
+                raise NotImplementedError("policy='rejection' (backend='device'): top_p without top_k (the full-vocabulary nucleus) is not "
+                                          "supported; give a top_k in 1..1024")
+        elif policy == "rejection" and any((policy_params or {}).get(key) is not None for key in ("top_k", "top_p")):
+            raise NotImplementedError("policy='rejection' with backend='host' is unshaped: top_k / top_p in policy_params belong to "
+                                      "backend='device'")
         if policy != "longest_prefix" and (mode != "vanilla" or medusa_heads is not None):
             raise NotImplementedError(f"policy={policy!r} drafts with the draft model (draft_mode='vanilla')")
         self.controller = create_controller(controller, **(controller_params or {}))
@@ -535,16 +547,17 @@ class SpeculativePipeline:
                 "top_p": None if top_p is None else float(top_p), "seed": int(kwargs.get("seed", self.config.get("seed") or 0))}
 
     def _spec_sampling_config(self, kwargs: Dict[str, Any]) -> Dict[str, Any]:
-        """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature and
-        seed. What the mode does not do is refused, not approximated."""
+        """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature,
+        seed, top_k and top_p (policy_params; call-level top_k / top_p stay refused: the policy shapes the mode). What the mode
+        does not do is refused, not approximated."""
         from ..policies.controllers import FixedKController
 
         if kwargs.get("top_k") or (kwargs.get("top_p") is not None and float(kwargs["top_p"]) < 1.0):
             raise NotImplementedError("policy='rejection' (backend='device'): top-k / top-p shaping of the two distributions is not supported")
         if not isinstance(self.controller, FixedKController):
             raise NotImplementedError("policy='rejection' (backend='device') keeps a fixed K (controller='fixed'): adaptive K is not supported")
-        return {"spec": True, "temperature": float(self.policy.temperature), "top_k": None, "top_p": None,
-                "seed": int(kwargs.get("seed", self.policy.seed))}
+        return {"spec": True, "temperature": float(self.policy.temperature), "top_k": self.policy.top_k,
+                "top_p": self.policy.top_p if self.policy.top_k else None, "seed": int(kwargs.get("seed", self.policy.seed))}
 
     def generate(self, prompt: PromptLike, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  do_sample: Optional[bool] = None, **kwargs) -> Dict[str, Any]:
@@ -851,7 +864,7 @@ class DecodeSession:
             if self.per_row or self.self_draft:
                 raise NotImplementedError("speculative sampling needs a draft model and a fixed K")
             self.loop.set_spec_sampling(True, sp["temperature"], sp["seed"], stream_ids=list(range(len(self.rows))),
-                                        draw_counts=[r.draws for r in self.rows])
+                                        draw_counts=[r.draws for r in self.rows], top_k=sp["top_k"], top_p=sp["top_p"])
             return
         self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
                                stream_ids=list(range(len(self.rows))), draw_counts=[r.draws for r in self.rows])

@@ -166,9 +166,13 @@ class RejectionSamplingPolicy(AcceptancePolicy):
     `seed` (or are passed in: `uniforms=`), so a run is reproducible and a CPU restatement (oracle/hostlogic_ref.py:
     rejection_accept) replays it. All arithmetic is float64 on the tensors' device."""
 
-    def __init__(self, temperature: float = 1.0, seed: int = 0):
+    def __init__(self, temperature: float = 1.0, seed: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None):
         self.temperature = float(temperature)
         self.seed = int(seed)
+        # the shape of both distributions on the DEVICE backend (the captured step); this class's own arithmetic — the host
+        # backend — is unshaped, and the pipeline refuses the two keys there
+        self.top_k = int(top_k) if top_k else None
+        self.top_p = None if top_p is None else float(top_p)
         self.name = "rejection"
         self._gen = torch.Generator().manual_seed(self.seed)
 
@@ -219,7 +223,8 @@ def create_policy(policy_name: str, **kwargs: Any) -> AcceptancePolicy:
         "conf_threshold": lambda: ConfidenceThresholdPolicy(kwargs.get("tau", 0.5)),
         "topk_agree": lambda: TopKAgreementPolicy(kwargs.get("k", 5)),
         "typical": lambda: TypicalAcceptancePolicy(kwargs.get("p", 0.9)),
-        "rejection": lambda: RejectionSamplingPolicy(kwargs.get("temperature", 1.0), kwargs.get("seed", 0)),
+        "rejection": lambda: RejectionSamplingPolicy(kwargs.get("temperature", 1.0), kwargs.get("seed", 0), kwargs.get("top_k"),
+                                                     kwargs.get("top_p")),
     }
     if policy_name not in makers:
         raise ValueError(f"Unknown policy: {policy_name}. Available: {list(makers.keys())}")

@@ -39,6 +39,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--spec-sampling", action="store_true",
                     help="speculative sampling inside the captured step (policy 'rejection', backend 'device'): the output is "
                          "distributed as the target's own sampling at --temperature; drawn with --seed; fixed K, draft-model mode")
+    ap.add_argument("--spec-top-k", type=int, help="--spec-sampling: keep the top_k (1..1024) largest logits of both distributions")
+    ap.add_argument("--spec-top-p", type=float, help="--spec-sampling: nucleus cut inside --spec-top-k (needs it)")
     ap.add_argument("--controller", type=str, choices=["fixed", "adaptive"], default="fixed")
     ap.add_argument("--K", type=int, default=4, help="K of the fixed controller")
     ap.add_argument("--adaptive-K", action="store_true")
@@ -91,6 +93,10 @@ def main(argv=None) -> int:
             return 1
         policy, pp = "rejection", {"backend": "device", "temperature": 0.7 if args.temperature is None else args.temperature,
                                "seed": 0 if args.seed is None else args.seed}   # (the pipeline refuses a temperature <= 0)
+        pp.update({k: v for k, v in (("top_k", args.spec_top_k), ("top_p", args.spec_top_p)) if v is not None})
+    elif args.spec_top_k is not None or args.spec_top_p is not None:
+        logging.error("--spec-top-k / --spec-top-p belong to --spec-sampling")
+        return 1
     try:
         pipe = SpeculativePipeline(config_path=args.config, base_model=args.base_model, draft_model=args.draft_model,
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,

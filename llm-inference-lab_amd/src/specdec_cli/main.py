@@ -44,6 +44,11 @@ def cmd_bench(args: argparse.Namespace) -> int:
 def cmd_run(args: argparse.Namespace) -> int:
     spec = getattr(args, "spec_sampling", False)
     extra = {"policy": "rejection", "policy_params": {"backend": "device", "temperature": args.temperature, "seed": args.seed}} if spec else {}
+    shape = {k: v for k, v in (("top_k", args.spec_top_k), ("top_p", args.spec_top_p)) if v is not None}
+    if shape and not spec:
+        raise SystemExit("--spec-top-k / --spec-top-p belong to --spec-sampling")
+    if spec:
+        extra["policy_params"].update(shape)
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
                                draft_mode="vanilla", **extra)
@@ -82,6 +87,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--do-sample", action="store_true")
     pr.add_argument("--spec-sampling", action="store_true",
                     help="speculative sampling on the device (policy 'rejection', backend 'device') at --temperature, drawn with --seed")
+    pr.add_argument("--spec-top-k", type=int, help="--spec-sampling: keep the top_k (1..1024) largest logits of both distributions")
+    pr.add_argument("--spec-top-p", type=float, help="--spec-sampling: nucleus cut inside --spec-top-k (needs it)")
     pr.add_argument("--seed", type=int, default=0)
     pr.add_argument("prompt", type=str)
     pr.set_defaults(func=cmd_run)

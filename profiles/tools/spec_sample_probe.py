@@ -1,13 +1,17 @@
 """Cost of speculative sampling inside the captured step (csrc/spec_sample.hip) on the headline pair (synthetic Llama-3.2-3B
 target + 1B draft, K = 4, bf16):
 
-  steps    ms per captured step of the greedy step, the sampled-bonus step (T 0.7, top_k 50, top_p 0.9) and the
-           speculative-sampling step, 1 row and 8 rows, the device advancing its own state (no host rule between steps);
+  steps    ms per captured step of the greedy step, the sampled-bonus step (T 0.7, top_k 50, top_p 0.9), the
+           speculative-sampling step and its top-k / top-p shaped variant (top_k 50, top_p 0.9), 1 row and 8 rows, the device
+           advancing its own state (no host rule between steps); --modes picks a subset (a library without the shaped
+           variant: --modes greedy,sampled-bonus,speculative);
   decode   tokens/s of generate_batch(policy="rejection") with backend="device" against backend="host" (the host loop);
-  trace    a short run of the speculative-sampling step alone, for `rocprofv3 --kernel-trace --stats -- python ... trace`.
+  trace    a short run of the speculative-sampling step alone, for `rocprofv3 --kernel-trace --stats -- python ... trace`;
+  trace-shaped   the same for the shaped step.
 
-`python profiles/tools/spec_sample_probe.py {steps,decode,trace} [--rows 1,8] [--steps 60]`. Run each leg in a process of
-its own with a time limit (`timeout -k 10 600 python ...`); results are written up in profiles/spec_sampling.md."""
+`python profiles/tools/spec_sample_probe.py {steps,decode,trace,trace-shaped} [--rows 1,8] [--steps 60]`. Run each leg in a
+process of its own with a time limit (`timeout -k 10 600 python ...`); results are written up in profiles/spec_sampling.md
+and profiles/spec_sampling_shaped.md."""
 import argparse
 import os
 import sys
@@ -21,7 +25,8 @@ from specdec_hip.engine import HipSpecDec  # noqa: E402
 from src.specdec import HipLM, SpeculativePipeline  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("leg", choices=["steps", "decode", "trace"])
+ap.add_argument("leg", choices=["steps", "decode", "trace", "trace-shaped"])
+ap.add_argument("--modes", default="greedy,sampled-bonus,speculative,shaped")
 ap.add_argument("--rows", default="1,8")
 ap.add_argument("--steps", type=int, default=60)
 ap.add_argument("--k", type=int, default=4)
@@ -71,12 +76,14 @@ def mode_steps(B, mode, n):
         loop.set_sampling(True, T, 50, 0.9, 1234)
     elif mode == "speculative":
         loop.set_spec_sampling(True, T, 1234)
+    elif mode == "shaped":
+        loop.set_spec_sampling(True, T, 1234, top_k=50, top_p=0.9)
     ms = time_steps(loop, n)
     rec = loop.sync()
     acc = float(rec.accept_len.mean())
     if mode == "sampled-bonus":
         loop.set_sampling(False)
-    elif mode == "speculative":
+    elif mode in ("speculative", "shaped"):
         loop.set_spec_sampling(False)
     sess.finish()
     return ms, acc
@@ -84,8 +91,8 @@ def mode_steps(B, mode, n):
 
 if args.leg == "steps":
     for B in [int(x) for x in args.rows.split(",")]:
-        res = {m: mode_steps(B, m, args.steps) for m in ("greedy", "sampled-bonus", "speculative")}
-        g = res["greedy"][0]
+        res = {m: mode_steps(B, m, args.steps) for m in args.modes.split(",")}
+        g = next(iter(res.values()))[0]
         print(f"3B + 1B, K={K}, {B} row(s), bf16, T={T}: " + ", ".join(
             f"{m} {ms:.3f} ms/step (x{ms / g:.3f}, last accept length {a:.2f})" for m, (ms, a) in res.items()), flush=True)
 elif args.leg == "decode":
@@ -107,5 +114,6 @@ elif args.leg == "decode":
             f"{b} {tps:.1f} tokens/s ({n} tokens, accepted/proposed {ar:.2f})" for b, (tps, n, ar) in out.items())
             + f" -> device / host = {out['device'][0] / out['host'][0]:.2f}", flush=True)
 else:
-    ms, _ = mode_steps(1, "speculative", 20)
-    print(f"trace leg: speculative step {ms:.3f} ms/step under the profiler", flush=True)
+    mode = "shaped" if args.leg == "trace-shaped" else "speculative"
+    ms, _ = mode_steps(1, mode, 20)
+    print(f"trace leg: {mode} step {ms:.3f} ms/step under the profiler", flush=True)
