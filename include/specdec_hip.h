@@ -118,6 +118,23 @@ int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_lo
                                  const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
                                  double* ratios_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Draft-target agreement of two logit blocks (csrc/spec_agree.hip): how much of the target's distribution a draft reproduces,
+ * position by position, without generating. draft_logits / target_logits: bf16, n rows of V elements, rows ld_q / ld_p
+ * elements apart (>= V). Per row t, in float64 over the stored bf16 values, x / T as sd_spec_sample_accept forms it (T the
+ * float32 temperature widened to double, no division when T == 1), a_v = P[t][v]/T - lse(P[t]/T), b_v likewise from Q:
+ *   alpha[t] = sum_v min(exp a_v, exp b_v)   the acceptance probability of speculative sampling at that position, 1 - TV(p, q)
+ *   kl[t]    = sum_v exp(a_v) (a_v - b_v)    KL(p || q) over the v with P[t][v] > -inf; +inf when q(v) = 0 under p(v) > 0
+ *   p_arg[t], q_arg[t]                       argmax ids (NaN first, larger value, lower index); agree[t] = (p_arg == q_arg)
+ * A row pair with a NaN in either row, or a maximum that is not finite, gives alpha = kl = NaN. Every output may be NULL.
+ * Bit-identical run to run; row t's outputs do not depend on n or on the other rows. workspace: sd_spec_agreement_workspace(n, V)
+ * bytes of device scratch, 16-byte aligned. Asynchronous on `stream`, no allocation, graph-capturable. Refused (nonzero +
+ * sd_last_error, before any device work): NULL logits, n < 1 or V < 1, a stride below V, temperature not > 0 or NaN, a short or
+ * misaligned workspace. */
+size_t sd_spec_agreement_workspace(int n, int V);
+int sd_spec_agreement(const void* draft_logits, int64_t ld_q, const void* target_logits, int64_t ld_p, int n, int V, float temperature,
+                      double* alpha, double* kl, int32_t* agree, int32_t* p_arg, int32_t* q_arg, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * kv_append (in place) — the KV-append path
  *   reference contract: kv_append_ref, src/kernels/reference.py:59-93
@@ -317,6 +334,13 @@ int sd_model_hidden_rows(sd_model* m, int row0, int n, void* out, void* stream);
  * d_model not a multiple of 64, an unbound model, row / positions out of range, a capturing stream. */
 int sd_model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0,
                    float* logprob, int32_t* greedy, void* stream);
+
+/* sd_model_score with one difference: the head STORES each position's logits — logits_bf16[i][v], bf16 [n][vocab] contiguous, HF
+ * row order, the bf16 value the score epilogue forms — instead of reducing them to a log-probability. Layer route, chunking, cache
+ * effect, sd_model_prefill_count accounting and greedy (may be NULL) are sd_model_score's; n >= 1. The refusals are
+ * sd_model_score's, plus NULL logits. Unlike sd_model_forward with logits_out it keeps the GEMM prefill route. */
+int sd_model_score_logits(sd_model* m, const int32_t* tokens, int n, int row, int pos0,
+                          void* logits_bf16, int32_t* greedy, void* stream);
 
 /* Measurement hook for bench.py's roofline leg: launches ONE of the forward's weight-
  * streaming GEMVs (which: 1 = attention out-proj, 2 = norm+gate/up+SwiGLU, 3 = down-proj,

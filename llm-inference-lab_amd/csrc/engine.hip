@@ -491,16 +491,18 @@ static int score_ws(sd_model* m, ScoreWs& w) {
   return 0;
 }
 
-// the head over rows [m0, m0 + mc) of the sequence, left by the layers at x (rows ldx apart)
+// the head over rows [m0, m0 + mc) of the sequence, left by the layers at x (rows ldx apart); logits (sd_model_score_logits): bf16 [n][vocab]
 static int score_chunk(sd_model* m, const ScoreWs& w, const uint16_t* x, int ldx, int mc, const int32_t* tokens, int n, int m0, float* logprob,
-                       int32_t* greedy, hipStream_t st) {
-  const int n_target = (n - 1 - m0 < mc) ? n - 1 - m0 : mc;   // token m0 + t predicts tokens[m0 + t + 1]
+                       int32_t* greedy, uint16_t* logits, hipStream_t st) {
+  const int n_target = logits ? 0 : ((n - 1 - m0 < mc) ? n - 1 - m0 : mc);   // token m0 + t predicts tokens[m0 + t + 1]
   if (int rc = launch_final_norm_rows(m->cfg, x, ldx, mc, w.xn, st)) return rc;
   return launch_score_head(m->native_plan, m->packed[4 * m->cfg.n_layers], m->scale(4 * m->cfg.n_layers), m->w8(), w.xn, mc, tokens + m0 + 1,
-                           n_target, w.part, w.tgt, logprob ? logprob + m0 : nullptr, greedy ? greedy + m0 : nullptr, st);
+                           n_target, w.part, w.tgt, logprob ? logprob + m0 : nullptr, greedy ? greedy + m0 : nullptr,
+                           logits ? logits + static_cast<size_t>(m0) * m->cfg.vocab : nullptr, st);
 }
 
-static int model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, hipStream_t st) {
+static int model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, uint16_t* logits,
+                       hipStream_t st) {
   if (!m->native_plan.buf)
     if (int rc = native_plan_build(m->cfg, m->native_plan)) return rc;
   ScoreWs w{};
@@ -510,15 +512,33 @@ static int model_score(sd_model* m, const int32_t* tokens, int n, int row, int p
   if (backend >= 0) m->prefill_count[backend] += 1;
   if (backend > SD_PREFILL_PASSES)
     return prefill_row(m, backend, tokens, w.zero, pos0, row, n, st, [&](int m0, int mc, const uint16_t* xr) {
-      return score_chunk(m, w, xr, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st);
+      return score_chunk(m, w, xr, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, logits, st);
     });
   // the passes: one pass when n fits, else chunks of `cap` positions in position order; the head over each pass's residual rows
   const int cap = (n <= m->small_t) ? m->small_t : m->max_t;
   for (int m0 = 0; m0 < n; m0 += cap) {
     const int mc = (n - m0 < cap) ? n - m0 : cap;
     if (int rc = forward_pass(m, tokens + m0, n, w.zero, pos0 + m0, row, 0, 1, mc, nullptr, mc, nullptr, SD_BF16, m->cfg.vocab, 1, st)) return rc;
-    if (int rc = score_chunk(m, w, m->x, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, st)) return rc;
+    if (int rc = score_chunk(m, w, m->x, m->cfg.d_model, mc, tokens, n, m0, logprob, greedy, logits, st)) return rc;
   }
+  return 0;
+}
+
+// the refusals sd_model_score and sd_model_score_logits share (n_min: 2 for a log-likelihood, 1 for logits)
+static int score_checks(sd_model* m, const int32_t* tokens, int n, int n_min, int row, int pos0, hipStream_t st) {
+  SD_REQUIRE(m, "score: NULL model");
+  SD_REQUIRE(tokens, "score: NULL tokens");
+  SD_REQUIRE(n >= 2 || n_min < 2, "score: n=%d tokens (a log-likelihood needs at least 2)", n);
+  SD_REQUIRE(n >= n_min, "score: n=%d tokens", n);
+  SD_REQUIRE(m->is_packed(), "score: the head reads the packed lm_head (this model has none: SPECDEC_NO_PACK)");
+  SD_REQUIRE(m->cfg.d_model % 64 == 0, "score: d_model=%d is not a multiple of 64 (the head GEMM's k stage)", m->cfg.d_model);
+  SD_REQUIRE(m->k_cache && m->x, "score: model not bound (sd_model_bind)");
+  SD_REQUIRE(row >= 0 && row < m->B, "score: row %d outside the bound batch of %d", row, m->B);
+  SD_REQUIRE(pos0 >= 0 && pos0 + n <= m->Lmax && pos0 + n <= m->cfg.max_pos, "score: positions [%d,%d) outside the cache rows (%d) / max_pos (%d)",
+             pos0, pos0 + n, m->Lmax, m->cfg.max_pos);
+  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+  SD_HIP_CHECK(hipStreamIsCapturing(st, &cap_st));
+  SD_REQUIRE(cap_st == hipStreamCaptureStatusNone, "score: the stream is capturing (score allocates its workspace and picks its route on the host)");
   return 0;
 }
 
@@ -833,20 +853,18 @@ extern "C" int sd_model_forward(sd_model* m, const int32_t* tokens, int tok_stri
 
 extern "C" int sd_model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, void* stream) {
   clear_error();
-  SD_REQUIRE(m, "score: NULL model");
-  SD_REQUIRE(tokens, "score: NULL tokens");
-  SD_REQUIRE(n >= 2, "score: n=%d tokens (a log-likelihood needs at least 2)", n);
-  SD_REQUIRE(m->is_packed(), "score: the head reads the packed lm_head (this model has none: SPECDEC_NO_PACK)");
-  SD_REQUIRE(m->cfg.d_model % 64 == 0, "score: d_model=%d is not a multiple of 64 (the head GEMM's k stage)", m->cfg.d_model);
-  SD_REQUIRE(m->k_cache && m->x, "score: model not bound (sd_model_bind)");
-  SD_REQUIRE(row >= 0 && row < m->B, "score: row %d outside the bound batch of %d", row, m->B);
-  SD_REQUIRE(pos0 >= 0 && pos0 + n <= m->Lmax && pos0 + n <= m->cfg.max_pos, "score: positions [%d,%d) outside the cache rows (%d) / max_pos (%d)",
-             pos0, pos0 + n, m->Lmax, m->cfg.max_pos);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-  SD_HIP_CHECK(hipStreamIsCapturing(st, &cap_st));
-  SD_REQUIRE(cap_st == hipStreamCaptureStatusNone, "score: the stream is capturing (score allocates its workspace and picks its route on the host)");
-  return model_score(m, tokens, n, row, pos0, logprob, greedy, st);
+  if (int rc = score_checks(m, tokens, n, 2, row, pos0, st)) return rc;
+  return model_score(m, tokens, n, row, pos0, logprob, greedy, nullptr, st);
+}
+
+extern "C" int sd_model_score_logits(sd_model* m, const int32_t* tokens, int n, int row, int pos0, void* logits_bf16, int32_t* greedy,
+                                     void* stream) {
+  clear_error();
+  SD_REQUIRE(logits_bf16, "score_logits: NULL logits");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = score_checks(m, tokens, n, 1, row, pos0, st)) return rc;
+  return model_score(m, tokens, n, row, pos0, nullptr, greedy, static_cast<uint16_t*>(logits_bf16), st);
 }
 
 extern "C" int sd_model_hidden_rows(sd_model* m, int row0, int n, void* out, void* stream) {

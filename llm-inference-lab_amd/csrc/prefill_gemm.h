@@ -37,8 +37,10 @@ int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const 
 size_t score_partial_bytes(const NativePlan& plan);
 // Xn: T <= kPrefillChunk normed rows (bf16 [T][d_model]). target[t] (t < n_target): the row whose logit gives logprob[t] = l_target - lse;
 // greedy[t] = argmax row (either may be null). part / tgt_logit: score_partial_bytes / T floats of workspace.
+// logits != null (sd_model_score_logits): every token's logits are stored as bf16 [T][vocab] as well, greedy as before, and target /
+// logprob are not used.
 int launch_score_head(const NativePlan& plan, const void* W, const float* w_scale, bool w8, const uint16_t* Xn, int T, const int32_t* target,
-                      int n_target, float4* part, float* tgt_logit, float* logprob, int32_t* greedy, hipStream_t st);
+                      int n_target, float4* part, float* tgt_logit, float* logprob, int32_t* greedy, uint16_t* logits, hipStream_t st);
 
 enum PrefillGemm { PREFILL_GEMM_ROCBLAS = 0, PREFILL_GEMM_NATIVE = 1 };
 

@@ -31,6 +31,8 @@ struct MfmaArgs {
   float* tgt_logit;         // [T] logit of row target[t]
   float4* part;             // [T][n_blocks] {max, sum of exp(l - max), argmax value, argmax row (int bits)}
   int n_target;
+  // score_logits_kernel (csrc/score_head.hip) only
+  uint16_t* logits;         // bf16 [T][N], HF row order: every token's logits as the score epilogue forms them
 };
 
 __device__ __forceinline__ void glds16(const char* src, char* lds_wave_base) {

@@ -12,6 +12,9 @@
 //     logit. The pad row of an odd vocabulary (hrow = -1) takes no part. No atomics.
 //   * score_finalize_kernel — one workgroup per token folds the token's partials in a fixed order (thread i: blocks i, i + 256,
 //     ...; then a fixed tree) and writes lse = M + log S, logprob = l_target - lse and the greedy row. Bit-identical run to run.
+//   * score_logits_kernel<RF, W8> (sd_model_score_logits) — a second epilogue over the same main loop: each token's logit, the same
+//     bf16 value, is STORED to logits[t][HF row] (the pad row of an odd vocabulary is not) and folded into the same partials, so
+//     score_finalize_kernel returns the greedy rows sd_model_score returns. It keeps no target logit.
 
 #include "prefill_mfma_device.h"
 
@@ -92,6 +95,62 @@ __global__ __launch_bounds__(kThreads, 2) void score_head_kernel(MfmaArgs a) {
   }
 }
 
+template <int RF, bool W8>
+__global__ __launch_bounds__(kThreads, 2) void score_logits_kernel(MfmaArgs a) {
+  __shared__ __attribute__((aligned(16))) char smem[mfma_smem_bytes<RF, W8>()];
+  f32x4_t acc[4][RF];
+  int hrow[RF], t0, rb;
+  mfma_block_product<RF, W8>(a, smem, acc, hrow, t0, rb);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wt = wave & 1, wr = wave >> 1, g = lane >> 4, n = lane & 15;
+  float sc[RF];
+#pragma unroll
+  for (int f = 0; f < RF; ++f) sc[f] = (W8 && hrow[f] >= 0) ? a.w_scale[hrow[f]] : 1.0f;
+
+  __syncthreads();   // every wave is done with the stage buffers: the first 4 KiB hold the row halves' partials
+  float4* red = reinterpret_cast<float4*>(smem);   // [wr][128 tokens]
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int tl = wt * 64 + q * 16 + 4 * g + e, t = t0 + tl;
+      uint16_t* out = a.logits + static_cast<size_t>(t) * a.N;
+      float l[RF];
+      float m = -INFINITY;
+#pragma unroll
+      for (int f = 0; f < RF; ++f) {
+        const uint16_t bits = float_to_bf16_bits(acc[q][f][e] * sc[f]);   // the logit EPI_ARGMAX forms
+        l[f] = bf16_bits_to_float(bits);
+        if (hrow[f] >= 0) {
+          m = fmaxf(m, l[f]);
+          if (t < a.T) out[hrow[f]] = bits;
+        }
+      }
+      float4 p = {m, 0.f, -INFINITY, __int_as_float(0x7fffffff)};
+#pragma unroll
+      for (int f = 0; f < RF; ++f)
+        if (hrow[f] >= 0) {
+          if (m != -INFINITY) p.y += expf(l[f] - m);
+          if (argmax_better(l[f], hrow[f], p.z, __float_as_int(p.w))) {
+            p.z = l[f];
+            p.w = __int_as_float(hrow[f]);
+          }
+        }
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) {
+        const float4 o = {__shfl_xor(p.x, off, 64), __shfl_xor(p.y, off, 64), __shfl_xor(p.z, off, 64), __shfl_xor(p.w, off, 64)};
+        fold(p, o);
+      }
+      if (n == 0) red[wr * kBT + tl] = p;
+    }
+  __syncthreads();
+  if (tid < kBT && t0 + tid < a.T) {
+    float4 p = red[tid];
+    fold(p, red[kBT + tid]);
+    a.part[static_cast<size_t>(t0 + tid) * a.n_blocks + rb] = p;
+  }
+}
+
 // token blockIdx.x: fold its n_blocks partials -> lse; logprob (t < n_target) and greedy row
 __global__ __launch_bounds__(kFinThreads) void score_finalize_kernel(const float4* part, int n_blocks, const float* tgt_logit, int n_target,
                                                                      float* logprob, int32_t* greedy) {
@@ -126,7 +185,7 @@ size_t score_partial_bytes(const NativePlan& plan) {
 }
 
 int launch_score_head(const NativePlan& plan, const void* W, const float* w_scale, bool w8, const uint16_t* Xn, int T, const int32_t* target,
-                      int n_target, float4* part, float* tgt_logit, float* logprob, int32_t* greedy, hipStream_t st) {
+                      int n_target, float4* part, float* tgt_logit, float* logprob, int32_t* greedy, uint16_t* logits, hipStream_t st) {
   SD_REQUIRE(plan.buf && plan.mat[4][0].tiles, "score: lm_head plan not built");
   SD_REQUIRE(T >= 1 && T <= kPrefillChunk && n_target >= 0 && n_target <= T, "score: head over %d rows (%d targets)", T, n_target);
   SD_REQUIRE(W && Xn && part && tgt_logit && (!w8 || w_scale) && (n_target == 0 || target), "score: head with a NULL operand");
@@ -153,9 +212,23 @@ int launch_score_head(const NativePlan& plan, const void* W, const float* w_scal
   a.tgt_logit = tgt_logit;
   a.part = part;
   a.n_target = n_target;
+  a.logits = logits;
+  const dim3 grid(m.n_blocks * n_tb), block(kThreads);
+  if (logits) {   // sd_model_score_logits: no target logit, no logprob
+    if (w8) {
+      if (v == 0) hipLaunchKernelGGL((score_logits_kernel<4, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((score_logits_kernel<2, true>), grid, block, 0, st, a);
+    } else {
+      if (v == 0) hipLaunchKernelGGL((score_logits_kernel<4, false>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((score_logits_kernel<2, false>), grid, block, 0, st, a);
+    }
+    SD_LAUNCH_CHECK();
+    if (greedy) hipLaunchKernelGGL(score_finalize_kernel, dim3(T), dim3(kFinThreads), 0, st, part, m.n_blocks, tgt_logit, 0, nullptr, greedy);
+    SD_LAUNCH_CHECK();
+    return 0;
+  }
   // a target row that is not a vocabulary row leaves NaN (0xffffffff), not a stale logit
   SD_HIP_CHECK(hipMemsetAsync(tgt_logit, 0xff, static_cast<size_t>(T) * sizeof(float), st));
-  const dim3 grid(m.n_blocks * n_tb), block(kThreads);
   if (w8) {
     if (v == 0) hipLaunchKernelGGL((score_head_kernel<4, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((score_head_kernel<2, true>), grid, block, 0, st, a);

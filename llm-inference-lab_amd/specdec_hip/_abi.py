@@ -59,6 +59,12 @@ SIGNATURES = {
         [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_float, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p,
          ctypes.c_uint32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
     ),
+    "sd_spec_agreement_workspace": (_c_size, [_c_int, _c_int]),
+    "sd_spec_agreement": (
+        _c_int,
+        [_c_void_p, _c_i64, _c_void_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+         _c_void_p, _c_size, _c_void_p],
+    ),
     "sd_kv_append": (
         _c_int,
         [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
@@ -94,6 +100,7 @@ SIGNATURES = {
          _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p],
     ),
     "sd_model_score": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "sd_model_score_logits": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "sd_model_probe_gemv": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p,
                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]),
     "sd_model_persist_tokens": (_c_int, [_c_void_p]),

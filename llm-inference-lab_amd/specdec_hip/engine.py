@@ -264,6 +264,31 @@ class HipModel:
         _abi.check(rc, "sd_model_score")
         return logprob, greedy
 
+    def score_logits(self, tokens, row: int = 0, pos0: int = 0, out: Optional[torch.Tensor] = None,
+                     stream: Optional[torch.cuda.Stream] = None):
+        """score() with the head storing each position's logits instead of reducing them (sd_model_score_logits): `tokens`
+        (n >= 1 ids) appended to cache row `row` at positions pos0 .. pos0+n-1 -> (logits bf16 [n][V], greedy int32 [n]).
+        Route, chunking, cache effect and prefill counters are score()'s. `out`: a contiguous bf16 buffer of at least n x V
+        elements to store into (its first n rows are returned)."""
+        t = torch.as_tensor(tokens).reshape(-1).to(self.device, torch.int32).contiguous()
+        n, V = int(t.numel()), self.cfg.vocab
+        if self.health():
+            self.check_health("sd_model_score_logits")
+        if self.page_len is not None and n >= 1 and 0 <= row < self.batch and pos0 >= 0:
+            self.reserve(int(row), int(pos0) + n, stream=stream)
+        if out is None:
+            logits = torch.empty((n, V), dtype=torch.bfloat16, device=self.device)
+        else:
+            if out.dtype != torch.bfloat16 or out.device != self.device or not out.is_contiguous() or out.numel() < n * V:
+                raise ValueError(f"score_logits: out must be a contiguous bf16 buffer of >= {n} x {V} elements on {self.device}")
+            logits = out.view(-1)[: n * V].view(n, V)
+        greedy = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.sd_model_score_logits(self.handle, t.data_ptr() if n else None, n, int(row), int(pos0), logits.data_ptr(),
+                                                _ptr(greedy), _stream(stream, self.device))
+        _abi.check(rc, "sd_model_score_logits")
+        return logits, greedy
+
     def hidden_rows(self, n: int, row0: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
         """bf16 [n][d_model]: the residual-stream rows (before the final norm) of the last forward pass (sd_model_hidden_rows)."""
         out = torch.empty((n, self.cfg.d_model), dtype=torch.bfloat16, device=self.device)

@@ -393,6 +393,47 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     return (accept, nxt, ratios) if return_ratios else (accept, nxt)
 
 
+def spec_agreement(draft_logits: torch.Tensor, target_logits: torch.Tensor, temperature: float = 1.0):
+    """Draft-target agreement per position (sd_spec_agreement, csrc/spec_agree.hip): how much of softmax(target / T) the draft's
+    softmax(draft / T) reproduces, in float64 over the stored bf16 logits.
+
+    draft_logits, target_logits: bf16 device tensors of equal shape [n, V] or [B, K, V] with unit inner stride (row strides are
+    passed on; rows taken as views of a wider buffer are not copied). Returns, shaped like the leading dimensions,
+    (alpha float64: the acceptance probability sum_v min(p, q) = 1 - TV(p, q); kl float64: KL(p || q); agree bool: equal argmax;
+    p_arg, q_arg int32: the target's and the draft's argmax id). A position whose rows hold a NaN or have a non-finite maximum
+    gives alpha = kl = NaN. Bit-identical run to run; a position's outputs do not depend on the other positions."""
+    lib = _abi.load()
+    dev = _require_device("spec_agreement", draft_logits, target_logits)
+    if draft_logits.dim() not in (2, 3) or draft_logits.shape != target_logits.shape:
+        raise ValueError(f"spec_agreement: need two [n,V] or [B,K,V] tensors of one shape, got {tuple(draft_logits.shape)} / "
+                         f"{tuple(target_logits.shape)}")
+    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16:
+        raise TypeError("spec_agreement: logits must be bfloat16")
+    lead, V = tuple(draft_logits.shape[:-1]), int(draft_logits.shape[-1])
+    n = 1
+    for d in lead:
+        n *= int(d)
+    if n < 1 or V < 1:
+        raise ValueError(f"spec_agreement: empty logits {tuple(draft_logits.shape)}")
+
+    def rows(t):   # -> ([n, V] view when the leading dimensions collapse (else a copy), elements between its rows)
+        t = t.reshape(n, V)
+        if t.stride(1) != 1 or (n > 1 and t.stride(0) < V):
+            t = t.contiguous()
+        return t, (int(t.stride(0)) if n > 1 else V)
+
+    (q, ld_q), (p, ld_p) = rows(draft_logits), rows(target_logits)
+    alpha = torch.empty(n, dtype=torch.float64, device=dev)
+    kl = torch.empty(n, dtype=torch.float64, device=dev)
+    ints = torch.empty((3, n), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(lib.sd_spec_agreement_workspace(n, V), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_spec_agreement(q.data_ptr(), ld_q, p.data_ptr(), ld_p, n, V, float(temperature), alpha.data_ptr(),
+                                         kl.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), ws.data_ptr(),
+                                         ws.numel(), _stream_ptr(dev)), "sd_spec_agreement")
+    return alpha.view(lead), kl.view(lead), ints[0].view(lead) != 0, ints[1].view(lead), ints[2].view(lead)
+
+
 def quantize_fp8_rows_hip(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(q float8_e4m3fn [N][K], scales float32 [N]) of a bf16 matrix: the per-output-row quantiser of the
     engine's fp8 weight storage (sd_quantize_fp8_rows)."""

@@ -1,4 +1,5 @@
-"""Perplexity of a text under a HIP model, scored on the device (HipLM.score: sd_model_score).
+"""Perplexity of a text under a HIP model, scored on the device (HipLM.score: sd_model_score), and the agreement of a draft model
+with a target on a text (AgreementEvaluator: SpeculativePipeline.draft_agreement, sd_spec_agreement).
 
 The counterpart of the reference's `PerplexityEvaluator` (same constructor, `calculate_perplexity` and `compare_texts`, same result
 keys). The model is what `create_hip_lm` builds from `model_name`: a local checkpoint directory, "synthetic:<preset>" or a hub name
@@ -91,3 +92,60 @@ class PerplexityEvaluator:
             "model": self.model_name,
             "device": self.device,
         }
+
+
+class AgreementEvaluator:
+    """Evaluates how well a draft model fits a target on given texts, without generating: per-position acceptance probability
+    of speculative sampling, KL(target || draft) and greedy agreement, over at most `max_length` tokens of a text
+    (SpeculativePipeline.draft_agreement, reduced on the device)."""
+
+    def __init__(self, base_model: str, draft_model: str, device: str = "cuda", pipeline: Any = None, max_length: int = 512,
+                 temperature: float = 1.0, chunk: int = 256):
+        """`pipeline`: anything with `draft_agreement(ids, temperature, chunk) -> dict` and `_encode(text) -> ids` (default: a
+        SpeculativePipeline over create_hip_lm's models)."""
+        self.base_model, self.draft_model = base_model, draft_model
+        self.device = device
+        self.max_length = int(max_length)
+        self.temperature = float(temperature)
+        self.chunk = int(chunk)
+        self.logger = logging.getLogger(__name__)
+        if pipeline is None:
+            from src.specdec.core.pipeline import SpeculativePipeline
+
+            self.logger.info("Loading models: %s / %s", base_model, draft_model)
+            pipeline = SpeculativePipeline(base_model=base_model, draft_model=draft_model, device=device)
+        self.pipeline = pipeline
+
+    def calculate_agreement(self, text: Any) -> Dict[str, Any]:
+        """{mean_alpha, mean_kl, greedy_agreement, expected_tokens_per_step, token_count, temperature, base_model, draft_model,
+        device}; on failure the three means are NaN plus `error`."""
+        try:
+            ids = [int(i) for i in self.pipeline._encode(text)][: self.max_length]
+            r = self.pipeline.draft_agreement(ids, temperature=self.temperature, chunk=self.chunk)
+            return {"mean_alpha": r["mean_alpha"], "mean_kl": r["mean_kl"], "greedy_agreement": r["greedy_agreement"],
+                    "expected_tokens_per_step": r["expected_tokens_per_step"], "token_count": len(ids),
+                    "temperature": self.temperature, "base_model": self.base_model, "draft_model": self.draft_model,
+                    "device": self.device}
+        except Exception as e:
+            self.logger.error("Agreement calculation failed: %s", e)
+            nan = float("nan")
+            return {"mean_alpha": nan, "mean_kl": nan, "greedy_agreement": nan, "expected_tokens_per_step": None, "token_count": 0,
+                    "temperature": self.temperature, "base_model": self.base_model, "draft_model": self.draft_model,
+                    "device": self.device, "error": str(e)}
+
+    def compare_texts(self, texts: List[Any], labels: Optional[List[str]] = None) -> Dict[str, Any]:
+        """Per-text results (with `label`) and the mean acceptance probability / greedy agreement over the texts that scored."""
+        if labels is None:
+            labels = [f"text_{i}" for i in range(len(texts))]
+        results = []
+        for text, label in zip(texts, labels):
+            r = self.calculate_agreement(text)
+            r["label"] = label
+            results.append(r)
+        ok = [r for r in results if "error" not in r]
+        nan = float("nan")
+        return {"results": results,
+                "statistics": {"avg_alpha": sum(r["mean_alpha"] for r in ok) / len(ok) if ok else nan,
+                               "avg_greedy_agreement": sum(r["greedy_agreement"] for r in ok) / len(ok) if ok else nan,
+                               "count": len(ok)},
+                "base_model": self.base_model, "draft_model": self.draft_model, "device": self.device}

@@ -130,6 +130,8 @@ def get_kernel_info():
         "prefill_backends": _prefill_backends() if lib_ok else [],
         # sequence log-likelihood on the device (sd_model_score: lm_head GEMM with a log-softmax epilogue, csrc/score_head.hip)
         "score_head": "hip" if lib_ok else "unavailable",
+        # draft-target agreement of two logit blocks (sd_spec_agreement, csrc/spec_agree.hip)
+        "spec_agreement": "hip" if lib_ok else "unavailable",
     }
 
 

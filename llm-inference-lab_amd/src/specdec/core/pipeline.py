@@ -68,6 +68,28 @@ def _clamp(tok: int, vocab: int) -> int:
     return 0 if tok < 0 else (vocab - 1 if tok >= vocab else int(tok))
 
 
+def expected_tokens_per_step(alpha: Sequence[float], k_max: int = 8) -> Dict[int, Optional[float]]:
+    """{K: mean over t of sum_{j=0..K} prod_{i<j} alpha[t+i]} for K = 1..k_max: the tokens a step of K proposals emits (the
+    accepted prefix plus the correction / bonus token) when position t+i accepts with probability alpha[t+i], averaged over the
+    windows t = 0 .. len(alpha)-K that fit; None for a K with no window."""
+    a = [float(x) for x in alpha]
+    out: Dict[int, Optional[float]] = {}
+    for K in range(1, int(k_max) + 1):
+        windows = len(a) - K + 1
+        if windows < 1:
+            out[K] = None
+            continue
+        total = 0.0
+        for t in range(windows):
+            prod, acc = 1.0, 1.0
+            for i in range(K):
+                prod *= a[t + i]
+                acc += prod
+            total += acc
+        out[K] = total / windows
+    return out
+
+
 class _Row:
     __slots__ = ("seq", "generated", "active", "proposed", "accepted", "draws", "steps", "strict_acc", "strict_prop", "k_trace", "counters")
 
@@ -720,6 +742,59 @@ class SpeculativePipeline:
                         "batch_metrics": {"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
                                           "void_row_steps": sess.stats["void_row_steps"], "k": sess.k}})
         return out
+
+    def draft_agreement(self, text_or_ids: PromptLike, temperature: float = 1.0, chunk: int = 256) -> Dict[str, Any]:
+        """How well the draft fits the target on a text, without generating: the sequence is teacher-forced through both models
+        (HipLM.score_logits, the prefill route of score) in chunks of <= `chunk` positions and the two logit rows of every
+        position are reduced on the device (specdec_hip.ops.spec_agreement) — the [n][V] logits stay in two reusable
+        [chunk][V] bf16 buffers and never pass through torch arithmetic.
+
+        Returns, for positions 0..n-2 (the predictions of tokens 1..n-1): `alpha` (per-position acceptance probability of
+        speculative sampling at `temperature`, sum_v min(p, q)), `kl` (KL(target || draft)), `agree` (equal argmax: what greedy
+        verification accepts), their means `mean_alpha` / `mean_kl` / `greedy_agreement`, and `expected_tokens_per_step`
+        {"sampling": {K: ..}, "greedy": {K: ..}} for K = 1..8 (expected_tokens_per_step over alpha, and over agree as 0 / 1).
+        `expected_tokens_per_step` is an estimate on the contexts of the GIVEN text: in a real step the later positions of a
+        window condition on the draft's own continuation, not on the text's tokens, so it is a guide to choosing K, not a
+        measurement of a run. Both cache rows 0 then hold the first n-1 tokens."""
+        from specdec_hip.ops import spec_agreement
+
+        if self._fake:
+            raise NotImplementedError("draft_agreement needs the HIP models (implementation='hip'): the fake models have no logits on the device")
+        mode = self.config.get("draft_mode", "vanilla")
+        if mode in ("medusa", "eagle") or self.draft_lm is None:
+            raise NotImplementedError(f"draft_agreement compares a separate draft model with the target; draft_mode={mode!r} drafts from "
+                                      "the target's own hidden state (no draft model / a different draft input)")
+        for lm in (self.base_lm, self.draft_lm):
+            if not hasattr(lm, "score_logits"):
+                raise NotImplementedError("draft_agreement needs models with score_logits (HipLM)")
+        ids = self._encode(text_or_ids)
+        if len(ids) < 2:
+            raise ValueError(f"draft_agreement: {len(ids)} token(s); an agreement needs at least 2")
+        if not (float(temperature) > 0.0):
+            raise ValueError(f"draft_agreement: temperature {temperature} (must be > 0)")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"draft_agreement: chunk={chunk}")
+        m = len(ids) - 1                                   # positions whose prediction has a token to be compared with
+        V, dev = self.base_lm.vocab_size, self.base_lm.device
+        c = min(chunk, m)
+        bufs = [torch.empty((c, V), dtype=torch.bfloat16, device=dev) for _ in range(2)]
+        alpha, kl, agree = [], [], []
+        for p0 in range(0, m, c):
+            part = ids[p0:min(p0 + c, m)]
+            q, _ = self.draft_lm.score_logits(part, pos0=p0, out=bufs[0], reserve=m)
+            p, _ = self.base_lm.score_logits(part, pos0=p0, out=bufs[1], reserve=m)
+            a, k, g, _, _ = spec_agreement(q, p, temperature)
+            alpha.append(a)
+            kl.append(k)
+            agree.append(g)
+        alpha = torch.cat(alpha).cpu().tolist()
+        kl = torch.cat(kl).cpu().tolist()
+        agree = [bool(x) for x in torch.cat(agree).cpu().tolist()]
+        return {"alpha": alpha, "kl": kl, "agree": agree, "positions": m, "temperature": float(temperature),
+                "mean_alpha": sum(alpha) / m, "mean_kl": sum(kl) / m, "greedy_agreement": sum(agree) / m,
+                "expected_tokens_per_step": {"sampling": expected_tokens_per_step(alpha),
+                                             "greedy": expected_tokens_per_step([1.0 if x else 0.0 for x in agree])}}
 
     def _sysinfo(self) -> Dict[str, Any]:
         return {

@@ -276,6 +276,29 @@ class HipLM(LanguageModel):
         self._cached[0] = ids[0].tolist()
         return logprob, greedy
 
+    def score_logits(self, input_ids: Any, pos0: int = 0, out: Optional[torch.Tensor] = None, reserve: int = 0):
+        """(logits bf16 [n][V], greedy int32 [n]) of n >= 1 ids appended to cache row 0 at positions pos0 .. pos0+n-1
+        (HipModel.score_logits): score() with the logits of every position kept on the device. pos0 > 0 continues a sequence whose
+        first pos0 ids the row caches (an earlier score / score_logits call). `reserve`: cache length to provide for, so that a
+        sequence scored in chunks keeps one engine; `out`: bf16 buffer to store into."""
+        return self._guarded("score_logits", lambda: self._score_logits(input_ids, int(pos0), out, int(reserve)))
+
+    def _score_logits(self, input_ids: Any, pos0: int, out: Optional[torch.Tensor], reserve: int):
+        ids = torch.as_tensor(input_ids).reshape(1, -1)
+        ids = validate_and_clamp_tokens(ids.long(), self.vocab_size, "score_logits")
+        L = ids.shape[1]
+        if L < 1 or pos0 < 0:
+            raise ValueError(f"score_logits: {L} token(s) at position {pos0}")
+        m = self._engine(1, max(pos0 + L, reserve) + 1)
+        if len(self._cached[0]) < pos0:
+            raise ValueError(f"score_logits: pos0={pos0} but cache row 0 holds {len(self._cached[0])} position(s)")
+        m.set_length_hint(max([pos0 + L, reserve] + [len(c) for c in self._cached]) + 1)
+        prefix = self._cached[0][:pos0]
+        self._cached[0] = []                      # rewritten from position pos0
+        logits, greedy = m.score_logits(ids[0].to(self._device, torch.int32), row=0, pos0=pos0, out=out)
+        self._cached[0] = prefix + ids[0].tolist()
+        return logits, greedy
+
     def perplexity(self, text_or_ids: Any) -> float:
         """exp(mean(-log p(x_i | x_<i))) over positions 1..n-1: the `labels=input_ids` loss of a HF causal LM, exponentiated."""
         ids = self.encode(text_or_ids) if isinstance(text_or_ids, str) else text_or_ids

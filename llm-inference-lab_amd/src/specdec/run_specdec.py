@@ -54,6 +54,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
+    ap.add_argument("--eval-agreement", action="store_true",
+                    help="add the draft's agreement with the target on prompt + generated tokens (acceptance probability at "
+                         "--temperature, KL, greedy agreement, expected tokens per step for K = 1..8; reduced on the device)")
     return ap.parse_args(argv)
 
 
@@ -66,6 +69,17 @@ def generated_perplexity(lm, tokens):
     logprob, _ = lm.score(ids)
     loss = -float(logprob.double().mean())
     return math.exp(loss), loss
+
+
+def sequence_agreement(pipe, tokens, temperature=None):
+    """The summary keys of SpeculativePipeline.draft_agreement over `tokens` (agreement_alpha, agreement_kl, agreement_greedy,
+    expected_tokens_per_step); None each for fewer than 2 tokens."""
+    ids = [int(t) for t in tokens]
+    if len(ids) < 2:
+        return {"agreement_alpha": None, "agreement_kl": None, "agreement_greedy": None, "expected_tokens_per_step": None}
+    r = pipe.draft_agreement(ids, temperature=1.0 if temperature is None else temperature)
+    return {"agreement_alpha": r["mean_alpha"], "agreement_kl": r["mean_kl"], "agreement_greedy": r["greedy_agreement"],
+            "expected_tokens_per_step": r["expected_tokens_per_step"]}
 
 
 def main(argv=None) -> int:
@@ -113,6 +127,8 @@ def main(argv=None) -> int:
             r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
         if args.eval_perplexity:
             r["perplexity"], r["perplexity_loss"] = generated_perplexity(pipe.base_lm, r["generated_tokens"])
+        if args.eval_agreement:
+            r.update(sequence_agreement(pipe, pipe._encode(args.prompt) + [int(t) for t in r["generated_tokens"]], args.temperature))
     except Exception as e:  # the reference CLI reports and exits 1 (run_specdec.py:276-278)
         logging.error("Error: %s", e)
         return 1
@@ -120,6 +136,8 @@ def main(argv=None) -> int:
             "base_model", "draft_model", "draft_mode", "dtype")
     if args.eval_perplexity:
         keys += ("perplexity", "perplexity_loss")
+    if args.eval_agreement:
+        keys += ("agreement_alpha", "agreement_kl", "agreement_greedy", "expected_tokens_per_step")
     print(json.dumps({k: r[k] for k in keys}))
     return 0
 
