@@ -299,6 +299,20 @@ int sd_model_bind_paged(sd_model* m, void* k_pool, void* v_pool, int n_pages, in
                         const int32_t* block_table, int max_pages_per_row, int B,
                         void* workspace, size_t workspace_bytes);
 
+/* KV shared between cache rows (csrc/kv_fork.hip): rows that hold the same prompt, or the same prefix, pay for it once.
+ * Both entries are asynchronous on `stream`, copy all layers, all KV heads, K and V in one launch per 64 list entries,
+ * take their lists from HOST memory (they travel in the kernels' argument blocks: no allocation, no copy, no
+ * synchronisation) and touch nothing but the first n_pos positions of the destinations. n_pos == 0 or an empty list
+ * succeeds and launches nothing. Refused before any device work (return code + sd_last_error): an unbound model, the dense
+ * entry on a paged model and the reverse, an index out of range, a destination equal to its source or listed twice (paged:
+ * also a destination that is a source of the same call), n_pos < 0 or beyond the row / page, a NULL list with a count > 0.
+ *
+ * Dense caches: the first n_pos positions of row src_row -> each of the n_dst rows dst_rows[]. */
+int sd_model_kv_fork(sd_model* m, int src_row, const int32_t* dst_rows, int n_dst, int n_pos, void* stream);
+/* Paged caches: the first n_pos <= page_len positions of page src_pages[i] -> page dst_pages[i] for n_pairs pairs
+ * (n_pos == page_len: whole pages). Block tables and page ownership stay the caller's. */
+int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, const int32_t* dst_pages, int n_pairs, int n_pos, void* stream);
+
 /* One forward over M new tokens per batch row, appended to the KV cache in place.
  *   tokens   : device int32, token (b,m) at tokens[b*tok_stride + m]
  *   pos_base : device int32[B]; token (b,m) sits at position pos_base[b] + pos_off + m

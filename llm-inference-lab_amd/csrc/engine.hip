@@ -694,6 +694,70 @@ extern "C" int sd_model_bind_paged(sd_model* m, void* k_pool, void* v_pool, int 
   return carve_workspace(m, workspace);
 }
 
+// ---- KV shared between cache rows (csrc/kv_fork.hip) -----------------------------------------------------------------
+// Both entries check the arguments that need no model first, then the model, then the indices against its geometry:
+// nothing is enqueued unless every check passed.
+extern "C" int sd_model_kv_fork(sd_model* m, int src_row, const int32_t* dst_rows, int n_dst, int n_pos, void* stream) {
+  clear_error();
+  SD_REQUIRE(n_dst >= 0, "kv_fork: n_dst=%d", n_dst);
+  SD_REQUIRE(n_dst == 0 || dst_rows, "kv_fork: NULL dst_rows with n_dst=%d", n_dst);
+  SD_REQUIRE(n_pos >= 0, "kv_fork: n_pos=%d is negative", n_pos);
+  SD_REQUIRE(src_row >= 0, "kv_fork: src_row %d is negative", src_row);
+  for (int i = 0; i < n_dst; ++i) {
+    SD_REQUIRE(dst_rows[i] >= 0, "kv_fork: destination row %d is negative", dst_rows[i]);
+    SD_REQUIRE(dst_rows[i] != src_row, "kv_fork: destination row %d is the source row", dst_rows[i]);
+  }
+  SD_REQUIRE(m, "kv_fork: NULL model");
+  SD_REQUIRE(m->k_cache && m->x, "kv_fork: model not bound (sd_model_bind)");
+  SD_REQUIRE(!m->block_table, "kv_fork: this model is bound to a paged cache (rows share pages: sd_model_kv_copy_pages)");
+  SD_REQUIRE(src_row < m->B, "kv_fork: src_row %d outside the bound batch of %d", src_row, m->B);
+  SD_REQUIRE(n_pos <= m->Lmax, "kv_fork: n_pos=%d exceeds Lmax=%d", n_pos, m->Lmax);
+  std::vector<char> seen(static_cast<size_t>(m->B), 0);
+  for (int i = 0; i < n_dst; ++i) {
+    SD_REQUIRE(dst_rows[i] < m->B, "kv_fork: destination row %d outside the bound batch of %d", dst_rows[i], m->B);
+    SD_REQUIRE(!seen[dst_rows[i]], "kv_fork: destination row %d is listed twice", dst_rows[i]);
+    seen[dst_rows[i]] = 1;
+  }
+  if (n_dst == 0 || n_pos == 0) return 0;
+  const sd_model_config& c = m->cfg;
+  return launch_kv_fork(m->k_cache, m->v_cache, c.n_layers, m->B, c.n_kv_heads, m->Lmax, c.head_dim, &src_row, dst_rows, 1, n_dst,
+                        n_pos, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, const int32_t* dst_pages, int n_pairs, int n_pos,
+                                      void* stream) {
+  clear_error();
+  SD_REQUIRE(n_pairs >= 0, "kv_copy_pages: n_pairs=%d", n_pairs);
+  SD_REQUIRE(n_pairs == 0 || (src_pages && dst_pages), "kv_copy_pages: NULL page list with n_pairs=%d", n_pairs);
+  SD_REQUIRE(n_pos >= 0, "kv_copy_pages: n_pos=%d is negative", n_pos);
+  for (int i = 0; i < n_pairs; ++i) {
+    SD_REQUIRE(src_pages[i] >= 0 && dst_pages[i] >= 0, "kv_copy_pages: pair %d (%d -> %d) has a negative page index", i, src_pages[i],
+               dst_pages[i]);
+    SD_REQUIRE(src_pages[i] != dst_pages[i], "kv_copy_pages: pair %d copies page %d onto itself", i, src_pages[i]);
+  }
+  SD_REQUIRE(m, "kv_copy_pages: NULL model");
+  SD_REQUIRE(m->k_cache && m->x, "kv_copy_pages: model not bound (sd_model_bind_paged)");
+  SD_REQUIRE(m->block_table, "kv_copy_pages: this model is bound to a dense cache (sd_model_kv_fork)");
+  const int page_len = 1 << m->page_shift;
+  SD_REQUIRE(n_pos <= page_len, "kv_copy_pages: n_pos=%d exceeds page_len=%d", n_pos, page_len);
+  // the pairs of a call run concurrently: a destination must not be a source or another pair's destination
+  std::vector<char> role(static_cast<size_t>(m->n_pages), 0);   // 1 = source, 2 = destination
+  for (int i = 0; i < n_pairs; ++i) {
+    SD_REQUIRE(src_pages[i] < m->n_pages && dst_pages[i] < m->n_pages, "kv_copy_pages: pair %d (%d -> %d) outside the pool of %d pages", i,
+               src_pages[i], dst_pages[i], m->n_pages);
+    role[src_pages[i]] |= 1;
+  }
+  for (int i = 0; i < n_pairs; ++i) {
+    SD_REQUIRE(role[dst_pages[i]] == 0, "kv_copy_pages: destination page %d is %s", dst_pages[i],
+               (role[dst_pages[i]] & 2) ? "listed twice" : "also a source of this call");
+    role[dst_pages[i]] |= 2;
+  }
+  if (n_pairs == 0 || n_pos == 0) return 0;
+  const sd_model_config& c = m->cfg;
+  return launch_kv_fork(m->k_cache, m->v_cache, c.n_layers, m->n_pages, c.n_kv_heads, page_len, c.head_dim, src_pages, dst_pages, n_pairs,
+                        1, n_pos, static_cast<hipStream_t>(stream));
+}
+
 static int carve_workspace(sd_model* m, void* workspace) {
   const sd_model_config& c = m->cfg;
   const size_t T = kSkinnyMaxT;

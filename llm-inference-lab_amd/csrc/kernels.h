@@ -189,4 +189,12 @@ int launch_embed(const EmbedArgs& a, hipStream_t st);
 int launch_argmax_finalize(const float* part_val, const int* part_idx, int T, int grid, int M,
                            int ids_stride, int32_t* ids_out, hipStream_t st, const int32_t* skip_k = nullptr, int skip_i = 0);
 
+// ---- KV fork (kv_fork.hip) ------------------------------------------------------------
+// First n_pos positions of slot src[g] -> slots dst[g * fan .. g * fan + fan), all layers / heads / K and V; a slot is a
+// row of a dense cache (Lslot = Lmax) or a page of a pool (Lslot = page_len). n_groups == 1: one source, any fan;
+// n_groups > 1: pairs (fan == 1). Lists are host memory; launches carry <= kForkMaxList entries each.
+constexpr int kForkMaxList = 64;
+int launch_kv_fork(uint16_t* k, uint16_t* v, int n_layers, int n_slots, int Hkv, int Lslot, int D, const int32_t* src,
+                   const int32_t* dst, int n_groups, int fan, int n_pos, hipStream_t st);
+
 }  // namespace sd

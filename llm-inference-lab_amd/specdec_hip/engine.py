@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from .pages import PagePool
 from .weights import ARCH_LLAMA, ModelConfig, ModelWeights
 
 _vp = ctypes.c_void_p
@@ -179,8 +180,10 @@ class HipModel:
             _abi.check(self.lib.sd_model_bind_paged(self.handle, self.k_cache.data_ptr(), self.v_cache.data_ptr(), self.n_pages, P,
                                                     self.block_table.data_ptr(), self.max_pages, self.batch,
                                                     self.workspace.data_ptr(), self.workspace.numel()), "sd_model_bind_paged")
-        self._free = list(range(self.n_pages - 1, -1, -1))       # stack of free page indices
-        self._owned: List[List[int]] = [[] for _ in range(self.batch)]
+        # host bookkeeping (pages.PagePool): free stack, pages per row in position order, owners per page
+        self._pool = PagePool(self.n_pages, self.batch, P)
+        self._free = self._pool.free
+        self._owned: List[List[int]] = self._pool.owned
 
     def reserve(self, row: int, length: int, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Make positions [0, length) of `row` addressable (paged engines; a no-op on dense ones). New table entries are
@@ -188,27 +191,63 @@ class HipModel:
         if self.page_len is None:
             return
         need = (min(int(length), self.l_max) + self.page_len - 1) // self.page_len
-        own = self._owned[row]
-        if need <= len(own):
-            return
-        if need - len(own) > len(self._free):
-            raise RuntimeError(f"KV page pool exhausted: row {row} needs {need - len(own)} more pages, {len(self._free)} free of {self.n_pages}")
-        first = len(own)
-        while len(own) < need:
-            own.append(self._free.pop())
-        new = torch.tensor(own[first:], dtype=torch.int32)
+        first, new = self._pool.reserve(row, need)
+        if new:
+            self._write_table(row, first, new, stream)
+
+    def _write_table(self, row: int, first: int, pages: Sequence[int], stream: Optional[torch.cuda.Stream]) -> None:
+        new = torch.tensor(list(pages), dtype=torch.int32)
         with torch.cuda.device(self.device), torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
-            self.block_table[row, first:need].copy_(new.to(self.device, non_blocking=False))
+            self.block_table[row, first:first + len(pages)].copy_(new.to(self.device, non_blocking=False))
 
     def release(self, row: int) -> None:
-        """Return the row's pages to the pool (its sequence is finished; the next reserve() starts from nothing)."""
+        """Return the row's pages to the pool (its sequence is finished; the next reserve() starts from nothing). A page that
+        other rows share (fork_row) stays theirs."""
         if self.page_len is None:
             return
-        self._free.extend(reversed(self._owned[row]))
-        self._owned[row] = []
+        self._pool.release(row)
 
     def pages_in_use(self) -> int:
-        return 0 if self.page_len is None else self.n_pages - len(self._free)
+        """Physical pages with an owner (a page shared by several rows counts once)."""
+        return 0 if self.page_len is None else self._pool.pages_in_use()
+
+    def unshare(self, row: int) -> None:
+        """Before a row's cache is rebuilt from position 0: a row that shares pages with others gives all its pages up, so
+        that the rebuild writes fresh ones (shared pages are never written). Rows that share nothing keep their pages."""
+        if self.page_len is not None and self._pool.shares(row):
+            self._pool.release(row)
+
+    def fork_row(self, src: int, dsts: Sequence[int], length: int, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Give the rows `dsts` the first `length` cached positions of row `src`, asynchronously on `stream` (default: the
+        current stream; the work that wrote the source must be ordered before it, what reads the destinations after it).
+        Dense caches: one sd_model_kv_fork copies them. Paged caches: every destination releases what it owns, then SHARES
+        the source's pages that no later write can touch (pages.shared_pages: those wholly below position length - 2) and
+        gets fresh pages for the rest, filled by sd_model_kv_copy_pages (whole pages, and length % page_len positions of a
+        partial last one); the table entries are written on `stream`, as reserve() does. Shared pages are immutable — rows
+        only append or roll back to >= their accepted length — so there is no copy-on-write. A pool that cannot serve the
+        fork raises before any table entry or ownership list has changed."""
+        dsts = [int(d) for d in dsts]
+        length = int(length)
+        st = _stream(stream, self.device)
+        if self.page_len is None:
+            arr = (ctypes.c_int32 * max(len(dsts), 1))(*dsts)
+            with torch.cuda.device(self.device):
+                _abi.check(self.lib.sd_model_kv_fork(self.handle, int(src), arr, len(dsts), length, st), "sd_model_kv_fork")
+            return
+        if not 0 <= length <= self.l_max:
+            raise ValueError(f"fork_row: length {length} outside [0, {self.l_max}]")
+        plan = self._pool.fork(int(src), dsts, length)
+        for d, pages in zip(dsts, plan.tables):
+            if pages:
+                self._write_table(d, 0, pages, stream)
+        by_n: dict = {}
+        for s, d, n in plan.copies:       # one call per distinct position count: whole pages, and the partial last page
+            by_n.setdefault(n, []).append((s, d))
+        with torch.cuda.device(self.device):
+            for n, pairs in by_n.items():
+                sp = (ctypes.c_int32 * len(pairs))(*[p[0] for p in pairs])
+                dp = (ctypes.c_int32 * len(pairs))(*[p[1] for p in pairs])
+                _abi.check(self.lib.sd_model_kv_copy_pages(self.handle, sp, dp, len(pairs), n, st), "sd_model_kv_copy_pages")
 
     def kv_view(self):
         c = self.cfg

@@ -61,6 +61,9 @@ _DEFAULTS: Dict[str, Any] = {
     "draft_mode": "vanilla",
     "medusa": {"enabled": False, "num_heads": 2, "head_init": "tie", "temperature": 0.7, "top_p": 1.0},
     "eagle": {"enabled": False, "alpha": 0.7, "max_draft": 2},
+    # share_prefix: a row is forked over a prefix it has in common with a row already in the cache from this many tokens on
+    # (rows whose whole prompts are equal are always forked)
+    "min_shared_prefix": 32,
 }
 
 
@@ -288,7 +291,51 @@ class SpeculativePipeline:
         if rt["draft"] is not None:
             rt["draft"].forward(toks, zero, 0, skip_head=True, row0=b)
 
-    def _prefill(self, rt, rows: List[_Row]) -> None:
+    def _absorb_row(self, rt, b: int, seq: List[int], held: List[Optional[List[int]]], stats: Dict[str, Any]) -> None:
+        """share_prefix: KV of seq[:-1] into row b of both caches, computing as little of it as the other rows allow.
+        held[j] is the token prefix whose KV row j's caches hold (None: nothing to rely on). The row with the longest common
+        prefix c is the source: c == len(seq) - 1 (the same prompt) -> the row is forked from it (HipModel.fork_row, both
+        engines) and nothing is computed; c >= min_shared_prefix -> forked over those c positions, and seq[c:-1] is forwarded
+        at pos_base = c; otherwise the row is prefilled as _prefill_row does. Runs on the current stream, like the prefill."""
+        want = seq[:-1]
+        held[b] = None
+        best, c = -1, 0
+        for j, h in enumerate(held):
+            if j == b or h is None:
+                continue
+            n = 0
+            for x, y in zip(want, h):
+                if x != y:
+                    break
+                n += 1
+            if n > c:
+                best, c = j, n
+        engines = [e for e in (rt["target"], rt["draft"]) if e is not None]
+        if want and c == len(want) or c >= max(int(self.config.get("min_shared_prefix", 32)), 1):
+            for e in engines:
+                e.fork_row(best, [b], c)
+            if c < len(want):
+                toks = torch.tensor([want[c:]], dtype=torch.int32, device="cuda")
+                base = torch.tensor([c], dtype=torch.int32, device="cuda")
+                for e in engines:
+                    e.forward(toks, base, 0, skip_head=True, row0=b)
+            stats["forked_rows"] += 1
+            stats["shared_positions"] += c
+        else:
+            self._prefill_row(rt, b, seq)
+            stats["prefilled_rows"] += 1 if want else 0
+        held[b] = list(want)
+
+    def _prefill(self, rt, rows: List[_Row], held: Optional[List[Optional[List[int]]]] = None,
+                 stats: Optional[Dict[str, Any]] = None) -> None:
+        """held (share_prefix): the session's record of what each row's caches hold; rows are then absorbed one by one, each
+        forked from an earlier one where their prompts allow (_absorb_row)."""
+        if held is not None:
+            for b, r in enumerate(rows):
+                self._absorb_row(rt, b, r.seq, held, stats)
+            return
+        if stats is not None:
+            stats["prefilled_rows"] += sum(1 for r in rows if len(r.seq) >= 2)
         lens = {len(r.seq) for r in rows}
         if len(lens) == 1 and len(rows[0].seq) >= 2:
             toks = torch.tensor([r.seq[:-1] for r in rows], dtype=torch.int32, device="cuda")
@@ -374,15 +421,17 @@ class SpeculativePipeline:
     # ------------------------------------------------------------------ the loop
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None,
-                      self_draft: bool = False) -> "DecodeSession":
+                      self_draft: bool = False, share_prefix: bool = False) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
-        (generate / generate_batch drive it to completion, bench.py times exact step counts)."""
-        return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft)
+        (generate / generate_batch drive it to completion, bench.py times exact step counts).
+        share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
+        (DecodeSession)."""
+        return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
-                sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False):
+                sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False):
         t_start = time.time()
-        sess = self.start_session(prompts, max_tokens, emit_mode, sampling, step_limit, self_draft)
+        sess = self.start_session(prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -586,6 +635,8 @@ class SpeculativePipeline:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
+        if kwargs.get("share_prefix") or int(kwargs.get("n", 1) or 1) != 1:
+            raise NotImplementedError("share_prefix / n belong to generate_batch and generate_many: generate() decodes one row")
         max_tokens = max_tokens or self.config["max_new_tokens"]
         temperature = temperature or self.config["temperature"]
         do_sample = do_sample if do_sample is not None else self.config["do_sample"]
@@ -628,11 +679,30 @@ class SpeculativePipeline:
 
     def generate_batch(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None,
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
-                       **kwargs) -> List[Dict[str, Any]]:
+                       share_prefix: bool = False, n: int = 1, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
-        step, step-count bound, no truncation to max_tokens. Rows are independent sequences."""
+        step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
+
+        share_prefix (opt-in; not in the reference): rows pay for a prompt once. Rows whose prompts are equal are prefilled
+        once, on the first of them, and the others are forked from it in both engines (csrc/kv_fork.hip: a copy of the KV, or
+        shared pages with paged KV); a row that has only a prefix of >= `min_shared_prefix` tokens (config key, default 32) in
+        common with a row already in the cache is forked over that prefix and forwards the rest of its prompt from there.
+        With equal prompts the result is that of the unshared run, token for token. With a partial prefix the suffix is
+        computed in other chunks than a whole-prompt prefill uses, so it may differ from the unshared run at bf16 rounding
+        level — which is why sharing is opt-in. `n` > 1: every prompt becomes n adjacent rows (n samples of it: do_sample=True,
+        or policy="rejection" with backend="device", whose per-row Philox streams make the rows differ), results come back
+        prompt-major; implies share_prefix. Both are for the captured step (longest_prefix, device sampling, rejection on
+        the device) and are refused elsewhere. batch_metrics carries prefilled_rows / forked_rows / shared_positions."""
         if not prompts:
             return []
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"n={n} (at least 1)")
+        share_prefix = bool(share_prefix) or n > 1
+        if share_prefix and (self._fake or (self.policy_name != "longest_prefix"
+                                            and not (self.policy_name == "rejection" and self.rejection_backend == "device"))):
+            raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip'; policy 'longest_prefix', "
+                                      "or 'rejection' with backend='device')")
         if self._fake:
             # the double has no tokenizer to pad a batch with: the reference falls back to generate() per prompt
             # ("No tokenizer access, falling back to sequential processing", pipeline.py:1680-1700)
@@ -644,9 +714,12 @@ class SpeculativePipeline:
         heads = self.medusa_heads is not None    # persistent heads also serve generate_batch (opt-in, not in the reference)
         if self.draft_lm is None and not heads:
             raise ValueError("generate_batch drafts with the draft model (the reference ignores draft_mode there): pass draft_lm / draft_model")
+        if n > 1:
+            prompts = [p for p in prompts for _ in range(n)]
         ids = [self._encode(p) for p in prompts]
         if self.policy_name == "rejection" and self.rejection_backend == "device":
-            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs))
+            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs),
+                                    share_prefix=share_prefix)
         elif self.policy_name == "rejection":
             rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
         elif self.policy_name != "longest_prefix":
@@ -654,7 +727,8 @@ class SpeculativePipeline:
                 raise NotImplementedError(f"policy={self.policy_name!r} with do_sample=True is not on the HIP path")
             rows, st = self._decode_host_policy(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
-            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=sampling, self_draft=heads)
+            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=sampling, self_draft=heads,
+                                    share_prefix=share_prefix)
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -665,6 +739,7 @@ class SpeculativePipeline:
             "total_generation_time_ms": total_ms, "total_time_ms": total_ms,
             "tokens_per_sec": tot_acc / (total_ms / 1e3) if total_ms > 0 else 0.0,
             "emitted_tokens": tot_gen, "resyncs": st["resyncs"], "k": st["k"],
+            **{key: st.get(key, 0) for key in ("prefilled_rows", "forked_rows", "shared_positions")},
         }
         out = []
         for i, (p, r) in enumerate(zip(prompts, rows)):
@@ -686,14 +761,26 @@ class SpeculativePipeline:
         return out
 
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
-                      temperature: Optional[float] = None, do_sample: Optional[bool] = None, **kwargs) -> List[Dict[str, Any]]:
+                      temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
+                      **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
         (comprehensive_k_sweep.py:444-535). Rows are independent, so every result equals the prompt's own
-        generate_batch([prompt]) run. Results come back in prompt order."""
+        generate_batch([prompt]) run. Results come back in prompt order.
+        share_prefix / n: as generate_batch — a prompt admitted to a slot is also compared with the rows the session holds at
+        that moment (finished rows whose caches are still intact included), so a system prompt in front of many questions is
+        computed once per session, not once per question; with n > 1 the results are prompt-major (n per prompt)."""
         if not prompts:
             return []
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"n={n} (at least 1)")
+        share_prefix = bool(share_prefix) or n > 1
+        if share_prefix and (self._fake or self.policy_name != "longest_prefix"):
+            raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip', policy='longest_prefix')")
+        if n > 1:
+            prompts = [p for p in prompts for _ in range(n)]
         max_tokens = max_tokens or self.config["max_new_tokens"]
         temperature = temperature or self.config["temperature"]
         do_sample = do_sample if do_sample is not None else self.config["do_sample"]
@@ -706,7 +793,8 @@ class SpeculativePipeline:
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
-        sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens)
+        sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens,
+                             share_prefix=share_prefix)
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -740,7 +828,8 @@ class SpeculativePipeline:
                         "steps": r.steps, "sequence": list(r.seq), "kv_append_enabled": True, "kv_append_backend": "hip",
                         **({"k_trace": list(r.k_trace)} if r.k_trace else {}),
                         "batch_metrics": {"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
-                                          "void_row_steps": sess.stats["void_row_steps"], "k": sess.k}})
+                                          "void_row_steps": sess.stats["void_row_steps"], "k": sess.k,
+                                          **{key: sess.stats[key] for key in ("prefilled_rows", "forked_rows", "shared_positions")}}})
         return out
 
     def draft_agreement(self, text_or_ids: PromptLike, temperature: float = 1.0, chunk: int = 256) -> Dict[str, Any]:
@@ -821,11 +910,19 @@ class DecodeSession:
     repaired there (idle stream) and it rejoins. Steps are counted per row, so the reference's step bound
     applies to each row's own valid steps. Adaptive K, the sampled mode and the persistent Medusa heads
     keep the launch -> wait -> rules order (their next launch depends on the host, or on counters that a void
-    step would disturb)."""
+    step would disturb).
+
+    share_prefix: the session records, per row, the token prefix whose KV the row's caches hold (the prompt without its last
+    token, from the moment it was prefilled or forked until the slot is handed to another prompt). A row that enters — at the
+    start, or through admit() — is forked from the recorded row it has the longest prefix in common with instead of being
+    prefilled (SpeculativePipeline._absorb_row); stats counts prefilled_rows / forked_rows / shared_positions."""
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
-                 sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None, self_draft: bool = False):
+                 sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None, self_draft: bool = False,
+                 share_prefix: bool = False):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
+        if share_prefix and pipe._fake:
+            raise NotImplementedError("share_prefix needs the HIP engines (implementation='hip')")
         self.self_draft = self_draft
         self.sampling = sampling
         # speculative sampling (policy="rejection", backend="device"): the step's third mode instead of the sampled bonus token
@@ -862,7 +959,11 @@ class DecodeSession:
             for b in range(len(self.rows)):
                 e.release(b)
         self._fresh: set = set()                # rows whose slot was handed to a new sequence (admit)
-        pipe._prefill(self.rt, self.rows)
+        self.stats = {"steps": 0, "resyncs": 0, "proposed": 0, "accepted": 0, "device_ms": 0.0, "void_row_steps": 0,
+                      "prefilled_rows": 0, "forked_rows": 0, "shared_positions": 0}
+        # share_prefix: per row, the tokens whose KV both caches hold at positions [0, len) — None: not to be relied on
+        self._held: Optional[List[Optional[List[int]]]] = [None] * len(self.rows) if share_prefix else None
+        pipe._prefill(self.rt, self.rows, self._held, self.stats)
         self.loop.join_current_stream()
         for b, r in enumerate(self.rows):
             pipe._set_row(self.loop, b, r)
@@ -878,7 +979,6 @@ class DecodeSession:
         self._stateful_draft = self_draft and (pipe.medusa_heads is not None or pipe._eagle())
         if self_draft and pipe._eagle():
             self.loop.reset_eagle()   # the reference keeps the state on the pipeline object, across generate() calls even; here a run starts clean
-        self.stats = {"steps": 0, "resyncs": 0, "proposed": 0, "accepted": 0, "device_ms": 0.0, "void_row_steps": 0}
         self.step = 0
         from ..policies.controllers import FixedKController
 
@@ -962,12 +1062,19 @@ class DecodeSession:
         pipe, loop, rt = self.pipe, self.loop, self.rt
         for b, what in self._flagged.items():
             r = self.rows[b]
-            if b in self._fresh:                   # a new sequence in the slot: the old one's pages go back first (idle stream)
+            fresh = b in self._fresh
+            if fresh:                              # a new sequence in the slot: the old one's pages go back first (idle stream)
                 for e in self._engines:
                     e.release(b)
                 self._fresh.discard(b)
-            if what == "resync" and r.active:      # the host rules rewrote the row: rebuild its caches
-                pipe._prefill_row(rt, b, r.seq)
+            if what == "resync" and r.active:      # a new sequence, or the host rules rewrote the row: rebuild its caches
+                if fresh and self._held is not None:
+                    pipe._absorb_row(rt, b, r.seq, self._held, self.stats)    # forked from a row the session holds, if one fits
+                else:
+                    for e in self._engines:
+                        e.unshare(b)               # (pages shared with other rows are never written: the rebuild gets fresh ones)
+                    pipe._prefill_row(rt, b, r.seq)
+                    self.stats["prefilled_rows"] += 1 if fresh else 0
                 loop.join_current_stream()
             pipe._set_row(loop, b, r)              # (re)position, or freeze a finished row
             if self.per_row:                       # the device counted steps the host voided: hand it the in-order view
@@ -994,6 +1101,8 @@ class DecodeSession:
         self.loop._captured_paths = None
         for b, r in enumerate(self.rows):
             self._flagged[b] = "resync" if r.active else "freeze"
+            if self._held is not None and not r.active:
+                self._held[b] = None      # a finished row is not rebuilt: its caches are no longer a source to fork from
 
     @property
     def _inflight(self) -> bool:
@@ -1152,6 +1261,8 @@ class DecodeSession:
             raise ValueError(f"prompt of {len(prompt)} tokens does not fit this session (l_max {self.rt['l_max']}, positions {self.pos_limit})")
         self.rows[b] = _Row(list(prompt))
         self._fresh.add(b)
+        if self._held is not None:
+            self._held[b] = None          # the slot is reused: what its caches hold is no longer on record
         if self.per_row:
             self.row_ctl[b] = self._new_row_controller()
         self._flagged[b] = "resync"

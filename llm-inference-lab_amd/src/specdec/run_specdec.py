@@ -52,6 +52,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--prefill-backend", type=str, choices=["auto", "passes", "rocblas", "native"], default="auto",
                     help="how prompts are absorbed into the KV cache: auto (rocBLAS where it serves the model, else the 128-token passes), "
                          "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
+    ap.add_argument("--n", type=int, default=1,
+                    help="n completions of the prompt as n rows of one generate_batch call: the prompt is prefilled once and the other "
+                         "rows are forked from it (implies --share-prefix); they differ under --spec-sampling (a Philox stream per row)")
+    ap.add_argument("--share-prefix", action="store_true",
+                    help="decode through generate_batch with share_prefix=True (rows pay for an equal prompt or a common prefix once)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
@@ -119,10 +124,12 @@ def main(argv=None) -> int:
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
-        if args.spec_sampling:      # a generate_batch mode (a correction / bonus token every step): a batch of one
-            r = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens)[0]
-            r = {**pipe._sysinfo(), **r, "latency_ms": r["total_time_ms"],
-                 "acceptance_rate": r["accepted"] / max(r["proposed"], 1)}
+        batch = args.spec_sampling or args.share_prefix or args.n != 1
+        if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
+            rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n)
+            r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],
+                 "acceptance_rate": rs[0]["accepted"] / max(rs[0]["proposed"], 1), "n": len(rs), "texts": [x["text"] for x in rs],
+                 "forked_rows": rs[0]["batch_metrics"]["forked_rows"], "shared_positions": rs[0]["batch_metrics"]["shared_positions"]}
         else:
             r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
         if args.eval_perplexity:
@@ -134,6 +141,8 @@ def main(argv=None) -> int:
         return 1
     keys = ("latency_ms", "proposed", "accepted", "acceptance_rate", "tokens_per_sec", "text", "impl", "device",
             "base_model", "draft_model", "draft_mode", "dtype")
+    if args.share_prefix or args.n != 1:
+        keys += ("n", "texts", "forked_rows", "shared_positions")
     if args.eval_perplexity:
         keys += ("perplexity", "perplexity_loss")
     if args.eval_agreement:

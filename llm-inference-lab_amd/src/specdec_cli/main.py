@@ -52,8 +52,11 @@ def cmd_run(args: argparse.Namespace) -> int:
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
                                draft_mode="vanilla", **extra)
-    if spec:   # speculative sampling inside the captured step: a generate_batch mode, here a batch of one
-        res = {**pipe._sysinfo(), **pipe.generate_batch([args.prompt], max_tokens=args.max_tokens)[0]}
+    if spec or args.share_prefix or args.n != 1:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+        rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n)
+        res = {**pipe._sysinfo(), **rs[0]}
+        for i, x in enumerate(rs[1:], 1):
+            print(f"Text {i}: {x.get('text', '')}")
     else:
         res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample)
     kinfo = get_kernel_info()
@@ -90,6 +93,9 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--spec-top-k", type=int, help="--spec-sampling: keep the top_k (1..1024) largest logits of both distributions")
     pr.add_argument("--spec-top-p", type=float, help="--spec-sampling: nucleus cut inside --spec-top-k (needs it)")
     pr.add_argument("--seed", type=int, default=0)
+    pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
+                                                     "once and forked into the others (implies --share-prefix)")
+    pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
     pr.add_argument("prompt", type=str)
     pr.set_defaults(func=cmd_run)
     return p
