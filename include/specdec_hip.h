@@ -443,6 +443,26 @@ int64_t sd_model_prefill_count(const sd_model* m, int backend);
  * SPECDEC_PERSIST_TAPS is set when the loop is created: its rows are then not updated by the loop's passes.) */
 int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void* out, void* stream);
 
+/* Diagnostics of the multi-token weight-streaming kernels (csrc/gemm_skinny.hip, csrc/gemm_pipe.hip); host-only, no device
+ * call, additive (SD_ABI_VERSION stays 1).
+ *
+ * sd_gemm_plan writes the name of the template instantiation that one matrix launch of T tokens runs for a matrix of
+ * n_pairs row pairs and K inputs: the launchers take the same decision from the same function. w8: 1 = fp8 e4m3 weights;
+ * prologue: 0 none, 1 RMSNorm, 2 LayerNorm; epi: 0 QKV + RoPE, 1 residual, 2 SwiGLU, 3 gelu_new, 4 argmax. Names:
+ *   "pipe<EPI,tgN,DT,scS>"     the chunk pipeline: N token groups of 16, S steps per wave per chunk
+ *   "chunked<EPI,tgN,DT,nbS>"  the chunked fallback: S weight steps per batch
+ *   "slice<tgN>", "direct<tgN>" the two plain-residual bodies (bf16, no norm)
+ *   "gemv"                      T <= 9: csrc/gemv.hip (its variants are not named)
+ *   "none"                      no kernel covers the shape (a launch would be refused)
+ * with EPI in qkv, resid, swiglu, gelu, argmax and DT in bf16, fp8. flags: bit 0 = plan as if SPECDEC_NO_DIRECT were set,
+ * bit 1 = as if SPECDEC_NO_PIPE were; 0 follows the process's own environment, as a launch does. Refused: NULL out, a cap
+ * that does not hold the name and its NUL (32 bytes always do), T < 1, an unknown prologue / epi / flag bit.
+ *
+ * sd_model_matrix_shape: rows, inputs, row pairs, epilogue and prologue of one of the model's five matrix kinds
+ * (which: 0 qkv, 1 out, 2 gate / up, 3 down, 4 lm_head), as every launch of the forward passes them. */
+int sd_gemm_plan(int T, int n_pairs, int K, int w8, int prologue, int epi, int flags, char* out, size_t cap);
+int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_pairs, int* epi, int* prologue);
+
 /* Measurement hook: `iters` whole forwards of one row of M tokens (token id 0, positions pos0..pos0+M-1 of cache row 0,
  * which they overwrite; the attention reads the pos0 positions below, whatever the cache holds) between two HIP events on `stream`; returns the average duration of a forward and the bytes of weights
  * it streams. skip_head = 1 leaves the lm_head out. timeline (optional, host memory, `timeline_cap` uint64): in-kernel

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdlib.h>
+#include <string.h>
 
 #include <new>
 #include <vector>
@@ -1061,6 +1062,36 @@ extern "C" int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void
   }
   SD_HIP_CHECK(hipMemcpyAsync(out, src + static_cast<size_t>(row0) * w, static_cast<size_t>(n) * w * 2, hipMemcpyDeviceToDevice,
                               static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_pairs, int* epi, int* prologue) {
+  clear_error();
+  SD_REQUIRE(m && N && K && n_pairs && epi && prologue, "matrix_shape: NULL argument");
+  SD_REQUIRE(which >= 0 && which <= 4, "matrix_shape: which=%d (0 qkv, 1 out, 2 gate / up, 3 down, 4 lm_head)", which);
+  const MatShape sh = matrix_shape(m->cfg, which);
+  *N = sh.N;
+  *K = sh.K;
+  *n_pairs = sh.n_pairs;
+  *epi = sh.epi;
+  // as matrix_args: a matrix behind a normalisation (qkv, gate / up, lm_head) takes the architecture's norm as prologue
+  const bool normed = matrix_weights(m->cfg, which == 4 ? 4 * m->cfg.n_layers : which).norm_w != nullptr;
+  *prologue = !normed ? PRO_NONE : (m->cfg.arch == SD_ARCH_LLAMA ? PRO_RMSNORM : PRO_LAYERNORM);
+  return 0;
+}
+
+extern "C" int sd_gemm_plan(int T, int n_pairs, int K, int w8, int prologue, int epi, int flags, char* out, size_t cap) {
+  clear_error();
+  SD_REQUIRE(out, "gemm_plan: NULL out");
+  SD_REQUIRE(T >= 1, "gemm_plan: T=%d", T);
+  SD_REQUIRE(prologue >= PRO_NONE && prologue <= PRO_LAYERNORM && epi >= EPI_QKV_ROPE && epi <= EPI_ARGMAX && (flags & ~3) == 0,
+             "gemm_plan: prologue=%d epi=%d flags=%d out of range", prologue, epi, flags);
+  char name[64];
+  int n;
+  if (T <= kGemvMaxT) n = snprintf(name, sizeof(name), "gemv");
+  else n = gemm_plan_name(gemm_plan(T, n_pairs, K, w8 != 0, prologue, epi, flags), epi, w8 != 0, name, sizeof(name));
+  SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(name) && static_cast<size_t>(n) < cap, "gemm_plan: cap=%zu is too short for the name (%d bytes with its NUL)", cap, n + 1);
+  memcpy(out, name, static_cast<size_t>(n) + 1);
   return 0;
 }
 

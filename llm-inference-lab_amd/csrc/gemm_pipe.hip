@@ -520,53 +520,60 @@ static int launch_pipe_one(const GemvArgs& a, const PipeGeom& pg, int grid, size
 }
 
 template <int EPI, int TG, bool W8>
-static int launch_pipe_sc(const GemvArgs& a, const PipeGeom& pg, int sc, int grid, size_t smem, hipStream_t st) {
-  switch (sc) {
+static int launch_pipe_sc(const GemvArgs& a, const PipeGeom& pg, const GemmPlan& pl, int grid, size_t smem, hipStream_t st) {
+  switch (pl.steps) {
     case 1: return launch_pipe_one<EPI, TG, W8, 1>(a, pg, grid, smem, st);
     case 2: return launch_pipe_one<EPI, TG, W8, 2>(a, pg, grid, smem, st);
     case 4: return launch_pipe_one<EPI, TG, W8, 4>(a, pg, grid, smem, st);
-    default: return launch_pipe_one<EPI, TG, W8, 8>(a, pg, grid, smem, st);
+    case 8: return launch_pipe_one<EPI, TG, W8, 8>(a, pg, grid, smem, st);
+    default: SD_REQUIRE(false, "gemm_pipe: no kernel for %d steps per chunk", pl.steps);
   }
+  return 0;
 }
 
 template <int EPI, bool W8>
-static int launch_pipe_tg(const GemvArgs& a, const PipeGeom& pg, int sc, int grid, size_t smem, hipStream_t st) {
-  switch ((a.T + 15) / 16) {
-    case 1: return launch_pipe_sc<EPI, 1, W8>(a, pg, sc, grid, smem, st);
-    case 2: return launch_pipe_sc<EPI, 2, W8>(a, pg, sc, grid, smem, st);
-    case 3: return launch_pipe_sc<EPI, 3, W8>(a, pg, sc, grid, smem, st);
-    default: return launch_pipe_sc<EPI, 4, W8>(a, pg, sc, grid, smem, st);
+static int launch_pipe_tg(const GemvArgs& a, const PipeGeom& pg, const GemmPlan& pl, int grid, size_t smem, hipStream_t st) {
+  switch (pl.tg) {
+    case 1: return launch_pipe_sc<EPI, 1, W8>(a, pg, pl, grid, smem, st);
+    case 2: return launch_pipe_sc<EPI, 2, W8>(a, pg, pl, grid, smem, st);
+    case 3: return launch_pipe_sc<EPI, 3, W8>(a, pg, pl, grid, smem, st);
+    case 4: return launch_pipe_sc<EPI, 4, W8>(a, pg, pl, grid, smem, st);
+    default: SD_REQUIRE(false, "gemm_pipe: no kernel for %d token groups", pl.tg);
   }
+  return 0;
 }
 
 template <int EPI>
-static int launch_pipe_epi(const GemvArgs& a, const PipeGeom& pg, int sc, int grid, size_t smem, hipStream_t st) {
-  return a.w8 ? launch_pipe_tg<EPI, true>(a, pg, sc, grid, smem, st) : launch_pipe_tg<EPI, false>(a, pg, sc, grid, smem, st);
+static int launch_pipe_epi(const GemvArgs& a, const PipeGeom& pg, const GemmPlan& pl, int grid, size_t smem, hipStream_t st) {
+  return a.w8 ? launch_pipe_tg<EPI, true>(a, pg, pl, grid, smem, st) : launch_pipe_tg<EPI, false>(a, pg, pl, grid, smem, st);
 }
 
-bool gemm_pipe_covers(int T, int n_pairs, int K, bool w8) {
+// chunk width and steps per chunk of the pipeline for a shape, or false: the plan's question (gemm_plan, gemm_skinny.hip)
+bool gemm_pipe_plan(int T, int n_pairs, int K, bool w8, int* kc_out, int* sc_out) {
   if (T < 1 || T > 64 || n_pairs < 1) return false;
   const GemvGeom q = gemv_geometry(n_pairs, K);
   int sc = 0;
-  return pipe_chunk(T, (T + 15) / 16, K, q.ksplit, q.kw, w8, &sc) != 0;
+  const int kc = pipe_chunk(T, (T + 15) / 16, K, q.ksplit, q.kw, w8, &sc);
+  if (kc == 0) return false;
+  *kc_out = kc;
+  *sc_out = sc;
+  return true;
 }
 
-// The launcher of gemm_skinny.hip tries this first (a.ppw .. a.kw and the derived fields already set by it).
-int launch_gemm_pipe(const GemvArgs& a, const GemvGeom& q, int epi, hipStream_t st) {
-  const int TG = (a.T + 15) / 16;
-  int sc = 0;
+// The launcher of gemm_skinny.hip calls this for a BODY_PIPE plan (a.ppw .. a.kw and the derived fields already set by it).
+int launch_gemm_pipe(const GemvArgs& a, const GemvGeom& q, const GemmPlan& pl, int epi, hipStream_t st) {
   PipeGeom pg{};
-  pg.kc = pipe_chunk(a.T, TG, a.K, q.ksplit, q.kw, a.w8 != 0, &sc);
-  SD_REQUIRE(pg.kc != 0, "gemm_pipe: shape T=%d K=%d (ksplit %d) is not covered", a.T, a.K, q.ksplit);
+  pg.kc = pl.kc;
+  SD_REQUIRE(pl.body == BODY_PIPE && pg.kc != 0, "gemm_pipe: shape T=%d K=%d (ksplit %d) is not covered", a.T, a.K, q.ksplit);
   SD_REQUIRE(a.prologue == PRO_NONE || a.x_stride == a.K, "gemm_pipe: normalised rows must be contiguous (x_stride %d != K %d)", a.x_stride, a.K);
   pg.nchunks = a.K / pg.kc;
-  const size_t smem = pipe_smem(a.T, TG, pg.kc);
+  const size_t smem = pipe_smem(a.T, pl.tg, pg.kc);
   switch (epi) {
-    case EPI_QKV_ROPE: return launch_pipe_epi<EPI_QKV_ROPE>(a, pg, sc, q.grid, smem, st);
-    case EPI_RESID: return launch_pipe_epi<EPI_RESID>(a, pg, sc, q.grid, smem, st);
-    case EPI_SWIGLU: return launch_pipe_epi<EPI_SWIGLU>(a, pg, sc, q.grid, smem, st);
-    case EPI_GELU: return launch_pipe_epi<EPI_GELU>(a, pg, sc, q.grid, smem, st);
-    case EPI_ARGMAX: return launch_pipe_epi<EPI_ARGMAX>(a, pg, sc, q.grid, smem, st);
+    case EPI_QKV_ROPE: return launch_pipe_epi<EPI_QKV_ROPE>(a, pg, pl, q.grid, smem, st);
+    case EPI_RESID: return launch_pipe_epi<EPI_RESID>(a, pg, pl, q.grid, smem, st);
+    case EPI_SWIGLU: return launch_pipe_epi<EPI_SWIGLU>(a, pg, pl, q.grid, smem, st);
+    case EPI_GELU: return launch_pipe_epi<EPI_GELU>(a, pg, pl, q.grid, smem, st);
+    case EPI_ARGMAX: return launch_pipe_epi<EPI_ARGMAX>(a, pg, pl, q.grid, smem, st);
     default: SD_REQUIRE(false, "gemm_pipe: unknown epilogue %d", epi);
   }
   return 0;

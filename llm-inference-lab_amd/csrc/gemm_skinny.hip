@@ -737,24 +737,27 @@ static int launch_slice_one(const GemvArgs& a, int grid, hipStream_t st) {
 }
 
 // shapes the wave-private kernel takes: whole sub-slices per wave, equal K slices
-static bool slice_covers(const GemvArgs& a, const GemvGeom& q, int TG) {
+static bool slice_covers(int K, const GemvGeom& q, int TG) {
   const int W = TG <= 3 ? 64 : 32;
-  return TG >= 1 && TG <= 4 && q.kw % W == 0 && q.kw * q.ksplit == a.K && q.n_tiles <= kGemvWaves / q.ksplit;
+  return TG >= 1 && TG <= 4 && q.kw % W == 0 && q.kw * q.ksplit == K && q.n_tiles <= kGemvWaves / q.ksplit;
 }
 
 template <int EPI>
-static int launch_slice(const GemvArgs& a, int grid, hipStream_t st) {
-  switch ((a.T + 15) / 16) {
+static int launch_slice(const GemvArgs& a, const GemmPlan& pl, int grid, hipStream_t st) {
+  switch (pl.tg) {
     case 1: return launch_slice_one<EPI, 1>(a, grid, st);
     case 2: return launch_slice_one<EPI, 2>(a, grid, st);
     case 3: return launch_slice_one<EPI, 3>(a, grid, st);
-    default: return launch_slice_one<EPI, 4>(a, grid, st);
+    case 4: return launch_slice_one<EPI, 4>(a, grid, st);
+    default: SD_REQUIRE(false, "gemm_skinny: no wave-private kernel for %d token groups", pl.tg);
   }
+  return 0;
 }
 
 template <int EPI>
-static int launch_direct(const GemvArgs& a, int grid, hipStream_t st) {
-  const int TG = (a.T + 15) / 16;
+static int launch_direct(const GemvArgs& a, const GemmPlan& pl, int grid, hipStream_t st) {
+  const int TG = pl.tg;
+  SD_REQUIRE(TG >= 1 && TG <= 4, "gemm_skinny: no direct kernel for %d token groups", TG);
   const size_t smem = skinny_part_bytes(TG) + sizeof(float) * kGemvWaves * TG * 32;   // partials + row-statistics scratch, <= 72 KiB
   static unsigned long long attr_set = 0;   // (only the 4-tile instance passes 64 KiB)
   if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void*>(&gemm_direct_kernel<EPI, 4>), 80 * 1024, attr_set)) return rc;
@@ -777,61 +780,86 @@ static int launch_skinny_one(const GemvArgs& a, const SkinnyGeom& sg, int grid, 
   return 0;
 }
 
+// (tg, NB) -> instantiation: NB = 1 and 2 for every token-group count, NB = 4 for one token group only (the cases keep the
+// order in which the kernels were first instantiated: it is the order of the kernels in the code object)
 template <int EPI, bool W8>
-static int launch_skinny_w(const GemvArgs& a, const SkinnyGeom& sg, int grid, size_t smem, hipStream_t st) {
-  const int sc = 1 << sg.sc_shift;   // steps per wave per chunk: batches must not straddle a chunk boundary
-  const int tg = (a.T + 15) / 16;   // token groups: 1..4, then 6 and 8 (5 and 7 round up)
-  if (sc == 1) {
-    switch (tg) {
-      case 1: return launch_skinny_one<EPI, 1, W8, 1>(a, sg, grid, smem, st);
-      case 2: return launch_skinny_one<EPI, 2, W8, 1>(a, sg, grid, smem, st);
-      case 3: return launch_skinny_one<EPI, 3, W8, 1>(a, sg, grid, smem, st);
-      case 4: return launch_skinny_one<EPI, 4, W8, 1>(a, sg, grid, smem, st);
-      case 5: case 6: return launch_skinny_one<EPI, 6, W8, 1>(a, sg, grid, smem, st);
-      default: return launch_skinny_one<EPI, 8, W8, 1>(a, sg, grid, smem, st);
-    }
+static int launch_skinny_w(const GemvArgs& a, const SkinnyGeom& sg, const GemmPlan& pl, int grid, size_t smem, hipStream_t st) {
+  switch (pl.steps * 16 + pl.tg) {
+    case 1 * 16 + 1: return launch_skinny_one<EPI, 1, W8, 1>(a, sg, grid, smem, st);
+    case 1 * 16 + 2: return launch_skinny_one<EPI, 2, W8, 1>(a, sg, grid, smem, st);
+    case 1 * 16 + 3: return launch_skinny_one<EPI, 3, W8, 1>(a, sg, grid, smem, st);
+    case 1 * 16 + 4: return launch_skinny_one<EPI, 4, W8, 1>(a, sg, grid, smem, st);
+    case 1 * 16 + 6: return launch_skinny_one<EPI, 6, W8, 1>(a, sg, grid, smem, st);
+    case 1 * 16 + 8: return launch_skinny_one<EPI, 8, W8, 1>(a, sg, grid, smem, st);
+    case 4 * 16 + 1: return launch_skinny_one<EPI, 1, W8, 4>(a, sg, grid, smem, st);
+    case 2 * 16 + 1: return launch_skinny_one<EPI, 1, W8, 2>(a, sg, grid, smem, st);
+    case 2 * 16 + 2: return launch_skinny_one<EPI, 2, W8, 2>(a, sg, grid, smem, st);
+    case 2 * 16 + 3: return launch_skinny_one<EPI, 3, W8, 2>(a, sg, grid, smem, st);
+    case 2 * 16 + 4: return launch_skinny_one<EPI, 4, W8, 2>(a, sg, grid, smem, st);
+    case 2 * 16 + 6: return launch_skinny_one<EPI, 6, W8, 2>(a, sg, grid, smem, st);
+    case 2 * 16 + 8: return launch_skinny_one<EPI, 8, W8, 2>(a, sg, grid, smem, st);
+    default: SD_REQUIRE(false, "gemm_skinny: no chunked kernel for %d token groups at %d steps per batch", pl.tg, pl.steps);
   }
-  switch (tg) {
-    case 1:
-      if (sc % 4 == 0) return launch_skinny_one<EPI, 1, W8, 4>(a, sg, grid, smem, st);
-      return launch_skinny_one<EPI, 1, W8, 2>(a, sg, grid, smem, st);
-    case 2: return launch_skinny_one<EPI, 2, W8, 2>(a, sg, grid, smem, st);
-    case 3: return launch_skinny_one<EPI, 3, W8, 2>(a, sg, grid, smem, st);
-    case 4: return launch_skinny_one<EPI, 4, W8, 2>(a, sg, grid, smem, st);
-    case 5: case 6: return launch_skinny_one<EPI, 6, W8, 2>(a, sg, grid, smem, st);
-    default: return launch_skinny_one<EPI, 8, W8, 2>(a, sg, grid, smem, st);
-  }
+  return 0;
 }
 
 template <int EPI>
-static int launch_skinny_epi(const GemvArgs& a, const SkinnyGeom& sg, int grid, size_t smem, hipStream_t st) {
-  return a.w8 ? launch_skinny_w<EPI, true>(a, sg, grid, smem, st) : launch_skinny_w<EPI, false>(a, sg, grid, smem, st);
+static int launch_skinny_epi(const GemvArgs& a, const SkinnyGeom& sg, const GemmPlan& pl, int grid, size_t smem, hipStream_t st) {
+  return a.w8 ? launch_skinny_w<EPI, true>(a, sg, pl, grid, smem, st) : launch_skinny_w<EPI, false>(a, sg, pl, grid, smem, st);
 }
 
-// Which body a multi-token launch takes — ONE function, used by the launcher and by the forward's question "does this
-// EPI_RESID launch publish the row statistics" (a second copy of these conditions would let the two drift apart: the
-// consumer would then fold stale partial sums with no error). The knobs are read once.
-enum SkinnyBody { BODY_DIRECT, BODY_SLICE, BODY_PIPE, BODY_CHUNKED };
-static SkinnyBody choose_skinny_body(const GemvArgs& a, const GemvGeom& q, int epi) {
-  static const bool no_direct = getenv(debug_env::kNoDirect) != nullptr;
-  static const bool no_pipe = getenv(debug_env::kNoPipe) != nullptr;
+// Which instantiation a multi-token launch takes — ONE function. The launch switches above and in gemm_pipe.hip consume
+// its result, the forward's question "does this EPI_RESID launch publish the row statistics" reads it, and sd_gemm_plan
+// prints it (a second copy of these conditions would let them drift apart: the consumer of the statistics would then fold
+// stale partial sums with no error, and a test would name a kernel that did not run). The knobs are read once; `flags`
+// (kPlanNoDirect, kPlanNoPipe) adds to them for the plan query and is 0 in every launch.
+GemmPlan gemm_plan(int T, int n_pairs, int K, bool w8, int prologue, int epi, int flags) {
+  static const bool env_no_direct = getenv(debug_env::kNoDirect) != nullptr;
+  static const bool env_no_pipe = getenv(debug_env::kNoPipe) != nullptr;
+  const bool no_direct = env_no_direct || (flags & kPlanNoDirect) != 0;
+  const bool no_pipe = env_no_pipe || (flags & kPlanNoPipe) != 0;
+  GemmPlan pl{BODY_NONE, 0, 0, 0};
+  if (T < 1 || T > kSkinnyMaxT || n_pairs < 1 || K < 8 || K % 8 != 0) return pl;
+  const GemvGeom q = gemv_geometry(n_pairs, K);
+  // the chunk of the fallback body: a shape without one is refused whichever body would have taken it
+  const int kc = skinny_chunk(T, K, q.ksplit, q.kw, w8);
+  if (kc == 0) return pl;
   constexpr int slice_min_t = 17;
-  const int TG = (a.T + 15) / 16;
-  const bool plain_resid = !a.w8 && a.prologue == PRO_NONE && epi == EPI_RESID;
+  const int TG = (T + 15) / 16;
+  const bool plain_resid = !w8 && prologue == PRO_NONE && epi == EPI_RESID;
   // un-normalised, single-round shapes (out / down projections): operands straight to registers (measured on the 3B shapes:
   // ahead of the staged kernel up to 16 tokens, behind it from 24 — its B loads touch 16 rows x 64 bytes per instruction)
-  if (TG == 1 && plain_resid && q.n_tiles <= kGemvWaves / q.ksplit && !no_direct) return BODY_DIRECT;
+  if (TG == 1 && plain_resid && q.n_tiles <= kGemvWaves / q.ksplit && !no_direct) return {BODY_DIRECT, TG, 0, 0};
   // ... and from 17 tokens the wave-private staging
-  if (a.T >= slice_min_t && a.T <= 48 && plain_resid && slice_covers(a, q, TG)) return BODY_SLICE;
+  if (T >= slice_min_t && T <= 48 && plain_resid && slice_covers(K, q, TG)) return {BODY_SLICE, TG, 0, 0};
   // the statically scheduled chunk pipeline (gemm_pipe.hip) for everything else up to 64 tokens
-  if (!no_pipe && a.T <= 64 && gemm_pipe_covers(a.T, a.n_pairs, a.K, a.w8 != 0)) return BODY_PIPE;
-  return BODY_CHUNKED;
+  int pkc = 0, psc = 0;
+  if (!no_pipe && T <= 64 && gemm_pipe_plan(T, n_pairs, K, w8, &pkc, &psc)) return {BODY_PIPE, TG, psc, pkc};
+  // the chunked fallback: batches of NB weight steps must not straddle a chunk of sc steps per wave
+  const int sc = kc / ((w8 ? 64 : 32) * q.ksplit);   // a power of two (skinny_chunk)
+  const int tg = skinny_tg(T);                        // 1..4, then 6 and 8 (5 and 7 round up)
+  const int nb = sc == 1 ? 1 : (tg == 1 && sc % 4 == 0 ? 4 : 2);
+  return {BODY_CHUNKED, tg, nb, kc};
+}
+
+int gemm_plan_name(const GemmPlan& pl, int epi, bool w8, char* out, size_t cap) {
+  static const char* const epis[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
+  const char* e = epi >= 0 && epi <= EPI_ARGMAX ? epis[epi] : "?";
+  const char* dt = w8 ? "fp8" : "bf16";
+  switch (pl.body) {
+    case BODY_DIRECT: return snprintf(out, cap, "direct<tg%d>", pl.tg);
+    case BODY_SLICE: return snprintf(out, cap, "slice<tg%d>", pl.tg);
+    case BODY_PIPE: return snprintf(out, cap, "pipe<%s,tg%d,%s,sc%d>", e, pl.tg, dt, pl.steps);
+    case BODY_CHUNKED: return snprintf(out, cap, "chunked<%s,tg%d,%s,nb%d>", e, pl.tg, dt, pl.steps);
+    default: return snprintf(out, cap, "none");
+  }
 }
 
 // direct, slice and pipe bodies publish the row statistics of an EPI_RESID launch (xstat_out), the chunked fallback does not
 bool gemm_resid_publishes_stats(const GemvArgs& a) {
   if (a.T <= kGemvMaxT || a.T > 64 || a.x_row) return false;
-  return choose_skinny_body(a, gemv_geometry(a.n_pairs, a.K), EPI_RESID) != BODY_CHUNKED;
+  const int body = gemm_plan(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, EPI_RESID, 0).body;
+  return body == BODY_DIRECT || body == BODY_SLICE || body == BODY_PIPE;
 }
 
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8) {
@@ -854,26 +882,26 @@ int launch_gemm_skinny(const GemvArgs& a_in, int epi, hipStream_t st) {
   a.kw = q.kw;
   a.n_tiles_full = (q.ppw + q.tile_pairs - 1) / q.tile_pairs;
   gemv_derive(a);   // the shared epilogues index with the derived shifts
+  const GemmPlan pl = gemm_plan(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, 0);
+  SD_REQUIRE(pl.body != BODY_NONE, "gemm_skinny: shape T=%d K=%d (ksplit %d) is not covered", a.T, a.K, q.ksplit);
+  switch (pl.body) {
+    case BODY_DIRECT: return launch_direct<EPI_RESID>(a, pl, q.grid, st);
+    case BODY_SLICE: return launch_slice<EPI_RESID>(a, pl, q.grid, st);
+    case BODY_PIPE: return launch_gemm_pipe(a, q, pl, epi, st);
+    default: break;
+  }
   SkinnyGeom sg{};
-  sg.kc = skinny_chunk(a.T, a.K, q.ksplit, q.kw, a.w8 != 0);
-  SD_REQUIRE(sg.kc != 0, "gemm_skinny: shape T=%d K=%d (ksplit %d) is not covered", a.T, a.K, q.ksplit);
+  sg.kc = pl.kc;
   const int sc = sg.kc / ((a.w8 ? 64 : 32) * q.ksplit);
   sg.sc_shift = 0;
   while ((1 << sg.sc_shift) < sc) ++sg.sc_shift;
-  const int TG = skinny_tg(a.T);
-  switch (choose_skinny_body(a, q, epi)) {
-    case BODY_DIRECT: return launch_direct<EPI_RESID>(a, q.grid, st);
-    case BODY_SLICE: return launch_slice<EPI_RESID>(a, q.grid, st);
-    case BODY_PIPE: return launch_gemm_pipe(a, q, epi, st);
-    default: break;
-  }
-  const size_t smem = skinny_smem(a.T, TG, sg.kc);
+  const size_t smem = skinny_smem(a.T, pl.tg, sg.kc);
   switch (epi) {
-    case EPI_QKV_ROPE: return launch_skinny_epi<EPI_QKV_ROPE>(a, sg, q.grid, smem, st);
-    case EPI_RESID: return launch_skinny_epi<EPI_RESID>(a, sg, q.grid, smem, st);
-    case EPI_SWIGLU: return launch_skinny_epi<EPI_SWIGLU>(a, sg, q.grid, smem, st);
-    case EPI_GELU: return launch_skinny_epi<EPI_GELU>(a, sg, q.grid, smem, st);
-    case EPI_ARGMAX: return launch_skinny_epi<EPI_ARGMAX>(a, sg, q.grid, smem, st);
+    case EPI_QKV_ROPE: return launch_skinny_epi<EPI_QKV_ROPE>(a, sg, pl, q.grid, smem, st);
+    case EPI_RESID: return launch_skinny_epi<EPI_RESID>(a, sg, pl, q.grid, smem, st);
+    case EPI_SWIGLU: return launch_skinny_epi<EPI_SWIGLU>(a, sg, pl, q.grid, smem, st);
+    case EPI_GELU: return launch_skinny_epi<EPI_GELU>(a, sg, pl, q.grid, smem, st);
+    case EPI_ARGMAX: return launch_skinny_epi<EPI_ARGMAX>(a, sg, pl, q.grid, smem, st);
     default: SD_REQUIRE(false, "gemm_skinny: unknown epilogue %d", epi);
   }
   return 0;

@@ -141,8 +141,20 @@ int launch_gemm_skinny(const GemvArgs& a, int epi, hipStream_t st);   // T <= 64
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8 = false);                  // shape handled by gemm_skinny.hip
 // gemm_pipe.hip: the statically scheduled chunk pipeline for <= 64 tokens (tried first by launch_gemm_skinny, which has
 // set the work split fields of `a`)
-bool gemm_pipe_covers(int T, int n_pairs, int K, bool w8 = false);
-int launch_gemm_pipe(const GemvArgs& a, const GemvGeom& q, int epi, hipStream_t st);
+bool gemm_pipe_plan(int T, int n_pairs, int K, bool w8, int* kc_out, int* sc_out);   // covered: chunk width, steps per chunk
+// The template instantiation a launch of 10..128 tokens runs: decided once (gemm_plan, gemm_skinny.hip), consumed by the
+// launch switches of both files and printed by sd_gemm_plan.
+enum GemmBody { BODY_NONE = 0, BODY_DIRECT, BODY_SLICE, BODY_PIPE, BODY_CHUNKED };
+struct GemmPlan {
+  int body;    // GemmBody; BODY_NONE: the shape is not covered
+  int tg;      // token groups of the instantiation: 1..4 (direct, slice, pipe), 1..4, 6 or 8 (chunked)
+  int steps;   // pipe: SC, steps per wave per chunk (1, 2, 4, 8); chunked: NB, steps per weight batch (1, 2, 4); else 0
+  int kc;      // chunk width in columns (pipe, chunked), else 0
+};
+constexpr int kPlanNoDirect = 1, kPlanNoPipe = 2;   // `flags`: plan as if SPECDEC_NO_DIRECT / SPECDEC_NO_PIPE were set
+GemmPlan gemm_plan(int T, int n_pairs, int K, bool w8, int prologue, int epi, int flags);
+int gemm_plan_name(const GemmPlan& pl, int epi, bool w8, char* out, size_t cap);   // snprintf's return value
+int launch_gemm_pipe(const GemvArgs& a, const GemvGeom& q, const GemmPlan& pl, int epi, hipStream_t st);
 
 // ---- attention over the appended KV cache (attention.hip) -------------------------
 struct AttnArgs {

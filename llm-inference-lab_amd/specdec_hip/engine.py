@@ -442,6 +442,23 @@ class HipModel:
                        "sd_model_debug_rows")
         return out
 
+    def matrix_shape(self, which: int):
+        """(N, K, n_pairs, epi, prologue) of matrix kind `which` (0 qkv, 1 out, 2 gate / up, 3 down, 4 lm_head) as the forward
+        launches it (sd_model_matrix_shape)."""
+        v = [ctypes.c_int(0) for _ in range(5)]
+        _abi.check(self.lib.sd_model_matrix_shape(self.handle, int(which), *[ctypes.byref(x) for x in v]), "sd_model_matrix_shape")
+        return tuple(int(x.value) for x in v)
+
+    def pass_plan(self, T: int, flags: int = 0) -> List[str]:
+        """The five kernel instantiations (ops.gemm_plan) a launch-path pass of T tokens runs for qkv, out, gate / up, down and
+        lm_head (every layer runs the same four)."""
+        from .ops import gemm_plan
+        out = []
+        for which in range(5):
+            _, K, n_pairs, epi, prologue = self.matrix_shape(which)
+            out.append(gemm_plan(T, n_pairs, K, self.weight_dtype == "fp8", prologue, epi, flags))
+        return out
+
     def probe_forward(self, M: int = 1, iters: int = 50, skip_head: bool = False, timeline: bool = False,
                       stream: Optional[torch.cuda.Stream] = None, pos0: int = 0):
         """(average microseconds per forward of M tokens, bytes of weights per forward, timeline or None): sd_model_probe_forward.

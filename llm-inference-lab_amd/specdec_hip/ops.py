@@ -8,6 +8,7 @@ by the HIP kernels in csrc/. CPU tensors are rejected: there is no CPU fallback.
 
 from __future__ import annotations
 
+import ctypes
 import weakref
 from typing import Dict, Optional, Tuple
 
@@ -448,3 +449,18 @@ def quantize_fp8_rows_hip(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     with torch.cuda.device(dev):
         _abi.check(lib.sd_quantize_fp8_rows(w.data_ptr(), N, K, q.data_ptr(), sc.data_ptr(), _stream_ptr(dev)), "sd_quantize_fp8_rows")
     return q.view(torch.float8_e4m3fn), sc
+
+
+PRO_NONE, PRO_RMSNORM, PRO_LAYERNORM = range(3)                              # enum GemvPrologue (csrc/kernels.h)
+EPI_QKV_ROPE, EPI_RESID, EPI_SWIGLU, EPI_GELU, EPI_ARGMAX = range(5)         # enum GemvEpilogue
+PLAN_NO_DIRECT, PLAN_NO_PIPE = 1, 2                                          # sd_gemm_plan flags
+
+
+def gemm_plan(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID, flags: int = 0) -> str:
+    """Name of the kernel instantiation one matrix launch of T tokens runs (sd_gemm_plan): "pipe<swiglu,tg2,bf16,sc4>",
+    "chunked<qkv,tg6,fp8,nb1>", "slice<tg3>", "direct<tg1>", "gemv" (T <= 9) or "none" (not covered). Host-only: needs no GPU."""
+    buf = ctypes.create_string_buffer(64)
+    _abi.check(_abi.load().sd_gemm_plan(int(T), int(n_pairs), int(K), 1 if w8 else 0, int(prologue), int(epi), int(flags), buf, len(buf)),
+               "sd_gemm_plan")
+    return buf.value.decode()
+

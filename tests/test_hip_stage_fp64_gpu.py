@@ -52,9 +52,10 @@ def _weights(cfg):
     return _MODELS[cfg.name]
 
 
-def _matrices(mw, weight_dtype):
-    """the matrices the engine multiplies by, as fp64 on the device (fp8: the device's own quantiser, dequantised)"""
-    lw = mw.layers[0]
+def _matrices(mw, weight_dtype, layer=0):
+    """the matrices the engine multiplies by (those of `layer`, and the lm_head), as fp64 on the device (fp8: the device's own
+    quantiser, dequantised)"""
+    lw = mw.layers[layer]
     out = {}
     for k, m in (("wqkv", lw.wqkv), ("wo", lw.wo), ("w_up", lw.w_up), ("w_down", lw.w_down), ("head", mw.lm_head)):
         if weight_dtype == "fp8":
@@ -65,17 +66,17 @@ def _matrices(mw, weight_dtype):
     return out
 
 
-def _cache_rows(eng, row, positions):
-    """K / V of `positions` of cache row `row` (layer 0): ([Hkv][n][D], [Hkv][n][D]), dense or paged"""
+def _cache_rows(eng, row, positions, layer=0):
+    """K / V of `positions` of cache row `row` (of `layer`): ([Hkv][n][D], [Hkv][n][D]), dense or paged"""
     k, v = eng.kv_view()
     positions = positions.to(eng.device)
     if eng.page_len is None:
-        return k[0, row][:, positions], v[0, row][:, :, positions].transpose(1, 2)
+        return k[layer, row][:, positions], v[layer, row][:, :, positions].transpose(1, 2)
     P = eng.page_len
     pages = eng.block_table[row].long()[positions // P]
     off = positions % P
-    kk = k[0][pages, :, off].transpose(0, 1)                       # [Hkv][n][D]
-    vv = v[0][pages, :, :, off].permute(1, 0, 2)                    # [Hkv][n][D]
+    kk = k[layer][pages, :, off].transpose(0, 1)                   # [Hkv][n][D]
+    vv = v[layer][pages, :, :, off].permute(1, 0, 2)                # [Hkv][n][D]
     return kk, vv
 
 
@@ -105,10 +106,12 @@ def _write_prefix(eng, row, n, gen, peaked=False, spikes=()):
         v[0][pages, :, :, pos % P] = vv.permute(1, 0, 2)
 
 
-def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what):
+def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what, layer=0, x_in=None):
     """all stage checks of the last pass over query rows with tokens / absolute positions / cache rows [T] (the rows the
-    taps hold, in tap order). -> {stage: worst error / bound}"""
-    c, lw = mw.config, mw.layers[0]
+    taps hold, in tap order). -> {stage: worst error / bound}. The taps are the last layer's: `layer` > 0 checks the last
+    layer of a deeper model from x_in, the exact bf16 rows entering it (the caller's: no input uncertainty), with `mats`
+    that layer's matrices."""
+    c, lw = mw.config, mw.layers[layer]
     Hq, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
     T = tokens.shape[0]
     q = eng.debug_rows(HipModel.DEBUG_Q, T)
@@ -116,7 +119,7 @@ def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what):
     act = eng.debug_rows(HipModel.DEBUG_ACT, T)
     x2 = eng.hidden_rows(T)
     res = {}
-    x0, x0d = R.embed(c, mw, tokens, positions)
+    x0, x0d = R.embed(c, mw, tokens, positions) if x_in is None else (x_in.to(torch.float64), None)
     ref, bnd = R.qkv_stage(c, lw, mats["wqkv"], x0, x0d, positions, mw.rope_cos, mw.rope_sin, chain)
     res["q"] = R.check(q, (ref[:, :Hq * D], bnd[:, :Hq * D]), f"{what}: q")
     kn = torch.empty(T, Hkv * D, dtype=torch.bfloat16, device=eng.device)
@@ -127,7 +130,7 @@ def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what):
     allpos = torch.arange(S)
     for r in sorted(set(rows.tolist())):
         sel = (rows == r).nonzero().flatten().to(eng.device)
-        k_r, v_r = _cache_rows(eng, r, allpos)
+        k_r, v_r = _cache_rows(eng, r, allpos, layer)
         kk[sel], vv[sel] = k_r, v_r
         kn[sel] = k_r[:, positions[sel]].transpose(0, 1).reshape(-1, Hkv * D)
         vn[sel] = v_r[:, positions[sel]].transpose(0, 1).reshape(-1, Hkv * D)
