@@ -463,6 +463,30 @@ int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void* out, void
 int sd_gemm_plan(int T, int n_pairs, int K, int w8, int prologue, int epi, int flags, char* out, size_t cap);
 int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_pairs, int* epi, int* prologue);
 
+/* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
+ *
+ * sd_persist_plan answers, from a model's dimensions and facts alone (no weights, no device call; a GPU of 256 CUs is
+ * assumed), what sd_model_bind and the launch decide from the same functions: *eligible = 1 when the model passes every
+ * static rule (Llama, packed bf16 weights, head_dim 64 or 128, d_model / Hq*D / d_ff in whole 128s, d_model <= 4096,
+ * 1..60 layers, no bias, every matrix cut for <= 256 workgroups, <= 4 QKV tiles and an even gate / up split per workgroup,
+ * one token's rows fitting the LDS); *max_tokens = tokens a pass can hold (0 when not eligible; what
+ * sd_model_set_persist_tokens can raise a bound model to, given a cache of whole 8-key vectors). For 1 <= T <= *max_tokens,
+ * `name` is the kernel instantiation a pass of T tokens runs, "persist<D,HC>" with D the head dimension and HC the
+ * 1024-granule chunks of a d_model-wide row (2 above d_model 2048), and *ring_bytes the weight ring the LDS carve of one
+ * row of T tokens leaves. Otherwise name is "none", *ring_bytes 0 and `reason` names the rule that refused (the first in
+ * the order above, or T above the limit); reason is "" for an eligible T. packed: 1 = the tile streams of sd_pack_weights;
+ * weight_dtype: SD_BF16 or SD_FP8_E4M3; has_bias: 1 when any layer matrix has a bias. SPECDEC_NO_PERSIST is honoured as at
+ * a bind. Refused (nonzero): a NULL output, T < 1, a dimension below 1, a cap that does not hold the text and its NUL
+ * (32 bytes for the name and 96 for the reason always do). */
+int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
+                    int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
+                    char* name, size_t name_cap, char* reason, size_t reason_cap);
+
+/* Whether the persistent passes of `m` also store the stage rows (1, the default of a model outside a loop) or run the
+ * instantiation without those stores (0: what sd_specdec_create selects for its draft). A pass with skip_head keeps its
+ * stores either way. While it is off, sd_model_debug_rows and sd_model_hidden_rows are stale after a persistent pass. */
+int sd_model_set_persist_taps(sd_model* m, int enable);
+
 /* Measurement hook: `iters` whole forwards of one row of M tokens (token id 0, positions pos0..pos0+M-1 of cache row 0,
  * which they overwrite; the attention reads the pos0 positions below, whatever the cache holds) between two HIP events on `stream`; returns the average duration of a forward and the bytes of weights
  * it streams. skip_head = 1 leaves the lm_head out. timeline (optional, host memory, `timeline_cap` uint64): in-kernel

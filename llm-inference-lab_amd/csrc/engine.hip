@@ -1095,6 +1095,45 @@ extern "C" int sd_gemm_plan(int T, int n_pairs, int K, int w8, int prologue, int
   return 0;
 }
 
+extern "C" int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
+                               int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
+                               char* name, size_t name_cap, char* reason, size_t reason_cap) {
+  clear_error();
+  SD_REQUIRE(eligible && max_tokens && ring_bytes && name && reason, "persist_plan: NULL argument");
+  SD_REQUIRE(T >= 1, "persist_plan: T=%d", T);
+  SD_REQUIRE(weight_dtype == SD_BF16 || weight_dtype == SD_FP8_E4M3, "persist_plan: weight_dtype=%d (SD_BF16 or SD_FP8_E4M3)", weight_dtype);
+  SD_REQUIRE(d_model >= 1 && n_heads >= 1 && n_kv_heads >= 1 && head_dim >= 1 && d_ff >= 1 && vocab >= 1 && d_model <= (1 << 20) &&
+                 n_heads <= (1 << 12) && n_kv_heads <= (1 << 12) && head_dim <= (1 << 12) && d_ff <= (1 << 22) && vocab <= (1 << 24),
+             "persist_plan: a dimension is below 1 or beyond any model");
+  sd_model_config c{};
+  c.arch = arch; c.n_layers = n_layers; c.d_model = d_model; c.n_heads = n_heads; c.n_kv_heads = n_kv_heads;
+  c.head_dim = head_dim; c.d_ff = d_ff; c.vocab = vocab; c.weight_dtype = weight_dtype;
+  // (one row of T tokens: a pass of B rows x M tokens stages the attention state of M tokens only and leaves no less)
+  const PersistPlan pl = persist_plan(c, packed != 0, weight_dtype != SD_BF16, has_bias != 0, kPersistCUs, T, T);
+  char nm[32], why[96];
+  int n, r;
+  if (pl.refusal) r = snprintf(why, sizeof(why), "%s", pl.refusal);
+  else if (!pl.D) r = snprintf(why, sizeof(why), "tokens: T=%d above the %d a pass of this model holds", T, pl.max_tokens);
+  else r = snprintf(why, sizeof(why), "%s", "");
+  if (pl.D) n = snprintf(nm, sizeof(nm), "persist<%d,%d>", pl.D, pl.HC);
+  else n = snprintf(nm, sizeof(nm), "none");
+  SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(nm) && static_cast<size_t>(n) < name_cap, "persist_plan: name_cap=%zu is too short for the name (%d bytes with its NUL)", name_cap, n + 1);
+  SD_REQUIRE(r >= 0 && static_cast<size_t>(r) < sizeof(why) && static_cast<size_t>(r) < reason_cap, "persist_plan: reason_cap=%zu is too short for the reason (%d bytes with its NUL)", reason_cap, r + 1);
+  memcpy(name, nm, static_cast<size_t>(n) + 1);
+  memcpy(reason, why, static_cast<size_t>(r) + 1);
+  *eligible = pl.refusal ? 0 : 1;
+  *max_tokens = pl.max_tokens;
+  *ring_bytes = static_cast<int>(pl.ring_bytes);
+  return 0;
+}
+
+extern "C" int sd_model_set_persist_taps(sd_model* m, int enable) {
+  clear_error();
+  SD_REQUIRE(m, "set_persist_taps: NULL model");
+  m->persist_taps = enable != 0;
+  return 0;
+}
+
 extern "C" int sd_model_probe_forward(sd_model* m, int M, int pos0, int iters, int skip_head, void* stream, float* avg_usec,
                                       double* bytes_per_forward, unsigned long long* timeline, size_t timeline_cap) {
   clear_error();

@@ -81,6 +81,16 @@ bool persist_model_ok(const sd_model_config& c, bool packed, bool w8, int n_cus)
 inline bool persist_cache_ok(int l_max) { return l_max >= 8 && l_max % 8 == 0; }
 // tokens one pass can hold for this model (LDS: staged rows + ring), 0 = none
 int persist_max_tokens(const sd_model_config& c);
+// The whole decision, from the model's dimensions and facts alone (c's pointers are not read): persist_model_ok,
+// persist_max_tokens and sd_persist_plan are views of it, and the launch takes its LDS carve and instantiation from the same
+// two functions this fills D / HC / ring_bytes from.
+struct PersistPlan {
+  const char* refusal;    // null: the model is eligible; else which rule refused it
+  int max_tokens;         // tokens a pass can hold (0 when refused)
+  int D, HC;              // persist_forward_kernel<D, HC, ...> of a pass of T = B * M tokens, M per row; 0, 0: no such pass
+  unsigned ring_bytes;    // the weight ring that pass's LDS carve leaves
+};
+PersistPlan persist_plan(const sd_model_config& c, bool packed, bool w8, bool has_bias, int n_cus, int T, int M);
 int launch_persist_forward(PersistArgs a, hipStream_t st);
 
 }  // namespace sd

@@ -1336,38 +1336,70 @@ static LdsPlan plan_lds(int d_model, int HqD, int d_ff, int head_dim, int T, int
   p.ring_bytes = p.ok ? ((static_cast<unsigned>(kLdsBytes) - off) / kPiece) * kPiece : 0;
   return p;
 }
+// 1024-granule chunks of a d_model-wide row a consumer sweeps: the HC of the instantiation
+static int persist_chunks(int d_model) { return d_model > 2048 ? 2 : 1; }
 
 }  // namespace
 
-bool persist_model_ok(const sd_model_config& c, bool packed, bool w8, int n_cus) {
-  if (getenv(debug_env::kNoPersist)) return false;
-  if (c.arch != SD_ARCH_LLAMA || !packed || w8 || n_cus != kPersistCUs) return false;
-  if (c.head_dim != 64 && c.head_dim != 128) return false;
+// The static rules, in the order they are tested: the rule that refuses the model, or null. One decision: persist_model_ok,
+// persist_max_tokens, the launch and the host-only query sd_persist_plan all read it (persist_plan below).
+static const char* persist_refusal(const sd_model_config& c, bool packed, bool w8, bool has_bias, int n_cus) {
+  if (getenv(debug_env::kNoPersist)) return "SPECDEC_NO_PERSIST is set";
+  if (c.arch != SD_ARCH_LLAMA) return "architecture: Llama only";
+  if (!packed) return "weights: row-major (the launch streams the packed tile streams)";
+  if (w8) return "weights: fp8 storage (bf16 only)";
+  if (n_cus != kPersistCUs) return "device: not 256 CUs";
+  if (c.head_dim != 64 && c.head_dim != 128) return "head_dim: 64 or 128 only";
   const int HqD = c.n_heads * c.head_dim;
-  if (c.d_model % 128 || HqD % 128 || c.d_ff % 128 || c.d_model > 4096) return false;   // rows: whole 64-granule sweeps, <= 2 chunks of 1024
-  if (c.n_layers < 1 || c.n_layers > 60) return false;                                    // tags: layer * 8 + edge + 1 < 512
-  for (int l = 0; l < c.n_layers; ++l) {
-    const sd_layer_weights& w = c.layers[l];
-    if (w.bqkv || w.bo || w.b_up || w.b_down) return false;
-  }
+  if (c.d_model % 128 || HqD % 128 || c.d_ff % 128) return "rows: d_model, Hq * D and d_ff in whole 128s";   // whole 64-granule sweeps
+  if (c.d_model > 4096) return "d_model: above 4096 (two chunks of 1024 granules)";
+  if (c.n_layers < 1 || c.n_layers > 60) return "layers: 1 to 60 (tags: layer * 8 + edge + 1 < 512)";
+  if (has_bias) return "bias: a matrix has one";
   GemvGeom g[5];
   for (int i = 0; i < 5; ++i) {
     const MatShape sh = matrix_shape(c, i);
     g[i] = gemv_geometry(sh.n_pairs, sh.K);
-    if (g[i].grid > kPersistCUs) return false;   // every matrix cut for <= 256 workgroups
+    if (g[i].grid > kPersistCUs) return "work split: a matrix cut for more than 256 workgroups";
   }
   // QKV tiles (RoPE factors are staged per tile), even SwiGLU tiles (an activation granule holds two neighbouring pairs)
-  if ((g[0].ppw + g[0].tile_pairs - 1) / g[0].tile_pairs > kPersistMaxQkvTiles) return false;
-  if ((g[2].ppw & 1) || (g[2].tile_pairs & 1) || (c.d_ff & 1)) return false;
-  return persist_max_tokens(c) >= 1;
+  if ((g[0].ppw + g[0].tile_pairs - 1) / g[0].tile_pairs > kPersistMaxQkvTiles) return "QKV: more than 4 tiles per workgroup";
+  if ((g[2].ppw & 1) || (g[2].tile_pairs & 1) || (c.d_ff & 1)) return "gate / up: an odd number of pairs per workgroup or tile";
+  return nullptr;
 }
 
-int persist_max_tokens(const sd_model_config& c) {
-  int best = 0;
-  for (int T = 1; T <= kPersistMaxT; ++T)
-    if (plan_lds(c.d_model, c.n_heads * c.head_dim, c.d_ff, c.head_dim, T, T).ok) best = T;
-  return best;
+PersistPlan persist_plan(const sd_model_config& c, bool packed, bool w8, bool has_bias, int n_cus, int T, int M) {
+  PersistPlan pl{};
+  pl.refusal = persist_refusal(c, packed, w8, has_bias, n_cus);
+  if (pl.refusal) return pl;
+  const int HqD = c.n_heads * c.head_dim;
+  for (int t = 1; t <= kPersistMaxT; ++t)
+    if (plan_lds(c.d_model, HqD, c.d_ff, c.head_dim, t, t).ok) pl.max_tokens = t;
+  if (pl.max_tokens < 1) {
+    pl.refusal = "LDS: one token's rows do not fit next to a 64 KiB ring";
+    return pl;
+  }
+  if (T >= 1 && T <= pl.max_tokens && M >= 1 && M <= T) {
+    const LdsPlan p = plan_lds(c.d_model, HqD, c.d_ff, c.head_dim, T, M);
+    if (p.ok) {
+      pl.D = c.head_dim;
+      pl.HC = persist_chunks(c.d_model);
+      pl.ring_bytes = p.ring_bytes;
+    }
+  }
+  return pl;
 }
+
+bool persist_model_ok(const sd_model_config& c, bool packed, bool w8, int n_cus) {
+  bool has_bias = false;
+  for (int l = 0; l < c.n_layers && c.layers; ++l) {
+    const sd_layer_weights& w = c.layers[l];
+    has_bias = has_bias || w.bqkv || w.bo || w.b_up || w.b_down;
+  }
+  return persist_plan(c, packed, w8, has_bias, n_cus, 0, 0).refusal == nullptr;
+}
+
+// (of a model persist_model_ok accepted: the engine asks in that order)
+int persist_max_tokens(const sd_model_config& c) { return persist_plan(c, true, false, false, kPersistCUs, 0, 0).max_tokens; }
 
 // storage granules of a vector of n granules per token at the widest unit stride (n is a multiple of 16)
 static size_t edge_storage(size_t n_per_tok, unsigned unit) { return (n_per_tok * kPersistMaxT / 16) * unit; }
@@ -1429,7 +1461,7 @@ int launch_persist_forward(PersistArgs a, hipStream_t st) {
   a.off_edge[PE_ACT] = static_cast<unsigned>(off); off += edge_storage(a.d_ff / 2, a.gran_unit);
   SD_REQUIRE(off <= a.gran_parity, "persist: granule buffer too small");
   const size_t smem = kLdsBytes;
-  const bool two = a.d_model > 2048;
+  const bool two = persist_chunks(a.d_model) == 2;
   if (a.head_dim == 64) return two ? launch_one<64, 2>(a, smem, st) : launch_one<64, 1>(a, smem, st);
   return two ? launch_one<128, 2>(a, smem, st) : launch_one<128, 1>(a, smem, st);
 }

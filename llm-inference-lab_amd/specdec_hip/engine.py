@@ -382,6 +382,22 @@ class HipModel:
         captured a step over this model must be invalidated (HipSpecDec.invalidate)."""
         _abi.check(self.lib.sd_model_set_persist_tokens(self.handle, int(max_tokens)), "sd_model_set_persist_tokens")
 
+    def set_persist_taps(self, enable: bool) -> None:
+        """Whether persistent passes also store the stage rows (the default) or run the instantiation without those stores, as the
+        draft of a loop does (sd_model_set_persist_taps). A pass with skip_head keeps its stores; while off, debug_rows and
+        hidden_rows are stale after a persistent pass."""
+        _abi.check(self.lib.sd_model_set_persist_taps(self.handle, 1 if enable else 0), "sd_model_set_persist_taps")
+
+    def persist_plan(self, T: int = 1):
+        """ops.persist_plan of this model's dimensions, storage and biases for a pass of T tokens: eligibility, token limit,
+        instantiation name, ring bytes, reason. The model's own state (token limit set, length hint, paging, cache size) is
+        persist_active's question."""
+        from .ops import persist_plan
+        c = self.cfg
+        has_bias = any(getattr(l, f) is not None for l in self.weights.layers for f in ("bqkv", "bo", "b_up", "b_down"))
+        return persist_plan(c.arch, c.n_layers, c.d_model, c.n_heads, c.n_kv_heads, c.head_dim, c.d_ff, c.vocab, T,
+                            packed=self._packed is not None, weight_dtype=self.weight_dtype, has_bias=has_bias)
+
     def set_length_hint(self, max_len: Optional[int]) -> None:
         """The caller's bound on the current length of the rows the coming passes touch (None: the cache size). The persistent
         launch serves rows of up to 1280 positions (sd_model_set_length_hint)."""

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -464,3 +464,24 @@ def gemm_plan(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PR
                "sd_gemm_plan")
     return buf.value.decode()
 
+
+class PersistPlan(NamedTuple):
+    eligible: bool       # the model passes every static rule of the persistent forward
+    max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)
+    name: str            # "persist<64,1>" ... "persist<128,2>" for an eligible T, else "none"
+    ring_bytes: int      # weight ring the LDS carve of one row of T tokens leaves (0 with "none")
+    reason: str          # "" for an eligible T, else the rule that refused
+
+
+def persist_plan(arch: int, n_layers: int, d_model: int, n_heads: int, n_kv_heads: int, head_dim: int, d_ff: int, vocab: int,
+                 T: int = 1, packed: bool = True, weight_dtype: str = "bf16", has_bias: bool = False) -> PersistPlan:
+    """What the persistent forward (csrc/persist.hip) decides for a model of these dimensions and a pass of T tokens
+    (sd_persist_plan): the bind's eligibility rules, the token limit and the launch's instantiation, from the functions the
+    engine itself asks. Host-only: needs no GPU (256 CUs are assumed)."""
+    el, mt, ring = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    name, reason = ctypes.create_string_buffer(32), ctypes.create_string_buffer(96)
+    wd = {"bf16": _abi.SD_BF16, "fp8": _abi.SD_FP8_E4M3}[weight_dtype]
+    _abi.check(_abi.load().sd_persist_plan(int(arch), int(n_layers), int(d_model), int(n_heads), int(n_kv_heads), int(head_dim), int(d_ff),
+                                           int(vocab), 1 if packed else 0, wd, 1 if has_bias else 0, int(T), ctypes.byref(el),
+                                           ctypes.byref(mt), ctypes.byref(ring), name, len(name), reason, len(reason)), "sd_persist_plan")
+    return PersistPlan(bool(el.value), int(mt.value), name.value.decode(), int(ring.value), reason.value.decode())

@@ -109,9 +109,17 @@ def _prefill_backends():
     return prefill_backends_available()
 
 
-def get_kernel_info():
+def _persist_info(eng):
+    """the persistent forward's plan for a bound engine (specdec_hip.engine.HipModel)"""
+    plan = eng.persist_plan(max(1, eng.persist_tokens))
+    return {"eligible": plan.eligible, "max_tokens": plan.max_tokens, "tokens": eng.persist_tokens, "instance": plan.name,
+            "ring_bytes": plan.ring_bytes, "reason": plan.reason, "active": eng.persist_active(1)}
+
+
+def get_kernel_info(model=None):
     """Backend names per op. Keys as the reference (kernels/__init__.py:116-156);
-    the HIP ops report "hip" (the reference's own allowed set has no such name)."""
+    the HIP ops report "hip" (the reference's own allowed set has no such name). With a bound `model` (a HipModel), also the plan of its
+    persistent forward ("persist": eligibility, token limit, instantiation at the limit in force, reason when refused)."""
     device = _default_device()
     status = registry.get_status("cuda")
     lib_ok = True
@@ -119,7 +127,9 @@ def get_kernel_info():
         _abi.load()
     except Exception:  # reported, never swallowed into a fallback
         lib_ok = False
+    extra = {"persist": _persist_info(model)} if model is not None and lib_ok else {}
     return {
+        **extra,
         "verify_backend": _backend_of(status.get("verify_prefix", "unknown")),
         "kv_append_backend": _backend_of(status.get("kv_append", "unknown")),
         "verify_available": verify_prefix is not None and lib_ok,
