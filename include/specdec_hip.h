@@ -625,6 +625,34 @@ int sd_specdec_reset_eagle(sd_specdec* s, void* stream);
  * Requires B*(K+1) within one verify pass. Drops the captured graph. */
 int sd_specdec_set_medusa(sd_specdec* s, int n_heads, const void* const* packed_heads, int weight_dtype);
 
+/* The head evaluation of the Medusa and EAGLE steps on caller-supplied rows (a test / diagnostic entry: the step and this
+ * call run one function, so what it returns is what a step would propose from the same bits). `m` gives the shape
+ * ([vocab][d_model]), the final norm and the workspace; x_bf16 holds n_rows device rows of d_model bf16 values; row b of the
+ * B evaluated rows is row row_idx[b] of x (device int32 [B]; NULL: row b). packed_heads: n_heads (1..64) matrices packed
+ * by sd_pack_head in `weight_dtype` for this model's vocab and d_model. Heads at a constant ascending stride take the one
+ * launch of sd_specdec_set_medusa, others one launch each; more rows than one GEMV pass of this model holds (9, fewer for
+ * wide activation rows: 5 at d_ff 14336) are gathered (row_idx given) and take the multi-token kernel, one launch per head. flags: SD_HEADS_PER_HEAD forces one launch per head (what SPECDEC_MEDUSA_PER_HEAD does to a
+ * loop); SD_HEADS_NORMALISED says the rows are final-norm outputs already (no norm in front of the product: the launch
+ * of the EAGLE step over its extrapolated rows).
+ * Out: ids int32 [B][n_heads], and, when vals is not NULL, fp32 [B][n_heads]: the value the kernels attached to each
+ * winning index (the bf16-rounded logit, read from the launch's partials before anything reuses them); when launch_info (host
+ * int[2]) is not NULL, the matrix launches the call enqueued (1 = the one launch) and whether the rows were gathered first.
+ * Refused: unbound model, NULL or misaligned heads, unknown dtype / flags, fp8 with d_model % 64 != 0, B above one pass of
+ * the head kernels, a row index outside [0, n_rows) (the indices are read back and checked: the call synchronises
+ * `stream` when row_idx is given). Must not run concurrently with a forward or a step of `m` (it uses m's partials). */
+#define SD_HEADS_PER_HEAD 1
+#define SD_HEADS_NORMALISED 2
+int sd_model_head_argmax(sd_model* m, const void* x_bf16, int n_rows, const int32_t* row_idx, int B, int n_heads,
+                         const void* const* packed_heads, int weight_dtype, int flags, int32_t* ids, float* vals, int* launch_info,
+                         void* stream);
+
+/* The extrapolation launch of the EAGLE step on caller-supplied buffers (test / diagnostic entry; the step launches the
+ * same kernel): x bf16 [B][d_model] residual rows, H bf16 [B*K][d_model] out, prev bf16 [B][d_model] and has_prev int32 [B]
+ * the per-row state, read and then overwritten (prev <- h_K, has_prev <- 1). norm_w / norm_b: bf16 [d_model] (norm_b only
+ * for rms = 0, LayerNorm). K in 1..8. */
+int sd_eagle_extrapolate(const void* x_bf16, void* H, void* prev, int32_t* has_prev, const void* norm_w, const void* norm_b,
+                         float eps, float alpha, int d_model, int B, int K, int rms, void* stream);
+
 /* Enqueue ONE draft-then-verify step for all rows: K draft forwards (the first over
  * (prev,last), the rest over one token), one verify forward over (last,d_1..d_K),
  * the accept scan (wave ballot), the in-place state advance, and the copy of the

@@ -42,6 +42,7 @@ struct SpecState {
 int launch_draft_next(int M, int i, const SpecState& s, hipStream_t st);
 int launch_draft_finalize(const float* part_val, const int* part_idx, int grid, int M, int i, int32_t* ids, const SpecState& s,
                           const int32_t* skip_k, int skip_i, hipStream_t st);
+int launch_argmax_value(const float* part_val, const int* part_idx, int T, int grid, int M, int stride, float* vals, hipStream_t st);
 int launch_medusa_fill(const SpecState& s, hipStream_t st);
 int launch_medusa_rows(const SpecState& s, int32_t* row_idx, hipStream_t st);
 int launch_medusa_commit(const SpecState& s, hipStream_t st);

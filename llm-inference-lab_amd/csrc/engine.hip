@@ -1238,45 +1238,93 @@ struct sd_specdec {
 
 namespace sd {
 
-// draft tokens of the NEXT step from the heads: d_{i+1} = argmax head_i(final_norm(h)), h = the residual row of the
-// position that produced the last emitted token. Heads the caller packed at a constant stride (sd_specdec_set_medusa)
-// are evaluated by ONE lm_head-shaped launch (grid y = head: same x rows, same geometry, per-head argmax partials) and
-// one finalize over K x B results; otherwise one launch + finalize per head.
-static int enqueue_medusa_heads(sd_specdec* s, hipStream_t st) {
-  sd_model* m = s->target;
+// Argmax of n_heads vocabulary-sized matrices over T activation rows: what the Medusa step, the EAGLE step and
+// sd_model_head_argmax all run. The matrices have the lm_head's shape (and, unless `prenormed`, its final norm in front);
+// id of (matrix j, row t) -> ids[(t / M) * ids_stride + t % M + j].
+struct HeadEval {
+  const void* x = nullptr;          // bf16 rows of d_model elements (stride d_model)
+  const int32_t* x_row = nullptr;   // nullable, device [T]: row t reads row x_row[t] of x
+  int T = 0, M = 1;                 // rows, rows per batch row (the id layout; M == 1 whenever n_heads > 1)
+  int n_heads = 0;
+  const void* const* W = nullptr;          // [n_heads]
+  const float* const* scale = nullptr;     // [n_heads] fp32 row scales (w8), else null
+  size_t stride = 0;                // bytes between consecutive matrices when constant (one launch), else 0 (one launch each)
+  int packed = 1, w8 = 0;
+  bool prenormed = false;           // the rows are final-norm outputs already: PRO_NONE, no norm weights
+  int32_t* ids = nullptr;
+  int ids_stride = 0;
+  float* vals = nullptr;            // nullable: the fp32 value attached to each winning index, laid out as ids (debug entry only)
+  int* launch_info = nullptr;       // nullable, host [2]: matrix launches enqueued, 1 if the rows were gathered first (debug entry only)
+};
+
+// Matrices at a constant stride are evaluated by ONE lm_head-shaped launch (grid y = matrix: same x rows, same geometry,
+// per-matrix argmax partials) and one finalize over n_heads x T results; otherwise one launch + finalize per matrix.
+static int enqueue_head_argmax(sd_model* m, const HeadEval& e, hipStream_t st) {
   const sd_model_config& c = m->cfg;
-  const int B = s->B, K = s->K;
-  if (int rc = launch_medusa_rows(s->st, s->head_rows, st)) return rc;
-  GemvArgs h = matrix_args(m, 4 * c.n_layers);   // the lm_head's shape and final norm; the heads' own weights below
-  h.packed = 1;
-  h.w8 = s->head_scales.empty() ? 0 : 1;
-  h.x_row = s->head_rows;
-  h.T = B;
-  h.M = 1;
-  if (B > m->small_t) {   // more rows than a GEMV pass: gather them (the attention-output buffer is free after the verify forward)
-    if (int rc = launch_medusa_gather(m->x, s->head_rows, m->attn, B, c.d_model, st)) return rc;
+  const int T = e.T, nh = e.n_heads;
+  GemvArgs h = matrix_args(m, 4 * c.n_layers);   // the lm_head's shape and final norm; the matrices' own weights below
+  h.packed = e.packed;
+  h.w8 = e.w8;
+  h.x = e.x;
+  h.x_row = e.x_row;
+  h.T = T;
+  h.M = e.M;
+  if (e.prenormed) {
+    h.prologue = PRO_NONE;
+    h.norm_w = h.norm_b = nullptr;
+    h.norm_eps = 0.f;
+  }
+  if (e.x_row && T > m->small_t) {   // more rows than a GEMV pass: gather them (the attention-output buffer is free after the verify forward)
+    if (int rc = launch_medusa_gather(e.x, e.x_row, m->attn, T, c.d_model, st)) return rc;
     h.x = m->attn;
     h.x_row = nullptr;
+    if (e.launch_info) e.launch_info[1] = 1;
   }
   int ppw = 1;
   const int grid = gemv_grid(h, &ppw);
-  if (B <= m->small_t && s->head_stride && static_cast<size_t>(K) * B * grid <= static_cast<size_t>(kSkinnyMaxT) * kMaxPartials) {
-    h.W = s->heads[0];
-    h.w_scale = s->head_scales.empty() ? nullptr : s->head_scales[0];
-    h.batch_bytes = s->head_stride;
-    h.n_batch = K;
+  if (nh >= 2 && T <= m->small_t && e.stride && e.M == 1 &&
+      static_cast<size_t>(nh) * T * grid <= static_cast<size_t>(kSkinnyMaxT) * kMaxPartials) {
+    h.W = e.W[0];
+    h.w_scale = e.scale ? e.scale[0] : nullptr;
+    h.batch_bytes = e.stride;
+    h.n_batch = nh;
     if (int rc = launch_gemv(h, EPI_ARGMAX, st)) return rc;
-    // result (head j, row b) = "token" j * B + b of the partials -> verify_tok[b][j + 1]
-    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, K * B, grid, -B, K + 1, s->st.verify_tok + 1, st)) return rc;
-    return launch_medusa_commit(s->st, st);
+    if (e.launch_info) e.launch_info[0] = 1;
+    // result (matrix j, row t) = "token" j * T + t of the partials -> ids[t][j]
+    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, nh * T, grid, -T, e.ids_stride, e.ids, st)) return rc;
+    if (e.vals)
+      if (int rc = launch_argmax_value(m->part_val, m->part_idx, nh * T, grid, -T, e.ids_stride, e.vals, st)) return rc;
+    return 0;
   }
-  for (int i = 0; i < K; ++i) {
-    h.w_scale = s->head_scales.empty() ? nullptr : s->head_scales[i];
-    h.W = s->heads[i];
+  for (int i = 0; i < nh; ++i) {
+    h.w_scale = e.scale ? e.scale[i] : nullptr;
+    h.W = e.W[i];
     if (int rc = launch_gemv(h, EPI_ARGMAX, st)) return rc;
-    // token of head i of row b -> verify_tok[b][i+1]
-    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, B, grid, 1, K + 1, s->st.verify_tok + i + 1, st)) return rc;
+    if (e.launch_info) e.launch_info[0] += 1;
+    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, T, grid, e.M, e.ids_stride, e.ids + i, st)) return rc;
+    if (e.vals)
+      if (int rc = launch_argmax_value(m->part_val, m->part_idx, T, grid, e.M, e.ids_stride, e.vals + i, st)) return rc;
   }
+  return 0;
+}
+
+// draft tokens of the NEXT step from the heads: d_{i+1} = argmax head_i(final_norm(h)), h = the residual row of the
+// position that produced the last emitted token -> verify_tok[b][i + 1] (enqueue_head_argmax).
+static int enqueue_medusa_heads(sd_specdec* s, hipStream_t st) {
+  sd_model* m = s->target;
+  if (int rc = launch_medusa_rows(s->st, s->head_rows, st)) return rc;
+  HeadEval e;
+  e.x = m->x;
+  e.x_row = s->head_rows;
+  e.T = s->B;
+  e.n_heads = s->K;
+  e.W = s->heads.data();
+  e.scale = s->head_scales.empty() ? nullptr : s->head_scales.data();
+  e.stride = s->head_stride;
+  e.w8 = s->head_scales.empty() ? 0 : 1;
+  e.ids = s->st.verify_tok + 1;
+  e.ids_stride = s->K + 1;
+  if (int rc = enqueue_head_argmax(m, e, st)) return rc;
   return launch_medusa_commit(s->st, st);
 }
 
@@ -1291,17 +1339,21 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
     if (int rc = launch_eagle_extrapolate(m->x, s->eagle_H, s->eagle_prev, s->eagle_has, c.final_norm_w, c.final_norm_b, c.norm_eps,
                                           s->eagle_alpha, c.d_model, B, K, c.arch == SD_ARCH_LLAMA ? 1 : 0, st_t))
       return rc;
-    GemvArgs h = matrix_args(m, 4 * c.n_layers);
-    h.x = s->eagle_H;
-    h.T = B * K;
-    h.M = K;
-    h.prologue = PRO_NONE;     // the rows are final-norm outputs already
-    h.norm_w = h.norm_b = nullptr;
-    h.norm_eps = 0.f;
-    int ppw = 1;
-    const int grid = gemv_grid(h, &ppw);
-    if (int rc = launch_gemv(h, EPI_ARGMAX, st_t)) return rc;
-    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, B * K, grid, K, K + 1, s->st.verify_tok + 1, st_t)) return rc;
+    const void* const w_head = m->mat(4 * c.n_layers, c.lm_head);
+    const float* const sc_head = m->scale(4 * c.n_layers);
+    HeadEval e;
+    e.x = s->eagle_H;
+    e.T = B * K;
+    e.M = K;
+    e.n_heads = 1;
+    e.W = &w_head;
+    e.scale = sc_head ? &sc_head : nullptr;
+    e.packed = m->is_packed();
+    e.w8 = m->w8();
+    e.prenormed = true;        // the rows are final-norm outputs already
+    e.ids = s->st.verify_tok + 1;
+    e.ids_stride = K + 1;
+    if (int rc = enqueue_head_argmax(m, e, st_t)) return rc;
     if (int rc = launch_medusa_commit(s->st, st_t)) return rc;
   } else if (!s->draft && s->heads.empty()) {
     // self-draft (Medusa-lite, tied heads): the target's own next token, K times
@@ -1733,6 +1785,17 @@ extern "C" int sd_specdec_reset_eagle(sd_specdec* s, void* stream) {
   return 0;
 }
 
+// bytes between consecutive heads when they sit at a constant, ascending stride (-> one launch for all of them), else 0
+static size_t constant_stride(int n_heads, const void* const* packed_heads) {
+  if (n_heads < 2) return 0;
+  const char* h0 = static_cast<const char*>(packed_heads[0]);
+  const char* h1 = static_cast<const char*>(packed_heads[1]);
+  bool even = h1 > h0;
+  for (int i = 2; even && i < n_heads; ++i)
+    even = static_cast<const char*>(packed_heads[i]) - static_cast<const char*>(packed_heads[i - 1]) == h1 - h0;
+  return even ? static_cast<size_t>(h1 - h0) : 0;
+}
+
 extern "C" int sd_specdec_set_medusa(sd_specdec* s, int n_heads, const void* const* packed_heads, int weight_dtype) {
   clear_error();
   SD_REQUIRE(s, "specdec_set_medusa: NULL");
@@ -1760,17 +1823,69 @@ extern "C" int sd_specdec_set_medusa(sd_specdec* s, int n_heads, const void* con
       s->head_scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + packed_fp8_weight_bytes(h.n_pairs, h.K)));
     }
   }
-  s->head_stride = 0;
-  if (n_heads >= 2 && !getenv(debug_env::kMedusaPerHead)) {
-    const char* h0 = static_cast<const char*>(packed_heads[0]);
-    const char* h1 = static_cast<const char*>(packed_heads[1]);
-    bool even = h1 > h0;
-    for (int i = 2; even && i < n_heads; ++i)
-      even = static_cast<const char*>(packed_heads[i]) - static_cast<const char*>(packed_heads[i - 1]) == h1 - h0;
-    if (even) s->head_stride = static_cast<size_t>(h1 - h0);
-  }
+  s->head_stride = getenv(debug_env::kMedusaPerHead) ? 0 : constant_stride(n_heads, packed_heads);
   if (!s->head_rows) SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->head_rows), sizeof(int32_t) * s->B));
   return 0;
+}
+
+// The step's head evaluation (enqueue_head_argmax) on caller-supplied rows: ids and the value attached to each of them.
+extern "C" int sd_model_head_argmax(sd_model* m, const void* x_bf16, int n_rows, const int32_t* row_idx, int B, int n_heads,
+                                    const void* const* packed_heads, int weight_dtype, int flags, int32_t* ids, float* vals,
+                                    int* launch_info, void* stream) {
+  clear_error();
+  SD_REQUIRE(m && m->x && x_bf16 && packed_heads && ids, "model_head_argmax: NULL argument / model not bound");
+  SD_REQUIRE(n_heads >= 1 && n_heads <= 64, "model_head_argmax: n_heads=%d (1..64)", n_heads);
+  SD_REQUIRE(weight_dtype == SD_BF16 || weight_dtype == SD_FP8_E4M3, "model_head_argmax: weight_dtype %d", weight_dtype);
+  SD_REQUIRE((flags & ~(SD_HEADS_PER_HEAD | SD_HEADS_NORMALISED)) == 0, "model_head_argmax: unknown flags %#x", flags);
+  const sd_model_config& c = m->cfg;
+  SD_REQUIRE(weight_dtype == SD_BF16 || c.d_model % 64 == 0, "model_head_argmax: fp8 heads need d_model (%d) in whole 64-k steps", c.d_model);
+  SD_REQUIRE(B >= 1 && n_rows >= 1 && (row_idx || B <= n_rows), "model_head_argmax: B=%d rows of %d", B, n_rows);
+  SD_REQUIRE(B <= m->small_t || (B <= m->max_t && (!row_idx || c.n_heads * c.head_dim >= c.d_model)),
+             "model_head_argmax: batch %d exceeds one pass of the head kernels (%d rows)", B, m->max_t);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (row_idx) {   // a debug entry: the indices are checked on the host before any kernel follows them
+    std::vector<int32_t> host(static_cast<size_t>(B));
+    SD_HIP_CHECK(hipMemcpyAsync(host.data(), row_idx, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+    SD_HIP_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+      SD_REQUIRE(host[b] >= 0 && host[b] < n_rows, "model_head_argmax: row_idx[%d] = %d outside the %d rows", b, host[b], n_rows);
+  }
+  std::vector<const void*> heads;
+  std::vector<const float*> scales;
+  const MatShape hs = matrix_shape(c, 4);
+  for (int i = 0; i < n_heads; ++i) {
+    SD_REQUIRE(packed_heads[i], "model_head_argmax: head %d is NULL", i);
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(packed_heads[i]) & 255) == 0, "model_head_argmax: head %d is not 256-byte aligned", i);
+    heads.push_back(packed_heads[i]);
+    if (weight_dtype == SD_FP8_E4M3)   // the fp32 row scales follow the packed bytes (sd_pack_head)
+      scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + packed_fp8_weight_bytes(hs.n_pairs, hs.K)));
+  }
+  HeadEval e;
+  e.x = x_bf16;
+  e.x_row = row_idx;
+  e.T = B;
+  e.n_heads = n_heads;
+  e.W = heads.data();
+  e.scale = scales.empty() ? nullptr : scales.data();
+  e.stride = (flags & SD_HEADS_PER_HEAD) ? 0 : constant_stride(n_heads, packed_heads);
+  e.w8 = scales.empty() ? 0 : 1;
+  e.prenormed = (flags & SD_HEADS_NORMALISED) != 0;
+  e.ids = ids;
+  e.ids_stride = n_heads;
+  e.vals = vals;
+  if (launch_info) launch_info[0] = launch_info[1] = 0;
+  e.launch_info = launch_info;
+  return enqueue_head_argmax(m, e, st);
+}
+
+extern "C" int sd_eagle_extrapolate(const void* x_bf16, void* H, void* prev, int32_t* has_prev, const void* norm_w, const void* norm_b,
+                                    float eps, float alpha, int d_model, int B, int K, int rms, void* stream) {
+  clear_error();
+  SD_REQUIRE(x_bf16 && H && prev && has_prev && norm_w, "eagle_extrapolate: NULL argument");
+  SD_REQUIRE(rms || norm_b, "eagle_extrapolate: LayerNorm needs the bias");
+  SD_REQUIRE(d_model >= 1 && B >= 1 && B <= 65535 && K >= 1 && K <= 8, "eagle_extrapolate: d_model=%d B=%d K=%d (K in 1..8)", d_model, B, K);
+  return launch_eagle_extrapolate(x_bf16, H, prev, has_prev, norm_w, norm_b, eps, alpha, d_model, B, K, rms ? 1 : 0,
+                                  static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_specdec_step(sd_specdec* s, void* stream_target, void* stream_draft, int use_graph) {

@@ -46,9 +46,9 @@ int launch_embed(const EmbedArgs& a, hipStream_t st) {
   return 0;
 }
 
-// wave-wide fold of one token's per-workgroup partials
-__device__ __forceinline__ int fold_partials(const float* pv, const int* pi, int grid, int lane) {
-  float v = -INFINITY;
+// wave-wide fold of one token's per-workgroup partials -> the winning index, and in `v` the value attached to it
+__device__ __forceinline__ int fold_partials(const float* pv, const int* pi, int grid, int lane, float& v) {
+  v = -INFINITY;
   int i = 0x7fffffff;
   for (int s = lane; s < grid; s += kWave) {
     const float sv = pv[s];
@@ -58,6 +58,21 @@ __device__ __forceinline__ int fold_partials(const float* pv, const int* pi, int
   wave_reduce_argmax(v, i);
   return i;
 }
+__device__ __forceinline__ int fold_partials(const float* pv, const int* pi, int grid, int lane) {
+  float v;
+  return fold_partials(pv, pi, grid, lane, v);
+}
+
+// where the result of partials row t goes. M > 0: token t = b * M + m -> [b][m]. M < 0 (the batched head launch): t = j * B + b
+// with B = -M rows per matrix j -> [b][j]
+__device__ __forceinline__ int finalize_slot(int t, int M, int stride) {
+  if (M > 0) {
+    const int b = t / M, m = t - b * M;
+    return b * stride + m;
+  }
+  const int j = t / -M, b = t + j * M;
+  return b * stride + j;
+}
 
 // ids[b*ids_stride + m] = argmax over the lm_head partials of token t = b*M + m
 __global__ __launch_bounds__(kWave) void argmax_finalize_kernel(const float* part_val, const int* part_idx,
@@ -66,22 +81,30 @@ __global__ __launch_bounds__(kWave) void argmax_finalize_kernel(const float* par
   SD_SKIP_IF_INACTIVE(skip_k, skip_i);
   const int t = blockIdx.x, lane = threadIdx.x;
   const int i = fold_partials(part_val + static_cast<size_t>(t) * grid, part_idx + static_cast<size_t>(t) * grid, grid, lane);
-  if (lane == 0) {
-    // M > 0: token t = b * M + m. M < 0 (the batched head launch): t = j * B + b with B = -M rows per matrix j -> ids[b][j]
-    if (M > 0) {
-      const int b = t / M, m = t - b * M;
-      ids[b * ids_stride + m] = i;
-    } else {
-      const int j = t / -M, b = t + j * M;
-      ids[b * ids_stride + j] = i;
-    }
-  }
+  if (lane == 0) ids[finalize_slot(t, M, ids_stride)] = i;
 }
 
 int launch_argmax_finalize(const float* part_val, const int* part_idx, int T, int grid, int M,
                            int ids_stride, int32_t* ids_out, hipStream_t st, const int32_t* skip_k, int skip_i) {
   hipLaunchKernelGGL(argmax_finalize_kernel, dim3(T), dim3(kWave), 0, st, part_val, part_idx, grid, M,
                      ids_stride, ids_out, skip_k, skip_i);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+// The value the kernels attached to each winning index (sd_model_head_argmax only; no step launches it): the fold of
+// argmax_finalize_kernel over the same partials, storing the winner's fp32 value where that kernel stores its index. Runs
+// right after the finalize launch, before another launch reuses the partials.
+__global__ __launch_bounds__(kWave) void argmax_value_kernel(const float* part_val, const int* part_idx, int grid, int M, int stride,
+                                                             float* vals) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  float v;
+  (void)fold_partials(part_val + static_cast<size_t>(t) * grid, part_idx + static_cast<size_t>(t) * grid, grid, lane, v);
+  if (lane == 0) vals[finalize_slot(t, M, stride)] = v;
+}
+
+int launch_argmax_value(const float* part_val, const int* part_idx, int T, int grid, int M, int stride, float* vals, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_value_kernel, dim3(T), dim3(kWave), 0, st, part_val, part_idx, grid, M, stride, vals);
   SD_LAUNCH_CHECK();
   return 0;
 }

@@ -139,6 +139,10 @@ SIGNATURES = {
     "sd_specdec_reset_eagle": (_c_int, [_c_void_p, _c_void_p]),
     "sd_packed_head_bytes": (_c_size, [_c_int, _c_int, _c_int]),
     "sd_pack_head": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_size, _c_void_p]),
+    "sd_model_head_argmax": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, ctypes.POINTER(_c_void_p), _c_int, _c_int,
+                                      _c_void_p, _c_void_p, ctypes.POINTER(_c_int), _c_void_p]),
+    "sd_eagle_extrapolate": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, ctypes.c_float, ctypes.c_float,
+                                      _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "sd_specdec_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int]),
     "sd_specdec_sync": (_c_int, [_c_void_p, _c_void_p]),
     "sd_specdec_launches": (ctypes.c_long, [_c_void_p]),

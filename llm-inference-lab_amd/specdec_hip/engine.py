@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -491,6 +491,33 @@ class HipModel:
         _abi.check(rc, "sd_model_probe_forward")
         return float(usec.value), float(nbytes.value), tl
 
+    def head_argmax(self, x: torch.Tensor, heads: "PackedHeads", rows: Optional[torch.Tensor] = None, per_head: bool = False,
+                    normalised: bool = False, stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The head evaluation of the Medusa / EAGLE steps on the caller's rows (sd_model_head_argmax): x bf16 [n][d_model];
+        rows: int32 device indices into x (None: every row of x in order); heads: pack_heads of [n_heads][vocab][d_model].
+        -> (ids int32 [B][n_heads], values float32 [B][n_heads]: the bf16-rounded logit the kernels attached to each id).
+        per_head: one launch per head; normalised: x holds final-norm outputs (no norm in front of the product).
+        `self.head_launches` then holds what the call enqueued: (matrix launches, rows gathered first)."""
+        if x.dim() != 2 or x.dtype != torch.bfloat16 or x.device != self.device or x.shape[1] != self.cfg.d_model or not x.is_contiguous():
+            raise ValueError(f"head_argmax: x must be contiguous bf16 [n][{self.cfg.d_model}] on {self.device}")
+        if (heads.vocab, heads.d_model) != (self.cfg.vocab, self.cfg.d_model) or heads.buffer.device != self.device:
+            raise ValueError(f"head_argmax: heads are [{heads.vocab}][{heads.d_model}], the model's head is [{self.cfg.vocab}][{self.cfg.d_model}]")
+        if rows is not None:
+            if rows.dtype != torch.int32 or rows.device != self.device or rows.dim() != 1 or not rows.is_contiguous():
+                raise ValueError("head_argmax: rows must be a contiguous int32 vector on the model's device")
+        B = int(x.shape[0]) if rows is None else int(rows.numel())
+        n = len(heads.ptrs)
+        ids = torch.empty((B, n), dtype=torch.int32, device=self.device)
+        vals = torch.empty((B, n), dtype=torch.float32, device=self.device)
+        arr = (ctypes.c_void_p * n)(*heads.ptrs)
+        flags = (1 if per_head else 0) | (2 if normalised else 0)      # SD_HEADS_PER_HEAD | SD_HEADS_NORMALISED
+        with torch.cuda.device(self.device):
+            info = (ctypes.c_int * 2)(0, 0)
+            _abi.check(self.lib.sd_model_head_argmax(self.handle, x.data_ptr(), int(x.shape[0]), _ptr(rows), B, n, arr, heads.wd, flags,
+                                                     ids.data_ptr(), vals.data_ptr(), info, _stream(stream, self.device)), "sd_model_head_argmax")
+        self.head_launches = (int(info[0]), bool(info[1]))
+        return ids, vals
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.sd_model_destroy(self.handle)
@@ -501,6 +528,37 @@ class HipModel:
             self.close()
         except Exception:
             pass
+
+
+class PackedHeads(NamedTuple):
+    """Vocabulary-sized matrices packed by sd_pack_head into one device buffer (pack_heads)."""
+    buffer: torch.Tensor     # uint8, owns the storage
+    ptrs: List[int]          # device address of each head
+    wd: int                  # _abi.SD_BF16 | _abi.SD_FP8_E4M3
+    vocab: int
+    d_model: int
+
+
+def pack_heads(heads: torch.Tensor, weight_dtype: str = "bf16", uneven: bool = False) -> PackedHeads:
+    """heads bf16 [n][V][d] on a GPU -> each packed (and quantised for fp8) like an lm_head (sd_pack_head), at a constant
+    256-byte aligned stride in ONE buffer; uneven: one more 256 bytes in front of the last head (n >= 3), so that the
+    stride is not constant and the engine takes one launch per head."""
+    if heads.dim() != 3 or heads.dtype != torch.bfloat16 or not heads.is_cuda:
+        raise ValueError("pack_heads: need bf16 [n][V][d] on a GPU")
+    lib = _abi.load()
+    n, V, d = (int(v) for v in heads.shape)
+    wd = {"bf16": _abi.SD_BF16, "fp8": _abi.SD_FP8_E4M3}[weight_dtype]
+    nbytes = lib.sd_packed_head_bytes(V, d, wd)
+    stride = (nbytes + 255) // 256 * 256
+    offs = [i * stride + (256 if uneven and i == n - 1 else 0) for i in range(n)]
+    with torch.cuda.device(heads.device):
+        st = torch.cuda.current_stream(heads.device)
+        buf = torch.zeros(offs[-1] + stride + 256, dtype=torch.uint8, device=heads.device)
+        base = (buf.data_ptr() + 255) // 256 * 256
+        for i in range(n):
+            _abi.check(lib.sd_pack_head(heads[i].contiguous().data_ptr(), V, d, wd, base + offs[i], nbytes, st.cuda_stream), "sd_pack_head")
+        st.synchronize()
+    return PackedHeads(buf, [base + o for o in offs], wd, V, d)
 
 
 class StepRecord:
@@ -591,18 +649,10 @@ class HipSpecDec:
         K, V, d = heads.shape
         if K != self.K or heads.dtype != torch.bfloat16 or heads.device != self.device:
             raise ValueError(f"medusa heads must be bf16 [{self.K}][V][d] on {self.device}")
-        wd = _abi.SD_FP8_E4M3 if weight_dtype == "fp8" else _abi.SD_BF16
-        nbytes = self.lib.sd_packed_head_bytes(V, d, wd)
-        stride = (nbytes + 255) // 256 * 256      # heads at a constant stride in ONE buffer: the engine evaluates them in one launch
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device)
-            self._heads_packed = torch.empty(K * stride, dtype=torch.uint8, device=self.device)
-            base = self._heads_packed.data_ptr()
-            for i in range(K):
-                _abi.check(self.lib.sd_pack_head(heads[i].contiguous().data_ptr(), V, d, wd, base + i * stride, nbytes, st.cuda_stream), "sd_pack_head")
-            st.synchronize()
-            arr = (ctypes.c_void_p * K)(*[base + i * stride for i in range(K)])
-            _abi.check(self.lib.sd_specdec_set_medusa(self.handle, K, arr, wd), "sd_specdec_set_medusa")
+            self._heads_packed = pack_heads(heads, weight_dtype)      # one buffer, constant stride: the engine evaluates them in one launch
+            arr = (ctypes.c_void_p * K)(*self._heads_packed.ptrs)
+            _abi.check(self.lib.sd_specdec_set_medusa(self.handle, K, arr, self._heads_packed.wd), "sd_specdec_set_medusa")
 
     def set_eagle(self, alpha: float = 0.7, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """EAGLE-lite drafting for a loop created with draft=None (sd_specdec_set_eagle): K extrapolated hidden rows

@@ -451,6 +451,31 @@ def quantize_fp8_rows_hip(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q.view(torch.float8_e4m3fn), sc
 
 
+def eagle_extrapolate(x: torch.Tensor, prev: torch.Tensor, has_prev: torch.Tensor, norm_w: torch.Tensor,
+                      norm_b: Optional[torch.Tensor], eps: float, alpha: float, K: int, rms: bool = True) -> torch.Tensor:
+    """The extrapolation launch of the EAGLE step (sd_eagle_extrapolate) on the caller's buffers: x bf16 [B][d] residual rows;
+    prev bf16 [B][d] and has_prev int32 [B], the per-row state, are read and then OVERWRITTEN (prev <- h_K, has_prev <- 1).
+    -> H bf16 [B][K][d]: h_1 .. h_K of every row."""
+    lib = _abi.load()
+    dev = _require_device("eagle_extrapolate", x, prev, has_prev, norm_w)
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or prev.dtype != torch.bfloat16 or prev.shape != x.shape or norm_w.dtype != torch.bfloat16:
+        raise TypeError("eagle_extrapolate: x and prev must be bf16 [B][d], norm_w bf16 [d]")
+    B, d = (int(v) for v in x.shape)
+    if has_prev.dtype != torch.int32 or has_prev.shape != (B,) or norm_w.shape != (d,):
+        raise TypeError("eagle_extrapolate: has_prev must be int32 [B], norm_w [d]")
+    if not rms and (norm_b is None or norm_b.dtype != torch.bfloat16 or norm_b.shape != (d,) or norm_b.device != dev):
+        raise TypeError("eagle_extrapolate: LayerNorm needs a bf16 bias [d]")
+    if not (x.is_contiguous() and prev.is_contiguous() and has_prev.is_contiguous() and norm_w.is_contiguous()
+            and (norm_b is None or norm_b.is_contiguous())):
+        raise ValueError("eagle_extrapolate: tensors must be contiguous")
+    H = torch.empty((B, int(K), d), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_eagle_extrapolate(x.data_ptr(), H.data_ptr(), prev.data_ptr(), has_prev.data_ptr(), norm_w.data_ptr(),
+                                            norm_b.data_ptr() if norm_b is not None else None, float(eps), float(alpha), d, B, int(K),
+                                            1 if rms else 0, _stream_ptr(dev)), "sd_eagle_extrapolate")
+    return H
+
+
 PRO_NONE, PRO_RMSNORM, PRO_LAYERNORM = range(3)                              # enum GemvPrologue (csrc/kernels.h)
 EPI_QKV_ROPE, EPI_RESID, EPI_SWIGLU, EPI_GELU, EPI_ARGMAX = range(5)         # enum GemvEpilogue
 PLAN_NO_DIRECT, PLAN_NO_PIPE = 1, 2                                          # sd_gemm_plan flags

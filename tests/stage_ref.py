@@ -88,9 +88,10 @@ def finish(ref: torch.Tensor, err: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
 
 
 # ---- norms with their possible flips (term 3) ----------------------------------------------------------------------------------
-def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, x_delta: Optional[torch.Tensor] = None):
+def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, x_delta: Optional[torch.Tensor] = None, detail: bool = False):
     """HF LlamaRMSNorm rounding points: bf16(bf16(x * rs) * w). x: exact bf16 values [T][d] (x_delta: how far the kernel's
-    own x may be from x, per element). -> (normalised rows, per-element flip magnitude)"""
+    own x may be from x, per element). -> (normalised rows, per-element flip magnitude); detail (x_delta None): also the
+    share of the allowed statistic error a kernel needs to round an element to the other neighbour (<= 1 where a flip is allowed)"""
     x, w = x.to(F64), w.to(F64)
     d = x.shape[-1]
     ss = (x * x).sum(-1, keepdim=True)
@@ -109,11 +110,14 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, x_delta: Optional[torc
             ra, aa, _ = bf16_neighbours(ta)
             for cand in (ra, aa):
                 delta = torch.where(moved, torch.maximum(delta, (rne(cand * w) - xn).abs()), delta)
+    if detail:
+        return xn, delta, (t - (r1 + alt1) / 2).abs() / (rel * t.abs()).clamp_min(2.0 ** -300)
     return xn, delta
 
 
-def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, x_delta: Optional[torch.Tensor] = None):
-    """GPT-2 LayerNorm, rounded once: bf16((x - mean) * rs * w + b), fp32 statistics"""
+def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, x_delta: Optional[torch.Tensor] = None, detail: bool = False):
+    """GPT-2 LayerNorm, rounded once: bf16((x - mean) * rs * w + b), fp32 statistics (mean, then the variance around it);
+    detail: as rmsnorm"""
     x, w, b = x.to(F64), w.to(F64), b.to(F64)
     d = x.shape[-1]
     mean = x.mean(-1, keepdim=True)
@@ -129,6 +133,9 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, x_d
     # every bf16 value the kernel may have stored: t within tol, rounded
     xn = rne(t)
     delta = torch.maximum((rne(t - tol) - xn).abs(), (rne(t + tol) - xn).abs())
+    if detail:
+        r, alt, _ = bf16_neighbours(t)
+        return xn, delta, (t - (r + alt) / 2).abs() / tol.clamp_min(2.0 ** -300)
     return xn, delta
 
 
@@ -277,6 +284,161 @@ def head_stage(cfg, weights, W_head, x, chain):
     xn, dl = norm(cfg, x, weights.final_norm_w, weights.final_norm_b)
     y, err = product(xn, dl, W_head, chain(cfg.d_model))
     return finish(y, err)
+
+
+def head_stage_normed(xn: torch.Tensor, W_head: torch.Tensor, chain):
+    """a head over rows that are final-norm outputs already (the EAGLE step's extrapolated rows; sd_model_head_argmax with
+    SD_HEADS_NORMALISED): the product alone. xn: the exact bf16 rows the kernel reads -> (ref, bound) [T][V]. The value the
+    argmax epilogue compares and reports is the bf16-ROUNDED product (epilogue<EPI_ARGMAX>, csrc/gemv_device.h), so the
+    output rounding term stays."""
+    xn = xn.to(F64)
+    y, err = product(xn, torch.zeros(1, device=xn.device, dtype=F64), W_head, chain(xn.shape[-1]))
+    return finish(y, err)
+
+
+def gemv_geometry(n_pairs: int, K: int) -> dict:
+    """The work split of one matrix over the chip (csrc/pack.hip, gemv_geometry), restated: the tests pick shapes and tie
+    positions from it. grid workgroups own ppw consecutive row pairs each, cut into n_tiles tiles of tile_pairs pairs;
+    ksplit K slices per tile."""
+    grid = min(256, n_pairs)
+    ppw = -(-n_pairs // grid)
+    grid = -(-n_pairs // ppw)
+    n_tiles = 1
+    while n_tiles * 8 < ppw:
+        n_tiles *= 2
+    tile_pairs = -(-ppw // n_tiles)
+    ksplit = 16 // min(n_tiles, 16)
+    while ksplit > 1 and -(-K // (ksplit * 32)) < 2:
+        ksplit //= 2
+    return dict(grid=grid, ppw=ppw, n_tiles=n_tiles, tile_pairs=tile_pairs, ksplit=ksplit, kw=-(-K // (ksplit * 32)) * 32)
+
+
+def check_head_argmax(ids: torch.Tensor, vals: torch.Tensor, ref_bound, what: str) -> float:
+    """ids / vals [B][n_heads] (row-major, as sd_model_head_argmax returns them) against (ref, bound) [n_heads][B][V]:
+    for every (head j, row b), with id = ids[b][j],
+      |vals[b][j] - ref[j][b][id]| <= bound[j][b][id]                  the value the kernel attached to its winner is that logit
+      ref[j][b][id] >= max_v ref[j][b][v] - 2 max_v bound[j][b][v]     and no other logit can have been the larger one
+    (every computed logit is within its bound of ref, so the computed maximum is at least max(ref) - max(bound), and the
+    winner's reference is within its own bound of that). Holds for every correct kernel on every row: none is excluded.
+    -> worst |value - ref[id]| / bound[id]"""
+    ref, bound = ref_bound
+    nh, B, V = ref.shape
+    assert tuple(ids.shape) == (B, nh) and tuple(vals.shape) == (B, nh), (tuple(ids.shape), tuple(vals.shape), (B, nh))
+    idx = ids.t().long()
+    if bool(((idx < 0) | (idx >= V)).any()):
+        raise AssertionError(f"{what}: an id outside [0, {V}): {ids.tolist()}")
+    r_at = ref.gather(2, idx.unsqueeze(-1)).squeeze(-1)
+    b_at = bound.gather(2, idx.unsqueeze(-1)).squeeze(-1)
+    ratio = (vals.t().to(F64) - r_at).abs() / b_at
+    worst = float(ratio.max())
+    if not worst <= 1.0:
+        j, b = (int(v) for v in torch.unravel_index(ratio.argmax(), ratio.shape))
+        raise AssertionError(f"{what}: head {j} row {b}: value {float(vals[b, j]):.6g} at id {int(ids[b, j])}, reference "
+                             f"{float(r_at[j, b]):.6g}, bound {float(b_at[j, b]):.3g} ({worst:.2f} x)")
+    slack = ref.amax(-1) - 2 * bound.amax(-1) - r_at
+    if bool((slack > 0).any()):
+        j, b = (int(v) for v in torch.unravel_index(slack.argmax(), slack.shape))
+        raise AssertionError(f"{what}: head {j} row {b}: id {int(ids[b, j])} has reference {float(r_at[j, b]):.6g}, but index "
+                             f"{int(ref[j, b].argmax())} has {float(ref[j, b].max()):.6g} (2 x worst bound {2 * float(bound[j, b].max()):.3g})")
+    return worst
+
+
+def tie_copies(V: int, d: int, r: int) -> list:
+    """indices that get a copy of a head's winning row `r` in the tie tests, placed by the work split of a [V][d] head: BOTH
+    slots of one row pair (one lane of the argmax epilogue compares them), a second pair of that tile, another tile of the same
+    workgroup, another workgroup, the workgroup 64 further on (which the finalize folds in the same lane), and the last two
+    rows of the vocabulary (for an odd V: the second slot of the last full pair and the first slot of a pair whose second row
+    does not exist) -> sorted, with r itself"""
+    n_pairs = (V + 1) // 2
+    g = gemv_geometry(n_pairs, d)
+    p0 = g["ppw"] * min(3, g["grid"] - 1)                         # first pair of a workgroup
+    other_tile = p0 + (g["tile_pairs"] if g["n_tiles"] > 1 else 0)
+    other_wg = min(p0 + g["ppw"] * 5, n_pairs - 1)
+    same_lane = min(p0 + g["ppw"] * 64, n_pairs - 1)              # 64 workgroups on: the same lane of the finalize's fold over workgroups
+    cand = [2 * p0, 2 * p0 + 1, 2 * (p0 + min(1, g["ppw"] - 1)), 2 * other_tile, 2 * other_wg + 1, 2 * same_lane, V - 2, V - 1, r]
+    return sorted({c for c in cand if 0 <= c < V})
+
+
+def plant_ties(head: torch.Tensor, r: int, positions) -> torch.Tensor:
+    """a copy of `head` (bf16 [V][d]) whose rows at `positions` hold 2 x row r — exact in bf16, and exact under the fp8
+    row quantiser too (the scale doubles, the codes stay) — so that their logits tie exactly and clear every other row's"""
+    out = head.clone()
+    out[torch.as_tensor(list(positions), device=head.device)] = (head[r].float() * 2).to(head.dtype)
+    return out
+
+
+def check_ties(ids_row: torch.Tensor, vals_row: torch.Tensor, copies, ref_bound, b: int, what: str) -> None:
+    """row b of a call over the heads [all `copies` planted] + [copy i alone for every i] (plant_ties): the first head must
+    return the lowest of the copies, head 1 + i its only copy, and all returned values are the same bits — the planted rows
+    are identical, so their sums tie exactly wherever the work split puts them. The planted logit must clear every other
+    logit of the row by more than the bounds (checked first, from the reference: the construction's precondition)."""
+    ref, bound = ref_bound
+    r0 = ref[0, b]
+    other = torch.ones_like(r0, dtype=torch.bool)
+    other[torch.as_tensor(list(copies), device=r0.device)] = False
+    gap = float(r0[~other].min() - r0[other].max())
+    assert gap > 2 * float(bound[0, b].max()), f"{what}: the planted rows do not clear the rest ({gap:.3g}): pick another row"
+    got = [int(v) for v in ids_row.tolist()]
+    if got[0] != min(copies):
+        raise AssertionError(f"{what}: copies at {list(copies)}: the kernel returned {got[0]}, not the lowest")
+    if got[1:] != list(copies):
+        raise AssertionError(f"{what}: single copies at {list(copies)} returned as {got[1:]}")
+    if not bool((vals_row.view(torch.int32) == vals_row.view(torch.int32)[0]).all()):
+        raise AssertionError(f"{what}: the copies' values differ: {vals_row.tolist()} (the ties were not exact)")
+
+
+# ---- EAGLE extrapolation (eagle_extrapolate_kernel, csrc/misc.hip) -----------------------------------------------------------
+def eagle_recurrence(h_t: torch.Tensor, prev: torch.Tensor, has_prev: torch.Tensor, alpha: float, K: int):
+    """Everything after the norm, restated: elementwise fp32 with three bf16 roundings per step, no reduction, so a correct
+    kernel matches it bit for bit. h_t, prev: bf16 [B][d] (the device's own bits); has_prev [B]; alpha is used as a float32.
+      prv = prev if has_prev else h_t;  cur = h_t
+      diff = bf16(cur - prv);  sc = bf16(float32(alpha) * diff);  h = bf16(cur + sc);  prv, cur = cur, h
+    -> (H bf16 [B][K][d], state E = h_K bf16 [B][d])"""
+    a = torch.tensor(alpha, dtype=torch.float32, device=h_t.device)
+    cur = h_t.float()
+    prv = torch.where(has_prev.view(-1, 1) != 0, prev.float(), cur)
+    rows = []
+    for _ in range(K):
+        diff = (cur - prv).bfloat16().float()
+        sc = (a * diff).bfloat16().float()
+        h = (cur + sc).bfloat16()
+        rows.append(h)
+        prv, cur = cur, h.float()
+    return torch.stack(rows, 1), rows[-1]
+
+
+def check_eagle_norm(h_t: torch.Tensor, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float, rms: bool,
+                     what: str):
+    """the kernel's h_t (bf16 [B][d]: row 0 of a call with has_prev = 0) against the fp64 norm of x: each element equals the
+    reference's rounding unless the reference arithmetic itself (an fp32 statistic: two-pass for LayerNorm) could have
+    rounded to the other neighbour, and then differs by at most that flip (rmsnorm / layernorm above).
+    -> (elements on the other neighbour, the largest share of the allowed statistic error any of them needed to get there)"""
+    xn, delta, need = rmsnorm(x, w, eps, detail=True) if rms else layernorm(x, w, b, eps, detail=True)
+    err = (h_t.to(F64) - xn).abs()
+    bad = err > delta
+    if bool(bad.any()):
+        i = int((err - delta).argmax())
+        r, c = (int(v) for v in torch.unravel_index(torch.tensor(i), err.shape))
+        raise AssertionError(f"{what}: {int(bad.sum())} of {err.numel()} elements outside the derived bound; worst at [{r}, {c}]: "
+                             f"got {float(h_t[r, c]):.6g}, reference {float(xn[r, c]):.6g}, allowed flip {float(delta[r, c]):.3g}")
+    moved = err > 0
+    worst = float(need[moved].max()) if bool(moved.any()) else 0.0
+    return int(moved.sum()), worst
+
+
+def check_eagle_exact(H, prev_out, has_out, h_t, prev_in, has_in, alpha: float, what: str) -> None:
+    """H [B][K][d], the stored state and flags of one call against the restated recurrence from the device's own h_t and
+    prev bits: bit for bit"""
+    K = H.shape[1]
+    want_H, want_E = eagle_recurrence(h_t, prev_in, has_in, alpha, K)
+    for name, got, want in (("H", H, want_H), ("state", prev_out, want_E)):
+        ne = got.view(torch.int16) != want.view(torch.int16)
+        if bool(ne.any()):
+            idx = [int(v[0]) for v in ne.nonzero(as_tuple=True)]
+            raise AssertionError(f"{what}: {name} differs from the restated recurrence in {int(ne.sum())} of {ne.numel()} elements; first at "
+                                 f"{idx}: got {float(got[tuple(idx)]):.6g}, want {float(want[tuple(idx)]):.6g}")
+    if not bool((has_out == 1).all()):
+        raise AssertionError(f"{what}: has_prev after the call is {has_out.tolist()}, want all 1")
 
 
 def check(got: torch.Tensor, ref_bound, what: str) -> float:
