@@ -443,6 +443,15 @@ int64_t sd_model_prefill_count(const sd_model* m, int backend);
  * SPECDEC_PERSIST_TAPS is set when the loop is created: its rows are then not updated by the loop's passes.) */
 int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void* out, void* stream);
 
+/* Rows [row0, row0+n) of the LAST chunk of the last GEMM-prefilled prompt (rocBLAS or native backend), in position order: row r is
+ * the chunk's position r, for every one of its Mc <= 512 positions — not only the last <= 128 that sd_model_debug_rows and
+ * sd_model_hidden_rows see. `which` as for sd_model_debug_rows (0 residual stream, 1 q, 2 attention, 3 activation; last layer);
+ * bf16, asynchronous copy on `stream` out of the prefill workspace, which the chunk left as it is: a pure copy, and rows
+ * [Mc - min(Mc, 128), Mc) are bit for bit the rows those two entries return. The record is dropped by a bind and by every forward
+ * of this model that is not such a chunk (a replay of a captured graph runs no host code and leaves it). Refused (nonzero) when no
+ * chunk is on record, the range leaves [0, Mc), or `which` is unknown. Additive (SD_ABI_VERSION stays 1). */
+int sd_model_prefill_rows(sd_model* m, int which, int row0, int n, void* out, void* stream);
+
 /* Diagnostics of the multi-token weight-streaming kernels (csrc/gemm_skinny.hip, csrc/gemm_pipe.hip); host-only, no device
  * call, additive (SD_ABI_VERSION stays 1).
  *
@@ -481,6 +490,29 @@ int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_p
 int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
                     int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
                     char* name, size_t name_cap, char* reason, size_t reason_cap);
+
+/* Diagnostics of the native prompt-prefill GEMM (csrc/prefill_mfma.hip); host-only, additive (SD_ABI_VERSION stays 1).
+ *
+ * sd_prefill_plan answers, from a model's dimensions alone (no weights, no device call), what the launcher decides from the same
+ * functions for layer product `which` (0 qkv, 1 out, 2 gate / up, 3 down) over one chunk of T positions (1 .. 512), w8 = 1 for
+ * fp8 e4m3 storage: `name` = the kernel instantiation, "mfma<rf4,DT>" (128-row blocks) or "mfma<rf2,DT>" (64-row blocks), DT in
+ * bf16, fp8; *row_blocks and *token_blocks (128 tokens each), *grid = their product, *swizzled = 1 when the grid is a multiple of 8
+ * and workgroups are dealt to blocks XCD by XCD; *last_rows = rows of the last token block; *min_block_rows = the fewest packed
+ * rows any row block holds (blocks are whole tiles of the packed stream, so a block may hold fewer rows than its height and
+ * leaves lanes without a row); *k_stages = 64-k stages of the main loop. packed: 1 = the model has the packed weight streams.
+ * For a model the native backend refuses (not Llama; no packed weights; d_model, Hq*D or d_ff not in whole 64s) *eligible = 0,
+ * name is "none", the numbers are 0 and `reason` is the text sd_model_set_prefill_backend(SD_PREFILL_NATIVE) refuses it with (one
+ * function serves both); reason is "" otherwise. Refused (nonzero): a NULL output, `which` or T out of range, a dimension below 1, a cap that does not hold the
+ * text and its NUL (32 bytes for the name and 96 for the reason always do).
+ *
+ * sd_prefill_plan_tables: the same plan's tables. blocks[2 b] = first row pair of row block b and blocks[2 b + 1] = its packed rows
+ * (n_blocks = *row_blocks entries of two ints); wg_block[g] = the linear block index rb * token_blocks + tb that workgroup g of
+ * the grid computes (n_grid = *grid ints). Refused when the model is not eligible or a count is not the plan's. */
+int sd_prefill_plan(int arch, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int which, int T, int w8,
+                    int packed, int* eligible, int* row_blocks, int* token_blocks, int* grid, int* swizzled, int* last_rows,
+                    int* min_block_rows, int* k_stages, char* name, size_t name_cap, char* reason, size_t reason_cap);
+int sd_prefill_plan_tables(int arch, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int which, int T,
+                           int* blocks, size_t n_blocks, int* wg_block, size_t n_grid);
 
 /* Whether the persistent passes of `m` also store the stage rows (1, the default of a model outside a loop) or run the
  * instantiation without those stores (0: what sd_specdec_create selects for its draft). A pass with skip_head keeps its

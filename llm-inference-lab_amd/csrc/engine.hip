@@ -70,6 +70,8 @@ struct sd_model {
   int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
   int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
   sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
+  sd::PrefillRows prefill_rows;            // the last GEMM-prefill chunk's rows in prefill_ws (sd_model_prefill_rows), valid while
+  int prefill_mc = 0;                      // prefill_mc > 0: cleared by a bind and by every pass that is not such a chunk
   void* score_ws = nullptr;                // sd_model_score: normed rows, head partials, target logits, a zero word (first call)
   unsigned* host_status = nullptr;         // pinned host word: a persistent launch that gives up stores its reason here as well
   int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
@@ -157,6 +159,7 @@ static int forward_pass(sd_model* m, const int32_t* tokens, int tok_stride, cons
                         void* logits_out, int logits_dtype, int logits_stride, int skip_head,
                         hipStream_t st) {
   const sd_model_config& c = m->cfg;
+  m->prefill_mc = 0;   // this pass's rows are the model's last: the record of a GEMM-prefill chunk ends here
   const int T = Bc * Mc;
   const int d = c.d_model, Hq = c.n_heads, Hkv = c.n_kv_heads, D = c.head_dim, ff = c.d_ff;
   const bool llama = (c.arch == SD_ARCH_LLAMA);
@@ -379,6 +382,7 @@ template <class OnChunk>
 static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const int32_t* pos_base_row, int pos_off, int row, int M,
                        hipStream_t st, OnChunk&& on_chunk) {
   const sd_model_config& c = m->cfg;
+  m->prefill_mc = 0;
   if (!m->prefill_ws) SD_HIP_CHECK(hipMalloc(&m->prefill_ws, prefill_gemm_workspace_bytes(c)));
   PrefillModel pm{&m->cfg, m->k_cache, m->v_cache, m->B, m->Lmax, m->attn_ws, m->attn_cnt};
   pm.block_table = m->block_table;
@@ -407,6 +411,8 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
       SD_HIP_CHECK(hipMemcpyAsync(tp.dst, tp.src + static_cast<size_t>(mc - keep) * tp.w, static_cast<size_t>(keep) * tp.w * 2,
                                   hipMemcpyDeviceToDevice, st));
     if (int rc = on_chunk(m0, mc, rows.x)) return rc;
+    m->prefill_rows = rows;
+    m->prefill_mc = mc;
   }
   return 0;
 }
@@ -659,6 +665,7 @@ extern "C" int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, i
   m->block_table = nullptr;
   m->page_shift = m->max_pages = m->n_pages = 0;
   m->prefill_backend = SD_PREFILL_AUTO;
+  m->prefill_mc = 0;
   for (int64_t& n : m->prefill_count) n = 0;
   return carve_workspace(m, workspace);
 }
@@ -691,6 +698,7 @@ extern "C" int sd_model_bind_paged(sd_model* m, void* k_pool, void* v_pool, int 
   m->max_pages = max_pages_per_row;
   m->n_pages = n_pages;
   m->prefill_backend = SD_PREFILL_AUTO;
+  m->prefill_mc = 0;
   for (int64_t& n : m->prefill_count) n = 0;
   return carve_workspace(m, workspace);
 }
@@ -870,9 +878,8 @@ extern "C" int sd_model_set_prefill_backend(sd_model* m, int backend) {
     SD_REQUIRE(!m->block_table, "set_prefill_backend: rocBLAS prefill serves dense KV only (this model is bound to a paged cache)");
     SD_REQUIRE(prefill_gemm_available(), "set_prefill_backend: rocBLAS could not be opened");
   } else if (backend == SD_PREFILL_NATIVE) {
-    SD_REQUIRE(!gpt2, "set_prefill_backend: native prefill serves Llama models only (this model is GPT-2)");
-    SD_REQUIRE(m->is_packed(), "set_prefill_backend: native prefill reads the packed weights (this model has none: SPECDEC_NO_PACK)");
-    SD_REQUIRE(prefill_native_shapes_ok(m->cfg), "set_prefill_backend: native prefill needs d_model, Hq*D and d_ff multiples of 64");
+    const char* why = prefill_native_refusal(m->cfg, m->is_packed() != 0);
+    SD_REQUIRE(!why, "set_prefill_backend: %s", why);
   }
   m->prefill_backend = backend;
   return 0;
@@ -1062,6 +1069,97 @@ extern "C" int sd_model_debug_rows(sd_model* m, int which, int row0, int n, void
   }
   SD_HIP_CHECK(hipMemcpyAsync(out, src + static_cast<size_t>(row0) * w, static_cast<size_t>(n) * w * 2, hipMemcpyDeviceToDevice,
                               static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int sd_model_prefill_rows(sd_model* m, int which, int row0, int n, void* out, void* stream) {
+  clear_error();
+  SD_REQUIRE(m && out, "prefill_rows: NULL argument");
+  SD_REQUIRE(m->prefill_mc > 0, "prefill_rows: no GEMM-prefill chunk on record (the model's last forward was not one, or it was bound since)");
+  SD_REQUIRE(row0 >= 0 && n >= 1 && n <= m->prefill_mc && row0 <= m->prefill_mc - n, "prefill_rows: %d rows from row %d are outside the %d rows of the last chunk",
+             n, row0, m->prefill_mc);
+  const sd_model_config& c = m->cfg;
+  const uint16_t* src = nullptr;
+  size_t w = 0;
+  switch (which) {
+    case 0: src = m->prefill_rows.x; w = c.d_model; break;
+    case 1: src = m->prefill_rows.q; w = static_cast<size_t>(c.n_heads) * c.head_dim; break;
+    case 2: src = m->prefill_rows.attn; w = static_cast<size_t>(c.n_heads) * c.head_dim; break;
+    case 3: src = m->prefill_rows.act; w = c.d_ff; break;
+    default: SD_REQUIRE(false, "prefill_rows: which=%d (0 x, 1 q, 2 attn, 3 act)", which);
+  }
+  SD_HIP_CHECK(hipMemcpyAsync(out, src + static_cast<size_t>(row0) * w, static_cast<size_t>(n) * w * 2, hipMemcpyDeviceToDevice,
+                              static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// the model the plan queries build from dimensions alone (no weights are read)
+static int prefill_plan_config(int arch, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int which, int T, sd_model_config& c) {
+  SD_REQUIRE(which >= 0 && which <= 3, "prefill_plan: which=%d (0 qkv, 1 out, 2 gate / up, 3 down)", which);
+  SD_REQUIRE(T >= 1 && T <= kPrefillChunk, "prefill_plan: T=%d (a chunk holds 1 .. %d positions)", T, kPrefillChunk);
+  SD_REQUIRE(d_model >= 1 && n_heads >= 1 && n_kv_heads >= 1 && head_dim >= 1 && d_ff >= 1 && d_model <= (1 << 20) && n_heads <= (1 << 12) &&
+                 n_kv_heads <= (1 << 12) && head_dim <= (1 << 12) && d_ff <= (1 << 22),
+             "prefill_plan: a dimension is below 1 or beyond any model");
+  c = sd_model_config{};
+  c.arch = arch; c.n_layers = 1; c.d_model = d_model; c.n_heads = n_heads; c.n_kv_heads = n_kv_heads; c.head_dim = head_dim; c.d_ff = d_ff;
+  c.vocab = 2;
+  return 0;
+}
+
+extern "C" int sd_prefill_plan(int arch, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int which, int T, int w8,
+                               int packed, int* eligible, int* row_blocks, int* token_blocks, int* grid, int* swizzled, int* last_rows,
+                               int* min_block_rows, int* k_stages, char* name, size_t name_cap, char* reason, size_t reason_cap) {
+  clear_error();
+  SD_REQUIRE(eligible && row_blocks && token_blocks && grid && swizzled && last_rows && min_block_rows && k_stages && name && reason,
+             "prefill_plan: NULL argument");
+  sd_model_config c{};
+  if (int rc = prefill_plan_config(arch, d_model, n_heads, n_kv_heads, head_dim, d_ff, which, T, c)) return rc;
+  const char* refusal = prefill_native_refusal(c, packed != 0);   // the rule sd_model_set_prefill_backend(SD_PREFILL_NATIVE) applies
+  PrefillPlanInfo pl{};
+  if (!refusal) {
+    NativeTables t;
+    if (int rc = native_plan_tables(c, t)) return rc;
+    pl = native_plan_info(t, c, which, T);
+  }
+  char nm[32], why[96];
+  const int n = refusal ? snprintf(nm, sizeof(nm), "none") : snprintf(nm, sizeof(nm), "mfma<rf%d,%s>", pl.variant == 0 ? 4 : 2, w8 ? "fp8" : "bf16");
+  const int r = snprintf(why, sizeof(why), "%s", refusal ? refusal : "");
+  SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(nm) && static_cast<size_t>(n) < name_cap, "prefill_plan: name_cap=%zu is too short for the name (%d bytes with its NUL)", name_cap, n + 1);
+  SD_REQUIRE(r >= 0 && static_cast<size_t>(r) < sizeof(why) && static_cast<size_t>(r) < reason_cap, "prefill_plan: reason_cap=%zu is too short for the reason (%d bytes with its NUL)", reason_cap, r + 1);
+  memcpy(name, nm, static_cast<size_t>(n) + 1);
+  memcpy(reason, why, static_cast<size_t>(r) + 1);
+  *eligible = refusal ? 0 : 1;
+  *row_blocks = pl.n_blocks;
+  *token_blocks = pl.n_tb;
+  *grid = pl.grid;
+  *swizzled = pl.swizzled;
+  *last_rows = pl.last_tb_rows;
+  *min_block_rows = refusal ? 0 : pl.min_block_rows;
+  *k_stages = pl.k_stages;
+  return 0;
+}
+
+extern "C" int sd_prefill_plan_tables(int arch, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int which, int T,
+                                      int* blocks, size_t n_blocks, int* wg_block, size_t n_grid) {
+  clear_error();
+  SD_REQUIRE(blocks && wg_block, "prefill_plan_tables: NULL argument");
+  sd_model_config c{};
+  if (int rc = prefill_plan_config(arch, d_model, n_heads, n_kv_heads, head_dim, d_ff, which, T, c)) return rc;
+  const char* refusal = prefill_native_refusal(c, true);
+  SD_REQUIRE(!refusal, "prefill_plan_tables: %s", refusal);
+  NativeTables t;
+  if (int rc = native_plan_tables(c, t)) return rc;
+  const PrefillPlanInfo pl = native_plan_info(t, c, which, T);
+  SD_REQUIRE(n_blocks == static_cast<size_t>(pl.n_blocks) && n_grid == static_cast<size_t>(pl.grid),
+             "prefill_plan_tables: the plan has %d row blocks and a grid of %d (asked for %zu and %zu)", pl.n_blocks, pl.grid, n_blocks, n_grid);
+  for (int b = 0; b < pl.n_blocks; ++b) {
+    const int2 blk = t.blocks[pl.first_block + b];
+    int rows = 0;
+    for (int k = 0; k < blk.y; ++k) rows += 2 * t.tiles[blk.x + k].y;
+    blocks[2 * b] = t.tiles[blk.x].z;
+    blocks[2 * b + 1] = rows;
+  }
+  for (int g = 0; g < pl.grid; ++g) wg_block[g] = native_block_of(g, pl.grid);
   return 0;
 }
 

@@ -1,6 +1,8 @@
 // Prompt prefill as library GEMMs + this repo's norm / epilogue / attention kernels (csrc/prefill_gemm.hip). Internal interface.
 #pragma once
 
+#include <vector>
+
 #include "kernels.h"
 
 namespace sd {
@@ -25,6 +27,36 @@ struct NativePlan {
   void* buf = nullptr;      // device tables of all of them
 };
 bool prefill_native_shapes_ok(const sd_model_config& c);     // Llama, every K a multiple of 64
+// The one rule that admits a model to the native backend: null, or why not (sd_model_set_prefill_backend refuses with it,
+// sd_prefill_plan reports it). packed: the model has the packed weight streams.
+const char* prefill_native_refusal(const sd_model_config& c, bool packed);
+// The host half of the plan: every shape's tiles in stream order and its row blocks of both heights, as the device tables hold
+// them (block tile indices are absolute). No device work: native_plan_build uploads it, sd_prefill_plan reads it.
+struct NativeTables {
+  struct Span { size_t tiles, blocks; int n_blocks; };
+  std::vector<int4> tiles;     // {first row in its block, pairs, first pair, 0}
+  std::vector<int2> blocks;    // {first tile, tiles}
+  Span spans[5][2] = {};       // [shape][128-row blocks, 64-row blocks]
+  bool layers = false;         // the four layer shapes are present (else the lm_head alone)
+};
+int native_plan_tables(const sd_model_config& c, NativeTables& t);
+// Block height of one product: 0 = 128-row blocks (RF = 4) unless they would fill fewer than the CUs (one workgroup per CU, two
+// resident), else 1 = 64-row blocks (RF = 2). n_blocks_128: the shape's row blocks of 128 rows; n_tb: token blocks of the chunk.
+inline int native_block_variant(int n_blocks_128, int n_tb) { return n_blocks_128 * n_tb >= 256 ? 0 : 1; }
+// Workgroup blockIdx.x of a grid of G -> linear (row block, token block) index rb * n_tb + tb: the token blocks of one row block are
+// consecutive on one XCD (dispatch is round-robin over the 8 XCDs), so a weight piece is fetched from HBM once and shared through
+// that XCD's L2. A grid that is no multiple of 8 keeps the launch order.
+__host__ __device__ inline int native_block_of(int wg, int G) { return (G & 7) == 0 ? (wg & 7) * (G >> 3) + (wg >> 3) : wg; }
+// What launch_prefill_mfma runs for product `which` (0 qkv, 1 out, 2 gate / up, 3 down) over T <= kPrefillChunk rows (sd_prefill_plan)
+struct PrefillPlanInfo {
+  int variant;                 // 0: 128-row blocks, 1: 64-row blocks
+  int first_block, n_blocks;   // the row blocks: NativeTables::blocks[first_block ...]
+  int n_tb, grid, swizzled;
+  int last_tb_rows;            // rows of the last token block (1 .. 128)
+  int min_block_rows;          // fewest packed rows any row block holds (blocks are whole tiles)
+  int k_stages;                // 64-k stages of the main loop
+};
+PrefillPlanInfo native_plan_info(const NativeTables& t, const sd_model_config& c, int which, int T);
 // the layer shapes where prefill_native_shapes_ok, and the lm_head (N = vocab, K = d_model, pairs (2p, 2p + 1); either arch)
 int native_plan_build(const sd_model_config& c, NativePlan& plan);
 void native_plan_free(NativePlan& plan);

@@ -194,6 +194,7 @@ size_t prefill_gemm_workspace_bytes(const sd_model_config& c) {
   const size_t HqD = static_cast<size_t>(c.n_heads) * c.head_dim;
   size_t nmax = static_cast<size_t>(2) * c.d_ff;
   if ((c.n_heads + 2 * static_cast<size_t>(c.n_kv_heads)) * c.head_dim > nmax) nmax = (c.n_heads + 2 * static_cast<size_t>(c.n_kv_heads)) * c.head_dim;
+  if (static_cast<size_t>(c.d_model) > nmax) nmax = c.d_model;   // the out and down products (a d_model wider than 2 d_ff and the QKV rows)
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   return up(T * c.d_model * 2) * 2 + up(T * HqD * 2) * 2 + up(T * c.d_ff * 2) + up(T * nmax * 4) + 256;
 }

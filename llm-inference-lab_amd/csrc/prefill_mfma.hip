@@ -54,16 +54,23 @@ bool prefill_native_shapes_ok(const sd_model_config& c) {
   return c.arch == SD_ARCH_LLAMA && c.d_model % 64 == 0 && (c.n_heads * c.head_dim) % 64 == 0 && c.d_ff % 64 == 0;
 }
 
+const char* prefill_native_refusal(const sd_model_config& c, bool packed) {
+  if (c.arch != SD_ARCH_LLAMA) return "native prefill serves Llama models only (this model is GPT-2)";
+  if (!packed) return "native prefill reads the packed weights (this model has none: SPECDEC_NO_PACK)";
+  if (!prefill_native_shapes_ok(c)) return "native prefill needs d_model, Hq*D and d_ff multiples of 64";
+  return nullptr;
+}
+
 // Tiles of each matrix shape in stream order (the loop of pack_kernel: per workgroup share of ppw pairs, tiles of tile_pairs),
 // grouped into row blocks of whole tiles of <= 128 (and, separately, <= 64) rows.
-int native_plan_build(const sd_model_config& c, NativePlan& plan) {
+int native_plan_tables(const sd_model_config& c, NativeTables& t) {
   SD_REQUIRE(c.d_model % 64 == 0, "prefill: the native GEMM needs d_model a multiple of 64 (got %d)", c.d_model);
-  const bool layers = prefill_native_shapes_ok(c);
-  std::vector<int4> tiles;
-  std::vector<int2> blocks;
-  struct Span { size_t tiles, blocks; int n_blocks; };
-  Span spans[5][2] = {};
-  for (int i = layers ? 0 : 4; i < 5; ++i) {
+  t = NativeTables{};
+  t.layers = prefill_native_shapes_ok(c);
+  std::vector<int4>& tiles = t.tiles;
+  std::vector<int2>& blocks = t.blocks;
+  auto& spans = t.spans;
+  for (int i = t.layers ? 0 : 4; i < 5; ++i) {
     const MatShape sh = matrix_shape(c, i);
     const int n_pairs = sh.n_pairs;
     const GemvGeom q = gemv_geometry(n_pairs, sh.K);
@@ -95,6 +102,37 @@ int native_plan_build(const sd_model_config& c, NativePlan& plan) {
     for (int v = 0; v < 2; ++v)
       for (int b = 0; b < spans[i][v].n_blocks; ++b) blocks[spans[i][v].blocks + b].x += static_cast<int>(spans[i][v].tiles);
   }
+  return 0;
+}
+
+PrefillPlanInfo native_plan_info(const NativeTables& t, const sd_model_config& c, int which, int T) {
+  PrefillPlanInfo p{};
+  p.n_tb = (T + kBT - 1) / kBT;
+  p.variant = native_block_variant(t.spans[which][0].n_blocks, p.n_tb);
+  const NativeTables::Span& sp = t.spans[which][p.variant];
+  p.first_block = static_cast<int>(sp.blocks);
+  p.n_blocks = sp.n_blocks;
+  p.grid = p.n_blocks * p.n_tb;
+  p.swizzled = (p.grid & 7) == 0 ? 1 : 0;
+  p.last_tb_rows = T - (p.n_tb - 1) * kBT;
+  p.min_block_rows = 1 << 30;
+  for (int b = 0; b < sp.n_blocks; ++b) {
+    const int2 blk = t.blocks[sp.blocks + b];
+    int rows = 0;
+    for (int k = 0; k < blk.y; ++k) rows += 2 * t.tiles[blk.x + k].y;
+    p.min_block_rows = std::min(p.min_block_rows, rows);
+  }
+  p.k_stages = matrix_shape(c, which).K >> 6;
+  return p;
+}
+
+int native_plan_build(const sd_model_config& c, NativePlan& plan) {
+  NativeTables t;
+  if (int rc = native_plan_tables(c, t)) return rc;
+  const std::vector<int4>& tiles = t.tiles;
+  const std::vector<int2>& blocks = t.blocks;
+  const auto& spans = t.spans;
+  const bool layers = t.layers;
   const size_t tb = tiles.size() * sizeof(int4), bb = blocks.size() * sizeof(int2);
   native_plan_free(plan);
   SD_HIP_CHECK(hipMalloc(&plan.buf, tb + bb));
@@ -132,8 +170,7 @@ int launch_prefill_mfma(const NativePlan& plan, int which, const void* W, const 
   SD_REQUIRE(T >= 1 && T <= kPrefillChunk, "prefill: native GEMM of %d rows", T);
   SD_REQUIRE(W && X && Y && (!w8 || w_scale), "prefill: native GEMM with a NULL operand");
   const int n_tb = (T + kBT - 1) / kBT;
-  // 128-row blocks unless they would fill fewer than the CUs (one workgroup per CU, two resident)
-  const int v = plan.mat[which][0].n_blocks * n_tb >= 256 ? 0 : 1;
+  const int v = native_block_variant(plan.mat[which][0].n_blocks, n_tb);
   const NativeMat& m = plan.mat[which][v];
   MfmaArgs a{};
   a.W = static_cast<const char*>(W);

@@ -82,11 +82,8 @@ __device__ __forceinline__ void mfma_block_product(const MfmaArgs& a, char* smem
   const int n = lane & 15, g = lane >> 4;
   const int wt = wave & 1, wr = wave >> 1;       // token half, row half of the workgroup tile
 
-  // workgroup -> (row block, token block): the token blocks of one row block are consecutive on one XCD (dispatch is
-  // round-robin over the 8 XCDs), so a weight piece is fetched from HBM once and shared through that XCD's L2
-  const int G = a.n_blocks * a.n_tb;
-  int L = blockIdx.x;
-  if ((G & 7) == 0) L = (L & 7) * (G >> 3) + (L >> 3);
+  // workgroup -> (row block, token block): native_block_of (csrc/prefill_gemm.h)
+  const int L = native_block_of(static_cast<int>(blockIdx.x), a.n_blocks * a.n_tb);
   rb = L / a.n_tb;
   const int tb = L - rb * a.n_tb;
   const int2 blk = a.blocks[rb];

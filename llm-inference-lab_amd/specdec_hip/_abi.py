@@ -117,6 +117,9 @@ SIGNATURES = {
     "sd_model_prefill_backend": (_c_int, [_c_void_p]),
     "sd_model_prefill_count": (_c_i64, [_c_void_p, _c_int]),
     "sd_model_debug_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "sd_model_prefill_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "sd_prefill_plan": (_c_int, [_c_int] * 10 + [ctypes.POINTER(_c_int)] * 8 + [ctypes.c_char_p, _c_size, ctypes.c_char_p, _c_size]),
+    "sd_prefill_plan_tables": (_c_int, [_c_int] * 8 + [ctypes.POINTER(_c_int), _c_size, ctypes.POINTER(_c_int), _c_size]),
     "sd_gemm_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_char_p, _c_size]),
     "sd_model_matrix_shape": (_c_int, [_c_void_p] + [_c_int] + [ctypes.POINTER(_c_int)] * 5),
     "sd_persist_plan": (_c_int, [_c_int] * 12 + [ctypes.POINTER(_c_int)] * 3 + [ctypes.c_char_p, _c_size, ctypes.c_char_p, _c_size]),

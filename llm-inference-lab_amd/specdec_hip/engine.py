@@ -458,6 +458,25 @@ class HipModel:
                        "sd_model_debug_rows")
         return out
 
+    def prefill_rows(self, which: int, row0: int, n: int, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+        """bf16 [n][width]: rows [row0, row0 + n) of the last chunk of the last GEMM-prefilled prompt, in position order, for
+        every position of the chunk (sd_model_prefill_rows; `which` as for debug_rows). Raises when the model's last forward was
+        not such a chunk."""
+        c = self.cfg
+        width = {0: c.d_model, 1: c.n_heads * c.head_dim, 2: c.n_heads * c.head_dim, 3: c.d_ff}[int(which)]
+        out = torch.empty((max(int(n), 0), width), dtype=torch.bfloat16, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.sd_model_prefill_rows(self.handle, int(which), int(row0), int(n), out.data_ptr(), _stream(stream, self.device)),
+                       "sd_model_prefill_rows")
+        return out
+
+    def prefill_plan(self, which: int, T: int):
+        """ops.prefill_plan of this model's dimensions and storage for layer product `which` over a chunk of T positions."""
+        from .ops import prefill_plan
+        c = self.cfg
+        return prefill_plan(c.arch, c.d_model, c.n_heads, c.n_kv_heads, c.head_dim, c.d_ff, which, T, self.weight_dtype == "fp8",
+                            packed=self._packed is not None)
+
     def matrix_shape(self, which: int):
         """(N, K, n_pairs, epi, prologue) of matrix kind `which` (0 qkv, 1 out, 2 gate / up, 3 down, 4 lm_head) as the forward
         launches it (sd_model_matrix_shape)."""

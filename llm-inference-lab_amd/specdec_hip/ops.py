@@ -510,3 +510,43 @@ def persist_plan(arch: int, n_layers: int, d_model: int, n_heads: int, n_kv_head
                                            int(vocab), 1 if packed else 0, wd, 1 if has_bias else 0, int(T), ctypes.byref(el),
                                            ctypes.byref(mt), ctypes.byref(ring), name, len(name), reason, len(reason)), "sd_persist_plan")
     return PersistPlan(bool(el.value), int(mt.value), name.value.decode(), int(ring.value), reason.value.decode())
+
+
+class PrefillPlan(NamedTuple):
+    eligible: bool        # the native backend serves a model of these dimensions
+    name: str             # "mfma<rf4,bf16>", "mfma<rf2,fp8>", ... or "none"
+    row_blocks: int       # workgroups along the packed rows (128 rows each for rf4, 64 for rf2: whole tiles, so some hold fewer)
+    token_blocks: int     # workgroups along the chunk's positions (128 each)
+    grid: int             # row_blocks * token_blocks
+    swizzled: bool        # the grid is a multiple of 8: workgroups are dealt to blocks XCD by XCD
+    last_rows: int        # rows of the last token block (1 .. 128)
+    min_block_rows: int   # fewest packed rows in any row block
+    k_stages: int         # 64-k stages of the main loop
+    reason: str           # "" or the rule that refused the model
+    blocks: Tuple[Tuple[int, int], ...]   # (first row pair, packed rows) of every row block
+    wg_block: Tuple[int, ...]             # workgroup -> linear block index row_block * token_blocks + token_block
+
+    @property
+    def rb(self) -> int:
+        """block height of the instantiation: 128 (rf4) or 64 (rf2)"""
+        return 128 if "rf4" in self.name else 64
+
+
+def prefill_plan(arch: int, d_model: int, n_heads: int, n_kv_heads: int, head_dim: int, d_ff: int, which: int, T: int,
+                 w8: bool = False, packed: bool = True) -> PrefillPlan:
+    """What the native prompt-prefill GEMM (csrc/prefill_mfma.hip) decides for layer product `which` (0 qkv, 1 out, 2 gate / up,
+    3 down) of a model of these dimensions over one chunk of T <= 512 positions (sd_prefill_plan, sd_prefill_plan_tables): the
+    launcher's own block-height choice, row-block tables and workgroup mapping; for a model the backend refuses, the reason sd_model_set_prefill_backend gives. Host-only: needs no GPU."""
+    lib = _abi.load()
+    v = [ctypes.c_int(0) for _ in range(8)]
+    name, reason = ctypes.create_string_buffer(32), ctypes.create_string_buffer(96)
+    dims = (int(arch), int(d_model), int(n_heads), int(n_kv_heads), int(head_dim), int(d_ff), int(which), int(T))
+    _abi.check(lib.sd_prefill_plan(*dims, 1 if w8 else 0, 1 if packed else 0, *[ctypes.byref(x) for x in v], name, len(name), reason, len(reason)),
+               "sd_prefill_plan")
+    el, nb, ntb, grid, swz, last, minrows, ks = (int(x.value) for x in v)
+    blocks, wg = (), ()
+    if el:
+        b, g = (ctypes.c_int * (2 * nb))(), (ctypes.c_int * grid)()
+        _abi.check(lib.sd_prefill_plan_tables(*dims, b, nb, g, grid), "sd_prefill_plan_tables")
+        blocks, wg = tuple((b[2 * i], b[2 * i + 1]) for i in range(nb)), tuple(g)
+    return PrefillPlan(bool(el), name.value.decode(), nb, ntb, grid, bool(swz), last, minrows, ks, reason.value.decode(), blocks, wg)

@@ -106,18 +106,21 @@ def _write_prefix(eng, row, n, gen, peaked=False, spikes=()):
         v[0][pages, :, :, pos % P] = vv.permute(1, 0, 2)
 
 
-def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what, layer=0, x_in=None):
+def _check_pass(eng, mw, mats, tokens, positions, rows, logits, chain, what, layer=0, x_in=None, taps=None):
     """all stage checks of the last pass over query rows with tokens / absolute positions / cache rows [T] (the rows the
     taps hold, in tap order). -> {stage: worst error / bound}. The taps are the last layer's: `layer` > 0 checks the last
     layer of a deeper model from x_in, the exact bf16 rows entering it (the caller's: no input uncertainty), with `mats`
-    that layer's matrices."""
+    that layer's matrices. taps(which, T): where the T rows of stage `which` (HipModel.DEBUG_*) come from instead of
+    debug_rows / hidden_rows (tests/test_hip_prefill_rows_fp64_gpu.py: any 128 rows of a prompt's last chunk)."""
     c, lw = mw.config, mw.layers[layer]
     Hq, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
     T = tokens.shape[0]
-    q = eng.debug_rows(HipModel.DEBUG_Q, T)
-    attn = eng.debug_rows(HipModel.DEBUG_ATTN, T)
-    act = eng.debug_rows(HipModel.DEBUG_ACT, T)
-    x2 = eng.hidden_rows(T)
+    if taps is None:
+        taps = lambda which, n: eng.hidden_rows(n) if which == HipModel.DEBUG_X else eng.debug_rows(which, n)
+    q = taps(HipModel.DEBUG_Q, T)
+    attn = taps(HipModel.DEBUG_ATTN, T)
+    act = taps(HipModel.DEBUG_ACT, T)
+    x2 = taps(HipModel.DEBUG_X, T)
     res = {}
     x0, x0d = R.embed(c, mw, tokens, positions) if x_in is None else (x_in.to(torch.float64), None)
     ref, bnd = R.qkv_stage(c, lw, mats["wqkv"], x0, x0d, positions, mw.rope_cos, mw.rope_sin, chain)

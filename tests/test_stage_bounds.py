@@ -10,6 +10,7 @@ import math
 import pytest
 import torch
 
+import prefill_cases as P
 import stage_ref as R
 from oracle.fp8_ref import quantize_rows
 from specdec_hip import weights as W
@@ -38,9 +39,9 @@ def _trunc(x):
 class Emu:
     """One row of M new tokens at positions pos0.. over a cache of pos0 prefix keys, with the device's rounding points."""
 
-    def __init__(self, cfg, weight_dtype="bf16", seed=0):
+    def __init__(self, cfg, weight_dtype="bf16", seed=0, weights=None):
         self.cfg = cfg
-        self.w = W.random_init(cfg, seed=seed)
+        self.w = W.random_init(cfg, seed=seed) if weights is None else weights
         self.fp8 = weight_dtype == "fp8"
         self.mats = {}
         for name in ("wqkv", "wo", "w_up", "w_down"):
@@ -77,10 +78,10 @@ class Emu:
         rs = torch.rsqrt(((x - mean) ** 2).mean(-1, keepdim=True) + c.norm_eps)
         return _bf((x - mean) * rs * w.float() + b.float())
 
-    def run(self, tokens, pos0, k_pre, v_pre, mut=None, spikes=(), stale=0):
+    def run(self, tokens, pos0, k_pre, v_pre, mut=None, spikes=(), stale=0, kv_only=False):
         """tokens [M]; k_pre / v_pre bf16 [Hkv][pos0][D]; `stale` positions after the pass hold old keys (never visible);
         the V rows at `spikes` (any position of the cache) are scaled by 256 in one channel each before the attention.
-        -> dict of taps (fp32 holding bf16 values) and the caches"""
+        -> dict of taps (fp32 holding bf16 values) and the caches (kv_only: the caches alone, no attention and nothing after it)"""
         c, lw = self.cfg, self.w.layers[0]
         Hq, Hkv, D, ff = c.n_heads, c.n_kv_heads, c.head_dim, c.d_ff
         M = tokens.shape[0]
@@ -109,6 +110,8 @@ class Emu:
         for j, s in enumerate(spikes):
             if 0 <= s < v.shape[1]:
                 v[:, s, j % D] *= 256
+        if kv_only:
+            return dict(k=k, v=v)
         S = v.shape[1]
         G = Hq // Hkv
         attn = torch.empty(M, Hq, D)
@@ -120,6 +123,8 @@ class Emu:
                 vis = vis | ((kp == p_m + 1) & ((p_m + 1) % 32 == 0))
             if mut == "mask_future_split":
                 vis = vis | ((kp == p_m + 1) & ((p_m + 1) % 512 == 0))
+            if mut == "leak_next":        # the last query but one also sees the pass's last key: ONE key of its future
+                vis = vis | ((kp == p_m + 1) & (m == M - 2))
             if mut == "mask_diag_32":
                 vis = vis & ~((kp == p_m) & (p_m % 32 == 0))
             if mut == "mask_diag_split":
@@ -226,3 +231,30 @@ def test_mutation_is_caught(mut, cfg, pos0, spikes):
     stage_checks(emu, toks, emu.run(toks, pos0, k, v, **kw))       # the unmutated run passes at the same place
     with pytest.raises(AssertionError, match="outside the derived bound"):
         stage_checks(emu, toks, emu.run(toks, pos0, k, v, mut=mut, **kw))
+
+
+# ---- the future-key construction of tests/test_hip_prefill_rows_fp64_gpu.py ------------------------------------------------------
+def test_one_leaked_spike_key_exceeds_the_attention_bound_at_the_largest_position():
+    """A prompt chunk's K / V are all appended before its attention runs, so a query at p has up to 384 keys of its own future
+    in the cache. An ordinary future key moves it by ~1/p of the V scale: under the attention bound at p ~ 400. The GPU test
+    therefore makes every future key a spike key (prefill_cases.spike_weights: V rows ~256 x the others, from the direction
+    of one embedding row). Here, at the largest query position it uses (the last ordinary position of its 1024 prompt, one
+    before the first spike): the emulation with the causal mask stays inside every bound, and a leak of that ONE spike key into
+    that one query exceeds the attention bound."""
+    L, s = max(P.FUTURE, key=lambda f: f[1])
+    emu = Emu(TOY, weights=P.spike_weights(W.random_init(TOY, seed=7)))
+    M = 6
+    pos0 = s - (M - 1)                                                    # queries s-5 .. s-1 are ordinary, the last token is the spike
+    toks = torch.cat([_tokens(TOY, s, 21), torch.full((1,), P.SPIKE_TOKEN)])
+    assert int((toks[:s] == P.SPIKE_TOKEN).sum()) == 0
+    empty = torch.empty(TOY.n_kv_heads, 0, TOY.head_dim)
+    pre = emu.run(toks[:pos0], 0, empty, empty, kv_only=True)             # the keys below the queries: the model's own, of ordinary size
+    out = emu.run(toks[pos0:], pos0, pre["k"], pre["v"])
+    v_abs = out["v"].abs().mean((0, 2))
+    assert float(v_abs[s]) > 100 * float(v_abs[:s].max())                 # the construction: the spike row's V is two orders up
+    res = stage_checks(emu, toks[pos0:], out)
+    assert all(r <= 1.0 for r in res.values()), res
+    leaked = emu.run(toks[pos0:], pos0, pre["k"], pre["v"], mut="leak_next")
+    assert torch.equal(leaked["attn"][:M - 2], out["attn"][:M - 2])        # one query moved, by one key
+    with pytest.raises(AssertionError, match=r"attention: .* outside the derived bound; worst at \[4, "):
+        stage_checks(emu, toks[pos0:], leaked)
