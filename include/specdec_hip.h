@@ -472,6 +472,14 @@ int sd_model_prefill_rows(sd_model* m, int which, int row0, int n, void* out, vo
 int sd_gemm_plan(int T, int n_pairs, int K, int w8, int prologue, int epi, int flags, char* out, size_t cap);
 int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_pairs, int* epi, int* prologue);
 
+/* sd_gemv_variant names the csrc/gemv.hip instance that a launch of T <= 9 tokens runs for a packed matrix without bias,
+ * gathered rows or batch (the layer matrices of a forward; arguments as sd_gemm_plan): "generic", or
+ * "fixed<EPI,ksS,tpP,PRO,ttT,kbB>" for a fixed-geometry instance with S K-slices per tile, P pairs per tile, prologue PRO
+ * (none, rmsnorm), token bound T and B loads per batch. The launcher asks the same function; SPECDEC_GEMV_GENERIC=1 in the
+ * environment makes both answer "generic". Host-only, additive (SD_ABI_VERSION stays 1). Refused: NULL out, a cap that does
+ * not hold the name (64 bytes always do), T outside 1..9, an unknown prologue / epi, n_pairs < 1, K no positive multiple of 8. */
+int sd_gemv_variant(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap);
+
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *
  * sd_persist_plan answers, from a model's dimensions and facts alone (no weights, no device call; a GPU of 256 CUs is

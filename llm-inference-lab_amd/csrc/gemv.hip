@@ -138,9 +138,20 @@ __device__ __forceinline__ void stage_x(const GemvArgs& a, uint16_t* xs, int KP,
 //   holds its A fragments of two consecutive 32-k steps; they are widened to bf16 in registers
 //   (v_cvt_scalef32_pk_bf16_fp8, exact) and feed two bf16 MFMAs; the fp32 sum of row r is scaled by
 //   w_scale[r] in the epilogue. Half the HBM bytes per token, bf16 activations unchanged.
-template <int EPI, bool MASK, int TT, bool W8, int KB>
+//   FKS >= 0 = a FIXED-GEOMETRY instance (the table kGemvFixed below): log2(ksplit), the pairs per tile (FTP) and the prologue
+//   kind (FPRO) are compile-time, and the launch is known to be packed, single-round, without x_row, bias or batch (and not
+//   aliased below the 9-token bound). The run-time index arithmetic and the kernel-uniform branches on those fields fold away in front of the first
+//   weight load; sums, rounding points and the thread -> item map are those of the generic kernel (FKS = -1), which stays
+//   the fallback and the reference (SPECDEC_GEMV_GENERIC=1 forces it).
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE>
 __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs a) {
   constexpr int kBatch = KB;
+  constexpr bool FIX = FKS >= 0;
+  // a geometry field of the argument block, or its compile-time value in a fixed instance. Used IN PLACE of the field, where
+  // the generic kernel reads it, so that the generic instantiations compile to the instructions they had before
+#define SD_GEOM(field, fixed) (FIX ? (fixed) : (a.field))
+#define SD_ALIASED SD_GEOM(alias_part, TT == kGemvMaxT && a.alias_part)   // (9 rows of K = 8192 are the one fixed shape that aliases)
+  static_assert(!FIX || (!MASK && !W8 && EPI != EPI_ARGMAX && EPI != EPI_GELU && FTP >= 1 && FTP <= 8 && FKS <= 4), "fixed instances: bf16 Llama layer matrices");
   pin_gemv_args<EPI, W8>(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int K = a.K, T = a.T;
@@ -150,16 +161,16 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   // fills the CU's 160 KiB (T=5, K=14336) the partials alias the x rows (single-round
   // launches only; one extra barrier before they are written).
   const size_t xs_bytes = (static_cast<size_t>(T) * KP * 2 + 15) & ~static_cast<size_t>(15);
-  float* part = reinterpret_cast<float*>(a.alias_part ? smem : smem + xs_bytes);  // [16 waves][16][16]
-  float* red = reinterpret_cast<float*>(smem + xs_bytes + (a.alias_part ? 0 : sizeof(float) * kGemvWaves * 256));
+  float* part = reinterpret_cast<float*>(SD_ALIASED ? smem : smem + xs_bytes);  // [16 waves][16][16]
+  float* red = reinterpret_cast<float*>(smem + xs_bytes + (SD_ALIASED ? 0 : sizeof(float) * kGemvWaves * 256));
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform, kept in SGPRs
   const int g = lane >> 4, n = lane & 15;
-  const int ksplit = a.ksplit;                 // power of two, <= 16
-  const int tiles_per_round = kGemvWaves >> a.ks_shift;
+  const int ksplit = SD_GEOM(ksplit, 1 << FKS);   // power of two, <= 16
+  const int tiles_per_round = kGemvWaves >> SD_GEOM(ks_shift, FKS);
   const int kpart = wave & (ksplit - 1);
-  const int tslot = wave >> a.ks_shift;
+  const int tslot = wave >> SD_GEOM(ks_shift, FKS);
   const int kw = a.kw;                         // K span of one slice (multiple of 32)
   const int k_begin = kpart * kw;
   const int steps = W8 ? (kw >> 6) : (kw >> 5);  // loads per slice (an fp8 load covers 64 k)
@@ -177,10 +188,11 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   // contiguous pair range of this workgroup, cut into n_tiles tiles of tile_pairs pairs
   const int p_lo = static_cast<int>(blockIdx.x) * a.ppw;
   const int p_hi = min(p_lo + a.ppw, a.n_pairs);
-  const int tile_pairs = a.tile_pairs;
-  // (only the last workgroup can own less than ppw pairs: everyone else takes the host's tile count, no division)
-  const int n_tiles = (p_lo + a.ppw <= a.n_pairs) ? a.n_tiles_full : (p_hi - p_lo + tile_pairs - 1) / tile_pairs;
-  const int rounds = (n_tiles + tiles_per_round - 1) >> (4 - a.ks_shift);
+  const int tile_pairs = SD_GEOM(tile_pairs, FTP);
+  // (only the last workgroup can own less than ppw pairs: everyone else takes the host's tile count, no division;
+  //  a fixed instance is single-round: a full share is exactly tiles_per_round tiles)
+  const int n_tiles = (p_lo + a.ppw <= a.n_pairs) ? SD_GEOM(n_tiles_full, tiles_per_round) : (p_hi - p_lo + tile_pairs - 1) / tile_pairs;
+  const int rounds = FIX ? 1 : (n_tiles + tiles_per_round - 1) >> (4 - a.ks_shift);
 
   // lane's weight row inside a tile: rows 0..7 = first rows of the pairs, 8..15 = second
   // rows. Lanes without a pair alias the tile's first row (same address as lane 0: no
@@ -193,7 +205,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   unsigned lane_off = 0;
   auto tile_base = [&](int tile) -> const uint16_t* {
     const int p0 = p_lo + tile * tile_pairs;
-    if (a.packed) {
+    if (SD_GEOM(packed, true)) {
       int np = min(tile_pairs, p_hi - p0);
       if (np < 1) np = 1;
       int jp = n & 7, second = n >> 3;
@@ -259,18 +271,24 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   constexpr bool fast_stage = !MASK;  // the launcher sends K > 8192 to the MASK variant
   const bool has_chunk = tid < nvec;
   const int cidx = has_chunk ? tid : nvec - 1;  // clamp: every thread loads, owners store
+  // fixed instances: a wave none of whose threads owns a chunk (10 of 16 at K = 3072) issues no clamped duplicates of the
+  // x and norm-weight loads in front of its weight batch (wave-uniform branch; the owners' waits stay counted)
+  const bool wave_loads = FIX ? (wave << 6) < nvec : true;
   u32x4 xr[TT];
   u32x4 nw4 = {0u, 0u, 0u, 0u}, nb4 = {0u, 0u, 0u, 0u};
   bool have_old = false;
   uint32_t old_pre = 0;
   if constexpr (fast_stage) {
     const uint16_t* xin = static_cast<const uint16_t*>(a.x);
-    if (a.x_row) {   // kernel-uniform: gathered rows (Medusa heads read the accepted position's hidden row)
+    if (SD_GEOM(x_row, static_cast<const int32_t*>(nullptr))) {   // kernel-uniform: gathered rows (Medusa heads read the accepted position's hidden row)
       int rows[TT];
 #pragma unroll
       for (int t = 0; t < TT; ++t) rows[t] = a.x_row[(t < T) ? t : T - 1];
 #pragma unroll
       for (int t = 0; t < TT; ++t) xr[t] = *reinterpret_cast<const u32x4*>(xin + static_cast<size_t>(rows[t]) * a.x_stride + cidx * 8);
+    } else if (FIX && !wave_loads) {
+#pragma unroll
+      for (int t = 0; t < TT; ++t) xr[t] = u32x4{0u, 0u, 0u, 0u};
     } else {
 #pragma unroll
       for (int t = 0; t < TT; ++t) {
@@ -278,9 +296,11 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
         xr[t] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(xin) + (static_cast<unsigned>(tt) * static_cast<unsigned>(a.x_stride) + static_cast<unsigned>(cidx) * 8u) * 2u);   // (32-bit offsets: <= 64 rows of <= 16384 elements)
       }
     }
-    if (a.prologue != PRO_NONE) {  // kernel-uniform
-      nw4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_w) + cidx * 8);
-      if (a.prologue == PRO_LAYERNORM) nb4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_b) + cidx * 8);
+    if (SD_GEOM(prologue, FPRO) != PRO_NONE) {  // kernel-uniform
+      if (!FIX || wave_loads) {
+        nw4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_w) + cidx * 8);
+        if (SD_GEOM(prologue, FPRO) == PRO_LAYERNORM) nb4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_b) + cidx * 8);
+      }
     }
     // residual epilogue: the old x value of this thread's (pair, token) item of round 0
     if constexpr (EPI == EPI_RESID) {
@@ -304,7 +324,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
 
   if constexpr (!fast_stage) {
     stage_x(a, xs, KP, red);
-  } else if (a.prologue == PRO_NONE) {
+  } else if (SD_GEOM(prologue, FPRO) == PRO_NONE) {
 #pragma unroll
     for (int t = 0; t < TT; ++t)
       if (t < T && has_chunk) *reinterpret_cast<u32x4*>(xs + static_cast<size_t>(t) * KP + tid * 8) = xr[t];
@@ -319,7 +339,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
       if (t < T) {
         float s1 = 0.f, s2 = 0.f;
         if (wave_has_chunk) {
-          const bool need_mean = a.prologue == PRO_LAYERNORM;   // kernel-uniform: RMSNorm only needs the squares
+          const bool need_mean = SD_GEOM(prologue, FPRO) == PRO_LAYERNORM;   // kernel-uniform: RMSNorm only needs the squares
           f32x2_t a1 = {0.f, 0.f}, a2 = {0.f, 0.f};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -348,7 +368,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
         const float2 pr = *reinterpret_cast<const float2*>(red + (t * kGemvWaves + (lane & 15)) * 2);
         const float sum = row16_reduce_sum(pr.x), sq = row16_reduce_sum(pr.y);
         u32x4 o;
-        if (a.prologue == PRO_RMSNORM) {
+        if (SD_GEOM(prologue, FPRO) == PRO_RMSNORM) {
           // HF LlamaRMSNorm: weight * (x * rsqrt(var + eps)).to(bf16)
           const float rs = rsqrtf(sq * invK + a.norm_eps);
 #pragma unroll
@@ -419,7 +439,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
     }
     if (r == 0) stamp(3);
     // publish this wave's partial 16x16 (row = 4g+reg, col = token n)
-    if (a.alias_part) __syncthreads();  // every wave is done reading x
+    if (SD_ALIASED) __syncthreads();  // every wave is done reading x
     float* slot = part + wave * 256;
 #pragma unroll
     for (int q = 0; q < 4; ++q) slot[(4 * g + q) * 16 + n] = acc[q];
@@ -432,14 +452,15 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
       const int p = p_lo + etile * tile_pairs + jp;
       if (etile < n_tiles && jp < tile_pairs && p < p_hi && t < T) {
         float y0, y1;
-        sum_slices(part + (ts * ksplit) * 256 + jp * 16 + t, 256, ksplit, y0, y1);   // (gemv_device.h)
+        if constexpr (FIX) sum_slices_fixed<(1 << (FIX ? FKS : 0))>(part + (ts * ksplit) * 256 + jp * 16 + t, 256, y0, y1);
+        else sum_slices(part + (ts * ksplit) * 256 + jp * 16 + t, 256, ksplit, y0, y1);   // (gemv_device.h)
         int r0, r1;
         pair_rows<EPI>(a, p, r0, r1);
         if constexpr (W8) {
           y0 *= wsc[r0];
           y1 *= (r1 < a.N) ? wsc[r1] : 0.f;
         }
-        epilogue<EPI>(a, p, r0, r1, t, y0, y1, best_v, best_i, have_old && r == 0 && it == tid, old_pre);
+        epilogue<EPI, false, FIX>(a, p, r0, r1, t, y0, y1, best_v, best_i, have_old && r == 0 && it == tid, old_pre);
       }
     }
     if (r == 0) stamp(5);
@@ -468,6 +489,9 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   }
 }
 
+#undef SD_GEOM
+#undef SD_ALIASED
+
 // ------------------------------------------------------------------------------
 // host-side launch
 // ------------------------------------------------------------------------------
@@ -492,12 +516,12 @@ int gemv_grid(const GemvArgs& a, int* ppw_out) {
   return q.grid;
 }
 
-template <int EPI, bool MASK, int TT, bool W8, int KB>
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE>
 static int launch_one(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
   // dynamic LDS above 64 KiB has to be opted into once per kernel
   static unsigned long long attr_set = 0;
-  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, MASK, TT, W8, KB>), 160 * 1024, attr_set)) return rc;  // whole LDS of the CU
-  hipLaunchKernelGGL((gemv_mfma_kernel<EPI, MASK, TT, W8, KB>), dim3(grid, a.batch_bytes ? a.n_batch : 1), dim3(kGemvThreads), smem, st, a);
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO>), 160 * 1024, attr_set)) return rc;  // whole LDS of the CU
+  hipLaunchKernelGGL((gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO>), dim3(grid, a.batch_bytes ? a.n_batch : 1), dim3(kGemvThreads), smem, st, a);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -512,13 +536,83 @@ static int launch_epi_w(const GemvArgs& a, bool mask, int grid, size_t smem, hip
   return launch_one<EPI, false, kGemvMaxT, W8, KB>(a, grid, smem, st);
 }
 
+// the deep batch: (3+ token launches, i.e. the verify forward: 16 — threshold 24 / 16 / 12 / 6 -> 4.62 / 4.60 / 4.62 / 4.63 ms per step)
+static bool gemv_deep(int T, int kw, bool w8) {
+  const int nsteps = kw >> (w8 ? 6 : 5);   // loads per wave over the whole K slice
+  return nsteps >= (T >= 3 ? kDeepStepsVerify : kDeepSteps);
+}
+static int gemv_tt(int T) { return T <= 1 ? 1 : T <= 2 ? 2 : T <= 3 ? 3 : T <= 5 ? 5 : kGemvMaxT; }
+
 template <int EPI>
 static int launch_epi(const GemvArgs& a, bool mask, int grid, size_t smem, hipStream_t st) {
-  // (3+ token launches, i.e. the verify forward: 16 — threshold 24 / 16 / 12 / 6 -> 4.62 / 4.60 / 4.62 / 4.63 ms per step)
-  const int nsteps = a.kw >> (a.w8 ? 6 : 5);   // loads per wave over the whole K slice
-  const bool deep = nsteps >= (a.T >= 3 ? kDeepStepsVerify : kDeepSteps);
+  const bool deep = gemv_deep(a.T, a.kw, a.w8);
   if (a.w8) return deep ? launch_epi_w<EPI, true, kBatchDeep>(a, mask, grid, smem, st) : launch_epi_w<EPI, true, kBatchShallow>(a, mask, grid, smem, st);
   return deep ? launch_epi_w<EPI, false, kBatchDeep>(a, mask, grid, smem, st) : launch_epi_w<EPI, false, kBatchShallow>(a, mask, grid, smem, st);
+}
+
+// ------------------------------------------------------------------------------
+// fixed-geometry instances: the (epilogue, K slices, pairs per tile, prologue) classes of the bf16 Llama layer matrices at
+// 1B / 3B / 8B dimensions, each at the five token bounds and both batch depths. Everything else — the lm_head (multi-round),
+// fp8, MASK shapes (8B down: K = 14336), GPT-2, gathered rows, biases, batched heads — runs the generic kernel.
+// ------------------------------------------------------------------------------
+#define SD_GEMV_FIXED_TABLE(X)                                                          \
+  X(EPI_QKV_ROPE, 4, 6, PRO_RMSNORM) /* 1B qkv: 1536 pairs */                           \
+  X(EPI_QKV_ROPE, 3, 5, PRO_RMSNORM) /* 3B qkv: 2560 */                                 \
+  X(EPI_QKV_ROPE, 3, 6, PRO_RMSNORM) /* 8B qkv: 3072 */                                 \
+  X(EPI_RESID, 4, 4, PRO_NONE)       /* 1B out, down: 1024 */                           \
+  X(EPI_RESID, 4, 6, PRO_NONE)       /* 3B out, down: 1536 */                           \
+  X(EPI_RESID, 4, 8, PRO_NONE)       /* 8B out: 2048 */                                 \
+  X(EPI_SWIGLU, 2, 8, PRO_RMSNORM)   /* 1B, 3B gate / up: 8192 */                       \
+  X(EPI_SWIGLU, 1, 7, PRO_RMSNORM)   /* 8B gate / up: 14336 */
+
+struct GemvFixed {
+  int epi, ks_shift, tile_pairs, prologue;
+};
+#define X(E, KS, TP, PRO) {E, KS, TP, PRO},
+static const GemvFixed kGemvFixed[] = {SD_GEMV_FIXED_TABLE(X)};
+#undef X
+
+// Index into kGemvFixed of the instance a launch takes, -1 for the generic kernel. `plain`: packed weights, no x_row, no
+// bias, no batch. The one decision behind launch_gemv and sd_gemv_variant; SPECDEC_GEMV_GENERIC is read at every call.
+static int gemv_fixed_index(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain) {
+  if (getenv(debug_env::kGemvGeneric) || !plain || w8 || T < 1 || T > kGemvMaxT || n_pairs < 1 || K < 8 || K % 8) return -1;
+  const GemvGeom q = gemv_geometry(n_pairs, K);
+  if (q.kw * q.ksplit != K || K / 8 > kGemvThreads) return -1;                       // MASK shapes
+  if (q.n_tiles * q.ksplit != kGemvWaves || (q.ppw + q.tile_pairs - 1) / q.tile_pairs != q.n_tiles) return -1;   // one full round
+  if (gemv_smem(T, K, true) > kLdsLimit) return -1;
+  if (T < kGemvMaxT && gemv_smem(T, K, false) > kLdsLimit) return -1;                // only the 9-token instances can alias
+  for (size_t i = 0; i < sizeof(kGemvFixed) / sizeof(kGemvFixed[0]); ++i) {
+    const GemvFixed& f = kGemvFixed[i];
+    if (f.epi == epi && f.prologue == prologue && (1 << f.ks_shift) == q.ksplit && f.tile_pairs == q.tile_pairs) return static_cast<int>(i);
+  }
+  return -1;
+}
+
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap) {
+  static const char* const epis[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
+  static const char* const pros[] = {"none", "rmsnorm", "layernorm"};
+  const int i = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, true);
+  if (i < 0) return snprintf(out, cap, "generic");
+  const GemvFixed& f = kGemvFixed[i];
+  const int kw = gemv_geometry(n_pairs, K).kw;
+  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d>", epis[f.epi], 1 << f.ks_shift, f.tile_pairs, pros[f.prologue], gemv_tt(T),
+                  gemv_deep(T, kw, false) ? kBatchDeep : kBatchShallow);
+}
+
+template <int EPI, int KS, int TP, int PRO, int TT>
+static int launch_fixed_tt(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
+  return gemv_deep(a.T, a.kw, false) ? launch_one<EPI, false, TT, false, kBatchDeep, KS, TP, PRO>(a, grid, smem, st)
+                                     : launch_one<EPI, false, TT, false, kBatchShallow, KS, TP, PRO>(a, grid, smem, st);
+}
+template <int EPI, int KS, int TP, int PRO>
+static int launch_fixed(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
+  switch (gemv_tt(a.T)) {
+    case 1: return launch_fixed_tt<EPI, KS, TP, PRO, 1>(a, grid, smem, st);
+    case 2: return launch_fixed_tt<EPI, KS, TP, PRO, 2>(a, grid, smem, st);
+    case 3: return launch_fixed_tt<EPI, KS, TP, PRO, 3>(a, grid, smem, st);
+    case 5: return launch_fixed_tt<EPI, KS, TP, PRO, 5>(a, grid, smem, st);
+    default: return launch_fixed_tt<EPI, KS, TP, PRO, kGemvMaxT>(a, grid, smem, st);
+  }
 }
 
 int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
@@ -558,6 +652,14 @@ int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
   // of 6..9 tokens — a pass may mix both kernels, they share layout, work split and epilogues
   if (smem > kLdsLimit && !a.x_row && !a.batch_bytes && gemm_skinny_covers(a.T, a.n_pairs, a.K, a.w8 != 0)) return launch_gemm_skinny(a_in, epi, st);
   SD_REQUIRE(smem <= kLdsLimit, "gemv: T=%d x K=%d does not fit LDS", a.T, a.K);
+  const int fixed = gemv_fixed_index(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes);
+  if (fixed >= 0) {
+    int i = 0;
+#define X(E, KS, TP, PRO) \
+    if (fixed == i++) return launch_fixed<E, KS, TP, PRO>(a, grid, smem, st);
+    SD_GEMV_FIXED_TABLE(X)
+#undef X
+  }
   switch (epi) {
     case EPI_QKV_ROPE: return launch_epi<EPI_QKV_ROPE>(a, mask, grid, smem, st);
     case EPI_RESID: return launch_epi<EPI_RESID>(a, mask, grid, smem, st);

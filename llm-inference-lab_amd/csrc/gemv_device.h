@@ -66,16 +66,20 @@ __device__ __forceinline__ void pair_rows(const GemvArgs& a, int p, int& r0, int
 // ------------------------------------------------------------------------------
 //   COH (EPI_RESID only): the new residual row is stored with an agent-scope relaxed atomic store (write-through to
 //   memory), for a consumer on another XCD inside the same launch.
-template <int EPI, bool COH = false>
+//   FIXED: called by a fixed-geometry instance of gemv.hip, whose outputs must equal the generic kernel's bit for bit: a.bias is
+//   known to be null, and the RoPE rotation has its roundings spelled out (see there).
+template <int EPI, bool COH = false, bool FIXED = false>
 __device__ __forceinline__ void epilogue(const GemvArgs& a, int p, int r0, int r1, int t, float y0,
                                          float y1, float& best_v, int& best_i, bool have_old = false,
                                          uint32_t old_pre = 0, float* st_sq = nullptr, float* st_sum = nullptr) {
   const int b = static_cast<int>((static_cast<unsigned>(t) * a.m_magic) >> 16), m = t - b * a.M;   // t / M (gemv_derive)
   if constexpr (EPI == EPI_QKV_ROPE) {
-    if (a.bias) {
-      const uint16_t* bs = static_cast<const uint16_t*>(a.bias);
-      y0 += bf16_bits_to_float(bs[r0]);
-      y1 += bf16_bits_to_float(bs[r1]);
+    if constexpr (!FIXED) {
+      if (a.bias) {
+        const uint16_t* bs = static_cast<const uint16_t*>(a.bias);
+        y0 += bf16_bits_to_float(bs[r0]);
+        y1 += bf16_bits_to_float(bs[r1]);
+      }
     }
     const int D = a.head_dim, half = D >> 1;
     const int h = (a.half_shift >= 0) ? (p >> a.half_shift) : p / half, i = p - h * half;
@@ -84,8 +88,20 @@ __device__ __forceinline__ void epilogue(const GemvArgs& a, int p, int r0, int r
     if (a.rope_cos && h < a.n_q_heads + a.n_kv_heads && pos >= 0 && pos < a.max_pos) {
       const float c = a.rope_cos[static_cast<size_t>(pos) * half + i];
       const float s = a.rope_sin[static_cast<size_t>(pos) * half + i];
-      o0 = y0 * c - y1 * s;
-      o1 = y1 * c + y0 * s;
+      if constexpr (FIXED) {
+        // hipcc contracts the two lines of the other branch, in every generic gemv instantiation, into a rounded product with s
+        // and a fused product with c; inlined behind a compile-time slice count it left BOTH products of the second line
+        // rounded, and q differed from the generic kernel's in the last bit. Spelled out, the roundings are the generic ones.
+        // (This copies what the compiler does with the other branch today: after a compiler change, run
+        // tests/test_hip_gemv_fixed_gpu.py, which fails if the generic side contracts differently, and follow it here.)
+#pragma clang fp contract(off)
+        const float s0 = y1 * s, s1 = y0 * s;
+        o0 = __builtin_fmaf(y0, c, -s0);
+        o1 = __builtin_fmaf(y1, c, s1);
+      } else {
+        o0 = y0 * c - y1 * s;
+        o1 = y1 * c + y0 * s;
+      }
     }
     const uint16_t u0 = float_to_bf16_bits(o0), u1 = float_to_bf16_bits(o1);
     if (h < a.n_q_heads) {
@@ -117,10 +133,12 @@ __device__ __forceinline__ void epilogue(const GemvArgs& a, int p, int r0, int r
       }
     }
   } else if constexpr (EPI == EPI_RESID) {
-    if (a.bias) {
-      const uint16_t* bs = static_cast<const uint16_t*>(a.bias);
-      y0 += bf16_bits_to_float(bs[r0]);
-      y1 += bf16_bits_to_float(bs[r1]);
+    if constexpr (!FIXED) {
+      if (a.bias) {
+        const uint16_t* bs = static_cast<const uint16_t*>(a.bias);
+        y0 += bf16_bits_to_float(bs[r0]);
+        y1 += bf16_bits_to_float(bs[r1]);
+      }
     }
     uint32_t* px = reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + static_cast<size_t>(t) * a.out_stride + r0);
     const uint32_t old = have_old ? old_pre : *px;  // prefetched at kernel entry when possible

@@ -138,6 +138,9 @@ int gemv_grid(const GemvArgs& a, int* ppw_out);
 int gemv_max_tokens(int K);                                          // tokens gemv.hip can stage for rows of K elements (<= 9)
 int launch_gemv(const GemvArgs& a, int epi, hipStream_t st);          // T <= 9: gemv.hip, else gemm_skinny.hip
 int launch_gemm_skinny(const GemvArgs& a, int epi, hipStream_t st);   // T <= 64
+// name of the gemv.hip instance a plain launch (packed, no bias / x_row / batch) of T <= 9 tokens takes: "generic" or
+// "fixed<...>"; decided by the function launch_gemv asks. snprintf's return value.
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap);
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8 = false);                  // shape handled by gemm_skinny.hip
 // gemm_pipe.hip: the statically scheduled chunk pipeline for <= 64 tokens (tried first by launch_gemm_skinny, which has
 // set the work split fields of `a`)

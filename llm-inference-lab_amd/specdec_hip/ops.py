@@ -490,6 +490,15 @@ def gemm_plan(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PR
     return buf.value.decode()
 
 
+def gemv_variant(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID) -> str:
+    """Name of the csrc/gemv.hip instance a layer-matrix launch of T <= 9 tokens runs (sd_gemv_variant): "generic" or
+    "fixed<qkv,ks8,tp5,rmsnorm,tt5,kb6>". Follows SPECDEC_GEMV_GENERIC in the environment, as a launch does. Host-only."""
+    buf = ctypes.create_string_buffer(64)
+    _abi.check(_abi.load().sd_gemv_variant(int(T), int(n_pairs), int(K), 1 if w8 else 0, int(prologue), int(epi), buf, len(buf)),
+               "sd_gemv_variant")
+    return buf.value.decode()
+
+
 class PersistPlan(NamedTuple):
     eligible: bool       # the model passes every static rule of the persistent forward
     max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)
