@@ -461,7 +461,8 @@ int sd_model_prefill_rows(sd_model* m, int which, int row0, int n, void* out, vo
  *   "pipe<EPI,tgN,DT,scS>"     the chunk pipeline: N token groups of 16, S steps per wave per chunk
  *   "chunked<EPI,tgN,DT,nbS>"  the chunked fallback: S weight steps per batch
  *   "slice<tgN>", "direct<tgN>" the two plain-residual bodies (bf16, no norm)
- *   "gemv"                      T <= 9: csrc/gemv.hip (its variants are not named)
+ *   "gemv"                      T <= 9: csrc/gemv.hip (its variants are not named). "gemv" names the launcher that is asked;
+ *                               sd_gemv_instance names the kernel that runs, which for rows too long to stage is a body above.
  *   "none"                      no kernel covers the shape (a launch would be refused)
  * with EPI in qkv, resid, swiglu, gelu, argmax and DT in bf16, fp8. flags: bit 0 = plan as if SPECDEC_NO_DIRECT were set,
  * bit 1 = as if SPECDEC_NO_PIPE were; 0 follows the process's own environment, as a launch does. Refused: NULL out, a cap
@@ -477,8 +478,21 @@ int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_p
  * "fixed<EPI,ksS,tpP,PRO,ttT,kbB>" for a fixed-geometry instance with S K-slices per tile, P pairs per tile, prologue PRO
  * (none, rmsnorm), token bound T and B loads per batch. The launcher asks the same function; SPECDEC_GEMV_GENERIC=1 in the
  * environment makes both answer "generic". Host-only, additive (SD_ABI_VERSION stays 1). Refused: NULL out, a cap that does
- * not hold the name (64 bytes always do), T outside 1..9, an unknown prologue / epi, n_pairs < 1, K no positive multiple of 8. */
+ * not hold the name (64 bytes always do), T outside 1..9, an unknown prologue / epi, n_pairs < 1, K no positive multiple of 8.
+ * "generic" names the launcher's fallback as asked; sd_gemv_instance names the kernel that runs.
+ *
+ * sd_gemv_instance names the kernel that launch really runs, from the one host-side choice launch_gemv consumes:
+ *   "fixed<...>"                               exactly sd_gemv_variant's answer
+ *   "generic<EPI,whole|mask,ttN,DT,kbB>"       the template key of the generic kernel: epilogue, whole 32-k slices or the
+ *                                              masked variant (always tt9), token bound N in 1, 2, 3, 5, 9, bf16 or fp8
+ *                                              storage, B loads per batch
+ *   "skinny:" + a name of sd_gemm_plan         T rows of K do not fit the LDS and csrc/gemm_skinny.hip takes the launch
+ *                                              (K = 14336 at 6..9 tokens): the body that runs, at T < 10
+ * Follows SPECDEC_GEMV_GENERIC at every call. Refused as sd_gemv_variant refuses, and where launch_gemv would refuse the
+ * launch (fp8 storage whose K slices are not whole 64-k steps; rows that fit neither kernel). Host-only, additive
+ * (SD_ABI_VERSION stays 1). */
 int sd_gemv_variant(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap);
+int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap);
 
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *

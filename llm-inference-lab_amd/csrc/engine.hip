@@ -1207,6 +1207,21 @@ extern "C" int sd_gemv_variant(int T, int n_pairs, int K, int w8, int prologue, 
   return 0;
 }
 
+extern "C" int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap) {
+  clear_error();
+  SD_REQUIRE(out, "gemv_instance: NULL out");
+  SD_REQUIRE(T >= 1 && T <= kGemvMaxT, "gemv_instance: T=%d out of range 1..%d", T, kGemvMaxT);
+  SD_REQUIRE(prologue >= PRO_NONE && prologue <= PRO_LAYERNORM && epi >= EPI_QKV_ROPE && epi <= EPI_ARGMAX,
+             "gemv_instance: prologue=%d epi=%d out of range", prologue, epi);
+  SD_REQUIRE(n_pairs >= 1 && K >= 8 && K % 8 == 0, "gemv_instance: n_pairs=%d K=%d (K must be a multiple of 8)", n_pairs, K);
+  char name[64];
+  int n = 0;
+  if (int rc = gemv_instance_name(T, n_pairs, K, w8 != 0, prologue, epi, name, sizeof(name), &n)) return rc;   // a launch launch_gemv refuses, in its words
+  SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(name) && static_cast<size_t>(n) < cap, "gemv_instance: cap=%zu is too short for the name (%d bytes with its NUL)", cap, n + 1);
+  memcpy(out, name, static_cast<size_t>(n) + 1);
+  return 0;
+}
+
 extern "C" int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
                                int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
                                char* name, size_t name_cap, char* reason, size_t reason_cap) {

@@ -526,29 +526,12 @@ static int launch_one(const GemvArgs& a, int grid, size_t smem, hipStream_t st) 
   return 0;
 }
 
-template <int EPI, bool W8, int KB>
-static int launch_epi_w(const GemvArgs& a, bool mask, int grid, size_t smem, hipStream_t st) {
-  if (mask) return launch_one<EPI, true, kGemvMaxT, W8, KB>(a, grid, smem, st);  // generic shapes: one variant
-  if (a.T <= 1) return launch_one<EPI, false, 1, W8, KB>(a, grid, smem, st);
-  if (a.T <= 2) return launch_one<EPI, false, 2, W8, KB>(a, grid, smem, st);
-  if (a.T <= 3) return launch_one<EPI, false, 3, W8, KB>(a, grid, smem, st);
-  if (a.T <= 5) return launch_one<EPI, false, 5, W8, KB>(a, grid, smem, st);
-  return launch_one<EPI, false, kGemvMaxT, W8, KB>(a, grid, smem, st);
-}
-
-// the deep batch: (3+ token launches, i.e. the verify forward: 16 — threshold 24 / 16 / 12 / 6 -> 4.62 / 4.60 / 4.62 / 4.63 ms per step)
+// The deep batch: (3+ token launches, i.e. the verify forward: 16 — threshold 24 / 16 / 12 / 6 -> 4.62 / 4.60 / 4.62 / 4.63 ms per step)
 static bool gemv_deep(int T, int kw, bool w8) {
   const int nsteps = kw >> (w8 ? 6 : 5);   // loads per wave over the whole K slice
   return nsteps >= (T >= 3 ? kDeepStepsVerify : kDeepSteps);
 }
 static int gemv_tt(int T) { return T <= 1 ? 1 : T <= 2 ? 2 : T <= 3 ? 3 : T <= 5 ? 5 : kGemvMaxT; }
-
-template <int EPI>
-static int launch_epi(const GemvArgs& a, bool mask, int grid, size_t smem, hipStream_t st) {
-  const bool deep = gemv_deep(a.T, a.kw, a.w8);
-  if (a.w8) return deep ? launch_epi_w<EPI, true, kBatchDeep>(a, mask, grid, smem, st) : launch_epi_w<EPI, true, kBatchShallow>(a, mask, grid, smem, st);
-  return deep ? launch_epi_w<EPI, false, kBatchDeep>(a, mask, grid, smem, st) : launch_epi_w<EPI, false, kBatchShallow>(a, mask, grid, smem, st);
-}
 
 // ------------------------------------------------------------------------------
 // fixed-geometry instances: the (epilogue, K slices, pairs per tile, prologue) classes of the bf16 Llama layer matrices at
@@ -588,30 +571,115 @@ static int gemv_fixed_index(int T, int n_pairs, int K, bool w8, int prologue, in
   return -1;
 }
 
+// Which kernel a launch of 1..9 tokens takes — ONE function, as gemm_plan is for 10..128 tokens. launch_gemv and its switches
+// below consume the result and sd_gemv_instance prints it (a second copy of these conditions would let a test name a kernel
+// that did not run). `plain` as for gemv_fixed_index; `hand_over`: the launch has no x_row and no batch, so the chunked
+// multi-token kernels can take it. T, n_pairs and K have passed launch_gemv's range checks.
+enum GemvRoute { GEMV_GENERIC = 0, GEMV_FIXED, GEMV_SKINNY, GEMV_NO_FP8_STEPS, GEMV_NO_LDS };
+struct GemvChoice {
+  int route;       // GemvRoute; the last two: launch_gemv refuses the launch
+  GemvGeom q;      // the work split
+  bool mask;       // MASK variant: slices that are not whole 32-k steps, or rows longer than the one-chunk-per-thread register staging covers
+  int tt;          // compile-time token bound: 1, 2, 3, 5 or 9 (a MASK instantiation: always 9)
+  bool deep;       // kBatchDeep loads per batch, else kBatchShallow
+  bool alias;      // the partials alias the x rows in LDS
+  int fixed;       // GEMV_FIXED: index into kGemvFixed
+  size_t smem;     // dynamic LDS of the launch
+};
+static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain, bool hand_over) {
+  GemvChoice c{};
+  c.q = gemv_geometry(n_pairs, K);
+  c.fixed = -1;
+  c.mask = (c.q.kw * c.q.ksplit != K) || (K / 8 > kGemvThreads);
+  c.tt = c.mask ? kGemvMaxT : gemv_tt(T);
+  c.deep = gemv_deep(T, c.q.kw, w8);
+  if (w8 && (K % 64 != 0 || c.q.kw % 64 != 0 || c.q.kw * c.q.ksplit != K)) {
+    c.route = GEMV_NO_FP8_STEPS;
+    return c;
+  }
+  c.smem = gemv_smem(T, K, false);
+  if (c.smem > kLdsLimit && c.q.n_tiles <= kGemvWaves / c.q.ksplit) {  // single round: partials may alias x
+    c.alias = true;
+    c.smem = gemv_smem(T, K, true);
+  }
+  // rows too long to stage T of them whole (d_ff = 14336 takes 5): the chunked multi-token kernel covers the rest
+  // of 6..9 tokens — a pass may mix both kernels, they share layout, work split and epilogues
+  if (c.smem > kLdsLimit) {
+    c.route = (hand_over && gemm_skinny_covers(T, n_pairs, K, w8)) ? GEMV_SKINNY : GEMV_NO_LDS;
+    return c;
+  }
+  c.fixed = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, plain);
+  c.route = c.fixed >= 0 ? GEMV_FIXED : GEMV_GENERIC;
+  return c;
+}
+// the refusals of a choice, in launch_gemv's words
+static int gemv_choice_refused(const GemvChoice& c, int T, int K) {
+  SD_REQUIRE(c.route != GEMV_NO_FP8_STEPS, "gemv: fp8 weights need K (%d) and the K slice (%d) in whole 64-k steps", K, c.q.kw);
+  SD_REQUIRE(c.route != GEMV_NO_LDS, "gemv: T=%d x K=%d does not fit LDS", T, K);
+  return 0;
+}
+
+template <int EPI, bool W8, int KB>
+static int launch_epi_w(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  if (c.mask) return launch_one<EPI, true, kGemvMaxT, W8, KB>(a, grid, c.smem, st);  // generic shapes: one variant
+  switch (c.tt) {
+    case 1: return launch_one<EPI, false, 1, W8, KB>(a, grid, c.smem, st);
+    case 2: return launch_one<EPI, false, 2, W8, KB>(a, grid, c.smem, st);
+    case 3: return launch_one<EPI, false, 3, W8, KB>(a, grid, c.smem, st);
+    case 5: return launch_one<EPI, false, 5, W8, KB>(a, grid, c.smem, st);
+    default: return launch_one<EPI, false, kGemvMaxT, W8, KB>(a, grid, c.smem, st);
+  }
+}
+
+template <int EPI>
+static int launch_epi(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  if (a.w8) return c.deep ? launch_epi_w<EPI, true, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, true, kBatchShallow>(a, c, grid, st);
+  return c.deep ? launch_epi_w<EPI, false, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, false, kBatchShallow>(a, c, grid, st);
+}
+
+static const char* const kEpiNames[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
+static const char* const kProNames[] = {"none", "rmsnorm", "layernorm"};
+
+static int gemv_fixed_name(int i, int tt, bool deep, char* out, size_t cap) {
+  const GemvFixed& f = kGemvFixed[i];
+  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d>", kEpiNames[f.epi], 1 << f.ks_shift, f.tile_pairs, kProNames[f.prologue], tt,
+                  deep ? kBatchDeep : kBatchShallow);
+}
+
 int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap) {
-  static const char* const epis[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
-  static const char* const pros[] = {"none", "rmsnorm", "layernorm"};
   const int i = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, true);
   if (i < 0) return snprintf(out, cap, "generic");
-  const GemvFixed& f = kGemvFixed[i];
-  const int kw = gemv_geometry(n_pairs, K).kw;
-  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d>", epis[f.epi], 1 << f.ks_shift, f.tile_pairs, pros[f.prologue], gemv_tt(T),
-                  gemv_deep(T, kw, false) ? kBatchDeep : kBatchShallow);
+  return gemv_fixed_name(i, gemv_tt(T), gemv_deep(T, gemv_geometry(n_pairs, K).kw, false), out, cap);
+}
+
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len) {
+  const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true);
+  if (int rc = gemv_choice_refused(c, T, K)) return rc;
+  if (c.route == GEMV_FIXED) {
+    *len = gemv_fixed_name(c.fixed, c.tt, c.deep, out, cap);
+  } else if (c.route == GEMV_SKINNY) {
+    const int n = snprintf(out, cap, "skinny:");
+    *len = n + gemm_plan_name(gemm_plan(T, n_pairs, K, w8, prologue, epi, 0), epi, w8, out + n, static_cast<size_t>(n) < cap ? cap - n : 0);
+  } else {
+    *len = snprintf(out, cap, "generic<%s,%s,tt%d,%s,kb%d>", kEpiNames[epi], c.mask ? "mask" : "whole", c.tt, w8 ? "fp8" : "bf16",
+                    c.deep ? kBatchDeep : kBatchShallow);
+  }
+  return 0;
 }
 
 template <int EPI, int KS, int TP, int PRO, int TT>
-static int launch_fixed_tt(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
-  return gemv_deep(a.T, a.kw, false) ? launch_one<EPI, false, TT, false, kBatchDeep, KS, TP, PRO>(a, grid, smem, st)
-                                     : launch_one<EPI, false, TT, false, kBatchShallow, KS, TP, PRO>(a, grid, smem, st);
+static int launch_fixed_tt(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  return c.deep ? launch_one<EPI, false, TT, false, kBatchDeep, KS, TP, PRO>(a, grid, c.smem, st)
+                : launch_one<EPI, false, TT, false, kBatchShallow, KS, TP, PRO>(a, grid, c.smem, st);
 }
 template <int EPI, int KS, int TP, int PRO>
-static int launch_fixed(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
-  switch (gemv_tt(a.T)) {
-    case 1: return launch_fixed_tt<EPI, KS, TP, PRO, 1>(a, grid, smem, st);
-    case 2: return launch_fixed_tt<EPI, KS, TP, PRO, 2>(a, grid, smem, st);
-    case 3: return launch_fixed_tt<EPI, KS, TP, PRO, 3>(a, grid, smem, st);
-    case 5: return launch_fixed_tt<EPI, KS, TP, PRO, 5>(a, grid, smem, st);
-    default: return launch_fixed_tt<EPI, KS, TP, PRO, kGemvMaxT>(a, grid, smem, st);
+static int launch_fixed(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  switch (c.tt) {
+    case 1: return launch_fixed_tt<EPI, KS, TP, PRO, 1>(a, c, grid, st);
+    case 2: return launch_fixed_tt<EPI, KS, TP, PRO, 2>(a, c, grid, st);
+    case 3: return launch_fixed_tt<EPI, KS, TP, PRO, 3>(a, c, grid, st);
+    case 5: return launch_fixed_tt<EPI, KS, TP, PRO, 5>(a, c, grid, st);
+    default: return launch_fixed_tt<EPI, KS, TP, PRO, kGemvMaxT>(a, c, grid, st);
   }
 }
 
@@ -625,47 +693,33 @@ int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
   SD_REQUIRE(a.K % 8 == 0 && a.x_stride % 8 == 0, "gemv: K=%d / x_stride=%d must be multiples of 8", a.K, a.x_stride);
   SD_REQUIRE(a.n_pairs > 0, "gemv: no rows");
   SD_REQUIRE(!a.batch_bytes || (epi == EPI_ARGMAX && a.n_batch >= 1 && a.n_batch <= 64 && !a.out), "gemv: batched matrices are an ARGMAX-epilogue feature (no logits store)");
+  SD_REQUIRE(!a.w8 || (a.packed && a.w_scale), "gemv: fp8 weights need the packed layout and row scales");
   // one workgroup (16 waves) per CU with an equal, contiguous share of the row pairs, cut into
   // a power-of-two count of <= 8-pair tiles; the 16 waves take (tile, K-slice) units
-  const GemvGeom q = gemv_geometry(a.n_pairs, a.K);
-  const int grid = q.grid, n_tiles = q.n_tiles, ksplit = q.ksplit;
-  a.ppw = q.ppw;
-  a.tile_pairs = q.tile_pairs;
-  a.ksplit = q.ksplit;
-  a.kw = q.kw;
-  a.n_tiles_full = (q.ppw + q.tile_pairs - 1) / q.tile_pairs;
+  const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes, !a.x_row && !a.batch_bytes);
+  if (int rc = gemv_choice_refused(c, a.T, a.K)) return rc;
+  if (c.route == GEMV_SKINNY) return launch_gemm_skinny(a_in, epi, st);
+  const int grid = c.q.grid;
+  a.ppw = c.q.ppw;
+  a.tile_pairs = c.q.tile_pairs;
+  a.ksplit = c.q.ksplit;
+  a.kw = c.q.kw;
+  a.n_tiles_full = (c.q.ppw + c.q.tile_pairs - 1) / c.q.tile_pairs;
   gemv_derive(a);
-  // MASK variant: slices that are not whole 32-k steps, or rows longer than the one-chunk-per-
-  // thread register staging covers
-  const bool mask = (a.kw * ksplit != a.K) || (a.K / 8 > kGemvThreads);
-  if (a.w8) {
-    SD_REQUIRE(a.packed && a.w_scale, "gemv: fp8 weights need the packed layout and row scales");
-    SD_REQUIRE(a.K % 64 == 0 && a.kw % 64 == 0 && a.kw * ksplit == a.K, "gemv: fp8 weights need K (%d) and the K slice (%d) in whole 64-k steps", a.K, a.kw);
-  }
-  size_t smem = gemv_smem(a.T, a.K, false);
-  a.alias_part = 0;
-  if (smem > kLdsLimit && n_tiles <= kGemvWaves / ksplit) {  // single round: partials may alias x
-    a.alias_part = 1;
-    smem = gemv_smem(a.T, a.K, true);
-  }
-  // rows too long to stage T of them whole (d_ff = 14336 takes 5): the chunked multi-token kernel covers the rest
-  // of 6..9 tokens — a pass may mix both kernels, they share layout, work split and epilogues
-  if (smem > kLdsLimit && !a.x_row && !a.batch_bytes && gemm_skinny_covers(a.T, a.n_pairs, a.K, a.w8 != 0)) return launch_gemm_skinny(a_in, epi, st);
-  SD_REQUIRE(smem <= kLdsLimit, "gemv: T=%d x K=%d does not fit LDS", a.T, a.K);
-  const int fixed = gemv_fixed_index(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes);
-  if (fixed >= 0) {
+  a.alias_part = c.alias ? 1 : 0;
+  if (c.route == GEMV_FIXED) {
     int i = 0;
 #define X(E, KS, TP, PRO) \
-    if (fixed == i++) return launch_fixed<E, KS, TP, PRO>(a, grid, smem, st);
+    if (c.fixed == i++) return launch_fixed<E, KS, TP, PRO>(a, c, grid, st);
     SD_GEMV_FIXED_TABLE(X)
 #undef X
   }
   switch (epi) {
-    case EPI_QKV_ROPE: return launch_epi<EPI_QKV_ROPE>(a, mask, grid, smem, st);
-    case EPI_RESID: return launch_epi<EPI_RESID>(a, mask, grid, smem, st);
-    case EPI_SWIGLU: return launch_epi<EPI_SWIGLU>(a, mask, grid, smem, st);
-    case EPI_GELU: return launch_epi<EPI_GELU>(a, mask, grid, smem, st);
-    case EPI_ARGMAX: return launch_epi<EPI_ARGMAX>(a, mask, grid, smem, st);
+    case EPI_QKV_ROPE: return launch_epi<EPI_QKV_ROPE>(a, c, grid, st);
+    case EPI_RESID: return launch_epi<EPI_RESID>(a, c, grid, st);
+    case EPI_SWIGLU: return launch_epi<EPI_SWIGLU>(a, c, grid, st);
+    case EPI_GELU: return launch_epi<EPI_GELU>(a, c, grid, st);
+    case EPI_ARGMAX: return launch_epi<EPI_ARGMAX>(a, c, grid, st);
     default: SD_REQUIRE(false, "gemv: unknown epilogue %d", epi);
   }
   return 0;

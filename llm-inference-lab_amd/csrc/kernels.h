@@ -141,6 +141,10 @@ int launch_gemm_skinny(const GemvArgs& a, int epi, hipStream_t st);   // T <= 64
 // name of the gemv.hip instance a plain launch (packed, no bias / x_row / batch) of T <= 9 tokens takes: "generic" or
 // "fixed<...>"; decided by the function launch_gemv asks. snprintf's return value.
 int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap);
+// name of the KERNEL such a launch runs, from the choice launch_gemv itself consumes: "fixed<...>" as above,
+// "generic<EPI,whole|mask,ttN,bf16|fp8,kbN>" (the template key of gemv_mfma_kernel) or "skinny:" + gemm_plan_name of the body the
+// launch is handed to (rows too long to stage T of them). *len: snprintf's return value. Nonzero (error set) where launch_gemv refuses.
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len);
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8 = false);                  // shape handled by gemm_skinny.hip
 // gemm_pipe.hip: the statically scheduled chunk pipeline for <= 64 tokens (tried first by launch_gemm_skinny, which has
 // set the work split fields of `a`)

@@ -494,6 +494,16 @@ class HipModel:
             out.append(gemm_plan(T, n_pairs, K, self.weight_dtype == "fp8", prologue, epi, flags))
         return out
 
+    def small_pass_instances(self, T: int) -> List[str]:
+        """The five kernels (ops.gemv_instance) a launch-path pass of T <= 9 tokens runs for qkv, out, gate / up, down and
+        lm_head, by analogy with pass_plan."""
+        from .ops import gemv_instance
+        out = []
+        for which in range(5):
+            _, K, n_pairs, epi, prologue = self.matrix_shape(which)
+            out.append(gemv_instance(T, n_pairs, K, self.weight_dtype == "fp8", prologue, epi))
+        return out
+
     def probe_forward(self, M: int = 1, iters: int = 50, skip_head: bool = False, timeline: bool = False,
                       stream: Optional[torch.cuda.Stream] = None, pos0: int = 0):
         """(average microseconds per forward of M tokens, bytes of weights per forward, timeline or None): sd_model_probe_forward.

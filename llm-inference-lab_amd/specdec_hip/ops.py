@@ -499,6 +499,17 @@ def gemv_variant(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int =
     return buf.value.decode()
 
 
+def gemv_instance(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID) -> str:
+    """Name of the kernel a layer-matrix launch of T <= 9 tokens really runs (sd_gemv_instance): "fixed<...>" as gemv_variant,
+    "generic<resid,mask,tt9,bf16,kb12>" (the generic kernel's template key) or "skinny:direct<tg1>" (rows too long to stage:
+    the csrc/gemm_skinny.hip body that takes the launch). Raises where the launcher would refuse. Follows SPECDEC_GEMV_GENERIC
+    in the environment, as a launch does. Host-only."""
+    buf = ctypes.create_string_buffer(64)
+    _abi.check(_abi.load().sd_gemv_instance(int(T), int(n_pairs), int(K), 1 if w8 else 0, int(prologue), int(epi), buf, len(buf)),
+               "sd_gemv_instance")
+    return buf.value.decode()
+
+
 class PersistPlan(NamedTuple):
     eligible: bool       # the model passes every static rule of the persistent forward
     max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)

@@ -86,8 +86,15 @@ def _first_argmax(logits):
     return torch.where(logits == top, idx, torch.full_like(idx, V)).amin(-1)
 
 
-def run_case(case: G.Case):
-    """-> {stage: worst error / bound}; raises AssertionError on any failed check"""
+def _planned_bodies(eng, case):
+    """the knobs of this process must be the ones the case was planned under, and the plan the one the case list recorded"""
+    T = case.T
+    assert eng.pass_plan(T) == case.names() == eng.pass_plan(T, case.flags), (case.id, eng.pass_plan(T), case.names())
+
+
+def run_case(case: G.Case, check_plan=_planned_bodies):
+    """-> {stage: worst error / bound}; raises AssertionError on any failed check. check_plan(engine, case): the assertion that
+    the kernels the engine is about to run are the ones the case records (tests/test_hip_gemv_instances_gpu.py passes its own)"""
     cfg, wd, B, M, T = case.cfg, case.wd, case.B, case.M, case.T
     what = case.id
     mw = _weights(cfg)
@@ -95,8 +102,7 @@ def run_case(case: G.Case):
     eng = _engine(mw, case.row0 + B + 1, l_max, wd, page_len=case.page_len)       # one cache row more than the pass uses
     eng.set_persist_tokens(0)
     assert T <= eng.pass_tokens, (what, T, eng.pass_tokens)                          # one pass
-    # the knobs of this process must be the ones the case was planned under, and the plan the one the case list recorded
-    assert eng.pass_plan(T) == case.names() == eng.pass_plan(T, case.flags), (what, eng.pass_plan(T), case.names())
+    check_plan(eng, case)
     if case.page_len is not None:
         random.Random(T).shuffle(eng._free)                                           # pages handed out in a scrambled order
     gen = torch.Generator(device="cuda").manual_seed(1000 * T + case.row0)
@@ -125,7 +131,7 @@ def run_case(case: G.Case):
         mw0 = dataclasses.replace(mw, config=dataclasses.replace(cfg, n_layers=1, name=cfg.name + "-layer0"), layers=[mw.layers[0]], meta={})
         e0 = _engine(mw0, 1, l_max, wd)
         e0.set_persist_tokens(0)
-        assert e0.pass_plan(T) == case.names()
+        check_plan(e0, case)
         e0.forward(tok, pos_base, skip_head=True)
         x_in = e0.hidden_rows(T)
         res = _check_pass(eng, mw, _matrices(mw, wd, layer=1), tok.reshape(-1).long(), positions, rows, logits.reshape(T, -1), R.chain_hip,

@@ -8,7 +8,9 @@ suites check against independent references (test_hip_fullshape_parity_gpu.py, t
 Models: one layer, vocabulary 1024 (a small head), the real layer dimensions of Llama-3.2-1B and 3B — the geometry is a function
 of (row pairs, K), so a narrower matrix would run another instance — dense KV and one paged case, plain random weights. The
 "short-last" model has dimensions at which the LAST workgroup of the QKV, out and gate / up launches owns fewer pairs than
-the others (2688 = 244 x 11 + 4, 1408 = 234 x 6 + 4, 8184 = 255 x 32 + 24 pairs) while the class is still a fixed one."""
+the others (2688 = 244 x 11 + 4, 1408 = 234 x 6 + 4, 8184 = 255 x 32 + 24 pairs) while the class is still a fixed one.
+The "8b" model runs the three 8B classes; its down-projection (K = 14336) is the generic MASK kernel up to 5 tokens and a
+csrc/gemm_skinny.hip body above (the 7-token context pass and the 9-token pass), on both sides of the switch."""
 
 import dataclasses
 
@@ -16,7 +18,7 @@ import pytest
 import torch
 
 from specdec_hip import weights as W
-from specdec_hip.ops import gemv_variant
+from specdec_hip.ops import gemv_instance, gemv_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +35,7 @@ MODELS = {
     "1b": (_one_layer(W.LLAMA_3_2_1B), None),
     "3b": (_one_layer(W.LLAMA_3_2_3B), None),
     "3b-paged": (_one_layer(W.LLAMA_3_2_3B), 32),
+    "8b": (_one_layer(W.LLAMA_3_8B), None),
     "short-last": (_one_layer(W.LLAMA_3_2_3B, d_model=2816, n_heads=28, n_kv_heads=7, head_dim=128, d_ff=8184, rope_scaling=None), None),
 }
 _weights = {}
@@ -54,6 +57,12 @@ def _variants(hm, T):
     return out
 
 
+def _down_instance(hm, T):
+    """the kernel the down-projection really runs (sd_gemv_instance; sd_gemv_variant names the launcher's family)"""
+    _, K, n_pairs, epi, pro = hm.matrix_shape(3)
+    return gemv_instance(T, n_pairs, K, False, pro, epi)
+
+
 def _run(name, generic, monkeypatch):
     """every observable of the passes: stage rows, ids, then the whole K and V caches"""
     from specdec_hip.engine import HipModel
@@ -67,10 +76,11 @@ def _run(name, generic, monkeypatch):
     hm = HipModel(_model_weights(name), batch=1, l_max=64, page_len=page_len)
     g = torch.Generator().manual_seed(11)
     toks = torch.randint(0, cfg.vocab, (1, CTX + sum(TOKENS)), generator=g).to(torch.int32).cuda()
-    seen, names = [], {}
+    seen, names, down = [], {}, {}
     pos = 0
     for T in (CTX,) + TOKENS:
         names[T] = _variants(hm, T)
+        down[T] = _down_instance(hm, T)
         ids, _ = hm.forward(toks[:, pos:pos + T].contiguous(), torch.tensor([pos], dtype=torch.int32, device="cuda"), 0,
                             skip_head=(pos == 0))
         for which in (hm.DEBUG_X, hm.DEBUG_Q, hm.DEBUG_ATTN, hm.DEBUG_ACT):
@@ -81,18 +91,21 @@ def _run(name, generic, monkeypatch):
     torch.cuda.synchronize()
     seen.append(("k cache", hm.k_cache.cpu()))
     seen.append(("v cache", hm.v_cache.cpu()))
-    return seen, names
+    return seen, names, down
 
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_fixed_instances_equal_the_generic_kernel_bit_for_bit(name, monkeypatch):
-    want, names_generic = _run(name, True, monkeypatch)
-    got, names_fixed = _run(name, False, monkeypatch)
+    want, names_generic, down_generic = _run(name, True, monkeypatch)
+    got, names_fixed, down_fixed = _run(name, False, monkeypatch)
     # the fixed path is what ran: every layer launch of every pass names a fixed instance (the down-projection of the
     # short-last model has K = 8184, no whole 32-k slices: a MASK shape, generic on both sides)
     for T, names in names_fixed.items():
         assert all(n.startswith("fixed<") for n in names[:3]), (name, T, names)
-        assert names[3].startswith("fixed<") or name == "short-last", (name, T, names)
+        assert names[3].startswith("fixed<") or name in ("short-last", "8b"), (name, T, names)
+    if name == "8b":    # the down-projection: the generic MASK kernel while T rows of 14336 fit the LDS, the hand-over above
+        for down in (down_fixed, down_generic):
+            assert down == {T: "generic<resid,mask,tt9,bf16,kb12>" if T <= 5 else "skinny:direct<tg1>" for T in (CTX,) + TOKENS}, down
     assert all(n == "generic" for names in names_generic.values() for n in names)
     assert len(got) == len(want)
     for (what, a), (_, b) in zip(got, want):
