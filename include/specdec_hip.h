@@ -633,6 +633,75 @@ int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float temperature, u
  * walk of sd_sample_token on two rows at once); top_p <= 0 or NaN. */
 int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p);
 
+/* Logit processors (csrc/logit_proc.hip): repetition / presence / frequency penalties and an additive bias, applied IN PLACE to
+ * stored bf16 logits rows before they are consumed. State, caller-owned device memory:
+ *   counts : uint16 [B][V] (sd_logit_counts_bytes: the table rounded up to 16 bytes). Bit 15 = the token occurs in the row's
+ *            prompt; bits 0..14 = how often the row has generated it, saturating at 32767. The repetition penalty looks at
+ *            prompt + generated (as HF and vLLM do), presence and frequency at generated only (as OpenAI and vLLM do).
+ *   bias   : optional float32 [B][V], added to the logit; -inf bans a token, an allowed set is its complement filled with -inf.
+ * The transform of one row of batch row b that is conditioned on the in-step tokens t_1..t_i, element v — every line one
+ * correctly rounded fp32 operation, no fused multiply-add, so a float32 restatement reproduces the bits (tests/logit_proc_ref.py):
+ *   x    = float(row[v])
+ *   c    = (counts[b][v] & 0x7fff) + #{j <= i : t_j == v}                      (integer)
+ *   seen = (counts[b][v] & 0x8000) != 0  or  c > 0
+ *   if seen and rp != 1:  x = (x < 0) ? x * rp : x / rp        (HF RepetitionPenaltyLogitsProcessor; x == 0 takes the division)
+ *   if c > 0:             x = x - presence
+ *                         x = x - (frequency * float(c))       (product rounded, then the subtraction)
+ *   if bias:              x = x + bias[b][v]
+ *   row[v] = bf16(x)      (round to nearest even, the conversion of the other epilogues; a NaN is stored as 0x7fc0)
+ *
+ * sd_logit_process: rows bf16, row (b, r) at rows + (b * R + r) * row_stride elements (row_stride >= V); tokens: device int32,
+ * row b's in-step tokens at tokens + b * tok_stride (nullable when no row has any); n_tokens < 0: row (b, r) is conditioned on
+ * the first r of them (the verify pass: i = r), else every row on the first n_tokens (<= 64). Rows with active[b] == 0
+ * (nullable) are not written. ids_out (nullable): ids_out[b * ids_stride + r] = argmax of the processed row — of the untouched
+ * row for an inactive b — in the order of the fused lm_head argmax (argmax_better, csrc/common.h): a NaN is the maximum, then
+ * the larger value, ties and several NaNs go to the lowest index. With rp = 1, presence = frequency = 0 and no bias the rows keep
+ * their bits (but a NaN's payload) and the ids are those of the fused path. workspace (needed with ids_out only):
+ * sd_logit_process_workspace(B, R, V) bytes, 4-byte aligned. A row is split over ceil(V / 4096) <= 64 workgroups, 16-byte
+ * accesses where logits, counts and bias of the row are 16-byte aligned, element-wise otherwise. Asynchronous on `stream`, no
+ * allocation, graph-capturable. Refused: NULL rows / counts, B, R, V < 1 or B * R > 65535, a stride below V, more than 64
+ * in-step tokens or a token stride below their number, rp <= 0 or NaN, non-finite presence / frequency, a short workspace.
+ *
+ * sd_logit_counts_set: row b <- cleared, bit 15 for every id of prompt_ids[0..n_prompt), one count for every occurrence in
+ * generated_ids[0..n_generated) (device lists; ids outside [0, V) are ignored). sd_logit_counts_add: for every row with
+ * active[b] != 0 (nullable) the first min(n_new[b], max_new) tokens of tokens + b * tok_stride are counted, a token listed twice
+ * counts twice, ids outside [0, V) (the -1 padding of a step's emitted tokens) are ignored; one lane per row, no atomics. */
+size_t sd_logit_process_workspace(int B, int R, int V);
+int sd_logit_process(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
+                     const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float repetition_penalty,
+                     float presence_penalty, float frequency_penalty, int32_t* ids_out, int ids_stride, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t sd_logit_counts_bytes(int B, int V);
+int sd_logit_counts_set(void* counts, int B, int V, int b, const int32_t* prompt_ids, int n_prompt, const int32_t* generated_ids,
+                        int n_generated, void* stream);
+int sd_logit_counts_add(void* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,
+                        const int32_t* active, void* stream);
+
+/* Logit processors inside the step: a further mode next to greedy, sampled-bonus and speculative sampling, combinable with each.
+ * With enable = 1 every logits row the step consumes is stored, processed (sd_logit_process, the same launcher), then consumed:
+ *   - draft forward i stores its last position's row (as the speculative-sampling mode does, including the device-selected two
+ *     forms of forward 0 and the persistent launch); the row is processed with in-step tokens d_1..d_i. Greedy and sampled-bonus:
+ *     the fused argmax of the processed row is d_{i+1}. Speculative sampling: the processed row is copied to q_i and drawn from by
+ *     the unchanged draw kernels.
+ *   - the verify forward stores p_0..p_K; ONE process launch covers all B * (K+1) rows, row (b, i) with in-step tokens d_1..d_i;
+ *     the argmax of the processed rows goes to the target-argmax slots. Greedy: the accept scan and the record follow as three
+ *     launches (the one-launch tail reads raw partials and is not taken). Sampled bonus: accept length and sampler on the
+ *     processed rows. Speculative sampling: the statistics and accept kernels on the processed p and q.
+ *   - after the accept kernel the counts of every active row advance by its emitted tokens (sd_logit_counts_add).
+ * So greedy output is the target's own greedy decoding under the processors, token for token, and speculative-sampling output
+ * is distributed as the target's own sampling from its processed rows: acceptance tests p'/q' of two processed distributions,
+ * and the usual proof applies unchanged. counts / bias (nullable) as above, [B][V], 16-byte aligned; counts are the caller's to
+ * initialise (sd_logit_counts_set) before the first step of a sequence. logits_buf: [B][K+1][V] bf16, 16-byte aligned, where the
+ * forwards store their rows while neither sampling mode is on (those modes' own buffers are used while one is: logits_buf may
+ * then be NULL; a step that finds no buffer is refused). workspace: sd_logit_process_workspace(B, K + 1, V) bytes.
+ * enable = 0 returns to the unprocessed step (launch for launch what it was). Either call drops the captured graph.
+ * Refused: repetition_penalty <= 0 or NaN; non-finite presence / frequency; NULL, short or misaligned buffers; loops without a
+ * draft model (self-draft, Medusa heads, EAGLE: their proposals come from no logits row); per-row adaptive K. Both emit modes
+ * are legal. */
+int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float repetition_penalty, float presence_penalty,
+                                    float frequency_penalty, void* counts, size_t counts_bytes, const float* bias, size_t bias_bytes,
+                                    void* logits_buf, size_t logits_bytes, void* workspace, size_t workspace_bytes);
+
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,
  * which the reference applies to one K for the whole batch from the host, pipeline.py:1994-2014). The loop keeps the

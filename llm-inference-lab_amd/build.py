@@ -59,7 +59,12 @@ def _digest(src: Path) -> str:
 # instruction is issued at full latency and the hot paths of a layer barely fit the instruction cache two CUs share; same-box A/B of
 # eight flag sets (profiles/round4_persist_ab.md): -O3 595.6 us per 1B forward, -O2 583.8, -Os 582.3, -align-all-nofallthru-blocks=6
 # 591.4, -align-all-blocks=4 605, the max-ilp / max-memory-clause scheduling strategies 595-596.
-FILE_FLAGS = {"persist.hip": ["-Os"]}
+FILE_FLAGS = {
+    "persist.hip": ["-Os"],
+    # csrc/logit_proc.hip promises one correctly rounded fp32 operation per line of its formula (a numpy float32 restatement
+    # reproduces the bits): no multiply-add contraction
+    "logit_proc.hip": ["-O3", "-ffp-contract=off"],
+}
 
 
 def _flags_for(src: Path) -> list[str]:

@@ -76,4 +76,14 @@ int launch_spec_step_shaped(const SpecState& s, const void* target_logits, const
                             int top_k, float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag,
                             int32_t* cand, hipStream_t st);
 
+// csrc/logit_proc.hip: logit processors (penalties, bias) on stored bf16 rows, in place; the step and the C-ABI ops run these
+size_t logit_process_workspace(int B, int R, int V);
+int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
+                         const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
+                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st);
+int launch_logit_counts_set(uint16_t* counts, int B, int V, int b, const int32_t* prompt, int n_prompt, const int32_t* gen, int n_gen,
+                            hipStream_t st);
+int launch_logit_counts_add(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,
+                            const int32_t* active, hipStream_t st);
+
 }  // namespace sd

@@ -1348,6 +1348,14 @@ struct sd_specdec {
   int32_t* spec_flags = nullptr;   // [2][B][K+1] device: accept flags, candidate next tokens
   int spec_top_k = 0;              // sd_specdec_set_spec_shaping: > 0 = both distributions shaped by top-k / top-p
   float spec_top_p = 1.0f;
+  // logit processors (sd_specdec_set_logit_processors): every logits row is stored, processed in place, then consumed
+  int lp = 0;
+  float lp_rp = 1.0f, lp_presence = 0.f, lp_frequency = 0.f;
+  uint16_t* lp_counts = nullptr;   // [B][V], caller-owned
+  const float* lp_bias = nullptr;  // [B][V] or null, caller-owned
+  void* lp_logits = nullptr;       // [B][K+1][V] bf16, caller-owned; used while neither sampling mode owns a buffer
+  void* lp_ws = nullptr;           // argmax partials of the process launches
+  size_t lp_ws_bytes = 0;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -1513,8 +1521,21 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
   // speculative sampling: every draft forward stores its logits, d_{i+1} is DRAWN from the last position's row (no argmax ids)
   const bool spec = s->spec != 0;
   const int V = s->target->cfg.vocab;
-  uint16_t* const q_pass = spec ? static_cast<uint16_t*>(s->spec_p) : nullptr;
-  int32_t* const ids_d = (one_pass_d || spec) ? nullptr : s->st.draft_ids;
+  // logit processors: the forwards store their rows (into the buffer of the sampling mode that is on, else the mode's own), the
+  // rows are processed in place and the argmax of the processed row replaces the fused one
+  const bool lp = s->lp != 0;
+  void* const p_buf = s->sample ? s->logits : (spec ? s->spec_p : (lp ? s->lp_logits : nullptr));
+  SD_REQUIRE(!lp || (s->draft && p_buf), "specdec_step: logit processors need a draft model and a logits buffer (sd_specdec_set_logit_processors)");
+  uint16_t* const q_pass = (spec || lp) ? static_cast<uint16_t*>(p_buf) : nullptr;   // (the verify forward overwrites it afterwards)
+  int32_t* const ids_d = (one_pass_d || spec || lp) ? nullptr : s->st.draft_ids;
+  // draft forward i left the logits of its M positions in q_pass: process row M - 1 of every batch row with d_1..d_i
+  const auto process_draft = [&](int M, int i) -> int {
+    if (int rc = launch_logit_process(q_pass + static_cast<size_t>(M - 1) * V, static_cast<long long>(M) * V, B, 1, V, s->lp_counts, s->lp_bias,
+                                      s->st.draft_tok, K, i, s->st.active, s->lp_rp, s->lp_presence, s->lp_frequency,
+                                      spec ? nullptr : s->st.draft_ids + (M - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d))
+      return rc;
+    return spec ? 0 : launch_draft_next(M, i, s->st, st_d);
+  };
   for (int i = 0; s->draft && i < K; ++i) {
     const int M = (i == 0) ? 2 : 1;
     const int32_t* toks = (i == 0) ? s->st.tok2 : s->st.next_tok;
@@ -1529,27 +1550,29 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
       s->draft->skip_k = s->st.fwd0_w;
       s->draft->skip_i = 1;
       rc_f = model_forward(s->draft, toks, 2, s->st.cur_len, -1, 0, B, 2, ids_d, 2, q_pass, SD_BF16, 0, st_d);
-      if (!rc_f && !spec) rc_f = finalize(2, 0, s->st.draft_ids, s->st.fwd0_w, 1);
+      if (!rc_f && !spec && !lp) rc_f = finalize(2, 0, s->st.draft_ids, s->st.fwd0_w, 1);
       if (!rc_f) {
         s->draft->skip_k = s->st.fwd0_w + 1;
         // (the 1-token form's logits row lands where the 2-token form leaves its second one, as its id does)
-        rc_f = model_forward(s->draft, toks + 1, 2, s->st.cur_len, 0, 0, B, 1, ids_d ? ids_d + 1 : nullptr, 2, spec ? q_pass + V : nullptr,
+        rc_f = model_forward(s->draft, toks + 1, 2, s->st.cur_len, 0, 0, B, 1, ids_d ? ids_d + 1 : nullptr, 2, q_pass ? q_pass + V : nullptr,
                              SD_BF16, 0, st_d);
       }
-      if (!rc_f && !spec) rc_f = finalize(1, 0, s->st.draft_ids + 1, s->st.fwd0_w + 1, 1);
+      if (!rc_f && !spec && !lp) rc_f = finalize(1, 0, s->st.draft_ids + 1, s->st.fwd0_w + 1, 1);
     } else {
       rc_f = model_forward(s->draft, toks, M, s->st.cur_len, off, 0, B, M, ids_d, 2, q_pass, SD_BF16, 0, st_d);
-      if (!rc_f && !spec) rc_f = finalize(M, i, s->st.draft_ids, s->draft->skip_k, i);
+      if (!rc_f && !spec && !lp) rc_f = finalize(M, i, s->st.draft_ids, s->draft->skip_k, i);
     }
     s->draft->skip_k = nullptr;
     if (rc_f) return rc_f;
+    if (lp)   // (exactly one form of forward 0 ran; both leave the last position's row in the same place)
+      if (int rc = process_draft(M, i)) return rc;
     if (spec && s->spec_top_k > 0) {
       if (int rc = launch_spec_draft_draw_shaped(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->spec_top_k, s->spec_top_p,
                                                  s->seed, s->draw, s->stream_id, st_d))
         return rc;
     } else if (spec) {   // exactly one form of forward 0 ran: one draw launch serves both
       if (int rc = launch_spec_draft_draw(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->seed, s->draw, s->stream_id, st_d)) return rc;
-    } else if (!one_pass_d) {
+    } else if (!one_pass_d && !lp) {
       if (int rc = launch_draft_next(M, i, s->st, st_d)) return rc;
     }
   }
@@ -1562,10 +1585,14 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
   // lm_head's partials (verify_tail_kernel) instead of three
   const unsigned* const st_word_d = (s->draft && s->draft->p_sync) ? s->draft->p_sync + 1 : nullptr;
   const unsigned* const st_word_t = s->target->p_sync ? s->target->p_sync + 1 : nullptr;
-  const bool tail = !s->sample && !spec && verify_tail_fits(s->st) && B * (K + 1) <= s->target->max_t;
+  const bool tail = !s->sample && !spec && !lp && verify_tail_fits(s->st) && B * (K + 1) <= s->target->max_t;
   if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, K + 1, tail ? nullptr : s->st.target_ids,
-                             K + 1, s->sample ? s->logits : (spec ? s->spec_p : nullptr), SD_BF16, 0, st_t))
+                             K + 1, p_buf, SD_BF16, 0, st_t))
     return rc;
+  if (lp)   // all B * (K+1) rows in one launch: row (b, i) is conditioned on d_1..d_i; the processed argmax replaces the fused ids
+    if (int rc = launch_logit_process(p_buf, V, B, K + 1, V, s->lp_counts, s->lp_bias, s->st.draft_tok, K, -1, s->st.active, s->lp_rp,
+                                      s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t))
+      return rc;
   if (tail) {
     if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
                                     s->step_counter, st_word_d, st_word_t, st_t))
@@ -1592,6 +1619,8 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
       return rc;
   }
   if (int rc = launch_accept(s->st, s->mode, spec ? 2 : s->sample, st_t)) return rc;
+  if (lp)   // the emitted tokens of every active row enter its counts
+    if (int rc = launch_logit_counts_add(s->lp_counts, B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
   if (int rc = launch_pack_record(s->st, s->host_record, s->rec, s->step_counter, st_word_d, st_word_t, st_t)) return rc;
   // persistent Medusa heads: the proposals of the next step, after the record of this one has left
   if (!s->heads.empty())
@@ -1743,6 +1772,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(target_rate == target_rate, "specdec_set_adaptive: target rate is NaN");
   SD_REQUIRE(s->heads.empty() && !s->eagle, "specdec_set_adaptive: stateful draft modes keep a fixed K");
   SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
+  SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -1857,6 +1887,55 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   s->spec_p = target_logits_buf;
   s->draw = draw_counters;
   s->stream_id = stream_ids;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float repetition_penalty, float presence_penalty,
+                                               float frequency_penalty, void* counts, size_t counts_bytes, const float* bias,
+                                               size_t bias_bytes, void* logits_buf, size_t logits_bytes, void* workspace,
+                                               size_t workspace_bytes_) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_logit_processors: NULL");
+  if (!enable) {
+    if (s->lp && s->exec) {
+      (void)hipGraphExecDestroy(s->exec);
+      (void)hipGraphDestroy(s->graph);
+      s->exec = nullptr;
+      s->graph = nullptr;
+    }
+    s->lp = 0;
+    return 0;
+  }
+  SD_REQUIRE(s->draft, "specdec_set_logit_processors: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_logit_processors: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(repetition_penalty == repetition_penalty && repetition_penalty > 0.f,
+             "specdec_set_logit_processors: repetition_penalty %g (must be > 0)", repetition_penalty);
+  SD_REQUIRE(presence_penalty - presence_penalty == 0.f && frequency_penalty - frequency_penalty == 0.f,
+             "specdec_set_logit_processors: presence_penalty %g / frequency_penalty %g must be finite", presence_penalty, frequency_penalty);
+  const size_t V = static_cast<size_t>(s->target->cfg.vocab), BV = static_cast<size_t>(s->B) * V;
+  SD_REQUIRE(counts && counts_bytes >= BV * 2, "specdec_set_logit_processors: counts buffer %zu B < %zu B ([B][V] uint16)", counts_bytes, BV * 2);
+  SD_REQUIRE(!bias || bias_bytes >= BV * 4, "specdec_set_logit_processors: bias buffer %zu B < %zu B ([B][V] float32)", bias_bytes, BV * 4);
+  const size_t need_p = BV * (s->K + 1) * 2, need_ws = logit_process_workspace(s->B, s->K + 1, static_cast<int>(V));
+  SD_REQUIRE(logits_buf || s->sample || s->spec, "specdec_set_logit_processors: NULL logits buffer (no sampling mode is on to lend its own)");
+  SD_REQUIRE(!logits_buf || logits_bytes >= need_p, "specdec_set_logit_processors: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need_p);
+  SD_REQUIRE(workspace && workspace_bytes_ >= need_ws, "specdec_set_logit_processors: workspace %zu B < %zu B", workspace_bytes_, need_ws);
+  SD_REQUIRE(((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(logits_buf) |
+               reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "specdec_set_logit_processors: buffers must be 16-byte aligned");
+  if (s->exec) {  // the captured step holds the unprocessed launches, or this mode's parameters
+    (void)hipGraphExecDestroy(s->exec);
+    (void)hipGraphDestroy(s->graph);
+    s->exec = nullptr;
+    s->graph = nullptr;
+  }
+  s->lp = 1;
+  s->lp_rp = repetition_penalty;
+  s->lp_presence = presence_penalty;
+  s->lp_frequency = frequency_penalty;
+  s->lp_counts = static_cast<uint16_t*>(counts);
+  s->lp_bias = bias;
+  s->lp_logits = logits_buf;
+  s->lp_ws = workspace;
+  s->lp_ws_bytes = workspace_bytes_;
   return 0;
 }
 

@@ -1,0 +1,295 @@
+// Logit processors inside the step: repetition / presence / frequency penalties, a per-row additive bias (logit_bias, banned
+// and allowed token sets) applied IN PLACE to stored bf16 logits rows before anything consumes them, with the argmax of each
+// processed row as an optional fused output. Restated on the CPU in tests/logit_proc_ref.py; the contract is written out at
+// sd_logit_process in include/specdec_hip.h.
+//
+// State: counts uint16 [B][V] — bit 15: the token occurs in the row's prompt; bits 0..14: how often the row has generated it
+// (saturating at 32767). bias: optional float32 [B][V]. For batch row b, a logits row conditioned on the in-step tokens
+// t_1..t_i, element v (every line one correctly rounded fp32 operation, no fused multiply-add: this file is built with
+// contraction off):
+//   x    = float(row[v])
+//   c    = (counts[b][v] & 0x7fff) + #{j <= i : t_j == v}
+//   seen = (counts[b][v] & 0x8000) != 0 or c > 0
+//   if seen and rp != 1:  x = (x < 0) ? x * rp : x / rp      (HF RepetitionPenaltyLogitsProcessor: x == 0 takes the division)
+//   if c > 0:             x = x - presence;  x = x - (frequency * float(c))
+//   if bias:              x = x + bias[b][v]
+//   row[v] = bf16(x)      (round to nearest even; a NaN is stored as 0x7fc0)
+//
+// Why in place: every consumer of a stored row (the sampler, the speculative-sampling statistics, the draws, the agreement
+// op) defines its contract on the stored bf16 values; processing the stored row keeps all of them word for word.
+//
+// Geometry: a row at V = 128256 is 256 KB of logits + 256 KB of counts + 513 KB of bias; through one CU's intake that is
+// ~18 us, so a row is split over S = ceil(V / 4096) <= 64 workgroups of 256 threads (grid S x rows), 16-byte loads of 8
+// elements per lane, the V % 8 tail elements by the row's last workgroup. Rows of an odd V are not 16-byte aligned from row to
+// row: a row whose logits, counts or bias pointer is misaligned takes the element-wise path, as the spec-sampling kernels do.
+// The argmax goes through per-workgroup partials [rows][S] and launch_argmax_finalize (the lm_head's layout and ordering:
+// NaN first, larger value, lower index). No grid barrier, no spin-wait, no atomics.
+//
+// Counts: logit_counts_set_kernel (one workgroup: clears a row, then marks prompt ids and counts generated ids; thread t owns
+// the ids with id % 1024 == t, so duplicates are applied in order by one thread) and logit_counts_add_kernel (one lane per
+// row walks its <= K + 1 emitted tokens serially; a token emitted twice counts twice; saturating).
+
+#pragma clang fp contract(off)
+
+#include "engine.h"
+
+namespace sd {
+
+constexpr int kLpThreads = 256;
+constexpr int kLpChunk = 4096;     // elements of a row per workgroup
+constexpr int kLpMaxSplit = 64;
+constexpr int kLpMaxTokens = 64;   // in-step tokens a row can be conditioned on
+constexpr int kLpSetThreads = 1024;
+
+int logit_process_split(int V) {
+  const int s = (V + kLpChunk - 1) / kLpChunk;
+  return s < 1 ? 1 : (s > kLpMaxSplit ? kLpMaxSplit : s);
+}
+
+struct LogitProcArgs {
+  uint16_t* rows;            // row (b, r) at rows + (b * R + r) * row_stride
+  long long row_stride;
+  int R, V;
+  const uint16_t* counts;    // [B][V]
+  const float* bias;         // [B][V] or null
+  const int32_t* tokens;     // in-step tokens of row b at tokens + b * tok_stride
+  int tok_stride;
+  int n_tokens;              // < 0: row (b, r) is conditioned on the first r tokens; else on the first n_tokens
+  const int32_t* active;     // nullable [B]
+  float rp, presence, frequency;
+  float* part_val;           // nullable: argmax partials [B * R][gridDim.x]
+  int* part_idx;
+};
+
+__device__ __forceinline__ uint16_t lp_element(float x, uint32_t cnt, int v, bool has_bias, float bias, const int* toks, int n,
+                                               const LogitProcArgs& a) {
+  int c = static_cast<int>(cnt & 0x7fffu);
+  for (int j = 0; j < n; ++j) c += (toks[j] == v) ? 1 : 0;
+  const bool seen = (cnt & 0x8000u) != 0 || c > 0;
+  if (seen && a.rp != 1.0f) x = (x < 0.0f) ? __fmul_rn(x, a.rp) : __fdiv_rn(x, a.rp);
+  if (c > 0) {
+    x = __fsub_rn(x, a.presence);
+    x = __fsub_rn(x, __fmul_rn(a.frequency, static_cast<float>(c)));
+  }
+  if (has_bias) x = __fadd_rn(x, bias);
+  return (x != x) ? static_cast<uint16_t>(0x7fc0u) : float_to_bf16_bits(x);
+}
+
+__global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitProcArgs a) {
+  __shared__ int toks[kLpMaxTokens];
+  __shared__ float sv[kLpThreads / kWave];
+  __shared__ int si[kLpThreads / kWave];
+  const int t = blockIdx.y, tid = threadIdx.x, V = a.V, S = gridDim.x, x0 = blockIdx.x;
+  const int b = t / a.R, r = t - b * a.R;
+  const bool act = !a.active || a.active[b] != 0;   // an inactive row is only read: its argmax is that of the untouched row
+  int n = a.n_tokens < 0 ? r : a.n_tokens;
+  n = (act && a.tokens) ? (n > kLpMaxTokens ? kLpMaxTokens : n) : 0;
+  if (tid < n) toks[tid] = a.tokens[static_cast<size_t>(b) * a.tok_stride + tid];
+  __syncthreads();
+  uint16_t* row = a.rows + static_cast<size_t>(t) * a.row_stride;
+  const uint16_t* cnt = a.counts + static_cast<size_t>(b) * V;
+  const float* bias = a.bias ? a.bias + static_cast<size_t>(b) * V : nullptr;
+  const bool has_bias = bias != nullptr;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  auto one = [&](int v) {
+    uint16_t w = row[v];
+    if (act) {
+      w = lp_element(bf16_bits_to_float(w), cnt[v], v, has_bias, has_bias ? bias[v] : 0.f, toks, n, a);
+      row[v] = w;
+    }
+    const float f = bf16_bits_to_float(w);
+    if (argmax_better(f, v, bv, bi)) { bv = f; bi = v; }
+  };
+  const bool aligned = ((reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(cnt) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0;
+  if (aligned) {
+    const int ngroups = V >> 3, gper = (ngroups + S - 1) / S;
+    const int g0 = x0 * gper, g1 = min(ngroups, g0 + gper);
+    uint4* row4 = reinterpret_cast<uint4*>(row);
+    const uint4* cnt4 = reinterpret_cast<const uint4*>(cnt);
+    const float4* bias4 = reinterpret_cast<const float4*>(bias);
+    for (int g = g0 + tid; g < g1; g += kLpThreads) {
+      const uint4 lw = row4[g];
+      uint32_t w[4] = {lw.x, lw.y, lw.z, lw.w};
+      if (act) {
+        const uint4 cw = cnt4[g];
+        const uint32_t c[4] = {cw.x, cw.y, cw.z, cw.w};
+        float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (has_bias) {
+          const float4 b0 = bias4[2 * g], b1 = bias4[2 * g + 1];
+          bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w;
+          bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint16_t lo = lp_element(__uint_as_float(w[j] << 16), c[j] & 0xffffu, 8 * g + 2 * j, has_bias, bb[2 * j], toks, n, a);
+          const uint16_t hi = lp_element(__uint_as_float(w[j] & 0xffff0000u), c[j] >> 16, 8 * g + 2 * j + 1, has_bias, bb[2 * j + 1], toks, n, a);
+          w[j] = static_cast<uint32_t>(lo) | (static_cast<uint32_t>(hi) << 16);
+        }
+        row4[g] = make_uint4(w[0], w[1], w[2], w[3]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float lo = __uint_as_float(w[j] << 16), hi = __uint_as_float(w[j] & 0xffff0000u);
+        if (argmax_better(lo, 8 * g + 2 * j, bv, bi)) { bv = lo; bi = 8 * g + 2 * j; }
+        if (argmax_better(hi, 8 * g + 2 * j + 1, bv, bi)) { bv = hi; bi = 8 * g + 2 * j + 1; }
+      }
+    }
+    if (x0 == S - 1)   // the V % 8 tail elements
+      for (int v = (ngroups << 3) + tid; v < V; v += kLpThreads) one(v);
+  } else {
+    const int eper = (V + S - 1) / S;
+    const int e0 = x0 * eper, e1 = min(V, e0 + eper);
+    for (int v = e0 + tid; v < e1; v += kLpThreads) one(v);
+  }
+  if (!a.part_val) return;   // (uniform)
+  wave_reduce_argmax(bv, bi);
+  if ((tid & (kWave - 1)) == 0) { sv[tid / kWave] = bv; si[tid / kWave] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kLpThreads / kWave; ++w)
+      if (argmax_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+    // (a workgroup whose share of the row is empty leaves (-inf, INT_MAX), which loses against every element)
+    a.part_val[static_cast<size_t>(t) * S + x0] = bv;
+    a.part_idx[static_cast<size_t>(t) * S + x0] = bi;
+  }
+}
+
+size_t logit_process_workspace(int B, int R, int V) {
+  if (B <= 0 || R <= 0 || V <= 0) return 0;
+  return static_cast<size_t>(B) * R * logit_process_split(V) * (sizeof(float) + sizeof(int));
+}
+
+int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
+                         const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
+                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  SD_REQUIRE(rows && counts, "logit_process: NULL rows / counts");
+  SD_REQUIRE(B >= 1 && R >= 1 && V >= 1 && static_cast<long long>(B) * R <= 65535, "logit_process: B=%d R=%d V=%d out of range", B, R, V);
+  SD_REQUIRE(row_stride >= V, "logit_process: row stride %lld < V=%d", row_stride, V);
+  const int n_max = n_tokens < 0 ? R - 1 : n_tokens;
+  SD_REQUIRE(n_max <= kLpMaxTokens, "logit_process: %d in-step tokens (at most %d)", n_max, kLpMaxTokens);
+  SD_REQUIRE(n_max == 0 || (tokens && tok_stride >= n_max), "logit_process: %d in-step tokens need a token array with a stride >= %d", n_max, n_max);
+  SD_REQUIRE(rp == rp && rp > 0.f, "logit_process: repetition_penalty %g (must be > 0)", rp);
+  SD_REQUIRE(presence - presence == 0.f && frequency - frequency == 0.f, "logit_process: presence %g / frequency %g must be finite", presence, frequency);
+  SD_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(counts)) & 1) == 0 && (reinterpret_cast<uintptr_t>(bias) & 3) == 0,
+             "logit_process: misaligned rows / counts / bias");
+  const int S = logit_process_split(V);
+  LogitProcArgs a{};
+  a.rows = static_cast<uint16_t*>(rows);
+  a.row_stride = row_stride;
+  a.R = R;
+  a.V = V;
+  a.counts = counts;
+  a.bias = bias;
+  a.tokens = tokens;
+  a.tok_stride = tok_stride;
+  a.n_tokens = n_tokens;
+  a.active = active;
+  a.rp = rp;
+  a.presence = presence;
+  a.frequency = frequency;
+  if (ids_out) {
+    SD_REQUIRE(workspace && workspace_bytes >= logit_process_workspace(B, R, V), "logit_process: workspace %zu B < %zu B", workspace_bytes,
+               logit_process_workspace(B, R, V));
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "logit_process: misaligned workspace");
+    SD_REQUIRE(ids_stride >= R, "logit_process: ids stride %d < R=%d", ids_stride, R);
+    a.part_val = static_cast<float*>(workspace);
+    a.part_idx = reinterpret_cast<int*>(a.part_val + static_cast<size_t>(B) * R * S);
+  }
+  hipLaunchKernelGGL(logit_process_kernel, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+  SD_LAUNCH_CHECK();
+  if (ids_out) return launch_argmax_finalize(a.part_val, a.part_idx, B * R, S, R, ids_stride, ids_out, st);
+  return 0;
+}
+
+// ---- counts ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kLpSetThreads) void logit_counts_set_kernel(uint16_t* row, int V, const int32_t* prompt, int n_prompt,
+                                                                         const int32_t* gen, int n_gen) {
+  const int tid = threadIdx.x;
+  for (int v = tid; v < V; v += kLpSetThreads) row[v] = 0;
+  __syncthreads();
+  // thread `tid` owns the ids with id % 1024 == tid: every word has one writer, which sees its own earlier stores
+  for (int j = 0; j < n_prompt; ++j) {
+    const int id = prompt[j];
+    if (id >= 0 && id < V && (id & (kLpSetThreads - 1)) == tid) row[id] = 0x8000u;
+  }
+  for (int j = 0; j < n_gen; ++j) {
+    const int id = gen[j];
+    if (id >= 0 && id < V && (id & (kLpSetThreads - 1)) == tid) {
+      const uint16_t c = row[id];
+      if ((c & 0x7fffu) != 0x7fffu) row[id] = static_cast<uint16_t>(c + 1);
+    }
+  }
+}
+
+int launch_logit_counts_set(uint16_t* counts, int B, int V, int b, const int32_t* prompt, int n_prompt, const int32_t* gen, int n_gen,
+                            hipStream_t st) {
+  SD_REQUIRE(counts && B >= 1 && V >= 1 && b >= 0 && b < B, "logit_counts_set: row %d of B=%d, V=%d", b, B, V);
+  SD_REQUIRE(n_prompt >= 0 && n_gen >= 0 && (n_prompt == 0 || prompt) && (n_gen == 0 || gen), "logit_counts_set: a NULL list with a count > 0");
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 1) == 0, "logit_counts_set: misaligned counts");
+  hipLaunchKernelGGL(logit_counts_set_kernel, dim3(1), dim3(kLpSetThreads), 0, st, counts + static_cast<size_t>(b) * V, V, prompt, n_prompt,
+                     gen, n_gen);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(kWave) void logit_counts_add_kernel(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride,
+                                                                 const int32_t* n_new, int max_new, const int32_t* active) {
+  const int b = blockIdx.x * kWave + threadIdx.x;
+  if (b >= B || (active && active[b] == 0)) return;
+  uint16_t* row = counts + static_cast<size_t>(b) * V;
+  int n = n_new[b];
+  n = n < 0 ? 0 : (n > max_new ? max_new : n);
+  for (int j = 0; j < n; ++j) {
+    const int id = tokens[static_cast<size_t>(b) * tok_stride + j];
+    if (id < 0 || id >= V) continue;
+    const uint16_t c = row[id];
+    if ((c & 0x7fffu) != 0x7fffu) row[id] = static_cast<uint16_t>(c + 1);
+  }
+}
+
+int launch_logit_counts_add(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,
+                            const int32_t* active, hipStream_t st) {
+  SD_REQUIRE(counts && tokens && n_new, "logit_counts_add: NULL argument");
+  SD_REQUIRE(B >= 1 && V >= 1 && max_new >= 0 && tok_stride >= max_new, "logit_counts_add: B=%d V=%d max_new=%d stride=%d", B, V, max_new, tok_stride);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 1) == 0, "logit_counts_add: misaligned counts");
+  hipLaunchKernelGGL(logit_counts_add_kernel, dim3((B + kWave - 1) / kWave), dim3(kWave), 0, st, counts, B, V, tokens, tok_stride, n_new,
+                     max_new, active);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace sd
+
+using namespace sd;
+
+extern "C" size_t sd_logit_process_workspace(int B, int R, int V) { return logit_process_workspace(B, R, V); }
+
+extern "C" int sd_logit_process(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
+                                const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float repetition_penalty,
+                                float presence_penalty, float frequency_penalty, int32_t* ids_out, int ids_stride, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  clear_error();
+  return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
+                              repetition_penalty, presence_penalty, frequency_penalty, ids_out, ids_stride, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t sd_logit_counts_bytes(int B, int V) {
+  if (B <= 0 || V <= 0) return 0;
+  return (static_cast<size_t>(B) * V * sizeof(uint16_t) + 15) / 16 * 16;
+}
+
+extern "C" int sd_logit_counts_set(void* counts, int B, int V, int b, const int32_t* prompt_ids, int n_prompt, const int32_t* generated_ids,
+                                   int n_generated, void* stream) {
+  clear_error();
+  return launch_logit_counts_set(static_cast<uint16_t*>(counts), B, V, b, prompt_ids, n_prompt, generated_ids, n_generated,
+                                 static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sd_logit_counts_add(void* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,
+                                   const int32_t* active, void* stream) {
+  clear_error();
+  return launch_logit_counts_add(static_cast<uint16_t*>(counts), B, V, tokens, tok_stride, n_new, max_new, active,
+                                 static_cast<hipStream_t>(stream));
+}

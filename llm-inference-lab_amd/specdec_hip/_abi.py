@@ -136,6 +136,17 @@ SIGNATURES = {
     "sd_specdec_set_spec_sampling": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p, _c_size,
                                               _c_void_p, _c_size, _c_void_p, _c_void_p]),
     "sd_specdec_set_spec_shaping": (_c_int, [_c_void_p, _c_int, ctypes.c_float]),
+    "sd_logit_process_workspace": (_c_size, [_c_int, _c_int, _c_int]),
+    "sd_logit_process": (
+        _c_int,
+        [_c_void_p, _c_i64, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, ctypes.c_float,
+         ctypes.c_float, ctypes.c_float, _c_void_p, _c_int, _c_void_p, _c_size, _c_void_p],
+    ),
+    "sd_logit_counts_bytes": (_c_size, [_c_int, _c_int]),
+    "sd_logit_counts_set": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "sd_logit_counts_add": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "sd_specdec_set_logit_processors": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_void_p, _c_size,
+                                                 _c_void_p, _c_size, _c_void_p, _c_size, _c_void_p, _c_size]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),

@@ -636,6 +636,9 @@ class HipSpecDec:
         self.sampling = self.spec_sampling = False
         self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
+        # logit processors (set_logit_processors): off; counts / bias tables are allocated at first use and kept
+        self.logit_processors = False
+        self.logit_counts = self.logit_bias = self._lp_ws = None
         self.rec_ints = self.lib.sd_specdec_record_ints(self.handle)
         ptr = self.lib.sd_specdec_record(self.handle)
         self._record = np.ctypeslib.as_array(ptr, shape=(2, self.B, self.rec_ints))   # slot = launch index & 1
@@ -757,6 +760,48 @@ class HipSpecDec:
                 self._draft_logits.numel() * 2, self._logits.data_ptr(), self._logits.numel() * 2, self._draw.data_ptr(),
                 self._stream_ids.data_ptr()), "sd_specdec_set_spec_sampling")
             self.spec_sampling = True
+
+    def set_logit_processors(self, enable: bool, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                             frequency_penalty: float = 0.0, bias: bool = False) -> None:
+        """Logit processors inside the step (sd_specdec_set_logit_processors): every logits row the step consumes is stored,
+        processed in place (penalties from `logit_counts`, then `logit_bias`), then consumed — greedy, sampled-bonus and
+        speculative sampling alike. The loop owns the buffers: `logit_counts` (int16 [B][V] holding the uint16 words: bit 15
+        prompt, bits 0..14 times generated; zeroed at first use, rows are the caller's to initialise with set_logit_counts_row),
+        `logit_bias` (float32 [B][V] of zeros, only with bias=True; -inf bans a token) and the logits [B][K+1][V] (shared with
+        the sampling modes: `step_logits`). The values are per loop, the tables per row."""
+        with torch.cuda.device(self.device):
+            if not enable:
+                _abi.check(self.lib.sd_specdec_set_logit_processors(self.handle, 0, 1.0, 0.0, 0.0, None, 0, None, 0, None, 0, None, 0),
+                           "sd_specdec_set_logit_processors")
+                self.logit_processors = False
+                return
+            V = self.target.weights.config.vocab
+            if self._logits is None:
+                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+            if self.logit_counts is None:
+                self.logit_counts = torch.zeros((self.B, V), dtype=torch.int16, device=self.device)
+                self._lp_ws = torch.empty(max(int(self.lib.sd_logit_process_workspace(self.B, self.K + 1, V)), 16), dtype=torch.uint8,
+                                          device=self.device)
+            if bias and self.logit_bias is None:
+                self.logit_bias = torch.zeros((self.B, V), dtype=torch.float32, device=self.device)
+            b = self.logit_bias if bias else None
+            torch.cuda.current_stream(self.device).synchronize()
+            _abi.check(self.lib.sd_specdec_set_logit_processors(
+                self.handle, 1, float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
+                self.logit_counts.data_ptr(), self.logit_counts.numel() * 2, b.data_ptr() if b is not None else None,
+                b.numel() * 4 if b is not None else 0, self._logits.data_ptr(), self._logits.numel() * 2, self._lp_ws.data_ptr(),
+                self._lp_ws.numel()), "sd_specdec_set_logit_processors")
+            self.logit_processors = True
+
+    def set_logit_counts_row(self, b: int, prompt_ids: Sequence[int], generated_ids: Sequence[int] = ()) -> None:
+        """Row b's counts for a new sequence in its slot: the prompt bit of every prompt id, one count per generated id
+        (sd_logit_counts_set on the loop's target stream)."""
+        from .ops import logit_counts_set
+        dev = self.device
+        with torch.cuda.device(dev), torch.cuda.stream(self.stream_t):   # the lists are uploaded on the stream that reads them
+            p = torch.tensor([int(x) for x in prompt_ids], dtype=torch.int32, device=dev) if len(prompt_ids) else None
+            g = torch.tensor([int(x) for x in generated_ids], dtype=torch.int32, device=dev) if len(generated_ids) else None
+            logit_counts_set(self.logit_counts, int(b), p, g)
 
     def set_draw_counts(self, draw_counts: Sequence[int]) -> None:
         """Rewrite the rows' draw counters (sampling modes) on the loop's target stream: the host's in-order view after steps

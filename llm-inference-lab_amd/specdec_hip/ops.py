@@ -394,6 +394,90 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     return (accept, nxt, ratios) if return_ratios else (accept, nxt)
 
 
+def logit_counts(B: int, V: int, device) -> torch.Tensor:
+    """A zeroed counts table for the logit processors: int16 [B][V] holding the uint16 words of sd_logit_process (bit 15: the
+    token is in the row's prompt, i.e. a negative int16; bits 0..14: times generated, saturating at 32767)."""
+    return torch.zeros((int(B), int(V)), dtype=torch.int16, device=device)
+
+
+def _check_counts(name: str, counts: torch.Tensor, dev) -> Tuple[int, int]:
+    if counts.dim() != 2 or counts.dtype != torch.int16 or counts.device != dev or not counts.is_contiguous():
+        raise ValueError(f"{name}: counts must be a contiguous int16 [B][V] tensor on {dev} (logit_counts)")
+    return int(counts.shape[0]), int(counts.shape[1])
+
+
+def logit_process(rows: torch.Tensor, counts: torch.Tensor, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                  frequency_penalty: float = 0.0, bias: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                  n_tokens: Optional[int] = None, active: Optional[torch.Tensor] = None, return_ids: bool = False):
+    """The logit processors on caller tensors, IN PLACE (sd_logit_process, csrc/logit_proc.hip; the formula is in
+    include/specdec_hip.h and restated in tests/logit_proc_ref.py).
+
+    rows: bf16 [B][R][V], unit inner stride, rows a constant stride apart (a view of a wider buffer is not copied); counts:
+    logit_counts(B, V); bias: optional float32 [B][V]; tokens: optional int32 [B][n], row b's in-step tokens; n_tokens: None =
+    row (b, r) is conditioned on the first r tokens (the verify pass), else every row on the first n_tokens; active: optional
+    int32 [B], rows with 0 are not written. Returns None, or with return_ids the int32 [B][R] argmax of each processed row."""
+    lib = _abi.load()
+    dev = _require_device("logit_process", rows, counts)
+    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
+        raise ValueError("logit_process: rows must be bfloat16 [B][R][V]")
+    B, R, V = (int(x) for x in rows.shape)
+    if _check_counts("logit_process", counts, dev) != (B, V):
+        raise ValueError(f"logit_process: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
+    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
+    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
+        raise ValueError("logit_process: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
+        raise ValueError(f"logit_process: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
+    n_tok = -1 if n_tokens is None else int(n_tokens)
+    tok_stride = 0
+    if tokens is not None:
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
+            raise ValueError(f"logit_process: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
+        tok_stride = int(tokens.shape[1])
+    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
+        raise ValueError(f"logit_process: active must be a contiguous int32 [{B}] tensor on {dev}")
+    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
+    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_logit_process(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
+                                        ptr(active), float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
+                                        ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(dev)), "sd_logit_process")
+    return ids
+
+
+def logit_counts_set(counts: torch.Tensor, b: int, prompt_ids: Optional[torch.Tensor] = None,
+                     generated_ids: Optional[torch.Tensor] = None) -> None:
+    """Row b of `counts` <- cleared, the prompt bit of every id in prompt_ids, one count per occurrence in generated_ids (int32
+    device vectors; sd_logit_counts_set). Asynchronous on the current stream."""
+    dev = _require_device("logit_counts_set", counts)
+    B, V = _check_counts("logit_counts_set", counts, dev)
+    for name, t in (("prompt_ids", prompt_ids), ("generated_ids", generated_ids)):
+        if t is not None and (t.dim() != 1 or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"logit_counts_set: {name} must be a contiguous int32 vector on {dev}")
+    n_p = int(prompt_ids.numel()) if prompt_ids is not None else 0
+    n_g = int(generated_ids.numel()) if generated_ids is not None else 0
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().sd_logit_counts_set(counts.data_ptr(), B, V, int(b), prompt_ids.data_ptr() if n_p else None, n_p,
+                                                   generated_ids.data_ptr() if n_g else None, n_g, _stream_ptr(dev)), "sd_logit_counts_set")
+
+
+def logit_counts_add(counts: torch.Tensor, tokens: torch.Tensor, n_new: torch.Tensor, active: Optional[torch.Tensor] = None) -> None:
+    """Every active row's first n_new[b] tokens of tokens[b] (int32 [B][n]; ids outside the vocabulary, such as a -1 padding,
+    are ignored) enter its counts, saturating; a token listed twice counts twice (sd_logit_counts_add)."""
+    dev = _require_device("logit_counts_add", counts, tokens, n_new)
+    B, V = _check_counts("logit_counts_add", counts, dev)
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or not tokens.is_contiguous():
+        raise ValueError(f"logit_counts_add: tokens must be a contiguous int32 [{B}][n] tensor")
+    for name, t in (("n_new", n_new), ("active", active)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"logit_counts_add: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    n = int(tokens.shape[1])
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().sd_logit_counts_add(counts.data_ptr(), B, V, tokens.data_ptr(), n, n_new.data_ptr(), n,
+                                                   active.data_ptr() if active is not None else None, _stream_ptr(dev)), "sd_logit_counts_add")
+
+
 def spec_agreement(draft_logits: torch.Tensor, target_logits: torch.Tensor, temperature: float = 1.0):
     """Draft-target agreement per position (sd_spec_agreement, csrc/spec_agree.hip): how much of softmax(target / T) the draft's
     softmax(draft / T) reproduces, in float64 over the stored bf16 logits.

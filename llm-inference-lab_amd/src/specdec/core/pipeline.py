@@ -25,6 +25,7 @@ host-policy loop and, seeded alike, makes the reference's draws (models/hip_lm.p
 from __future__ import annotations
 
 import logging
+import math
 import os
 import time
 from typing import Any, Dict, List, Optional, Sequence, Union
@@ -94,10 +95,12 @@ def expected_tokens_per_step(alpha: Sequence[float], k_max: int = 8) -> Dict[int
 
 
 class _Row:
-    __slots__ = ("seq", "generated", "active", "proposed", "accepted", "draws", "steps", "strict_acc", "strict_prop", "k_trace", "counters")
+    __slots__ = ("seq", "generated", "active", "proposed", "accepted", "draws", "steps", "strict_acc", "strict_prop", "k_trace", "counters",
+                 "n_prompt")
 
     def __init__(self, seq: List[int]):
         self.seq, self.generated, self.active = seq, [], True
+        self.n_prompt = len(seq)                   # seq[:n_prompt] is the prompt, the rest was generated (logit processors)
         self.proposed = self.accepted = self.draws = self.steps = 0
         self.counters: List[tuple] = []            # after each of the row's own steps: (proposed, accepted, tokens generated, accept length)
         self.strict_acc = self.strict_prop = 0     # per-row adaptive K: what the row's controller is fed with
@@ -421,17 +424,20 @@ class SpeculativePipeline:
     # ------------------------------------------------------------------ the loop
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None,
-                      self_draft: bool = False, share_prefix: bool = False) -> "DecodeSession":
+                      self_draft: bool = False, share_prefix: bool = False, **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
-        (DecodeSession)."""
-        return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix)
+        (DecodeSession). processors: repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids,
+        allowed_token_ids (logit_processor_config); identity values leave the mode off."""
+        return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix,
+                             self.logit_processor_config(processors))
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
-                sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False):
+                sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False,
+                processors: Optional[Dict[str, Any]] = None):
         t_start = time.time()
-        sess = self.start_session(prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix)
+        sess = DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix, processors)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -617,6 +623,76 @@ class SpeculativePipeline:
         return {"temperature": float(temperature), "top_k": int(top_k) if top_k else None,
                 "top_p": None if top_p is None else float(top_p), "seed": int(kwargs.get("seed", self.config.get("seed") or 0))}
 
+    _PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "bad_token_ids", "allowed_token_ids")
+
+    def logit_processor_config(self, kwargs: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+        """The logit processors of a run (call kwargs over config): repetition_penalty (> 0; over prompt + generated tokens),
+        presence_penalty / frequency_penalty (over generated tokens), logit_bias {id: value}, bad_token_ids, allowed_token_ids.
+        -> None for identity values (the mode stays off and the step is the unprocessed one), else {"rp", "presence",
+        "frequency", "bias": float32 [V] on the host or None}: logit_bias, banned and allowed ids all come down to the one
+        additive table (-inf bans). Refused: a penalty out of range, ids outside the vocabulary, an empty allowed set."""
+        unknown = set(kwargs) - set(self._PROCESSOR_KEYS)
+        if unknown:
+            raise TypeError(f"unknown logit-processor argument(s): {sorted(unknown)}")
+
+        def val(key, default):
+            v = kwargs.get(key)
+            if v is None:
+                v = self.config.get(key)
+            return default if v is None else v
+
+        rp, pres, freq = float(val("repetition_penalty", 1.0)), float(val("presence_penalty", 0.0)), float(val("frequency_penalty", 0.0))
+        if not rp > 0.0:
+            raise ValueError(f"repetition_penalty={rp} (must be > 0)")
+        if not (math.isfinite(pres) and math.isfinite(freq)):
+            raise ValueError(f"presence_penalty={pres} / frequency_penalty={freq} must be finite")
+        V = self.base_lm.vocab_size
+        lb, bad, allowed = val("logit_bias", None), val("bad_token_ids", None), val("allowed_token_ids", None)
+
+        def ids_of(name, xs):
+            out = [int(x) for x in xs]
+            for x in out:
+                if not 0 <= x < V:
+                    raise ValueError(f"{name}: id {x} is outside the vocabulary [0, {V})")
+            return out
+
+        bias = None
+        if lb or bad or allowed is not None:
+            bias = torch.zeros(V, dtype=torch.float32)
+            if allowed is not None:
+                keep = ids_of("allowed_token_ids", allowed)
+                if not keep:
+                    raise ValueError("allowed_token_ids is empty: no token could be emitted")
+                bias.fill_(float("-inf"))
+                bias[keep] = 0.0
+            for t, v in zip(ids_of("logit_bias", (lb or {}).keys()), (lb or {}).values()):
+                if math.isnan(float(v)):
+                    raise ValueError(f"logit_bias[{t}] is NaN")
+                bias[t] += float(v)
+            if bad:
+                bias[ids_of("bad_token_ids", bad)] = float("-inf")
+        if rp == 1.0 and pres == 0.0 and freq == 0.0 and bias is None:
+            return None
+        return {"rp": rp, "presence": pres, "frequency": freq, "bias": bias}
+
+    def _processors_for_step(self, kwargs: Dict[str, Any], route_ok: bool, what: str) -> Optional[Dict[str, Any]]:
+        """logit_processor_config of a call, refused where the run does not go through the captured step with a draft model and a
+        fixed K: the processors are a device stage of that step and are not approximated elsewhere."""
+        from ..policies.controllers import FixedKController
+
+        lp = self.logit_processor_config({k: kwargs[k] for k in self._PROCESSOR_KEYS if k in kwargs})
+        if lp is None:
+            return None
+        if not route_ok:
+            raise NotImplementedError(f"logit processors (penalties, logit_bias, token bans) run inside the captured device step: {what} "
+                                      "is not supported with them")
+        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None:
+            raise NotImplementedError("logit processors need the draft-model mode (draft_mode='vanilla'): medusa / eagle proposals come "
+                                      "from no logits row")
+        if not isinstance(self.controller, FixedKController):
+            raise NotImplementedError("logit processors keep a fixed K (controller='fixed'): adaptive K is not supported")
+        return lp
+
     def _spec_sampling_config(self, kwargs: Dict[str, Any]) -> Dict[str, Any]:
         """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature,
         seed, top_k and top_p (policy_params; call-level top_k / top_p stay refused: the policy shapes the mode). What the mode
@@ -653,13 +729,16 @@ class SpeculativePipeline:
         # drafts with the draft model
         if self.policy_name == "rejection":
             raise NotImplementedError("policy='rejection' is a generate_batch policy (it emits a correction / bonus token every step)")
+        processors = self._processors_for_step(
+            kwargs, self.policy_name == "longest_prefix" and not self._fake and sample_t is None,
+            "generate(do_sample=True)" if sample_t is not None else f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
         if self.policy_name != "longest_prefix" or self._medusa_random() or self._fake or sample_t is not None:
             rows, st = self._decode_host_policy([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
                                                 temperature=float(temperature), sample_t=sample_t,
                                                 sample_kwargs={k: kwargs[k] for k in ("top_k", "top_p") if k in kwargs})
         else:
             rows, st = self._decode([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
-                                    self_draft=self.config.get("draft_mode") in ("medusa", "eagle"))
+                                    self_draft=self.config.get("draft_mode") in ("medusa", "eagle"), processors=processors)
         r = rows[0]
         total_ms = (time.time() - t_begin) * 1e3
         self.metrics = {"total_proposed": r.proposed, "total_accepted": r.accepted, "total_steps": st["steps"],
@@ -717,9 +796,11 @@ class SpeculativePipeline:
         if n > 1:
             prompts = [p for p in prompts for _ in range(n)]
         ids = [self._encode(p) for p in prompts]
+        device_step = self.policy_name == "longest_prefix" or (self.policy_name == "rejection" and self.rejection_backend == "device")
+        processors = self._processors_for_step(kwargs, device_step, f"policy={self.policy_name!r} on the host loop")
         if self.policy_name == "rejection" and self.rejection_backend == "device":
             rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs),
-                                    share_prefix=share_prefix)
+                                    share_prefix=share_prefix, processors=processors)
         elif self.policy_name == "rejection":
             rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
         elif self.policy_name != "longest_prefix":
@@ -728,7 +809,7 @@ class SpeculativePipeline:
             rows, st = self._decode_host_policy(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
             rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=sampling, self_draft=heads,
-                                    share_prefix=share_prefix)
+                                    share_prefix=share_prefix, processors=processors)
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -787,6 +868,8 @@ class SpeculativePipeline:
         sampling = self._sampling_config(do_sample, temperature, kwargs)
         if self.draft_lm is None:
             raise ValueError("generate_many drafts with the draft model: pass draft_lm / draft_model")
+        processors = self._processors_for_step(kwargs, self.policy_name == "longest_prefix" and not self._fake,
+                                               f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
         ids = [self._encode(p) for p in prompts]
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
@@ -794,7 +877,7 @@ class SpeculativePipeline:
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
         sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens,
-                             share_prefix=share_prefix)
+                             share_prefix=share_prefix, processors=processors)
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -919,8 +1002,13 @@ class DecodeSession:
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                  sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None, self_draft: bool = False,
-                 share_prefix: bool = False):
+                 share_prefix: bool = False, processors: Optional[Dict[str, Any]] = None):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
+        # logit processors (SpeculativePipeline.logit_processor_config; None: off): a device stage of the step, with a counts row
+        # per cache row that is (re)written wherever the row's device state is
+        self.processors = processors
+        if processors is not None and (self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))):
+            raise NotImplementedError("logit processors need the HIP step with a draft model and a fixed K")
         if share_prefix and pipe._fake:
             raise NotImplementedError("share_prefix needs the HIP engines (implementation='hip')")
         self.self_draft = self_draft
@@ -976,6 +1064,7 @@ class DecodeSession:
                 for b in range(len(self.rows)):
                     self.loop.set_adaptive_row(b, ctl.initial_k)
         self._apply_sampling()
+        self._apply_processors()
         self._stateful_draft = self_draft and (pipe.medusa_heads is not None or pipe._eagle())
         if self_draft and pipe._eagle():
             self.loop.reset_eagle()   # the reference keeps the state on the pipeline object, across generate() calls even; here a run starts clean
@@ -1044,6 +1133,29 @@ class DecodeSession:
         self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
                                stream_ids=list(range(len(self.rows))), draw_counts=[r.draws for r in self.rows])
 
+    def _apply_processors(self) -> None:
+        """Loops are cached per (batch, K): switch the one in use to this run's processors (or off), fill the bias rows and every
+        row's counts — each row's own, from its own prompt, forked rows included."""
+        lp, loop = self.processors, self.loop
+        if lp is None:
+            if loop.logit_processors:
+                loop.sync()
+                loop.set_logit_processors(False)
+            return
+        loop.sync()
+        loop.set_logit_processors(True, lp["rp"], lp["presence"], lp["frequency"], bias=lp["bias"] is not None)
+        if lp["bias"] is not None:
+            with torch.cuda.stream(loop.stream_t):
+                loop.logit_bias.copy_(lp["bias"].to(loop.device).unsqueeze(0).expand_as(loop.logit_bias))
+        for b in range(len(self.rows)):
+            self._set_counts(b)
+
+    def _set_counts(self, b: int) -> None:
+        """Row b's counts as the host sees the row: the prompt's ids, and what it has generated so far."""
+        if self.processors is not None:
+            r = self.rows[b]
+            self.loop.set_logit_counts_row(b, r.seq[:r.n_prompt], r.seq[r.n_prompt:])
+
     def _resampler(self, b: int, row: _Row):
         """Draw at another position of the step's logits with the row's current Philox draw."""
         from specdec_hip.ops import sample_token_hip
@@ -1077,6 +1189,8 @@ class DecodeSession:
                     self.stats["prefilled_rows"] += 1 if fresh else 0
                 loop.join_current_stream()
             pipe._set_row(loop, b, r)              # (re)position, or freeze a finished row
+            if r.active:
+                self._set_counts(b)                # (void steps counted tokens the row never kept: back to the in-order view)
             if self.per_row:                       # the device counted steps the host voided: hand it the in-order view
                 m = self.row_ctl[b]
                 loop.set_adaptive_row(b, m.current_k, r.strict_acc, r.strict_prop, m.acceptance_history[-4:])
@@ -1178,6 +1292,7 @@ class DecodeSession:
                 for b, r in enumerate(rows):
                     pipe._set_row(self.loop, b, r)
                 self._apply_sampling()
+                self._apply_processors()
         k, loop, rt = self.k, self.loop, self.rt
         t0 = time.time()
         if not self._queue:

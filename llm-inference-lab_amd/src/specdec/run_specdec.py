@@ -57,6 +57,11 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "rows are forked from it (implies --share-prefix); they differ under --spec-sampling (a Philox stream per row)")
     ap.add_argument("--share-prefix", action="store_true",
                     help="decode through generate_batch with share_prefix=True (rows pay for an equal prompt or a common prefix once)")
+    ap.add_argument("--repetition-penalty", type=float, help="divide (multiply, when negative) the logits of tokens in the prompt or "
+                                                              "generated so far by this (> 0; inside the captured step)")
+    ap.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
+    ap.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
+    ap.add_argument("--ban-token", type=int, action="append", metavar="ID", help="never emit this token id (repeatable)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
@@ -125,13 +130,15 @@ def main(argv=None) -> int:
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         batch = args.spec_sampling or args.share_prefix or args.n != 1
+        proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
+                                  ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
-            rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n)
+            rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],
                  "acceptance_rate": rs[0]["accepted"] / max(rs[0]["proposed"], 1), "n": len(rs), "texts": [x["text"] for x in rs],
                  "forked_rows": rs[0]["batch_metrics"]["forked_rows"], "shared_positions": rs[0]["batch_metrics"]["shared_positions"]}
         else:
-            r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False)
+            r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False, **proc)
         if args.eval_perplexity:
             r["perplexity"], r["perplexity_loss"] = generated_perplexity(pipe.base_lm, r["generated_tokens"])
         if args.eval_agreement:

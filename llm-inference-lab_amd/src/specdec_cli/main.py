@@ -52,13 +52,15 @@ def cmd_run(args: argparse.Namespace) -> int:
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
                                draft_mode="vanilla", **extra)
+    proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
+                              ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
     if spec or args.share_prefix or args.n != 1:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
-        rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n)
+        rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
             print(f"Text {i}: {x.get('text', '')}")
     else:
-        res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample)
+        res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample, **proc)
     kinfo = get_kernel_info()
     print(f"Device: {res.get('device')} | Dtype: {res.get('dtype')} | "
           f"Backends: verify={kinfo.get('verify_backend')}, kv_append={kinfo.get('kv_append_backend')}")
@@ -93,6 +95,10 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--spec-top-k", type=int, help="--spec-sampling: keep the top_k (1..1024) largest logits of both distributions")
     pr.add_argument("--spec-top-p", type=float, help="--spec-sampling: nucleus cut inside --spec-top-k (needs it)")
     pr.add_argument("--seed", type=int, default=0)
+    pr.add_argument("--repetition-penalty", type=float, help="repetition penalty (> 0) over prompt + generated tokens, inside the captured step")
+    pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
+    pr.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
+    pr.add_argument("--ban-token", type=int, action="append", metavar="ID", help="never emit this token id (repeatable)")
     pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
                                                      "once and forked into the others (implies --share-prefix)")
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
