@@ -7,7 +7,7 @@
 namespace sd {
 namespace debug_env {
 
-// ---- persistent forward (csrc/persist.hip, engine.hip) ------------------------------------------------------------------
+// ---- persistent forward (csrc/persist.hip, engine.hip; the loop's two: spec_loop.hip) -------------------------------------
 constexpr const char* kNoPersist = "SPECDEC_NO_PERSIST";            // set: no model is eligible (every pass on the launch path). For a
                                                                      // GPU shared with other processes: the launch needs all 256 CUs.
 constexpr const char* kPersistMaxT = "SPECDEC_PERSIST_MAX_T";       // tokens per persistent pass at bind time (default 2 for d_model <= 2048, else 0)

@@ -1,12 +1,81 @@
-// Engine-internal types: model instance and the device-side state of the
-// draft-then-verify loop. The C-ABI view of these is in include/specdec_hip.h.
+// Engine-internal types: model instance (csrc/engine.hip) and the device-side state of the
+// draft-then-verify loop (csrc/spec_loop.hip). The C-ABI view of these is in include/specdec_hip.h.
 #pragma once
 
 #include <vector>
 
 #include "kernels.h"
+#include "persist.h"
+#include "prefill_gemm.h"
+
+struct sd_model {
+  sd_model_config cfg;
+  std::vector<sd_layer_weights> layers;
+  // bound storage
+  uint16_t* k_cache = nullptr;
+  uint16_t* v_cache = nullptr;
+  int B = 0, Lmax = 0;
+  // paged KV (sd_model_bind_paged): k_cache / v_cache are page pools of n_pages pages per layer, Lmax = max_pages * page_len
+  const int32_t* block_table = nullptr;   // device [B][max_pages], caller-owned and caller-maintained
+  int page_shift = 0, max_pages = 0, n_pages = 0;
+  // workspace carve
+  uint16_t* x = nullptr;     // [64][d]
+  uint16_t* q = nullptr;     // [64][Hq*D]
+  uint16_t* attn = nullptr;  // [64][Hq*D]
+  uint16_t* act = nullptr;   // [64][ff]
+  int32_t* probe_pos = nullptr;  // [1] zero: position base of the QKV probe
+  float* attn_ws = nullptr;      // split-KV partial tiles (attention.hip)
+  unsigned* attn_cnt = nullptr;  // arrival counters, zero between launches
+  float* xstat = nullptr;    // [2][128][256]: row statistics handed from an EPI_RESID launch to the next norm-fused one (> 9 tokens)
+  float* part_val = nullptr; // [64][512]
+  int small_t = sd::kGemvMaxT; // tokens per pass of gemv.hip for this model's widest activation row (<= 9)
+  int max_t = sd::kGemvMaxT; // tokens per pass: 64 when every matrix of the model is covered by gemm_skinny.hip
+  int* part_idx = nullptr;
+  int head_grid = 0;         // grid of the last lm_head launch (partials per token)
+  const int32_t* skip_k = nullptr;   // set around a draft forward of the adaptive step (enqueue_step): every launch of the
+  int skip_i = 0;                    // forward returns at entry when *skip_k <= skip_i
+  std::vector<const void*> packed;  // per matrix (4 per layer + lm_head) or empty: row-major weights
+  std::vector<const float*> scales; // fp8 storage: fp32 row scales per matrix
+  const void* mat(int index, const void* row_major) const { return packed.empty() ? row_major : packed[index]; }
+  int is_packed() const { return packed.empty() ? 0 : 1; }
+  int w8() const { return scales.empty() ? 0 : 1; }
+  const float* scale(int index) const { return scales.empty() ? nullptr : scales[index]; }
+  // persistent forward (csrc/persist.hip): passes of <= persist_t tokens run as ONE launch
+  int persist_t = 0;                       // 0 = not available for this model / device
+  bool persist_taps = true;                // stage rows written by persistent passes (sd_specdec_create turns them off for its draft)
+  sd::PersistOp* p_ops = nullptr;          // device: 4 per layer + lm_head, stream order
+  unsigned long long* p_gran = nullptr;    // granule buffers, two parities
+  unsigned p_gran_parity = 0;
+  unsigned* p_sync = nullptr;              // [0] launch counter, [1] status
+  unsigned long long* p_debug = nullptr;   // optional timeline (sd_model_probe_persist)
+  void* prefill_ws = nullptr;              // lazily allocated workspace of the GEMM prefill path (csrc/prefill_gemm.hip)
+  int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
+  int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
+  sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
+  sd::PrefillRows prefill_rows;            // the last GEMM-prefill chunk's rows in prefill_ws (sd_model_prefill_rows), valid while
+  int prefill_mc = 0;                      // prefill_mc > 0: cleared by a bind and by every pass that is not such a chunk
+  void* score_ws = nullptr;                // sd_model_score: normed rows, head partials, target logits, a zero word (first call)
+  unsigned* host_status = nullptr;         // pinned host word: a persistent launch that gives up stores its reason here as well
+  int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
+  int len_hint = 0;                        // caller's bound on the rows' current lengths (sd_model_set_length_hint; default Lmax)
+  int ctx_limit = 0;                       // longest rows the persistent launch serves (kPersistMaxCtx; lifted by SPECDEC_PERSIST_MAX_T)
+  ~sd_model() {
+    if (host_status) (void)hipHostFree(host_status);
+    if (prefill_ws) (void)hipFree(prefill_ws);
+    if (score_ws) (void)hipFree(score_ws);
+    sd::native_plan_free(native_plan);
+  }
+};
 
 namespace sd {
+
+// csrc/engine.hip: what the step loop (csrc/spec_loop.hip) needs from the model
+constexpr int kMaxPartials = 512;
+// rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are indexed from row0
+int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base, int pos_off, int row0, int B, int M,
+                  int32_t* ids_out, int ids_stride, void* logits_out, int logits_dtype, int skip_head, hipStream_t st);
+GemvArgs matrix_args(const sd_model* m, int index);
+bool persist_pass_ok(const sd_model* m, int T, int Bc, int Mc);
 
 // device-resident loop state (all int32, B rows, K draft tokens per step)
 struct SpecState {
@@ -63,18 +132,13 @@ int launch_sample_step(const SpecState& s, const void* logits, int V, float temp
                        uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st);
 
 
-// csrc/spec_sample.hip: speculative sampling inside the step
+// csrc/spec_sample.hip: speculative sampling inside the step. top_k == 0: the plain distributions; top_k in 1..1024: both
+// distributions shaped by top-k / top-p
 int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                           float temperature, uint64_t seed, const uint32_t* draw, const int32_t* stream_id, hipStream_t st);
-int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
-                     uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
-// the same two with both distributions shaped by top-k / top-p (top_k in 1..1024)
-int launch_spec_draft_draw_shaped(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                                  float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw,
-                                  const int32_t* stream_id, hipStream_t st);
-int launch_spec_step_shaped(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
-                            int top_k, float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag,
-                            int32_t* cand, hipStream_t st);
+                           float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
+                           hipStream_t st);
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
+                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
 
 // csrc/logit_proc.hip: logit processors (penalties, bias) on stored bf16 rows, in place; the step and the C-ABI ops run these
 size_t logit_process_workspace(int B, int R, int V);

@@ -1,4 +1,6 @@
-// Decoder forward orchestration and the draft-then-verify step for gfx950.
+// Decoder forward orchestration for gfx950: the model behind sd_model_* (create, bind, forward, prompt
+// routing, scoring, probes and plan queries). The draft-then-verify step that drives two of
+// these models is csrc/spec_loop.hip.
 //
 // Host-side C++ behind the C-ABI (include/specdec_hip.h). It enqueues the kernels
 // of gemv.hip / attention.hip / misc.hip on caller-provided HIP streams, never
@@ -7,12 +9,7 @@
 //
 // What it replaces in the reference: HFWrapper._generate_tokens_async
 // (hf_wrappers.py:272-627: one HF forward + argmax per generated token, the whole
-// prefix re-fed unless a KV cache is threaded through) and the device-facing half of
-// the step loop of SpeculativePipeline.generate_batch (pipeline.py:2306-2846: draft
-// stream / verify stream / event waits). The reference verifies by letting the base
-// model generate K tokens autoregressively (speculative_scheduler.py:192-199); here
-// the target scores all K+1 positions in ONE forward over (last, d_1..d_K), which
-// under greedy decoding yields the same accepted prefix and bonus token.
+// prefix re-fed unless a KV cache is threaded through).
 
 #include <hip/hip_runtime.h>
 
@@ -23,67 +20,6 @@
 #include <vector>
 
 #include "engine.h"
-#include "persist.h"
-#include "prefill_gemm.h"
-
-struct sd_model {
-  sd_model_config cfg;
-  std::vector<sd_layer_weights> layers;
-  // bound storage
-  uint16_t* k_cache = nullptr;
-  uint16_t* v_cache = nullptr;
-  int B = 0, Lmax = 0;
-  // paged KV (sd_model_bind_paged): k_cache / v_cache are page pools of n_pages pages per layer, Lmax = max_pages * page_len
-  const int32_t* block_table = nullptr;   // device [B][max_pages], caller-owned and caller-maintained
-  int page_shift = 0, max_pages = 0, n_pages = 0;
-  // workspace carve
-  uint16_t* x = nullptr;     // [64][d]
-  uint16_t* q = nullptr;     // [64][Hq*D]
-  uint16_t* attn = nullptr;  // [64][Hq*D]
-  uint16_t* act = nullptr;   // [64][ff]
-  int32_t* probe_pos = nullptr;  // [1] zero: position base of the QKV probe
-  float* attn_ws = nullptr;      // split-KV partial tiles (attention.hip)
-  unsigned* attn_cnt = nullptr;  // arrival counters, zero between launches
-  float* xstat = nullptr;    // [2][128][256]: row statistics handed from an EPI_RESID launch to the next norm-fused one (> 9 tokens)
-  float* part_val = nullptr; // [64][512]
-  int small_t = sd::kGemvMaxT; // tokens per pass of gemv.hip for this model's widest activation row (<= 9)
-  int max_t = sd::kGemvMaxT; // tokens per pass: 64 when every matrix of the model is covered by gemm_skinny.hip
-  int* part_idx = nullptr;
-  int head_grid = 0;         // grid of the last lm_head launch (partials per token)
-  const int32_t* skip_k = nullptr;   // set around a draft forward of the adaptive step (enqueue_step): every launch of the
-  int skip_i = 0;                    // forward returns at entry when *skip_k <= skip_i
-  std::vector<const void*> packed;  // per matrix (4 per layer + lm_head) or empty: row-major weights
-  std::vector<const float*> scales; // fp8 storage: fp32 row scales per matrix
-  const void* mat(int index, const void* row_major) const { return packed.empty() ? row_major : packed[index]; }
-  int is_packed() const { return packed.empty() ? 0 : 1; }
-  int w8() const { return scales.empty() ? 0 : 1; }
-  const float* scale(int index) const { return scales.empty() ? nullptr : scales[index]; }
-  // persistent forward (csrc/persist.hip): passes of <= persist_t tokens run as ONE launch
-  int persist_t = 0;                       // 0 = not available for this model / device
-  bool persist_taps = true;                // stage rows written by persistent passes (sd_specdec_create turns them off for its draft)
-  sd::PersistOp* p_ops = nullptr;          // device: 4 per layer + lm_head, stream order
-  unsigned long long* p_gran = nullptr;    // granule buffers, two parities
-  unsigned p_gran_parity = 0;
-  unsigned* p_sync = nullptr;              // [0] launch counter, [1] status
-  unsigned long long* p_debug = nullptr;   // optional timeline (sd_model_probe_persist)
-  void* prefill_ws = nullptr;              // lazily allocated workspace of the GEMM prefill path (csrc/prefill_gemm.hip)
-  int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
-  int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
-  sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
-  sd::PrefillRows prefill_rows;            // the last GEMM-prefill chunk's rows in prefill_ws (sd_model_prefill_rows), valid while
-  int prefill_mc = 0;                      // prefill_mc > 0: cleared by a bind and by every pass that is not such a chunk
-  void* score_ws = nullptr;                // sd_model_score: normed rows, head partials, target logits, a zero word (first call)
-  unsigned* host_status = nullptr;         // pinned host word: a persistent launch that gives up stores its reason here as well
-  int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
-  int len_hint = 0;                        // caller's bound on the rows' current lengths (sd_model_set_length_hint; default Lmax)
-  int ctx_limit = 0;                       // longest rows the persistent launch serves (kPersistMaxCtx; lifted by SPECDEC_PERSIST_MAX_T)
-  ~sd_model() {
-    if (host_status) (void)hipHostFree(host_status);
-    if (prefill_ws) (void)hipFree(prefill_ws);
-    if (score_ws) (void)hipFree(score_ws);
-    sd::native_plan_free(native_plan);
-  }
-};
 
 namespace sd {
 // One CU (three waves) walks a head's whole cache in the persistent launch, where the launch path splits long rows over up to 32
@@ -92,14 +28,12 @@ namespace sd {
 // up to this many positions (where the two lines cross: 723 + 0.161 (L - 1024) against 764 + 0.003 (L - 1024) us at L = 1283;
 // round 4's context sweep: 5.07 ms per step on the persistent launch at 1400-1536 positions against 4.96 on the launch path at 2048).
 constexpr int kPersistMaxCtx = 1280;
-static bool persist_pass_ok(const sd_model* m, int T, int Bc, int Mc) {
+bool persist_pass_ok(const sd_model* m, int T, int Bc, int Mc) {
   return m->persist_t > 0 && T <= m->persist_t && Mc <= 8 && !m->block_table && Bc * m->cfg.n_heads <= kPersistCUs && m->len_hint <= m->ctx_limit;
 }
 }  // namespace sd
 
 namespace sd {
-
-constexpr int kMaxPartials = 512;
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -118,7 +52,7 @@ static size_t workspace_bytes(const sd_model_config& c) {
 
 // Matrix `index` (4 * layer + which; 4 * n_layers = the lm_head) as the forward launches it: weights, shape and bias, the fused
 // norm, and the workspace rows it reads and writes. The caller adds what belongs to the call: tokens, positions, caches, statistics.
-static GemvArgs matrix_args(const sd_model* m, int index) {
+GemvArgs matrix_args(const sd_model* m, int index) {
   const sd_model_config& c = m->cfg;
   const int which = matrix_which(c, index);
   const MatShape sh = matrix_shape(c, which);
@@ -419,9 +353,9 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
 
 // rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are
 // indexed from row0 (element 0 of each array belongs to row row0)
-static int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base,
-                         int pos_off, int row0, int B, int M, int32_t* ids_out, int ids_stride, void* logits_out,
-                         int logits_dtype, int skip_head, hipStream_t st) {
+int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base,
+                  int pos_off, int row0, int B, int M, int32_t* ids_out, int ids_stride, void* logits_out,
+                  int logits_dtype, int skip_head, hipStream_t st) {
   SD_REQUIRE(m && m->k_cache && m->x, "forward: model not bound (sd_model_bind)");
   SD_REQUIRE(row0 >= 0 && B >= 1 && row0 + B <= m->B, "forward: rows [%d,%d) exceeds bound batch %d", row0, row0 + B, m->B);
   SD_REQUIRE(M >= 1, "forward: M=%d", M);
@@ -1309,864 +1243,3 @@ extern "C" int sd_model_probe_forward(sd_model* m, int M, int pos0, int iters, i
   }
   return 0;
 }
-
-// ---------------------------------------------------------------------------- step loop
-static constexpr int kStageInts = 24;   // per row: 8 ints of set_row, then (accepted, proposed, hist_n, k) + 4 doubles
-
-struct sd_specdec {
-  sd_model* draft = nullptr;
-  sd_model* target = nullptr;
-  int B = 0, K = 0, mode = 0;
-  SpecState st{};
-  int32_t* dev_block = nullptr;   // all device state in one allocation
-  int32_t* step_counter = nullptr; // device: steps executed (its parity selects the record slot)
-  int32_t* host_record = nullptr;  // pinned, device-accessible: [2 slots][B][rec]
-  hipEvent_t ev_done[2] = {nullptr, nullptr};   // recorded after launch i on the target stream (i & 1)
-  long launches = 0;
-  int32_t* host_stage = nullptr;  // pinned staging for set_row / set_adaptive_row: [B][kStageInts]
-  int a_initial = 0;
-  int rec = 0;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipStream_t graph_st_t = nullptr, graph_st_d = nullptr;
-  long steps = 0;
-  // sampled bonus token (sd_specdec_set_sampling); all buffers are caller-owned
-  int sample = 0;
-  float temperature = 1.0f, top_p = 1.0f;
-  int top_k = 0;
-  uint64_t seed = 0;
-  void* logits = nullptr;          // [B][K+1][V] bf16
-  uint32_t* draw = nullptr;        // [B]
-  const int32_t* stream_id = nullptr;
-  // speculative sampling (sd_specdec_set_spec_sampling): draft tokens drawn from q, accept by p/q, residual redraw. Shares
-  // temperature / seed / draw / stream_id with the sampled-bonus mode (the two are mutually exclusive).
-  int spec = 0;
-  void* spec_q = nullptr;          // [B][K][V] bf16 draft logits, caller-owned
-  void* spec_p = nullptr;          // [B][K+1][V] bf16 target logits, caller-owned; until the verify forward overwrites it, its first
-                                   // rows are where each draft forward leaves the logits of its pass ([B][M][V])
-  int32_t* spec_flags = nullptr;   // [2][B][K+1] device: accept flags, candidate next tokens
-  int spec_top_k = 0;              // sd_specdec_set_spec_shaping: > 0 = both distributions shaped by top-k / top-p
-  float spec_top_p = 1.0f;
-  // logit processors (sd_specdec_set_logit_processors): every logits row is stored, processed in place, then consumed
-  int lp = 0;
-  float lp_rp = 1.0f, lp_presence = 0.f, lp_frequency = 0.f;
-  uint16_t* lp_counts = nullptr;   // [B][V], caller-owned
-  const float* lp_bias = nullptr;  // [B][V] or null, caller-owned
-  void* lp_logits = nullptr;       // [B][K+1][V] bf16, caller-owned; used while neither sampling mode owns a buffer
-  void* lp_ws = nullptr;           // argmax partials of the process launches
-  size_t lp_ws_bytes = 0;
-  // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
-  std::vector<const void*> heads;
-  std::vector<const float*> head_scales;
-  int32_t* head_rows = nullptr;    // [B] device: row of the target's residual stream each head reads
-  size_t head_stride = 0;          // bytes between consecutive heads when they sit at a constant stride (one launch), else 0
-  // EAGLE-lite (sd_specdec_set_eagle): extrapolated hidden rows instead of a draft model; caller-owned workspace
-  bool draft_taps = false;         // the draft's persistent passes also store their stage rows (debug)
-  bool want_fwd0_select = false;   // device-selected form of draft forward 0 (storage carved at create; eligibility per capture)
-  int eagle = 0;
-  float eagle_alpha = 0.7f;
-  uint16_t* eagle_H = nullptr;     // [B*K][d]
-  uint16_t* eagle_prev = nullptr;  // [B][d] last extrapolated row of the previous step
-  int32_t* eagle_has = nullptr;    // [B]
-};
-
-namespace sd {
-
-// Argmax of n_heads vocabulary-sized matrices over T activation rows: what the Medusa step, the EAGLE step and
-// sd_model_head_argmax all run. The matrices have the lm_head's shape (and, unless `prenormed`, its final norm in front);
-// id of (matrix j, row t) -> ids[(t / M) * ids_stride + t % M + j].
-struct HeadEval {
-  const void* x = nullptr;          // bf16 rows of d_model elements (stride d_model)
-  const int32_t* x_row = nullptr;   // nullable, device [T]: row t reads row x_row[t] of x
-  int T = 0, M = 1;                 // rows, rows per batch row (the id layout; M == 1 whenever n_heads > 1)
-  int n_heads = 0;
-  const void* const* W = nullptr;          // [n_heads]
-  const float* const* scale = nullptr;     // [n_heads] fp32 row scales (w8), else null
-  size_t stride = 0;                // bytes between consecutive matrices when constant (one launch), else 0 (one launch each)
-  int packed = 1, w8 = 0;
-  bool prenormed = false;           // the rows are final-norm outputs already: PRO_NONE, no norm weights
-  int32_t* ids = nullptr;
-  int ids_stride = 0;
-  float* vals = nullptr;            // nullable: the fp32 value attached to each winning index, laid out as ids (debug entry only)
-  int* launch_info = nullptr;       // nullable, host [2]: matrix launches enqueued, 1 if the rows were gathered first (debug entry only)
-};
-
-// Matrices at a constant stride are evaluated by ONE lm_head-shaped launch (grid y = matrix: same x rows, same geometry,
-// per-matrix argmax partials) and one finalize over n_heads x T results; otherwise one launch + finalize per matrix.
-static int enqueue_head_argmax(sd_model* m, const HeadEval& e, hipStream_t st) {
-  const sd_model_config& c = m->cfg;
-  const int T = e.T, nh = e.n_heads;
-  GemvArgs h = matrix_args(m, 4 * c.n_layers);   // the lm_head's shape and final norm; the matrices' own weights below
-  h.packed = e.packed;
-  h.w8 = e.w8;
-  h.x = e.x;
-  h.x_row = e.x_row;
-  h.T = T;
-  h.M = e.M;
-  if (e.prenormed) {
-    h.prologue = PRO_NONE;
-    h.norm_w = h.norm_b = nullptr;
-    h.norm_eps = 0.f;
-  }
-  if (e.x_row && T > m->small_t) {   // more rows than a GEMV pass: gather them (the attention-output buffer is free after the verify forward)
-    if (int rc = launch_medusa_gather(e.x, e.x_row, m->attn, T, c.d_model, st)) return rc;
-    h.x = m->attn;
-    h.x_row = nullptr;
-    if (e.launch_info) e.launch_info[1] = 1;
-  }
-  int ppw = 1;
-  const int grid = gemv_grid(h, &ppw);
-  if (nh >= 2 && T <= m->small_t && e.stride && e.M == 1 &&
-      static_cast<size_t>(nh) * T * grid <= static_cast<size_t>(kSkinnyMaxT) * kMaxPartials) {
-    h.W = e.W[0];
-    h.w_scale = e.scale ? e.scale[0] : nullptr;
-    h.batch_bytes = e.stride;
-    h.n_batch = nh;
-    if (int rc = launch_gemv(h, EPI_ARGMAX, st)) return rc;
-    if (e.launch_info) e.launch_info[0] = 1;
-    // result (matrix j, row t) = "token" j * T + t of the partials -> ids[t][j]
-    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, nh * T, grid, -T, e.ids_stride, e.ids, st)) return rc;
-    if (e.vals)
-      if (int rc = launch_argmax_value(m->part_val, m->part_idx, nh * T, grid, -T, e.ids_stride, e.vals, st)) return rc;
-    return 0;
-  }
-  for (int i = 0; i < nh; ++i) {
-    h.w_scale = e.scale ? e.scale[i] : nullptr;
-    h.W = e.W[i];
-    if (int rc = launch_gemv(h, EPI_ARGMAX, st)) return rc;
-    if (e.launch_info) e.launch_info[0] += 1;
-    if (int rc = launch_argmax_finalize(m->part_val, m->part_idx, T, grid, e.M, e.ids_stride, e.ids + i, st)) return rc;
-    if (e.vals)
-      if (int rc = launch_argmax_value(m->part_val, m->part_idx, T, grid, e.M, e.ids_stride, e.vals + i, st)) return rc;
-  }
-  return 0;
-}
-
-// draft tokens of the NEXT step from the heads: d_{i+1} = argmax head_i(final_norm(h)), h = the residual row of the
-// position that produced the last emitted token -> verify_tok[b][i + 1] (enqueue_head_argmax).
-static int enqueue_medusa_heads(sd_specdec* s, hipStream_t st) {
-  sd_model* m = s->target;
-  if (int rc = launch_medusa_rows(s->st, s->head_rows, st)) return rc;
-  HeadEval e;
-  e.x = m->x;
-  e.x_row = s->head_rows;
-  e.T = s->B;
-  e.n_heads = s->K;
-  e.W = s->heads.data();
-  e.scale = s->head_scales.empty() ? nullptr : s->head_scales.data();
-  e.stride = s->head_stride;
-  e.w8 = s->head_scales.empty() ? 0 : 1;
-  e.ids = s->st.verify_tok + 1;
-  e.ids_stride = s->K + 1;
-  if (int rc = enqueue_head_argmax(m, e, st)) return rc;
-  return launch_medusa_commit(s->st, st);
-}
-
-static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
-  const int B = s->B, K = s->K;
-  const bool two = (st_d != st_t) && s->draft;
-  if (!s->draft && s->eagle) {
-    // EAGLE-lite: residual row of `last` (1-token forward, head skipped) -> K extrapolated rows -> one lm_head launch
-    sd_model* m = s->target;
-    const sd_model_config& c = m->cfg;
-    if (int rc = model_forward(m, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, 1, nullptr, 2, nullptr, SD_BF16, 1, st_t)) return rc;
-    if (int rc = launch_eagle_extrapolate(m->x, s->eagle_H, s->eagle_prev, s->eagle_has, c.final_norm_w, c.final_norm_b, c.norm_eps,
-                                          s->eagle_alpha, c.d_model, B, K, c.arch == SD_ARCH_LLAMA ? 1 : 0, st_t))
-      return rc;
-    const void* const w_head = m->mat(4 * c.n_layers, c.lm_head);
-    const float* const sc_head = m->scale(4 * c.n_layers);
-    HeadEval e;
-    e.x = s->eagle_H;
-    e.T = B * K;
-    e.M = K;
-    e.n_heads = 1;
-    e.W = &w_head;
-    e.scale = sc_head ? &sc_head : nullptr;
-    e.packed = m->is_packed();
-    e.w8 = m->w8();
-    e.prenormed = true;        // the rows are final-norm outputs already
-    e.ids = s->st.verify_tok + 1;
-    e.ids_stride = K + 1;
-    if (int rc = enqueue_head_argmax(m, e, st_t)) return rc;
-    if (int rc = launch_medusa_commit(s->st, st_t)) return rc;
-  } else if (!s->draft && s->heads.empty()) {
-    // self-draft (Medusa-lite, tied heads): the target's own next token, K times
-    if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, 1, s->st.draft_ids, 2, nullptr, SD_BF16, 0, st_t))
-      return rc;
-    if (int rc = launch_medusa_fill(s->st, st_t)) return rc;
-  }
-  if (two) {
-    SD_HIP_CHECK(hipEventRecord(s->ev_fork, st_t));
-    SD_HIP_CHECK(hipStreamWaitEvent(st_d, s->ev_fork, 0));
-  }
-  // draft: forward 0 over (prev, last) at positions cur_len-1, cur_len; then one token each
-  struct TapsGuard {   // the draft's stage taps are this loop's choice, for the duration of its forwards only
-    sd_model* m; bool saved;
-    TapsGuard(sd_model* m_, bool v) : m(m_), saved(m_ ? m_->persist_taps : false) { if (m) m->persist_taps = v; }
-    ~TapsGuard() { if (m) m->persist_taps = saved; }
-  } taps_guard(s->draft, s->draft_taps);
-  // both forms of forward 0 with the device picking one: only while the draft's 1- and 2-token passes are persistent launches
-  // (a pass that is not needed then costs one launch that returns at entry, not 80) — decided per capture, the model may have
-  // been re-bound or its persistent passes switched off since the loop was created
-  const bool fwd0_select = s->draft && s->st.fwd0_w && B == 1 && persist_pass_ok(s->draft, 2, 1, 2);
-  // a draft forward that is ONE pass leaves the lm_head partials of all its tokens in the model's workspace: ids and the hand-over
-  // of d_{i+1} are then one launch (draft_finalize_kernel) instead of two
-  const bool one_pass_d = s->draft && B * 2 <= s->draft->max_t;
-  const auto finalize = [&](int M, int i, int32_t* ids, const int32_t* skip_k, int skip_i) -> int {
-    if (one_pass_d)
-      return launch_draft_finalize(s->draft->part_val, s->draft->part_idx, s->draft->head_grid, M, i, ids, s->st, skip_k, skip_i, st_d);
-    return 0;
-  };
-  // speculative sampling: every draft forward stores its logits, d_{i+1} is DRAWN from the last position's row (no argmax ids)
-  const bool spec = s->spec != 0;
-  const int V = s->target->cfg.vocab;
-  // logit processors: the forwards store their rows (into the buffer of the sampling mode that is on, else the mode's own), the
-  // rows are processed in place and the argmax of the processed row replaces the fused one
-  const bool lp = s->lp != 0;
-  void* const p_buf = s->sample ? s->logits : (spec ? s->spec_p : (lp ? s->lp_logits : nullptr));
-  SD_REQUIRE(!lp || (s->draft && p_buf), "specdec_step: logit processors need a draft model and a logits buffer (sd_specdec_set_logit_processors)");
-  uint16_t* const q_pass = (spec || lp) ? static_cast<uint16_t*>(p_buf) : nullptr;   // (the verify forward overwrites it afterwards)
-  int32_t* const ids_d = (one_pass_d || spec || lp) ? nullptr : s->st.draft_ids;
-  // draft forward i left the logits of its M positions in q_pass: process row M - 1 of every batch row with d_1..d_i
-  const auto process_draft = [&](int M, int i) -> int {
-    if (int rc = launch_logit_process(q_pass + static_cast<size_t>(M - 1) * V, static_cast<long long>(M) * V, B, 1, V, s->lp_counts, s->lp_bias,
-                                      s->st.draft_tok, K, i, s->st.active, s->lp_rp, s->lp_presence, s->lp_frequency,
-                                      spec ? nullptr : s->st.draft_ids + (M - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d))
-      return rc;
-    return spec ? 0 : launch_draft_next(M, i, s->st, st_d);
-  };
-  for (int i = 0; s->draft && i < K; ++i) {
-    const int M = (i == 0) ? 2 : 1;
-    const int32_t* toks = (i == 0) ? s->st.tok2 : s->st.next_tok;
-    const int off = (i == 0) ? -1 : i;
-    // per-row adaptive K: forward i >= 1 only matters while some row proposes more than i tokens
-    s->draft->skip_k = (s->st.adaptive && i >= 1) ? s->st.k_active : nullptr;
-    s->draft->skip_i = i;
-    int rc_f;
-    if (i == 0 && fwd0_select) {
-      // both forms of forward 0, the device picks (SpecState::fwd0_w, written by accept_kernel): the 2-token pass, then the
-      // 1-token pass over `last` alone, whose id lands where the 2-token pass leaves its second one
-      s->draft->skip_k = s->st.fwd0_w;
-      s->draft->skip_i = 1;
-      rc_f = model_forward(s->draft, toks, 2, s->st.cur_len, -1, 0, B, 2, ids_d, 2, q_pass, SD_BF16, 0, st_d);
-      if (!rc_f && !spec && !lp) rc_f = finalize(2, 0, s->st.draft_ids, s->st.fwd0_w, 1);
-      if (!rc_f) {
-        s->draft->skip_k = s->st.fwd0_w + 1;
-        // (the 1-token form's logits row lands where the 2-token form leaves its second one, as its id does)
-        rc_f = model_forward(s->draft, toks + 1, 2, s->st.cur_len, 0, 0, B, 1, ids_d ? ids_d + 1 : nullptr, 2, q_pass ? q_pass + V : nullptr,
-                             SD_BF16, 0, st_d);
-      }
-      if (!rc_f && !spec && !lp) rc_f = finalize(1, 0, s->st.draft_ids + 1, s->st.fwd0_w + 1, 1);
-    } else {
-      rc_f = model_forward(s->draft, toks, M, s->st.cur_len, off, 0, B, M, ids_d, 2, q_pass, SD_BF16, 0, st_d);
-      if (!rc_f && !spec && !lp) rc_f = finalize(M, i, s->st.draft_ids, s->draft->skip_k, i);
-    }
-    s->draft->skip_k = nullptr;
-    if (rc_f) return rc_f;
-    if (lp)   // (exactly one form of forward 0 ran; both leave the last position's row in the same place)
-      if (int rc = process_draft(M, i)) return rc;
-    if (spec && s->spec_top_k > 0) {
-      if (int rc = launch_spec_draft_draw_shaped(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->spec_top_k, s->spec_top_p,
-                                                 s->seed, s->draw, s->stream_id, st_d))
-        return rc;
-    } else if (spec) {   // exactly one form of forward 0 ran: one draw launch serves both
-      if (int rc = launch_spec_draft_draw(s->st, q_pass, M, M - 1, s->spec_q, i, V, s->temperature, s->seed, s->draw, s->stream_id, st_d)) return rc;
-    } else if (!one_pass_d && !lp) {
-      if (int rc = launch_draft_next(M, i, s->st, st_d)) return rc;
-    }
-  }
-  if (two) {
-    SD_HIP_CHECK(hipEventRecord(s->ev_join, st_d));
-    SD_HIP_CHECK(hipStreamWaitEvent(st_t, s->ev_join, 0));
-  }
-  // verify: one forward over (last, d_1..d_K)
-  // greedy steps whose verify forward is ONE pass: ids, accept scan, state advance and the step record are one launch over the
-  // lm_head's partials (verify_tail_kernel) instead of three
-  const unsigned* const st_word_d = (s->draft && s->draft->p_sync) ? s->draft->p_sync + 1 : nullptr;
-  const unsigned* const st_word_t = s->target->p_sync ? s->target->p_sync + 1 : nullptr;
-  const bool tail = !s->sample && !spec && !lp && verify_tail_fits(s->st) && B * (K + 1) <= s->target->max_t;
-  if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, K + 1, tail ? nullptr : s->st.target_ids,
-                             K + 1, p_buf, SD_BF16, 0, st_t))
-    return rc;
-  if (lp)   // all B * (K+1) rows in one launch: row (b, i) is conditioned on d_1..d_i; the processed argmax replaces the fused ids
-    if (int rc = launch_logit_process(p_buf, V, B, K + 1, V, s->lp_counts, s->lp_bias, s->st.draft_tok, K, -1, s->st.active, s->lp_rp,
-                                      s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t))
-      return rc;
-  if (tail) {
-    if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
-                                    s->step_counter, st_word_d, st_word_t, st_t))
-      return rc;
-    if (!s->heads.empty())
-      if (int rc = enqueue_medusa_heads(s, st_t)) return rc;
-    return 0;
-  }
-  if (s->sample) {
-    // accept length -> draw the token after the accepted prefix from the stored logits of that position
-    if (int rc = launch_accept_len(s->st, st_t)) return rc;
-    if (int rc = launch_sample_step(s->st, s->logits, s->target->cfg.vocab, s->temperature, s->top_k, s->top_p, s->seed,
-                                    s->draw, s->stream_id, st_t))
-      return rc;
-  }
-  if (spec && s->spec_top_k > 0) {
-    if (int rc = launch_spec_step_shaped(s->st, s->spec_p, s->spec_q, V, s->temperature, s->spec_top_k, s->spec_top_p, s->seed, s->draw,
-                                         s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
-      return rc;
-  } else if (spec) {
-    // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
-    if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, s->seed, s->draw, s->stream_id, s->spec_flags,
-                                  s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
-      return rc;
-  }
-  if (int rc = launch_accept(s->st, s->mode, spec ? 2 : s->sample, st_t)) return rc;
-  if (lp)   // the emitted tokens of every active row enter its counts
-    if (int rc = launch_logit_counts_add(s->lp_counts, B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
-  if (int rc = launch_pack_record(s->st, s->host_record, s->rec, s->step_counter, st_word_d, st_word_t, st_t)) return rc;
-  // persistent Medusa heads: the proposals of the next step, after the record of this one has left
-  if (!s->heads.empty())
-    if (int rc = enqueue_medusa_heads(s, st_t)) return rc;
-  return 0;
-}
-
-}  // namespace sd
-
-extern "C" int sd_specdec_create(sd_model* draft, sd_model* target, int B, int K, int emit_mode, sd_specdec** out) {
-  clear_error();
-  SD_REQUIRE(target && out, "specdec_create: NULL argument");   // draft == NULL: self-draft (Medusa-lite, tied heads)
-  SD_REQUIRE(B >= 1 && K >= 1 && K <= 8, "specdec_create: B=%d K=%d (K in 1..8)", B, K);
-  SD_REQUIRE(B * (K + 1) <= 65535, "specdec_create: batch too large");
-  SD_REQUIRE((!draft || draft->B >= B) && target->B >= B, "specdec_create: models must be bound with batch >= %d", B);
-  SD_REQUIRE(!draft || draft->cfg.vocab == target->cfg.vocab, "specdec_create: draft/target vocabularies differ");
-  SD_REQUIRE(emit_mode == SD_EMIT_BONUS || emit_mode == SD_EMIT_DRAFT, "specdec_create: emit_mode %d", emit_mode);
-  // verify of B rows must fit the passes of the target forward: any B works (tiled)
-  sd_specdec* s = new (std::nothrow) sd_specdec();
-  SD_REQUIRE(s, "specdec_create: out of memory");
-  s->draft = draft;
-  s->target = target;
-  // nobody reads the hidden rows of a loop's draft: its persistent passes skip the stage taps (csrc/persist.hip, TAPS). The
-  // choice belongs to the LOOP (enqueue_step sets it around the draft's forwards): the same model object used elsewhere — as a
-  // standalone model, or as another loop's target — keeps its taps.
-  s->draft_taps = getenv(debug_env::kPersistTaps) != nullptr;
-  s->B = B;
-  s->K = K;
-  s->mode = emit_mode;
-  s->rec = 7 + 3 * K;
-  const size_t n_state = static_cast<size_t>(B) * (1 + 1 + 2 + 1 + 2 + K + (K + 1) + (K + 1) + 1 + 1 + (K + 1) + 1);
-  const size_t n_adapt = static_cast<size_t>(B) * (1 + 4 + 8) + 2 + 2 + 2;   // k_row, ctl, ctl_hist (doubles), k_active (+ alignment), fwd0_w
-  const size_t n_total = n_state + 4 + n_adapt;
-  hipError_t e = hipMalloc(&s->dev_block, n_total * sizeof(int32_t));
-  if (e != hipSuccess) {
-    delete s;
-    SD_REQUIRE(false, "specdec_create: hipMalloc failed: %s", hipGetErrorString(e));
-  }
-  (void)hipMemset(s->dev_block, 0, n_total * sizeof(int32_t));
-  int32_t* p = s->dev_block;
-  SpecState& st = s->st;
-  st.B = B;
-  st.K = K;
-  st.cur_len = p; p += B;
-  st.active = p; p += B;
-  st.tok2 = p; p += 2 * B;
-  st.next_tok = p; p += B;
-  st.draft_ids = p; p += 2 * B;
-  st.draft_tok = p; p += static_cast<size_t>(B) * K;
-  st.verify_tok = p; p += static_cast<size_t>(B) * (K + 1);
-  st.target_ids = p; p += static_cast<size_t>(B) * (K + 1);
-  st.accept_len = p; p += B;
-  st.n_new = p; p += B;
-  st.new_tok = p; p += static_cast<size_t>(B) * (K + 1);
-  st.sampled = p; p += B;
-  s->step_counter = p; p += 4;
-  if ((p - s->dev_block) & 1) ++p;         // the doubles below: 8-byte aligned (hipMalloc is 256-byte aligned)
-  st.ctl_hist = reinterpret_cast<double*>(p); p += static_cast<size_t>(B) * 8;
-  st.ctl = p; p += static_cast<size_t>(B) * 4;
-  st.k_row = p; p += B;
-  st.k_active = p; p += 1;
-  st.adaptive = 0;
-  // device-selected form of draft forward 0: one sequence, a draft whose 1- and 2-token passes are persistent launches (a pass
-  // that is not needed then costs one launch that returns at entry, not 80)
-  st.fwd0_w = nullptr;
-  if (draft && B == 1 && draft->persist_cap >= 2 && !getenv(debug_env::kNoFwd0Select)) {
-    st.fwd0_w = p; p += 2;
-    const int32_t init[2] = {2, 1};
-    (void)hipMemcpy(st.fwd0_w, init, sizeof(init), hipMemcpyHostToDevice);
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&s->host_record), sizeof(int32_t) * 2 * B * s->rec, hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_done[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_done[1], hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->host_stage), sizeof(int32_t) * (B * kStageInts + 4), hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess) {
-    sd_specdec_destroy(s);
-    SD_REQUIRE(false, "specdec_create: pinned memory / event creation failed");
-  }
-  *out = s;
-  return 0;
-}
-
-extern "C" int sd_specdec_destroy(sd_specdec* s) {
-  if (!s) return 0;
-  if (s->exec) (void)hipGraphExecDestroy(s->exec);
-  if (s->graph) (void)hipGraphDestroy(s->graph);
-  if (s->ev_done[0]) (void)hipEventDestroy(s->ev_done[0]);
-  if (s->ev_done[1]) (void)hipEventDestroy(s->ev_done[1]);
-  if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-  if (s->ev_join) (void)hipEventDestroy(s->ev_join);
-  if (s->host_record) (void)hipHostFree(s->host_record);
-  if (s->host_stage) (void)hipHostFree(s->host_stage);
-  if (s->dev_block) (void)hipFree(s->dev_block);
-  if (s->head_rows) (void)hipFree(s->head_rows);
-  if (s->spec_flags) (void)hipFree(s->spec_flags);
-  delete s;
-  return 0;
-}
-
-extern "C" int sd_specdec_set_row(sd_specdec* s, int b, int seq_len, int prev_tok, int last_tok, int active,
-                                  void* stream) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_row: NULL");
-  SD_REQUIRE(b >= 0 && b < s->B, "specdec_set_row: row %d out of range", b);
-  SD_REQUIRE(seq_len >= 1, "specdec_set_row: seq_len=%d (need at least one token)", seq_len);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // the staging slot of row b must not be rewritten while a previous copy is in flight
-  SD_HIP_CHECK(hipStreamSynchronize(st));
-  int32_t* h = s->host_stage + b * kStageInts;
-  h[0] = seq_len - 1;  // cur_len: position of `last`
-  h[1] = active ? 1 : 0;
-  h[2] = prev_tok;
-  h[3] = last_tok;
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.cur_len + b, h + 0, 4, hipMemcpyHostToDevice, st));
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.active + b, h + 1, 4, hipMemcpyHostToDevice, st));
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.tok2 + 2 * b, h + 2, 8, hipMemcpyHostToDevice, st));
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.verify_tok + static_cast<size_t>(b) * (s->K + 1), h + 3, 4, hipMemcpyHostToDevice, st));
-  if (s->st.fwd0_w) {   // whatever the caller did to the caches: the next step recomputes prev's K/V
-    h[4] = 2;
-    h[5] = 1;
-    SD_HIP_CHECK(hipMemcpyAsync(s->st.fwd0_w, h + 4, 8, hipMemcpyHostToDevice, st));
-  }
-  return 0;
-}
-
-// Per-row adaptive K. The captured step keeps the shape K = max_k; row b's proposals past k_row[b]
-// do not count (accept length clamped, bonus token = the target's token after the clamped prefix), and accept_kernel
-// moves k_row[b] by the reference's rule. enable: all rows restart (k = initial_k, history = [0.0] — the reference's
-// first get_k call reports acceptance_rate 0.0 before any step).
-extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k, int min_k, int max_k, int step_size,
-                                       double target_rate, void* stream) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_adaptive: NULL");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (s->exec) {   // the captured kernels hold the loop state by value
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  if (!enable) {
-    s->st.adaptive = 0;
-    return 0;
-  }
-  SD_REQUIRE(min_k >= 1 && min_k <= max_k && max_k <= s->K, "specdec_set_adaptive: need 1 <= min_k (%d) <= max_k (%d) <= K of the loop (%d)", min_k, max_k, s->K);
-  SD_REQUIRE(initial_k >= min_k && initial_k <= max_k, "specdec_set_adaptive: initial_k %d outside [%d, %d]", initial_k, min_k, max_k);
-  SD_REQUIRE(step_size >= 1, "specdec_set_adaptive: step_size %d", step_size);
-  SD_REQUIRE(target_rate == target_rate, "specdec_set_adaptive: target rate is NaN");
-  SD_REQUIRE(s->heads.empty() && !s->eagle, "specdec_set_adaptive: stateful draft modes keep a fixed K");
-  SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
-  SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
-  s->st.adaptive = 1;
-  s->st.a_min = min_k;
-  s->st.a_max = max_k;
-  s->st.a_step = step_size;
-  s->st.a_hi = target_rate + 0.1;
-  s->st.a_lo = target_rate - 0.1;
-  s->a_initial = initial_k;
-  for (int b = 0; b < s->B; ++b)
-    if (int rc = sd_specdec_set_adaptive_row(s, b, initial_k, 0, 0, 1, nullptr, st)) return rc;
-  return 0;
-}
-
-// (Re)write one row's controller state — a new sequence in the row's slot, or the host's in-order view after the host
-// rules overrode steps that were launched ahead. hist: hist_n <= 4 rates, oldest first (NULL: [0.0]).
-extern "C" int sd_specdec_set_adaptive_row(sd_specdec* s, int b, int k, int accepted, int proposed, int hist_n, const double* hist,
-                                           void* stream) {
-  clear_error();
-  SD_REQUIRE(s && s->st.adaptive, "specdec_set_adaptive_row: adaptive K is not enabled");
-  SD_REQUIRE(b >= 0 && b < s->B, "specdec_set_adaptive_row: row %d out of range", b);
-  SD_REQUIRE(k >= s->st.a_min && k <= s->st.a_max, "specdec_set_adaptive_row: k=%d outside [%d, %d]", k, s->st.a_min, s->st.a_max);
-  SD_REQUIRE(hist_n >= 0 && hist_n <= 4 && accepted >= 0 && proposed >= 0, "specdec_set_adaptive_row: bad counters");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  SD_HIP_CHECK(hipStreamSynchronize(st));   // the staging slot must not be rewritten under a copy in flight
-  int32_t* h = s->host_stage + b * kStageInts + 8;
-  double* hd = reinterpret_cast<double*>(h + 4);
-  h[0] = accepted;
-  h[1] = proposed;
-  h[2] = hist ? hist_n : 1;
-  h[3] = k;
-  for (int i = 0; i < 4; ++i) hd[i] = (hist && i < hist_n) ? hist[i] : 0.0;
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.ctl + 4 * b, h, 16, hipMemcpyHostToDevice, st));
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.ctl_hist + 4 * b, hd, 32, hipMemcpyHostToDevice, st));
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.k_row + b, h + 3, 4, hipMemcpyHostToDevice, st));
-  // k_active (which draft forwards run) is recomputed at the end of every step; until then: all of them
-  int32_t* ka = s->host_stage + s->B * kStageInts;
-  *ka = s->st.a_max;
-  SD_HIP_CHECK(hipMemcpyAsync(s->st.k_active, ka, 4, hipMemcpyHostToDevice, st));
-  return 0;
-}
-
-extern "C" int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperature, int top_k, float top_p,
-                                       uint64_t seed, void* logits_buf, size_t logits_bytes, uint32_t* draw_counters,
-                                       const int32_t* stream_ids) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_sampling: NULL");
-  if (s->exec) {  // the captured step holds the sampling launches and their parameters
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  if (!enable) {
-    s->sample = 0;
-    return 0;
-  }
-  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_sampling: only the bonus-token emit mode (generate_batch) samples");
-  SD_REQUIRE(!s->spec, "specdec_set_sampling: speculative sampling is enabled (sd_specdec_set_spec_sampling); the two modes are mutually exclusive");
-  SD_REQUIRE(logits_buf && draw_counters, "specdec_set_sampling: NULL logits buffer / draw counters");
-  const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * s->target->cfg.vocab * 2;
-  SD_REQUIRE(logits_bytes >= need, "specdec_set_sampling: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need);
-  SD_REQUIRE(temperature == temperature && temperature >= 0.f, "specdec_set_sampling: temperature %g", temperature);
-  SD_REQUIRE(top_k <= 0 || (top_k < s->target->cfg.vocab ? top_k : s->target->cfg.vocab) <= 1024, "specdec_set_sampling: top_k=%d > 1024", top_k);
-  s->sample = 1;
-  s->temperature = temperature;
-  s->top_k = top_k;
-  s->top_p = top_p;
-  s->seed = seed;
-  s->logits = logits_buf;
-  s->draw = draw_counters;
-  s->stream_id = stream_ids;
-  return 0;
-}
-
-extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float temperature, uint64_t seed, void* draft_logits_buf,
-                                            size_t draft_logits_bytes, void* target_logits_buf, size_t target_logits_bytes,
-                                            uint32_t* draw_counters, const int32_t* stream_ids) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_spec_sampling: NULL");
-  if (!enable) {
-    if (s->spec && s->exec) {
-      (void)hipGraphExecDestroy(s->exec);
-      (void)hipGraphDestroy(s->graph);
-      s->exec = nullptr;
-      s->graph = nullptr;
-    }
-    s->spec = 0;
-    return 0;
-  }
-  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_spec_sampling: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
-  SD_REQUIRE(s->draft, "specdec_set_spec_sampling: needs a draft model (self-draft, Medusa heads and EAGLE loops propose without a distribution q)");
-  SD_REQUIRE(!s->st.adaptive, "specdec_set_spec_sampling: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
-  SD_REQUIRE(!s->sample, "specdec_set_spec_sampling: the sampled-bonus mode is enabled (sd_specdec_set_sampling); the two modes are mutually exclusive");
-  SD_REQUIRE(temperature == temperature && temperature > 0.f, "specdec_set_spec_sampling: temperature %g (must be > 0)", temperature);
-  SD_REQUIRE(draft_logits_buf && target_logits_buf && draw_counters, "specdec_set_spec_sampling: NULL logits buffer / draw counters");
-  const size_t V = static_cast<size_t>(s->target->cfg.vocab);
-  const size_t need_q = static_cast<size_t>(s->B) * s->K * V * 2, need_p = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
-  SD_REQUIRE(draft_logits_bytes >= need_q, "specdec_set_spec_sampling: draft logits buffer %zu B < %zu B ([B][K][V] bf16)", draft_logits_bytes, need_q);
-  SD_REQUIRE(target_logits_bytes >= need_p, "specdec_set_spec_sampling: target logits buffer %zu B < %zu B ([B][K+1][V] bf16)", target_logits_bytes, need_p);
-  SD_REQUIRE(((reinterpret_cast<uintptr_t>(draft_logits_buf) | reinterpret_cast<uintptr_t>(target_logits_buf)) & 15) == 0,
-             "specdec_set_spec_sampling: logits buffers must be 16-byte aligned");
-  if (!s->spec_flags) SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->spec_flags), sizeof(int32_t) * 2 * s->B * (s->K + 1)));
-  if (s->exec) {  // the captured step holds the other mode's launches, or this mode's parameters
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  s->spec = 1;
-  s->temperature = temperature;
-  s->seed = seed;
-  s->spec_q = draft_logits_buf;
-  s->spec_p = target_logits_buf;
-  s->draw = draw_counters;
-  s->stream_id = stream_ids;
-  return 0;
-}
-
-extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float repetition_penalty, float presence_penalty,
-                                               float frequency_penalty, void* counts, size_t counts_bytes, const float* bias,
-                                               size_t bias_bytes, void* logits_buf, size_t logits_bytes, void* workspace,
-                                               size_t workspace_bytes_) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_logit_processors: NULL");
-  if (!enable) {
-    if (s->lp && s->exec) {
-      (void)hipGraphExecDestroy(s->exec);
-      (void)hipGraphDestroy(s->graph);
-      s->exec = nullptr;
-      s->graph = nullptr;
-    }
-    s->lp = 0;
-    return 0;
-  }
-  SD_REQUIRE(s->draft, "specdec_set_logit_processors: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
-  SD_REQUIRE(!s->st.adaptive, "specdec_set_logit_processors: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
-  SD_REQUIRE(repetition_penalty == repetition_penalty && repetition_penalty > 0.f,
-             "specdec_set_logit_processors: repetition_penalty %g (must be > 0)", repetition_penalty);
-  SD_REQUIRE(presence_penalty - presence_penalty == 0.f && frequency_penalty - frequency_penalty == 0.f,
-             "specdec_set_logit_processors: presence_penalty %g / frequency_penalty %g must be finite", presence_penalty, frequency_penalty);
-  const size_t V = static_cast<size_t>(s->target->cfg.vocab), BV = static_cast<size_t>(s->B) * V;
-  SD_REQUIRE(counts && counts_bytes >= BV * 2, "specdec_set_logit_processors: counts buffer %zu B < %zu B ([B][V] uint16)", counts_bytes, BV * 2);
-  SD_REQUIRE(!bias || bias_bytes >= BV * 4, "specdec_set_logit_processors: bias buffer %zu B < %zu B ([B][V] float32)", bias_bytes, BV * 4);
-  const size_t need_p = BV * (s->K + 1) * 2, need_ws = logit_process_workspace(s->B, s->K + 1, static_cast<int>(V));
-  SD_REQUIRE(logits_buf || s->sample || s->spec, "specdec_set_logit_processors: NULL logits buffer (no sampling mode is on to lend its own)");
-  SD_REQUIRE(!logits_buf || logits_bytes >= need_p, "specdec_set_logit_processors: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need_p);
-  SD_REQUIRE(workspace && workspace_bytes_ >= need_ws, "specdec_set_logit_processors: workspace %zu B < %zu B", workspace_bytes_, need_ws);
-  SD_REQUIRE(((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(logits_buf) |
-               reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "specdec_set_logit_processors: buffers must be 16-byte aligned");
-  if (s->exec) {  // the captured step holds the unprocessed launches, or this mode's parameters
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  s->lp = 1;
-  s->lp_rp = repetition_penalty;
-  s->lp_presence = presence_penalty;
-  s->lp_frequency = frequency_penalty;
-  s->lp_counts = static_cast<uint16_t*>(counts);
-  s->lp_bias = bias;
-  s->lp_logits = logits_buf;
-  s->lp_ws = workspace;
-  s->lp_ws_bytes = workspace_bytes_;
-  return 0;
-}
-
-extern "C" int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p) {
-  clear_error();
-  SD_REQUIRE(top_p == top_p && top_p > 0.f, "specdec_set_spec_shaping: top_p %g (must be > 0)", top_p);
-  SD_REQUIRE(top_k > 0 || top_p >= 1.0f, "specdec_set_spec_shaping: top_p = %g without top_k (the full-vocabulary nucleus) is not supported; "
-             "give a top_k in 1..1024", top_p);
-  SD_REQUIRE(top_k <= 1024, "specdec_set_spec_shaping: top_k=%d > 1024 is not supported", top_k);
-  SD_REQUIRE(s, "specdec_set_spec_shaping: NULL");
-  if (s->exec) {  // the captured step holds the launches of the other shape
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  s->spec_top_k = top_k > 0 ? top_k : 0;
-  s->spec_top_p = top_k > 0 ? top_p : 1.0f;
-  return 0;
-}
-
-extern "C" size_t sd_specdec_eagle_bytes(int B, int K, int d_model) {
-  if (B <= 0 || K <= 0 || d_model <= 0) return 0;
-  return (static_cast<size_t>(B) * K * d_model + static_cast<size_t>(B) * d_model) * 2 + static_cast<size_t>(B) * 4 + 1024;
-}
-
-// workspace layout: [state rows B x d bf16][has_prev B x int32][extrapolated rows B*K x d bf16] — the state sits at
-// offsets that do not depend on K, so loops of different K over the same workspace (adaptive K) share it
-extern "C" int sd_specdec_set_eagle(sd_specdec* s, float alpha, void* workspace, size_t workspace_bytes_) {
-  clear_error();
-  SD_REQUIRE(s && workspace, "specdec_set_eagle: NULL argument");
-  SD_REQUIRE(!s->draft, "specdec_set_eagle: the loop was created with a draft model (pass draft = NULL)");
-  SD_REQUIRE(s->heads.empty(), "specdec_set_eagle: the loop already has Medusa heads");
-  const int d = s->target->cfg.d_model;
-  SD_REQUIRE(workspace_bytes_ >= sd_specdec_eagle_bytes(s->B, s->K, d), "specdec_set_eagle: workspace too small");
-  SD_REQUIRE(s->B * s->K <= s->target->max_t, "specdec_set_eagle: B*K = %d rows exceed one lm_head pass (%d)", s->B * s->K, s->target->max_t);
-  SD_REQUIRE(!s->exec, "specdec_set_eagle: call before the first captured step");
-  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  s->eagle_prev = reinterpret_cast<uint16_t*>(p);
-  p += (static_cast<size_t>(s->B) * d * 2 + 255) & ~static_cast<size_t>(255);
-  s->eagle_has = reinterpret_cast<int32_t*>(p);
-  p += (static_cast<size_t>(s->B) * 4 + 255) & ~static_cast<size_t>(255);
-  s->eagle_H = reinterpret_cast<uint16_t*>(p);
-  s->eagle_alpha = alpha;
-  s->eagle = 1;
-  return 0;
-}
-
-extern "C" int sd_specdec_reset_eagle(sd_specdec* s, void* stream) {
-  clear_error();
-  SD_REQUIRE(s && s->eagle, "specdec_reset_eagle: EAGLE mode is not set");
-  SD_HIP_CHECK(hipMemsetAsync(s->eagle_has, 0, static_cast<size_t>(s->B) * 4, static_cast<hipStream_t>(stream)));
-  return 0;
-}
-
-// bytes between consecutive heads when they sit at a constant, ascending stride (-> one launch for all of them), else 0
-static size_t constant_stride(int n_heads, const void* const* packed_heads) {
-  if (n_heads < 2) return 0;
-  const char* h0 = static_cast<const char*>(packed_heads[0]);
-  const char* h1 = static_cast<const char*>(packed_heads[1]);
-  bool even = h1 > h0;
-  for (int i = 2; even && i < n_heads; ++i)
-    even = static_cast<const char*>(packed_heads[i]) - static_cast<const char*>(packed_heads[i - 1]) == h1 - h0;
-  return even ? static_cast<size_t>(h1 - h0) : 0;
-}
-
-extern "C" int sd_specdec_set_medusa(sd_specdec* s, int n_heads, const void* const* packed_heads, int weight_dtype) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_set_medusa: NULL");
-  SD_REQUIRE(!s->draft, "specdec_set_medusa: the loop was created with a draft model (pass draft = NULL)");
-  SD_REQUIRE(n_heads == s->K && packed_heads, "specdec_set_medusa: need K = %d heads, got %d", s->K, n_heads);
-  SD_REQUIRE(weight_dtype == SD_BF16 || weight_dtype == SD_FP8_E4M3, "specdec_set_medusa: weight_dtype %d", weight_dtype);
-  const sd_model_config& c = s->target->cfg;
-  SD_REQUIRE(s->B <= s->target->small_t || (s->B <= s->target->max_t && c.n_heads * c.head_dim >= c.d_model),
-             "specdec_set_medusa: batch %d exceeds one pass of the head kernels (%d rows)", s->B, s->target->max_t);
-  SD_REQUIRE(s->B * (s->K + 1) <= s->target->max_t, "specdec_set_medusa: the verify pass must be a single pass (B*(K+1) = %d > %d)",
-             s->B * (s->K + 1), s->target->max_t);
-  if (s->exec) {
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  s->heads.clear();
-  s->head_scales.clear();
-  for (int i = 0; i < n_heads; ++i) {
-    SD_REQUIRE(packed_heads[i], "specdec_set_medusa: head %d is NULL", i);
-    s->heads.push_back(packed_heads[i]);
-    if (weight_dtype == SD_FP8_E4M3) {
-      const MatShape h = matrix_shape(c, 4);   // the fp32 row scales follow the packed bytes (sd_pack_head)
-      s->head_scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + packed_fp8_weight_bytes(h.n_pairs, h.K)));
-    }
-  }
-  s->head_stride = getenv(debug_env::kMedusaPerHead) ? 0 : constant_stride(n_heads, packed_heads);
-  if (!s->head_rows) SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->head_rows), sizeof(int32_t) * s->B));
-  return 0;
-}
-
-// The step's head evaluation (enqueue_head_argmax) on caller-supplied rows: ids and the value attached to each of them.
-extern "C" int sd_model_head_argmax(sd_model* m, const void* x_bf16, int n_rows, const int32_t* row_idx, int B, int n_heads,
-                                    const void* const* packed_heads, int weight_dtype, int flags, int32_t* ids, float* vals,
-                                    int* launch_info, void* stream) {
-  clear_error();
-  SD_REQUIRE(m && m->x && x_bf16 && packed_heads && ids, "model_head_argmax: NULL argument / model not bound");
-  SD_REQUIRE(n_heads >= 1 && n_heads <= 64, "model_head_argmax: n_heads=%d (1..64)", n_heads);
-  SD_REQUIRE(weight_dtype == SD_BF16 || weight_dtype == SD_FP8_E4M3, "model_head_argmax: weight_dtype %d", weight_dtype);
-  SD_REQUIRE((flags & ~(SD_HEADS_PER_HEAD | SD_HEADS_NORMALISED)) == 0, "model_head_argmax: unknown flags %#x", flags);
-  const sd_model_config& c = m->cfg;
-  SD_REQUIRE(weight_dtype == SD_BF16 || c.d_model % 64 == 0, "model_head_argmax: fp8 heads need d_model (%d) in whole 64-k steps", c.d_model);
-  SD_REQUIRE(B >= 1 && n_rows >= 1 && (row_idx || B <= n_rows), "model_head_argmax: B=%d rows of %d", B, n_rows);
-  SD_REQUIRE(B <= m->small_t || (B <= m->max_t && (!row_idx || c.n_heads * c.head_dim >= c.d_model)),
-             "model_head_argmax: batch %d exceeds one pass of the head kernels (%d rows)", B, m->max_t);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (row_idx) {   // a debug entry: the indices are checked on the host before any kernel follows them
-    std::vector<int32_t> host(static_cast<size_t>(B));
-    SD_HIP_CHECK(hipMemcpyAsync(host.data(), row_idx, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-    SD_HIP_CHECK(hipStreamSynchronize(st));
-    for (int b = 0; b < B; ++b)
-      SD_REQUIRE(host[b] >= 0 && host[b] < n_rows, "model_head_argmax: row_idx[%d] = %d outside the %d rows", b, host[b], n_rows);
-  }
-  std::vector<const void*> heads;
-  std::vector<const float*> scales;
-  const MatShape hs = matrix_shape(c, 4);
-  for (int i = 0; i < n_heads; ++i) {
-    SD_REQUIRE(packed_heads[i], "model_head_argmax: head %d is NULL", i);
-    SD_REQUIRE((reinterpret_cast<uintptr_t>(packed_heads[i]) & 255) == 0, "model_head_argmax: head %d is not 256-byte aligned", i);
-    heads.push_back(packed_heads[i]);
-    if (weight_dtype == SD_FP8_E4M3)   // the fp32 row scales follow the packed bytes (sd_pack_head)
-      scales.push_back(reinterpret_cast<const float*>(static_cast<const char*>(packed_heads[i]) + packed_fp8_weight_bytes(hs.n_pairs, hs.K)));
-  }
-  HeadEval e;
-  e.x = x_bf16;
-  e.x_row = row_idx;
-  e.T = B;
-  e.n_heads = n_heads;
-  e.W = heads.data();
-  e.scale = scales.empty() ? nullptr : scales.data();
-  e.stride = (flags & SD_HEADS_PER_HEAD) ? 0 : constant_stride(n_heads, packed_heads);
-  e.w8 = scales.empty() ? 0 : 1;
-  e.prenormed = (flags & SD_HEADS_NORMALISED) != 0;
-  e.ids = ids;
-  e.ids_stride = n_heads;
-  e.vals = vals;
-  if (launch_info) launch_info[0] = launch_info[1] = 0;
-  e.launch_info = launch_info;
-  return enqueue_head_argmax(m, e, st);
-}
-
-extern "C" int sd_eagle_extrapolate(const void* x_bf16, void* H, void* prev, int32_t* has_prev, const void* norm_w, const void* norm_b,
-                                    float eps, float alpha, int d_model, int B, int K, int rms, void* stream) {
-  clear_error();
-  SD_REQUIRE(x_bf16 && H && prev && has_prev && norm_w, "eagle_extrapolate: NULL argument");
-  SD_REQUIRE(rms || norm_b, "eagle_extrapolate: LayerNorm needs the bias");
-  SD_REQUIRE(d_model >= 1 && B >= 1 && B <= 65535 && K >= 1 && K <= 8, "eagle_extrapolate: d_model=%d B=%d K=%d (K in 1..8)", d_model, B, K);
-  return launch_eagle_extrapolate(x_bf16, H, prev, has_prev, norm_w, norm_b, eps, alpha, d_model, B, K, rms ? 1 : 0,
-                                  static_cast<hipStream_t>(stream));
-}
-
-extern "C" int sd_specdec_step(sd_specdec* s, void* stream_target, void* stream_draft, int use_graph) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_step: NULL");
-  hipStream_t st_t = static_cast<hipStream_t>(stream_target);
-  hipStream_t st_d = stream_draft ? static_cast<hipStream_t>(stream_draft) : st_t;
-  s->steps++;
-  if (!use_graph || s->steps == 1) {
-    // the first step always runs eagerly: it also performs the one-time kernel
-    // attribute setup that must not happen inside a capture
-    if (int rc = enqueue_step(s, st_t, st_d)) return rc;
-    SD_HIP_CHECK(hipEventRecord(s->ev_done[s->launches & 1], st_t));
-    s->launches++;
-    return 0;
-  }
-  if (s->exec && (s->graph_st_t != st_t || s->graph_st_d != st_d)) {
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  if (!s->exec) {
-    SD_HIP_CHECK(hipStreamBeginCapture(st_t, hipStreamCaptureModeRelaxed));
-    const int rc = enqueue_step(s, st_t, st_d);
-    hipGraph_t g = nullptr;
-    const hipError_t ee = hipStreamEndCapture(st_t, &g);
-    if (rc != 0) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    SD_HIP_CHECK(ee);
-    s->graph = g;
-    SD_HIP_CHECK(hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-    s->graph_st_t = st_t;
-    s->graph_st_d = st_d;
-  }
-  SD_HIP_CHECK(hipGraphLaunch(s->exec, st_t));
-  SD_HIP_CHECK(hipEventRecord(s->ev_done[s->launches & 1], st_t));   // completion of THIS step (sd_specdec_wait)
-  s->launches++;
-  return 0;
-}
-
-extern "C" int sd_specdec_invalidate(sd_specdec* s) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_invalidate: NULL");
-  if (s->exec) {
-    (void)hipGraphExecDestroy(s->exec);
-    (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-  }
-  s->steps = 0;   // the next step runs eagerly (kernels of the other path may still need their one-time attribute setup)
-  return 0;
-}
-
-extern "C" long sd_specdec_launches(const sd_specdec* s) { return s ? s->launches : 0; }
-
-extern "C" int sd_specdec_wait(sd_specdec* s, long launch_index) {
-  clear_error();
-  SD_REQUIRE(s, "specdec_wait: NULL");
-  SD_REQUIRE(launch_index >= 0 && launch_index < s->launches && launch_index + 2 >= s->launches,
-             "specdec_wait: step %ld is not one of the last two launches (%ld launched)", launch_index, s->launches);
-  SD_HIP_CHECK(hipEventSynchronize(s->ev_done[launch_index & 1]));
-  return 0;
-}
-
-extern "C" int sd_specdec_sync(sd_specdec* s, void* stream) {
-  clear_error();
-  (void)s;
-  SD_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-  return 0;
-}
-
-// two slots of [B][record_ints]: the record of launch i is in slot i & 1
-extern "C" const int32_t* sd_specdec_record(const sd_specdec* s) { return s ? s->host_record : nullptr; }
-
-extern "C" int sd_specdec_record_ints(const sd_specdec* s) { return s ? s->rec : 0; }

@@ -375,7 +375,7 @@ __device__ __forceinline__ void accept_row(const SpecState& s, int b, int lane, 
     s.accept_len[b] = a;
     s.n_new[b] = n_new;
     if (s.fwd0_w && b == 0) {
-      // Next step's draft forward 0 (engine.hip enqueue_step). New `prev` sits at old cur_len + n_new - 1. Bonus mode: that is
+      // Next step's draft forward 0 (spec_loop.hip enqueue_draft). New `prev` sits at old cur_len + n_new - 1. Bonus mode: that is
       // d_a (a >= 1; an input of draft forward a, which ran iff a < k) or the old `last` (a == 0; forward 0's input): its K/V
       // are in the draft cache unless a == k. Draft-emit mode: prev is d_{a-1} or the old `last`: always there.
       const int k_eff = s.adaptive ? s.k_row[b] : K;   // (before this step's controller update)

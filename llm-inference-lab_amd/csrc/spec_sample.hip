@@ -195,11 +195,8 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const S
   }
 }
 
-int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                           float temperature, uint64_t seed, const uint32_t* draw, const int32_t* stream_id, hipStream_t st) {
-  SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
-  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
-             "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, float temperature,
+                                   uint64_t seed, const uint32_t* draw, const int32_t* stream_id) {
   SpecDrawArgs a{};
   a.src = static_cast<const uint16_t*>(src);
   a.src_rows_per_b = src_rows_per_b;
@@ -212,9 +209,7 @@ int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per
   a.seed_hi = static_cast<uint32_t>(seed >> 32);
   a.draw = draw;
   a.stream_id = stream_id;
-  hipLaunchKernelGGL(spec_draft_draw_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, s);
-  SD_LAUNCH_CHECK();
-  return 0;
+  return a;
 }
 
 // ---------------------------------------------------------------------------------- per-position statistics and candidate
@@ -342,36 +337,27 @@ __global__ __launch_bounds__(kWave) void spec_accept_kernel(const SpecAcceptArgs
   }
 }
 
-static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, hipStream_t st) {
-  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1, "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
-  SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
-  hipLaunchKernelGGL(spec_stats_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa);
-  SD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
-  SD_LAUNCH_CHECK();
-  return 0;
-}
-
-// the step's statistics + accept: accept length -> s.accept_len, next token -> s.sampled, counters advanced
-int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
-                     uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st) {
-  SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
+// flag / cand: [B][K+1] each; the step passes draw0 = 0 and no ratios, the stand-alone ops their caller's
+static SpecStatArgs spec_stat_args(const void* target_logits, const void* draft_logits, const int32_t* draft_ids, int K, int V,
+                                   float temperature, uint64_t seed, const uint32_t* draw, uint32_t draw0, const int32_t* stream_id,
+                                   const int32_t* active, int32_t* flag, int32_t* cand, double* ratios) {
   SpecStatArgs sa{};
   sa.P = static_cast<const uint16_t*>(target_logits);
   sa.Q = static_cast<const uint16_t*>(draft_logits);
-  sa.draft_ids = s.draft_tok;
-  sa.K = s.K;
+  sa.draft_ids = draft_ids;
+  sa.K = K;
   sa.V = V;
   sa.temperature = temperature;
   sa.seed_lo = static_cast<uint32_t>(seed);
   sa.seed_hi = static_cast<uint32_t>(seed >> 32);
   sa.draw = draw;
+  sa.draw0 = draw0;
   sa.stream_id = stream_id;
-  sa.active = s.active;
+  sa.active = active;
   sa.flag = flag;
   sa.cand = cand;
-  SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
-  return launch_spec_kernels(sa, aa, s.B, st);
+  sa.ratios = ratios;
+  return sa;
 }
 
 // ------------------------------------------------------------------------------------------ shaped variant (top-k / top-p)
@@ -411,26 +397,22 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(
   }
 }
 
-int launch_spec_draft_draw_shaped(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                                  float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw,
-                                  const int32_t* stream_id, hipStream_t st) {
+// the draw + hand-over after a draft forward; top_k == 0: spec_draft_draw_kernel, else the shaped kernel
+int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
+                           float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
+                           hipStream_t st) {
   SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
-  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
-             "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
-  if (int rc = check_spec_shape("spec_draft_draw", top_k, top_p)) return rc;
-  SpecDrawArgs a{};
-  a.src = static_cast<const uint16_t*>(src);
-  a.src_rows_per_b = src_rows_per_b;
-  a.src_row = src_row;
-  a.q = static_cast<uint16_t*>(q);
-  a.i = i;
-  a.V = V;
-  a.temperature = temperature;
-  a.seed_lo = static_cast<uint32_t>(seed);
-  a.seed_hi = static_cast<uint32_t>(seed >> 32);
-  a.draw = draw;
-  a.stream_id = stream_id;
-  hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{top_k, top_p}, s);
+  const SpecDrawArgs a = spec_draw_args(src, src_rows_per_b, src_row, q, i, V, temperature, seed, draw, stream_id);
+  if (top_k > 0) {
+    SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
+               "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+    if (int rc = check_spec_shape("spec_draft_draw", top_k, top_p)) return rc;
+    hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{top_k, top_p}, s);
+  } else {
+    SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
+               "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+    hipLaunchKernelGGL(spec_draft_draw_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, s);
+  }
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -503,38 +485,34 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const
   }
 }
 
-static int launch_spec_kernels_shaped(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st) {
-  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && sa.V <= (1 << kIdxBits),
-             "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+// statistics, then accept; top_k == 0: spec_stats_kernel, else the shaped kernel
+static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st) {
+  if (top_k > 0)
+    SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && sa.V <= (1 << kIdxBits),
+               "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+  else
+    SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1, "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
   SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
-  if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
-  hipLaunchKernelGGL(spec_stats_shaped_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, SpecShape{top_k, top_p});
+  if (top_k > 0) {
+    if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
+    hipLaunchKernelGGL(spec_stats_shaped_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, SpecShape{top_k, top_p});
+  } else {
+    hipLaunchKernelGGL(spec_stats_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa);
+  }
   SD_LAUNCH_CHECK();
   hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
   SD_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_spec_step_shaped(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature,
-                            int top_k, float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag,
-                            int32_t* cand, hipStream_t st) {
+// the step's statistics + accept: accept length -> s.accept_len, next token -> s.sampled, counters advanced
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
+                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st) {
   SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
-  SpecStatArgs sa{};
-  sa.P = static_cast<const uint16_t*>(target_logits);
-  sa.Q = static_cast<const uint16_t*>(draft_logits);
-  sa.draft_ids = s.draft_tok;
-  sa.K = s.K;
-  sa.V = V;
-  sa.temperature = temperature;
-  sa.seed_lo = static_cast<uint32_t>(seed);
-  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
-  sa.draw = draw;
-  sa.stream_id = stream_id;
-  sa.active = s.active;
-  sa.flag = flag;
-  sa.cand = cand;
-  SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
-  return launch_spec_kernels_shaped(sa, aa, s.B, top_k, top_p, st);
+  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, s.draft_tok, s.K, V, temperature, seed, draw, 0, stream_id, s.active,
+                                         flag, cand, nullptr);
+  const SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
+  return launch_spec_kernels(sa, aa, s.B, top_k, top_p, st);
 }
 
 }  // namespace sd
@@ -559,24 +537,10 @@ extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* targe
              "spec_sample_accept: misaligned workspace / ratios");
   int32_t* flag = static_cast<int32_t*>(workspace);
   int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
-  SpecStatArgs sa{};
-  sa.P = static_cast<const uint16_t*>(target_logits);
-  sa.Q = static_cast<const uint16_t*>(draft_logits);
-  sa.draft_ids = draft_ids;
-  sa.K = K;
-  sa.V = V;
-  sa.temperature = temperature;
-  sa.seed_lo = static_cast<uint32_t>(seed);
-  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
-  sa.draw = draw_counters;
-  sa.draw0 = draw0;
-  sa.stream_id = stream_ids;
-  sa.active = active;
-  sa.flag = flag;
-  sa.cand = cand;
-  sa.ratios = ratios_out;
-  SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels(sa, aa, B, static_cast<hipStream_t>(stream));
+  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
+                                         active, flag, cand, ratios_out);
+  const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
+  return launch_spec_kernels(sa, aa, B, 0, 1.0f, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
@@ -597,22 +561,8 @@ extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void
              "spec_sample_accept_shaped: misaligned workspace / ratios");
   int32_t* flag = static_cast<int32_t*>(workspace);
   int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
-  SpecStatArgs sa{};
-  sa.P = static_cast<const uint16_t*>(target_logits);
-  sa.Q = static_cast<const uint16_t*>(draft_logits);
-  sa.draft_ids = draft_ids;
-  sa.K = K;
-  sa.V = V;
-  sa.temperature = temperature;
-  sa.seed_lo = static_cast<uint32_t>(seed);
-  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
-  sa.draw = draw_counters;
-  sa.draw0 = draw0;
-  sa.stream_id = stream_ids;
-  sa.active = active;
-  sa.flag = flag;
-  sa.cand = cand;
-  sa.ratios = ratios_out;
-  SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels_shaped(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
+  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
+                                         active, flag, cand, ratios_out);
+  const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
+  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
 }

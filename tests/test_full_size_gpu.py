@@ -105,7 +105,7 @@ def test_fp8_storage_at_full_size_multi_token_passes():
 def test_device_selected_first_draft_forward_changes_nothing(full_pair, monkeypatch):
     """One sequence with a persistent draft: the captured step holds draft forward 0 twice — the 2-token pass over (prev, last)
     and the 1-token pass over `last` — and the device runs the one the previous step's accept length calls for
-    (engine.hip enqueue_step, misc.hip accept_kernel: prev's K/V are missing from the draft cache only after a fully accepted
+    (spec_loop.hip enqueue_step, misc.hip accept_kernel: prev's K/V are missing from the draft cache only after a fully accepted
     step). The proposals must not depend on it: same tokens, same step count, same proposed / accepted counters as with the
     selection switched off (always the 2-token pass), over a run that contains fully and partly accepted steps."""
     from src.specdec import SpeculativePipeline

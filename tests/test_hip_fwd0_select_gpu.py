@@ -1,4 +1,4 @@
-"""Device-selected draft forward 0 (engine.hip enqueue_step / misc.hip accept_kernel) against the CPU oracle.
+"""Device-selected draft forward 0 (spec_loop.hip enqueue_step / misc.hip accept_kernel) against the CPU oracle.
 
 With one sequence and a draft whose 1- and 2-token passes are persistent launches, the captured step holds draft forward 0 in
 two forms — the 2-token pass over (prev, last) and the 1-token pass over `last` — and accept_kernel writes which one the next

@@ -3,7 +3,7 @@
 Speculative decoding is lossless: a wrong draft token never changes the text, it only lowers `accepted`, so the
 token-equality tests of the pipeline (engineered margins: the right logit ~ d, every other ~ sqrt(d)) cannot see a head
 kernel that lost a K slice or read another head's scales. Here the step's own head evaluation (sd_model_head_argmax: one
-function with the Medusa and EAGLE steps, csrc/engine.hip enqueue_head_argmax) and the EAGLE extrapolation launch
+function with the Medusa and EAGLE steps, csrc/spec_loop.hip enqueue_head_argmax) and the EAGLE extrapolation launch
 (sd_eagle_extrapolate) run on N(0, 0.02) heads and random rows, and are checked with tests/stage_ref.py:
 
   heads   for every (head, row): the value the kernel attached to its id is that id's fp64 logit within the derived bound, and
