@@ -702,6 +702,55 @@ int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float repetition_
                                     float frequency_penalty, void* counts, size_t counts_bytes, const float* bias, size_t bias_bytes,
                                     void* logits_buf, size_t logits_bytes, void* workspace, size_t workspace_bytes);
 
+/* Grammar-constrained decoding (csrc/grammar.hip; the compiler from regular expressions and answer lists is
+ * specdec_hip/grammar.py): a token automaton whose mask is one more line of the transform above. Tables, caller-owned device
+ * memory, 16-byte aligned:
+ *   next  : uint16 [S][V], 1 <= S <= 65534; next[s][v] = the state after token v in state s, 0xFFFF = v is not allowed in s.
+ *   allow : uint32 [S][ceil(V / 32)] (sd_fsm_mask_bytes: rounded up to 16 bytes); bit v % 32 of word v / 32 = next[s][v] !=
+ *           0xFFFF, pad bits 0. sd_fsm_build_masks builds it on the device from `next`: one source of truth.
+ *   state : int32 [B]; -1 = the row is unconstrained, 0..S-1 = its state, anything else = DEAD (the kernels store DEAD as
+ *           0xFFFF). step(s, t) = DEAD if s is DEAD, t is outside [0, V) or next[s][t] is 0xFFFF or >= S; else next[s][t].
+ * The transform of a row of batch row b conditioned on the in-step tokens t_1..t_n gains, after the bias line and instead of
+ * the plain rounding:
+ *   if state[b] >= 0:  s = step(..step(state[b], t_1).., t_n)
+ *                      allowed(v) = (s is DEAD) ? v == eos_id : bit v of allow[s]
+ *                      if not allowed(v):  row[v] = 0xff80 (-inf), whatever x is: the mask overrides a NaN
+ *   else, and for an allowed v:  row[v] = bf16(x) as above (a NaN is stored as 0x7fc0)
+ * so a +inf bias at a disallowed id gives -inf, and a row at -1 is processed exactly as sd_logit_process processes it.
+ *
+ * sd_logit_process_fsm: the arguments of sd_logit_process, then the tables, S, the rows' states and eos_id. Same launch
+ * geometry, same argmax, same refusals; the mask is folded into the kernel (on the 16-byte path a lane's 8 elements are one
+ * byte of the mask row), no launch is added. Each workgroup walks its row's tokens from state[b] (n <= 64 dependent lookups;
+ * the step below chains instead). Further refused: NULL or misaligned tables, NULL state, S outside 1..65534, eos_id outside
+ * [0, V).
+ *
+ * sd_fsm_advance: for every row with active[b] != 0 (nullable) and state[b] >= 0, state[b] <- step over the first
+ * min(n_new[b], max_new) tokens of tokens + b * tok_stride (a -1 padding inside that range leads to DEAD, as any id outside
+ * the vocabulary does); one lane per row, no atomics. */
+size_t sd_fsm_mask_bytes(int S, int V);
+int sd_fsm_build_masks(const void* next, int S, int V, void* allow, size_t allow_bytes, void* stream);
+int sd_fsm_advance(const void* next, int S, int V, int32_t* fsm_state, int B, const int32_t* tokens, int tok_stride,
+                   const int32_t* n_new, int max_new, const int32_t* active, void* stream);
+int sd_logit_process_fsm(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
+                         const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float repetition_penalty,
+                         float presence_penalty, float frequency_penalty, int32_t* ids_out, int ids_stride, void* workspace,
+                         size_t workspace_bytes, const void* next, const void* allow, int S, const int32_t* fsm_state, int eos_id,
+                         void* stream);
+
+/* The grammar inside the step: with enable = 1 every process launch of the logit-processor stage also applies the mask, row
+ * (b, i) in the state reached from fsm_state[b] over the step's own d_1..d_i, so the draft proposes and the target emits only
+ * tokens the automaton allows. The launch after draft forward i finds the state after d_1..d_{i-1} in a position table of the
+ * loop ([B][K+1], written by workgroup 0 of the launch before it) and does one lookup; each workgroup of verify row (b, i)
+ * reads entry i - 1 and does the one lookup it is ahead of: no serial walk, no spin-wait, no atomics, no grid barrier. After
+ * the accept kernel fsm_state advances over the emitted tokens of every active row (sd_fsm_advance), next to the counts. The
+ * caller sets fsm_state[b] to the row's start state before its first step and repairs it like the counts when it voids steps
+ * that ran ahead. All sampling modes work unchanged: a masked token has probability 0 in p and q alike. enable = 0 unbinds
+ * (the step is launch for launch the stage without a grammar); switching the stage off unbinds too. Either call drops the
+ * captured graph. Refused: the logit-processor stage off; S outside 1..65534; eos_id outside [0, V); NULL or misaligned
+ * tables (16 bytes); per-row adaptive K; loops without a draft model (self-draft, Medusa heads, EAGLE). Additive
+ * (SD_ABI_VERSION stays 1). */
+int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* next, const void* allow, int S, int32_t* fsm_state, int eos_id);
+
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,
  * which the reference applies to one K for the whole batch from the host, pipeline.py:1994-2014). The loop keeps the
@@ -788,6 +837,10 @@ int sd_specdec_step(sd_specdec* s, void* stream_target, void* stream_draft, int 
  * the host may keep a second step queued behind the running one (the device advances its own state) and still read
  * the record of the older one — slot (index & 1) of sd_specdec_record. */
 long sd_specdec_launches(const sd_specdec* s);
+/* Nodes of the captured step's graph (kernel launches and the event nodes of the two-stream fork and join); 0 while no step is
+ * captured, -1 if the runtime refuses the query. Host-only, additive (SD_ABI_VERSION stays 1): tests compare the step's launch
+ * count between modes with it. */
+long sd_specdec_graph_nodes(const sd_specdec* s);
 int sd_specdec_wait(sd_specdec* s, long launch_index);
 
 /* Drop the captured step (its kernels were chosen at capture time: after sd_model_set_persist_tokens /

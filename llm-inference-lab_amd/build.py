@@ -64,6 +64,8 @@ FILE_FLAGS = {
     # csrc/logit_proc.hip promises one correctly rounded fp32 operation per line of its formula (a numpy float32 restatement
     # reproduces the bits): no multiply-add contraction
     "logit_proc.hip": ["-O3", "-ffp-contract=off"],
+    # csrc/grammar.hip extends that transform (its mask line sits in logit_proc.hip's kernel): built the same way
+    "grammar.hip": ["-O3", "-ffp-contract=off"],
 }
 
 

@@ -140,11 +140,39 @@ int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per
 int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
                      float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
 
-// csrc/logit_proc.hip: logit processors (penalties, bias) on stored bf16 rows, in place; the step and the C-ABI ops run these
+// csrc/grammar.hip: token automata (grammar-constrained decoding). next: uint16 [S][V], 0xFFFF = the token is not allowed in the
+// state; allow: the same as one bit per token, uint32 [S][ceil(V / 32)]. A row's state: -1 unconstrained, 0..S-1, else DEAD
+// (only eos is allowed; kept as kFsmDead).
+constexpr int kFsmDead = 0xFFFF;
+constexpr int kFsmMaxStates = 65534;
+constexpr uint16_t kBf16NegInf = 0xff80u;
+struct FsmBind {
+  const uint16_t* next;
+  const uint32_t* allow;
+  int S;
+  const int32_t* state;   // [B]
+  int eos_id;
+  int32_t* pos;           // nullable [B][pos_stride]: the state after the row's first n in-step tokens at [b][n] (the step's chain)
+  int pos_stride;
+};
+__device__ __forceinline__ int fsm_step(const uint16_t* next, int S, int V, int s, int tok) {
+  if (s < 0) return -1;
+  if (s >= S || tok < 0 || tok >= V) return kFsmDead;
+  const int nx = next[static_cast<size_t>(s) * V + tok];
+  return nx >= S ? kFsmDead : nx;
+}
+size_t fsm_mask_bytes(int S, int V);
+int launch_fsm_build_masks(const uint16_t* next, int S, int V, uint32_t* allow, size_t allow_bytes, hipStream_t st);
+int launch_fsm_advance(const uint16_t* next, int S, int V, int32_t* fsm_state, int B, const int32_t* tokens, int tok_stride,
+                       const int32_t* n_new, int max_new, const int32_t* active, hipStream_t st);
+
+// csrc/logit_proc.hip: logit processors (penalties, bias) on stored bf16 rows, in place; the step and the C-ABI ops run these.
+// fsm (nullable): the grammar line, folded into the same launch
 size_t logit_process_workspace(int B, int R, int V);
 int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
                          const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
-                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st);
+                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
+                         const FsmBind* fsm = nullptr);
 int launch_logit_counts_set(uint16_t* counts, int B, int V, int b, const int32_t* prompt, int n_prompt, const int32_t* gen, int n_gen,
                             hipStream_t st);
 int launch_logit_counts_add(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,

@@ -14,6 +14,8 @@
 //   if c > 0:             x = x - presence;  x = x - (frequency * float(c))
 //   if bias:              x = x + bias[b][v]
 //   row[v] = bf16(x)      (round to nearest even; a NaN is stored as 0x7fc0)
+// With a grammar bound (csrc/grammar.hip; logit_process_kernel<true>) one more line follows the bias: an element the row's
+// automaton state does not allow is stored as -inf whatever x is, a NaN too (the contract is at sd_logit_process_fsm).
 //
 // Why in place: every consumer of a stored row (the sampler, the speculative-sampling statistics, the draws, the agreement
 // op) defines its contract on the stored bf16 values; processing the stored row keeps all of them word for word.
@@ -59,7 +61,27 @@ struct LogitProcArgs {
   float rp, presence, frequency;
   float* part_val;           // nullable: argmax partials [B * R][gridDim.x]
   int* part_idx;
+  FsmBind fsm;               // the grammar line (logit_process_kernel<true> only)
 };
+
+// The state a row's mask is taken from: batch row b's automaton state after its n in-step tokens. With a position table
+// (the step) launch n finds the state after n - 1 tokens where launch n - 1 left it and does the one missing lookup; without
+// one (the stand-alone op) it walks. Both read the tokens from memory: the caller is one thread, ahead of the workgroup's barrier.
+__device__ __forceinline__ int lp_fsm_state(const LogitProcArgs& a, int b, int n) {
+  const FsmBind& f = a.fsm;
+  int s = f.state[b];
+  const int32_t* tk = a.tokens + static_cast<size_t>(b) * a.tok_stride;
+  if (f.pos && n >= 1) {
+    // the row's own state (is it constrained at all), the chained state and the token go out together; one dependent lookup
+    // follows. (The entry of an unconstrained row holds -1, which fsm_step passes through without a lookup.)
+    const int nx = fsm_step(f.next, f.S, a.V, f.pos[static_cast<size_t>(b) * f.pos_stride + n - 1], tk[n - 1]);
+    return s < 0 ? -1 : nx;
+  }
+  if (s < 0) return -1;
+  if (s >= f.S) s = kFsmDead;
+  for (int j = 0; j < n; ++j) s = fsm_step(f.next, f.S, a.V, s, tk[j]);
+  return s;
+}
 
 __device__ __forceinline__ uint16_t lp_element(float x, uint32_t cnt, int v, bool has_bias, float bias, const int* toks, int n,
                                                const LogitProcArgs& a) {
@@ -75,8 +97,12 @@ __device__ __forceinline__ uint16_t lp_element(float x, uint32_t cnt, int v, boo
   return (x != x) ? static_cast<uint16_t>(0x7fc0u) : float_to_bf16_bits(x);
 }
 
+// FSM: the grammar line after the bias — an element the row's automaton state does not allow is stored as -inf, whatever
+// the lines above made of it (a NaN too). The <false> instantiation is the kernel without a grammar, instruction for instruction.
+template <bool FSM>
 __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitProcArgs a) {
   __shared__ int toks[kLpMaxTokens];
+  __shared__ int fsm_s;
   __shared__ float sv[kLpThreads / kWave];
   __shared__ int si[kLpThreads / kWave];
   const int t = blockIdx.y, tid = threadIdx.x, V = a.V, S = gridDim.x, x0 = blockIdx.x;
@@ -85,7 +111,17 @@ __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitPr
   int n = a.n_tokens < 0 ? r : a.n_tokens;
   n = (act && a.tokens) ? (n > kLpMaxTokens ? kLpMaxTokens : n) : 0;
   if (tid < n) toks[tid] = a.tokens[static_cast<size_t>(b) * a.tok_stride + tid];
+  if (FSM && tid == 0) {
+    const int s = act ? lp_fsm_state(a, b, n) : -1;
+    fsm_s = s;
+    // the draft forwards' launches (one row per batch row, n tokens each) leave the state for launch n + 1 and the verify
+    if (act && a.fsm.pos && a.n_tokens >= 0 && x0 == 0) a.fsm.pos[static_cast<size_t>(b) * a.fsm.pos_stride + n] = s;
+  }
   __syncthreads();
+  const int fs = FSM ? fsm_s : -1;   // -1: no mask; kFsmDead: only eos; else row fs of the mask table
+  const bool dead = fs == kFsmDead;
+  const int eos = a.fsm.eos_id;
+  const uint32_t* allow = (FSM && fs >= 0 && !dead) ? a.fsm.allow + static_cast<size_t>(fs) * ((V + 31) >> 5) : nullptr;
   uint16_t* row = a.rows + static_cast<size_t>(t) * a.row_stride;
   const uint16_t* cnt = a.counts + static_cast<size_t>(b) * V;
   const float* bias = a.bias ? a.bias + static_cast<size_t>(b) * V : nullptr;
@@ -96,6 +132,7 @@ __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitPr
     uint16_t w = row[v];
     if (act) {
       w = lp_element(bf16_bits_to_float(w), cnt[v], v, has_bias, has_bias ? bias[v] : 0.f, toks, n, a);
+      if (FSM && fs >= 0 && !(dead ? v == eos : ((allow[v >> 5] >> (v & 31)) & 1u) != 0)) w = kBf16NegInf;
       row[v] = w;
     }
     const float f = bf16_bits_to_float(w);
@@ -125,6 +162,14 @@ __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitPr
           const uint16_t lo = lp_element(__uint_as_float(w[j] << 16), c[j] & 0xffffu, 8 * g + 2 * j, has_bias, bb[2 * j], toks, n, a);
           const uint16_t hi = lp_element(__uint_as_float(w[j] & 0xffff0000u), c[j] >> 16, 8 * g + 2 * j + 1, has_bias, bb[2 * j + 1], toks, n, a);
           w[j] = static_cast<uint32_t>(lo) | (static_cast<uint32_t>(hi) << 16);
+        }
+        if (FSM && fs >= 0) {   // the lane's 8 elements are byte g of the state's mask row
+          const uint32_t m = dead ? ((eos >> 3) == g ? 1u << (eos & 7) : 0u) : reinterpret_cast<const uint8_t*>(allow)[g];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (!((m >> (2 * j)) & 1u)) w[j] = (w[j] & 0xffff0000u) | kBf16NegInf;
+            if (!((m >> (2 * j + 1)) & 1u)) w[j] = (w[j] & 0x0000ffffu) | (static_cast<uint32_t>(kBf16NegInf) << 16);
+          }
         }
         row4[g] = make_uint4(w[0], w[1], w[2], w[3]);
       }
@@ -162,7 +207,8 @@ size_t logit_process_workspace(int B, int R, int V) {
 
 int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
                          const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
-                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
+                         const FsmBind* fsm) {
   SD_REQUIRE(rows && counts, "logit_process: NULL rows / counts");
   SD_REQUIRE(B >= 1 && R >= 1 && V >= 1 && static_cast<long long>(B) * R <= 65535, "logit_process: B=%d R=%d V=%d out of range", B, R, V);
   SD_REQUIRE(row_stride >= V, "logit_process: row stride %lld < V=%d", row_stride, V);
@@ -196,7 +242,21 @@ int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, 
     a.part_val = static_cast<float*>(workspace);
     a.part_idx = reinterpret_cast<int*>(a.part_val + static_cast<size_t>(B) * R * S);
   }
-  hipLaunchKernelGGL(logit_process_kernel, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+  if (fsm) {
+    SD_REQUIRE(fsm->next && fsm->allow && fsm->state, "logit_process: NULL automaton table / mask table / state");
+    SD_REQUIRE(fsm->S >= 1 && fsm->S <= kFsmMaxStates, "logit_process: S=%d states (1..%d)", fsm->S, kFsmMaxStates);
+    SD_REQUIRE(fsm->eos_id >= 0 && fsm->eos_id < V, "logit_process: eos_id %d outside [0, %d)", fsm->eos_id, V);
+    SD_REQUIRE(((reinterpret_cast<uintptr_t>(fsm->next) | reinterpret_cast<uintptr_t>(fsm->allow)) & 15) == 0,
+               "logit_process: automaton and mask tables must be 16-byte aligned");
+    // with a position table: n_tokens >= 0 reads [b][n_tokens - 1] and writes [b][n_tokens] (one row per batch row, or two
+    // workgroups would write one word); n_tokens < 0 reads [b][r - 1]
+    SD_REQUIRE(!fsm->pos || (n_tokens >= 0 ? (R == 1 && fsm->pos_stride > n_tokens) : fsm->pos_stride >= n_max),
+               "logit_process: position table of stride %d for R=%d rows of %d tokens", fsm->pos_stride, R, n_tokens);
+    a.fsm = *fsm;
+    hipLaunchKernelGGL(logit_process_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(logit_process_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+  }
   SD_LAUNCH_CHECK();
   if (ids_out) return launch_argmax_finalize(a.part_val, a.part_idx, B * R, S, R, ids_stride, ids_out, st);
   return 0;
@@ -272,7 +332,7 @@ extern "C" int sd_logit_process(void* rows, int64_t row_stride, int B, int R, in
   clear_error();
   return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
                               repetition_penalty, presence_penalty, frequency_penalty, ids_out, ids_stride, workspace, workspace_bytes,
-                              static_cast<hipStream_t>(stream));
+                              static_cast<hipStream_t>(stream), nullptr);
 }
 
 extern "C" size_t sd_logit_counts_bytes(int B, int V) {

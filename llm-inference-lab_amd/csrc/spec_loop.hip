@@ -68,6 +68,10 @@ struct sd_specdec {
   void* lp_logits = nullptr;       // [B][K+1][V] bf16, caller-owned; used while neither sampling mode owns a buffer
   void* lp_ws = nullptr;           // argmax partials of the process launches
   size_t lp_ws_bytes = 0;
+  // grammar (sd_specdec_set_grammar): one more line of the processors' transform; tables and per-row state are caller-owned
+  int fsm = 0;
+  sd::FsmBind fsm_bind{};          // pos: [B][K+1], the loop's own (allocated at first use)
+  int32_t* fsm_pos = nullptr;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -299,7 +303,8 @@ static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, i
   if (p.lp)   // the forward left the logits of its positions in q_pass: process row rows - 1 of every batch row with d_1..d_i
     if (int rc = launch_logit_process(p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V, s->lp_counts,
                                       s->lp_bias, s->st.draft_tok, s->K, i, s->st.active, s->lp_rp, s->lp_presence, s->lp_frequency,
-                                      p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d))
+                                      p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d,
+                                      s->fsm ? &s->fsm_bind : nullptr))
       return rc;
   if (p.hand == HAND_DRAW)
     return launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p,
@@ -350,7 +355,8 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
     return rc;
   if (p.lp)   // all B * (K+1) rows in one launch: row (b, i) is conditioned on d_1..d_i; the processed argmax replaces the fused ids
     if (int rc = launch_logit_process(p.p_buf, V, B, K + 1, V, s->lp_counts, s->lp_bias, s->st.draft_tok, K, -1, s->st.active, s->lp_rp,
-                                      s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t))
+                                      s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t,
+                                      s->fsm ? &s->fsm_bind : nullptr))
       return rc;
   if (p.tail) {
     if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
@@ -371,6 +377,10 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
     if (int rc = launch_accept(s->st, s->mode, use_sampled, st_t)) return rc;
     if (p.lp)   // the emitted tokens of every active row enter its counts
       if (int rc = launch_logit_counts_add(s->lp_counts, B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
+    if (p.lp && s->fsm)   // and advance its automaton state
+      if (int rc = launch_fsm_advance(s->fsm_bind.next, s->fsm_bind.S, V, const_cast<int32_t*>(s->fsm_bind.state), B, s->st.new_tok, K + 1,
+                                      s->st.n_new, K + 1, s->st.active, st_t))
+        return rc;
     if (int rc = launch_pack_record(s->st, s->host_record, s->rec, s->step_counter, st_word_d, st_word_t, st_t)) return rc;
   }
   // persistent Medusa heads: the proposals of the next step, after the record of this one has left
@@ -496,6 +506,7 @@ extern "C" int sd_specdec_destroy(sd_specdec* s) {
   if (s->dev_block) (void)hipFree(s->dev_block);
   if (s->head_rows) (void)hipFree(s->head_rows);
   if (s->spec_flags) (void)hipFree(s->spec_flags);
+  if (s->fsm_pos) (void)hipFree(s->fsm_pos);
   delete s;
   return 0;
 }
@@ -658,6 +669,7 @@ extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float 
   if (!enable) {
     if (s->lp) drop_graph(s);   // only if the mode was on: otherwise the captured step holds none of it
     s->lp = 0;
+    s->fsm = 0;                 // the grammar is a line of this stage
     return 0;
   }
   SD_REQUIRE(s->draft, "specdec_set_logit_processors: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
@@ -685,6 +697,38 @@ extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float 
   s->lp_logits = logits_buf;
   s->lp_ws = workspace;
   s->lp_ws_bytes = workspace_bytes_;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* next, const void* allow, int S, int32_t* fsm_state, int eos_id) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_grammar: NULL");
+  if (!enable) {
+    if (s->fsm) drop_graph(s);   // only if a grammar was bound: otherwise the captured step holds none of it
+    s->fsm = 0;
+    return 0;
+  }
+  SD_REQUIRE(s->draft, "specdec_set_grammar: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_grammar: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(s->lp, "specdec_set_grammar: the logit-processor stage is off (sd_specdec_set_logit_processors first; identity penalties will do)");
+  SD_REQUIRE(S >= 1 && S <= kFsmMaxStates, "specdec_set_grammar: S=%d states (1..%d)", S, kFsmMaxStates);
+  SD_REQUIRE(eos_id >= 0 && eos_id < s->target->cfg.vocab, "specdec_set_grammar: eos_id %d outside [0, %d)", eos_id, s->target->cfg.vocab);
+  SD_REQUIRE(next && allow && fsm_state, "specdec_set_grammar: NULL automaton table / mask table / state");
+  SD_REQUIRE(((reinterpret_cast<uintptr_t>(next) | reinterpret_cast<uintptr_t>(allow)) & 15) == 0 && (reinterpret_cast<uintptr_t>(fsm_state) & 3) == 0,
+             "specdec_set_grammar: tables must be 16-byte aligned (the state 4-byte)");
+  if (!s->fsm_pos) {
+    SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->fsm_pos), sizeof(int32_t) * s->B * (s->K + 1)));
+    SD_HIP_CHECK(hipMemset(s->fsm_pos, 0xff, sizeof(int32_t) * s->B * (s->K + 1)));   // (-1; every entry is written before it is read)
+  }
+  drop_graph(s);   // the captured step holds the launches without the mask, or another grammar's tables
+  s->fsm = 1;
+  s->fsm_bind.next = static_cast<const uint16_t*>(next);
+  s->fsm_bind.allow = static_cast<const uint32_t*>(allow);
+  s->fsm_bind.S = S;
+  s->fsm_bind.state = fsm_state;
+  s->fsm_bind.eos_id = eos_id;
+  s->fsm_bind.pos = s->fsm_pos;
+  s->fsm_bind.pos_stride = s->K + 1;
   return 0;
 }
 
@@ -878,6 +922,12 @@ extern "C" int sd_specdec_invalidate(sd_specdec* s) {
 }
 
 extern "C" long sd_specdec_launches(const sd_specdec* s) { return s ? s->launches : 0; }
+
+extern "C" long sd_specdec_graph_nodes(const sd_specdec* s) {
+  if (!s || !s->graph) return 0;
+  size_t n = 0;
+  return hipGraphGetNodes(s->graph, nullptr, &n) == hipSuccess ? static_cast<long>(n) : -1;
+}
 
 extern "C" int sd_specdec_wait(sd_specdec* s, long launch_index) {
   clear_error();

@@ -147,6 +147,15 @@ SIGNATURES = {
     "sd_logit_counts_add": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "sd_specdec_set_logit_processors": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_void_p, _c_size,
                                                  _c_void_p, _c_size, _c_void_p, _c_size, _c_void_p, _c_size]),
+    "sd_fsm_mask_bytes": (_c_size, [_c_int, _c_int]),
+    "sd_fsm_build_masks": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_size, _c_void_p]),
+    "sd_fsm_advance": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "sd_logit_process_fsm": (
+        _c_int,
+        [_c_void_p, _c_i64, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, ctypes.c_float,
+         ctypes.c_float, ctypes.c_float, _c_void_p, _c_int, _c_void_p, _c_size, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
+    ),
+    "sd_specdec_set_grammar": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),
@@ -162,6 +171,7 @@ SIGNATURES = {
     "sd_specdec_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int]),
     "sd_specdec_sync": (_c_int, [_c_void_p, _c_void_p]),
     "sd_specdec_launches": (ctypes.c_long, [_c_void_p]),
+    "sd_specdec_graph_nodes": (ctypes.c_long, [_c_void_p]),
     "sd_specdec_wait": (_c_int, [_c_void_p, ctypes.c_long]),
     "sd_specdec_invalidate": (_c_int, [_c_void_p]),
     "sd_specdec_record": (ctypes.POINTER(ctypes.c_int32), [_c_void_p]),

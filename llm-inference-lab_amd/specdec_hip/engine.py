@@ -639,6 +639,10 @@ class HipSpecDec:
         # logit processors (set_logit_processors): off; counts / bias tables are allocated at first use and kept
         self.logit_processors = False
         self.logit_counts = self.logit_bias = self._lp_ws = None
+        # grammar (set_grammar): none; a TokenFSM's device tables are uploaded once per object and kept
+        self.grammar = None
+        self.grammar_state = None      # int32 [B] on the device: -1 unconstrained, 0..S-1, 0xFFFF dead
+        self._grammar_tables = {}      # id(fsm) -> (fsm, next, allow)
         self.rec_ints = self.lib.sd_specdec_record_ints(self.handle)
         ptr = self.lib.sd_specdec_record(self.handle)
         self._record = np.ctypeslib.as_array(ptr, shape=(2, self.B, self.rec_ints))   # slot = launch index & 1
@@ -774,6 +778,7 @@ class HipSpecDec:
                 _abi.check(self.lib.sd_specdec_set_logit_processors(self.handle, 0, 1.0, 0.0, 0.0, None, 0, None, 0, None, 0, None, 0),
                            "sd_specdec_set_logit_processors")
                 self.logit_processors = False
+                self.grammar = None        # the grammar is a line of this stage: the library unbinds it too
                 return
             V = self.target.weights.config.vocab
             if self._logits is None:
@@ -802,6 +807,43 @@ class HipSpecDec:
             p = torch.tensor([int(x) for x in prompt_ids], dtype=torch.int32, device=dev) if len(prompt_ids) else None
             g = torch.tensor([int(x) for x in generated_ids], dtype=torch.int32, device=dev) if len(generated_ids) else None
             logit_counts_set(self.logit_counts, int(b), p, g)
+
+    def set_grammar(self, fsm, eos_id: Optional[int] = None) -> None:
+        """A token automaton inside the step (sd_specdec_set_grammar; specdec_hip.grammar.TokenFSM, None unbinds): every
+        process launch of the logit-processor stage also masks its row by the state the row's automaton reaches over the step's
+        own draft tokens, and the accept stage advances `grammar_state` (int32 [B]) over the emitted tokens. The stage must be
+        on (set_logit_processors; identity penalties will do). Binding leaves every row unconstrained (-1) unless the same
+        automaton is bound again; set_grammar_state gives a row its start state. The tables are uploaded once per TokenFSM."""
+        with torch.cuda.device(self.device):
+            if fsm is None:
+                _abi.check(self.lib.sd_specdec_set_grammar(self.handle, 0, None, None, 0, None, 0), "sd_specdec_set_grammar")
+                self.grammar = None
+                return
+            V = self.target.weights.config.vocab
+            if fsm.V != V:
+                raise ValueError(f"set_grammar: the automaton is over {fsm.V} tokens, the models' vocabulary has {V}")
+            if id(fsm) not in self._grammar_tables:
+                from .ops import fsm_tables
+                self._grammar_tables[id(fsm)] = (fsm,) + fsm_tables(fsm, self.device)
+                torch.cuda.current_stream(self.device).synchronize()
+            _, nxt, allow = self._grammar_tables[id(fsm)]
+            if self.grammar_state is None:
+                self.grammar_state = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+                torch.cuda.current_stream(self.device).synchronize()
+            elif self.grammar is not fsm:
+                with torch.cuda.stream(self.stream_t):
+                    self.grammar_state.fill_(-1)
+            _abi.check(self.lib.sd_specdec_set_grammar(self.handle, 1, nxt.data_ptr(), allow.data_ptr(), fsm.S, self.grammar_state.data_ptr(),
+                                                       int(fsm.eos_id if eos_id is None else eos_id)), "sd_specdec_set_grammar")
+            self.grammar = fsm
+
+    def set_grammar_state(self, b: int, state: int) -> None:
+        """Row b's automaton state (-1: unconstrained), written on the loop's target stream: a new sequence's start state, or
+        the host's in-order view after steps that were launched ahead turned out void for the row."""
+        if self.grammar_state is None:
+            raise RuntimeError("set_grammar_state: no grammar is bound (set_grammar)")
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream_t):
+            self.grammar_state[int(b):int(b) + 1].fill_(int(state))
 
     def set_draw_counts(self, draw_counts: Sequence[int]) -> None:
         """Rewrite the rows' draw counters (sampling modes) on the loop's target stream: the host's in-order view after steps
@@ -843,6 +885,11 @@ class HipSpecDec:
     @property
     def launches(self) -> int:
         return int(self.lib.sd_specdec_launches(self.handle))
+
+    @property
+    def graph_nodes(self) -> int:
+        """Nodes of the captured step's graph (0: no step is captured) — sd_specdec_graph_nodes."""
+        return int(self.lib.sd_specdec_graph_nodes(self.handle))
 
     def invalidate(self) -> None:
         """Drop the captured step (a model's path changed: set_persist_tokens / set_length_hint / a re-bind). The caller has

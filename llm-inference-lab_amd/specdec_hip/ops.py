@@ -478,6 +478,98 @@ def logit_counts_add(counts: torch.Tensor, tokens: torch.Tensor, n_new: torch.Te
                                                    active.data_ptr() if active is not None else None, _stream_ptr(dev)), "sd_logit_counts_add")
 
 
+def _check_fsm_table(name: str, nxt: torch.Tensor, dev) -> Tuple[int, int]:
+    if nxt.dim() != 2 or nxt.dtype != torch.int16 or nxt.device != dev or not nxt.is_contiguous():
+        raise ValueError(f"{name}: next must be a contiguous int16 [S][V] tensor on {dev} holding the automaton's uint16 words (fsm_tables)")
+    return int(nxt.shape[0]), int(nxt.shape[1])
+
+
+def fsm_build_masks(nxt: torch.Tensor) -> torch.Tensor:
+    """The mask table of a token automaton, built on the device from its transition table (sd_fsm_build_masks, csrc/grammar.hip).
+    nxt: int16 [S][V] holding the uint16 words (0xFFFF = not allowed) -> int32 [S][ceil(V / 32)]: bit v % 32 of word v / 32 is
+    set where nxt[s][v] != 0xFFFF, pad bits 0."""
+    lib = _abi.load()
+    dev = _require_device("fsm_build_masks", nxt)
+    S, V = _check_fsm_table("fsm_build_masks", nxt, dev)
+    W = (V + 31) // 32
+    nbytes = int(lib.sd_fsm_mask_bytes(S, V))
+    buf = torch.zeros(nbytes // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_fsm_build_masks(nxt.data_ptr(), S, V, buf.data_ptr(), nbytes, _stream_ptr(dev)), "sd_fsm_build_masks")
+    return buf[:S * W].view(S, W)
+
+
+def fsm_tables(fsm, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A specdec_hip.grammar.TokenFSM on the device: (next int16 [S][V], allow int32 [S][ceil(V / 32)])."""
+    import numpy as np
+
+    nxt = torch.from_numpy(np.ascontiguousarray(fsm.next).view(np.int16)).to(device)
+    return nxt, fsm_build_masks(nxt)
+
+
+def logit_process_fsm(rows: torch.Tensor, counts: torch.Tensor, nxt: torch.Tensor, allow: torch.Tensor, fsm_state: torch.Tensor,
+                      eos_id: int, repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                      bias: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, n_tokens: Optional[int] = None,
+                      active: Optional[torch.Tensor] = None, return_ids: bool = False):
+    """logit_process with the grammar line (sd_logit_process_fsm): row (b, r) is masked by the state its automaton reaches from
+    fsm_state[b] (int32 [B]; -1 = unconstrained) over the row's in-step tokens; a disallowed element is stored as -inf. nxt /
+    allow: fsm_tables. Everything else as logit_process."""
+    lib = _abi.load()
+    dev = _require_device("logit_process_fsm", rows, counts, nxt, allow, fsm_state)
+    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
+        raise ValueError("logit_process_fsm: rows must be bfloat16 [B][R][V]")
+    B, R, V = (int(x) for x in rows.shape)
+    if _check_counts("logit_process_fsm", counts, dev) != (B, V):
+        raise ValueError(f"logit_process_fsm: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
+    S, Vn = _check_fsm_table("logit_process_fsm", nxt, dev)
+    if Vn != V or allow.dtype != torch.int32 or tuple(allow.shape) != (S, (V + 31) // 32) or not allow.is_contiguous():
+        raise ValueError(f"logit_process_fsm: tables {tuple(nxt.shape)} / {tuple(allow.shape)} for V={V} (fsm_tables)")
+    if fsm_state.dtype != torch.int32 or fsm_state.numel() != B or not fsm_state.is_contiguous():
+        raise ValueError(f"logit_process_fsm: fsm_state must be a contiguous int32 [{B}] tensor")
+    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
+    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
+        raise ValueError("logit_process_fsm: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
+        raise ValueError(f"logit_process_fsm: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
+    n_tok = -1 if n_tokens is None else int(n_tokens)
+    tok_stride = 0
+    if tokens is not None:
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
+            raise ValueError(f"logit_process_fsm: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
+        tok_stride = int(tokens.shape[1])
+    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
+        raise ValueError(f"logit_process_fsm: active must be a contiguous int32 [{B}] tensor on {dev}")
+    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
+    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_logit_process_fsm(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
+                                            ptr(active), float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
+                                            ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0, nxt.data_ptr(), allow.data_ptr(), S,
+                                            fsm_state.data_ptr(), int(eos_id), _stream_ptr(dev)), "sd_logit_process_fsm")
+    return ids
+
+
+def fsm_advance(nxt: torch.Tensor, fsm_state: torch.Tensor, tokens: torch.Tensor, n_new: torch.Tensor,
+                active: Optional[torch.Tensor] = None) -> None:
+    """Every active row with a state >= 0 walks its first n_new[b] tokens of tokens[b] (int32 [B][n]), in place in fsm_state
+    (int32 [B]); a token the state does not allow, or an id outside the vocabulary, leads to DEAD = 0xFFFF (sd_fsm_advance)."""
+    dev = _require_device("fsm_advance", nxt, fsm_state, tokens, n_new)
+    S, V = _check_fsm_table("fsm_advance", nxt, dev)
+    B = int(fsm_state.numel())
+    if fsm_state.dtype != torch.int32 or not fsm_state.is_contiguous():
+        raise ValueError("fsm_advance: fsm_state must be a contiguous int32 [B] tensor")
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or not tokens.is_contiguous():
+        raise ValueError(f"fsm_advance: tokens must be a contiguous int32 [{B}][n] tensor")
+    for name, t in (("n_new", n_new), ("active", active)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"fsm_advance: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    n = int(tokens.shape[1])
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().sd_fsm_advance(nxt.data_ptr(), S, V, fsm_state.data_ptr(), B, tokens.data_ptr(), n, n_new.data_ptr(), n,
+                                              active.data_ptr() if active is not None else None, _stream_ptr(dev)), "sd_fsm_advance")
+
+
 def spec_agreement(draft_logits: torch.Tensor, target_logits: torch.Tensor, temperature: float = 1.0):
     """Draft-target agreement per position (sd_spec_agreement, csrc/spec_agree.hip): how much of softmax(target / T) the draft's
     softmax(draft / T) reproduces, in float64 over the stored bf16 logits.

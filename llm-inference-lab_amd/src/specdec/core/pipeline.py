@@ -357,11 +357,12 @@ class SpeculativePipeline:
 
     # ------------------------------------------------------------------ host-side rules
     def _rules_batch(self, row: _Row, k: int, a: int, t: List[int], max_tokens: int, eos: Optional[int],
-                     resample=None) -> None:
+                     resample=None, dedup: bool = True) -> None:
         """One row of one generate_batch step (pipeline.py:3018-3590), from the step record:
         a = accepted length, t[i] = target argmax after the row's sequence + d_1..d_i (sampling mode:
         t[a] is the token the device sampled at position a; `resample(pos)` draws at another position
-        with the same Philox draw — only an EOS-cut full acceptance needs it)."""
+        with the same Philox draw — only an EOS-cut full acceptance needs it). dedup=False (a row under a grammar): the
+        overlap / de-duplication rules are not applied — they delete tokens the row's automaton has consumed."""
         V = self.base_lm.vocab_size
         gen = row.generated
         if a > 0:
@@ -374,7 +375,7 @@ class SpeculativePipeline:
             if eos is not None and bonus == eos:         # bonus EOS stays in the output (:3274-3280)
                 row.active = False
             acc.append(bonus)
-            if gen:                                      # overlap with the generated tail (:3295-3318)
+            if gen and dedup:                            # overlap with the generated tail (:3295-3318)
                 for c in range(min(5, len(gen), len(acc)), 0, -1):
                     if gen[-c:] == acc[:c]:
                         acc = acc[c:]
@@ -386,14 +387,14 @@ class SpeculativePipeline:
             if eos is not None and emitted[0] == eos:    # (:3360-3365)
                 row.active = False
                 emitted = []
-            if emitted and gen and gen[-1] == emitted[0]:  # (:3367-3376)
+            if dedup and emitted and gen and gen[-1] == emitted[0]:  # (:3367-3376)
                 emitted = []
             gen.extend(emitted)
         row.proposed += k
         row.accepted += len(emitted)
         if emitted:                                      # sequence update with its own overlap rule (:3470-3572)
             acc, cur = list(emitted), row.seq
-            c = min(5, len(cur), len(acc))
+            c = min(5, len(cur), len(acc)) if dedup else 0
             if c > 0 and cur[-c:] == acc[:c]:
                 if len(acc) > c:
                     acc = acc[c:]
@@ -424,20 +425,21 @@ class SpeculativePipeline:
     # ------------------------------------------------------------------ the loop
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None,
-                      self_draft: bool = False, share_prefix: bool = False, **processors) -> "DecodeSession":
+                      self_draft: bool = False, share_prefix: bool = False, grammar=None, **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
         (DecodeSession). processors: repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids,
-        allowed_token_ids (logit_processor_config); identity values leave the mode off."""
+        allowed_token_ids (logit_processor_config); identity values leave the mode off. grammar: a TokenFSM, or a list with one
+        entry per prompt (None: that row is unconstrained) — grammar_config."""
         return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix,
-                             self.logit_processor_config(processors))
+                             self.logit_processor_config(processors), self.grammar_config(grammar, len(prompts)))
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
                 sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False,
-                processors: Optional[Dict[str, Any]] = None):
+                processors: Optional[Dict[str, Any]] = None, grammar: Optional[Dict[str, Any]] = None):
         t_start = time.time()
-        sess = DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix, processors)
+        sess = DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix, processors, grammar)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -693,6 +695,75 @@ class SpeculativePipeline:
             raise NotImplementedError("logit processors keep a fixed K (controller='fixed'): adaptive K is not supported")
         return lp
 
+    def grammar_config(self, grammar, n_prompts: int) -> Optional[Dict[str, Any]]:
+        """The grammar of a run: a specdec_hip.grammar.TokenFSM for every prompt, or a list with one entry per prompt (None: that
+        row is unconstrained). -> None, or {"fsm": the one table the device walks, "starts": each prompt's start state (-1:
+        unconstrained)}; different automata are merged with TokenFSM.union (one merge per combination, kept). The automaton's
+        eos_id must be the pipeline's EOS where it has one: that is the token the host's EOS rule stops a row on."""
+        if grammar is None:
+            return None
+        from specdec_hip.grammar import TokenFSM
+
+        entries = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar] * n_prompts
+        if len(entries) != n_prompts:
+            raise ValueError(f"grammar: {len(entries)} entries for {n_prompts} prompts")
+        members: List[Any] = []
+        for g in entries:
+            if g is not None and not isinstance(g, TokenFSM):
+                raise TypeError(f"grammar: expected a TokenFSM or None, got {type(g).__name__}")
+            if g is not None and not any(g is m for m in members):
+                members.append(g)
+        if not members:
+            return None
+        V, eos = self.base_lm.vocab_size, self.base_lm.get_tokenizer_info().get("eos_token_id")
+        for g in members:
+            if g.V != V:
+                raise ValueError(f"grammar: the automaton is over {g.V} tokens, the vocabulary has {V}")
+            if g.eos_id != members[0].eos_id or (eos is not None and g.eos_id != eos):
+                raise ValueError(f"grammar: the automaton ends on eos_id {g.eos_id}, the pipeline's EOS is {eos}")
+        if len(members) == 1:
+            fsm, starts = members[0], [members[0].start]
+        else:
+            cache = self.__dict__.setdefault("_grammar_unions", {})
+            key = tuple(id(m) for m in members)
+            if key not in cache:
+                cache[key] = (members,) + TokenFSM.union(members)      # (the members are held: their ids stay theirs)
+            _, fsm, starts = cache[key]
+        start_of = {id(m): st for m, st in zip(members, starts)}
+        return {"fsm": fsm, "starts": [-1 if g is None else start_of[id(g)] for g in entries]}
+
+    def grammar_from_regex(self, pattern: str, eos_id: Optional[int] = None):
+        """The TokenFSM of a regular expression over the target's tokenizer (specdec_hip.grammar.from_tokenizer; its limitation
+        for byte-level BPE vocabularies is written there). eos_id defaults to the pipeline's EOS; a pipeline without one must
+        pass it. Compiled once per (pattern, eos_id) and kept."""
+        from specdec_hip.grammar import from_tokenizer
+
+        if eos_id is None:
+            eos_id = self.base_lm.get_tokenizer_info().get("eos_token_id")
+            if eos_id is None:
+                raise ValueError("grammar_from_regex: the pipeline has no EOS token; pass eos_id")
+        cache = self.__dict__.setdefault("_grammar_regexes", {})
+        if (pattern, int(eos_id)) not in cache:
+            cache[(pattern, int(eos_id))] = from_tokenizer(pattern, self.base_lm._tokenizer, self.base_lm.vocab_size, int(eos_id))
+        return cache[(pattern, int(eos_id))]
+
+    def _grammar_for_step(self, grammar, n_prompts: int, route_ok: bool, what: str) -> Optional[Dict[str, Any]]:
+        """grammar_config of a call, refused where the run does not go through the captured step with a draft model and a fixed
+        K: the automaton is a line of that step's logit-processor stage."""
+        from ..policies.controllers import FixedKController
+
+        gr = self.grammar_config(grammar, n_prompts)
+        if gr is None:
+            return None
+        if not route_ok:
+            raise NotImplementedError(f"a grammar runs inside the captured device step: {what} is not supported with it")
+        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None:
+            raise NotImplementedError("a grammar needs the draft-model mode (draft_mode='vanilla'): medusa / eagle proposals come from no "
+                                      "logits row")
+        if not isinstance(self.controller, FixedKController):
+            raise NotImplementedError("a grammar keeps a fixed K (controller='fixed'): adaptive K is not supported")
+        return gr
+
     def _spec_sampling_config(self, kwargs: Dict[str, Any]) -> Dict[str, Any]:
         """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature,
         seed, top_k and top_p (policy_params; call-level top_k / top_p stay refused: the policy shapes the mode). What the mode
@@ -711,6 +782,7 @@ class SpeculativePipeline:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
+        grammar = kwargs.pop("grammar", None)
         if kwargs.get("share_prefix") or int(kwargs.get("n", 1) or 1) != 1:
             raise NotImplementedError("share_prefix / n belong to generate_batch and generate_many: generate() decodes one row")
         max_tokens = max_tokens or self.config["max_new_tokens"]
@@ -732,13 +804,16 @@ class SpeculativePipeline:
         processors = self._processors_for_step(
             kwargs, self.policy_name == "longest_prefix" and not self._fake and sample_t is None,
             "generate(do_sample=True)" if sample_t is not None else f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
+        grammar = self._grammar_for_step(
+            grammar, 1, self.policy_name == "longest_prefix" and not self._fake and sample_t is None and not self._medusa_random(),
+            "generate(do_sample=True)" if sample_t is not None else f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
         if self.policy_name != "longest_prefix" or self._medusa_random() or self._fake or sample_t is not None:
             rows, st = self._decode_host_policy([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
                                                 temperature=float(temperature), sample_t=sample_t,
                                                 sample_kwargs={k: kwargs[k] for k in ("top_k", "top_p") if k in kwargs})
         else:
             rows, st = self._decode([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
-                                    self_draft=self.config.get("draft_mode") in ("medusa", "eagle"), processors=processors)
+                                    self_draft=self.config.get("draft_mode") in ("medusa", "eagle"), processors=processors, grammar=grammar)
         r = rows[0]
         total_ms = (time.time() - t_begin) * 1e3
         self.metrics = {"total_proposed": r.proposed, "total_accepted": r.accepted, "total_steps": st["steps"],
@@ -758,7 +833,7 @@ class SpeculativePipeline:
 
     def generate_batch(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None,
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
-                       share_prefix: bool = False, n: int = 1, **kwargs) -> List[Dict[str, Any]]:
+                       share_prefix: bool = False, n: int = 1, grammar=None, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -771,7 +846,13 @@ class SpeculativePipeline:
         level — which is why sharing is opt-in. `n` > 1: every prompt becomes n adjacent rows (n samples of it: do_sample=True,
         or policy="rejection" with backend="device", whose per-row Philox streams make the rows differ), results come back
         prompt-major; implies share_prefix. Both are for the captured step (longest_prefix, device sampling, rejection on
-        the device) and are refused elsewhere. batch_metrics carries prefilled_rows / forked_rows / shared_positions."""
+        the device) and are refused elsewhere. batch_metrics carries prefilled_rows / forked_rows / shared_positions.
+
+        grammar (opt-in; not in the reference): a specdec_hip.grammar.TokenFSM, or a list with one entry per prompt (None: that
+        row is unconstrained). A row under a grammar emits only token sequences its automaton allows, draft and target alike
+        (the mask is a line of the step's logit-processor stage), ends on the automaton's eos, and is exempt from the overlap /
+        de-duplication rules, which would delete tokens the automaton has consumed; greedy output is the target's own greedy
+        decoding under the mask, token for token."""
         if not prompts:
             return []
         n = int(n)
@@ -785,6 +866,8 @@ class SpeculativePipeline:
         if self._fake:
             # the double has no tokenizer to pad a batch with: the reference falls back to generate() per prompt
             # ("No tokenizer access, falling back to sequential processing", pipeline.py:1680-1700)
+            if grammar is not None:
+                raise NotImplementedError("a grammar runs inside the captured device step: implementation='fake' is not supported with it")
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
         max_tokens = max_tokens or self.config["max_new_tokens"]
         temperature = temperature or self.config["temperature"]
@@ -794,13 +877,16 @@ class SpeculativePipeline:
         if self.draft_lm is None and not heads:
             raise ValueError("generate_batch drafts with the draft model (the reference ignores draft_mode there): pass draft_lm / draft_model")
         if n > 1:
+            if isinstance(grammar, (list, tuple)):
+                grammar = [g for g in grammar for _ in range(n)]
             prompts = [p for p in prompts for _ in range(n)]
         ids = [self._encode(p) for p in prompts]
         device_step = self.policy_name == "longest_prefix" or (self.policy_name == "rejection" and self.rejection_backend == "device")
         processors = self._processors_for_step(kwargs, device_step, f"policy={self.policy_name!r} on the host loop")
+        grammar = self._grammar_for_step(grammar, len(ids), device_step and not heads, f"policy={self.policy_name!r} on the host loop")
         if self.policy_name == "rejection" and self.rejection_backend == "device":
             rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs),
-                                    share_prefix=share_prefix, processors=processors)
+                                    share_prefix=share_prefix, processors=processors, grammar=grammar)
         elif self.policy_name == "rejection":
             rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
         elif self.policy_name != "longest_prefix":
@@ -809,7 +895,7 @@ class SpeculativePipeline:
             rows, st = self._decode_host_policy(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
             rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=sampling, self_draft=heads,
-                                    share_prefix=share_prefix, processors=processors)
+                                    share_prefix=share_prefix, processors=processors, grammar=grammar)
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -843,7 +929,7 @@ class SpeculativePipeline:
 
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
-                      **kwargs) -> List[Dict[str, Any]]:
+                      grammar=None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -851,7 +937,8 @@ class SpeculativePipeline:
         generate_batch([prompt]) run. Results come back in prompt order.
         share_prefix / n: as generate_batch — a prompt admitted to a slot is also compared with the rows the session holds at
         that moment (finished rows whose caches are still intact included), so a system prompt in front of many questions is
-        computed once per session, not once per question; with n > 1 the results are prompt-major (n per prompt)."""
+        computed once per session, not once per question; with n > 1 the results are prompt-major (n per prompt).
+        grammar: as generate_batch, one entry per prompt; a prompt admitted to a slot starts in its own automaton's start state."""
         if not prompts:
             return []
         n = int(n)
@@ -861,6 +948,8 @@ class SpeculativePipeline:
         if share_prefix and (self._fake or self.policy_name != "longest_prefix"):
             raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip', policy='longest_prefix')")
         if n > 1:
+            if isinstance(grammar, (list, tuple)):
+                grammar = [g for g in grammar for _ in range(n)]
             prompts = [p for p in prompts for _ in range(n)]
         max_tokens = max_tokens or self.config["max_new_tokens"]
         temperature = temperature or self.config["temperature"]
@@ -871,13 +960,16 @@ class SpeculativePipeline:
         processors = self._processors_for_step(kwargs, self.policy_name == "longest_prefix" and not self._fake,
                                                f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
         ids = [self._encode(p) for p in prompts]
+        grammar = self._grammar_for_step(grammar, len(ids), self.policy_name == "longest_prefix" and not self._fake,
+                                         f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
         sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens,
-                             share_prefix=share_prefix, processors=processors)
+                             share_prefix=share_prefix, processors=processors,
+                             grammar=None if grammar is None else {"fsm": grammar["fsm"], "starts": [grammar["starts"][i] for i in first]})
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -890,7 +982,7 @@ class SpeculativePipeline:
                     owner[b] = None
                     if waiting:
                         nxt = waiting.pop(0)
-                        sess.admit(b, ids[nxt])
+                        sess.admit(b, ids[nxt], -1 if grammar is None else grammar["starts"][nxt])
                         owner[b] = nxt
             if not sess.any_active() and not waiting and all(o is None for o in owner):
                 break
@@ -1002,13 +1094,19 @@ class DecodeSession:
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                  sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None, self_draft: bool = False,
-                 share_prefix: bool = False, processors: Optional[Dict[str, Any]] = None):
+                 share_prefix: bool = False, processors: Optional[Dict[str, Any]] = None, grammar: Optional[Dict[str, Any]] = None):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
+        # grammar (SpeculativePipeline.grammar_config; None: off): a token automaton as one more line of the processor stage, with
+        # a state per cache row that is (re)written wherever the row's counts are. It needs the stage: identity penalties will do
+        self.grammar = grammar["fsm"] if grammar is not None else None
+        self.grammar_starts: List[int] = list(grammar["starts"]) if grammar is not None else [-1] * len(prompts)
+        if grammar is not None and processors is None:
+            processors = {"rp": 1.0, "presence": 0.0, "frequency": 0.0, "bias": None}
         # logit processors (SpeculativePipeline.logit_processor_config; None: off): a device stage of the step, with a counts row
         # per cache row that is (re)written wherever the row's device state is
         self.processors = processors
         if processors is not None and (self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))):
-            raise NotImplementedError("logit processors need the HIP step with a draft model and a fixed K")
+            raise NotImplementedError("logit processors and grammars need the HIP step with a draft model and a fixed K")
         if share_prefix and pipe._fake:
             raise NotImplementedError("share_prefix needs the HIP engines (implementation='hip')")
         self.self_draft = self_draft
@@ -1149,6 +1247,18 @@ class DecodeSession:
                 loop.logit_bias.copy_(lp["bias"].to(loop.device).unsqueeze(0).expand_as(loop.logit_bias))
         for b in range(len(self.rows)):
             self._set_counts(b)
+        if self.grammar is not None:
+            loop.set_grammar(self.grammar)               # (the tables are uploaded once per automaton and kept by the loop)
+            for b in range(len(self.rows)):
+                self._set_grammar_state(b)
+        elif loop.grammar is not None:
+            loop.set_grammar(None)
+
+    def _set_grammar_state(self, b: int) -> None:
+        """Row b's automaton state as the host sees the row: its own start state walked over what it has generated so far."""
+        if self.grammar is not None:
+            r, st = self.rows[b], self.grammar_starts[b]
+            self.loop.set_grammar_state(b, self.grammar.walk(st, r.seq[r.n_prompt:]) if st >= 0 else -1)
 
     def _set_counts(self, b: int) -> None:
         """Row b's counts as the host sees the row: the prompt's ids, and what it has generated so far."""
@@ -1191,6 +1301,7 @@ class DecodeSession:
             pipe._set_row(loop, b, r)              # (re)position, or freeze a finished row
             if r.active:
                 self._set_counts(b)                # (void steps counted tokens the row never kept: back to the in-order view)
+                self._set_grammar_state(b)         # (and advanced its automaton over them)
             if self.per_row:                       # the device counted steps the host voided: hand it the in-order view
                 m = self.row_ctl[b]
                 loop.set_adaptive_row(b, m.current_k, r.strict_acc, r.strict_prop, m.acceptance_history[-4:])
@@ -1338,12 +1449,14 @@ class DecodeSession:
                 t[a] = int(rec.new_tokens[b][a])       # the token the device sampled at position a
             assumed = before + t[: int(rec.n_new[b])]  # what the device advanced to
             if self.emit_mode == HipSpecDec.EMIT_BONUS:
-                pipe._rules_batch(r, k, a, t, self.max_tokens, self.eos,
-                                  self._resampler(b, r) if (self.sampling is not None and not self._spec) else None)
+                constrained = self.grammar is not None and self.grammar_starts[b] >= 0
+                pipe._rules_batch(r, k, a, t, self.max_tokens, self.grammar.eos_id if constrained else self.eos,
+                                  self._resampler(b, r) if (self.sampling is not None and not self._spec) else None, dedup=not constrained)
                 if self.sampling is not None:
                     r.draws += (k + 1) if self._spec else 1
             else:
-                pipe._rules_single(r, k, a, d, t, self.max_tokens, self.eos)
+                pipe._rules_single(r, k, a, d, t, self.max_tokens,
+                                   self.grammar.eos_id if (self.grammar is not None and self.grammar_starts[b] >= 0) else self.eos)
             r.steps += 1
             r.counters.append((r.proposed, r.accepted, len(r.generated), a))
             if a >= k:
@@ -1365,16 +1478,20 @@ class DecodeSession:
         stats["steps"] = max(r.steps for r in rows)
         return True
 
-    def admit(self, b: int, prompt: List[int]) -> None:
+    def admit(self, b: int, prompt: List[int], grammar_start: int = -1) -> None:
         """Continuous batching: put a new sequence into the slot of a finished row. Its caches are prefilled
-        and its device state set at the next launch point; the other rows keep stepping meanwhile."""
+        and its device state set at the next launch point; the other rows keep stepping meanwhile. grammar_start: the new
+        row's start state in the session's automaton (-1: unconstrained)."""
         if self.rows[b].active:
             raise ValueError(f"row {b} is still decoding")
         if not prompt:
             raise ValueError("empty prompt")
         if len(prompt) + self.max_tokens + 2 * self.k + 8 > self.rt["l_max"] or len(prompt) + 2 * self.k + 4 > self.pos_limit:
             raise ValueError(f"prompt of {len(prompt)} tokens does not fit this session (l_max {self.rt['l_max']}, positions {self.pos_limit})")
+        if grammar_start >= 0 and self.grammar is None:
+            raise ValueError("admit: the session was started without a grammar")
         self.rows[b] = _Row(list(prompt))
+        self.grammar_starts[b] = int(grammar_start)
         self._fresh.add(b)
         if self._held is not None:
             self._held[b] = None          # the slot is reused: what its caches hold is no longer on record

@@ -62,6 +62,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
     ap.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
     ap.add_argument("--ban-token", type=int, action="append", metavar="ID", help="never emit this token id (repeatable)")
+    ap.add_argument("--regex", type=str, metavar="PATTERN",
+                    help="constrain the output to full matches of this regular expression over the tokens' bytes: a token automaton "
+                         "masks draft and target logits inside the captured step (literals, classes, groups, |, * + ? {m,n})")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
@@ -132,6 +135,8 @@ def main(argv=None) -> int:
         batch = args.spec_sampling or args.share_prefix or args.n != 1
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
+        if args.regex is not None:
+            proc["grammar"] = pipe.grammar_from_regex(args.regex)
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
             rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],

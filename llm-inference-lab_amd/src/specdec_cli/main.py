@@ -54,6 +54,8 @@ def cmd_run(args: argparse.Namespace) -> int:
                                draft_mode="vanilla", **extra)
     proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                               ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
+    if args.regex is not None:
+        proc["grammar"] = pipe.grammar_from_regex(args.regex)
     if spec or args.share_prefix or args.n != 1:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
@@ -99,6 +101,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
     pr.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
     pr.add_argument("--ban-token", type=int, action="append", metavar="ID", help="never emit this token id (repeatable)")
+    pr.add_argument("--regex", type=str, metavar="PATTERN", help="constrain the output to full matches of this regular expression over the "
+                                                                 "tokens' bytes (a token automaton inside the captured step)")
     pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
                                                      "once and forked into the others (implies --share-prefix)")
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
