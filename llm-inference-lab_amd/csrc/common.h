@@ -157,7 +157,8 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 }
 
 // torch.argmax ordering: NaN is the maximum, ties go to the lower index.
-__device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) {
+template <typename T>
+__device__ __forceinline__ bool nan_first_better(T v, int i, T bv, int bi) {
   const bool vn = (v != v), bn = (bv != bv);
   if (vn | bn) {
     if (vn & bn) return i < bi;
@@ -165,17 +166,69 @@ __device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) 
   }
   return (v > bv) | ((v == bv) & (i < bi));
 }
+__device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) { return nan_first_better(v, i, bv, bi); }
+__device__ __forceinline__ bool better_d(double v, int i, double bv, int bi) { return nan_first_better(v, i, bv, bi); }
 
-__device__ __forceinline__ void wave_reduce_argmax(float& v, int& i) {
+__device__ __forceinline__ bool is_finite_d(double v) { return v - v == 0.0; }
+
+// ---- reductions in a fixed order: xor tree inside a wave, then the waves in wave order --------------------------------
+// Best (value, index) of the wave under Better (argmax_better / better_d), in every lane.
+template <typename T, bool (*Better)(T, int, T, int)>
+__device__ __forceinline__ void wave_reduce_best(T& v, int& i) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    float ov = __shfl_xor(v, off, 64);
-    int oi = __shfl_xor(i, off, 64);
-    if (argmax_better(ov, oi, v, i)) {
+    const T ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    if (Better(ov, oi, v, i)) {
       v = ov;
       i = oi;
     }
   }
+}
+__device__ __forceinline__ void wave_reduce_argmax(float& v, int& i) { wave_reduce_best<float, argmax_better>(v, i); }
+
+__device__ __forceinline__ double wave_reduce_sum_d(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// The workgroup helpers below take W-entry LDS scratch from the caller and hold ONE barrier, between their stores and
+// their loads: the scratch must be free on entry (a caller that reuses it for back-to-back reductions puts a
+// __syncthreads() between them), and every thread of the W-wave workgroup calls them.
+// Best (value, index) of the workgroup under Better; valid in thread 0 only.
+template <int W, typename T, bool (*Better)(T, int, T, int)>
+__device__ __forceinline__ void block_arg_best(T& v, int& i, T* sv, int* si) {
+  wave_reduce_best<T, Better>(v, i);
+  if ((threadIdx.x & (kWave - 1)) == 0) { sv[threadIdx.x / kWave] = v; si[threadIdx.x / kWave] = i; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < W; ++w)
+      if (Better(sv[w], si[w], v, i)) { v = sv[w]; i = si[w]; }
+  }
+}
+
+// Sum / maximum of doubles over the workgroup, in every thread.
+template <int W>
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {
+  v = wave_reduce_sum_d(v);
+  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < W; ++w) r += sh[w];
+  return r;
+}
+
+template <int W>
+__device__ __forceinline__ double block_max_d(double v, double* sh) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < W; ++w) r = fmax(r, sh[w]);
+  return r;
 }
 
 #endif  // __HIPCC__

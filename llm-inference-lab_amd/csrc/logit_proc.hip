@@ -188,12 +188,8 @@ __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitPr
     for (int v = e0 + tid; v < e1; v += kLpThreads) one(v);
   }
   if (!a.part_val) return;   // (uniform)
-  wave_reduce_argmax(bv, bi);
-  if ((tid & (kWave - 1)) == 0) { sv[tid / kWave] = bv; si[tid / kWave] = bi; }
-  __syncthreads();
+  block_arg_best<kLpThreads / kWave, float, argmax_better>(bv, bi, sv, si);
   if (tid == 0) {
-    for (int w = 1; w < kLpThreads / kWave; ++w)
-      if (argmax_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
     // (a workgroup whose share of the row is empty leaves (-inf, INT_MAX), which loses against every element)
     a.part_val[static_cast<size_t>(t) * S + x0] = bv;
     a.part_idx[static_cast<size_t>(t) * S + x0] = bi;

@@ -81,11 +81,12 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
   __shared__ uint32_t hist[2048];
   __shared__ uint64_t sel[kSampleThreads];
   __shared__ double ev[kSampleThreads];
-  __shared__ uint32_t s_cnt, s_digit, s_above;
-  __shared__ double s_z, s_cum, s_z2, s_target, s_c;
+  __shared__ uint32_t s_cnt;
+  __shared__ RadixPick s_radix;
+  __shared__ double s_z, s_cum, s_z2, s_u, s_c;
   __shared__ int s_done, s_keep, s_pick;
   __shared__ uint64_t s_best;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
@@ -96,8 +97,6 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
     double v = static_cast<double>(load_logit(row, a.dtype, i));
     return scale ? v / T : v;
   };
-  constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1u;
-  auto key_index = [&](uint64_t c) { return static_cast<int>(kIdxMask - static_cast<uint32_t>(c & kIdxMask)); };
 
   // ---- the top element (largest composite key) and the normaliser
   if (tid == 0) s_best = 0;
@@ -118,8 +117,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
   __syncthreads();
   const int top_idx = key_index(s_best);
   const double m = scaled(top_idx);
-  const bool finite = (m == m) && (m - m == 0.0);
-  if (!finite) {                       // -inf / NaN / +inf on top: the reference falls back to argmax (:129-131)
+  if (!is_finite_d(m)) {                     // -inf / NaN / +inf on top: the reference falls back to argmax (:129-131)
     if (tid == 0) {
       a.out[b] = top_idx;
       if (a.draw) a.draw[b] = a.draw[b] + 1u;
@@ -147,61 +145,11 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
   }
   __syncthreads();
 
-  // exact composite key of rank k (1-based from the top): radix select over all 52 bits
-  auto select_kth = [&](int k) -> uint64_t {
-    const int widths[5] = {11, 11, 10, 10, 10};
-    uint64_t prefix = 0;
-    int decided = 0, need = k;
-    for (int p = 0; p < 5; ++p) {
-      const int w = widths[p];
-      const int shift = 52 - decided - w;
-      for (int i = tid; i < 2048; i += kSampleThreads) hist[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < V; i += kSampleThreads) {
-        const uint64_t c = composite_key(load_logit(row, a.dtype, i), i);
-        if ((c >> (shift + w)) == prefix) atomicAdd(&hist[(c >> shift) & ((1u << w) - 1u)], 1u);
-      }
-      __syncthreads();
-      if (wave == 0) {
-        const int nb = 1 << w;
-        uint32_t local = 0;
-        for (int j = 0; j < 32; ++j) {
-          const int d = lane * 32 + j;
-          if (d < nb) local += hist[d];
-        }
-        uint32_t incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const uint32_t o = __shfl_down(incl, off, 64);
-          if (lane + off < 64) incl += o;
-        }
-        uint32_t above = incl - local;
-        if (above < static_cast<uint32_t>(need) && incl >= static_cast<uint32_t>(need)) {
-          for (int j = 31; j >= 0; --j) {
-            const int d = lane * 32 + j;
-            if (d >= nb) continue;
-            const uint32_t h = hist[d];
-            if (above + h >= static_cast<uint32_t>(need)) {
-              s_digit = d;
-              s_above = above;
-              break;
-            }
-            above += h;
-          }
-        }
-      }
-      __syncthreads();
-      prefix = (prefix << w) | s_digit;
-      decided += w;
-      need -= static_cast<int>(s_above);
-      __syncthreads();
-    }
-    return prefix;
-  };
   // block r: the elements of ranks (1024 r, min(1024 (r+1), V)], sorted descending into sel[] / ev[]; returns their count
   auto load_block = [&](int r, uint64_t upper_excl, uint64_t& thr_out) -> int {
     const int k_hi = min((r + 1) * kSampleThreads, V);
-    const uint64_t thr = select_kth(k_hi);
+    int decided;   // 52: stop_bucket = 0 runs every pass, the prefix is the exact composite key of rank k_hi
+    const uint64_t thr = radix_select(row, a.dtype, V, k_hi, 0, hist, s_radix, decided);
     thr_out = thr;
     if (tid == 0) s_cnt = 0;
     sel[tid] = 0;
@@ -214,18 +162,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
       }
     }
     __syncthreads();
-    for (int size = 2; size <= kSampleThreads; size <<= 1) {        // descending bitonic sort of the 1024 slots (0 = empty, last)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        if (tid < kSampleThreads / 2) {
-          const int lo = 2 * tid - (tid & (stride - 1));
-          const int hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const uint64_t x = sel[lo], y = sel[hi];
-          if ((x < y) == desc) { sel[lo] = y; sel[hi] = x; }
-        }
-        __syncthreads();
-      }
-    }
+    sort_desc(sel, kSampleThreads);   // 0 = empty, last
     const int n = k_hi - r * kSampleThreads;
     if (tid < n) {
       const int idx = key_index(sel[tid] - 1);
@@ -273,25 +210,16 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
   if (tid == 0) {
     const uint32_t d = a.draw ? a.draw[b] : a.draw0;
     const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
-    uint32_t r0;
-    philox4x32_10(d, sid, 0u, kTagCdf, a.seed_lo, a.seed_hi, r0);
-    s_target = static_cast<double>(r0) * 2.3283064365386963e-10 * s_z2;  // 2^-32
+    s_u = philox_uniform(d, sid, kTagCdf, a.seed_lo, a.seed_hi);
     s_c = 0.0;
     s_pick = -1;
   }
   __syncthreads();
   const int n_keep = s_keep;
   if (blocks_used == 1) {              // the common case: block 0 is still in LDS
-    if (tid == 0) {
-      int pick = n_keep - 1;
-      double c = 0.0;
-      for (int i = 0; i < n_keep; ++i) {
-        c += ev[i];
-        if (s_target < c) { pick = i; break; }
-      }
-      s_pick = static_cast<int>(sel[pick]);
-    }
+    if (tid == 0) s_pick = static_cast<int>(sel[invert_weights(ev, n_keep, s_z2, s_u)]);
   } else {
+    const double target = s_u * s_z2;  // invert_weights, continued from block to block with the running sum in s_c
     upper = ~0ull;
     int last_tok = top_idx;
     for (int r = 0; r * kSampleThreads < n_keep; ++r) {
@@ -303,7 +231,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
         double c = s_c;
         for (int i = 0; i < lim; ++i) {
           c += ev[i];
-          if (s_target < c) { s_pick = static_cast<int>(sel[i]); break; }
+          if (target < c) { s_pick = static_cast<int>(sel[i]); break; }
         }
         s_c = c;
       }
@@ -323,7 +251,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
 __global__ __launch_bounds__(kSampleThreads) void sample_gumbel_kernel(const SampleArgs a) {
   __shared__ double sv[kSampleThreads / kWave];
   __shared__ int si[kSampleThreads / kWave];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
@@ -336,26 +264,22 @@ __global__ __launch_bounds__(kSampleThreads) void sample_gumbel_kernel(const Sam
   for (int i = tid; i < a.V; i += kSampleThreads) {
     double v = static_cast<double>(load_logit(row, a.dtype, i));
     if (scale) v = v / T;
-    uint32_t r0;
-    philox4x32_10(d, sid, static_cast<uint32_t>(i), kTagGumbel, a.seed_lo, a.seed_hi, r0);
-    const double u = (static_cast<double>(r0) + 0.5) * 2.3283064365386963e-10;
-    const double s = v + (-log(-log(u)));
+    const double s = v + gumbel_noise(d, sid, i, a.seed_lo, a.seed_hi);
     if (better_d(s, i, bv, bi)) { bv = s; bi = i; }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (better_d(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
-  __syncthreads();
+  block_arg_best<kSampleThreads / kWave, double, better_d>(bv, bi, sv, si);
   if (tid == 0) {
-    for (int w = 1; w < kSampleThreads / kWave; ++w)
-      if (better_d(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
     a.out[b] = bi;
     if (a.draw) a.draw[b] = a.draw[b] + 1u;
   }
+}
+
+// (the fields in declaration order, the seed split into the two Philox key words)
+static SampleArgs sample_args(const void* logits, int dtype, int64_t row_stride, int V, const int32_t* pos, int rows_per_b,
+                              const int32_t* active, float temperature, int top_k, float top_p, uint64_t seed, uint32_t* draw,
+                              uint32_t draw0, const int32_t* stream_id, int32_t* out) {
+  return SampleArgs{logits, dtype, row_stride, V, pos, rows_per_b, active, temperature, top_k, top_p, seed_lo32(seed), seed_hi32(seed),
+                    draw, draw0, stream_id, out};
 }
 
 int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
@@ -379,23 +303,8 @@ int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
 // the step's draw: entry b samples from row b*(K+1) + accept_len[b] of the verify logits
 int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
                        uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st) {
-  SampleArgs a{};
-  a.logits = logits;
-  a.dtype = SD_BF16;
-  a.row_stride = V;
-  a.V = V;
-  a.pos = s.accept_len;
-  a.rows_per_b = s.K + 1;
-  a.active = s.active;
-  a.temperature = temperature;
-  a.top_k = top_k;
-  a.top_p = top_p;
-  a.seed_lo = static_cast<uint32_t>(seed);
-  a.seed_hi = static_cast<uint32_t>(seed >> 32);
-  a.draw = draw;
-  a.stream_id = stream_id;
-  a.out = s.sampled;
-  return launch_sample(a, s.B, st);
+  return launch_sample(sample_args(logits, SD_BF16, V, V, s.accept_len, s.K + 1, s.active, temperature, top_k, top_p, seed, draw, 0,
+                                   stream_id, s.sampled), s.B, st);
 }
 
 }  // namespace sd
@@ -407,22 +316,6 @@ extern "C" int sd_sample_token(const void* logits, int logits_dtype, int64_t row
                                int top_k, float top_p, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
                                const int32_t* stream_id, int32_t* out_ids, void* stream) {
   clear_error();
-  SampleArgs a{};
-  a.logits = logits;
-  a.dtype = logits_dtype;
-  a.row_stride = row_stride;
-  a.V = V;
-  a.pos = pos;
-  a.rows_per_b = rows_per_b;
-  a.active = active;
-  a.temperature = temperature;
-  a.top_k = top_k;
-  a.top_p = top_p;
-  a.seed_lo = static_cast<uint32_t>(seed);
-  a.seed_hi = static_cast<uint32_t>(seed >> 32);
-  a.draw = draw_counters;
-  a.draw0 = draw0;
-  a.stream_id = stream_id;
-  a.out = out_ids;
-  return launch_sample(a, B, static_cast<hipStream_t>(stream));
+  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, temperature, top_k, top_p, seed,
+                                   draw_counters, draw0, stream_id, out_ids), B, static_cast<hipStream_t>(stream));
 }

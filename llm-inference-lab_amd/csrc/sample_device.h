@@ -1,6 +1,8 @@
-// Device building blocks shared by the samplers (csrc/sample.hip, csrc/spec_sample.hip): the Philox4x32-10 draw, the
-// row walkers, the total order of Gumbel scores and the kept set of a temperature -> top-k -> top-p shaped row
-// (row_survivors: the ONE definition of "tie at the cut"). Arithmetic as oracle/sampling_ref.py.
+// Device building blocks shared by the samplers (csrc/sample.hip, csrc/spec_sample.hip), one definition each: the row
+// walkers, the composite key and its selection pieces (bitonic sort, radix select), the kept set of a temperature -> top-k
+// -> top-p shaped row (row_survivors: the ONE definition of "tie at the cut"), the Philox4x32-10 draws (uniform, Gumbel
+// noise) and the inversion of a uniform through weights. The workgroup reductions and the total order of scores
+// (better_d) are in common.h. Arithmetic as oracle/sampling_ref.py.
 #pragma once
 
 #include <hip/hip_fp16.h>
@@ -52,21 +54,21 @@ __device__ __forceinline__ uint64_t composite_key(float x, int i) {
   return (static_cast<uint64_t>(order_key(x)) << kIdxBits) | static_cast<uint64_t>(((1u << kIdxBits) - 1u) - static_cast<uint32_t>(i));
 }
 
-// f(value, index) for every element of the row, 16-byte loads when the row allows it.
-// The visiting order differs between the two forms; every use below is order-independent.
+__device__ __forceinline__ int key_index(uint64_t c) {
+  constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1u;
+  return static_cast<int>(kIdxMask - static_cast<uint32_t>(c & kIdxMask));
+}
+
+// f(value, index) for every element of a bf16 row, each loaded word stored to dst as well when dst is not null: 16-byte accesses,
+// vector v = tid + 1024 j, when both pointers are 16-byte aligned and V % 8 == 0, else element i = tid + 1024 j.
 template <typename F>
-__device__ __forceinline__ void for_each_logit(const void* row, int dtype, int V, int tid, F&& f) {
-  const bool aligned = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
-  if (dtype == SD_F32 && aligned && (V & 3) == 0) {
-    const float4* p = static_cast<const float4*>(row);
-    for (int v = tid; v < (V >> 2); v += kSampleThreads) {
-      const float4 q = p[v];
-      f(q.x, 4 * v); f(q.y, 4 * v + 1); f(q.z, 4 * v + 2); f(q.w, 4 * v + 3);
-    }
-  } else if (dtype == SD_BF16 && aligned && (V & 7) == 0) {
-    const uint4* p = static_cast<const uint4*>(row);
+__device__ __forceinline__ void copy_and_visit_bf16_row(const uint16_t* src, uint16_t* dst, int V, int tid, F&& f) {
+  if ((((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) && (V & 7) == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(src);
+    uint4* o = reinterpret_cast<uint4*>(dst);
     for (int v = tid; v < (V >> 3); v += kSampleThreads) {
       const uint4 q = p[v];
+      if (dst) o[v] = q;
       const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -75,17 +77,110 @@ __device__ __forceinline__ void for_each_logit(const void* row, int dtype, int V
       }
     }
   } else {
+    for (int i = tid; i < V; i += kSampleThreads) {
+      const uint16_t w = src[i];
+      if (dst) dst[i] = w;
+      f(bf16_bits_to_float(w), i);
+    }
+  }
+}
+
+// f(value, index) for every element of the row, 16-byte loads when the row allows it.
+// The visiting order differs between the two forms; every use below is order-independent.
+template <typename F>
+__device__ __forceinline__ void for_each_logit(const void* row, int dtype, int V, int tid, F&& f) {
+  if (dtype == SD_BF16) return copy_and_visit_bf16_row(static_cast<const uint16_t*>(row), nullptr, V, tid, f);
+  if (dtype == SD_F32 && (reinterpret_cast<uintptr_t>(row) & 15) == 0 && (V & 3) == 0) {
+    const float4* p = static_cast<const float4*>(row);
+    for (int v = tid; v < (V >> 2); v += kSampleThreads) {
+      const float4 q = p[v];
+      f(q.x, 4 * v); f(q.y, 4 * v + 1); f(q.z, 4 * v + 2); f(q.w, 4 * v + 3);
+    }
+  } else {
     for (int i = tid; i < V; i += kSampleThreads) f(load_logit(row, dtype, i), i);
   }
 }
 
-__device__ __forceinline__ bool better_d(double v, int i, double bv, int bi) {
-  const bool vn = (v != v), bn = (bv != bv);
-  if (vn | bn) {
-    if (vn & bn) return i < bi;
-    return vn;
+// The two selection pieces below are called by every thread of a 1024-thread workgroup (barriers inside) on LDS of the caller.
+// Descending bitonic sort of keys[0, n), n a power of two.
+__device__ __forceinline__ void sort_desc(uint64_t* keys, int n) {
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < n / 2; t += kSampleThreads) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const uint64_t x = keys[lo], y = keys[hi];
+        if ((x < y) == desc) { keys[lo] = y; keys[hi] = x; }
+      }
+      __syncthreads();
+    }
   }
-  return (v > bv) | ((v == bv) & (i < bi));
+}
+
+struct RadixPick {   // what wave 0 hands the workgroup after a pass: the chosen digit, the keys above it, the keys in it
+  uint32_t digit, above, bucket;
+};
+
+// Radix select of the k-th largest composite key of the row (k 1-based), most significant digits first, in up to 5 passes
+// of 11/11/10/10/10 bits: a pass histograms the next digit of the keys that match the prefix decided so far (hist: 2048
+// words) and wave 0 picks the digit that holds the k-th. The passes stop once that digit's bucket holds <= stop_bucket keys
+// (0: never, all 52 bits are decided). Returns the decided high bits, right-aligned, and their number in `decided`: the
+// k-th key itself when decided == 52, else every key whose top `decided` bits are >= the return value is a candidate.
+__device__ __forceinline__ uint64_t radix_select(const void* row, int dtype, int V, int k, uint32_t stop_bucket, uint32_t* hist,
+                                                 RadixPick& pick, int& decided) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int widths[5] = {11, 11, 10, 10, 10};
+  uint64_t prefix = 0;       // decided high bits (right-aligned)
+  int need = k;              // rank of the wanted element inside the current bucket (1-based from the top)
+  decided = 0;
+  for (int p = 0; p < 5; ++p) {
+    const int w = widths[p];
+    const int shift = 52 - decided - w;
+    for (int i = tid; i < 2048; i += kSampleThreads) hist[i] = 0;
+    __syncthreads();
+    for_each_logit(row, dtype, V, tid, [&](float x, int i) {
+      const uint64_t c = composite_key(x, i);
+      if ((c >> (shift + w)) == prefix) atomicAdd(&hist[(c >> shift) & ((1u << w) - 1u)], 1u);
+    });
+    __syncthreads();
+    if (wave == 0) {
+      // lane l owns digits [32 l, 32 l + 32); scan from the top digit down
+      const int nb = 1 << w;
+      uint32_t local = 0;
+      for (int j = 0; j < 32; ++j) {
+        const int d = lane * 32 + j;
+        if (d < nb) local += hist[d];
+      }
+      uint32_t incl = local;  // suffix sum over lanes >= this one
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_down(incl, off, 64);
+        if (lane + off < 64) incl += o;
+      }
+      uint32_t above = incl - local;
+      if (above < static_cast<uint32_t>(need) && incl >= static_cast<uint32_t>(need)) {
+        for (int j = 31; j >= 0; --j) {
+          const int d = lane * 32 + j;
+          if (d >= nb) continue;
+          const uint32_t h = hist[d];
+          if (above + h >= static_cast<uint32_t>(need)) {
+            pick = RadixPick{static_cast<uint32_t>(d), above, h};
+            break;
+          }
+          above += h;
+        }
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << w) | pick.digit;
+    decided += w;
+    need -= static_cast<int>(pick.above);
+    const uint32_t bucket = pick.bucket;
+    __syncthreads();
+    if (bucket <= stop_bucket) break;
+  }
+  return prefix;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -100,13 +195,14 @@ struct SurvivorLds {
   double ev[kSampleMaxK];
   uint32_t hist[2048];
   double z;
-  uint32_t cnt, digit, above, bucket;
+  uint32_t cnt;
+  RadixPick pick;
   int n_keep;
 };
 
 // k = min(top_k, V) in 1..kSampleMaxK; every thread of the workgroup calls it (barriers inside)
 __device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, int dtype, int V, int k, float temperature, float top_p) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   // gather every element whose composite key, shifted right by `shift`, is >= `bound`
   auto gather = [&](uint64_t bound, int shift) {
     if (tid == 0) L.cnt = 0;
@@ -121,21 +217,6 @@ __device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, i
     });
     __syncthreads();
   };
-  // descending bitonic sort of sel[0, n), n a power of two
-  auto sort_desc = [&](int n) {
-    for (int size = 2; size <= n; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < n / 2; t += kSampleThreads) {
-          const int lo = 2 * t - (t & (stride - 1));
-          const int hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const uint64_t x = L.sel[lo], y = L.sel[hi];
-          if ((x < y) == desc) { L.sel[lo] = y; L.sel[hi] = x; }
-        }
-        __syncthreads();
-      }
-    }
-  };
 
   // ---- 1a. fast path: the k-th largest thread maximum bounds the k-th largest element from below
   {
@@ -146,7 +227,7 @@ __device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, i
     });
     L.sel[tid] = best;  // threads without an element hold 0: below every real key
     __syncthreads();
-    sort_desc(kSampleThreads);
+    sort_desc(L.sel, kSampleThreads);
     const uint64_t tau = L.sel[k - 1];  // k <= min(1024, V): at least k threads saw an element
     __syncthreads();
     gather(tau, 0);
@@ -154,73 +235,22 @@ __device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, i
 
   // ---- 1b. fallback: radix select on the composite key, most significant digits first
   if (L.cnt > static_cast<uint32_t>(kSampleSort)) {
-    const int widths[5] = {11, 11, 10, 10, 10};
-    uint64_t prefix = 0;       // decided high bits (right-aligned)
-    int decided = 0;           // number of decided bits (of 52)
-    int need = k;              // rank of the wanted element inside the current bucket (1-based from the top)
-    for (int p = 0; p < 5; ++p) {
-      const int w = widths[p];
-      const int shift = 52 - decided - w;
-      for (int i = tid; i < 2048; i += kSampleThreads) L.hist[i] = 0;
-      __syncthreads();
-      for_each_logit(row, dtype, V, tid, [&](float x, int i) {
-        const uint64_t c = composite_key(x, i);
-        if ((c >> (shift + w)) == prefix) atomicAdd(&L.hist[(c >> shift) & ((1u << w) - 1u)], 1u);
-      });
-      __syncthreads();
-      if (wave == 0) {
-        // lane l owns digits [32 l, 32 l + 32); scan from the top digit down
-        const int nb = 1 << w;
-        uint32_t local = 0;
-        for (int j = 0; j < 32; ++j) {
-          const int d = lane * 32 + j;
-          if (d < nb) local += L.hist[d];
-        }
-        uint32_t incl = local;  // suffix sum over lanes >= this one
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const uint32_t o = __shfl_down(incl, off, 64);
-          if (lane + off < 64) incl += o;
-        }
-        uint32_t above = incl - local;
-        if (above < static_cast<uint32_t>(need) && incl >= static_cast<uint32_t>(need)) {
-          for (int j = 31; j >= 0; --j) {
-            const int d = lane * 32 + j;
-            if (d >= nb) continue;
-            const uint32_t h = L.hist[d];
-            if (above + h >= static_cast<uint32_t>(need)) {
-              L.digit = d;
-              L.above = above;
-              L.bucket = h;
-              break;
-            }
-            above += h;
-          }
-        }
-      }
-      __syncthreads();
-      prefix = (prefix << w) | L.digit;
-      decided += w;
-      need -= static_cast<int>(L.above);
-      const uint32_t bucket = L.bucket;
-      __syncthreads();
-      if (bucket <= static_cast<uint32_t>(kSampleCap)) break;
-    }
+    int decided;
+    const uint64_t prefix = radix_select(row, dtype, V, k, kSampleCap, L.hist, L.pick, decided);
     gather(prefix, 52 - decided);
   }
 
   // ---- 2. sort the candidates (>= k of them, the k largest among them) descending
   int n_sort = 2;  // next power of two >= gathered count (workgroup-uniform)
   while (n_sort < static_cast<int>(L.cnt)) n_sort <<= 1;
-  sort_desc(n_sort);
+  sort_desc(L.sel, n_sort);
 
   // ---- 3. the k survivors in sorted order: weights in float64
   const double T = static_cast<double>(temperature);
   const bool scale = (temperature > 0.f) && (temperature != 1.0f);
   int my_idx = 0;
   if (tid < k) {
-    const uint64_t c = L.sel[tid] - 1;
-    my_idx = static_cast<int>(((1u << kIdxBits) - 1u) - static_cast<uint32_t>(c & ((1u << kIdxBits) - 1u)));
+    my_idx = key_index(L.sel[tid] - 1);
     double v = static_cast<double>(load_logit(row, dtype, my_idx));
     if (scale) v = v / T;
     L.ev[tid] = v;
@@ -240,8 +270,7 @@ __device__ __forceinline__ void row_survivors(SurvivorLds& L, const void* row, i
   if (tid == 0) {
     int n_keep = 1;
     double z2 = 1.0;
-    const bool finite = (m == m) && (m - m == 0.0);
-    if (finite) {
+    if (is_finite_d(m)) {
       n_keep = k;
       if (top_p < 1.0f) {
         const double tp = static_cast<double>(top_p);
@@ -283,5 +312,17 @@ __device__ __forceinline__ double philox_uniform(uint32_t draw, uint32_t sid, ui
   philox4x32_10(draw, sid, 0u, tag, seed_lo, seed_hi, r0);
   return static_cast<double>(r0) * 2.3283064365386963e-10;  // 2^-32
 }
+
+// the Gumbel noise -log(-log(u)), u = (r0 + 0.5) * 2^-32 in (0, 1), of Philox counter (draw, stream, element, kTagGumbel)
+__device__ __forceinline__ double gumbel_noise(uint32_t draw, uint32_t sid, int i, uint32_t seed_lo, uint32_t seed_hi) {
+  uint32_t r0;
+  philox4x32_10(draw, sid, static_cast<uint32_t>(i), kTagGumbel, seed_lo, seed_hi, r0);
+  const double u = (static_cast<double>(r0) + 0.5) * 2.3283064365386963e-10;  // 2^-32
+  return -log(-log(u));
+}
+
+// the Philox key words of a 64-bit seed
+inline uint32_t seed_lo32(uint64_t seed) { return static_cast<uint32_t>(seed); }
+inline uint32_t seed_hi32(uint64_t seed) { return static_cast<uint32_t>(seed >> 32); }
 
 }  // namespace sd

@@ -68,10 +68,9 @@ struct AgreeArgs {
   int32_t* q_arg;
 };
 
-__device__ __forceinline__ bool is_finite_d(double v) { return v - v == 0.0; }
-
 // f(target value, draft value, index) over elements [e0, e1) of two bf16 rows, e0 a multiple of 8: thread tid visits the chunks
 // e0 / 8 + tid + kAgreeThreads j, each in element order
+// (spec_sample.hip's for_each_pair visits in another order on unaligned rows; each file's float64 sums need its own: two walkers)
 template <typename F>
 __device__ __forceinline__ void for_each_pair_slice(const uint16_t* rp, const uint16_t* rq, int e0, int e1, int tid, bool vec, F&& f) {
   for (int base = e0 + 8 * tid; base < e1; base += 8 * kAgreeThreads) {
@@ -92,11 +91,8 @@ __device__ __forceinline__ void for_each_pair_slice(const uint16_t* rp, const ui
 
 // sums of two doubles over the workgroup, every thread gets both: xor tree inside a wave, then the waves in order
 __device__ __forceinline__ void block_sum2(double& x, double& y, double (*sh)[kAgreeWaves]) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    x += __shfl_xor(x, off, 64);
-    y += __shfl_xor(y, off, 64);
-  }
+  x = wave_reduce_sum_d(x);
+  y = wave_reduce_sum_d(y);
   if ((threadIdx.x & 63) == 0) {
     sh[0][threadIdx.x >> 6] = x;
     sh[1][threadIdx.x >> 6] = y;
@@ -163,14 +159,9 @@ __global__ __launch_bounds__(kAgreeThreads) void agree_partial_kernel(const Agre
     if (argmax_better(xp, i, pv, pi)) { pv = xp; pi = i; }
     if (argmax_better(xq, i, qv, qi)) { qv = xq; qi = i; }
   });
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float opv = __shfl_xor(pv, off, 64), oqv = __shfl_xor(qv, off, 64);
-    const int opi = __shfl_xor(pi, off, 64), oqi = __shfl_xor(qi, off, 64);
-    if (argmax_better(opv, opi, pv, pi)) { pv = opv; pi = opi; }
-    if (argmax_better(oqv, oqi, qv, qi)) { qv = oqv; qi = oqi; }
-  }
-  if (lane == 0) {
+  wave_reduce_argmax(pv, pi);
+  wave_reduce_argmax(qv, qi);
+  if (lane == 0) {   // both pairs in every thread behind ONE barrier: block_arg_best's fold, by all threads
     s_v[0][wave] = pv; s_i[0][wave] = pi;
     s_v[1][wave] = qv; s_i[1][wave] = qi;
   }

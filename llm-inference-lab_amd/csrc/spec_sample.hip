@@ -66,14 +66,8 @@ namespace sd {
 
 constexpr int kSpecWaves = kSampleThreads / kWave;
 
-__device__ __forceinline__ double gumbel_noise(uint32_t c, uint32_t sid, int i, uint32_t seed_lo, uint32_t seed_hi) {
-  uint32_t r0;
-  philox4x32_10(c, sid, static_cast<uint32_t>(i), kTagGumbel, seed_lo, seed_hi, r0);
-  const double u = (static_cast<double>(r0) + 0.5) * 2.3283064365386963e-10;  // 2^-32
-  return -log(-log(u));
-}
-
 // f(p value, q value, index) over two bf16 rows of V elements, 16-byte loads when both allow it
+// (spec_agree.hip's for_each_pair_slice visits in another order on unaligned rows; each file's float64 sums need its own: two walkers)
 template <typename F>
 __device__ __forceinline__ void for_each_pair(const uint16_t* rp, const uint16_t* rq, int V, int tid, F&& f) {
   const bool aligned = ((reinterpret_cast<uintptr_t>(rp) | reinterpret_cast<uintptr_t>(rq)) & 15) == 0;
@@ -93,47 +87,6 @@ __device__ __forceinline__ void for_each_pair(const uint16_t* rp, const uint16_t
     for (int i = tid; i < V; i += kSampleThreads) f(bf16_bits_to_float(rp[i]), bf16_bits_to_float(rq[i]), i);
   }
 }
-
-// workgroup-wide reductions; every thread gets the result. Fixed order: xor tree inside a wave, then the waves in order.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < kSpecWaves; ++w) r += sh[w];
-  return r;
-}
-
-__device__ __forceinline__ double block_max(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < kSpecWaves; ++w) r = fmax(r, sh[w]);
-  return r;
-}
-
-// best (score, index) of the workgroup under better_d; valid in thread 0
-__device__ __forceinline__ void block_best(double& bv, int& bi, double* sv, int* si) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (better_d(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < kSpecWaves; ++w)
-      if (better_d(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
-}
-
-__device__ __forceinline__ bool is_finite_d(double v) { return v - v == 0.0; }
 
 // ---------------------------------------------------------------------------------------------- draft draw + hand-over
 struct SpecDrawArgs {
@@ -159,34 +112,13 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const S
   const uint32_t sid = a.stream_id ? static_cast<uint32_t>(a.stream_id[b]) : static_cast<uint32_t>(b);
   double bv = -INFINITY;
   int bi = 0x7fffffff;
-  auto visit = [&](float x, int i) {
+  copy_and_visit_bf16_row(src, dst, V, tid, [&](float x, int i) {
     double v = static_cast<double>(x);
     if (scale) v = v / T;
     const double sc = v + gumbel_noise(c, sid, i, a.seed_lo, a.seed_hi);
     if (better_d(sc, i, bv, bi)) { bv = sc; bi = i; }
-  };
-  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  if (aligned && (V & 7) == 0) {
-    const uint4* p = reinterpret_cast<const uint4*>(src);
-    uint4* o = reinterpret_cast<uint4*>(dst);
-    for (int v = tid; v < (V >> 3); v += kSampleThreads) {
-      const uint4 w4 = p[v];
-      o[v] = w4;
-      const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        visit(__uint_as_float(w[j] << 16), 8 * v + 2 * j);
-        visit(__uint_as_float(w[j] & 0xffff0000u), 8 * v + 2 * j + 1);
-      }
-    }
-  } else {
-    for (int i = tid; i < V; i += kSampleThreads) {
-      const uint16_t w = src[i];
-      dst[i] = w;
-      visit(bf16_bits_to_float(w), i);
-    }
-  }
-  block_best(bv, bi, sv, si);
+  });
+  block_arg_best<kSpecWaves, double, better_d>(bv, bi, sv, si);
   if (tid == 0) {
     const int d = bi;   // always a valid index: V >= 1 and the first element visited beats the initial (-inf, INT_MAX)
     s.draft_tok[b * s.K + a.i] = d;
@@ -205,8 +137,8 @@ static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_
   a.i = i;
   a.V = V;
   a.temperature = temperature;
-  a.seed_lo = static_cast<uint32_t>(seed);
-  a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.seed_lo = seed_lo32(seed);
+  a.seed_hi = seed_hi32(seed);
   a.draw = draw;
   a.stream_id = stream_id;
   return a;
@@ -258,8 +190,10 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecSt
       mp = fmax(mp, vp);
       mq = fmax(mq, vq);
     });
-    mp = block_max(mp, sh);
-    mq = block_max(mq, sh);
+    // sh is reused from reduction to reduction: a barrier between two uses (the __syncthreads_or is one)
+    mp = block_max_d<kSpecWaves>(mp, sh);
+    __syncthreads();
+    mq = block_max_d<kSpecWaves>(mq, sh);
     const bool bad = __syncthreads_or(nan) || !is_finite_d(mp) || !is_finite_d(mq);
     if (!bad) {
       double sp = 0.0, sq = 0.0;
@@ -267,8 +201,9 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecSt
         sp += exp(scaled(xp) - mp);
         sq += exp(scaled(xq) - mq);
       });
-      sp = block_sum(sp, sh);
-      sq = block_sum(sq, sh);
+      sp = block_sum_d<kSpecWaves>(sp, sh);
+      __syncthreads();
+      sq = block_sum_d<kSpecWaves>(sq, sh);
       lse_p = mp + log(sp);
       lse_q = mq + log(sq);
       residual = true;
@@ -278,9 +213,7 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecSt
       d = d < 0 ? 0 : (d >= V ? V - 1 : d);
       double ratio = NAN;
       if (!bad) ratio = exp((scaled(bf16_bits_to_float(rp[d])) - lse_p) - (scaled(bf16_bits_to_float(rq[d])) - lse_q));
-      uint32_t r0;
-      philox4x32_10(c0 + static_cast<uint32_t>(i), sid, 0u, kTagCdf, a.seed_lo, a.seed_hi, r0);
-      const double u = static_cast<double>(r0) * 2.3283064365386963e-10;  // 2^-32
+      const double u = philox_uniform(c0 + static_cast<uint32_t>(i), sid, kTagCdf, a.seed_lo, a.seed_hi);
       a.flag[b * (K + 1) + i] = (u < ratio) ? 1 : 0;
       if (a.ratios) a.ratios[b * K + i] = ratio;
     }
@@ -303,8 +236,11 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecSt
       }
     }
   });
-  block_best(pv, pi, sv, si);
-  if (residual) block_best(rv, ri, sv, si);   // (workgroup-uniform)
+  block_arg_best<kSpecWaves, double, better_d>(pv, pi, sv, si);
+  if (residual) {   // (workgroup-uniform)
+    __syncthreads();   // thread 0 is done with sv / si
+    block_arg_best<kSpecWaves, double, better_d>(rv, ri, sv, si);
+  }
   if (tid == 0) a.cand[b * (K + 1) + i] = (residual && ri != 0x7fffffff) ? ri : pi;
 }
 
@@ -348,8 +284,8 @@ static SpecStatArgs spec_stat_args(const void* target_logits, const void* draft_
   sa.K = K;
   sa.V = V;
   sa.temperature = temperature;
-  sa.seed_lo = static_cast<uint32_t>(seed);
-  sa.seed_hi = static_cast<uint32_t>(seed >> 32);
+  sa.seed_lo = seed_lo32(seed);
+  sa.seed_hi = seed_hi32(seed);
   sa.draw = draw;
   sa.draw0 = draw0;
   sa.stream_id = stream_id;
@@ -379,13 +315,7 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(
   const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
   const uint16_t* src = a.src + (static_cast<size_t>(b) * a.src_rows_per_b + a.src_row) * V;
   uint16_t* dst = a.q + (static_cast<size_t>(b) * s.K + a.i) * V;
-  if ((((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) && (V & 7) == 0) {
-    const uint4* p = reinterpret_cast<const uint4*>(src);
-    uint4* o = reinterpret_cast<uint4*>(dst);
-    for (int v = tid; v < (V >> 3); v += kSampleThreads) o[v] = p[v];
-  } else {
-    for (int i = tid; i < V; i += kSampleThreads) dst[i] = src[i];
-  }
+  copy_and_visit_bf16_row(src, dst, V, tid, [](float, int) {});
   row_survivors(L, src, SD_BF16, V, min(sh.top_k, V), a.temperature, sh.top_p);
   if (tid == 0) {
     const uint32_t c = a.draw[b] + static_cast<uint32_t>(a.i);
@@ -403,14 +333,12 @@ int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per
                            hipStream_t st) {
   SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
   const SpecDrawArgs a = spec_draw_args(src, src_rows_per_b, src_row, q, i, V, temperature, seed, draw, stream_id);
+  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && (top_k <= 0 || V <= (1 << kIdxBits)) && src_rows_per_b >= 1 && src_row >= 0 &&
+                 src_row < src_rows_per_b, "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
   if (top_k > 0) {
-    SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
-               "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
     if (int rc = check_spec_shape("spec_draft_draw", top_k, top_p)) return rc;
     hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{top_k, top_p}, s);
   } else {
-    SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
-               "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
     hipLaunchKernelGGL(spec_draft_draw_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, s);
   }
   SD_LAUNCH_CHECK();
@@ -487,11 +415,8 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const
 
 // statistics, then accept; top_k == 0: spec_stats_kernel, else the shaped kernel
 static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st) {
-  if (top_k > 0)
-    SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && sa.V <= (1 << kIdxBits),
-               "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
-  else
-    SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1, "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && (top_k <= 0 || sa.V <= (1 << kIdxBits)),
+             "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
   SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
   if (top_k > 0) {
     if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
@@ -524,23 +449,33 @@ extern "C" size_t sd_spec_sample_workspace(int B, int K) {
   return static_cast<size_t>(B) * (K + 1) * 2 * sizeof(int32_t);
 }
 
-extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
-                                     int V, float temperature, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
-                                     const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
-                                     double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
-  clear_error();
-  SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "spec_sample_accept: NULL argument");
-  SD_REQUIRE(B >= 1 && K >= 1, "spec_sample_accept: B=%d K=%d", B, K);
-  SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "spec_sample_accept: workspace %zu B < %zu B", workspace_bytes,
+// the stand-alone op, shaped (top_k > 0) or not; `who` is the op's name in the messages
+static int spec_sample_accept_op(const char* who, int top_k, float top_p, const void* draft_logits, const void* target_logits,
+                                 const int32_t* draft_ids, int B, int K, int V, float temperature, uint64_t seed, uint32_t* draw_counters,
+                                 uint32_t draw0, const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out,
+                                 int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
+  SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "%s: NULL argument", who);
+  SD_REQUIRE(B >= 1 && K >= 1, "%s: B=%d K=%d", who, B, K);
+  SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "%s: workspace %zu B < %zu B", who, workspace_bytes,
              sd_spec_sample_workspace(B, K));
   SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && (!ratios_out || (reinterpret_cast<uintptr_t>(ratios_out) & 7) == 0),
-             "spec_sample_accept: misaligned workspace / ratios");
+             "%s: misaligned workspace / ratios", who);
   int32_t* flag = static_cast<int32_t*>(workspace);
   int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
   const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
                                          active, flag, cand, ratios_out);
   const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels(sa, aa, B, 0, 1.0f, static_cast<hipStream_t>(stream));
+  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
+                                     int V, float temperature, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
+                                     const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
+                                     double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  return spec_sample_accept_op("spec_sample_accept", 0, 1.0f, draft_logits, target_logits, draft_ids, B, K, V, temperature, seed,
+                               draw_counters, draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace,
+                               workspace_bytes, stream);
 }
 
 extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
@@ -553,16 +488,7 @@ extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void
   SD_REQUIRE(top_k > 0, "spec_sample_accept_shaped: top_k=%d with top_p=%g: the shaped op needs a top_k in 1..1024 (top_p without top_k, "
              "the full-vocabulary nucleus, is not supported; the unshaped op is sd_spec_sample_accept)", top_k, top_p);
   SD_REQUIRE(top_k <= kSampleMaxK, "spec_sample_accept_shaped: top_k=%d > %d is not supported", top_k, kSampleMaxK);
-  SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "spec_sample_accept_shaped: NULL argument");
-  SD_REQUIRE(B >= 1 && K >= 1, "spec_sample_accept_shaped: B=%d K=%d", B, K);
-  SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "spec_sample_accept_shaped: workspace %zu B < %zu B", workspace_bytes,
-             sd_spec_sample_workspace(B, K));
-  SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && (!ratios_out || (reinterpret_cast<uintptr_t>(ratios_out) & 7) == 0),
-             "spec_sample_accept_shaped: misaligned workspace / ratios");
-  int32_t* flag = static_cast<int32_t*>(workspace);
-  int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
-  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
-                                         active, flag, cand, ratios_out);
-  const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
+  return spec_sample_accept_op("spec_sample_accept_shaped", top_k, top_p, draft_logits, target_logits, draft_ids, B, K, V, temperature,
+                               seed, draw_counters, draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace,
+                               workspace_bytes, stream);
 }

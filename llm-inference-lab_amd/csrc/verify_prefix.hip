@@ -126,17 +126,10 @@ __global__ __launch_bounds__(kVerifyThreads) void verify_partial_kernel(
     }
   }
 
-  wave_reduce_argmax(bv, bi);
   __shared__ float s_v[kVerifyThreads / kWave];
   __shared__ int s_i[kVerifyThreads / kWave];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-  __syncthreads();
+  block_arg_best<kVerifyThreads / kWave, float, argmax_better>(bv, bi, s_v, s_i);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kVerifyThreads / kWave; ++w) {
-      if (argmax_better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
-    }
     ws_val[row * nsplit + split] = bv;
     ws_idx[row * nsplit + split] = bi;
   }
