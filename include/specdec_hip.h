@@ -244,7 +244,9 @@ typedef struct sd_model_config {
   const sd_layer_weights* layers; /* host array [n_layers] (copied by sd_model_create) */
   const void* packed;       /* optional: buffer written by sd_pack_weights for THIS config; the
                                GEMVs then stream the packed copy (the row-major matrices are no
-                               longer read by the forward, except tok_emb for the gather) */
+                               longer read by the forward, except tok_emb for the gather). A bf16 model
+                               may add a lossless 12-bit copy of it for the launches of 1..9 tokens
+                               (sd_model_set_w12); `packed` stays what every other launch reads */
 } sd_model_config;
 
 /* The weight quantiser of the fp8 storage mode on a row-major bf16 matrix [N][K]:
@@ -269,6 +271,35 @@ typedef struct sd_model sd_model;
 /* Create a model over caller-owned device weights (borrowed for the model's life). */
 int sd_model_create(const sd_model_config* cfg, sd_model** out);
 int sd_model_destroy(sd_model* m);
+
+/* W12: an ADDITIONAL, lossless copy of a bf16 model's packed matrices at ~0.76 of their bytes, streamed by the launches
+ * of 1..9 tokens (csrc/gemv.hip) in place of `packed`; every other reader (launches of more than 9 tokens, prefill, the
+ * persistent forward) keeps `packed`, and fp8 models have no W12 copy. Every (tile, 32-k step) block of a packed stream
+ * whose exponents fit a 16-value window is stored as 12-bit codes (sign, 4-bit exponent offset, mantissa) that widen to
+ * exactly the bf16 bits; other blocks stay raw (format: csrc/pack.hip, restated in specdec_hip/w12.py). Results are
+ * bit-identical with and without the copy. Built once per model, in three steps (cfg->packed: the bf16 buffer of
+ * sd_pack_weights; n_wide: HOST uint32 [4 * n_layers + 1], the wide-block count of every matrix):
+ *   sd_w12_measure   classifies and numbers the blocks of every matrix into `scratch` (device, 256-byte aligned,
+ *                    sd_w12_scratch_bytes) and returns the counts; synchronises `stream`.
+ *   sd_w12_bytes     size of the copy. A matrix takes part when its W12 bytes are at least 15 % below its packed bf16
+ *                    bytes and the W12 kernels cover its shape (whole 32-k steps per K slice); others contribute nothing.
+ *   sd_w12_pack      writes the copy to dst (device, 256-byte aligned); asynchronous on `stream`; scratch may be freed
+ *                    once it has run.
+ * sd_w12_matrix reports matrix `index` (4 * layer + 0 qkv / 1 out / 2 gate-up / 3 down; 4 * n_layers = the lm_head):
+ * whether it takes part, its offset in the copy, the padded bytes of its main stream, overflow and table, its table
+ * entries (blocks) and its packed bf16 bytes; any out pointer may be NULL.
+ * sd_model_set_w12 hands the copy to a model created from the same config (borrowed for the model's life; NULL: back to
+ * the bf16 streams). classes: which matrix classes read it, bit 0 qkv, 1 out, 2 gate / up, 3 down, 4 lm_head; the other
+ * classes keep their bf16 stream. SD_W12_DEFAULT_CLASSES is what the measurements kept. SPECDEC_NO_W12 in the environment keeps every launch on the bf16 stream (read per launch). */
+size_t sd_w12_scratch_bytes(const sd_model_config* cfg);
+int sd_w12_measure(const sd_model_config* cfg, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream);
+size_t sd_w12_bytes(const sd_model_config* cfg, const uint32_t* n_wide);
+int sd_w12_matrix(const sd_model_config* cfg, const uint32_t* n_wide, int index, int* taken, size_t* offset, size_t* main_bytes,
+                  size_t* ovf_bytes, size_t* table_bytes, size_t* blocks, size_t* bf16_bytes);
+int sd_w12_pack(const sd_model_config* cfg, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream);
+#define SD_W12_SKIP 0xFFFFFFFFu          /* n_wide[i] = SD_W12_SKIP (set by the caller after sd_w12_measure): matrix i is left out of the copy */
+#define SD_W12_DEFAULT_CLASSES 0x10u   /* the lm_head: the one class the 5-token probes of 3B shapes found faster (profiles/w12_verify.md) */
+int sd_model_set_w12(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes);
 
 /* Tokens one pass of sd_model_forward covers: 128 or 64 when every matrix of the model has a shape the
  * multi-token kernel (gemm_skinny.hip) handles at that size, else 9 or fewer (x rows must fit the LDS). Larger B*M are tiled into passes. */
@@ -488,6 +519,9 @@ int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_p
  *                                              storage, B loads per batch
  *   "skinny:" + a name of sd_gemm_plan         T rows of K do not fit the LDS and csrc/gemm_skinny.hip takes the launch
  *                                              (K = 14336 at 6..9 tokens): the body that runs, at T < 10
+ * w8 = 2 in either function asks for a bf16 matrix that has a W12 copy (sd_model_set_w12): where the W12 kernels cover the
+ * shape the names end in ",w12>" for a fixed instance (W12 twins exist at token bound 5; a fixed class at another token
+ * count runs the generic W12 kernel) and carry DT = w12 for the generic kernel; SPECDEC_NO_W12 turns both back to bf16.
  * Follows SPECDEC_GEMV_GENERIC at every call. Refused as sd_gemv_variant refuses, and where launch_gemv would refuse the
  * launch (fp8 storage whose K slices are not whole 64-k steps; rows that fit neither kernel). Host-only, additive
  * (SD_ABI_VERSION stays 1). */

@@ -22,6 +22,7 @@ constexpr const char* kNoAttnSplit = "SPECDEC_NO_ATTN_SPLIT";       // attention
 constexpr const char* kNoGemmPrefill = "SPECDEC_NO_GEMM_PREFILL";   // prompts always go through the 128-token passes (tests: the two prefill paths against each other)
 constexpr const char* kPrefillMinTokens = "SPECDEC_PREFILL_MIN_TOKENS";   // shortest pass that takes the GEMM prefill path (default kPrefillMinTokens; read once)
 constexpr const char* kGemvGeneric = "SPECDEC_GEMV_GENERIC";         // set: gemv.hip never takes a fixed-geometry instance (read at every launch; A/B runs, tests of both paths)
+constexpr const char* kNoW12 = "SPECDEC_NO_W12";                    // set: gemv.hip streams the packed bf16 weights even where the model has a W12 copy (read at every launch; A/B runs, tests)
 constexpr const char* kMedusaPerHead = "SPECDEC_MEDUSA_PER_HEAD";   // Medusa heads: one launch per head even when they sit at a constant stride
 // ---- measurement hooks (sd_model_probe_gemv) --------------------------------------------------------------------------------
 constexpr const char* kGemvTimeline = "SPECDEC_GEMV_TIMELINE";      // in-kernel 100 MHz stamps of the probed launch, printed to stderr ("2": per workgroup too)

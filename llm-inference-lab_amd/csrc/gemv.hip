@@ -143,16 +143,23 @@ __device__ __forceinline__ void stage_x(const GemvArgs& a, uint16_t* xs, int KP,
 //   aliased below the 9-token bound). The run-time index arithmetic and the kernel-uniform branches on those fields fold away in front of the first
 //   weight load; sums, rounding points and the thread -> item map are those of the generic kernel (FKS = -1), which stays
 //   the fallback and the reference (SPECDEC_GEMV_GENERIC=1 forces it).
-template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE>
+//   W12 = the weights are the lossless 12-bit copy of csrc/pack.hip (same blocks, same order): a lane loads the 12 bytes of its
+//   chunk (global_load_dwordx3, at an address that does not depend on the side table) and widens its 8 codes to the bf16 bits
+//   they stand for with ~30 integer VALU instructions; the rare wide block adds a fourth dword from the overflow stream. Whether
+//   a block is wide, and its exponent base, come from the side table: one vector load per batch, issued in front of the batch's
+//   weight loads and read with readlane (wave-uniform branches). MFMA operands, sums and epilogues are those of the bf16 kernel:
+//   every output is bit-identical by construction. 3/4 of the HBM bytes (+ ~1 % for wide blocks and the table).
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, bool W12 = false>
 __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs a) {
   constexpr int kBatch = KB;
   constexpr bool FIX = FKS >= 0;
+  static_assert(!W12 || (!MASK && !W8), "W12: bf16 matrices in whole 32-k steps");
   // a geometry field of the argument block, or its compile-time value in a fixed instance. Used IN PLACE of the field, where
   // the generic kernel reads it, so that the generic instantiations compile to the instructions they had before
 #define SD_GEOM(field, fixed) (FIX ? (fixed) : (a.field))
 #define SD_ALIASED SD_GEOM(alias_part, TT == kGemvMaxT && a.alias_part)   // (9 rows of K = 8192 are the one fixed shape that aliases)
   static_assert(!FIX || (!MASK && !W8 && EPI != EPI_ARGMAX && EPI != EPI_GELU && FTP >= 1 && FTP <= 8 && FKS <= 4), "fixed instances: bf16 Llama layer matrices");
-  pin_gemv_args<EPI, W8>(a);
+  pin_gemv_args<EPI, W8, W12>(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int K = a.K, T = a.T;
   const int KP = K + kXPad;
@@ -205,11 +212,16 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   unsigned lane_off = 0;
   auto tile_base = [&](int tile) -> const uint16_t* {
     const int p0 = p_lo + tile * tile_pairs;
-    if (SD_GEOM(packed, true)) {
+    if (W12 || SD_GEOM(packed, true)) {   // (W12 is a packed layout: the row-major branch below is not compiled into its instances)
       int np = min(tile_pairs, p_hi - p0);
       if (np < 1) np = 1;
       int jp = n & 7, second = n >> 3;
       if (jp >= np) { jp = 0; second = 0; }  // alias a valid lane: same address, no extra traffic
+      if constexpr (W12) {   // 12 bytes per chunk: 3/4 of every bf16 offset
+        wstride = np * 48;
+        lane_off = static_cast<unsigned>((g * 2 * np + second * np + jp) * 6);
+        return W + static_cast<size_t>(p0) * (K32 >> 1) * 3 + static_cast<size_t>(k_begin >> 5) * wstride;
+      }
       wstride = np * 64;
       lane_off = static_cast<unsigned>((g * 2 * np + second * np + jp) * 8);
       if constexpr (W8) return W + static_cast<size_t>(p0) * ((K + 63) & ~63) + static_cast<size_t>(k_begin >> 6) * wstride;  // 1 byte per weight
@@ -227,6 +239,45 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   };
 
   u32x4 buf[kBatch];
+  // a lane's load of one step: its 16-byte chunk, or the 12 bytes of its W12 slot (4-byte aligned: lane * 12)
+  typedef unsigned int u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+  auto load_chunk = [&](const uint16_t* ubase, unsigned s) -> u32x4 {
+    const char* p = reinterpret_cast<const char*>(ubase) + (s * static_cast<unsigned>(wstride) + lane_off) * 2u;
+    if constexpr (W12) {
+      const auto v = __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4*>(p));
+      return u32x4{v[0], v[1], v[2], 0u};
+    } else {
+      return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+    }
+  };
+  // W12 side table: lane j of `ent` holds the entry of step s0 + j of the batch (clamped to the slice, as the loads are)
+  const uint32_t* w12_tab = reinterpret_cast<const uint32_t*>(a.w_scale);
+  uint32_t ent = 0;
+  auto load_ent = [&](int tile, int s0) {
+    if constexpr (W12) {
+      const unsigned tb = (static_cast<unsigned>(blockIdx.x) * static_cast<unsigned>(SD_GEOM(n_tiles_full, tiles_per_round)) + static_cast<unsigned>(tile)) * static_cast<unsigned>(K32 >> 5) + static_cast<unsigned>(k_begin >> 5);
+      ent = w12_tab[tb + static_cast<unsigned>(min(s0 + lane, steps - 1))];
+    }
+  };
+  // the fourth dword of the batch's wide blocks (wave-uniform branch per step; ~3 % of the blocks of N(0, s) weights). Fixed
+  // instances keep them in registers of their own, written and read only under that branch: loaded into buf[j][3], the
+  // widening of a NARROW block j (which uses that register as a temporary) waits for every load of the batch, vmcnt(0), instead
+  // of for its own. The generic kernel, 40 VGPRs fuller, takes that wait (the 12 extra registers spilled 1-4 of them).
+  constexpr bool kWide4 = W12 && FIX;
+  uint32_t wide4[kWide4 ? kBatch : 1];
+  auto issue_wide = [&](int s0) {
+    if constexpr (W12) {
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) {
+        const uint32_t e = __builtin_amdgcn_readlane(ent, j);
+        if ((e >> 31) && s0 + j < steps) {
+          const uint32_t v = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(static_cast<const char*>(a.w12_ovf) + static_cast<size_t>(e & 0x7FFFFFu) * kW12OvfBlock) + lane_off / 6u);
+          if constexpr (kWide4) wide4[j] = v;
+          else buf[j][3] = v;
+        }
+      }
+    }
+  };
   // first batch: unconditional (steps past the slice re-read its last step; never used). It is
   // issued in two parts: kPre loads per wave before the prologue (64 KiB per CU: enough to keep
   // HBM busy, few enough not to fill the CU's memory queue, which would stall the waves at
@@ -238,7 +289,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
         // (32-bit element offsets from the wave-uniform tile base: a workgroup's share of a matrix is far below 2^31 elements; as
         //  size_t products every load of the batch cost ~11 scalar instructions of 64-bit address arithmetic in the launch's preamble)
         const unsigned s = (j < steps) ? j : steps - 1;
-        buf[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ubase) + (s * static_cast<unsigned>(wstride) + lane_off) * 2u));
+        buf[j] = load_chunk(ubase, s);
       }
     }
   };
@@ -248,7 +299,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
       const int s = s0 + j;
       bool ok = s < steps;  // wave-uniform
       if constexpr (MASK && !W8) ok = ok && (a.packed ? (k_begin + s * 32 < K32) : (k_begin + s * 32 + g * 8 + 8 <= K));
-      if (ok) buf[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ubase) + (static_cast<unsigned>(s) * static_cast<unsigned>(wstride) + lane_off) * 2u));
+      if (ok) buf[j] = load_chunk(ubase, static_cast<unsigned>(s));
       else buf[j] = u32x4{0u, 0u, 0u, 0u};
     }
   };
@@ -262,6 +313,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
   // per-row adaptive K: a launch of a draft forward no row needs leaves here — after the index arithmetic above, which
   // runs under the latency of the argument loads (at kernel entry the branch kept it behind them: 0.5 % of the step)
   SD_SKIP_IF_INACTIVE(a.skip_k, a.skip_i);
+  load_ent(tslot < n_tiles ? tslot : 0, 0);   // W12: the first batch's table entries, the launch's first vector load
 
   // ---- x staging, fast path (K <= 8192): thread `tid` owns the 16-byte chunk `tid` of every
   // token row. Its loads (x rows, norm weights, the residual value of its epilogue item) are
@@ -286,7 +338,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
       for (int t = 0; t < TT; ++t) rows[t] = a.x_row[(t < T) ? t : T - 1];
 #pragma unroll
       for (int t = 0; t < TT; ++t) xr[t] = *reinterpret_cast<const u32x4*>(xin + static_cast<size_t>(rows[t]) * a.x_stride + cidx * 8);
-    } else if (FIX && !wave_loads) {
+    } else if (FIX && !W12 && !wave_loads) {   // (W12: every wave loads, as in the generic kernel — see the norm weights below)
 #pragma unroll
       for (int t = 0; t < TT; ++t) xr[t] = u32x4{0u, 0u, 0u, 0u};
     } else {
@@ -297,7 +349,8 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
       }
     }
     if (SD_GEOM(prologue, FPRO) != PRO_NONE) {  // kernel-uniform
-      if (!FIX || wave_loads) {
+      // (W12: unconditional, at the clamped index — under the branch hipcc waited for this load at the join, vmcnt(0), in front of the weight stream)
+      if (!FIX || W12 || wave_loads) {
         nw4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_w) + cidx * 8);
         if (SD_GEOM(prologue, FPRO) == PRO_LAYERNORM) nb4 = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.norm_b) + cidx * 8);
       }
@@ -386,6 +439,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
     __syncthreads();
   }
   if constexpr (!MASK) issue_first(wrow0, kPre, kBatch);
+  issue_wide(0);
   stamp(2);
 
   float best_v = -INFINITY;
@@ -403,7 +457,11 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
     if (tile < n_tiles) {
       const uint16_t* wrow = (r == 0) ? wrow0 : tile_base(tile);
       for (int s0 = 0; s0 < steps; s0 += kBatch) {
-        if (r != 0 || s0 != 0) issue(wrow, s0);
+        if (r != 0 || s0 != 0) {
+          load_ent(tile, s0);
+          issue(wrow, s0);
+          issue_wide(s0);
+        }
 #pragma unroll
         for (int j = 0; j < kBatch; ++j) {
           const int s = s0 + j;
@@ -430,7 +488,13 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
               } else {
                 xb = *reinterpret_cast<const u32x4*>(xrow + s * 32);
               }
-              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, buf[j]),
+              u32x4 wv = buf[j];
+              if constexpr (W12) {
+                const uint32_t e = __builtin_amdgcn_readlane(ent, j);   // wave-uniform
+                if (e >> 31) { if constexpr (kWide4) wv[3] = wide4[j]; }
+                else wv = w12_widen(buf[j], ((e >> 23) & 0xFFu) * 0x00800080u);
+              }
+              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wv),
                                                             __builtin_bit_cast(bf16x8_t, xb), acc, 0, 0, 0);
             }
           }
@@ -516,12 +580,12 @@ int gemv_grid(const GemvArgs& a, int* ppw_out) {
   return q.grid;
 }
 
-template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE>
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, bool W12 = false>
 static int launch_one(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
   // dynamic LDS above 64 KiB has to be opted into once per kernel
   static unsigned long long attr_set = 0;
-  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO>), 160 * 1024, attr_set)) return rc;  // whole LDS of the CU
-  hipLaunchKernelGGL((gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO>), dim3(grid, a.batch_bytes ? a.n_batch : 1), dim3(kGemvThreads), smem, st, a);
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO, W12>), 160 * 1024, attr_set)) return rc;  // whole LDS of the CU
+  hipLaunchKernelGGL((gemv_mfma_kernel<EPI, MASK, TT, W8, KB, FKS, FTP, FPRO, W12>), dim3(grid, a.batch_bytes ? a.n_batch : 1), dim3(kGemvThreads), smem, st, a);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -536,7 +600,8 @@ static int gemv_tt(int T) { return T <= 1 ? 1 : T <= 2 ? 2 : T <= 3 ? 3 : T <= 5
 // ------------------------------------------------------------------------------
 // fixed-geometry instances: the (epilogue, K slices, pairs per tile, prologue) classes of the bf16 Llama layer matrices at
 // 1B / 3B / 8B dimensions, each at the five token bounds and both batch depths. Everything else — the lm_head (multi-round),
-// fp8, MASK shapes (8B down: K = 14336), GPT-2, gathered rows, biases, batched heads — runs the generic kernel.
+// fp8, MASK shapes (8B down: K = 14336), GPT-2, gathered rows, biases, batched heads — runs the generic kernel. Every class has
+// a W12 twin at token bound 5 (kW12FixedTT), taken when the matrix streams its W12 copy.
 // ------------------------------------------------------------------------------
 #define SD_GEMV_FIXED_TABLE(X)                                                          \
   X(EPI_QKV_ROPE, 4, 6, PRO_RMSNORM) /* 1B qkv: 1536 pairs */                           \
@@ -585,8 +650,18 @@ struct GemvChoice {
   bool alias;      // the partials alias the x rows in LDS
   int fixed;       // GEMV_FIXED: index into kGemvFixed
   size_t smem;     // dynamic LDS of the launch
+  bool w12;        // GEMV_GENERIC / GEMV_FIXED: the W12 twin of the kernel, over the matrix's W12 copy
 };
-static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain, bool hand_over) {
+// token bound at which the fixed-geometry instances have W12 twins: 5, the verify pass of a K = 4 step. A W12 launch of a
+// fixed class at another token count runs the generic W12 kernel.
+constexpr int kW12FixedTT = 5;
+bool gemv_w12_covers(int n_pairs, int K) {
+  if (n_pairs < 1 || K < 32) return false;
+  const GemvGeom q = gemv_geometry(n_pairs, K);
+  return q.kw * q.ksplit == K && K / 8 <= kGemvThreads;   // no MASK variant: whole 32-k steps, register-staged x
+}
+// `w12`: the matrix has a W12 copy and the launch may use it (packed bf16, not batched); SPECDEC_NO_W12 is read at every call
+static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain, bool hand_over, bool w12 = false) {
   GemvChoice c{};
   c.q = gemv_geometry(n_pairs, K);
   c.fixed = -1;
@@ -609,6 +684,8 @@ static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, 
     return c;
   }
   c.fixed = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, plain);
+  c.w12 = w12 && !w8 && !c.mask && !getenv(debug_env::kNoW12);
+  if (c.w12 && c.tt != kW12FixedTT) c.fixed = -1;
   c.route = c.fixed >= 0 ? GEMV_FIXED : GEMV_GENERIC;
   return c;
 }
@@ -631,8 +708,20 @@ static int launch_epi_w(const GemvArgs& a, const GemvChoice& c, int grid, hipStr
   }
 }
 
+template <int EPI, int KB>
+static int launch_epi_w12(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  switch (c.tt) {
+    case 1: return launch_one<EPI, false, 1, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+    case 2: return launch_one<EPI, false, 2, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+    case 3: return launch_one<EPI, false, 3, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+    case 5: return launch_one<EPI, false, 5, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+    default: return launch_one<EPI, false, kGemvMaxT, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+  }
+}
+
 template <int EPI>
 static int launch_epi(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  if (c.w12) return c.deep ? launch_epi_w12<EPI, kBatchDeep>(a, c, grid, st) : launch_epi_w12<EPI, kBatchShallow>(a, c, grid, st);
   if (a.w8) return c.deep ? launch_epi_w<EPI, true, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, true, kBatchShallow>(a, c, grid, st);
   return c.deep ? launch_epi_w<EPI, false, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, false, kBatchShallow>(a, c, grid, st);
 }
@@ -640,28 +729,28 @@ static int launch_epi(const GemvArgs& a, const GemvChoice& c, int grid, hipStrea
 static const char* const kEpiNames[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
 static const char* const kProNames[] = {"none", "rmsnorm", "layernorm"};
 
-static int gemv_fixed_name(int i, int tt, bool deep, char* out, size_t cap) {
+static int gemv_fixed_name(int i, int tt, bool deep, char* out, size_t cap, bool w12 = false) {
   const GemvFixed& f = kGemvFixed[i];
-  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d>", kEpiNames[f.epi], 1 << f.ks_shift, f.tile_pairs, kProNames[f.prologue], tt,
-                  deep ? kBatchDeep : kBatchShallow);
+  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d%s>", kEpiNames[f.epi], 1 << f.ks_shift, f.tile_pairs, kProNames[f.prologue], tt,
+                  deep ? kBatchDeep : kBatchShallow, w12 ? ",w12" : "");
 }
 
-int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap) {
-  const int i = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, true);
-  if (i < 0) return snprintf(out, cap, "generic");
-  return gemv_fixed_name(i, gemv_tt(T), gemv_deep(T, gemv_geometry(n_pairs, K).kw, false), out, cap);
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, bool w12) {
+  const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true, w12);
+  if (c.route != GEMV_FIXED) return snprintf(out, cap, "generic");
+  return gemv_fixed_name(c.fixed, c.tt, c.deep, out, cap, c.w12);
 }
 
-int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len) {
-  const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true);
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, bool w12) {
+  const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true, w12);
   if (int rc = gemv_choice_refused(c, T, K)) return rc;
   if (c.route == GEMV_FIXED) {
-    *len = gemv_fixed_name(c.fixed, c.tt, c.deep, out, cap);
+    *len = gemv_fixed_name(c.fixed, c.tt, c.deep, out, cap, c.w12);
   } else if (c.route == GEMV_SKINNY) {
     const int n = snprintf(out, cap, "skinny:");
     *len = n + gemm_plan_name(gemm_plan(T, n_pairs, K, w8, prologue, epi, 0), epi, w8, out + n, static_cast<size_t>(n) < cap ? cap - n : 0);
   } else {
-    *len = snprintf(out, cap, "generic<%s,%s,tt%d,%s,kb%d>", kEpiNames[epi], c.mask ? "mask" : "whole", c.tt, w8 ? "fp8" : "bf16",
+    *len = snprintf(out, cap, "generic<%s,%s,tt%d,%s,kb%d>", kEpiNames[epi], c.mask ? "mask" : "whole", c.tt, c.w12 ? "w12" : w8 ? "fp8" : "bf16",
                     c.deep ? kBatchDeep : kBatchShallow);
   }
   return 0;
@@ -674,6 +763,9 @@ static int launch_fixed_tt(const GemvArgs& a, const GemvChoice& c, int grid, hip
 }
 template <int EPI, int KS, int TP, int PRO>
 static int launch_fixed(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
+  if (c.w12)   // (gemv_choose: c.tt == kW12FixedTT)
+    return c.deep ? launch_one<EPI, false, kW12FixedTT, false, kBatchDeep, KS, TP, PRO, true>(a, grid, c.smem, st)
+                  : launch_one<EPI, false, kW12FixedTT, false, kBatchShallow, KS, TP, PRO, true>(a, grid, c.smem, st);
   switch (c.tt) {
     case 1: return launch_fixed_tt<EPI, KS, TP, PRO, 1>(a, c, grid, st);
     case 2: return launch_fixed_tt<EPI, KS, TP, PRO, 2>(a, c, grid, st);
@@ -696,9 +788,15 @@ int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
   SD_REQUIRE(!a.w8 || (a.packed && a.w_scale), "gemv: fp8 weights need the packed layout and row scales");
   // one workgroup (16 waves) per CU with an equal, contiguous share of the row pairs, cut into
   // a power-of-two count of <= 8-pair tiles; the 16 waves take (tile, K-slice) units
-  const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes, !a.x_row && !a.batch_bytes);
+  const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes, !a.x_row && !a.batch_bytes,
+                                   a.w12_main && a.w12_table && a.packed && !a.batch_bytes);
   if (int rc = gemv_choice_refused(c, a.T, a.K)) return rc;
   if (c.route == GEMV_SKINNY) return launch_gemm_skinny(a_in, epi, st);
+  a.w12 = c.w12 ? 1 : 0;
+  if (c.w12) {   // the W12 copy in place of the packed bf16 stream; the table takes the (unused) row-scale slot in line 1 of the block
+    a.W = a.w12_main;
+    a.w_scale = reinterpret_cast<const float*>(a.w12_table);
+  }
   const int grid = c.q.grid;
   a.ppw = c.q.ppw;
   a.tile_pairs = c.q.tile_pairs;

@@ -21,6 +21,38 @@ __device__ __forceinline__ float gelu_new(float x) {
   return 0.5f * x * (1.0f + tanhf(c * (x + 0.044715f * x * x * x)));
 }
 
+// ---- W12 (csrc/pack.hip): a lane's 8 weights of a narrow block as 12-bit codes  sign<<11 | (exp - base)<<7 | mantissa,
+// weight i at bit 12*i of its 12 bytes. Widening is exact: ((c & 0x800) << 4) | ((c & 0x7ff) + (base << 7)), two codes per
+// dword; base + 15 <= 255, so the add never reaches bit 15. base2 = (base << 7) * 0x10001 (wave-uniform: scalar registers).
+__device__ __forceinline__ uint32_t w12_widen_pair(uint32_t t, uint32_t base2) {   // t: two codes in bits 0..23 (higher bits: anything)
+  const uint32_t x = (t & 0xFFFu) | ((t << 4) & 0x0FFF0000u);
+  return ((x & 0x08000800u) << 4) | ((x & 0x07FF07FFu) + base2);
+}
+__device__ __forceinline__ u32x4 w12_widen(const u32x4 v, uint32_t base2) {   // v[0..2]: the codes; v[3] unused
+  u32x4 o;
+  o[0] = w12_widen_pair(v[0], base2);
+  o[1] = w12_widen_pair(__builtin_amdgcn_alignbit(v[1], v[0], 24), base2);
+  o[2] = w12_widen_pair(__builtin_amdgcn_alignbit(v[2], v[1], 16), base2);
+  o[3] = w12_widen_pair(v[2] >> 8, base2);
+  return o;
+}
+// the packer's side: exponent offsets are taken mod 16, so a block that does not fit the window widens to OTHER bits —
+// pack.hip keeps a block narrow only if w12_widen(w12_encode(v)) == v for all its weights
+__device__ __forceinline__ u32x4 w12_encode(const u32x4 v, uint32_t base) {
+  uint32_t c[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t h = (v[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+    c[i] = ((h >> 15) << 11) | (((((h >> 7) & 0xFFu) - base) & 0xFu) << 7) | (h & 0x7Fu);
+  }
+  u32x4 o;
+  o[0] = c[0] | (c[1] << 12) | (c[2] << 24);
+  o[1] = (c[2] >> 8) | (c[3] << 4) | (c[4] << 16) | (c[5] << 28);
+  o[2] = (c[5] >> 4) | (c[6] << 8) | (c[7] << 20);
+  o[3] = 0u;
+  return o;
+}
+
 // Kernel arguments into SGPRs at kernel entry: hipcc loads a by-value argument struct lazily, next to each first
 // use, which puts 5-6 DEPENDENT scalar-cache round trips (s_load -> s_waitcnt) in front of the first vector load of
 // these latency-bound kernels (0.7 us from wave entry to the first weight load in the in-kernel timeline). One empty
@@ -28,7 +60,7 @@ __device__ __forceinline__ float gelu_new(float x) {
 // back to back (merged into x8 / x16 loads) and waited for once. (Inputs only: as in/out operands the pointers lose
 // their address space, every load becomes a flat_load and the counted vmcnt waits of the prologue are gone.)
 // (SD_PIN: common.h)
-template <int EPI, bool W8>
+template <int EPI, bool W8, bool W12 = false>
 __device__ __forceinline__ void pin_gemv_args(const GemvArgs& a) {
   SD_PIN("s"(a.W), "s"(a.x), "s"(a.out), "s"(a.norm_w), "s"(a.norm_b), "s"(a.bias), "s"(a.x_row), "s"(a.skip_k), "s"(a.debug_ts),
          "s"(a.N), "s"(a.K), "s"(a.n_pairs), "s"(a.kw), "s"(a.x_stride), "s"(a.out_stride), "s"(a.m_magic), "s"(a.norm_eps),
@@ -36,7 +68,7 @@ __device__ __forceinline__ void pin_gemv_args(const GemvArgs& a) {
          "s"(static_cast<int>(a.tile_pairs)), "s"(static_cast<int>(a.ksplit)), "s"(static_cast<int>(a.alias_part)),
          "s"(static_cast<int>(a.packed)), "s"(static_cast<int>(a.prologue)), "s"(static_cast<int>(a.ks_shift)),
          "s"(static_cast<int>(a.skip_i)));
-  if constexpr (W8) SD_PIN("s"(a.w_scale));
+  if constexpr (W8 || W12) SD_PIN("s"(a.w_scale));   // (W12: the side table)
   if constexpr (EPI == EPI_QKV_ROPE)
     SD_PIN("s"(static_cast<int>(a.head_dim)), "s"(static_cast<int>(a.n_q_heads)), "s"(static_cast<int>(a.n_kv_heads)), "s"(a.pos_base), "s"(a.pos_off), "s"(a.rope_cos),
            "s"(a.rope_sin), "s"(a.max_pos), "s"(a.k_cache), "s"(a.v_cache), "s"(a.l_max), "s"(static_cast<int>(a.half_shift)),

@@ -52,13 +52,13 @@ struct GemvArgs {
   unsigned alias_part : 1;    // partial sums alias the staged x rows (set by launch_gemv)
   unsigned packed : 1;        // W is in the packed tile-stream order of csrc/pack.hip
   unsigned w8 : 1;            // W holds OCP fp8 e4m3 values (packed only); acc of row r is scaled by w_scale[r]
-  unsigned : 1;
+  unsigned w12 : 1;           // set by launch_gemv: W is the W12 main stream, w_scale its side table (see w12_main below)
   unsigned prologue : 2;      // GemvPrologue
   unsigned out_dtype : 2;     // SD_BF16 | SD_F32 (logits only)
   unsigned skip_i : 4;
   int half_shift : 8;         // log2(head_dim / 2), or -1 when head_dim / 2 is not a power of two (division fallback)
   // ---- epilogue-specific
-  const float* w_scale;          // fp32 [N] row scales (w8)
+  const float* w_scale;          // fp32 [N] row scales (w8); w12: the uint32 side table (in line 1 of the block: a wave's first load)
   // QKV epilogue: one 64-byte line (bytes 128..191)
   const int32_t* pos_base;  // device [B]
   const float* rope_cos;    // [max_pos][head_dim/2] or null (no RoPE)
@@ -88,6 +88,11 @@ struct GemvArgs {
   int xstat_n;
   float* xstat_out;
   const float* xstat_in;
+  // W12 copy of the matrix (csrc/pack.hip: lossless 12-bit codes), or null. W stays the packed bf16 stream: launch_gemv
+  // moves a launch of <= 9 tokens that the W12 kernels cover onto w12_main / w12_table, everything else reads W.
+  const void* w12_main;
+  const uint32_t* w12_table;
+  const void* w12_ovf;           // fourth dwords of the wide blocks, 256 bytes each (read by the kernel, late and rarely)
 };
 constexpr int kStatStride = 256;                    // partials per token (>= workgroups of the producing launch)
 constexpr int kStatPlane = kSkinnyMaxT * kStatStride;   // floats per plane (plane 0: sum of squares, plane 1: sum)
@@ -133,6 +138,16 @@ size_t packed_matrix_bytes(int n_pairs, int K);
 size_t packed_fp8_weight_bytes(int n_pairs, int K);                     // fp8: the packed bytes, before the row scales
 size_t packed_any_matrix_bytes(int n_pairs, int K, int weight_dtype);   // bf16 or fp8 (+ scales)
 int pack_one_matrix(const void* w_bf16, int N, int K, int n_pairs, int epi, int head_dim, int weight_dtype, void* dst, hipStream_t st);
+// W12 copy of a matrix (pack.hip): [main stream][overflow of the wide blocks][table], each padded to 256 bytes
+constexpr int kW12OvfBlock = 256;
+struct W12Layout {
+  size_t main_bytes, ovf_bytes, table_bytes;   // padded
+  size_t total() const { return main_bytes + ovf_bytes + table_bytes; }
+};
+size_t w12_table_entries(int n_pairs, int K);
+W12Layout w12_layout(int n_pairs, int K, uint32_t n_wide);
+size_t w12_offset(const sd_model_config& c, const uint32_t* n_wide, int index);   // copy of matrix `index` in the buffer of sd_w12_pack
+bool w12_taken(int n_pairs, int K, uint32_t n_wide);   // covered by the kernels and >= 15 % smaller than the packed bf16 stream
 size_t packed_offset(const sd_model_config& c, int index);  // byte offset of matrix `index` in the buffer of sd_pack_weights
 int gemv_grid(const GemvArgs& a, int* ppw_out);
 int gemv_max_tokens(int K);                                          // tokens gemv.hip can stage for rows of K elements (<= 9)
@@ -140,11 +155,12 @@ int launch_gemv(const GemvArgs& a, int epi, hipStream_t st);          // T <= 9:
 int launch_gemm_skinny(const GemvArgs& a, int epi, hipStream_t st);   // T <= 64
 // name of the gemv.hip instance a plain launch (packed, no bias / x_row / batch) of T <= 9 tokens takes: "generic" or
 // "fixed<...>"; decided by the function launch_gemv asks. snprintf's return value.
-int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap);
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, bool w12 = false);
 // name of the KERNEL such a launch runs, from the choice launch_gemv itself consumes: "fixed<...>" as above,
 // "generic<EPI,whole|mask,ttN,bf16|fp8,kbN>" (the template key of gemv_mfma_kernel) or "skinny:" + gemm_plan_name of the body the
 // launch is handed to (rows too long to stage T of them). *len: snprintf's return value. Nonzero (error set) where launch_gemv refuses.
-int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len);
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, bool w12 = false);
+bool gemv_w12_covers(int n_pairs, int K);   // shape the W12 kernels stream: whole 32-k steps per K slice, one x chunk per thread
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8 = false);                  // shape handled by gemm_skinny.hip
 // gemm_pipe.hip: the statically scheduled chunk pipeline for <= 64 tokens (tried first by launch_gemm_skinny, which has
 // set the work split fields of `a`)

@@ -19,7 +19,7 @@
 // the kernel multiplies the fp32 accumulator of row r by scale[r]. The scales (fp32 [N]) follow the
 // packed bytes of their matrix. K is padded to a multiple of 64.
 
-#include "kernels.h"
+#include "gemv_device.h"
 
 namespace sd {
 
@@ -230,9 +230,250 @@ int pack_one_matrix(const void* w_bf16, int N, int K, int n_pairs, int epi, int 
   return 0;
 }
 
+// ------------------------------------------------------------------------------
+// W12: a lossless 12-bit copy of a packed bf16 stream, for the launches of <= 9 tokens (gemv.hip).
+//
+// A BLOCK is one (tile, 32-k step) unit of the stream above — 8*np chunks of 16 bytes, what one wave-instruction
+// loads. bf16 weights use a narrow exponent range locally: where all 16*np*16 exponents of a block lie within 16
+// values [base, base + 15] the block is NARROW and chunk c becomes 12 bytes, its 8 weights as 12-bit codes
+//     sign << 11 | (exp - base) << 7 | mantissa          (weight i at bit 12 i; widened exactly by w12_widen)
+// Any other block (an exact zero or a denormal among normal weights, a value more than 15 binades under the block's
+// largest, inf / nan) is WIDE and keeps its 16 raw bytes per chunk, split 12 + 4. Three parts per matrix:
+//   main      the slot of a block, 8*np x 12 bytes, sits at 3/4 of the block's byte offset in the bf16 stream: a narrow
+//             chunk's codes or the first 12 bytes of a wide chunk. A wave reads a slot with one global_load_dwordx3 at
+//             lane * 12, at an address it computes WITHOUT the table — the weight stream does not wait for it.
+//   overflow  wide block number k (stream order) owns 256 bytes at 256 k: the fourth dword of chunk c at 4 c.
+//   table     one uint32 per (tile, step), index (workgroup * n_tiles_full + tile) * (K / 32) + step:
+//             wide << 31 | base << 23 | k. A wave fetches the entries of a batch with one vector load in front of the
+//             batch's weight loads and reads them with readlane; only the widening and the rare overflow load wait for it.
+// Whether a block is narrow is decided by widening its codes and comparing bits (w12_classify_kernel), not by a rule on
+// the exponents. specdec_hip/w12.py restates the format; the measured narrow share is in profiles/w12_verify.md.
+// ------------------------------------------------------------------------------
+size_t w12_table_entries(int n_pairs, int K) {
+  const GemvGeom q = gemv_geometry(n_pairs, K);
+  const size_t ntf = (q.ppw + q.tile_pairs - 1) / q.tile_pairs;
+  return static_cast<size_t>(q.grid) * ntf * (((static_cast<size_t>(K) + 31) & ~static_cast<size_t>(31)) >> 5);
+}
+
+W12Layout w12_layout(int n_pairs, int K, uint32_t n_wide) {
+  const size_t K32 = (static_cast<size_t>(K) + 31) & ~static_cast<size_t>(31);
+  auto pad = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  return {pad(static_cast<size_t>(n_pairs) * 2 * K32 * 2 / 4 * 3), pad(static_cast<size_t>(n_wide) * kW12OvfBlock), pad(w12_table_entries(n_pairs, K) * 4)};
+}
+
+bool w12_taken(int n_pairs, int K, uint32_t n_wide) {
+  if (!gemv_w12_covers(n_pairs, K) || n_wide >= (1u << 23)) return false;
+  return static_cast<double>(w12_layout(n_pairs, K, n_wide).total()) <= 0.85 * static_cast<double>(packed_matrix_bytes(n_pairs, K));
+}
+
+struct W12Job {
+  const uint16_t* src;   // packed bf16 stream
+  uint32_t* table;
+  unsigned char* main;
+  unsigned char* ovf;
+  int n_pairs, K32, ppw, tile_pairs, ntf;
+};
+
+// block `b` of the table: pairs of its tile (0: the last workgroup has no such tile) and its byte offset in the bf16 stream
+__device__ __forceinline__ int w12_block(const W12Job& j, size_t b, size_t& off) {
+  const int nst = j.K32 >> 5;
+  const int gt = static_cast<int>(b / nst), step = static_cast<int>(b - static_cast<size_t>(gt) * nst);
+  const int c = gt / j.ntf, t = gt - c * j.ntf;
+  const int p_lo = c * j.ppw, p_hi = min(p_lo + j.ppw, j.n_pairs);
+  const int p0 = p_lo + t * j.tile_pairs;
+  if (p0 >= p_hi) return 0;
+  const int np = min(j.tile_pairs, p_hi - p0);
+  off = static_cast<size_t>(p0) * 2 * j.K32 * 2 + static_cast<size_t>(step) * 128 * np;
+  return np;
+}
+
+// one wave per block: table[b] = base << 23 for a narrow block, 1 << 31 for a wide one (numbered by w12_number_kernel)
+__global__ __launch_bounds__(256) void w12_classify_kernel(W12Job j, size_t n_entries) {
+  const int lane = threadIdx.x & 63;
+  const size_t n_waves = static_cast<size_t>(gridDim.x) * 4;
+  for (size_t b = static_cast<size_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); b < n_entries; b += n_waves) {
+    size_t off = 0;
+    const int np = w12_block(j, b, off);
+    uint32_t ent = 0;
+    if (np) {
+      const bool active = lane < 8 * np;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (active) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(j.src) + off + lane * 16);
+      int emax = 0;
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) emax = max(emax, static_cast<int>((v[i >> 1] >> (16 * (i & 1) + 7)) & 0xFFu));
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) emax = max(emax, __shfl_xor(emax, o, 64));
+      const uint32_t base = static_cast<uint32_t>(max(emax - 15, 0));
+      const u32x4 back = w12_widen(w12_encode(v, base), (base << 7) * 0x10001u);
+      const bool same = !active || (back[0] == v[0] && back[1] == v[1] && back[2] == v[2] && back[3] == v[3]);
+      ent = (__ballot(same) == ~0ull) ? (base << 23) : 0x80000000u;
+    }
+    if (lane == 0) j.table[b] = ent;
+  }
+}
+
+// one workgroup: number the wide blocks in table (= stream) order; *n_wide = their count
+__global__ __launch_bounds__(1024) void w12_number_kernel(uint32_t* __restrict__ table, size_t n, uint32_t* __restrict__ n_wide) {
+  __shared__ uint32_t cnt[1024];
+  const int tid = threadIdx.x;
+  const size_t per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
+  uint32_t c = 0;
+  for (size_t i = lo; i < hi; ++i) c += table[i] >> 31;
+  cnt[tid] = c;
+  __syncthreads();
+  uint32_t k = 0;
+  for (int t = 0; t < tid; ++t) k += cnt[t];
+  for (size_t i = lo; i < hi; ++i)
+    if (table[i] >> 31) table[i] = 0x80000000u | k++;
+  if (tid == 1023) *n_wide = k;
+}
+
+// one wave per block: the main slot, and a wide block's overflow
+__global__ __launch_bounds__(256) void w12_fill_kernel(W12Job j, size_t n_entries) {
+  const int lane = threadIdx.x & 63;
+  const size_t n_waves = static_cast<size_t>(gridDim.x) * 4;
+  for (size_t b = static_cast<size_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); b < n_entries; b += n_waves) {
+    size_t off = 0;
+    const int np = w12_block(j, b, off);
+    if (!np) continue;
+    const uint32_t ent = j.table[b];
+    const bool active = lane < 8 * np;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (active) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(j.src) + off + lane * 16);
+    if (ent >> 31) *reinterpret_cast<uint32_t*>(j.ovf + static_cast<size_t>(ent & 0x7FFFFFu) * kW12OvfBlock + lane * 4) = v[3];   // (lanes without a chunk: zero)
+    else v = w12_encode(v, (ent >> 23) & 0xFFu);
+    if (active) {
+      uint32_t* d = reinterpret_cast<uint32_t*>(j.main + off / 4 * 3 + lane * 12);
+      d[0] = v[0];
+      d[1] = v[1];
+      d[2] = v[2];
+    }
+  }
+}
+
+static W12Job w12_job(const void* packed_bf16, int n_pairs, int K, uint32_t* table, void* main, void* ovf) {
+  const GemvGeom q = gemv_geometry(n_pairs, K);
+  return {static_cast<const uint16_t*>(packed_bf16), table, static_cast<unsigned char*>(main), static_cast<unsigned char*>(ovf),
+          n_pairs, (K + 31) & ~31, q.ppw, q.tile_pairs, (q.ppw + q.tile_pairs - 1) / q.tile_pairs};
+}
+
+static int w12_grid(size_t n_entries) { return static_cast<int>(n_entries / 4 + 1 < 8192 ? n_entries / 4 + 1 : 8192); }
+
+// table of one matrix (classified and numbered) and its wide-block count, on the device
+int w12_measure_matrix(const void* packed_bf16, int n_pairs, int K, uint32_t* table, uint32_t* n_wide, hipStream_t st) {
+  const size_t n = w12_table_entries(n_pairs, K);
+  hipLaunchKernelGGL(w12_classify_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, table, nullptr, nullptr), n);
+  SD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(w12_number_kernel, dim3(1), dim3(1024), 0, st, table, n, n_wide);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+// the W12 copy at dst ([main][overflow][table], w12_layout) from the packed stream and its measured table
+int w12_fill_matrix(const void* packed_bf16, int n_pairs, int K, const uint32_t* table, uint32_t n_wide, void* dst, hipStream_t st) {
+  const W12Layout l = w12_layout(n_pairs, K, n_wide);
+  const size_t n = w12_table_entries(n_pairs, K);
+  char* d = static_cast<char*>(dst);
+  uint32_t* tab = reinterpret_cast<uint32_t*>(d + l.main_bytes + l.ovf_bytes);
+  SD_HIP_CHECK(hipMemcpyAsync(tab, table, n * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(w12_fill_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, tab, d, d + l.main_bytes), n);
+  SD_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t w12_scratch_offset(const sd_model_config& c, int index) {   // table of matrix `index` in the scratch of sd_w12_measure
+  size_t off = 0;
+  for (int i = 0; i < index; ++i) {
+    const MatShape m = matrix_shape(c, matrix_which(c, i));
+    off += (w12_table_entries(m.n_pairs, m.K) * 4 + 255) & ~static_cast<size_t>(255);
+  }
+  return off;
+}
+
+size_t w12_offset(const sd_model_config& c, const uint32_t* n_wide, int index) {   // copy of matrix `index` in the buffer of sd_w12_pack
+  size_t off = 0;
+  for (int i = 0; i < index && i <= 4 * c.n_layers; ++i) {
+    const MatShape m = matrix_shape(c, matrix_which(c, i));
+    if (w12_taken(m.n_pairs, m.K, n_wide[i])) off += w12_layout(m.n_pairs, m.K, n_wide[i]).total();
+  }
+  return off;
+}
+
 }  // namespace sd
 
 using namespace sd;
+
+static int w12_cfg_ok(const sd_model_config* cfg, const char* who) {
+  SD_REQUIRE(cfg && cfg->layers && cfg->packed, "%s: needs a config with the packed bf16 buffer of sd_pack_weights", who);
+  SD_REQUIRE(cfg->weight_dtype == SD_BF16, "%s: W12 is a copy of bf16 weights (weight_dtype %d)", who, cfg->weight_dtype);
+  return 0;
+}
+
+extern "C" size_t sd_w12_scratch_bytes(const sd_model_config* cfg) {
+  if (!cfg || !cfg->layers) return 0;
+  const int n = 4 * cfg->n_layers + 1;
+  return w12_scratch_offset(*cfg, n) + ((static_cast<size_t>(n) * 4 + 255) & ~static_cast<size_t>(255));
+}
+
+extern "C" int sd_w12_measure(const sd_model_config* cfg, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream) {
+  clear_error();
+  if (int rc = w12_cfg_ok(cfg, "w12_measure")) return rc;
+  SD_REQUIRE(scratch && n_wide && scratch_bytes >= sd_w12_scratch_bytes(cfg), "w12_measure: scratch too small or NULL");
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "w12_measure: scratch must be 256-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int n = 4 * cfg->n_layers + 1;
+  char* s = static_cast<char*>(scratch);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(s + w12_scratch_offset(*cfg, n));
+  for (int i = 0; i < n; ++i) {
+    const MatShape m = matrix_shape(*cfg, matrix_which(*cfg, i));
+    const void* src = static_cast<const char*>(cfg->packed) + packed_offset(*cfg, i);
+    if (int rc = w12_measure_matrix(src, m.n_pairs, m.K, reinterpret_cast<uint32_t*>(s + w12_scratch_offset(*cfg, i)), counts + i, st)) return rc;
+  }
+  SD_HIP_CHECK(hipMemcpyAsync(n_wide, counts, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
+  SD_HIP_CHECK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" size_t sd_w12_bytes(const sd_model_config* cfg, const uint32_t* n_wide) {
+  if (!cfg || !cfg->layers || !n_wide) return 0;
+  return w12_offset(*cfg, n_wide, 4 * cfg->n_layers + 1);
+}
+
+extern "C" int sd_w12_matrix(const sd_model_config* cfg, const uint32_t* n_wide, int index, int* taken, size_t* offset, size_t* main_bytes,
+                             size_t* ovf_bytes, size_t* table_bytes, size_t* blocks, size_t* bf16_bytes) {
+  clear_error();
+  SD_REQUIRE(cfg && cfg->layers && n_wide && index >= 0 && index <= 4 * cfg->n_layers, "w12_matrix: bad argument");
+  const MatShape m = matrix_shape(*cfg, matrix_which(*cfg, index));
+  const W12Layout l = w12_layout(m.n_pairs, m.K, n_wide[index]);
+  if (taken) *taken = w12_taken(m.n_pairs, m.K, n_wide[index]) ? 1 : 0;
+  if (offset) *offset = w12_offset(*cfg, n_wide, index);
+  if (main_bytes) *main_bytes = l.main_bytes;
+  if (ovf_bytes) *ovf_bytes = l.ovf_bytes;
+  if (table_bytes) *table_bytes = l.table_bytes;
+  if (blocks) *blocks = w12_table_entries(m.n_pairs, m.K);   // (entries of tiles the last workgroup does not have count as narrow)
+  if (bf16_bytes) *bf16_bytes = packed_matrix_bytes(m.n_pairs, m.K);
+  return 0;
+}
+
+extern "C" int sd_w12_pack(const sd_model_config* cfg, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream) {
+  clear_error();
+  if (int rc = w12_cfg_ok(cfg, "w12_pack")) return rc;
+  SD_REQUIRE(scratch && n_wide && (dst || !sd_w12_bytes(cfg, n_wide)), "w12_pack: NULL argument");
+  SD_REQUIRE(dst_bytes >= sd_w12_bytes(cfg, n_wide), "w12_pack: destination too small");
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 255) == 0, "w12_pack: destination must be 256-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  for (int i = 0; i <= 4 * cfg->n_layers; ++i) {
+    const MatShape m = matrix_shape(*cfg, matrix_which(*cfg, i));
+    if (!w12_taken(m.n_pairs, m.K, n_wide[i])) continue;
+    const void* src = static_cast<const char*>(cfg->packed) + packed_offset(*cfg, i);
+    const uint32_t* table = reinterpret_cast<const uint32_t*>(static_cast<const char*>(scratch) + w12_scratch_offset(*cfg, i));
+    if (int rc = w12_fill_matrix(src, m.n_pairs, m.K, table, n_wide[i], static_cast<char*>(dst) + w12_offset(*cfg, n_wide, i), st)) return rc;
+  }
+  return 0;
+}
 
 // A vocabulary-sized output matrix [V][d] outside a model (Medusa heads): same layout and quantiser as the lm_head.
 extern "C" size_t sd_packed_head_bytes(int vocab, int d_model, int weight_dtype) {

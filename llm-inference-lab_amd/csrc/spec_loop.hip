@@ -126,6 +126,8 @@ static int enqueue_head_argmax(sd_model* m, const HeadEval& e, hipStream_t st) {
   GemvArgs h = matrix_args(m, 4 * c.n_layers);   // the lm_head's shape and final norm; the matrices' own weights below
   h.packed = e.packed;
   h.w8 = e.w8;
+  h.w12_main = h.w12_ovf = nullptr;   // (the lm_head's W12 copy does not describe e.W)
+  h.w12_table = nullptr;
   h.x = e.x;
   h.x_row = e.x_row;
   h.T = T;

@@ -84,6 +84,12 @@ SIGNATURES = {
     # ---- decoder forward + step loop ----
     "sd_packed_bytes": (_c_size, [_c_void_p]),
     "sd_pack_weights": (_c_int, [_c_void_p, _c_void_p, _c_size, _c_void_p]),
+    "sd_w12_scratch_bytes": (_c_size, [_c_void_p]),
+    "sd_w12_measure": (_c_int, [_c_void_p, _c_void_p, _c_size, _c_void_p, _c_void_p]),
+    "sd_w12_bytes": (_c_size, [_c_void_p, _c_void_p]),
+    "sd_w12_matrix": (_c_int, [_c_void_p, _c_void_p, _c_int, ctypes.POINTER(_c_int)] + [ctypes.POINTER(_c_size)] * 6),
+    "sd_w12_pack": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p]),
+    "sd_model_set_w12": (_c_int, [_c_void_p, _c_void_p, _c_void_p, ctypes.c_uint]),
     "sd_model_create": (_c_int, [_c_void_p, _c_void_p]),
     "sd_model_destroy": (_c_int, [_c_void_p]),
     "sd_quantize_fp8_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),

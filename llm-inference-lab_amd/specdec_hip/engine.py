@@ -50,6 +50,38 @@ def _stream(stream: Optional[torch.cuda.Stream], device) -> int:
     return (stream or torch.cuda.current_stream(device)).cuda_stream
 
 
+W12_DEFAULT = True   # bf16 models get the W12 copy (profiles/w12_verify.md)
+W12_CLASSES = 0x10   # matrix classes that stream it (SD_W12_DEFAULT_CLASSES: the lm_head); SPECDEC_W12_CLASSES=0x1f: all five
+
+
+def build_w12(lib, mc: "_ModelConfig", dev, classes: int = 0x1F) -> Tuple[torch.Tensor, np.ndarray]:
+    """The W12 copy of a config's packed bf16 matrices of the given classes (bit 0 qkv .. bit 4 lm_head): (device buffer, host
+    uint32 wide-block counts per matrix, SD_W12_SKIP = 0xFFFFFFFF for a matrix that is left out)."""
+    n_wide = np.zeros(4 * mc.n_layers + 1, dtype=np.uint32)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        scratch = torch.empty(lib.sd_w12_scratch_bytes(ctypes.byref(mc)), dtype=torch.uint8, device=dev)
+        _abi.check(lib.sd_w12_measure(ctypes.byref(mc), scratch.data_ptr(), scratch.numel(), n_wide.ctypes.data, st), "sd_w12_measure")
+        for i in range(n_wide.size):
+            if not (classes >> (4 if i == 4 * mc.n_layers else i & 3)) & 1:
+                n_wide[i] = 0xFFFFFFFF
+        nbytes = lib.sd_w12_bytes(ctypes.byref(mc), n_wide.ctypes.data)
+        buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        _abi.check(lib.sd_w12_pack(ctypes.byref(mc), scratch.data_ptr(), n_wide.ctypes.data, buf.data_ptr(), buf.numel(), st), "sd_w12_pack")
+        torch.cuda.current_stream(dev).synchronize()   # scratch is read by the pack
+    return buf, n_wide
+
+
+def w12_matrix_info(lib, mc: "_ModelConfig", n_wide: np.ndarray, index: int) -> dict:
+    """sd_w12_matrix as a dict: taken, offset, main_bytes, ovf_bytes, table_bytes, blocks, bf16_bytes, n_wide."""
+    taken = ctypes.c_int()
+    v = [ctypes.c_size_t() for _ in range(6)]
+    _abi.check(lib.sd_w12_matrix(ctypes.byref(mc), n_wide.ctypes.data, index, ctypes.byref(taken), *[ctypes.byref(x) for x in v]),
+               "sd_w12_matrix")
+    keys = ("offset", "main_bytes", "ovf_bytes", "table_bytes", "blocks", "bf16_bytes")
+    return {"taken": bool(taken.value), "n_wide": int(n_wide[index]), **{k: int(x.value) for k, x in zip(keys, v)}}
+
+
 class EngineGaveUp(_abi.HipLibraryError):
     """A persistent forward hit one of its bounded waits (another kernel held CUs it needs, or a workgroup never ran) and left.
     Nothing hangs and nothing is silently wrong: the health word says so, the caller repeats the work on the launch path."""
@@ -139,6 +171,21 @@ class HipModel:
         handle = _vp()
         _abi.check(self.lib.sd_model_create(ctypes.byref(mc), ctypes.byref(handle)), "sd_model_create")
         self.handle = handle
+        # W12: a lossless 12-bit copy of the packed bf16 matrices for the launches of 1..9 tokens (csrc/pack.hip), one per
+        # ModelWeights like the packed copy. W12_DEFAULT / W12_CLASSES: what profiles/w12_verify.md measured; SPECDEC_W12=1 / 0 and
+        # SPECDEC_W12_CLASSES (bit mask: 1 qkv, 2 out, 4 gate / up, 8 down, 16 lm_head) override them, and
+        # SPECDEC_NO_W12 (the library's per-launch switch) also skips building the copy.
+        self._w12 = None
+        self._mc = mc
+        want_w12 = os.environ.get("SPECDEC_W12", "1" if W12_DEFAULT else "0") not in ("", "0")
+        if weight_dtype == "bf16" and packed is not None and want_w12 and not os.environ.get("SPECDEC_NO_W12"):
+            classes = int(os.environ.get("SPECDEC_W12_CLASSES", str(W12_CLASSES)), 0) & 0x1F
+            key = f"_w12_{classes:02x}"
+            self._w12 = weights.meta.get(key)
+            if self._w12 is None:
+                self._w12 = weights.meta[key] = build_w12(self.lib, mc, dev, classes)
+            buf, n_wide = self._w12
+            _abi.check(self.lib.sd_model_set_w12(self.handle, _ptr(buf), n_wide.ctypes.data, classes), "sd_model_set_w12")
         self.batch, self.l_max = int(batch), (int(l_max) + 31) // 32 * 32  # whole 32-key blocks
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):
