@@ -785,6 +785,57 @@ int sd_logit_process_fsm(void* rows, int64_t row_stride, int B, int R, int V, co
  * (SD_ABI_VERSION stays 1). */
 int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* next, const void* allow, int S, int32_t* fsm_state, int eos_id);
 
+/* Per-request sampling parameters, row by row (csrc/sample.hip, csrc/spec_sample.hip, csrc/logit_proc.hip). A table is
+ * sd_row_sampling[B] in device memory: caller-owned, 16-byte aligned, READ BY THE KERNELS AT RUN TIME, so the caller may
+ * rewrite entry b on the stream between two launches (or two replays of a captured step) and the next launch follows it.
+ * The host cannot check the contents at launch; every kernel normalises its row's entry with one device function
+ * (normalise_row_sampling, csrc/sample_device.h) and is memory-safe for every bit pattern:
+ *   a GREEDY ROW, exactly (temperature 1, top_k 1, top_p 1), when !(temperature > 0) (0 is the documented way to ask for
+ *   greedy; a NaN falls here too), or min(top_k, V) > 1024, or top_p is NaN or <= 0, or — in the speculative-sampling kernels
+ *   only — top_k <= 0 with top_p < 1 (the full-vocabulary nucleus stays unsupported there);
+ *   otherwise top_k <= 0 = no top-k, top_p >= 1 = no nucleus cut, Philox key = (seed_lo, seed_hi);
+ *   penalties the scalar entries refuse (repetition_penalty <= 0 or NaN, a presence or frequency penalty that is not finite)
+ *   are the identity (1, 0, 0) for that row.
+ * Row b's workgroups then branch, workgroup-uniformly, into the code the scalar kernel runs, so row b of a _rows launch gives
+ * bit for bit what the scalar entry gives when called on that row alone with the normalised entry, the same draw counter and
+ * the same stream id: ids, accept lengths, counters, float64 ratios, processed bf16 rows.
+ *   sd_sample_token_rows        sd_sample_token with the table in place of temperature, top_k, top_p, seed: one launch, each row
+ *                               on the top-k, the full-vocabulary nucleus or the Gumbel-max path
+ *   sd_spec_sample_accept_rows  sd_spec_sample_accept_shaped likewise (same workspace): a row with top_k <= 0 and top_p >= 1
+ *                               runs the unshaped statistics of sd_spec_sample_accept, any other row the shaped ones; counters
+ *                               advance by K + 1 either way
+ *   sd_logit_process_rows       sd_logit_process_fsm with the table in place of the three penalties; next == allow ==
+ *                               fsm_state == NULL: no grammar
+ * Refused by the host: a NULL or misaligned table, B < 1, and what the scalar entries refuse about their other arguments.
+ * Additive (SD_ABI_VERSION stays 1). */
+typedef struct sd_row_sampling {
+  float temperature; int32_t top_k; float top_p;
+  uint32_t seed_lo, seed_hi;
+  float repetition_penalty, presence_penalty, frequency_penalty;
+} sd_row_sampling;
+size_t sd_row_sampling_bytes(void);
+int sd_sample_token_rows(const void* logits, int logits_dtype, int64_t row_stride, int B, int V, const int32_t* pos, int rows_per_b,
+                         const int32_t* active, const sd_row_sampling* table, uint32_t* draw_counters, uint32_t draw0,
+                         const int32_t* stream_id, int32_t* out_ids, void* stream);
+int sd_spec_sample_accept_rows(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K, int V,
+                               const sd_row_sampling* table, uint32_t* draw_counters, uint32_t draw0, const int32_t* stream_ids,
+                               const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out, double* ratios_out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int sd_logit_process_rows(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
+                          const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, const sd_row_sampling* table,
+                          int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, const void* next,
+                          const void* allow, int S, const int32_t* fsm_state, int eos_id, void* stream);
+
+/* The table inside the step: with a table ([B], device) the sampled-bonus draw, the speculative-sampling draws, statistics and
+ * accept, and the logit-processor launches take their parameters from table[b]; the loop's scalars (temperature, top_k, top_p,
+ * seed, spec shaping, penalties) are ignored for those launches. Which mode runs and which buffers it uses stay what
+ * sd_specdec_set_sampling / sd_specdec_set_spec_sampling / sd_specdec_set_logit_processors configured. While a table is bound
+ * the caller may rewrite table[b], stream_ids[b], draw_counters[b] and the bias row of a slot on the loop's stream between
+ * steps and THE CAPTURED GRAPH IS KEPT: admitting a request captures nothing again. NULL returns to the scalars; a step
+ * without a table is launch for launch what it was. Either call drops the captured graph. Refused: a misaligned table; a
+ * table while neither a sampling mode nor the logit-processor stage is on. Additive (SD_ABI_VERSION stays 1). */
+int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling* table);
+
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,
  * which the reference applies to one K for the whole batch from the host, pipeline.py:1994-2014). The loop keeps the

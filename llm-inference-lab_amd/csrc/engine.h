@@ -133,16 +133,17 @@ int launch_verify_tail(const SpecState& s, const float* part_val, const int* par
 // csrc/sample.hip
 struct SampleArgs;
 int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
-                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st);
+                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st, const sd_row_sampling* table = nullptr);
 
 
 // csrc/spec_sample.hip: speculative sampling inside the step. top_k == 0: the plain distributions; top_k in 1..1024: both
 // distributions shaped by top-k / top-p
 int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
                            float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
-                           hipStream_t st);
+                           hipStream_t st, const sd_row_sampling* table = nullptr);
 int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st);
+                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st,
+                     const sd_row_sampling* table = nullptr);
 
 // csrc/grammar.hip: token automata (grammar-constrained decoding). next: uint16 [S][V], 0xFFFF = the token is not allowed in the
 // state; allow: the same as one bit per token, uint32 [S][ceil(V / 32)]. A row's state: -1 unconstrained, 0..S-1, else DEAD
@@ -176,7 +177,7 @@ size_t logit_process_workspace(int B, int R, int V);
 int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
                          const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
                          float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
-                         const FsmBind* fsm = nullptr);
+                         const FsmBind* fsm = nullptr, const sd_row_sampling* table = nullptr);
 int launch_logit_counts_set(uint16_t* counts, int B, int V, int b, const int32_t* prompt, int n_prompt, const int32_t* gen, int n_gen,
                             hipStream_t st);
 int launch_logit_counts_add(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,

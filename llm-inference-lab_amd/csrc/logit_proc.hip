@@ -17,6 +17,9 @@
 // With a grammar bound (csrc/grammar.hip; logit_process_kernel<true>) one more line follows the bias: an element the row's
 // automaton state does not allow is stored as -inf whatever x is, a NaN too (the contract is at sd_logit_process_fsm).
 //
+// Per-row penalties (sd_logit_process_rows): logit_process_rows_kernel takes rp / presence / frequency of batch row b from its
+// sd_row_sampling entry (normalised: what the scalar entry refuses is the identity for the row) and runs the same transform.
+//
 // Why in place: every consumer of a stored row (the sampler, the speculative-sampling statistics, the draws, the agreement
 // op) defines its contract on the stored bf16 values; processing the stored row keeps all of them word for word.
 //
@@ -34,6 +37,7 @@
 #pragma clang fp contract(off)
 
 #include "engine.h"
+#include "sample_device.h"   // normalise_row_sampling
 
 namespace sd {
 
@@ -99,14 +103,22 @@ __device__ __forceinline__ uint16_t lp_element(float x, uint32_t cnt, int v, boo
 
 // FSM: the grammar line after the bias — an element the row's automaton state does not allow is stored as -inf, whatever
 // the lines above made of it (a NaN too). The <false> instantiation is the kernel without a grammar, instruction for instruction.
+// The transform of one workgroup's share of row t = b * R + r as a device function on an LDS block of its caller:
+// logit_process_kernel calls it with the launch's penalties, logit_process_rows_kernel with the row's own.
+struct LogitProcLds {
+  int toks[kLpMaxTokens];
+  int fsm_s;
+  float sv[kLpThreads / kWave];
+  int si[kLpThreads / kWave];
+};
+
 template <bool FSM>
-__global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitProcArgs a) {
-  __shared__ int toks[kLpMaxTokens];
-  __shared__ int fsm_s;
-  __shared__ float sv[kLpThreads / kWave];
-  __shared__ int si[kLpThreads / kWave];
-  const int t = blockIdx.y, tid = threadIdx.x, V = a.V, S = gridDim.x, x0 = blockIdx.x;
-  const int b = t / a.R, r = t - b * a.R;
+__device__ __forceinline__ void logit_process_share(LogitProcLds& G, const LogitProcArgs& a, int t, int b, int r) {
+  int* const toks = G.toks;
+  int& fsm_s = G.fsm_s;
+  float* const sv = G.sv;
+  int* const si = G.si;
+  const int tid = threadIdx.x, V = a.V, S = gridDim.x, x0 = blockIdx.x;
   const bool act = !a.active || a.active[b] != 0;   // an inactive row is only read: its argmax is that of the untouched row
   int n = a.n_tokens < 0 ? r : a.n_tokens;
   n = (act && a.tokens) ? (n > kLpMaxTokens ? kLpMaxTokens : n) : 0;
@@ -196,6 +208,26 @@ __global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitPr
   }
 }
 
+template <bool FSM>
+__global__ __launch_bounds__(kLpThreads) void logit_process_kernel(const LogitProcArgs a) {
+  __shared__ LogitProcLds G;
+  const int t = blockIdx.y, b = t / a.R;
+  logit_process_share<FSM>(G, a, t, b, t - b * a.R);
+}
+
+// Per-row penalties (sd_logit_process_rows): every workgroup of batch row b normalises table[b] and runs the same transform
+template <bool FSM>
+__global__ __launch_bounds__(kLpThreads) void logit_process_rows_kernel(const LogitProcArgs a0, const sd_row_sampling* table) {
+  __shared__ LogitProcLds G;
+  const int t = blockIdx.y, b = t / a0.R;
+  const sd_row_sampling e = normalise_row_sampling(table, b, a0.V, false);
+  LogitProcArgs a = a0;
+  a.rp = e.repetition_penalty;
+  a.presence = e.presence_penalty;
+  a.frequency = e.frequency_penalty;
+  logit_process_share<FSM>(G, a, t, b, t - b * a0.R);
+}
+
 size_t logit_process_workspace(int B, int R, int V) {
   if (B <= 0 || R <= 0 || V <= 0) return 0;
   return static_cast<size_t>(B) * R * logit_process_split(V) * (sizeof(float) + sizeof(int));
@@ -204,15 +236,19 @@ size_t logit_process_workspace(int B, int R, int V) {
 int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
                          const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
                          float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
-                         const FsmBind* fsm) {
+                         const FsmBind* fsm, const sd_row_sampling* table) {
   SD_REQUIRE(rows && counts, "logit_process: NULL rows / counts");
   SD_REQUIRE(B >= 1 && R >= 1 && V >= 1 && static_cast<long long>(B) * R <= 65535, "logit_process: B=%d R=%d V=%d out of range", B, R, V);
   SD_REQUIRE(row_stride >= V, "logit_process: row stride %lld < V=%d", row_stride, V);
   const int n_max = n_tokens < 0 ? R - 1 : n_tokens;
   SD_REQUIRE(n_max <= kLpMaxTokens, "logit_process: %d in-step tokens (at most %d)", n_max, kLpMaxTokens);
   SD_REQUIRE(n_max == 0 || (tokens && tok_stride >= n_max), "logit_process: %d in-step tokens need a token array with a stride >= %d", n_max, n_max);
-  SD_REQUIRE(rp == rp && rp > 0.f, "logit_process: repetition_penalty %g (must be > 0)", rp);
-  SD_REQUIRE(presence - presence == 0.f && frequency - frequency == 0.f, "logit_process: presence %g / frequency %g must be finite", presence, frequency);
+  if (table) {   // the penalties are the rows' own, normalised on the device
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "logit_process: the row table must be 16-byte aligned");
+  } else {
+    SD_REQUIRE(rp == rp && rp > 0.f, "logit_process: repetition_penalty %g (must be > 0)", rp);
+    SD_REQUIRE(presence - presence == 0.f && frequency - frequency == 0.f, "logit_process: presence %g / frequency %g must be finite", presence, frequency);
+  }
   SD_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(counts)) & 1) == 0 && (reinterpret_cast<uintptr_t>(bias) & 3) == 0,
              "logit_process: misaligned rows / counts / bias");
   const int S = logit_process_split(V);
@@ -249,9 +285,11 @@ int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, 
     SD_REQUIRE(!fsm->pos || (n_tokens >= 0 ? (R == 1 && fsm->pos_stride > n_tokens) : fsm->pos_stride >= n_max),
                "logit_process: position table of stride %d for R=%d rows of %d tokens", fsm->pos_stride, R, n_tokens);
     a.fsm = *fsm;
-    hipLaunchKernelGGL(logit_process_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+    if (table) hipLaunchKernelGGL(logit_process_rows_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, table);
+    else hipLaunchKernelGGL(logit_process_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
   } else {
-    hipLaunchKernelGGL(logit_process_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
+    if (table) hipLaunchKernelGGL(logit_process_rows_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, table);
+    else hipLaunchKernelGGL(logit_process_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
   }
   SD_LAUNCH_CHECK();
   if (ids_out) return launch_argmax_finalize(a.part_val, a.part_idx, B * R, S, R, ids_stride, ids_out, st);
@@ -329,6 +367,26 @@ extern "C" int sd_logit_process(void* rows, int64_t row_stride, int B, int R, in
   return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
                               repetition_penalty, presence_penalty, frequency_penalty, ids_out, ids_stride, workspace, workspace_bytes,
                               static_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int sd_logit_process_rows(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
+                                     const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, const sd_row_sampling* table,
+                                     int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, const void* next,
+                                     const void* allow, int S, const int32_t* fsm_state, int eos_id, void* stream) {
+  clear_error();
+  SD_REQUIRE(table, "logit_process_rows: NULL table");
+  SD_REQUIRE(B >= 1, "logit_process_rows: B=%d", B);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "logit_process_rows: the row table must be 16-byte aligned");
+  const bool grammar = next || allow || fsm_state;   // all three NULL: no grammar
+  FsmBind f{};
+  f.next = static_cast<const uint16_t*>(next);
+  f.allow = static_cast<const uint32_t*>(allow);
+  f.S = S;
+  f.state = fsm_state;
+  f.eos_id = eos_id;
+  return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
+                              1.0f, 0.f, 0.f, ids_out, ids_stride, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
+                              grammar ? &f : nullptr, table);
 }
 
 extern "C" size_t sd_logit_counts_bytes(int B, int V) {

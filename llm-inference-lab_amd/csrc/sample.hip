@@ -23,6 +23,10 @@
 // Without top-k and top-p the draw is a Gumbel-max over the whole row (one Philox value per
 // element, block argmax): no ordered prefix sum over 128 K probabilities.
 // Full-vocabulary nucleus sampling (top_p < 1 without top_k): sample_nucleus_kernel below, rank blocks of 1024.
+//
+// Per-row parameters (sd_sample_token_rows, sd_row_sampling in include/specdec_hip.h): the three draws are __device__ functions
+// over the argument block and an LDS block; sample_rows_kernel reads row b's table entry, normalises it
+// (normalise_row_sampling, sample_device.h) and calls the one launch_sample would have launched for those parameters.
 
 #include "engine.h"
 #include "sample_device.h"
@@ -47,9 +51,10 @@ struct SampleArgs {
   int32_t* out;            // [B]
 };
 
-__global__ __launch_bounds__(kSampleThreads) void sample_topk_kernel(const SampleArgs a) {
-  __shared__ SurvivorLds L;
-  const int b = blockIdx.x, tid = threadIdx.x;
+// The three draws of one row, each by one 1024-thread workgroup on an LDS block of its caller: the scalar kernels below call
+// them with the launch's parameters, sample_rows_kernel with the row's own.
+__device__ __forceinline__ void sample_topk_row(SurvivorLds& L, const SampleArgs& a, int b) {
+  const int tid = threadIdx.x;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
@@ -77,16 +82,27 @@ __global__ __launch_bounds__(kSampleThreads) void sample_topk_kernel(const Sampl
 //   cum += e_i / Z in sorted order; kept while i == 0 or !(cum > top_p); the draw inverts one Philox uniform through
 //   the kept weights in sorted order.
 // ------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const SampleArgs a) {
-  __shared__ uint32_t hist[2048];
-  __shared__ uint64_t sel[kSampleThreads];
-  __shared__ double ev[kSampleThreads];
-  __shared__ uint32_t s_cnt;
-  __shared__ RadixPick s_radix;
-  __shared__ double s_z, s_cum, s_z2, s_u, s_c;
-  __shared__ int s_done, s_keep, s_pick;
-  __shared__ uint64_t s_best;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+struct NucleusLds {
+  uint32_t hist[2048];
+  uint64_t sel[kSampleThreads];
+  double ev[kSampleThreads];
+  uint32_t s_cnt;
+  RadixPick s_radix;
+  double s_z, s_cum, s_z2, s_u, s_c;
+  int s_done, s_keep, s_pick;
+  uint64_t s_best;
+};
+
+__device__ __forceinline__ void sample_nucleus_row(NucleusLds& N, const SampleArgs& a, int b) {
+  uint32_t* const hist = N.hist;
+  uint64_t* const sel = N.sel;
+  double* const ev = N.ev;
+  uint32_t& s_cnt = N.s_cnt;
+  RadixPick& s_radix = N.s_radix;
+  double &s_z = N.s_z, &s_cum = N.s_cum, &s_z2 = N.s_z2, &s_u = N.s_u, &s_c = N.s_c;
+  int &s_done = N.s_done, &s_keep = N.s_keep, &s_pick = N.s_pick;
+  uint64_t& s_best = N.s_best;
+  const int tid = threadIdx.x, lane = tid & 63;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
@@ -248,10 +264,15 @@ __global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const Sa
   }
 }
 
-__global__ __launch_bounds__(kSampleThreads) void sample_gumbel_kernel(const SampleArgs a) {
-  __shared__ double sv[kSampleThreads / kWave];
-  __shared__ int si[kSampleThreads / kWave];
-  const int b = blockIdx.x, tid = threadIdx.x;
+struct GumbelLds {
+  double sv[kSampleThreads / kWave];
+  int si[kSampleThreads / kWave];
+};
+
+__device__ __forceinline__ void sample_gumbel_row(GumbelLds& G, const SampleArgs& a, int b) {
+  double* const sv = G.sv;
+  int* const si = G.si;
+  const int tid = threadIdx.x;
   if (a.active && a.active[b] == 0) return;
   const int rowi = b * a.rows_per_b + (a.pos ? a.pos[b] : 0);
   const char* row = static_cast<const char*>(a.logits) + static_cast<size_t>(rowi) * a.row_stride * (a.dtype == SD_F32 ? 4 : 2);
@@ -274,6 +295,45 @@ __global__ __launch_bounds__(kSampleThreads) void sample_gumbel_kernel(const Sam
   }
 }
 
+__global__ __launch_bounds__(kSampleThreads) void sample_topk_kernel(const SampleArgs a) {
+  __shared__ SurvivorLds L;
+  sample_topk_row(L, a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_nucleus_kernel(const SampleArgs a) {
+  __shared__ NucleusLds N;
+  sample_nucleus_row(N, a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_gumbel_kernel(const SampleArgs a) {
+  __shared__ GumbelLds G;
+  sample_gumbel_row(G, a, blockIdx.x);
+}
+
+// Per-row parameters (sd_sample_token_rows): row b's workgroup normalises table[b] and takes, workgroup-uniformly, the path
+// launch_sample picks for those parameters. Only one path runs per workgroup: the three LDS blocks overlay each other.
+union SampleRowsLds {
+  SurvivorLds topk;
+  NucleusLds nucleus;
+  GumbelLds gumbel;
+};
+
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const SampleArgs a0, const sd_row_sampling* table) {
+  __shared__ SampleRowsLds U;
+  const int b = blockIdx.x;
+  if (a0.active && a0.active[b] == 0) return;
+  const sd_row_sampling e = normalise_row_sampling(table, b, a0.V, false);
+  SampleArgs a = a0;
+  a.temperature = e.temperature;
+  a.top_k = e.top_k;
+  a.top_p = e.top_p;
+  a.seed_lo = e.seed_lo;
+  a.seed_hi = e.seed_hi;
+  if (a.top_k > 0) sample_topk_row(U.topk, a, b);
+  else if (a.top_p < 1.0f) sample_nucleus_row(U.nucleus, a, b);
+  else sample_gumbel_row(U.gumbel, a, b);
+}
+
 // (the fields in declaration order, the seed split into the two Philox key words)
 static SampleArgs sample_args(const void* logits, int dtype, int64_t row_stride, int V, const int32_t* pos, int rows_per_b,
                               const int32_t* active, float temperature, int top_k, float top_p, uint64_t seed, uint32_t* draw,
@@ -282,11 +342,18 @@ static SampleArgs sample_args(const void* logits, int dtype, int64_t row_stride,
                     draw, draw0, stream_id, out};
 }
 
-int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
+// table: per-row parameters (the scalar ones of `a` are ignored), else null
+int launch_sample(const SampleArgs& a, int B, hipStream_t st, const sd_row_sampling* table = nullptr) {
   SD_REQUIRE(a.logits && a.out, "sample: NULL logits/out");
   SD_REQUIRE(a.dtype == SD_F32 || a.dtype == SD_BF16 || a.dtype == SD_F16, "sample: logits dtype %d", a.dtype);
   SD_REQUIRE(B >= 1 && B <= 65535 && a.V >= 1 && a.V <= (1 << kIdxBits), "sample: B=%d V=%d out of range", B, a.V);
   SD_REQUIRE(a.rows_per_b >= 1, "sample: rows_per_b=%d", a.rows_per_b);
+  if (table) {
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "sample: the row table must be 16-byte aligned");
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(kSampleThreads), 0, st, a, table);
+    SD_LAUNCH_CHECK();
+    return 0;
+  }
   SD_REQUIRE(a.temperature == a.temperature, "sample: temperature is NaN");
   if (a.top_k > 0) {
     SD_REQUIRE((a.top_k < a.V ? a.top_k : a.V) <= kSampleMaxK, "sample: top_k=%d > %d is not supported", a.top_k, kSampleMaxK);
@@ -302,9 +369,9 @@ int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
 
 // the step's draw: entry b samples from row b*(K+1) + accept_len[b] of the verify logits
 int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
-                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st) {
+                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st, const sd_row_sampling* table) {
   return launch_sample(sample_args(logits, SD_BF16, V, V, s.accept_len, s.K + 1, s.active, temperature, top_k, top_p, seed, draw, 0,
-                                   stream_id, s.sampled), s.B, st);
+                                   stream_id, s.sampled), s.B, st, table);
 }
 
 }  // namespace sd
@@ -318,4 +385,17 @@ extern "C" int sd_sample_token(const void* logits, int logits_dtype, int64_t row
   clear_error();
   return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, temperature, top_k, top_p, seed,
                                    draw_counters, draw0, stream_id, out_ids), B, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t sd_row_sampling_bytes(void) { return sizeof(sd_row_sampling); }
+
+extern "C" int sd_sample_token_rows(const void* logits, int logits_dtype, int64_t row_stride, int B, int V, const int32_t* pos,
+                                    int rows_per_b, const int32_t* active, const sd_row_sampling* table, uint32_t* draw_counters,
+                                    uint32_t draw0, const int32_t* stream_id, int32_t* out_ids, void* stream) {
+  clear_error();
+  SD_REQUIRE(table, "sample_token_rows: NULL table");
+  SD_REQUIRE(B >= 1, "sample_token_rows: B=%d", B);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "sample_token_rows: the row table must be 16-byte aligned");
+  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, 1.0f, 0, 1.0f, 0, draw_counters, draw0,
+                                   stream_id, out_ids), B, static_cast<hipStream_t>(stream), table);
 }

@@ -321,6 +321,43 @@ __device__ __forceinline__ double gumbel_noise(uint32_t draw, uint32_t sid, int 
   return -log(-log(u));
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-row parameters (sd_row_sampling, include/specdec_hip.h): the ONE normalisation of a table entry, used by every _rows
+// kernel. The table is device memory the host cannot check at launch, so whatever bits an entry holds come out as values the
+// scalar kernels accept: top_k in 0..kSampleMaxK after the clamp to V, top_p in (0, 1], temperature > 0, penalties the scalar
+// entries take. `spec`: the speculative-sampling kernels, where the full-vocabulary nucleus is a greedy row too.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ sd_row_sampling normalise_row_sampling(const sd_row_sampling* table, int b, int V, bool spec) {
+  // a 32-byte entry of a 16-byte aligned table: two 16-byte loads
+  const uint4 w0 = reinterpret_cast<const uint4*>(table)[2 * b], w1 = reinterpret_cast<const uint4*>(table)[2 * b + 1];
+  sd_row_sampling e;
+  e.temperature = __uint_as_float(w0.x);
+  e.top_k = static_cast<int32_t>(w0.y);
+  e.top_p = __uint_as_float(w0.z);
+  e.seed_lo = w0.w;
+  e.seed_hi = w1.x;
+  e.repetition_penalty = __uint_as_float(w1.y);
+  e.presence_penalty = __uint_as_float(w1.z);
+  e.frequency_penalty = __uint_as_float(w1.w);
+  if (e.top_k < 0) e.top_k = 0;
+  if (e.top_p >= 1.0f) e.top_p = 1.0f;
+  const bool greedy = !(e.temperature > 0.f) || min(e.top_k, V) > kSampleMaxK || !(e.top_p > 0.f) ||
+                      (spec && e.top_k == 0 && e.top_p < 1.0f);
+  if (greedy) {
+    e.temperature = 1.0f;
+    e.top_k = 1;
+    e.top_p = 1.0f;
+  }
+  const bool pen_ok = e.repetition_penalty > 0.f && (e.presence_penalty - e.presence_penalty == 0.f) &&
+                      (e.frequency_penalty - e.frequency_penalty == 0.f);
+  if (!pen_ok) {
+    e.repetition_penalty = 1.0f;
+    e.presence_penalty = 0.f;
+    e.frequency_penalty = 0.f;
+  }
+  return e;
+}
+
 // the Philox key words of a 64-bit seed
 inline uint32_t seed_lo32(uint64_t seed) { return static_cast<uint32_t>(seed); }
 inline uint32_t seed_hi32(uint64_t seed) { return static_cast<uint32_t>(seed >> 32); }

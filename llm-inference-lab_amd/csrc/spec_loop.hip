@@ -72,6 +72,8 @@ struct sd_specdec {
   int fsm = 0;
   sd::FsmBind fsm_bind{};          // pos: [B][K+1], the loop's own (allocated at first use)
   int32_t* fsm_pos = nullptr;
+  // per-row parameters (sd_specdec_set_row_sampling): device [B], caller-owned, read by the kernels at run time
+  const sd_row_sampling* row_table = nullptr;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -201,6 +203,8 @@ struct StepPlan {
   bool heads;         // Medusa heads propose the NEXT step's tokens after the verify (set_medusa on an EAGLE loop keeps both)
   Select select;
   bool shaped;        // speculative sampling with both distributions shaped by top-k / top-p
+  bool rows;          // a row table is bound: the draws, the statistics and the process launches are the _rows kernels, which read
+                      // their parameters from table[b] at run time (the loop's scalars are not in those launches)
   bool lp;            // logit processors: the forwards store their rows (into the buffer of the sampling mode that is on, else the
                       // mode's own), the rows are processed in place and the argmax of the processed row replaces the fused one
   bool two;           // the draft forwards run on a stream of their own, forked from and joined to the target's
@@ -229,6 +233,7 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   p.select = s.sample ? SELECT_SAMPLED_BONUS : (s.spec ? SELECT_SPEC : SELECT_GREEDY);   // (the setters keep the two apart)
   const bool spec = p.select == SELECT_SPEC;
   p.shaped = spec && s.spec_top_k > 0;
+  p.rows = s.row_table != nullptr;
   p.lp = s.lp != 0;
   p.two = two_streams && s.draft;
   p.fwd0_select = s.draft && s.st.fwd0_w && s.B == 1 && persist_pass_ok(s.draft, 2, 1, 2);
@@ -299,6 +304,7 @@ struct DraftScope {
 static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, int rows, bool more_forms, hipStream_t st_d) {
   const sd_model* d = s->draft;
   const int V = s->target->cfg.vocab;
+  const sd_row_sampling* const table = p.rows ? s->row_table : nullptr;
   if (p.hand == HAND_FINALIZE)
     return launch_draft_finalize(d->part_val, d->part_idx, d->head_grid, M, i, s->st.draft_ids + (rows - M), s->st, d->skip_k, d->skip_i, st_d);
   if (more_forms) return 0;
@@ -306,11 +312,11 @@ static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, i
     if (int rc = launch_logit_process(p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V, s->lp_counts,
                                       s->lp_bias, s->st.draft_tok, s->K, i, s->st.active, s->lp_rp, s->lp_presence, s->lp_frequency,
                                       p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d,
-                                      s->fsm ? &s->fsm_bind : nullptr))
+                                      s->fsm ? &s->fsm_bind : nullptr, table))
       return rc;
   if (p.hand == HAND_DRAW)
     return launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p,
-                                  s->seed, s->draw, s->stream_id, st_d);
+                                  s->seed, s->draw, s->stream_id, st_d, table);
   return launch_draft_next(rows, i, s->st, st_d);
 }
 
@@ -352,13 +358,14 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
   const int B = s->B, K = s->K, V = s->target->cfg.vocab;
   const unsigned* const st_word_d = (s->draft && s->draft->p_sync) ? s->draft->p_sync + 1 : nullptr;
   const unsigned* const st_word_t = s->target->p_sync ? s->target->p_sync + 1 : nullptr;
+  const sd_row_sampling* const table = p.rows ? s->row_table : nullptr;
   if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, K + 1, p.tail ? nullptr : s->st.target_ids,
                              K + 1, p.p_buf, SD_BF16, 0, st_t))
     return rc;
   if (p.lp)   // all B * (K+1) rows in one launch: row (b, i) is conditioned on d_1..d_i; the processed argmax replaces the fused ids
     if (int rc = launch_logit_process(p.p_buf, V, B, K + 1, V, s->lp_counts, s->lp_bias, s->st.draft_tok, K, -1, s->st.active, s->lp_rp,
                                       s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t,
-                                      s->fsm ? &s->fsm_bind : nullptr))
+                                      s->fsm ? &s->fsm_bind : nullptr, table))
       return rc;
   if (p.tail) {
     if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
@@ -368,11 +375,11 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
     if (p.select == SELECT_SAMPLED_BONUS) {
       // accept length -> draw the token after the accepted prefix from the stored logits of that position
       if (int rc = launch_accept_len(s->st, st_t)) return rc;
-      if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t)) return rc;
+      if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t, table)) return rc;
     } else if (p.select == SELECT_SPEC) {
       // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
       if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p, s->seed,
-                                    s->draw, s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
+                                    s->draw, s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t, table))
         return rc;
     }
     const int use_sampled = p.select == SELECT_SPEC ? 2 : (p.select == SELECT_SAMPLED_BONUS ? 1 : 0);
@@ -744,6 +751,19 @@ extern "C" int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p
   drop_graph(s);   // unconditional, whether or not speculative sampling is on: the captured step holds the launches of the other shape
   s->spec_top_k = top_k > 0 ? top_k : 0;
   s->spec_top_p = top_k > 0 ? top_p : 1.0f;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling* table) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_row_sampling: NULL");
+  if (table) {
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "specdec_set_row_sampling: the row table must be 16-byte aligned");
+    SD_REQUIRE(s->sample || s->spec || s->lp, "specdec_set_row_sampling: neither a sampling mode nor the logit-processor stage is on "
+               "(sd_specdec_set_sampling / sd_specdec_set_spec_sampling / sd_specdec_set_logit_processors first)");
+  }
+  drop_graph(s);   // unconditional: the captured step holds either the scalar launches or the row launches
+  s->row_table = table;
   return 0;
 }
 

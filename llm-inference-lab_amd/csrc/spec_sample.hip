@@ -58,6 +58,11 @@
 //   spec_stats_shaped_kernel       grid (K+1, B): the kept sets of q_i (re-selected from the stored row) and p_i, the lookup
 //                                  of d in both, ratio and flag, q' looked up for each of p's <= 1024 ids, the residual walk
 //   spec_accept_kernel             unchanged
+//
+// PER-ROW parameters (sd_spec_sample_accept_rows, sd_specdec_set_row_sampling): spec_draft_draw_rows_kernel and
+// spec_stats_rows_kernel read row b's sd_row_sampling entry, normalise it for speculative sampling (normalise_row_sampling,
+// sample_device.h: the full-vocabulary nucleus is a greedy row here) and run the unshaped body for a row without top_k and
+// top_p, the shaped body for any other — each row the draw schedule of its scalar mode; spec_accept_kernel is unchanged.
 
 #include "engine.h"
 #include "sample_device.h"
@@ -100,10 +105,18 @@ struct SpecDrawArgs {
   const int32_t* stream_id;
 };
 
-__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const SpecDrawArgs a, SpecState s) {
-  __shared__ double sv[kSpecWaves];
-  __shared__ int si[kSpecWaves];
-  const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+// The bodies of the draw and statistics kernels, unshaped and shaped, as device functions on an LDS block of their caller: the
+// scalar kernels call them with the launch's parameters, the _rows kernels with the row's own (temperature and seed in the
+// argument block, the shape beside it).
+struct SpecArgBestLds {
+  double sv[kSpecWaves];
+  int si[kSpecWaves];
+};
+
+__device__ __forceinline__ void spec_draft_draw_row(SpecArgBestLds& G, const SpecDrawArgs& a, const SpecState& s, int b) {
+  double* const sv = G.sv;
+  int* const si = G.si;
+  const int tid = threadIdx.x, V = a.V;
   const uint16_t* src = a.src + (static_cast<size_t>(b) * a.src_rows_per_b + a.src_row) * V;
   uint16_t* dst = a.q + (static_cast<size_t>(b) * s.K + a.i) * V;
   const double T = static_cast<double>(a.temperature);
@@ -125,6 +138,11 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const S
     s.verify_tok[b * (s.K + 1) + a.i + 1] = d;
     s.next_tok[b] = d;
   }
+}
+
+__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const SpecDrawArgs a, SpecState s) {
+  __shared__ SpecArgBestLds G;
+  spec_draft_draw_row(G, a, s, blockIdx.x);
 }
 
 static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, float temperature,
@@ -161,11 +179,17 @@ struct SpecStatArgs {
   double* ratios;             // nullable [B][K]
 };
 
-__global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecStatArgs a) {
-  __shared__ double sh[kSpecWaves];
-  __shared__ double sv[kSpecWaves];
-  __shared__ int si[kSpecWaves];
-  const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, K = a.K, V = a.V;
+struct SpecStatsLds {
+  double sh[kSpecWaves];
+  double sv[kSpecWaves];
+  int si[kSpecWaves];
+};
+
+__device__ __forceinline__ void spec_stats_row(SpecStatsLds& G, const SpecStatArgs& a, int i, int b) {
+  double* const sh = G.sh;
+  double* const sv = G.sv;
+  int* const si = G.si;
+  const int tid = threadIdx.x, K = a.K, V = a.V;
   if (a.active && a.active[b] == 0) return;
   const uint16_t* rp = a.P + (static_cast<size_t>(b) * (K + 1) + i) * V;
   const uint16_t* rq = i < K ? a.Q + (static_cast<size_t>(b) * K + i) * V : rp;   // position K has no q row
@@ -244,6 +268,11 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecSt
   if (tid == 0) a.cand[b * (K + 1) + i] = (residual && ri != 0x7fffffff) ? ri : pi;
 }
 
+__global__ __launch_bounds__(kSampleThreads) void spec_stats_kernel(const SpecStatArgs a) {
+  __shared__ SpecStatsLds G;
+  spec_stats_row(G, a, blockIdx.x, blockIdx.y);
+}
+
 // ------------------------------------------------------------------------------------------------------------- accept
 struct SpecAcceptArgs {
   const int32_t* flag;
@@ -310,9 +339,8 @@ static int check_spec_shape(const char* who, int top_k, float top_p) {
   return 0;
 }
 
-__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(const SpecDrawArgs a, const SpecShape sh, SpecState s) {
-  __shared__ SurvivorLds L;
-  const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+__device__ __forceinline__ void spec_draft_draw_shaped_row(SurvivorLds& L, const SpecDrawArgs& a, const SpecShape& sh, const SpecState& s, int b) {
+  const int tid = threadIdx.x, V = a.V;
   const uint16_t* src = a.src + (static_cast<size_t>(b) * a.src_rows_per_b + a.src_row) * V;
   uint16_t* dst = a.q + (static_cast<size_t>(b) * s.K + a.i) * V;
   copy_and_visit_bf16_row(src, dst, V, tid, [](float, int) {});
@@ -327,12 +355,52 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(
   }
 }
 
-// the draw + hand-over after a draft forward; top_k == 0: spec_draft_draw_kernel, else the shaped kernel
+__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_shaped_kernel(const SpecDrawArgs a, const SpecShape sh, SpecState s) {
+  __shared__ SurvivorLds L;
+  spec_draft_draw_shaped_row(L, a, sh, s, blockIdx.x);
+}
+
+// Per-row parameters: the row's entry, normalised for speculative sampling, written over the launch's temperature and seed;
+// returns the row's shape (top_k == 0: the unshaped statistics).
+template <typename Args>
+__device__ __forceinline__ SpecShape spec_row_params(Args& a, const sd_row_sampling* table, int b) {
+  const sd_row_sampling e = normalise_row_sampling(table, b, a.V, true);
+  a.temperature = e.temperature;
+  a.seed_lo = e.seed_lo;
+  a.seed_hi = e.seed_hi;
+  return SpecShape{e.top_k, e.top_p};
+}
+
+// one path runs per workgroup: the LDS blocks of the two overlay each other
+union SpecDrawRowsLds {
+  SpecArgBestLds plain;
+  SurvivorLds shaped;
+};
+
+__global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_rows_kernel(const SpecDrawArgs a0, const sd_row_sampling* table, SpecState s) {
+  __shared__ SpecDrawRowsLds U;
+  const int b = blockIdx.x;
+  SpecDrawArgs a = a0;
+  const SpecShape sh = spec_row_params(a, table, b);
+  if (sh.top_k > 0) spec_draft_draw_shaped_row(U.shaped, a, sh, s, b);
+  else spec_draft_draw_row(U.plain, a, s, b);
+}
+
+// the draw + hand-over after a draft forward; top_k == 0: spec_draft_draw_kernel, else the shaped kernel; with a table the row
+// kernel, whatever the scalars say
 int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
                            float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
-                           hipStream_t st) {
+                           hipStream_t st, const sd_row_sampling* table) {
   SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
   const SpecDrawArgs a = spec_draw_args(src, src_rows_per_b, src_row, q, i, V, temperature, seed, draw, stream_id);
+  if (table) {
+    SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
+               "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_draft_draw: the row table must be 16-byte aligned");
+    hipLaunchKernelGGL(spec_draft_draw_rows_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, table, s);
+    SD_LAUNCH_CHECK();
+    return 0;
+  }
   SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && (top_k <= 0 || V <= (1 << kIdxBits)) && src_rows_per_b >= 1 && src_row >= 0 &&
                  src_row < src_rows_per_b, "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
   if (top_k > 0) {
@@ -347,13 +415,21 @@ int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per
 
 // position i of row b: flag + ratio (i < K) and the candidate next token. Static LDS: the survivor block (48 KB) + q's kept set
 // (12 KB); q's weights are overwritten by the residual once every lookup of q' has been made.
-__global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const SpecStatArgs a, const SpecShape sh) {
-  __shared__ SurvivorLds L;
-  __shared__ double qe[kSampleMaxK];
-  __shared__ int qi[kSampleMaxK];
-  __shared__ double s_ep, s_eq;
-  __shared__ int s_in_q;
-  const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, K = a.K, V = a.V;
+struct SpecShapedLds {
+  SurvivorLds L;
+  double qe[kSampleMaxK];
+  int qi[kSampleMaxK];
+  double s_ep, s_eq;
+  int s_in_q;
+};
+
+__device__ __forceinline__ void spec_stats_shaped_row(SpecShapedLds& G, const SpecStatArgs& a, const SpecShape& sh, int i, int b) {
+  SurvivorLds& L = G.L;
+  double* const qe = G.qe;
+  int* const qi = G.qi;
+  double &s_ep = G.s_ep, &s_eq = G.s_eq;
+  int& s_in_q = G.s_in_q;
+  const int tid = threadIdx.x, K = a.K, V = a.V;
   if (a.active && a.active[b] == 0) return;
   const uint16_t* rp = a.P + (static_cast<size_t>(b) * (K + 1) + i) * V;
   const int k = min(sh.top_k, V);
@@ -413,10 +489,39 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const
   }
 }
 
-// statistics, then accept; top_k == 0: spec_stats_kernel, else the shaped kernel
-static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st) {
-  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && (top_k <= 0 || sa.V <= (1 << kIdxBits)),
+__global__ __launch_bounds__(kSampleThreads) void spec_stats_shaped_kernel(const SpecStatArgs a, const SpecShape sh) {
+  __shared__ SpecShapedLds G;
+  spec_stats_shaped_row(G, a, sh, blockIdx.x, blockIdx.y);
+}
+
+union SpecStatsRowsLds {
+  SpecStatsLds plain;
+  SpecShapedLds shaped;
+};
+
+__global__ __launch_bounds__(kSampleThreads) void spec_stats_rows_kernel(const SpecStatArgs a0, const sd_row_sampling* table) {
+  __shared__ SpecStatsRowsLds U;
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (a0.active && a0.active[b] == 0) return;
+  SpecStatArgs a = a0;
+  const SpecShape sh = spec_row_params(a, table, b);
+  if (sh.top_k > 0) spec_stats_shaped_row(U.shaped, a, sh, i, b);
+  else spec_stats_row(U.plain, a, i, b);
+}
+
+// statistics, then accept; top_k == 0: spec_stats_kernel, else the shaped kernel; with a table the row kernel
+static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st,
+                               const sd_row_sampling* table = nullptr) {
+  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && ((top_k <= 0 && !table) || sa.V <= (1 << kIdxBits)),
              "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
+  if (table) {
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_sample: the row table must be 16-byte aligned");
+    hipLaunchKernelGGL(spec_stats_rows_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, table);
+    SD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
+    SD_LAUNCH_CHECK();
+    return 0;
+  }
   SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
   if (top_k > 0) {
     if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
@@ -432,12 +537,13 @@ static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa,
 
 // the step's statistics + accept: accept length -> s.accept_len, next token -> s.sampled, counters advanced
 int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st) {
+                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st,
+                     const sd_row_sampling* table) {
   SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
   const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, s.draft_tok, s.K, V, temperature, seed, draw, 0, stream_id, s.active,
                                          flag, cand, nullptr);
   const SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
-  return launch_spec_kernels(sa, aa, s.B, top_k, top_p, st);
+  return launch_spec_kernels(sa, aa, s.B, top_k, top_p, st, table);
 }
 
 }  // namespace sd
@@ -453,7 +559,8 @@ extern "C" size_t sd_spec_sample_workspace(int B, int K) {
 static int spec_sample_accept_op(const char* who, int top_k, float top_p, const void* draft_logits, const void* target_logits,
                                  const int32_t* draft_ids, int B, int K, int V, float temperature, uint64_t seed, uint32_t* draw_counters,
                                  uint32_t draw0, const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out,
-                                 int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
+                                 int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes, void* stream,
+                                 const sd_row_sampling* table = nullptr) {
   SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "%s: NULL argument", who);
   SD_REQUIRE(B >= 1 && K >= 1, "%s: B=%d K=%d", who, B, K);
   SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "%s: workspace %zu B < %zu B", who, workspace_bytes,
@@ -465,7 +572,7 @@ static int spec_sample_accept_op(const char* who, int top_k, float top_p, const 
   const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
                                          active, flag, cand, ratios_out);
   const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream));
+  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream), table);
 }
 
 extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
@@ -491,4 +598,16 @@ extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void
   return spec_sample_accept_op("spec_sample_accept_shaped", top_k, top_p, draft_logits, target_logits, draft_ids, B, K, V, temperature,
                                seed, draw_counters, draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace,
                                workspace_bytes, stream);
+}
+
+extern "C" int sd_spec_sample_accept_rows(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K, int V,
+                                          const sd_row_sampling* table, uint32_t* draw_counters, uint32_t draw0, const int32_t* stream_ids,
+                                          const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out, double* ratios_out,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  SD_REQUIRE(table, "spec_sample_accept_rows: NULL table");
+  SD_REQUIRE(B >= 1, "spec_sample_accept_rows: B=%d", B);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_sample_accept_rows: the row table must be 16-byte aligned");
+  return spec_sample_accept_op("spec_sample_accept_rows", 0, 1.0f, draft_logits, target_logits, draft_ids, B, K, V, 1.0f, 0, draw_counters,
+                               draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace, workspace_bytes, stream, table);
 }

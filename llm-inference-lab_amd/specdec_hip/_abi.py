@@ -162,6 +162,23 @@ SIGNATURES = {
          ctypes.c_float, ctypes.c_float, _c_void_p, _c_int, _c_void_p, _c_size, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
     ),
     "sd_specdec_set_grammar": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int]),
+    "sd_row_sampling_bytes": (_c_size, []),
+    "sd_sample_token_rows": (
+        _c_int,
+        [_c_void_p, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, ctypes.c_uint32, _c_void_p,
+         _c_void_p, _c_void_p],
+    ),
+    "sd_spec_sample_accept_rows": (
+        _c_int,
+        [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, ctypes.c_uint32, _c_void_p, _c_void_p,
+         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
+    ),
+    "sd_logit_process_rows": (
+        _c_int,
+        [_c_void_p, _c_i64, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
+         _c_void_p, _c_int, _c_void_p, _c_size, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
+    ),
+    "sd_specdec_set_row_sampling": (_c_int, [_c_void_p, _c_void_p]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),
@@ -229,6 +246,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         got = lib.sd_abi_version()
         if got != SD_ABI_VERSION:
             raise HipLibraryError(f"{path}: ABI version {got}, binding expects {SD_ABI_VERSION}")
+        from .sampling_params import ROW_BYTES
+
+        if lib.sd_row_sampling_bytes() != ROW_BYTES:
+            raise HipLibraryError(f"{path}: sd_row_sampling is {lib.sd_row_sampling_bytes()} bytes, the binding's struct {ROW_BYTES}")
         _lib = lib
         return lib
 

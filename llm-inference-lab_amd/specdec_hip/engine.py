@@ -683,6 +683,10 @@ class HipSpecDec:
         self.sampling = self.spec_sampling = False
         self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
+        # per-row parameters (set_row_sampling): none; the table is allocated at first use and kept (rewritten in place)
+        self.row_table = None          # uint8 [B][32] on the device: sd_row_sampling[B], or None while the scalars rule
+        self.row_params = None         # the host's view of it: List[SamplingParams]
+        self._row_table_buf = None
         # logit processors (set_logit_processors): off; counts / bias tables are allocated at first use and kept
         self.logit_processors = False
         self.logit_counts = self.logit_bias = self._lp_ws = None
@@ -891,6 +895,54 @@ class HipSpecDec:
             raise RuntimeError("set_grammar_state: no grammar is bound (set_grammar)")
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream_t):
             self.grammar_state[int(b):int(b) + 1].fill_(int(state))
+
+    def set_row_sampling(self, params) -> None:
+        """Per-row sampling parameters inside the step (sd_specdec_set_row_sampling): `params` is one SamplingParams per batch
+        row (seeds resolved), or None to return to the loop's scalars. With a table the draws, the speculative-sampling
+        statistics and the logit-processor launches read row b's temperature, top_k, top_p, seed and penalties from the table
+        at run time; the mode and the buffers stay what set_sampling / set_spec_sampling / set_logit_processors configured.
+        Either call drops the captured step; set_row_params then rewrites a slot and keeps it."""
+        from .sampling_params import ROW_BYTES, pack
+
+        with torch.cuda.device(self.device):
+            if params is None:
+                _abi.check(self.lib.sd_specdec_set_row_sampling(self.handle, None), "sd_specdec_set_row_sampling")
+                self.row_table = self.row_params = None
+                return
+            params = list(params)
+            if len(params) != self.B:
+                raise ValueError(f"set_row_sampling: {len(params)} entries for {self.B} rows")
+            if self._row_table_buf is None:
+                self._row_table_buf = torch.zeros((self.B, ROW_BYTES), dtype=torch.uint8, device=self.device)
+            with torch.cuda.stream(self.stream_t):
+                self._row_table_buf.copy_(pack(params, self.device))
+            _abi.check(self.lib.sd_specdec_set_row_sampling(self.handle, self._row_table_buf.data_ptr()), "sd_specdec_set_row_sampling")
+            self.row_table = self._row_table_buf
+            self.row_params = params
+
+    def set_row_params(self, b: int, params, stream_id: Optional[int] = None, draw_count: Optional[int] = None) -> None:
+        """Slot b's entry of the bound table <- `params` (a SamplingParams, seed resolved), written on the loop's target stream:
+        a new request in the slot. stream_id / draw_count: the slot's Philox stream and draw counter, rewritten the same way.
+        The captured step is kept — its kernels read all three at run time."""
+        from .sampling_params import pack
+
+        if self.row_table is None:
+            raise RuntimeError("set_row_params: no table is bound (set_row_sampling)")
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"set_row_params: row {b} of {self.B}")
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream_t):
+            self.row_table[b:b + 1].copy_(pack([params], self.device))
+            if stream_id is not None:
+                self._stream_ids[b:b + 1].fill_(int(stream_id))
+            if draw_count is not None:
+                self._draw[b:b + 1].copy_(torch.tensor([int(draw_count) & 0xFFFFFFFF], dtype=torch.int64).to(torch.int32).to(self.device))
+        self.row_params[b] = params
+
+    @property
+    def stream_ids(self) -> List[int]:
+        """The rows' Philox stream ids on the device (synchronises)."""
+        return [int(x) for x in self._stream_ids.cpu().tolist()]
 
     def set_draw_counts(self, draw_counts: Sequence[int]) -> None:
         """Rewrite the rows' draw counters (sampling modes) on the loop's target stream: the host's in-order view after steps

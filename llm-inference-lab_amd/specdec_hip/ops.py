@@ -394,6 +394,84 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     return (accept, nxt, ratios) if return_ratios else (accept, nxt)
 
 
+def _row_table(name: str, table, B: int, dev) -> torch.Tensor:
+    """The device table of a _rows op: a list of SamplingParams is packed, a tensor (sampling_params.pack: uint8 [B][32]) is
+    taken as it is."""
+    from .sampling_params import ROW_BYTES, pack
+
+    if not isinstance(table, torch.Tensor):
+        table = pack(list(table), dev)
+    if table.dtype != torch.uint8 or table.device != dev or not table.is_contiguous() or table.numel() != B * ROW_BYTES:
+        raise ValueError(f"{name}: the table must be a contiguous uint8 [{B}][{ROW_BYTES}] tensor on {dev} (sampling_params.pack)")
+    return table
+
+
+def sample_token_rows_hip(logits: torch.Tensor, table, draw: int = 0, pos: Optional[torch.Tensor] = None, rows_per_entry: int = 1,
+                          draw_counters: Optional[torch.Tensor] = None, stream_ids: Optional[torch.Tensor] = None,
+                          active: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sample_token_hip with every entry's own temperature, top_k, top_p and seed (sd_sample_token_rows): `table` is a list of
+    SamplingParams, one per entry, or their packed tensor. Entry b's result is that of sample_token_hip on its row alone with
+    its normalised parameters, the same draw and the same stream id."""
+    lib = _abi.load()
+    if logits.dim() == 1:
+        logits = logits.unsqueeze(0)
+    if logits.dim() != 2:
+        raise ValueError(f"sample_token_rows: logits must be [rows, V], got {tuple(logits.shape)}")
+    dev = _require_device("sample_token_rows", logits)
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    rows, V = logits.shape
+    if rows % rows_per_entry:
+        raise ValueError(f"sample_token_rows: {rows} rows is not a multiple of rows_per_entry={rows_per_entry}")
+    B = rows // rows_per_entry
+    for name, t in (("pos", pos), ("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"sample_token_rows: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    table = _row_table("sample_token_rows", table, B, dev)
+    out = torch.empty(B, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_sample_token_rows(logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0), B, V, ptr(pos),
+                                            int(rows_per_entry), ptr(active), table.data_ptr(), ptr(draw_counters),
+                                            int(draw) & 0xFFFFFFFF, ptr(stream_ids), out.data_ptr(), _stream_ptr(dev)),
+                   "sd_sample_token_rows")
+    return out
+
+
+def spec_sample_accept_rows_hip(draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor, table, draw: int = 0,
+                                draw_counters: Optional[torch.Tensor] = None, stream_ids: Optional[torch.Tensor] = None,
+                                active: Optional[torch.Tensor] = None, return_ratios: bool = False):
+    """spec_sample_accept_hip with every row's own temperature, top_k, top_p and seed (sd_spec_sample_accept_rows): a row
+    without top_k and top_p runs the unshaped statistics, any other row the shaped ones; a row the speculative-sampling
+    kernels cannot honour (temperature 0, top_p without top_k, ...) is a greedy row. Shapes and results as
+    spec_sample_accept_hip."""
+    lib = _abi.load()
+    dev = _require_device("spec_sample_accept_rows", draft_logits, target_logits, draft_ids)
+    if draft_logits.dim() != 3 or target_logits.dim() != 3 or draft_ids.dim() != 2:
+        raise ValueError("spec_sample_accept_rows: need draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]")
+    B, K, V = draft_logits.shape
+    if tuple(target_logits.shape) != (B, K + 1, V) or tuple(draft_ids.shape) != (B, K):
+        raise ValueError(f"spec_sample_accept_rows: shapes {tuple(draft_logits.shape)} / {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
+    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16 or draft_ids.dtype != torch.int32:
+        raise TypeError("spec_sample_accept_rows: logits must be bfloat16 and draft_ids int32")
+    draft_logits, target_logits, draft_ids = draft_logits.contiguous(), target_logits.contiguous(), draft_ids.contiguous()
+    for name, t in (("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"spec_sample_accept_rows: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    table = _row_table("spec_sample_accept_rows", table, B, dev)
+    accept = torch.zeros(B, dtype=torch.int32, device=dev)
+    nxt = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
+    ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_spec_sample_accept_rows(draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V,
+                                                  table.data_ptr(), ptr(draw_counters), int(draw) & 0xFFFFFFFF, ptr(stream_ids),
+                                                  ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios), ws.data_ptr(), ws.numel(),
+                                                  _stream_ptr(dev)), "sd_spec_sample_accept_rows")
+    return (accept, nxt, ratios) if return_ratios else (accept, nxt)
+
+
 def logit_counts(B: int, V: int, device) -> torch.Tensor:
     """A zeroed counts table for the logit processors: int16 [B][V] holding the uint16 words of sd_logit_process (bit 15: the
     token is in the row's prompt, i.e. a negative int16; bits 0..14: times generated, saturating at 32767)."""
@@ -547,6 +625,54 @@ def logit_process_fsm(rows: torch.Tensor, counts: torch.Tensor, nxt: torch.Tenso
                                             ptr(active), float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
                                             ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0, nxt.data_ptr(), allow.data_ptr(), S,
                                             fsm_state.data_ptr(), int(eos_id), _stream_ptr(dev)), "sd_logit_process_fsm")
+    return ids
+
+
+def logit_process_rows_hip(rows: torch.Tensor, counts: torch.Tensor, table, bias: Optional[torch.Tensor] = None,
+                           tokens: Optional[torch.Tensor] = None, n_tokens: Optional[int] = None, active: Optional[torch.Tensor] = None,
+                           return_ids: bool = False, nxt: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                           fsm_state: Optional[torch.Tensor] = None, eos_id: int = 0):
+    """logit_process / logit_process_fsm with every batch row's own penalties (sd_logit_process_rows): `table` is a list of
+    SamplingParams, one per batch row, or their packed tensor; a row whose penalties the scalar op would refuse is processed
+    with the identity. nxt / allow / fsm_state: the grammar of logit_process_fsm, all None for none."""
+    lib = _abi.load()
+    grammar = nxt is not None or allow is not None or fsm_state is not None
+    if grammar and (nxt is None or allow is None or fsm_state is None):
+        raise ValueError("logit_process_rows: a grammar needs nxt, allow and fsm_state")
+    dev = _require_device("logit_process_rows", rows, counts, *([nxt, allow, fsm_state] if grammar else []))
+    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
+        raise ValueError("logit_process_rows: rows must be bfloat16 [B][R][V]")
+    B, R, V = (int(x) for x in rows.shape)
+    if _check_counts("logit_process_rows", counts, dev) != (B, V):
+        raise ValueError(f"logit_process_rows: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
+    S = 0
+    if grammar:
+        S, Vn = _check_fsm_table("logit_process_rows", nxt, dev)
+        if Vn != V or allow.dtype != torch.int32 or tuple(allow.shape) != (S, (V + 31) // 32) or not allow.is_contiguous():
+            raise ValueError(f"logit_process_rows: tables {tuple(nxt.shape)} / {tuple(allow.shape)} for V={V} (fsm_tables)")
+        if fsm_state.dtype != torch.int32 or fsm_state.numel() != B or not fsm_state.is_contiguous():
+            raise ValueError(f"logit_process_rows: fsm_state must be a contiguous int32 [{B}] tensor")
+    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
+    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
+        raise ValueError("logit_process_rows: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
+        raise ValueError(f"logit_process_rows: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
+    n_tok = -1 if n_tokens is None else int(n_tokens)
+    tok_stride = 0
+    if tokens is not None:
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
+            raise ValueError(f"logit_process_rows: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
+        tok_stride = int(tokens.shape[1])
+    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
+        raise ValueError(f"logit_process_rows: active must be a contiguous int32 [{B}] tensor on {dev}")
+    table = _row_table("logit_process_rows", table, B, dev)
+    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
+    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_logit_process_rows(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
+                                             ptr(active), table.data_ptr(), ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0,
+                                             ptr(nxt), ptr(allow), S, ptr(fsm_state), int(eos_id), _stream_ptr(dev)), "sd_logit_process_rows")
     return ids
 
 

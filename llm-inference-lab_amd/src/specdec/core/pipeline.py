@@ -425,15 +425,21 @@ class SpeculativePipeline:
     # ------------------------------------------------------------------ the loop
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None,
-                      self_draft: bool = False, share_prefix: bool = False, grammar=None, **processors) -> "DecodeSession":
+                      self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
+                      **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
         (DecodeSession). processors: repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids,
         allowed_token_ids (logit_processor_config); identity values leave the mode off. grammar: a TokenFSM, or a list with one
-        entry per prompt (None: that row is unconstrained) — grammar_config."""
+        entry per prompt (None: that row is unconstrained) — grammar_config. sampling_params: one SamplingParams per prompt
+        (row_sampling_config; in place of `sampling` and of penalty arguments)."""
+        if sampling_params is not None:
+            if sampling is not None:
+                raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
+            sampling = self.row_sampling_config(sampling_params, len(prompts), 1, None, processors, heads=self_draft)
         return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix,
-                             self.logit_processor_config(processors), self.grammar_config(grammar, len(prompts)))
+                             self._row_processors(sampling, self.logit_processor_config(processors)), self.grammar_config(grammar, len(prompts)))
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
                 sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False,
@@ -777,12 +783,66 @@ class SpeculativePipeline:
         return {"spec": True, "temperature": float(self.policy.temperature), "top_k": self.policy.top_k,
                 "top_p": self.policy.top_p if self.policy.top_k else None, "seed": int(kwargs.get("seed", self.policy.seed))}
 
+    _ROW_SAMPLING_CLASH = ("top_k", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty")
+
+    def row_sampling_config(self, sampling_params, n_prompts: int, n: int, do_sample: Optional[bool], kwargs: Dict[str, Any],
+                            heads: bool = False) -> Optional[Dict[str, Any]]:
+        """Per-request sampling parameters of a call: one specdec_hip.sampling_params.SamplingParams per prompt, expanded
+        with `n` as a grammar list is. -> None, or the session's `sampling` description: the step's mode (the sampled bonus
+        token under policy="longest_prefix", speculative sampling under policy="rejection" with backend="device") with "rows"
+        = every row's parameters, seeds resolved (an entry without a seed takes the call's), and "ids" = every row's Philox
+        stream id, its index among the call's rows — what a request samples does not depend on the slot it decodes in.
+        Refused: call-level do_sample / top_k / top_p / penalties next to it (which of the two would rule a row?), the
+        host-loop policies, adaptive K, Medusa / EAGLE drafting, implementation="fake", and values the device would only turn
+        into a greedy row (SamplingParams.check)."""
+        if sampling_params is None:
+            return None
+        from specdec_hip.sampling_params import SamplingParams
+
+        from ..policies.controllers import FixedKController
+
+        clash = [k for k in self._ROW_SAMPLING_CLASH if kwargs.get(k) is not None] + (["do_sample"] if do_sample is not None else [])
+        if clash:
+            raise ValueError(f"sampling_params carries every request's own parameters: the call-level {sorted(clash)} cannot be given with it")
+        entries = list(sampling_params)
+        if len(entries) != n_prompts:
+            raise ValueError(f"sampling_params: {len(entries)} entries for {n_prompts} prompts")
+        for e in entries:
+            if not isinstance(e, SamplingParams):
+                raise TypeError(f"sampling_params: expected SamplingParams, got {type(e).__name__}")
+        spec = self.policy_name == "rejection" and self.rejection_backend == "device"
+        if self._fake or not (self.policy_name == "longest_prefix" or spec):
+            raise NotImplementedError("sampling_params are read by the captured device step (implementation='hip'; policy 'longest_prefix', "
+                                      f"or 'rejection' with backend='device'): policy={self.policy_name!r} on the host loop is not supported with them")
+        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None or heads:
+            raise NotImplementedError("sampling_params need the draft-model mode (draft_mode='vanilla'): medusa / eagle drafting is not "
+                                      "supported with them")
+        if not isinstance(self.controller, FixedKController):
+            raise NotImplementedError("sampling_params keep a fixed K (controller='fixed'): adaptive K is not supported")
+        seed = int(kwargs.get("seed", self.policy.seed if spec else (self.config.get("seed") or 0)))
+        V = self.base_lm.vocab_size
+        rows = [e.with_seed(seed) for e in entries for _ in range(int(n))]
+        for e in rows:
+            e.check(V, spec=spec)
+        base = {"spec": True, "temperature": float(self.policy.temperature)} if spec else {"temperature": 1.0}
+        return {**base, "top_k": None, "top_p": None, "seed": seed, "rows": rows, "ids": list(range(len(rows)))}
+
+    @staticmethod
+    def _row_processors(sampling: Optional[Dict[str, Any]], processors: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
+        """Requests with penalties of their own switch the logit-processor stage on (identity scalars: the table rules)."""
+        if processors is None and sampling is not None and any(e.has_penalties for e in sampling.get("rows") or ()):
+            return {"rp": 1.0, "presence": 0.0, "frequency": 0.0, "bias": None}
+        return processors
+
     def generate(self, prompt: PromptLike, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  do_sample: Optional[bool] = None, **kwargs) -> Dict[str, Any]:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
         grammar = kwargs.pop("grammar", None)
+        if kwargs.pop("sampling_params", None) is not None:
+            raise NotImplementedError("sampling_params belong to generate_batch and generate_many (one entry per prompt of a batch): "
+                                      "generate() decodes one row")
         if kwargs.get("share_prefix") or int(kwargs.get("n", 1) or 1) != 1:
             raise NotImplementedError("share_prefix / n belong to generate_batch and generate_many: generate() decodes one row")
         max_tokens = max_tokens or self.config["max_new_tokens"]
@@ -833,7 +893,7 @@ class SpeculativePipeline:
 
     def generate_batch(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None,
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
-                       share_prefix: bool = False, n: int = 1, grammar=None, **kwargs) -> List[Dict[str, Any]]:
+                       share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -852,12 +912,18 @@ class SpeculativePipeline:
         row is unconstrained). A row under a grammar emits only token sequences its automaton allows, draft and target alike
         (the mask is a line of the step's logit-processor stage), ends on the automaton's eos, and is exempt from the overlap /
         de-duplication rules, which would delete tokens the automaton has consumed; greedy output is the target's own greedy
-        decoding under the mask, token for token."""
+        decoding under the mask, token for token.
+
+        sampling_params (opt-in; not in the reference): one SamplingParams per prompt (expanded with n) — every request its own
+        temperature (0: greedy), top_k, top_p, seed and penalties, read by the step's kernels row by row (row_sampling_config).
+        Under policy="longest_prefix" the step samples the bonus token; under policy="rejection" with backend="device" it is
+        speculative sampling. A request's Philox stream is its index among the call's rows."""
         if not prompts:
             return []
         n = int(n)
         if n < 1:
             raise ValueError(f"n={n} (at least 1)")
+        row_sampling = self.row_sampling_config(sampling_params, len(prompts), n, do_sample, kwargs, heads=self.medusa_heads is not None)
         share_prefix = bool(share_prefix) or n > 1
         if share_prefix and (self._fake or (self.policy_name != "longest_prefix"
                                             and not (self.policy_name == "rejection" and self.rejection_backend == "device"))):
@@ -872,7 +938,7 @@ class SpeculativePipeline:
         max_tokens = max_tokens or self.config["max_new_tokens"]
         temperature = temperature or self.config["temperature"]
         do_sample = do_sample if do_sample is not None else self.config["do_sample"]
-        sampling = self._sampling_config(do_sample, temperature, kwargs)
+        sampling = row_sampling if row_sampling is not None else self._sampling_config(do_sample, temperature, kwargs)
         heads = self.medusa_heads is not None    # persistent heads also serve generate_batch (opt-in, not in the reference)
         if self.draft_lm is None and not heads:
             raise ValueError("generate_batch drafts with the draft model (the reference ignores draft_mode there): pass draft_lm / draft_model")
@@ -882,10 +948,11 @@ class SpeculativePipeline:
             prompts = [p for p in prompts for _ in range(n)]
         ids = [self._encode(p) for p in prompts]
         device_step = self.policy_name == "longest_prefix" or (self.policy_name == "rejection" and self.rejection_backend == "device")
-        processors = self._processors_for_step(kwargs, device_step, f"policy={self.policy_name!r} on the host loop")
+        processors = self._row_processors(row_sampling, self._processors_for_step(kwargs, device_step, f"policy={self.policy_name!r} on the host loop"))
         grammar = self._grammar_for_step(grammar, len(ids), device_step and not heads, f"policy={self.policy_name!r} on the host loop")
         if self.policy_name == "rejection" and self.rejection_backend == "device":
-            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=self._spec_sampling_config(kwargs),
+            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens,
+                                    sampling=row_sampling if row_sampling is not None else self._spec_sampling_config(kwargs),
                                     share_prefix=share_prefix, processors=processors, grammar=grammar)
         elif self.policy_name == "rejection":
             rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
@@ -929,7 +996,7 @@ class SpeculativePipeline:
 
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
-                      grammar=None, **kwargs) -> List[Dict[str, Any]]:
+                      grammar=None, sampling_params=None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -938,12 +1005,16 @@ class SpeculativePipeline:
         share_prefix / n: as generate_batch — a prompt admitted to a slot is also compared with the rows the session holds at
         that moment (finished rows whose caches are still intact included), so a system prompt in front of many questions is
         computed once per session, not once per question; with n > 1 the results are prompt-major (n per prompt).
-        grammar: as generate_batch, one entry per prompt; a prompt admitted to a slot starts in its own automaton's start state."""
+        grammar: as generate_batch, one entry per prompt; a prompt admitted to a slot starts in its own automaton's start state.
+        sampling_params: as generate_batch, one entry per prompt; a prompt admitted to a slot brings its own entry, its seed and
+        its Philox stream (its index among the call's rows) with it — the slot's table entry, stream id and draw counter are
+        rewritten on the loop's stream and the captured step is kept."""
         if not prompts:
             return []
         n = int(n)
         if n < 1:
             raise ValueError(f"n={n} (at least 1)")
+        row_sampling = self.row_sampling_config(sampling_params, len(prompts), n, do_sample, kwargs)
         share_prefix = bool(share_prefix) or n > 1
         if share_prefix and (self._fake or self.policy_name != "longest_prefix"):
             raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip', policy='longest_prefix')")
@@ -959,6 +1030,7 @@ class SpeculativePipeline:
             raise ValueError("generate_many drafts with the draft model: pass draft_lm / draft_model")
         processors = self._processors_for_step(kwargs, self.policy_name == "longest_prefix" and not self._fake,
                                                f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
+        processors = self._row_processors(row_sampling, processors)
         ids = [self._encode(p) for p in prompts]
         grammar = self._grammar_for_step(grammar, len(ids), self.policy_name == "longest_prefix" and not self._fake,
                                          f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
@@ -967,6 +1039,8 @@ class SpeculativePipeline:
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
+        if row_sampling is not None:      # the session's rows: the first prompts' entries, each with its own index as stream id
+            sampling = {**row_sampling, "rows": [row_sampling["rows"][i] for i in first], "ids": list(first)}
         sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens,
                              share_prefix=share_prefix, processors=processors,
                              grammar=None if grammar is None else {"fsm": grammar["fsm"], "starts": [grammar["starts"][i] for i in first]})
@@ -982,7 +1056,8 @@ class SpeculativePipeline:
                     owner[b] = None
                     if waiting:
                         nxt = waiting.pop(0)
-                        sess.admit(b, ids[nxt], -1 if grammar is None else grammar["starts"][nxt])
+                        sess.admit(b, ids[nxt], -1 if grammar is None else grammar["starts"][nxt],
+                                   params=None if row_sampling is None else row_sampling["rows"][nxt], index=nxt)
                         owner[b] = nxt
             if not sess.any_active() and not waiting and all(o is None for o in owner):
                 break
@@ -1111,6 +1186,14 @@ class DecodeSession:
             raise NotImplementedError("share_prefix needs the HIP engines (implementation='hip')")
         self.self_draft = self_draft
         self.sampling = sampling
+        # per-request parameters (SpeculativePipeline.row_sampling_config; None: the run's scalars): the host's view of the
+        # table the step's kernels read, and every row's Philox stream id — its request's index, not its slot
+        self.row_params = list(sampling["rows"]) if sampling is not None and sampling.get("rows") is not None else None
+        self.row_ids: List[int] = list(sampling["ids"]) if self.row_params is not None else list(range(len(prompts)))
+        if self.row_params is not None and (len(self.row_params) != len(prompts) or len(self.row_ids) != len(prompts)):
+            raise ValueError(f"sampling: {len(self.row_params)} rows / {len(self.row_ids)} ids for {len(prompts)} prompts")
+        if self.row_params is not None and (self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))):
+            raise NotImplementedError("sampling_params need the HIP step with a draft model and a fixed K")
         # speculative sampling (policy="rejection", backend="device"): the step's third mode instead of the sampled bonus token
         self._spec = bool(sampling and sampling.get("spec"))
         self.step_limit = step_limit
@@ -1213,6 +1296,9 @@ class DecodeSession:
         """Loops are cached per (batch, K): (re)configure the one in use for this run."""
         sp = self.sampling
         spec = self._spec
+        if self.loop.row_table is not None and self.row_params is None:   # a cached loop another run left a table on
+            self.loop.sync()
+            self.loop.set_row_sampling(None)
         if self.loop.spec_sampling and not spec:
             self.loop.sync()
             self.loop.set_spec_sampling(False)
@@ -1225,11 +1311,13 @@ class DecodeSession:
         if spec:
             if self.per_row or self.self_draft:
                 raise NotImplementedError("speculative sampling needs a draft model and a fixed K")
-            self.loop.set_spec_sampling(True, sp["temperature"], sp["seed"], stream_ids=list(range(len(self.rows))),
+            self.loop.set_spec_sampling(True, sp["temperature"], sp["seed"], stream_ids=list(self.row_ids),
                                         draw_counts=[r.draws for r in self.rows], top_k=sp["top_k"], top_p=sp["top_p"])
-            return
-        self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
-                               stream_ids=list(range(len(self.rows))), draw_counts=[r.draws for r in self.rows])
+        else:
+            self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
+                                   stream_ids=list(self.row_ids), draw_counts=[r.draws for r in self.rows])
+        if self.row_params is not None:   # the mode's launches read table[b]; the scalars above are not in them
+            self.loop.set_row_sampling(self.row_params)
 
     def _apply_processors(self) -> None:
         """Loops are cached per (batch, K): switch the one in use to this run's processors (or off), fill the bias rows and every
@@ -1271,11 +1359,14 @@ class DecodeSession:
         from specdec_hip.ops import sample_token_hip
 
         sp, loop = self.sampling, self.loop
+        if self.row_params is not None:    # the row's own parameters, as the step's kernels normalise them
+            sp = self.row_params[b].scalars(vocab=self.pipe.base_lm.vocab_size)
+        sid = self.row_ids[b]
 
         def resample(pos: int) -> int:
             with torch.cuda.stream(loop.stream_t):
                 tok = sample_token_hip(loop.step_logits[b, pos], sp["temperature"], sp["top_k"], sp["top_p"], seed=sp["seed"],
-                                       draw=row.draws, stream_ids=torch.tensor([b], dtype=torch.int32, device="cuda"))
+                                       draw=row.draws, stream_ids=torch.tensor([sid], dtype=torch.int32, device="cuda"))
                 return int(tok.item())
         return resample
 
@@ -1478,10 +1569,13 @@ class DecodeSession:
         stats["steps"] = max(r.steps for r in rows)
         return True
 
-    def admit(self, b: int, prompt: List[int], grammar_start: int = -1) -> None:
+    def admit(self, b: int, prompt: List[int], grammar_start: int = -1, params=None, index: Optional[int] = None) -> None:
         """Continuous batching: put a new sequence into the slot of a finished row. Its caches are prefilled
         and its device state set at the next launch point; the other rows keep stepping meanwhile. grammar_start: the new
-        row's start state in the session's automaton (-1: unconstrained)."""
+        row's start state in the session's automaton (-1: unconstrained). params / index (a session with per-request
+        parameters): the new request's SamplingParams (seed resolved) and its Philox stream id; the slot's table entry, stream
+        id and draw counter are rewritten on the loop's stream, behind the steps in flight (which are void for the slot), and
+        the captured step is kept."""
         if self.rows[b].active:
             raise ValueError(f"row {b} is still decoding")
         if not prompt:
@@ -1490,6 +1584,11 @@ class DecodeSession:
             raise ValueError(f"prompt of {len(prompt)} tokens does not fit this session (l_max {self.rt['l_max']}, positions {self.pos_limit})")
         if grammar_start >= 0 and self.grammar is None:
             raise ValueError("admit: the session was started without a grammar")
+        if (params is not None) != (self.row_params is not None):
+            raise ValueError("admit: the session was started without sampling_params" if params is not None else
+                             "admit: the session decodes with per-request sampling parameters; pass the new request's")
+        if params is not None and params.has_penalties and self.processors is None:
+            raise ValueError("admit: the request has penalties but the session's logit-processor stage is off")
         self.rows[b] = _Row(list(prompt))
         self.grammar_starts[b] = int(grammar_start)
         self._fresh.add(b)
@@ -1500,7 +1599,11 @@ class DecodeSession:
         self._flagged[b] = "resync"
         for _, vs in self._queue:
             vs.add(b)
-        if self.sampling is not None:
+        if params is not None:
+            self.row_params[b] = params = params.with_seed(self.sampling["seed"])
+            self.row_ids[b] = b if index is None else int(index)
+            self.loop.set_row_params(b, params, stream_id=self.row_ids[b], draw_count=0)
+        elif self.sampling is not None:
             self._resample_state = True   # draw counters restart for the new row at the next launch point
 
     def finish(self) -> None:

@@ -65,12 +65,30 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--regex", type=str, metavar="PATTERN",
                     help="constrain the output to full matches of this regular expression over the tokens' bytes: a token automaton "
                          "masks draft and target logits inside the captured step (literals, classes, groups, |, * + ? {m,n})")
+    ap.add_argument("--sampling-params", type=str, metavar="FILE",
+                    help="JSON list with one object per prompt (temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, "
+                         "frequency_penalty): per-request parameters read row by row inside the captured step; temperature 0 is a "
+                         "greedy request; with --n every completion shares its prompt's entry; decodes through generate_batch "
+                         "(sampled bonus token, or speculative sampling with --spec-sampling)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
                     help="add the draft's agreement with the target on prompt + generated tokens (acceptance probability at "
                          "--temperature, KL, greedy agreement, expected tokens per step for K = 1..8; reduced on the device)")
     return ap.parse_args(argv)
+
+
+def cli_sampling_params(args: argparse.Namespace):
+    """The entries of --sampling-params (None without it); ValueError where another option carries the same parameter or
+    selects a mode the entries are not read in."""
+    from specdec_hip.sampling_params import load_for_cli
+
+    return load_for_cli(args.sampling_params, 1, {
+        "--repetition-penalty": args.repetition_penalty, "--presence-penalty": args.presence_penalty,
+        "--frequency-penalty": args.frequency_penalty, "--spec-top-k": args.spec_top_k, "--spec-top-p": args.spec_top_p,
+        "--adaptive-K": args.adaptive_K, "--controller adaptive": args.controller == "adaptive", "--per-row-K": args.per_row_K,
+        "--draft-mode " + args.draft_mode: args.draft_mode != "vanilla",
+        "--policy " + args.policy: args.policy != "longest_prefix"})
 
 
 def generated_perplexity(lm, tokens):
@@ -102,6 +120,11 @@ def main(argv=None) -> int:
     if any(a == "--K" or a.startswith("--K=") for a in raw) and args.adaptive_K:
         logging.error("Cannot specify both --K and --adaptive-K")
         return 1
+    try:
+        row_params = cli_sampling_params(args)
+    except (OSError, ValueError, TypeError) as e:
+        logging.error("Error: %s", e)
+        return 1
     if args.adaptive_K or args.controller == "adaptive":
         controller, cp = "adaptive", {k: v for k, v in (("min_k", args.min_k), ("max_k", args.max_k),
                                                        ("target_acceptance_rate", args.target_acceptance)) if v is not None}
@@ -132,11 +155,13 @@ def main(argv=None) -> int:
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
-        batch = args.spec_sampling or args.share_prefix or args.n != 1
+        batch = args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:
             proc["grammar"] = pipe.grammar_from_regex(args.regex)
+        if row_params is not None:
+            proc["sampling_params"] = row_params
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
             rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],

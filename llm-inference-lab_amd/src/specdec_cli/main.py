@@ -41,7 +41,20 @@ def cmd_bench(args: argparse.Namespace) -> int:
     return 0
 
 
+def cli_sampling_params(args: argparse.Namespace):
+    """The entries of `run --sampling-params` (None without it); ValueError where another option carries the same parameter."""
+    from specdec_hip.sampling_params import load_for_cli
+
+    return load_for_cli(args.sampling_params, 1, {
+        "--do-sample": args.do_sample, "--repetition-penalty": args.repetition_penalty, "--presence-penalty": args.presence_penalty,
+        "--frequency-penalty": args.frequency_penalty, "--spec-top-k": args.spec_top_k, "--spec-top-p": args.spec_top_p})
+
+
 def cmd_run(args: argparse.Namespace) -> int:
+    try:
+        row_params = cli_sampling_params(args)
+    except (OSError, ValueError, TypeError) as e:
+        raise SystemExit(f"--sampling-params: {e}")
     spec = getattr(args, "spec_sampling", False)
     extra = {"policy": "rejection", "policy_params": {"backend": "device", "temperature": args.temperature, "seed": args.seed}} if spec else {}
     shape = {k: v for k, v in (("top_k", args.spec_top_k), ("top_p", args.spec_top_p)) if v is not None}
@@ -56,7 +69,9 @@ def cmd_run(args: argparse.Namespace) -> int:
                               ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
     if args.regex is not None:
         proc["grammar"] = pipe.grammar_from_regex(args.regex)
-    if spec or args.share_prefix or args.n != 1:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    if row_params is not None:
+        proc["sampling_params"] = row_params
+    if spec or args.share_prefix or args.n != 1 or row_params is not None:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
@@ -103,6 +118,9 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--ban-token", type=int, action="append", metavar="ID", help="never emit this token id (repeatable)")
     pr.add_argument("--regex", type=str, metavar="PATTERN", help="constrain the output to full matches of this regular expression over the "
                                                                  "tokens' bytes (a token automaton inside the captured step)")
+    pr.add_argument("--sampling-params", type=str, metavar="FILE",
+                    help="JSON list with one object per prompt (temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, "
+                         "frequency_penalty): per-request parameters read row by row inside the captured step (generate_batch)")
     pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
                                                      "once and forked into the others (implies --share-prefix)")
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
