@@ -694,6 +694,10 @@ class HipSpecDec:
         self.grammar = None
         self.grammar_state = None      # int32 [B] on the device: -1 unconstrained, 0..S-1, 0xFFFF dead
         self._grammar_tables = {}      # id(fsm) -> (fsm, next, allow)
+        # kept for the sessions that use the loop one after another (a loop outlives them): the models' paths (persistent /
+        # launch) the captured step was recorded on, and the parameters set_adaptive was last enabled with
+        self.captured_paths = None
+        self.adaptive_params = None
         self.rec_ints = self.lib.sd_specdec_record_ints(self.handle)
         ptr = self.lib.sd_specdec_record(self.handle)
         self._record = np.ctypeslib.as_array(ptr, shape=(2, self.B, self.rec_ints))   # slot = launch index & 1

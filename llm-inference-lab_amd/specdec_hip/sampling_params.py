@@ -31,10 +31,19 @@ class RowSampling(ctypes.Structure):
 ROW_BYTES = ctypes.sizeof(RowSampling)
 
 
+def check_penalties(rp: float, pres: float, freq: float) -> None:
+    """What a repetition / presence / frequency penalty may be, for a request's own and for a call's."""
+    if not rp > 0.0:
+        raise ValueError(f"repetition_penalty={rp} (must be > 0)")
+    if not (math.isfinite(pres) and math.isfinite(freq)):
+        raise ValueError(f"presence_penalty={pres} / frequency_penalty={freq} must be finite")
+
+
 @dataclass(frozen=True)
 class SamplingParams:
     """One request's sampling parameters. temperature 0 asks for greedy decoding; top_k None / 0 = no top-k (else 1..1024);
-    top_p None / >= 1 = no nucleus cut; seed None = the call's seed; the penalties as logit_processor_config defines them."""
+    top_p None / >= 1 = no nucleus cut; seed None = the call's seed; the penalties as the call-level arguments define them
+    (src/specdec/core/step_options.py)."""
 
     temperature: float = 1.0
     top_k: Optional[int] = None
@@ -54,11 +63,7 @@ class SamplingParams:
             raise ValueError(f"top_k={self.top_k} (must be >= 0; 0 or None: no top-k)")
         if self.top_p is not None and not float(self.top_p) > 0.0:
             raise ValueError(f"top_p={self.top_p} (must be > 0)")
-        rp, pres, freq = float(self.repetition_penalty), float(self.presence_penalty), float(self.frequency_penalty)
-        if not rp > 0.0:
-            raise ValueError(f"repetition_penalty={rp} (must be > 0)")
-        if not (math.isfinite(pres) and math.isfinite(freq)):
-            raise ValueError(f"presence_penalty={pres} / frequency_penalty={freq} must be finite")
+        check_penalties(float(self.repetition_penalty), float(self.presence_penalty), float(self.frequency_penalty))
         if self.seed is not None and int(self.seed) != self.seed:
             raise ValueError(f"seed={self.seed} (an integer)")
 

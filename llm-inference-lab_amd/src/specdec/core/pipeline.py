@@ -25,9 +25,9 @@ host-policy loop and, seeded alike, makes the reference's draws (models/hip_lm.p
 from __future__ import annotations
 
 import logging
-import math
 import os
 import time
+from collections import deque
 from typing import Any, Dict, List, Optional, Sequence, Union
 
 import psutil
@@ -37,10 +37,11 @@ import yaml
 from specdec_hip.engine import EngineGaveUp, HipModel, HipSpecDec
 
 from ..models.hip_lm import HipLM, create_hip_lm, create_hip_pair, is_named_pair
-from ..policies.controllers import create_controller
+from ..policies.controllers import FixedKController, create_controller
 from ..policies.policies import create_policy
 from ..utils.deterministic import ensure_deterministic, set_deterministic_mode
 from ..utils.interfaces import LanguageModel
+from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
 PromptLike = Union[str, Sequence[int], torch.Tensor]
 
@@ -231,6 +232,8 @@ class SpeculativePipeline:
         self.scheduler = create_speculative_scheduler(device="cuda")
         self.metrics: Dict[str, Any] = {}
         self._runtimes: Dict[Any, Any] = {}
+        # kept: the ids of member automata -> (the members, their union, its starts); (pattern, eos_id) -> the compiled TokenFSM
+        self._grammar_unions, self._grammar_regexes = {}, {}
 
     # ------------------------------------------------------------------ configuration
     def _load_config(self, config_path: Optional[str]) -> Dict[str, Any]:
@@ -424,28 +427,27 @@ class SpeculativePipeline:
 
     # ------------------------------------------------------------------ the loop
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
-                      sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None,
+                      sampling: Union[None, Dict[str, Any], StepOptions] = None, step_limit: Optional[int] = None,
                       self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
                       **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
-        (DecodeSession). processors: repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids,
-        allowed_token_ids (logit_processor_config); identity values leave the mode off. grammar: a TokenFSM, or a list with one
-        entry per prompt (None: that row is unconstrained) — grammar_config. sampling_params: one SamplingParams per prompt
-        (row_sampling_config; in place of `sampling` and of penalty arguments)."""
-        if sampling_params is not None:
-            if sampling is not None:
-                raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
-            sampling = self.row_sampling_config(sampling_params, len(prompts), 1, None, processors, heads=self_draft)
-        return DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix,
-                             self._row_processors(sampling, self.logit_processor_config(processors)), self.grammar_config(grammar, len(prompts)))
+        (DecodeSession). sampling: None (greedy), {"temperature", "top_k", "top_p", "seed"} or a StepOptions. processors:
+        repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids, allowed_token_ids; identity values
+        leave the stage off. grammar: a TokenFSM, or a list with one entry per prompt (None: that row is unconstrained).
+        sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated."""
+        if sampling_params is not None and sampling is not None:
+            raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
+        options = (StepOptions.from_sampling(sampling) if sampling_params is None else
+                   row_options(self, sampling_params, len(prompts), 1, None, processors, self_draft))
+        options = with_stage(self, options, processors, grammar, len(prompts))
+        return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
-                sampling: Optional[Dict[str, Any]] = None, self_draft: bool = False, share_prefix: bool = False,
-                processors: Optional[Dict[str, Any]] = None, grammar: Optional[Dict[str, Any]] = None):
+                options: Optional[StepOptions] = None, self_draft: bool = False, share_prefix: bool = False):
         t_start = time.time()
-        sess = DecodeSession(self, prompts, max_tokens, emit_mode, sampling, step_limit, self_draft, share_prefix, processors, grammar)
+        sess = DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -620,124 +622,6 @@ class SpeculativePipeline:
         return rows, stats
 
     # ------------------------------------------------------------------ public API
-    def _sampling_config(self, do_sample: bool, temperature: float, kwargs: Dict[str, Any]) -> Optional[Dict[str, Any]]:
-        """Sampler parameters of a do_sample=True run (kwargs over config, pipeline.py:3148-3153)."""
-        if not do_sample:
-            return None
-        top_p = kwargs.get("top_p", self.config.get("top_p", None))
-        top_k = kwargs.get("top_k", self.config.get("top_k", None))
-        if top_k and min(int(top_k), self.base_lm.vocab_size) > 1024:
-            raise NotImplementedError(f"do_sample=True: top_k={top_k} > 1024 is not on the HIP path")
-        return {"temperature": float(temperature), "top_k": int(top_k) if top_k else None,
-                "top_p": None if top_p is None else float(top_p), "seed": int(kwargs.get("seed", self.config.get("seed") or 0))}
-
-    _PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "bad_token_ids", "allowed_token_ids")
-
-    def logit_processor_config(self, kwargs: Dict[str, Any]) -> Optional[Dict[str, Any]]:
-        """The logit processors of a run (call kwargs over config): repetition_penalty (> 0; over prompt + generated tokens),
-        presence_penalty / frequency_penalty (over generated tokens), logit_bias {id: value}, bad_token_ids, allowed_token_ids.
-        -> None for identity values (the mode stays off and the step is the unprocessed one), else {"rp", "presence",
-        "frequency", "bias": float32 [V] on the host or None}: logit_bias, banned and allowed ids all come down to the one
-        additive table (-inf bans). Refused: a penalty out of range, ids outside the vocabulary, an empty allowed set."""
-        unknown = set(kwargs) - set(self._PROCESSOR_KEYS)
-        if unknown:
-            raise TypeError(f"unknown logit-processor argument(s): {sorted(unknown)}")
-
-        def val(key, default):
-            v = kwargs.get(key)
-            if v is None:
-                v = self.config.get(key)
-            return default if v is None else v
-
-        rp, pres, freq = float(val("repetition_penalty", 1.0)), float(val("presence_penalty", 0.0)), float(val("frequency_penalty", 0.0))
-        if not rp > 0.0:
-            raise ValueError(f"repetition_penalty={rp} (must be > 0)")
-        if not (math.isfinite(pres) and math.isfinite(freq)):
-            raise ValueError(f"presence_penalty={pres} / frequency_penalty={freq} must be finite")
-        V = self.base_lm.vocab_size
-        lb, bad, allowed = val("logit_bias", None), val("bad_token_ids", None), val("allowed_token_ids", None)
-
-        def ids_of(name, xs):
-            out = [int(x) for x in xs]
-            for x in out:
-                if not 0 <= x < V:
-                    raise ValueError(f"{name}: id {x} is outside the vocabulary [0, {V})")
-            return out
-
-        bias = None
-        if lb or bad or allowed is not None:
-            bias = torch.zeros(V, dtype=torch.float32)
-            if allowed is not None:
-                keep = ids_of("allowed_token_ids", allowed)
-                if not keep:
-                    raise ValueError("allowed_token_ids is empty: no token could be emitted")
-                bias.fill_(float("-inf"))
-                bias[keep] = 0.0
-            for t, v in zip(ids_of("logit_bias", (lb or {}).keys()), (lb or {}).values()):
-                if math.isnan(float(v)):
-                    raise ValueError(f"logit_bias[{t}] is NaN")
-                bias[t] += float(v)
-            if bad:
-                bias[ids_of("bad_token_ids", bad)] = float("-inf")
-        if rp == 1.0 and pres == 0.0 and freq == 0.0 and bias is None:
-            return None
-        return {"rp": rp, "presence": pres, "frequency": freq, "bias": bias}
-
-    def _processors_for_step(self, kwargs: Dict[str, Any], route_ok: bool, what: str) -> Optional[Dict[str, Any]]:
-        """logit_processor_config of a call, refused where the run does not go through the captured step with a draft model and a
-        fixed K: the processors are a device stage of that step and are not approximated elsewhere."""
-        from ..policies.controllers import FixedKController
-
-        lp = self.logit_processor_config({k: kwargs[k] for k in self._PROCESSOR_KEYS if k in kwargs})
-        if lp is None:
-            return None
-        if not route_ok:
-            raise NotImplementedError(f"logit processors (penalties, logit_bias, token bans) run inside the captured device step: {what} "
-                                      "is not supported with them")
-        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None:
-            raise NotImplementedError("logit processors need the draft-model mode (draft_mode='vanilla'): medusa / eagle proposals come "
-                                      "from no logits row")
-        if not isinstance(self.controller, FixedKController):
-            raise NotImplementedError("logit processors keep a fixed K (controller='fixed'): adaptive K is not supported")
-        return lp
-
-    def grammar_config(self, grammar, n_prompts: int) -> Optional[Dict[str, Any]]:
-        """The grammar of a run: a specdec_hip.grammar.TokenFSM for every prompt, or a list with one entry per prompt (None: that
-        row is unconstrained). -> None, or {"fsm": the one table the device walks, "starts": each prompt's start state (-1:
-        unconstrained)}; different automata are merged with TokenFSM.union (one merge per combination, kept). The automaton's
-        eos_id must be the pipeline's EOS where it has one: that is the token the host's EOS rule stops a row on."""
-        if grammar is None:
-            return None
-        from specdec_hip.grammar import TokenFSM
-
-        entries = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar] * n_prompts
-        if len(entries) != n_prompts:
-            raise ValueError(f"grammar: {len(entries)} entries for {n_prompts} prompts")
-        members: List[Any] = []
-        for g in entries:
-            if g is not None and not isinstance(g, TokenFSM):
-                raise TypeError(f"grammar: expected a TokenFSM or None, got {type(g).__name__}")
-            if g is not None and not any(g is m for m in members):
-                members.append(g)
-        if not members:
-            return None
-        V, eos = self.base_lm.vocab_size, self.base_lm.get_tokenizer_info().get("eos_token_id")
-        for g in members:
-            if g.V != V:
-                raise ValueError(f"grammar: the automaton is over {g.V} tokens, the vocabulary has {V}")
-            if g.eos_id != members[0].eos_id or (eos is not None and g.eos_id != eos):
-                raise ValueError(f"grammar: the automaton ends on eos_id {g.eos_id}, the pipeline's EOS is {eos}")
-        if len(members) == 1:
-            fsm, starts = members[0], [members[0].start]
-        else:
-            cache = self.__dict__.setdefault("_grammar_unions", {})
-            key = tuple(id(m) for m in members)
-            if key not in cache:
-                cache[key] = (members,) + TokenFSM.union(members)      # (the members are held: their ids stay theirs)
-            _, fsm, starts = cache[key]
-        start_of = {id(m): st for m, st in zip(members, starts)}
-        return {"fsm": fsm, "starts": [-1 if g is None else start_of[id(g)] for g in entries]}
-
     def grammar_from_regex(self, pattern: str, eos_id: Optional[int] = None):
         """The TokenFSM of a regular expression over the target's tokenizer (specdec_hip.grammar.from_tokenizer; its limitation
         for byte-level BPE vocabularies is written there). eos_id defaults to the pipeline's EOS; a pipeline without one must
@@ -748,132 +632,28 @@ class SpeculativePipeline:
             eos_id = self.base_lm.get_tokenizer_info().get("eos_token_id")
             if eos_id is None:
                 raise ValueError("grammar_from_regex: the pipeline has no EOS token; pass eos_id")
-        cache = self.__dict__.setdefault("_grammar_regexes", {})
+        cache = self._grammar_regexes
         if (pattern, int(eos_id)) not in cache:
             cache[(pattern, int(eos_id))] = from_tokenizer(pattern, self.base_lm._tokenizer, self.base_lm.vocab_size, int(eos_id))
         return cache[(pattern, int(eos_id))]
 
-    def _grammar_for_step(self, grammar, n_prompts: int, route_ok: bool, what: str) -> Optional[Dict[str, Any]]:
-        """grammar_config of a call, refused where the run does not go through the captured step with a draft model and a fixed
-        K: the automaton is a line of that step's logit-processor stage."""
-        from ..policies.controllers import FixedKController
-
-        gr = self.grammar_config(grammar, n_prompts)
-        if gr is None:
-            return None
-        if not route_ok:
-            raise NotImplementedError(f"a grammar runs inside the captured device step: {what} is not supported with it")
-        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None:
-            raise NotImplementedError("a grammar needs the draft-model mode (draft_mode='vanilla'): medusa / eagle proposals come from no "
-                                      "logits row")
-        if not isinstance(self.controller, FixedKController):
-            raise NotImplementedError("a grammar keeps a fixed K (controller='fixed'): adaptive K is not supported")
-        return gr
-
-    def _spec_sampling_config(self, kwargs: Dict[str, Any]) -> Dict[str, Any]:
-        """policy="rejection", backend="device": the step's speculative-sampling mode, shaped by the POLICY's temperature,
-        seed, top_k and top_p (policy_params; call-level top_k / top_p stay refused: the policy shapes the mode). What the mode
-        does not do is refused, not approximated."""
-        from ..policies.controllers import FixedKController
-
-        if kwargs.get("top_k") or (kwargs.get("top_p") is not None and float(kwargs["top_p"]) < 1.0):
-            raise NotImplementedError("policy='rejection' (backend='device'): top-k / top-p shaping of the two distributions is not supported")
-        if not isinstance(self.controller, FixedKController):
-            raise NotImplementedError("policy='rejection' (backend='device') keeps a fixed K (controller='fixed'): adaptive K is not supported")
-        return {"spec": True, "temperature": float(self.policy.temperature), "top_k": self.policy.top_k,
-                "top_p": self.policy.top_p if self.policy.top_k else None, "seed": int(kwargs.get("seed", self.policy.seed))}
-
-    _ROW_SAMPLING_CLASH = ("top_k", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty")
-
-    def row_sampling_config(self, sampling_params, n_prompts: int, n: int, do_sample: Optional[bool], kwargs: Dict[str, Any],
-                            heads: bool = False) -> Optional[Dict[str, Any]]:
-        """Per-request sampling parameters of a call: one specdec_hip.sampling_params.SamplingParams per prompt, expanded
-        with `n` as a grammar list is. -> None, or the session's `sampling` description: the step's mode (the sampled bonus
-        token under policy="longest_prefix", speculative sampling under policy="rejection" with backend="device") with "rows"
-        = every row's parameters, seeds resolved (an entry without a seed takes the call's), and "ids" = every row's Philox
-        stream id, its index among the call's rows — what a request samples does not depend on the slot it decodes in.
-        Refused: call-level do_sample / top_k / top_p / penalties next to it (which of the two would rule a row?), the
-        host-loop policies, adaptive K, Medusa / EAGLE drafting, implementation="fake", and values the device would only turn
-        into a greedy row (SamplingParams.check)."""
-        if sampling_params is None:
-            return None
-        from specdec_hip.sampling_params import SamplingParams
-
-        from ..policies.controllers import FixedKController
-
-        clash = [k for k in self._ROW_SAMPLING_CLASH if kwargs.get(k) is not None] + (["do_sample"] if do_sample is not None else [])
-        if clash:
-            raise ValueError(f"sampling_params carries every request's own parameters: the call-level {sorted(clash)} cannot be given with it")
-        entries = list(sampling_params)
-        if len(entries) != n_prompts:
-            raise ValueError(f"sampling_params: {len(entries)} entries for {n_prompts} prompts")
-        for e in entries:
-            if not isinstance(e, SamplingParams):
-                raise TypeError(f"sampling_params: expected SamplingParams, got {type(e).__name__}")
-        spec = self.policy_name == "rejection" and self.rejection_backend == "device"
-        if self._fake or not (self.policy_name == "longest_prefix" or spec):
-            raise NotImplementedError("sampling_params are read by the captured device step (implementation='hip'; policy 'longest_prefix', "
-                                      f"or 'rejection' with backend='device'): policy={self.policy_name!r} on the host loop is not supported with them")
-        if self.config.get("draft_mode", "vanilla") != "vanilla" or self.draft_lm is None or self.medusa_heads is not None or heads:
-            raise NotImplementedError("sampling_params need the draft-model mode (draft_mode='vanilla'): medusa / eagle drafting is not "
-                                      "supported with them")
-        if not isinstance(self.controller, FixedKController):
-            raise NotImplementedError("sampling_params keep a fixed K (controller='fixed'): adaptive K is not supported")
-        seed = int(kwargs.get("seed", self.policy.seed if spec else (self.config.get("seed") or 0)))
-        V = self.base_lm.vocab_size
-        rows = [e.with_seed(seed) for e in entries for _ in range(int(n))]
-        for e in rows:
-            e.check(V, spec=spec)
-        base = {"spec": True, "temperature": float(self.policy.temperature)} if spec else {"temperature": 1.0}
-        return {**base, "top_k": None, "top_p": None, "seed": seed, "rows": rows, "ids": list(range(len(rows)))}
-
-    @staticmethod
-    def _row_processors(sampling: Optional[Dict[str, Any]], processors: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
-        """Requests with penalties of their own switch the logit-processor stage on (identity scalars: the table rules)."""
-        if processors is None and sampling is not None and any(e.has_penalties for e in sampling.get("rows") or ()):
-            return {"rp": 1.0, "presence": 0.0, "frequency": 0.0, "bias": None}
-        return processors
+    _spec_sampling_config = spec_options     # the `sampling` of policy="rejection" with backend="device", for start_session
 
     def generate(self, prompt: PromptLike, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  do_sample: Optional[bool] = None, **kwargs) -> Dict[str, Any]:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
-        grammar = kwargs.pop("grammar", None)
-        if kwargs.pop("sampling_params", None) is not None:
-            raise NotImplementedError("sampling_params belong to generate_batch and generate_many (one entry per prompt of a batch): "
-                                      "generate() decodes one row")
-        if kwargs.get("share_prefix") or int(kwargs.get("n", 1) or 1) != 1:
-            raise NotImplementedError("share_prefix / n belong to generate_batch and generate_many: generate() decodes one row")
-        max_tokens = max_tokens or self.config["max_new_tokens"]
-        temperature = temperature or self.config["temperature"]
-        do_sample = do_sample if do_sample is not None else self.config["do_sample"]
-        sample_t: Optional[float] = None
-        if do_sample and not self._fake:   # (the fake double ignores sampling parameters, in the reference as here)
-            # pipeline.py:1019-1027 / :1217-1224: the DRAFT's proposals, and the one base token of a zero-accept step, are drawn at the
-            # call's temperature (transformers' sampling on torch's global generator, models/hip_lm.py hf_sampling_probs);
-            # every verification path of the scheduler is greedy (speculative_scheduler.py:192-199, :304-310, :339-345)
-            if self.config.get("draft_mode", "vanilla") in ("medusa", "eagle") or self.policy_name != "longest_prefix":
-                raise NotImplementedError("generate(do_sample=True) is restated for the draft-model mode with the longest_prefix policy")
-            sample_t = float(temperature)
-        ids = self._encode(prompt)
-        # draft modes are a generate() feature in the reference (pipeline.py:1016-1041); generate_batch always
-        # drafts with the draft model
-        if self.policy_name == "rejection":
-            raise NotImplementedError("policy='rejection' is a generate_batch policy (it emits a correction / bonus token every step)")
-        processors = self._processors_for_step(
-            kwargs, self.policy_name == "longest_prefix" and not self._fake and sample_t is None,
-            "generate(do_sample=True)" if sample_t is not None else f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
-        grammar = self._grammar_for_step(
-            grammar, 1, self.policy_name == "longest_prefix" and not self._fake and sample_t is None and not self._medusa_random(),
-            "generate(do_sample=True)" if sample_t is not None else f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
-        if self.policy_name != "longest_prefix" or self._medusa_random() or self._fake or sample_t is not None:
-            rows, st = self._decode_host_policy([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
-                                                temperature=float(temperature), sample_t=sample_t,
+        call = resolve(self, [prompt], max_tokens, temperature, do_sample, kwargs, grammar=kwargs.pop("grammar", None),
+                       sampling_params=kwargs.pop("sampling_params", None), share_prefix=kwargs.get("share_prefix"), n=kwargs.get("n", 1),
+                       single=True)
+        if call.route == "host_policy":
+            rows, st = self._decode_host_policy(call.ids, call.max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * call.max_tokens,
+                                                temperature=call.temperature, sample_t=call.sample_t,
                                                 sample_kwargs={k: kwargs[k] for k in ("top_k", "top_p") if k in kwargs})
         else:
-            rows, st = self._decode([ids], max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * max_tokens,
-                                    self_draft=self.config.get("draft_mode") in ("medusa", "eagle"), processors=processors, grammar=grammar)
+            rows, st = self._decode(call.ids, call.max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * call.max_tokens,
+                                    options=call.options, self_draft=call.self_draft)
         r = rows[0]
         total_ms = (time.time() - t_begin) * 1e3
         self.metrics = {"total_proposed": r.proposed, "total_accepted": r.accepted, "total_steps": st["steps"],
@@ -915,54 +695,23 @@ class SpeculativePipeline:
         decoding under the mask, token for token.
 
         sampling_params (opt-in; not in the reference): one SamplingParams per prompt (expanded with n) — every request its own
-        temperature (0: greedy), top_k, top_p, seed and penalties, read by the step's kernels row by row (row_sampling_config).
+        temperature (0: greedy), top_k, top_p, seed and penalties, read by the step's kernels row by row (step_options).
         Under policy="longest_prefix" the step samples the bonus token; under policy="rejection" with backend="device" it is
         speculative sampling. A request's Philox stream is its index among the call's rows."""
         if not prompts:
             return []
-        n = int(n)
-        if n < 1:
-            raise ValueError(f"n={n} (at least 1)")
-        row_sampling = self.row_sampling_config(sampling_params, len(prompts), n, do_sample, kwargs, heads=self.medusa_heads is not None)
-        share_prefix = bool(share_prefix) or n > 1
-        if share_prefix and (self._fake or (self.policy_name != "longest_prefix"
-                                            and not (self.policy_name == "rejection" and self.rejection_backend == "device"))):
-            raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip'; policy 'longest_prefix', "
-                                      "or 'rejection' with backend='device')")
-        if self._fake:
-            # the double has no tokenizer to pad a batch with: the reference falls back to generate() per prompt
-            # ("No tokenizer access, falling back to sequential processing", pipeline.py:1680-1700)
-            if grammar is not None:
-                raise NotImplementedError("a grammar runs inside the captured device step: implementation='fake' is not supported with it")
+        call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
+                       sampling_params=sampling_params)
+        if call.route == "fake":
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
-        max_tokens = max_tokens or self.config["max_new_tokens"]
-        temperature = temperature or self.config["temperature"]
-        do_sample = do_sample if do_sample is not None else self.config["do_sample"]
-        sampling = row_sampling if row_sampling is not None else self._sampling_config(do_sample, temperature, kwargs)
-        heads = self.medusa_heads is not None    # persistent heads also serve generate_batch (opt-in, not in the reference)
-        if self.draft_lm is None and not heads:
-            raise ValueError("generate_batch drafts with the draft model (the reference ignores draft_mode there): pass draft_lm / draft_model")
-        if n > 1:
-            if isinstance(grammar, (list, tuple)):
-                grammar = [g for g in grammar for _ in range(n)]
-            prompts = [p for p in prompts for _ in range(n)]
-        ids = [self._encode(p) for p in prompts]
-        device_step = self.policy_name == "longest_prefix" or (self.policy_name == "rejection" and self.rejection_backend == "device")
-        processors = self._row_processors(row_sampling, self._processors_for_step(kwargs, device_step, f"policy={self.policy_name!r} on the host loop"))
-        grammar = self._grammar_for_step(grammar, len(ids), device_step and not heads, f"policy={self.policy_name!r} on the host loop")
-        if self.policy_name == "rejection" and self.rejection_backend == "device":
-            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens,
-                                    sampling=row_sampling if row_sampling is not None else self._spec_sampling_config(kwargs),
-                                    share_prefix=share_prefix, processors=processors, grammar=grammar)
-        elif self.policy_name == "rejection":
-            rows, st = self._decode_rejection(ids, max_tokens, step_limit=max_tokens)   # sampling IS the policy
-        elif self.policy_name != "longest_prefix":
-            if sampling is not None:
-                raise NotImplementedError(f"policy={self.policy_name!r} with do_sample=True is not on the HIP path")
-            rows, st = self._decode_host_policy(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
+        prompts, max_tokens = call.prompts, call.max_tokens
+        if call.route == "host_rejection":
+            rows, st = self._decode_rejection(call.ids, max_tokens, step_limit=max_tokens)
+        elif call.route == "host_policy":
+            rows, st = self._decode_host_policy(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
-            rows, st = self._decode(ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, sampling=sampling, self_draft=heads,
-                                    share_prefix=share_prefix, processors=processors, grammar=grammar)
+            rows, st = self._decode(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, options=call.options,
+                                    self_draft=call.self_draft, share_prefix=call.share_prefix)
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -1011,39 +760,16 @@ class SpeculativePipeline:
         rewritten on the loop's stream and the captured step is kept."""
         if not prompts:
             return []
-        n = int(n)
-        if n < 1:
-            raise ValueError(f"n={n} (at least 1)")
-        row_sampling = self.row_sampling_config(sampling_params, len(prompts), n, do_sample, kwargs)
-        share_prefix = bool(share_prefix) or n > 1
-        if share_prefix and (self._fake or self.policy_name != "longest_prefix"):
-            raise NotImplementedError("share_prefix / n need the captured device step (implementation='hip', policy='longest_prefix')")
-        if n > 1:
-            if isinstance(grammar, (list, tuple)):
-                grammar = [g for g in grammar for _ in range(n)]
-            prompts = [p for p in prompts for _ in range(n)]
-        max_tokens = max_tokens or self.config["max_new_tokens"]
-        temperature = temperature or self.config["temperature"]
-        do_sample = do_sample if do_sample is not None else self.config["do_sample"]
-        sampling = self._sampling_config(do_sample, temperature, kwargs)
-        if self.draft_lm is None:
-            raise ValueError("generate_many drafts with the draft model: pass draft_lm / draft_model")
-        processors = self._processors_for_step(kwargs, self.policy_name == "longest_prefix" and not self._fake,
-                                               f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
-        processors = self._row_processors(row_sampling, processors)
-        ids = [self._encode(p) for p in prompts]
-        grammar = self._grammar_for_step(grammar, len(ids), self.policy_name == "longest_prefix" and not self._fake,
-                                         f"policy={self.policy_name!r} / implementation={self.config['implementation']!r}")
+        call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
+                       sampling_params=sampling_params, policy_routes=False)
+        prompts, ids, max_tokens, options = call.prompts, call.ids, call.max_tokens, call.options
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
-        if row_sampling is not None:      # the session's rows: the first prompts' entries, each with its own index as stream id
-            sampling = {**row_sampling, "rows": [row_sampling["rows"][i] for i in first], "ids": list(first)}
-        sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, sampling, max_tokens,
-                             share_prefix=share_prefix, processors=processors,
-                             grammar=None if grammar is None else {"fsm": grammar["fsm"], "starts": [grammar["starts"][i] for i in first]})
+        sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, options.rows(first), max_tokens,
+                             share_prefix=call.share_prefix)
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -1056,8 +782,8 @@ class SpeculativePipeline:
                     owner[b] = None
                     if waiting:
                         nxt = waiting.pop(0)
-                        sess.admit(b, ids[nxt], -1 if grammar is None else grammar["starts"][nxt],
-                                   params=None if row_sampling is None else row_sampling["rows"][nxt], index=nxt)
+                        sess.admit(b, ids[nxt], -1 if options.fsm is None else options.grammar_starts[nxt],
+                                   params=None if options.row_params is None else options.row_params[nxt], index=nxt)
                         owner[b] = nxt
             if not sess.any_active() and not waiting and all(o is None for o in owner):
                 break
@@ -1168,37 +894,29 @@ class DecodeSession:
     prefilled (SpeculativePipeline._absorb_row); stats counts prefilled_rows / forked_rows / shared_positions."""
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
-                 sampling: Optional[Dict[str, Any]] = None, step_limit: Optional[int] = None, self_draft: bool = False,
-                 share_prefix: bool = False, processors: Optional[Dict[str, Any]] = None, grammar: Optional[Dict[str, Any]] = None):
+                 options: Optional[StepOptions] = None, step_limit: Optional[int] = None, self_draft: bool = False, share_prefix: bool = False):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
-        # grammar (SpeculativePipeline.grammar_config; None: off): a token automaton as one more line of the processor stage, with
-        # a state per cache row that is (re)written wherever the row's counts are. It needs the stage: identity penalties will do
-        self.grammar = grammar["fsm"] if grammar is not None else None
-        self.grammar_starts: List[int] = list(grammar["starts"]) if grammar is not None else [-1] * len(prompts)
-        if grammar is not None and processors is None:
-            processors = {"rp": 1.0, "presence": 0.0, "frequency": 0.0, "bias": None}
-        # logit processors (SpeculativePipeline.logit_processor_config; None: off): a device stage of the step, with a counts row
-        # per cache row that is (re)written wherever the row's device state is
-        self.processors = processors
-        if processors is not None and (self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))):
+        self.options = o = options if options is not None else StepOptions()      # what the step does: greedy, sampled bonus token, spec
+        other_step = self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))     # no draft model, or no fixed K
+        if o.processors is not None and other_step:
             raise NotImplementedError("logit processors and grammars need the HIP step with a draft model and a fixed K")
         if share_prefix and pipe._fake:
             raise NotImplementedError("share_prefix needs the HIP engines (implementation='hip')")
-        self.self_draft = self_draft
-        self.sampling = sampling
-        # per-request parameters (SpeculativePipeline.row_sampling_config; None: the run's scalars): the host's view of the
-        # table the step's kernels read, and every row's Philox stream id — its request's index, not its slot
-        self.row_params = list(sampling["rows"]) if sampling is not None and sampling.get("rows") is not None else None
-        self.row_ids: List[int] = list(sampling["ids"]) if self.row_params is not None else list(range(len(prompts)))
-        if self.row_params is not None and (len(self.row_params) != len(prompts) or len(self.row_ids) != len(prompts)):
-            raise ValueError(f"sampling: {len(self.row_params)} rows / {len(self.row_ids)} ids for {len(prompts)} prompts")
-        if self.row_params is not None and (self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))):
+        if o.row_params is not None and (len(o.row_params) != len(prompts) or len(o.row_ids) != len(prompts)):
+            raise ValueError(f"sampling: {len(o.row_params)} rows / {len(o.row_ids)} ids for {len(prompts)} prompts")
+        if o.row_params is not None and other_step:
             raise NotImplementedError("sampling_params need the HIP step with a draft model and a fixed K")
-        # speculative sampling (policy="rejection", backend="device"): the step's third mode instead of the sampled bonus token
-        self._spec = bool(sampling and sampling.get("spec"))
-        self.step_limit = step_limit
-        if sampling is not None and emit_mode != HipSpecDec.EMIT_BONUS:
+        if o.mode != "greedy" and emit_mode != HipSpecDec.EMIT_BONUS:
             raise ValueError("sampling is a generate_batch (bonus-token) feature")
+        self._sampled, self._spec = o.mode != "greedy", o.mode == "spec"
+        # the processor stage (None: off) has a counts row, and the grammar (None: off) a state, per cache row: both are (re)written wherever
+        # the row's device state is. What admit() rewrites — start states, per-request parameters, stream ids — is the session's own
+        self.grammar, self.processors, self.self_draft = o.fsm, o.processors, self_draft
+        self.grammar_starts: List[int] = list(o.grammar_starts) if o.fsm is not None else [-1] * len(prompts)
+        self.row_params = list(o.row_params) if o.row_params is not None else None
+        self.row_ids: List[int] = list(o.row_ids) if o.row_ids is not None else list(range(len(prompts)))
+        self._resample_state = False            # admit() without per-request parameters: draw counters restart at the next launch point
+        self.step_limit = step_limit
         self.rows = [_Row(list(p)) for p in prompts]
         for r in self.rows:
             if not r.seq:
@@ -1238,32 +956,27 @@ class DecodeSession:
             pipe._set_row(self.loop, b, r)
         if self.per_row:
             params = (ctl.initial_k, ctl.min_k, ctl.max_k, ctl.step_size, ctl.target_acceptance_rate)
-            if getattr(self.loop, "_adaptive_params", None) != params:
+            if self.loop.adaptive_params != params:
                 self.loop.set_adaptive(True, ctl.initial_k, ctl.min_k, ctl.max_k, ctl.step_size, ctl.target_acceptance_rate)
-                self.loop._adaptive_params = params       # (enabling restarts every row; drops the captured step once)
+                self.loop.adaptive_params = params       # (enabling restarts every row; drops the captured step once)
             else:
                 for b in range(len(self.rows)):
                     self.loop.set_adaptive_row(b, ctl.initial_k)
-        self._apply_sampling()
-        self._apply_processors()
+        self._configure_loop()
         self._stateful_draft = self_draft and (pipe.medusa_heads is not None or pipe._eagle())
         if self_draft and pipe._eagle():
             self.loop.reset_eagle()   # the reference keeps the state on the pipeline object, across generate() calls even; here a run starts clean
         self.step = 0
-        from ..policies.controllers import FixedKController
-
         # (persistent Medusa heads / EAGLE-lite: a void step would replace the next proposals with ones derived from stale
         # state — harmless for the tokens, but the counters would no longer be those of the in-order loop)
         # (speculative sampling advances a row's draw counter on the device by K + 1 per step, void steps included: the host's
         # in-order counters are written back whenever a row is repaired, so its steps can be queued ahead like greedy ones)
-        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and (sampling is None or self._spec)
+        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and (not self._sampled or self._spec)
                        and not self._stateful_draft
                        and os.environ.get("SPECDEC_EARLY_LAUNCH", "1") != "0")
         self._depth = 2 if self._early else 1
         if os.environ.get("SPECDEC_LAUNCH_DEPTH"):
             self._depth = max(1, min(2, int(os.environ["SPECDEC_LAUNCH_DEPTH"])))
-        from collections import deque
-
         self._queue = deque()                # launched, not yet consumed: (launch index, set of rows it is void for)
         self._flagged: Dict[int, str] = {}   # rows whose device state must be repaired before the next launch
         # The persistent draft forward serves rows of up to 1280 positions (one CU walks a head's whole cache); a session whose
@@ -1292,47 +1005,46 @@ class DecodeSession:
         m.get_k(1, {"step": 1, "generated_tokens": 0, "acceptance_rate": 0.0})
         return m
 
-    def _apply_sampling(self) -> None:
-        """Loops are cached per (batch, K): (re)configure the one in use for this run."""
-        sp = self.sampling
-        spec = self._spec
-        if self.loop.row_table is not None and self.row_params is None:   # a cached loop another run left a table on
-            self.loop.sync()
-            self.loop.set_row_sampling(None)
-        if self.loop.spec_sampling and not spec:
-            self.loop.sync()
-            self.loop.set_spec_sampling(False)
-        if self.loop.sampling and (sp is None or spec):
-            self.loop.sync()
-            self.loop.set_sampling(False)
-        if sp is None:
-            return
-        self.loop.sync()
-        if spec:
-            if self.per_row or self.self_draft:
-                raise NotImplementedError("speculative sampling needs a draft model and a fixed K")
-            self.loop.set_spec_sampling(True, sp["temperature"], sp["seed"], stream_ids=list(self.row_ids),
-                                        draw_counts=[r.draws for r in self.rows], top_k=sp["top_k"], top_p=sp["top_p"])
-        else:
-            self.loop.set_sampling(True, sp["temperature"], sp["top_k"], sp["top_p"], sp["seed"],
-                                   stream_ids=list(self.row_ids), draw_counts=[r.draws for r in self.rows])
-        if self.row_params is not None:   # the mode's launches read table[b]; the scalars above are not in them
-            self.loop.set_row_sampling(self.row_params)
+    def _configure_sampling(self) -> None:
+        """Loops are cached per (batch, K) and outlive sessions: switch the one in use off what another run left on it and to this
+        run's sampling mode, with every row's stream id and draw count. Every set_* call drops the captured step."""
+        o, loop, spec = self.options, self.loop, self._spec
+        if loop.row_table is not None and self.row_params is None:   # a cached loop another run left a table on
+            loop.sync()
+            loop.set_row_sampling(None)
+        if loop.spec_sampling and not spec:
+            loop.sync()
+            loop.set_spec_sampling(False)
+        if loop.sampling and (not self._sampled or spec):
+            loop.sync()
+            loop.set_sampling(False)
+        if self._sampled:
+            loop.sync()
+            if spec:
+                if self.per_row or self.self_draft:
+                    raise NotImplementedError("speculative sampling needs a draft model and a fixed K")
+                loop.set_spec_sampling(True, o.temperature, o.seed, stream_ids=list(self.row_ids),
+                                       draw_counts=[r.draws for r in self.rows], top_k=o.top_k, top_p=o.top_p)
+            else:
+                loop.set_sampling(True, o.temperature, o.top_k, o.top_p, o.seed,
+                                  stream_ids=list(self.row_ids), draw_counts=[r.draws for r in self.rows])
+            if self.row_params is not None:   # the mode's launches read table[b]; the scalars above are not in them
+                loop.set_row_sampling(self.row_params)
 
-    def _apply_processors(self) -> None:
-        """Loops are cached per (batch, K): switch the one in use to this run's processors (or off), fill the bias rows and every
-        row's counts — each row's own, from its own prompt, forked rows included."""
+    def _configure_loop(self) -> None:
+        """_configure_sampling, then the processor stage: on or off, its bias rows, every row's counts (forked rows' own too), the grammar."""
+        self._configure_sampling()
         lp, loop = self.processors, self.loop
-        if lp is None:
-            if loop.logit_processors:
-                loop.sync()
-                loop.set_logit_processors(False)
+        if lp is None and not loop.logit_processors:
             return
         loop.sync()
-        loop.set_logit_processors(True, lp["rp"], lp["presence"], lp["frequency"], bias=lp["bias"] is not None)
-        if lp["bias"] is not None:
+        if lp is None:
+            loop.set_logit_processors(False)
+            return
+        loop.set_logit_processors(True, lp.rp, lp.presence, lp.frequency, bias=lp.bias is not None)
+        if lp.bias is not None:
             with torch.cuda.stream(loop.stream_t):
-                loop.logit_bias.copy_(lp["bias"].to(loop.device).unsqueeze(0).expand_as(loop.logit_bias))
+                loop.logit_bias.copy_(lp.bias.to(loop.device).unsqueeze(0).expand_as(loop.logit_bias))
         for b in range(len(self.rows)):
             self._set_counts(b)
         if self.grammar is not None:
@@ -1358,7 +1070,7 @@ class DecodeSession:
         """Draw at another position of the step's logits with the row's current Philox draw."""
         from specdec_hip.ops import sample_token_hip
 
-        sp, loop = self.sampling, self.loop
+        sp, loop = vars(self.options), self.loop       # (read by key: temperature, top_k, top_p, seed)
         if self.row_params is not None:    # the row's own parameters, as the step's kernels normalise them
             sp = self.row_params[b].scalars(vocab=self.pipe.base_lm.vocab_size)
         sid = self.row_ids[b]
@@ -1414,7 +1126,7 @@ class DecodeSession:
         for e in self._engines:
             e.recover(self.loop.stream_t)
         self.loop.invalidate()
-        self.loop._captured_paths = None
+        self.loop.captured_paths = None
         for b, r in enumerate(self.rows):
             self._flagged[b] = "resync" if r.active else "freeze"
             if self._held is not None and not r.active:
@@ -1426,20 +1138,20 @@ class DecodeSession:
 
     def _launch(self) -> None:
         """Only with an empty queue are repairs possible (idle stream); callers guarantee it when rows are flagged."""
-        if self._flagged or getattr(self, "_resample_state", False):
+        if self._flagged or self._resample_state:
             assert not self._queue
             self._repair_rows()
-            if getattr(self, "_resample_state", False):
+            if self._resample_state:
                 self._resample_state = False
-                self._apply_sampling()
+                self._configure_sampling()
         if not self._queue:
             paths = self._hint()
-            was = getattr(self.loop, "_captured_paths", None)
+            was = self.loop.captured_paths
             if was is not None and was != paths:      # a model changed path (rows passed the persistent launch's context bound)
                 self.loop.drain()
                 self.loop.invalidate()
                 self.stats["path_switches"] = self.stats.get("path_switches", 0) + 1
-            self.loop._captured_paths = paths
+            self.loop.captured_paths = paths
         idx = self.loop.launches
         if self._engines[0].page_len is not None:
             # paged KV: the device advances by itself, so every row gets the pages of all the steps in flight plus this one
@@ -1454,9 +1166,9 @@ class DecodeSession:
 
     def _can_launch_ahead(self) -> bool:
         """Conservative: some row cannot finish within the steps already launched, and nothing waits for a repair."""
-        if self._flagged or getattr(self, "_resample_state", False):
+        if self._flagged or self._resample_state:
             return False
-        if self._hint() != getattr(self.loop, "_captured_paths", None):
+        if self._hint() != self.loop.captured_paths:
             return False                   # a path switch is due: the queue drains first (_launch re-captures)
         ahead = len(self._queue) + 1       # steps whose records are still to come, counting the one being considered
         per_step = self.k + 1 if self.emit_mode == HipSpecDec.EMIT_BONUS else self.k
@@ -1493,8 +1205,7 @@ class DecodeSession:
                 self.loop.join_current_stream()
                 for b, r in enumerate(rows):
                     pipe._set_row(self.loop, b, r)
-                self._apply_sampling()
-                self._apply_processors()
+                self._configure_loop()
         k, loop, rt = self.k, self.loop, self.rt
         t0 = time.time()
         if not self._queue:
@@ -1536,14 +1247,14 @@ class DecodeSession:
                 # rule appends t[pos] — a < k: pos = a, the token redrawn after the accepted prefix (the EOS itself is dropped);
                 # a == k: pos = length of the cut, which is the EOS (it stays as the last token)
                 t = [int(x) for x in rec.new_tokens[b]]
-            elif self.sampling is not None:
+            elif self._sampled:
                 t[a] = int(rec.new_tokens[b][a])       # the token the device sampled at position a
             assumed = before + t[: int(rec.n_new[b])]  # what the device advanced to
             if self.emit_mode == HipSpecDec.EMIT_BONUS:
                 constrained = self.grammar is not None and self.grammar_starts[b] >= 0
                 pipe._rules_batch(r, k, a, t, self.max_tokens, self.grammar.eos_id if constrained else self.eos,
-                                  self._resampler(b, r) if (self.sampling is not None and not self._spec) else None, dedup=not constrained)
-                if self.sampling is not None:
+                                  self._resampler(b, r) if (self._sampled and not self._spec) else None, dedup=not constrained)
+                if self._sampled:
                     r.draws += (k + 1) if self._spec else 1
             else:
                 pipe._rules_single(r, k, a, d, t, self.max_tokens,
@@ -1600,10 +1311,10 @@ class DecodeSession:
         for _, vs in self._queue:
             vs.add(b)
         if params is not None:
-            self.row_params[b] = params = params.with_seed(self.sampling["seed"])
+            self.row_params[b] = params = params.with_seed(self.options.seed)
             self.row_ids[b] = b if index is None else int(index)
             self.loop.set_row_params(b, params, stream_id=self.row_ids[b], draw_count=0)
-        elif self.sampling is not None:
+        elif self._sampled:
             self._resample_state = True   # draw counters restart for the new row at the next launch point
 
     def finish(self) -> None:
