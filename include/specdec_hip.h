@@ -301,6 +301,22 @@ int sd_w12_pack(const sd_model_config* cfg, const void* scratch, const uint32_t*
 #define SD_W12_DEFAULT_CLASSES 0x10u   /* the lm_head: the one class the 5-token probes of 3B shapes found faster (profiles/w12_verify.md) */
 int sd_model_set_w12(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes);
 
+/* W12S, the split-byte FORM of the W12 copy: same blocks, slots, overflow stream, table and sizes per wide-block count; a
+ * narrow block's 12 bytes per lane hold the 8 low bytes of its weights raw and their high bytes (sign, exponent >> 1) as
+ * 4-bit codes over a per-block base, so a block is narrow when its exponents fit an EVEN-ALIGNED 16-value window (a few
+ * per cent fewer blocks than the code form) and the kernel widens it with 12 instructions instead of ~30
+ * (csrc/gemv_device.h; measurements: profiles/w12_split.md). The *_form functions are sd_w12_measure / sd_w12_pack with the
+ * form named; the counts of one form do not describe a copy of the other. sd_w12_bytes and sd_w12_matrix serve both.
+ * sd_model_set_w12_form puts the matrices of `classes` on a copy of `form` and leaves every other matrix on what it
+ * streams: a model may hold a code-form copy for some classes and a split-byte copy for others (sd_model_set_w12 first
+ * drops every copy, then sets the code form). SD_W12S_DEFAULT_CLASSES is what the measurements kept. */
+#define SD_W12_FORM_CODES 1
+#define SD_W12_FORM_SPLIT 2
+#define SD_W12S_DEFAULT_CLASSES 0x14u   /* gate / up and the lm_head: the classes whose 5-token launch on 3B shapes is faster on W12S than on what they streamed before */
+int sd_w12_measure_form(const sd_model_config* cfg, int form, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream);
+int sd_w12_pack_form(const sd_model_config* cfg, int form, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream);
+int sd_model_set_w12_form(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes, int form);
+
 /* Tokens one pass of sd_model_forward covers: 128 or 64 when every matrix of the model has a shape the
  * multi-token kernel (gemm_skinny.hip) handles at that size, else 9 or fewer (x rows must fit the LDS). Larger B*M are tiled into passes. */
 int sd_model_pass_tokens(const sd_model* m);
@@ -521,7 +537,8 @@ int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_p
  *                                              (K = 14336 at 6..9 tokens): the body that runs, at T < 10
  * w8 = 2 in either function asks for a bf16 matrix that has a W12 copy (sd_model_set_w12): where the W12 kernels cover the
  * shape the names end in ",w12>" for a fixed instance (W12 twins exist at token bound 5; a fixed class at another token
- * count runs the generic W12 kernel) and carry DT = w12 for the generic kernel; SPECDEC_NO_W12 turns both back to bf16.
+ * count runs the generic W12 kernel) and carry DT = w12 for the generic kernel; SPECDEC_NO_W12 turns both back to bf16. w8 = 3 asks the same for a copy in the
+ * split-byte form (sd_model_set_w12_form): ",w12s>" and DT = w12s.
  * Follows SPECDEC_GEMV_GENERIC at every call. Refused as sd_gemv_variant refuses, and where launch_gemv would refuse the
  * launch (fp8 storage whose K slices are not whole 64-k steps; rows that fit neither kernel). Host-only, additive
  * (SD_ABI_VERSION stays 1). */

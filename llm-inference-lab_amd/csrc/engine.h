@@ -40,9 +40,10 @@ struct sd_model {
   int is_packed() const { return packed.empty() ? 0 : 1; }
   int w8() const { return scales.empty() ? 0 : 1; }
   const float* scale(int index) const { return scales.empty() ? nullptr : scales[index]; }
-  // W12 copies (sd_model_set_w12; csrc/pack.hip), per matrix or empty; main == nullptr: the matrix keeps its bf16 stream.
+  // W12 copies (sd_model_set_w12 / sd_model_set_w12_form; csrc/pack.hip), per matrix or empty; main == nullptr: the matrix keeps
+  // its bf16 stream. `form` (W12Form) is recorded per matrix: the classes of one model may stream different forms.
   // Read by launches of <= 9 tokens only (launch_gemv); the persistent forward, prefill and > 9 tokens read `packed`.
-  struct W12Mat { const void* main; const uint32_t* table; const void* ovf; };
+  struct W12Mat { const void* main; const uint32_t* table; const void* ovf; int form; };
   std::vector<W12Mat> w12;
   // persistent forward (csrc/persist.hip): passes of <= persist_t tokens run as ONE launch
   int persist_t = 0;                       // 0 = not available for this model / device

@@ -66,6 +66,7 @@ GemvArgs matrix_args(const sd_model* m, int index) {
     a.w12_main = m->w12[index].main;
     a.w12_table = m->w12[index].table;
     a.w12_ovf = m->w12[index].ovf;
+    a.w12_form = m->w12[index].form;
   }
   a.bias = wt.bias;
   a.N = sh.N;
@@ -578,25 +579,37 @@ extern "C" int sd_model_destroy(sd_model* m) {
   return 0;
 }
 
-extern "C" int sd_model_set_w12(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes) {
-  clear_error();
-  SD_REQUIRE(m, "model_set_w12: NULL model");
-  m->w12.clear();
-  if (!w12) return 0;   // back to the bf16 streams
-  SD_REQUIRE(n_wide, "model_set_w12: NULL counts");
+// the matrices of `classes` onto a copy of `form`; the other matrices keep what they stream
+static int model_add_w12(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes, int form) {
+  SD_REQUIRE(w12 && n_wide, "model_set_w12: NULL buffer or counts");
+  SD_REQUIRE(form == W12_CODES || form == W12_SPLIT, "model_set_w12: form %d (SD_W12_FORM_CODES or SD_W12_FORM_SPLIT)", form);
   SD_REQUIRE(m->is_packed() && !m->w8() && m->cfg.weight_dtype == SD_BF16, "model_set_w12: W12 is a copy of packed bf16 weights");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(w12) & 255) == 0, "model_set_w12: the buffer must be 256-byte aligned");
   const sd_model_config& c = m->cfg;
-  m->w12.assign(4 * c.n_layers + 1, sd_model::W12Mat{nullptr, nullptr, nullptr});
+  if (m->w12.empty()) m->w12.assign(4 * c.n_layers + 1, sd_model::W12Mat{nullptr, nullptr, nullptr, W12_NONE});
   for (int i = 0; i <= 4 * c.n_layers; ++i) {
     const int which = matrix_which(c, i);
     const MatShape sh = matrix_shape(c, which);
     if (!w12_taken(sh.n_pairs, sh.K, n_wide[i]) || !((classes >> which) & 1)) continue;
     const W12Layout l = w12_layout(sh.n_pairs, sh.K, n_wide[i]);
     const char* p = static_cast<const char*>(w12) + w12_offset(c, n_wide, i);
-    m->w12[i] = {p, reinterpret_cast<const uint32_t*>(p + l.main_bytes + l.ovf_bytes), p + l.main_bytes};
+    m->w12[i] = {p, reinterpret_cast<const uint32_t*>(p + l.main_bytes + l.ovf_bytes), p + l.main_bytes, form};
   }
   return 0;
+}
+
+extern "C" int sd_model_set_w12(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes) {
+  clear_error();
+  SD_REQUIRE(m, "model_set_w12: NULL model");
+  m->w12.clear();
+  if (!w12) return 0;   // back to the bf16 streams
+  return model_add_w12(m, w12, n_wide, classes, W12_CODES);
+}
+
+extern "C" int sd_model_set_w12_form(sd_model* m, const void* w12, const uint32_t* n_wide, unsigned classes, int form) {
+  clear_error();
+  SD_REQUIRE(m, "model_set_w12_form: NULL model");
+  return model_add_w12(m, w12, n_wide, classes, form);
 }
 
 extern "C" int sd_model_pass_tokens(const sd_model* m) { return m ? m->max_t : 0; }
@@ -1161,7 +1174,7 @@ extern "C" int sd_gemv_variant(int T, int n_pairs, int K, int w8, int prologue, 
              "gemv_variant: prologue=%d epi=%d out of range", prologue, epi);
   SD_REQUIRE(n_pairs >= 1 && K >= 8 && K % 8 == 0, "gemv_variant: n_pairs=%d K=%d (K must be a multiple of 8)", n_pairs, K);
   char name[64];
-  const int n = gemv_variant_name(T, n_pairs, K, w8 == 1, prologue, epi, name, sizeof(name), w8 == 2);   // w8: 0 bf16, 1 fp8, 2 bf16 with a W12 copy
+  const int n = gemv_variant_name(T, n_pairs, K, w8 == 1, prologue, epi, name, sizeof(name), w8 == 2 ? W12_CODES : w8 == 3 ? W12_SPLIT : W12_NONE);   // w8: 0 bf16, 1 fp8, 2 bf16 with a W12 copy, 3 with a W12S copy
   SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(name) && static_cast<size_t>(n) < cap, "gemv_variant: cap=%zu is too short for the name (%d bytes with its NUL)", cap, n + 1);
   memcpy(out, name, static_cast<size_t>(n) + 1);
   return 0;
@@ -1176,7 +1189,7 @@ extern "C" int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue,
   SD_REQUIRE(n_pairs >= 1 && K >= 8 && K % 8 == 0, "gemv_instance: n_pairs=%d K=%d (K must be a multiple of 8)", n_pairs, K);
   char name[64];
   int n = 0;
-  if (int rc = gemv_instance_name(T, n_pairs, K, w8 == 1, prologue, epi, name, sizeof(name), &n, w8 == 2)) return rc;   // a launch launch_gemv refuses, in its words
+  if (int rc = gemv_instance_name(T, n_pairs, K, w8 == 1, prologue, epi, name, sizeof(name), &n, w8 == 2 ? W12_CODES : w8 == 3 ? W12_SPLIT : W12_NONE)) return rc;   // a launch launch_gemv refuses, in its words
   SD_REQUIRE(n > 0 && static_cast<size_t>(n) < sizeof(name) && static_cast<size_t>(n) < cap, "gemv_instance: cap=%zu is too short for the name (%d bytes with its NUL)", cap, n + 1);
   memcpy(out, name, static_cast<size_t>(n) + 1);
   return 0;

@@ -149,10 +149,13 @@ __device__ __forceinline__ void stage_x(const GemvArgs& a, uint16_t* xs, int KP,
 //   a block is wide, and its exponent base, come from the side table: one vector load per batch, issued in front of the batch's
 //   weight loads and read with readlane (wave-uniform branches). MFMA operands, sums and epilogues are those of the bf16 kernel:
 //   every output is bit-identical by construction. 3/4 of the HBM bytes (+ ~1 % for wide blocks and the table).
-template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, bool W12 = false>
+//   W12F = W12_SPLIT is the split-byte form of the same copy (W12S, gemv_device.h): raw low bytes and 4-bit high-byte codes,
+//   widened with 12 instructions (v_perm_b32 through a two-register table). Nothing else in the kernel knows the form.
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, int W12F = W12_NONE>
 __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs a) {
   constexpr int kBatch = KB;
   constexpr bool FIX = FKS >= 0;
+  constexpr bool W12 = W12F != W12_NONE;   // either form: slots, table and overflow are shared, only the widening differs
   static_assert(!W12 || (!MASK && !W8), "W12: bf16 matrices in whole 32-k steps");
   // a geometry field of the argument block, or its compile-time value in a fixed instance. Used IN PLACE of the field, where
   // the generic kernel reads it, so that the generic instantiations compile to the instructions they had before
@@ -492,7 +495,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_mfma_kernel(const GemvArgs 
               if constexpr (W12) {
                 const uint32_t e = __builtin_amdgcn_readlane(ent, j);   // wave-uniform
                 if (e >> 31) { if constexpr (kWide4) wv[3] = wide4[j]; }
-                else wv = w12_widen(buf[j], ((e >> 23) & 0xFFu) * 0x00800080u);
+                else wv = w12_widen_form<W12F>(buf[j], (e >> 23) & 0xFFu);
               }
               acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wv),
                                                             __builtin_bit_cast(bf16x8_t, xb), acc, 0, 0, 0);
@@ -580,7 +583,7 @@ int gemv_grid(const GemvArgs& a, int* ppw_out) {
   return q.grid;
 }
 
-template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, bool W12 = false>
+template <int EPI, bool MASK, int TT, bool W8, int KB, int FKS = -1, int FTP = 0, int FPRO = PRO_NONE, int W12 = W12_NONE>
 static int launch_one(const GemvArgs& a, int grid, size_t smem, hipStream_t st) {
   // dynamic LDS above 64 KiB has to be opted into once per kernel
   static unsigned long long attr_set = 0;
@@ -650,7 +653,7 @@ struct GemvChoice {
   bool alias;      // the partials alias the x rows in LDS
   int fixed;       // GEMV_FIXED: index into kGemvFixed
   size_t smem;     // dynamic LDS of the launch
-  bool w12;        // GEMV_GENERIC / GEMV_FIXED: the W12 twin of the kernel, over the matrix's W12 copy
+  int w12;         // GEMV_GENERIC / GEMV_FIXED: W12Form of the W12 twin of the kernel, over the matrix's W12 copy (W12_NONE: bf16 / fp8)
 };
 // token bound at which the fixed-geometry instances have W12 twins: 5, the verify pass of a K = 4 step. A W12 launch of a
 // fixed class at another token count runs the generic W12 kernel.
@@ -660,8 +663,8 @@ bool gemv_w12_covers(int n_pairs, int K) {
   const GemvGeom q = gemv_geometry(n_pairs, K);
   return q.kw * q.ksplit == K && K / 8 <= kGemvThreads;   // no MASK variant: whole 32-k steps, register-staged x
 }
-// `w12`: the matrix has a W12 copy and the launch may use it (packed bf16, not batched); SPECDEC_NO_W12 is read at every call
-static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain, bool hand_over, bool w12 = false) {
+// `w12`: the matrix has a W12 copy of that form and the launch may use it (packed bf16, not batched); SPECDEC_NO_W12 is read at every call
+static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, int epi, bool plain, bool hand_over, int w12 = W12_NONE) {
   GemvChoice c{};
   c.q = gemv_geometry(n_pairs, K);
   c.fixed = -1;
@@ -684,7 +687,7 @@ static GemvChoice gemv_choose(int T, int n_pairs, int K, bool w8, int prologue, 
     return c;
   }
   c.fixed = gemv_fixed_index(T, n_pairs, K, w8, prologue, epi, plain);
-  c.w12 = w12 && !w8 && !c.mask && !getenv(debug_env::kNoW12);
+  c.w12 = (!w8 && !c.mask && !getenv(debug_env::kNoW12)) ? w12 : W12_NONE;
   if (c.w12 && c.tt != kW12FixedTT) c.fixed = -1;
   c.route = c.fixed >= 0 ? GEMV_FIXED : GEMV_GENERIC;
   return c;
@@ -708,20 +711,21 @@ static int launch_epi_w(const GemvArgs& a, const GemvChoice& c, int grid, hipStr
   }
 }
 
-template <int EPI, int KB>
+template <int EPI, int KB, int FORM>
 static int launch_epi_w12(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
   switch (c.tt) {
-    case 1: return launch_one<EPI, false, 1, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
-    case 2: return launch_one<EPI, false, 2, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
-    case 3: return launch_one<EPI, false, 3, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
-    case 5: return launch_one<EPI, false, 5, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
-    default: return launch_one<EPI, false, kGemvMaxT, false, KB, -1, 0, PRO_NONE, true>(a, grid, c.smem, st);
+    case 1: return launch_one<EPI, false, 1, false, KB, -1, 0, PRO_NONE, FORM>(a, grid, c.smem, st);
+    case 2: return launch_one<EPI, false, 2, false, KB, -1, 0, PRO_NONE, FORM>(a, grid, c.smem, st);
+    case 3: return launch_one<EPI, false, 3, false, KB, -1, 0, PRO_NONE, FORM>(a, grid, c.smem, st);
+    case 5: return launch_one<EPI, false, 5, false, KB, -1, 0, PRO_NONE, FORM>(a, grid, c.smem, st);
+    default: return launch_one<EPI, false, kGemvMaxT, false, KB, -1, 0, PRO_NONE, FORM>(a, grid, c.smem, st);
   }
 }
 
 template <int EPI>
 static int launch_epi(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
-  if (c.w12) return c.deep ? launch_epi_w12<EPI, kBatchDeep>(a, c, grid, st) : launch_epi_w12<EPI, kBatchShallow>(a, c, grid, st);
+  if (c.w12 == W12_SPLIT) return c.deep ? launch_epi_w12<EPI, kBatchDeep, W12_SPLIT>(a, c, grid, st) : launch_epi_w12<EPI, kBatchShallow, W12_SPLIT>(a, c, grid, st);
+  if (c.w12) return c.deep ? launch_epi_w12<EPI, kBatchDeep, W12_CODES>(a, c, grid, st) : launch_epi_w12<EPI, kBatchShallow, W12_CODES>(a, c, grid, st);
   if (a.w8) return c.deep ? launch_epi_w<EPI, true, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, true, kBatchShallow>(a, c, grid, st);
   return c.deep ? launch_epi_w<EPI, false, kBatchDeep>(a, c, grid, st) : launch_epi_w<EPI, false, kBatchShallow>(a, c, grid, st);
 }
@@ -729,19 +733,20 @@ static int launch_epi(const GemvArgs& a, const GemvChoice& c, int grid, hipStrea
 static const char* const kEpiNames[] = {"qkv", "resid", "swiglu", "gelu", "argmax"};
 static const char* const kProNames[] = {"none", "rmsnorm", "layernorm"};
 
-static int gemv_fixed_name(int i, int tt, bool deep, char* out, size_t cap, bool w12 = false) {
+static const char* const kW12Names[] = {"", "w12", "w12s"};   // by W12Form
+static int gemv_fixed_name(int i, int tt, bool deep, char* out, size_t cap, int w12 = W12_NONE) {
   const GemvFixed& f = kGemvFixed[i];
-  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d%s>", kEpiNames[f.epi], 1 << f.ks_shift, f.tile_pairs, kProNames[f.prologue], tt,
-                  deep ? kBatchDeep : kBatchShallow, w12 ? ",w12" : "");
+  return snprintf(out, cap, "fixed<%s,ks%d,tp%d,%s,tt%d,kb%d%s%s>", kEpiNames[f.epi], 1 << f.ks_shift, f.tile_pairs, kProNames[f.prologue], tt,
+                  deep ? kBatchDeep : kBatchShallow, w12 ? "," : "", kW12Names[w12]);
 }
 
-int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, bool w12) {
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int w12) {
   const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true, w12);
   if (c.route != GEMV_FIXED) return snprintf(out, cap, "generic");
   return gemv_fixed_name(c.fixed, c.tt, c.deep, out, cap, c.w12);
 }
 
-int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, bool w12) {
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, int w12) {
   const GemvChoice c = gemv_choose(T, n_pairs, K, w8, prologue, epi, true, true, w12);
   if (int rc = gemv_choice_refused(c, T, K)) return rc;
   if (c.route == GEMV_FIXED) {
@@ -750,7 +755,7 @@ int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi
     const int n = snprintf(out, cap, "skinny:");
     *len = n + gemm_plan_name(gemm_plan(T, n_pairs, K, w8, prologue, epi, 0), epi, w8, out + n, static_cast<size_t>(n) < cap ? cap - n : 0);
   } else {
-    *len = snprintf(out, cap, "generic<%s,%s,tt%d,%s,kb%d>", kEpiNames[epi], c.mask ? "mask" : "whole", c.tt, c.w12 ? "w12" : w8 ? "fp8" : "bf16",
+    *len = snprintf(out, cap, "generic<%s,%s,tt%d,%s,kb%d>", kEpiNames[epi], c.mask ? "mask" : "whole", c.tt, c.w12 ? kW12Names[c.w12] : w8 ? "fp8" : "bf16",
                     c.deep ? kBatchDeep : kBatchShallow);
   }
   return 0;
@@ -763,9 +768,12 @@ static int launch_fixed_tt(const GemvArgs& a, const GemvChoice& c, int grid, hip
 }
 template <int EPI, int KS, int TP, int PRO>
 static int launch_fixed(const GemvArgs& a, const GemvChoice& c, int grid, hipStream_t st) {
-  if (c.w12)   // (gemv_choose: c.tt == kW12FixedTT)
-    return c.deep ? launch_one<EPI, false, kW12FixedTT, false, kBatchDeep, KS, TP, PRO, true>(a, grid, c.smem, st)
-                  : launch_one<EPI, false, kW12FixedTT, false, kBatchShallow, KS, TP, PRO, true>(a, grid, c.smem, st);
+  if (c.w12 == W12_SPLIT)   // (gemv_choose: c.tt == kW12FixedTT)
+    return c.deep ? launch_one<EPI, false, kW12FixedTT, false, kBatchDeep, KS, TP, PRO, W12_SPLIT>(a, grid, c.smem, st)
+                  : launch_one<EPI, false, kW12FixedTT, false, kBatchShallow, KS, TP, PRO, W12_SPLIT>(a, grid, c.smem, st);
+  if (c.w12)
+    return c.deep ? launch_one<EPI, false, kW12FixedTT, false, kBatchDeep, KS, TP, PRO, W12_CODES>(a, grid, c.smem, st)
+                  : launch_one<EPI, false, kW12FixedTT, false, kBatchShallow, KS, TP, PRO, W12_CODES>(a, grid, c.smem, st);
   switch (c.tt) {
     case 1: return launch_fixed_tt<EPI, KS, TP, PRO, 1>(a, c, grid, st);
     case 2: return launch_fixed_tt<EPI, KS, TP, PRO, 2>(a, c, grid, st);
@@ -789,7 +797,7 @@ int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
   // one workgroup (16 waves) per CU with an equal, contiguous share of the row pairs, cut into
   // a power-of-two count of <= 8-pair tiles; the 16 waves take (tile, K-slice) units
   const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes, !a.x_row && !a.batch_bytes,
-                                   a.w12_main && a.w12_table && a.packed && !a.batch_bytes);
+                                   (a.w12_main && a.w12_table && a.packed && !a.batch_bytes) ? (a.w12_form == W12_SPLIT ? W12_SPLIT : W12_CODES) : W12_NONE);
   if (int rc = gemv_choice_refused(c, a.T, a.K)) return rc;
   if (c.route == GEMV_SKINNY) return launch_gemm_skinny(a_in, epi, st);
   a.w12 = c.w12 ? 1 : 0;

@@ -53,6 +53,57 @@ __device__ __forceinline__ u32x4 w12_encode(const u32x4 v, uint32_t base) {
   return o;
 }
 
+// ---- W12S, the split-byte form of W12 (same blocks, slots, overflow and table): a bf16 weight is a high byte
+// h = sign<<7 | exp>>1 and a low byte l = (exp&1)<<7 | mantissa. A lane's 12 bytes of a narrow block are
+//   dword 0   low bytes of weights 0..3, weight i at byte i, raw
+//   dword 1   low bytes of weights 4..7, raw
+//   dword 2   eight 4-bit codes  sign<<3 | ((exp>>1) - base),  byte j = code[j] | code[j+4] << 4
+// with base = max(0, (emax>>1) - 7) in the table entry's base field. Widening is 12 VALU instructions per lane per block:
+// the 8-entry high-byte table base + 0..7 is two wave-uniform dwords (tlo, thi: scalar registers); per group of four weights
+// one AND makes the byte selectors, one v_perm_b32 looks the high bytes up, one v_bfi_b32 puts the sign bits in (for weights
+// 0..3 they come from d2 << 4, for 4..7 from d2 itself after the selectors were taken from d2 >> 4), and four v_perm_b32
+// interleave high and low bytes into the four output dwords (weight 2k is the low half of dword k).
+// (__builtin_amdgcn_perm(a, b, sel): selector byte 0..3 takes byte 0..3 of b, 4..7 takes byte 0..3 of a.)
+__device__ __forceinline__ u32x4 w12s_widen(const u32x4 v, uint32_t tlo, uint32_t thi) {   // v[0..1]: low bytes, v[2]: codes; v[3] unused
+  const uint32_t d2 = v[2];
+  const uint32_t ha = __builtin_amdgcn_perm(thi, tlo, d2 & 0x07070707u);
+  const uint32_t hb = __builtin_amdgcn_perm(thi, tlo, (d2 >> 4) & 0x07070707u);
+  const uint32_t ga = ((d2 << 4) & 0x80808080u) | (ha & 0x7F7F7F7Fu);
+  const uint32_t gb = (d2 & 0x80808080u) | (hb & 0x7F7F7F7Fu);
+  u32x4 o;
+  o[0] = __builtin_amdgcn_perm(ga, v[0], 0x05010400u);
+  o[1] = __builtin_amdgcn_perm(ga, v[0], 0x07030602u);
+  o[2] = __builtin_amdgcn_perm(gb, v[1], 0x05010400u);
+  o[3] = __builtin_amdgcn_perm(gb, v[1], 0x07030602u);
+  return o;
+}
+// the packer's side: high-byte offsets are taken mod 8, so a block that does not fit the window widens to OTHER bits
+__device__ __forceinline__ u32x4 w12s_encode(const u32x4 v, uint32_t base) {
+  u32x4 o = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t h = (v[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+    const uint32_t code = ((h >> 15) << 3) | ((((h >> 8) & 0x7Fu) - base) & 7u);
+    o[i >> 2] |= (h & 0xFFu) << (8 * (i & 3));
+    o[2] |= code << (8 * (i & 3) + 4 * (i >> 2));
+  }
+  return o;
+}
+
+// One widening / encoding / base rule per form (W12Form, kernels.h); `base` is the table entry's base field (wave-uniform).
+template <int FORM>
+__device__ __forceinline__ u32x4 w12_widen_form(const u32x4 v, uint32_t base) {
+  if constexpr (FORM == W12_SPLIT) {
+    const uint32_t b4 = base * 0x01010101u;
+    return w12s_widen(v, b4 + 0x03020100u, b4 + 0x07060504u);
+  } else {
+    return w12_widen(v, base * 0x00800080u);
+  }
+}
+__device__ __forceinline__ uint32_t w12_base_of(int form, int emax) {   // emax: the largest exponent of the block
+  return static_cast<uint32_t>(form == W12_SPLIT ? max((emax >> 1) - 7, 0) : max(emax - 15, 0));
+}
+
 // Kernel arguments into SGPRs at kernel entry: hipcc loads a by-value argument struct lazily, next to each first
 // use, which puts 5-6 DEPENDENT scalar-cache round trips (s_load -> s_waitcnt) in front of the first vector load of
 // these latency-bound kernels (0.7 us from wave entry to the first weight load in the in-kernel timeline). One empty

@@ -93,6 +93,7 @@ struct GemvArgs {
   const void* w12_main;
   const uint32_t* w12_table;
   const void* w12_ovf;           // fourth dwords of the wide blocks, 256 bytes each (read by the kernel, late and rarely)
+  int w12_form;                  // W12Form of that copy (0 with a copy: W12_CODES); read by launch_gemv, not by the kernels
 };
 constexpr int kStatStride = 256;                    // partials per token (>= workgroups of the producing launch)
 constexpr int kStatPlane = kSkinnyMaxT * kStatStride;   // floats per plane (plane 0: sum of squares, plane 1: sum)
@@ -140,6 +141,8 @@ size_t packed_any_matrix_bytes(int n_pairs, int K, int weight_dtype);   // bf16 
 int pack_one_matrix(const void* w_bf16, int N, int K, int n_pairs, int epi, int head_dim, int weight_dtype, void* dst, hipStream_t st);
 // W12 copy of a matrix (pack.hip): [main stream][overflow of the wide blocks][table], each padded to 256 bytes
 constexpr int kW12OvfBlock = 256;
+// what a narrow block's 12 bytes per lane hold (gemv_device.h): 12-bit codes, or raw low bytes + 4-bit high-byte codes (W12S)
+enum W12Form { W12_NONE = 0, W12_CODES = 1, W12_SPLIT = 2 };
 struct W12Layout {
   size_t main_bytes, ovf_bytes, table_bytes;   // padded
   size_t total() const { return main_bytes + ovf_bytes + table_bytes; }
@@ -155,11 +158,11 @@ int launch_gemv(const GemvArgs& a, int epi, hipStream_t st);          // T <= 9:
 int launch_gemm_skinny(const GemvArgs& a, int epi, hipStream_t st);   // T <= 64
 // name of the gemv.hip instance a plain launch (packed, no bias / x_row / batch) of T <= 9 tokens takes: "generic" or
 // "fixed<...>"; decided by the function launch_gemv asks. snprintf's return value.
-int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, bool w12 = false);
+int gemv_variant_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int w12 = W12_NONE);   // w12: W12Form of the matrix's copy
 // name of the KERNEL such a launch runs, from the choice launch_gemv itself consumes: "fixed<...>" as above,
-// "generic<EPI,whole|mask,ttN,bf16|fp8,kbN>" (the template key of gemv_mfma_kernel) or "skinny:" + gemm_plan_name of the body the
+// "generic<EPI,whole|mask,ttN,bf16|fp8|w12|w12s,kbN>" (the template key of gemv_mfma_kernel) or "skinny:" + gemm_plan_name of the body the
 // launch is handed to (rows too long to stage T of them). *len: snprintf's return value. Nonzero (error set) where launch_gemv refuses.
-int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, bool w12 = false);
+int gemv_instance_name(int T, int n_pairs, int K, bool w8, int prologue, int epi, char* out, size_t cap, int* len, int w12 = W12_NONE);
 bool gemv_w12_covers(int n_pairs, int K);   // shape the W12 kernels stream: whole 32-k steps per K slice, one x chunk per thread
 bool gemm_skinny_covers(int T, int n_pairs, int K, bool w8 = false);                  // shape handled by gemm_skinny.hip
 // gemm_pipe.hip: the statically scheduled chunk pipeline for <= 64 tokens (tried first by launch_gemm_skinny, which has

@@ -248,6 +248,9 @@ int pack_one_matrix(const void* w_bf16, int N, int K, int n_pairs, int epi, int 
 //             batch's weight loads and reads them with readlane; only the widening and the rare overflow load wait for it.
 // Whether a block is narrow is decided by widening its codes and comparing bits (w12_classify_kernel), not by a rule on
 // the exponents. specdec_hip/w12.py restates the format; the measured narrow share is in profiles/w12_verify.md.
+// The split-byte FORM (W12_SPLIT, "W12S") keeps all of the above and changes only what a narrow chunk's 12 bytes hold — the 8 low
+// bytes raw, the high bytes as 4-bit codes in an even-aligned 16-exponent window (gemv_device.h) — and with it the base rule and
+// the widening. One packer, two encoders; profiles/w12_split.md has its narrow share.
 // ------------------------------------------------------------------------------
 size_t w12_table_entries(int n_pairs, int K) {
   const GemvGeom q = gemv_geometry(n_pairs, K);
@@ -272,6 +275,7 @@ struct W12Job {
   unsigned char* main;
   unsigned char* ovf;
   int n_pairs, K32, ppw, tile_pairs, ntf;
+  int form;   // W12Form
 };
 
 // block `b` of the table: pairs of its tile (0: the last workgroup has no such tile) and its byte offset in the bf16 stream
@@ -306,8 +310,8 @@ __global__ __launch_bounds__(256) void w12_classify_kernel(W12Job j, size_t n_en
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) emax = max(emax, __shfl_xor(emax, o, 64));
-      const uint32_t base = static_cast<uint32_t>(max(emax - 15, 0));
-      const u32x4 back = w12_widen(w12_encode(v, base), (base << 7) * 0x10001u);
+      const uint32_t base = w12_base_of(j.form, emax);
+      const u32x4 back = j.form == W12_SPLIT ? w12_widen_form<W12_SPLIT>(w12s_encode(v, base), base) : w12_widen_form<W12_CODES>(w12_encode(v, base), base);
       const bool same = !active || (back[0] == v[0] && back[1] == v[1] && back[2] == v[2] && back[3] == v[3]);
       ent = (__ballot(same) == ~0ull) ? (base << 23) : 0x80000000u;
     }
@@ -344,7 +348,7 @@ __global__ __launch_bounds__(256) void w12_fill_kernel(W12Job j, size_t n_entrie
     u32x4 v = {0u, 0u, 0u, 0u};
     if (active) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(j.src) + off + lane * 16);
     if (ent >> 31) *reinterpret_cast<uint32_t*>(j.ovf + static_cast<size_t>(ent & 0x7FFFFFu) * kW12OvfBlock + lane * 4) = v[3];   // (lanes without a chunk: zero)
-    else v = w12_encode(v, (ent >> 23) & 0xFFu);
+    else v = j.form == W12_SPLIT ? w12s_encode(v, (ent >> 23) & 0xFFu) : w12_encode(v, (ent >> 23) & 0xFFu);
     if (active) {
       uint32_t* d = reinterpret_cast<uint32_t*>(j.main + off / 4 * 3 + lane * 12);
       d[0] = v[0];
@@ -354,18 +358,18 @@ __global__ __launch_bounds__(256) void w12_fill_kernel(W12Job j, size_t n_entrie
   }
 }
 
-static W12Job w12_job(const void* packed_bf16, int n_pairs, int K, uint32_t* table, void* main, void* ovf) {
+static W12Job w12_job(const void* packed_bf16, int n_pairs, int K, uint32_t* table, void* main, void* ovf, int form) {
   const GemvGeom q = gemv_geometry(n_pairs, K);
   return {static_cast<const uint16_t*>(packed_bf16), table, static_cast<unsigned char*>(main), static_cast<unsigned char*>(ovf),
-          n_pairs, (K + 31) & ~31, q.ppw, q.tile_pairs, (q.ppw + q.tile_pairs - 1) / q.tile_pairs};
+          n_pairs, (K + 31) & ~31, q.ppw, q.tile_pairs, (q.ppw + q.tile_pairs - 1) / q.tile_pairs, form};
 }
 
 static int w12_grid(size_t n_entries) { return static_cast<int>(n_entries / 4 + 1 < 8192 ? n_entries / 4 + 1 : 8192); }
 
 // table of one matrix (classified and numbered) and its wide-block count, on the device
-int w12_measure_matrix(const void* packed_bf16, int n_pairs, int K, uint32_t* table, uint32_t* n_wide, hipStream_t st) {
+int w12_measure_matrix(const void* packed_bf16, int n_pairs, int K, uint32_t* table, uint32_t* n_wide, int form, hipStream_t st) {
   const size_t n = w12_table_entries(n_pairs, K);
-  hipLaunchKernelGGL(w12_classify_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, table, nullptr, nullptr), n);
+  hipLaunchKernelGGL(w12_classify_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, table, nullptr, nullptr, form), n);
   SD_LAUNCH_CHECK();
   hipLaunchKernelGGL(w12_number_kernel, dim3(1), dim3(1024), 0, st, table, n, n_wide);
   SD_LAUNCH_CHECK();
@@ -373,13 +377,13 @@ int w12_measure_matrix(const void* packed_bf16, int n_pairs, int K, uint32_t* ta
 }
 
 // the W12 copy at dst ([main][overflow][table], w12_layout) from the packed stream and its measured table
-int w12_fill_matrix(const void* packed_bf16, int n_pairs, int K, const uint32_t* table, uint32_t n_wide, void* dst, hipStream_t st) {
+int w12_fill_matrix(const void* packed_bf16, int n_pairs, int K, const uint32_t* table, uint32_t n_wide, void* dst, int form, hipStream_t st) {
   const W12Layout l = w12_layout(n_pairs, K, n_wide);
   const size_t n = w12_table_entries(n_pairs, K);
   char* d = static_cast<char*>(dst);
   uint32_t* tab = reinterpret_cast<uint32_t*>(d + l.main_bytes + l.ovf_bytes);
   SD_HIP_CHECK(hipMemcpyAsync(tab, table, n * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(w12_fill_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, tab, d, d + l.main_bytes), n);
+  hipLaunchKernelGGL(w12_fill_kernel, dim3(w12_grid(n)), dim3(256), 0, st, w12_job(packed_bf16, n_pairs, K, tab, d, d + l.main_bytes, form), n);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -418,9 +422,15 @@ extern "C" size_t sd_w12_scratch_bytes(const sd_model_config* cfg) {
   return w12_scratch_offset(*cfg, n) + ((static_cast<size_t>(n) * 4 + 255) & ~static_cast<size_t>(255));
 }
 
-extern "C" int sd_w12_measure(const sd_model_config* cfg, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream) {
+static int w12_form_ok(int form, const char* who) {
+  SD_REQUIRE(form == W12_CODES || form == W12_SPLIT, "%s: form %d (SD_W12_FORM_CODES or SD_W12_FORM_SPLIT)", who, form);
+  return 0;
+}
+
+extern "C" int sd_w12_measure_form(const sd_model_config* cfg, int form, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream) {
   clear_error();
   if (int rc = w12_cfg_ok(cfg, "w12_measure")) return rc;
+  if (int rc = w12_form_ok(form, "w12_measure")) return rc;
   SD_REQUIRE(scratch && n_wide && scratch_bytes >= sd_w12_scratch_bytes(cfg), "w12_measure: scratch too small or NULL");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "w12_measure: scratch must be 256-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -430,11 +440,15 @@ extern "C" int sd_w12_measure(const sd_model_config* cfg, void* scratch, size_t 
   for (int i = 0; i < n; ++i) {
     const MatShape m = matrix_shape(*cfg, matrix_which(*cfg, i));
     const void* src = static_cast<const char*>(cfg->packed) + packed_offset(*cfg, i);
-    if (int rc = w12_measure_matrix(src, m.n_pairs, m.K, reinterpret_cast<uint32_t*>(s + w12_scratch_offset(*cfg, i)), counts + i, st)) return rc;
+    if (int rc = w12_measure_matrix(src, m.n_pairs, m.K, reinterpret_cast<uint32_t*>(s + w12_scratch_offset(*cfg, i)), counts + i, form, st)) return rc;
   }
   SD_HIP_CHECK(hipMemcpyAsync(n_wide, counts, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
   SD_HIP_CHECK(hipStreamSynchronize(st));
   return 0;
+}
+
+extern "C" int sd_w12_measure(const sd_model_config* cfg, void* scratch, size_t scratch_bytes, uint32_t* n_wide, void* stream) {
+  return sd_w12_measure_form(cfg, W12_CODES, scratch, scratch_bytes, n_wide, stream);
 }
 
 extern "C" size_t sd_w12_bytes(const sd_model_config* cfg, const uint32_t* n_wide) {
@@ -458,9 +472,10 @@ extern "C" int sd_w12_matrix(const sd_model_config* cfg, const uint32_t* n_wide,
   return 0;
 }
 
-extern "C" int sd_w12_pack(const sd_model_config* cfg, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream) {
+extern "C" int sd_w12_pack_form(const sd_model_config* cfg, int form, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream) {
   clear_error();
   if (int rc = w12_cfg_ok(cfg, "w12_pack")) return rc;
+  if (int rc = w12_form_ok(form, "w12_pack")) return rc;
   SD_REQUIRE(scratch && n_wide && (dst || !sd_w12_bytes(cfg, n_wide)), "w12_pack: NULL argument");
   SD_REQUIRE(dst_bytes >= sd_w12_bytes(cfg, n_wide), "w12_pack: destination too small");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 255) == 0, "w12_pack: destination must be 256-byte aligned");
@@ -470,9 +485,13 @@ extern "C" int sd_w12_pack(const sd_model_config* cfg, const void* scratch, cons
     if (!w12_taken(m.n_pairs, m.K, n_wide[i])) continue;
     const void* src = static_cast<const char*>(cfg->packed) + packed_offset(*cfg, i);
     const uint32_t* table = reinterpret_cast<const uint32_t*>(static_cast<const char*>(scratch) + w12_scratch_offset(*cfg, i));
-    if (int rc = w12_fill_matrix(src, m.n_pairs, m.K, table, n_wide[i], static_cast<char*>(dst) + w12_offset(*cfg, n_wide, i), st)) return rc;
+    if (int rc = w12_fill_matrix(src, m.n_pairs, m.K, table, n_wide[i], static_cast<char*>(dst) + w12_offset(*cfg, n_wide, i), form, st)) return rc;
   }
   return 0;
+}
+
+extern "C" int sd_w12_pack(const sd_model_config* cfg, const void* scratch, const uint32_t* n_wide, void* dst, size_t dst_bytes, void* stream) {
+  return sd_w12_pack_form(cfg, W12_CODES, scratch, n_wide, dst, dst_bytes, stream);
 }
 
 // A vocabulary-sized output matrix [V][d] outside a model (Medusa heads): same layout and quantiser as the lm_head.

@@ -90,6 +90,9 @@ SIGNATURES = {
     "sd_w12_matrix": (_c_int, [_c_void_p, _c_void_p, _c_int, ctypes.POINTER(_c_int)] + [ctypes.POINTER(_c_size)] * 6),
     "sd_w12_pack": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p]),
     "sd_model_set_w12": (_c_int, [_c_void_p, _c_void_p, _c_void_p, ctypes.c_uint]),
+    "sd_w12_measure_form": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_size, _c_void_p, _c_void_p]),
+    "sd_w12_pack_form": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p]),
+    "sd_model_set_w12_form": (_c_int, [_c_void_p, _c_void_p, _c_void_p, ctypes.c_uint, _c_int]),
     "sd_model_create": (_c_int, [_c_void_p, _c_void_p]),
     "sd_model_destroy": (_c_int, [_c_void_p]),
     "sd_quantize_fp8_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),

@@ -52,34 +52,48 @@ def _stream(stream: Optional[torch.cuda.Stream], device) -> int:
 
 W12_DEFAULT = True   # bf16 models get the W12 copy (profiles/w12_verify.md)
 W12_CLASSES = 0x10   # matrix classes that stream it (SD_W12_DEFAULT_CLASSES: the lm_head); SPECDEC_W12_CLASSES=0x1f: all five
+W12S_CLASSES = 0x14  # classes that stream the split-byte form instead: gate / up and the lm_head (SD_W12S_DEFAULT_CLASSES; profiles/w12_split.md)
+W12_CODES, W12_SPLIT = 1, 2   # enum W12Form
 
 
-def build_w12(lib, mc: "_ModelConfig", dev, classes: int = 0x1F) -> Tuple[torch.Tensor, np.ndarray]:
-    """The W12 copy of a config's packed bf16 matrices of the given classes (bit 0 qkv .. bit 4 lm_head): (device buffer, host
-    uint32 wide-block counts per matrix, SD_W12_SKIP = 0xFFFFFFFF for a matrix that is left out)."""
+def w12_class_masks(env=None) -> Tuple[int, int]:
+    """(code-form classes, split-byte classes) of a new model, disjoint. SPECDEC_W12_CLASSES and SPECDEC_W12S_CLASSES override the
+    defaults; a class in both masks takes W12S, except that a class NAMED in an explicitly set SPECDEC_W12_CLASSES is not
+    moved to W12S by the mere default of the other mask (the code form stays reachable exactly as it was)."""
+    env = os.environ if env is None else env
+    codes_set, split_set = env.get("SPECDEC_W12_CLASSES"), env.get("SPECDEC_W12S_CLASSES")
+    codes = (int(codes_set, 0) if codes_set is not None else W12_CLASSES) & 0x1F
+    split = (int(split_set, 0) & 0x1F) if split_set is not None else (W12S_CLASSES & ~codes if codes_set is not None else W12S_CLASSES)
+    return codes & ~split, split
+
+
+def build_w12(lib, mc: "_ModelConfig", dev, classes: int = 0x1F, form: int = W12_CODES) -> Tuple[torch.Tensor, np.ndarray]:
+    """The W12 copy, in the given form, of a config's packed bf16 matrices of the given classes (bit 0 qkv .. bit 4 lm_head):
+    (device buffer, host uint32 wide-block counts per matrix, SD_W12_SKIP = 0xFFFFFFFF for a matrix that is left out)."""
     n_wide = np.zeros(4 * mc.n_layers + 1, dtype=np.uint32)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         scratch = torch.empty(lib.sd_w12_scratch_bytes(ctypes.byref(mc)), dtype=torch.uint8, device=dev)
-        _abi.check(lib.sd_w12_measure(ctypes.byref(mc), scratch.data_ptr(), scratch.numel(), n_wide.ctypes.data, st), "sd_w12_measure")
+        _abi.check(lib.sd_w12_measure_form(ctypes.byref(mc), form, scratch.data_ptr(), scratch.numel(), n_wide.ctypes.data, st), "sd_w12_measure_form")
         for i in range(n_wide.size):
             if not (classes >> (4 if i == 4 * mc.n_layers else i & 3)) & 1:
                 n_wide[i] = 0xFFFFFFFF
         nbytes = lib.sd_w12_bytes(ctypes.byref(mc), n_wide.ctypes.data)
         buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        _abi.check(lib.sd_w12_pack(ctypes.byref(mc), scratch.data_ptr(), n_wide.ctypes.data, buf.data_ptr(), buf.numel(), st), "sd_w12_pack")
+        _abi.check(lib.sd_w12_pack_form(ctypes.byref(mc), form, scratch.data_ptr(), n_wide.ctypes.data, buf.data_ptr(), buf.numel(), st), "sd_w12_pack_form")
         torch.cuda.current_stream(dev).synchronize()   # scratch is read by the pack
     return buf, n_wide
 
 
-def w12_matrix_info(lib, mc: "_ModelConfig", n_wide: np.ndarray, index: int) -> dict:
-    """sd_w12_matrix as a dict: taken, offset, main_bytes, ovf_bytes, table_bytes, blocks, bf16_bytes, n_wide."""
+def w12_matrix_info(lib, mc: "_ModelConfig", n_wide: np.ndarray, index: int, form: int = W12_CODES) -> dict:
+    """sd_w12_matrix as a dict: taken, offset, main_bytes, ovf_bytes, table_bytes, blocks, bf16_bytes, n_wide, and the form
+    (W12_CODES / W12_SPLIT) of the copy the counts belong to, as the caller names it."""
     taken = ctypes.c_int()
     v = [ctypes.c_size_t() for _ in range(6)]
     _abi.check(lib.sd_w12_matrix(ctypes.byref(mc), n_wide.ctypes.data, index, ctypes.byref(taken), *[ctypes.byref(x) for x in v]),
                "sd_w12_matrix")
     keys = ("offset", "main_bytes", "ovf_bytes", "table_bytes", "blocks", "bf16_bytes")
-    return {"taken": bool(taken.value), "n_wide": int(n_wide[index]), **{k: int(x.value) for k, x in zip(keys, v)}}
+    return {"taken": bool(taken.value), "n_wide": int(n_wide[index]), "form": int(form), **{k: int(x.value) for k, x in zip(keys, v)}}
 
 
 class EngineGaveUp(_abi.HipLibraryError):
@@ -174,18 +188,22 @@ class HipModel:
         # W12: a lossless 12-bit copy of the packed bf16 matrices for the launches of 1..9 tokens (csrc/pack.hip), one per
         # ModelWeights like the packed copy. W12_DEFAULT / W12_CLASSES: what profiles/w12_verify.md measured; SPECDEC_W12=1 / 0 and
         # SPECDEC_W12_CLASSES (bit mask: 1 qkv, 2 out, 4 gate / up, 8 down, 16 lm_head) override them, and
-        # SPECDEC_NO_W12 (the library's per-launch switch) also skips building the copy.
+        # SPECDEC_NO_W12 (the library's per-launch switch) also skips building the copy. A copy is built per (classes, form):
+        # _w12 the code form, _w12s the split-byte form (W12S_CLASSES / SPECDEC_W12S_CLASSES; w12_class_masks).
         self._w12 = None
+        self._w12s = None
         self._mc = mc
         want_w12 = os.environ.get("SPECDEC_W12", "1" if W12_DEFAULT else "0") not in ("", "0")
         if weight_dtype == "bf16" and packed is not None and want_w12 and not os.environ.get("SPECDEC_NO_W12"):
-            classes = int(os.environ.get("SPECDEC_W12_CLASSES", str(W12_CLASSES)), 0) & 0x1F
-            key = f"_w12_{classes:02x}"
-            self._w12 = weights.meta.get(key)
-            if self._w12 is None:
-                self._w12 = weights.meta[key] = build_w12(self.lib, mc, dev, classes)
-            buf, n_wide = self._w12
-            _abi.check(self.lib.sd_model_set_w12(self.handle, _ptr(buf), n_wide.ctypes.data, classes), "sd_model_set_w12")
+            for attr, classes, form in zip(("_w12", "_w12s"), w12_class_masks(), (W12_CODES, W12_SPLIT)):
+                if not classes:
+                    continue
+                key = f"{attr}_{classes:02x}"
+                copy = weights.meta.get(key)
+                if copy is None:
+                    copy = weights.meta[key] = build_w12(self.lib, mc, dev, classes, form)
+                setattr(self, attr, copy)
+                _abi.check(self.lib.sd_model_set_w12_form(self.handle, _ptr(copy[0]), copy[1].ctypes.data, classes, form), "sd_model_set_w12_form")
         self.batch, self.l_max = int(batch), (int(l_max) + 31) // 32 * 32  # whole 32-key blocks
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):

@@ -792,23 +792,24 @@ def gemm_plan(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PR
     return buf.value.decode()
 
 
-def gemv_variant(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID, w12: bool = False) -> str:
+def gemv_variant(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID, w12: int = 0) -> str:
     """Name of the csrc/gemv.hip instance a layer-matrix launch of T <= 9 tokens runs (sd_gemv_variant): "generic" or
     "fixed<qkv,ks8,tp5,rmsnorm,tt5,kb6>". w12: the (bf16) matrix has a W12 copy — "fixed<...,w12>" at 5 tokens, "generic" at other
-    counts; SPECDEC_NO_W12 turns it off. Follows SPECDEC_GEMV_GENERIC in the environment, as a launch does. Host-only."""
+    counts; SPECDEC_NO_W12 turns it off. w12 is the form of the copy: True / W12_CODES (1) the code form, W12_SPLIT (2) the
+    split-byte form, whose names say "w12s". Follows SPECDEC_GEMV_GENERIC in the environment, as a launch does. Host-only."""
     buf = ctypes.create_string_buffer(64)
-    _abi.check(_abi.load().sd_gemv_variant(int(T), int(n_pairs), int(K), 1 if w8 else 2 if w12 else 0, int(prologue), int(epi), buf, len(buf)),
+    _abi.check(_abi.load().sd_gemv_variant(int(T), int(n_pairs), int(K), 1 if w8 else 1 + int(w12) if w12 else 0, int(prologue), int(epi), buf, len(buf)),
                "sd_gemv_variant")
     return buf.value.decode()
 
 
-def gemv_instance(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID, w12: bool = False) -> str:
+def gemv_instance(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int = PRO_NONE, epi: int = EPI_RESID, w12: int = 0) -> str:
     """Name of the kernel a layer-matrix launch of T <= 9 tokens really runs (sd_gemv_instance): "fixed<...>" as gemv_variant,
     "generic<resid,mask,tt9,bf16,kb12>" (the generic kernel's template key) or "skinny:direct<tg1>" (rows too long to stage:
-    the csrc/gemm_skinny.hip body that takes the launch). Raises where the launcher would refuse. Follows SPECDEC_GEMV_GENERIC
+    the csrc/gemm_skinny.hip body that takes the launch). w12: as for gemv_variant ("generic<...,w12s,kb12>"). Raises where the launcher would refuse. Follows SPECDEC_GEMV_GENERIC
     in the environment, as a launch does. Host-only."""
     buf = ctypes.create_string_buffer(64)
-    _abi.check(_abi.load().sd_gemv_instance(int(T), int(n_pairs), int(K), 1 if w8 else 2 if w12 else 0, int(prologue), int(epi), buf, len(buf)),
+    _abi.check(_abi.load().sd_gemv_instance(int(T), int(n_pairs), int(K), 1 if w8 else 1 + int(w12) if w12 else 0, int(prologue), int(epi), buf, len(buf)),
                "sd_gemv_instance")
     return buf.value.decode()
 

@@ -16,7 +16,17 @@ the 8 weights k = 32*step + 8*g + 0..7 of one row. W12 keeps the order of the bl
 
 A block's slot is at an address the kernel computes without the table, so the weight loads do not wait for it; only
 the widening (base) and the rare fourth dword of a wide block do. Decode of a code c: ((c & 0x800) << 4) | ((c & 0x7ff) +
-(base << 7)) — the bf16 bits again, exactly."""
+(base << 7)) — the bf16 bits again, exactly.
+
+W12S, the split-byte FORM (W12_SPLIT; the *_split / w12s_* functions below), keeps the blocks, slots, overflow and table and
+changes what a narrow chunk's 12 bytes hold. A bf16 weight is a high byte h = sign<<7 | exp>>1 and a low byte
+l = (exp&1)<<7 | mantissa:
+
+  bytes 0..7    the low bytes of weights 0..7, raw
+  bytes 8..11   eight 4-bit codes  sign<<3 | ((exp>>1) - base),  byte 8 + j = code[j] | code[j+4] << 4
+
+with base = max(0, (emax>>1) - 7) in the entry's base field: a block is narrow when its exponents lie in the even-aligned
+16-value window 2*base .. 2*base + 15. Decode: h = (code & 8) << 4 | ((code & 7) + base), bits = h << 8 | l."""
 
 from __future__ import annotations
 
@@ -28,6 +38,7 @@ import numpy as np
 EPI_QKV_ROPE, EPI_RESID, EPI_SWIGLU, EPI_GELU, EPI_ARGMAX = 0, 1, 2, 3, 4
 OVF_BLOCK = 256           # bytes of overflow per wide block
 MIN_SAVING = 0.15         # a matrix takes W12 when its W12 bytes are at least this much below its bf16 bytes
+W12_CODES, W12_SPLIT = 1, 2   # enum W12Form (csrc/kernels.h): what a narrow block's 12 bytes per lane hold
 
 
 @dataclass(frozen=True)
@@ -123,7 +134,13 @@ def _block_view(stream: np.ndarray, p0: int, npairs: int, K32: int) -> np.ndarra
     return stream[p0 * 2 * K32:(p0 + npairs) * 2 * K32].reshape(K32 // 32, 8 * npairs, 8)   # [step][chunk][8]
 
 
-def block_classes(stream: np.ndarray, n_pairs: int, K: int):
+def block_base(emax: np.ndarray, form: int = W12_CODES) -> np.ndarray:
+    """A block's base from its largest exponent: the code form's window ends at emax, the split form's at emax | 1."""
+    emax = np.asarray(emax, dtype=np.int64)
+    return np.maximum((emax >> 1) - 7, 0) if form == W12_SPLIT else np.maximum(emax - 15, 0)
+
+
+def block_classes(stream: np.ndarray, n_pairs: int, K: int, form: int = W12_CODES):
     """Per (tile, step): (table index, base, narrow) arrays over all blocks in stream order."""
     K32 = (K + 31) & ~31
     q = geometry(n_pairs, K)
@@ -133,15 +150,15 @@ def block_classes(stream: np.ndarray, n_pairs: int, K: int):
         e = (_block_view(stream, p0, npairs, K32) >> 7) & 0xFF
         emax = e.max(axis=(1, 2)).astype(np.int64)
         emin = e.min(axis=(1, 2)).astype(np.int64)
-        b = np.maximum(emax - 15, 0)
+        b = block_base(emax, form)
         idx.append((c * ntf + t) * nst + np.arange(nst))
         base.append(b)
-        narrow.append(emin >= b)
+        narrow.append((emin >> 1) >= b if form == W12_SPLIT else emin >= b)
     return np.concatenate(idx), np.concatenate(base), np.concatenate(narrow)
 
 
-def narrow_share(stream: np.ndarray, n_pairs: int, K: int) -> float:
-    return float(block_classes(stream, n_pairs, K)[2].mean())
+def narrow_share(stream: np.ndarray, n_pairs: int, K: int, form: int = W12_CODES) -> float:
+    return float(block_classes(stream, n_pairs, K, form)[2].mean())
 
 
 def w12_bytes(n_pairs: int, K: int, n_wide: int) -> int:
@@ -172,8 +189,24 @@ def decode_codes(b12: np.ndarray, base) -> np.ndarray:
     return (((c & 0x800) << 4) | ((c & 0x7FF) + (base << 7))).astype(np.uint16)
 
 
-def w12_pack(stream: np.ndarray, n_pairs: int, K: int) -> W12Matrix:
+def encode_split(bits: np.ndarray, base) -> np.ndarray:
+    """W12S, 12 bytes per 8 weights: bits uint16 [..., 8] -> uint8 [..., 12] (high-byte offsets taken mod 8)."""
+    b = bits.astype(np.int64)
+    code = ((b >> 15) << 3) | ((((b >> 8) & 0x7F) - np.asarray(base, dtype=np.int64)) & 7)
+    return np.concatenate([b & 0xFF, code[..., :4] | (code[..., 4:] << 4)], axis=-1).astype(np.uint8)
+
+
+def decode_split(b12: np.ndarray, base) -> np.ndarray:
+    """uint8 [..., 12] -> bf16 bits uint16 [..., 8]: h = (code & 8) << 4 | ((code & 7) + base), bits = h << 8 | l."""
+    n = b12[..., 8:].astype(np.int64)
+    code = np.concatenate([n & 0xF, n >> 4], axis=-1)
+    h = ((code & 8) << 4) | (((code & 7) + np.asarray(base, dtype=np.int64)) & 0x7F)
+    return ((h << 8) | b12[..., :8].astype(np.int64)).astype(np.uint16)
+
+
+def w12_pack(stream: np.ndarray, n_pairs: int, K: int, form: int = W12_CODES) -> W12Matrix:
     """W12 copy of a packed bf16 stream. A block is narrow only if its codes decode to its bits."""
+    enc, dec = (encode_split, decode_split) if form == W12_SPLIT else (encode_codes, decode_codes)
     K32 = (K + 31) & ~31
     q = geometry(n_pairs, K)
     ntf, nst = n_tiles_full(q), K32 // 32
@@ -184,9 +217,9 @@ def w12_pack(stream: np.ndarray, n_pairs: int, K: int) -> W12Matrix:
     for c, t, p0, npairs in tiles(n_pairs, K):
         blk = _block_view(stream, p0, npairs, K32)                      # [step][chunk][8]
         e = (blk >> 7) & 0xFF
-        base = np.maximum(e.max(axis=(1, 2)).astype(np.int64) - 15, 0)
-        codes = encode_codes(blk, base[:, None, None])   # (exponent offsets taken mod 16: a block that does not fit decodes to other bits)
-        narrow = (decode_codes(codes, base[:, None, None]) == blk).all(axis=(1, 2))
+        base = block_base(e.max(axis=(1, 2)), form)
+        codes = enc(blk, base[:, None, None])   # (exponent offsets taken mod 16 / mod 8: a block that does not fit decodes to other bits)
+        narrow = (dec(codes, base[:, None, None]) == blk).all(axis=(1, 2))
         raw = np.ascontiguousarray(blk).view(np.uint8).reshape(nst, 8 * npairs, 16)
         slot = np.where(narrow[:, None, None], codes, raw[..., :12])
         o = p0 * 2 * K32 * 2 * 3 // 4
@@ -204,8 +237,9 @@ def w12_pack(stream: np.ndarray, n_pairs: int, K: int) -> W12Matrix:
     return W12Matrix(main, ovf_arr, table, n_blocks, n_wide)
 
 
-def w12_unpack(m: W12Matrix, n_pairs: int, K: int) -> np.ndarray:
+def w12_unpack(m: W12Matrix, n_pairs: int, K: int, form: int = W12_CODES) -> np.ndarray:
     """The packed bf16 stream a W12 copy decodes to."""
+    dec = decode_split if form == W12_SPLIT else decode_codes
     K32 = (K + 31) & ~31
     q = geometry(n_pairs, K)
     ntf, nst = n_tiles_full(q), K32 // 32
@@ -216,7 +250,7 @@ def w12_unpack(m: W12Matrix, n_pairs: int, K: int) -> np.ndarray:
         base = ((ent >> 23) & 0xFF).astype(np.uint64)
         o = p0 * 2 * K32 * 2 * 3 // 4
         slot = m.main[o:o + nst * 8 * npairs * 12].reshape(nst, 8 * npairs, 12)
-        blk = decode_codes(slot, base[:, None, None])
+        blk = dec(slot, base[:, None, None])
         for s in np.nonzero(wide)[0]:
             k = int(ent[s] & 0x7FFFFF)
             raw = np.empty((8 * npairs, 16), dtype=np.uint8)
@@ -225,3 +259,12 @@ def w12_unpack(m: W12Matrix, n_pairs: int, K: int) -> np.ndarray:
             blk[s] = raw.view("<u2").reshape(8 * npairs, 8)
         out[p0 * 2 * K32:(p0 + npairs) * 2 * K32] = blk.reshape(-1)
     return out
+
+
+def w12s_pack(stream: np.ndarray, n_pairs: int, K: int) -> W12Matrix:
+    """W12S copy of a packed bf16 stream: w12_pack in the split-byte form."""
+    return w12_pack(stream, n_pairs, K, W12_SPLIT)
+
+
+def w12s_unpack(m: W12Matrix, n_pairs: int, K: int) -> np.ndarray:
+    return w12_unpack(m, n_pairs, K, W12_SPLIT)

@@ -19,7 +19,7 @@ bad = 0
 rows = []
 for k in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
     f = {m.group(1): m.group(2) for m in re.finditer(r"\.(\w+):\s+(\S+)", k)}
-    m = re.match(r"_ZN2sd16gemv_mfma_kernelILi(\d)ELb0ELi(\d+)ELb0ELi(\d+)ELi(n?\d+)ELi(\d+)ELi(\d+)ELb([01])EEE", f.get("name", ""))
+    m = re.match(r"_ZN2sd16gemv_mfma_kernelILi(\d)ELb0ELi(\d+)ELb0ELi(\d+)ELi(n?\d+)ELi(\d+)ELi(\d+)ELi([012])EEE", f.get("name", ""))
     if not m or (m.group(4) == "n1" and m.group(7) == "0"):
         continue   # the generic bf16 / fp8 / MASK kernels (FKS = -1) and other kernels
     e, tt, kb, tp, pro, w12 = (int(m.group(i)) for i in (1, 2, 3, 5, 6, 7))
@@ -27,7 +27,8 @@ for k in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
     vg, sg, scratch, spill = int(f["vgpr_count"]), int(f["sgpr_count"]), int(f["private_segment_fixed_size"]), int(f["vgpr_spill_count"])
     flag = "" if (scratch == 0 and spill == 0 and vg <= 128) else "  <-- over the limit"
     bad += bool(flag)
-    name = f"generic<{EPI[e]},whole,tt{tt},w12,kb{kb}>" if ks < 0 else f"fixed<{EPI[e]},ks{1 << ks},tp{tp},{PRO[pro]},tt{tt},kb{kb}{',w12' if w12 else ''}>"
+    form = ("", "w12", "w12s")[w12]   # W12Form: none, codes, split
+    name = f"generic<{EPI[e]},whole,tt{tt},{form},kb{kb}>" if ks < 0 else f"fixed<{EPI[e]},ks{1 << ks},tp{tp},{PRO[pro]},tt{tt},kb{kb}{',' + form if w12 else ''}>"
     rows.append(f"{name}: vgpr {vg} sgpr {sg} scratch {scratch} vgpr_spill {spill}{flag}")
 print("\n".join(sorted(rows)))
 print(f"{len(rows)} fixed / W12 instances, {bad} over the limit")

@@ -3,8 +3,9 @@
 
     python profiles/tools/w12_share.py            # first layer + lm_head of the synthetic 3B and 1B, and a plain randn matrix
 
-Prints, per matrix class, the share of (tile, 32-k step) blocks whose exponents fit a 16-value window (stored as 12-bit
-codes) and the size of the W12 copy relative to the packed bf16 stream. Layers of `synthetic_llama` are drawn alike, so
+Prints, per matrix class and for both forms of the copy, the share of (tile, 32-k step) blocks whose exponents fit the form's
+16-value window (the code form's ends at the largest exponent, the split-byte form's is aligned to an even one) and the size
+of the copy relative to the packed bf16 stream. Layers of `synthetic_llama` are drawn alike, so
 the first one stands for all of them."""
 
 from __future__ import annotations
@@ -29,11 +30,12 @@ def bits(t: torch.Tensor) -> np.ndarray:
 def report(name: str, w: torch.Tensor, n_pairs: int, epi: int, head_dim: int = 0) -> None:
     N, K = w.shape
     stream = w12.pack_bf16(bits(w), n_pairs, epi, head_dim)
-    _, _, narrow = w12.block_classes(stream, n_pairs, K)
-    n_wide = int((~narrow).sum())
-    size = w12.w12_bytes(n_pairs, K, n_wide)
-    print(f"{name:28s} N={N:6d} K={K:5d} blocks={narrow.size:7d} narrow={narrow.mean() * 100:6.2f} %  "
-          f"w12/bf16 bytes={size / stream.nbytes:.4f}", flush=True)
+    line = f"{name:28s} N={N:6d} K={K:5d}"
+    for tag, form in (("w12", w12.W12_CODES), ("w12s", w12.W12_SPLIT)):   # the code form, then the split-byte form
+        _, _, narrow = w12.block_classes(stream, n_pairs, K, form)
+        size = w12.w12_bytes(n_pairs, K, int((~narrow).sum()))
+        line += f"  {tag}: blocks={narrow.size:7d} narrow={narrow.mean() * 100:6.2f} % /bf16 bytes={size / stream.nbytes:.4f}"
+    print(line, flush=True)
 
 
 def model(cfg: W.ModelConfig, seed: int, **kw) -> W.ModelWeights:
