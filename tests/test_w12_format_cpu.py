@@ -7,17 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import w12_cases as C
 from specdec_hip import w12
-
-# (N, K, epi, head_dim): rows, inputs, epilogue (pair mapping)
-SHAPES = {
-    "8 pairs per tile": (4096, 64, w12.EPI_RESID, 0),            # 2048 pairs: 256 workgroups x 8
-    "5 pairs per tile": (2560, 256, w12.EPI_RESID, 0),           # 1280 pairs: 256 x 5
-    "1 pair per tile": (64, 512, w12.EPI_RESID, 0),              # 32 workgroups of one pair, 16 K slices
-    "qkv pairs": (512, 64, w12.EPI_QKV_ROPE, 64),                # rows (i, i + 32) of a head
-    "swiglu pairs, short last": (2 * 2051, 96, w12.EPI_SWIGLU, 0),   # 2051 pairs = 227 x 9 + 8: two tiles of 5 and 4, a short last workgroup
-    "odd N head": (1001, 64, w12.EPI_ARGMAX, 0),                 # 501 pairs, the last second row is zero
-}
+from w12_cases import FORCERS, SHAPES
 
 
 def _bits(t: torch.Tensor) -> np.ndarray:
@@ -59,9 +51,7 @@ def test_packed_stream_holds_every_weight_once():
 
 def test_all_narrow_matrix():
     N, K, epi, hd = SHAPES["8 pairs per tile"]
-    g = torch.Generator().manual_seed(1)
-    w = (1.0 + torch.rand(N, K, generator=g)) * torch.where(torch.rand(N, K, generator=g) < 0.5, -1.0, 1.0)   # one binade, both signs
-    stream, m = _roundtrip(_bits(w), epi, hd)
+    stream, m = _roundtrip(C.one_binade_both_signs(N, K), epi, hd)   # one binade, both signs
     assert m.n_wide == 0 and (m.table >> 31 == 0).all()
     # base = the block's largest exponent - 15: 127 for [1, 2), 128 where a value rounded up to 2.0 in bf16
     assert set(((m.table >> 23) & 0xFF).tolist()) <= {127 - 15, 128 - 15}
@@ -70,33 +60,20 @@ def test_all_narrow_matrix():
 
 def test_all_wide_matrix():
     N, K, epi, hd = SHAPES["5 pairs per tile"]
-    g = torch.Generator().manual_seed(2)
-    w = torch.randn(N, K, generator=g)
-    w[:, ::8] = 0.0                                       # an exact zero in every chunk
-    stream, m = _roundtrip(_bits(w), epi, hd)
+    stream, m = _roundtrip(C.all_wide(N, K), epi, hd)     # an exact zero in every chunk
     assert m.n_wide == m.n_blocks
     wide = m.table[m.table >> 31 == 1] & 0x7FFFFF
     assert np.array_equal(np.sort(wide), np.arange(m.n_blocks))    # numbered once each, in stream order
     assert np.array_equal(wide, np.sort(wide))
 
 
-FORCERS = {
-    "zero": 0x0000, "negative zero": 0x8000, "denormal": 0x0001, "2^-30": ((127 - 30) << 7), "+inf": 0x7F80, "-inf": 0xFF80,
-    "nan": 0x7FC1,
-}
-
-
 @pytest.mark.parametrize("what", list(FORCERS))
 @pytest.mark.parametrize("name", ["8 pairs per tile", "5 pairs per tile", "odd N head"])
 def test_one_value_forces_its_block_wide(what, name):
     N, K, epi, hd = SHAPES[name]
-    g = torch.Generator().manual_seed(3)
-    wb = _bits(1.0 + torch.rand(N, K, generator=g))       # every block narrow
     if name == "odd N head":
-        wb = wb[: N - 1]                                  # (even N here: the zero row of an odd N is its own forcer, below)
-        N -= 1
-    r, k = N // 3, 40
-    wb[r, k] = FORCERS[what]
+        N -= 1                                            # (even N here: the zero row of an odd N is its own forcer, below)
+    wb = C.forcer_case(N, K, what)                        # every block narrow but the one of (N // 3, 40)
     stream, m = _roundtrip(wb, epi, hd)
     assert m.n_wide == 1
     # the wide block is the one that holds (r, k): its 16 raw bytes per chunk come back, its neighbours alternate narrow
@@ -116,10 +93,7 @@ def test_odd_n_zero_row_is_wide_and_exact():
 
 def test_alternating_wide_and_narrow_blocks():
     N, K, epi, hd = 64, 512, w12.EPI_RESID, 0             # one pair per tile, 16 steps per tile
-    g = torch.Generator().manual_seed(5)
-    w = 1.0 + torch.rand(N, K, generator=g)
-    w[:, 0::64] = 0.0                                     # every other 32-k step of every row
-    stream, m = _roundtrip(_bits(w), epi, hd)
+    stream, m = _roundtrip(C.alternating(N, K), epi, hd)  # a zero in every other 32-k step of every row
     flags = (m.table >> 31).reshape(-1, K // 32)
     assert (flags[:, 0::2] == 1).all() and (flags[:, 1::2] == 0).all()
 

@@ -9,23 +9,9 @@ below-and-including it do, so a span of 16 is already wide there (the cases belo
 import numpy as np
 import pytest
 
+import w12_cases as C
 from specdec_hip import w12
-
-# (N, K, epi, head_dim): the six small geometries of the code form's format test
-SHAPES = {
-    "8 pairs per tile": (4096, 64, w12.EPI_RESID, 0),
-    "5 pairs per tile": (2560, 256, w12.EPI_RESID, 0),
-    "1 pair per tile": (64, 512, w12.EPI_RESID, 0),
-    "qkv pairs": (512, 64, w12.EPI_QKV_ROPE, 64),
-    "swiglu pairs, short last": (2 * 2051, 96, w12.EPI_SWIGLU, 0),
-    "odd N head": (1001, 64, w12.EPI_ARGMAX, 0),
-}
-
-
-def _bf16(x: np.ndarray) -> np.ndarray:
-    """float32 -> bf16 bits, round to nearest even (finite inputs)"""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+from w12_cases import FORCERS, SHAPES, SPLIT_SPANS, bf16 as _bf16, exps as _exps, one_binade as _one_binade
 
 
 def _roundtrip(wb, epi, head_dim):
@@ -44,30 +30,18 @@ def _roundtrip(wb, epi, head_dim):
     return stream, m
 
 
-def _one_binade(N, K, seed):
-    rng = np.random.default_rng(seed)
-    return _bf16((1.0 + 0.98 * rng.random((N, K))).astype(np.float32))    # [1, 1.98]: exponent 127 only, after rounding too
-
-
 # ---- one pair per tile (N = 64, K = 512): block (p, s) is rows 2p, 2p + 1 x columns 32 s .. 32 s + 31 --------------------------
 def _block_case(fill):
     """A [1, 2) matrix whose block (pair 3, step 5) is rewritten by fill(view of its 2 x 32 bits); returns (matrix, its entry)"""
     N, K, epi, hd = SHAPES["1 pair per tile"]
-    wb = _one_binade(N, K, 7)
-    fill(wb[6:8, 160:192])
+    wb, index = C.block_case(N, K, epi, hd, fill)
+    assert index == 3 * (K // 32) + 5
     stream, m = _roundtrip(wb, epi, hd)
     q = w12.geometry(N // 2, K)
     assert q.grid == 32 and q.tile_pairs == 1 and w12.n_tiles_full(q) == 1
     others = np.delete(m.table, 3 * (K // 32) + 5)
     assert (others >> 31 == 0).all()                                   # every other block: one binade, narrow
     return m, int(m.table[3 * (K // 32) + 5])
-
-
-def _exps(lo, hi):
-    """64 bf16 patterns whose exponents are lo..hi (every value present, both signs, varied mantissas)"""
-    e = np.resize(np.arange(lo, hi + 1), 64).astype(np.uint16)
-    i = np.arange(64, dtype=np.uint16)
-    return (((i & 1) << 15) | (e << 7) | ((i * 37) & 0x7F)).astype(np.uint16).reshape(2, 32)
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -80,8 +54,7 @@ def test_random_matrices_round_trip(name):
 
 def test_one_binade_with_both_signs_has_no_wide_block():
     N, K, epi, hd = SHAPES["8 pairs per tile"]
-    wb = _one_binade(N, K, 1)
-    wb[np.random.default_rng(2).random((N, K)) < 0.5] |= 0x8000
+    wb = C.one_binade_both_signs(N, K)
     assert np.unique((wb >> 7) & 0xFF).tolist() == [127] and np.unique(wb >> 15).tolist() == [0, 1]
     stream, m = _roundtrip(wb, epi, hd)
     assert m.n_wide == 0 and (m.table >> 31 == 0).all()
@@ -89,26 +62,23 @@ def test_one_binade_with_both_signs_has_no_wide_block():
     assert m.nbytes < 0.77 * stream.nbytes
 
 
-@pytest.mark.parametrize("emax, span, narrow", [
-    (127, 16, True), (127, 17, False),      # odd largest exponent: the window 112..127 ends at it
-    (128, 15, True), (128, 16, False), (128, 17, False),   # even: the window 114..129 reaches one past it, 15 values fit below
-])
+def test_the_span_cases_are_the_window_edges():
+    # odd largest exponent: the window 112..127 ends at it; even: the window 114..129 reaches one past it, 15 values fit below
+    assert SPLIT_SPANS == [(127, 16, True), (127, 17, False), (128, 15, True), (128, 16, False), (128, 17, False)]
+    assert np.array_equal(np.unique((_exps(112, 127) >> 7) & 0xFF), np.arange(112, 128))
+
+
+@pytest.mark.parametrize("emax, span, narrow", SPLIT_SPANS)
 def test_exponent_span_against_the_even_aligned_window(emax, span, narrow):
-    def fill(b):
-        b[:] = _exps(emax - span + 1, emax)
-    m, ent = _block_case(fill)
+    m, ent = _block_case(C.fill_span(emax, span))
     assert (ent >> 31 == 0) == narrow and m.n_wide == (0 if narrow else 1)
     if narrow:
         assert (ent >> 23) & 0xFF == (emax >> 1) - 7
 
 
 def test_all_eight_offsets_and_both_signs_in_one_lane():
-    lane = np.array([(s << 15) | ((112 + 2 * o + (o & 1)) << 7) | (0x55 ^ o) for o, s in zip(range(8), [0, 1, 0, 1, 1, 0, 1, 0])], dtype=np.uint16)
-
-    def fill(b):
-        b[:] = (127 << 7) | 0x11
-        b[1, 8:16] = lane
-    m, ent = _block_case(fill)
+    lane = C.OFFSETS_LANE
+    m, ent = _block_case(C.fill_offsets)
     assert ent >> 31 == 0 and (ent >> 23) & 0xFF == 56
     codes = w12.encode_split(lane[None], 56)[0, 8:]
     nib = np.concatenate([codes & 0xF, codes >> 4])
@@ -116,40 +86,24 @@ def test_all_eight_offsets_and_both_signs_in_one_lane():
 
 
 def test_base_is_clamped_at_zero():
-    def fill(b):
-        b[:] = _exps(0, 15)              # zeros' and denormals' exponent 0 up to 15: h = 0..7, base 0
-        b[0, 0], b[0, 1], b[0, 2] = 0x0000, 0x8000, 0x0001
-    m, ent = _block_case(fill)
+    m, ent = _block_case(C.fill_base0)   # zeros' and denormals' exponent 0 up to 15: h = 0..7, base 0
     assert ent == 0                      # narrow, base 0: no value is special, only the span decides
-    def fill_wide(b):
-        b[:] = _exps(0, 16)
-    m, ent = _block_case(fill_wide)
+    m, ent = _block_case(C.fill_base0_wide)
     assert ent >> 31 == 1
 
 
 def test_exponents_254_and_255_inside_a_fitting_window():
-    def fill(b):
-        b[:] = _exps(240, 255)           # inf and nan patterns among huge values: h = 120..127
-        b[0, 0], b[0, 1], b[1, 2] = 0x7F80, 0xFF80, 0x7FC1
-    m, ent = _block_case(fill)
+    m, ent = _block_case(C.fill_254_255)   # inf and nan patterns among huge values: h = 120..127
     assert ent >> 31 == 0 and (ent >> 23) & 0xFF == 120
-
-
-FORCERS = {
-    "zero": 0x0000, "negative zero": 0x8000, "denormal": 0x0001, "2^-30": ((127 - 30) << 7), "+inf": 0x7F80, "-inf": 0xFF80,
-    "nan": 0x7FC1,
-}
 
 
 @pytest.mark.parametrize("what", list(FORCERS))
 @pytest.mark.parametrize("name", ["8 pairs per tile", "5 pairs per tile", "odd N head"])
 def test_one_value_forces_exactly_one_block_wide(what, name):
     N, K, epi, hd = SHAPES[name]
-    wb = _one_binade(N, K, 3)
     if name == "odd N head":
-        wb = wb[: N - 1]                 # (even N here: the zero row of an odd N is a forcer of its own, below)
-        N -= 1
-    wb[N // 3, 40] = FORCERS[what]
+        N -= 1                           # (even N here: the zero row of an odd N is a forcer of its own, below)
+    wb = C.forcer_case(N, K, what)
     stream, m = _roundtrip(wb, epi, hd)
     assert m.n_wide == 1
     idx, base, narrow = w12.block_classes(stream, (N + 1) // 2, K, w12.W12_SPLIT)
@@ -164,8 +118,7 @@ def test_odd_n_zero_row_is_wide_and_exact():
 
 def test_alternating_wide_and_narrow_blocks_along_k():
     N, K, epi, hd = SHAPES["1 pair per tile"]
-    wb = _one_binade(N, K, 5)
-    wb[:, 0::64] = 0
+    wb = C.alternating(N, K)
     stream, m = _roundtrip(wb, epi, hd)
     flags = (m.table >> 31).reshape(-1, K // 32)
     assert (flags[:, 0::2] == 1).all() and (flags[:, 1::2] == 0).all()
