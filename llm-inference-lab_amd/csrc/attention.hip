@@ -65,9 +65,9 @@ static void launch_attention_d(const AttnArgs& a, int waves, dim3 grid, hipStrea
   // contexts, 5.48 vs 5.40 at 512 keys: the pass is not bound by its memory round trip)
 }
 
-size_t attention_split_ws_bytes(int head_dim) {
-  return static_cast<size_t>(kAttnSplitSlots) * kAttnRows * (head_dim + 2) * sizeof(float) + static_cast<size_t>(kAttnSplitSlots) * sizeof(unsigned);
-}
+// the split-KV workspace: kAttnSplitSlots partial tiles (O[16][D], max[16], sum[16] in fp32), then one arrival counter per slot
+size_t attention_split_tiles_bytes(int head_dim) { return static_cast<size_t>(kAttnSplitSlots) * kAttnRows * (head_dim + 2) * sizeof(float); }
+size_t attention_split_ws_bytes(int head_dim) { return attention_split_tiles_bytes(head_dim) + static_cast<size_t>(kAttnSplitSlots) * sizeof(unsigned); }
 
 int launch_attention(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;

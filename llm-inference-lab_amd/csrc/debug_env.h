@@ -7,7 +7,7 @@
 namespace sd {
 namespace debug_env {
 
-// ---- persistent forward (csrc/persist.hip, engine.hip; the loop's two: spec_loop.hip) -------------------------------------
+// ---- persistent forward (csrc/persist.hip, model.hip; the loop's two: spec_loop.hip) --------------------------------------
 constexpr const char* kNoPersist = "SPECDEC_NO_PERSIST";            // set: no model is eligible (every pass on the launch path). For a
                                                                      // GPU shared with other processes: the launch needs all 256 CUs.
 constexpr const char* kPersistMaxT = "SPECDEC_PERSIST_MAX_T";       // tokens per persistent pass at bind time (default 2 for d_model <= 2048, else 0)
@@ -24,7 +24,7 @@ constexpr const char* kPrefillMinTokens = "SPECDEC_PREFILL_MIN_TOKENS";   // sho
 constexpr const char* kGemvGeneric = "SPECDEC_GEMV_GENERIC";         // set: gemv.hip never takes a fixed-geometry instance (read at every launch; A/B runs, tests of both paths)
 constexpr const char* kNoW12 = "SPECDEC_NO_W12";                    // set: gemv.hip streams the packed bf16 weights even where the model has a W12 copy (read at every launch; A/B runs, tests)
 constexpr const char* kMedusaPerHead = "SPECDEC_MEDUSA_PER_HEAD";   // Medusa heads: one launch per head even when they sit at a constant stride
-// ---- measurement hooks (sd_model_probe_gemv) --------------------------------------------------------------------------------
+// ---- measurement hooks (sd_model_probe_gemv, csrc/probe.hip) ----------------------------------------------------------------
 constexpr const char* kGemvTimeline = "SPECDEC_GEMV_TIMELINE";      // in-kernel 100 MHz stamps of the probed launch, printed to stderr ("2": per workgroup too)
 constexpr const char* kProbeHot = "SPECDEC_PROBE_HOT";              // cycle over n layers only (1: cache-resident weights)
 constexpr const char* kProbeNoXstat = "SPECDEC_PROBE_NO_XSTAT";     // probed launches compute their own row statistics

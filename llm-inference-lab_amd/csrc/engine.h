@@ -1,5 +1,6 @@
-// Engine-internal types: model instance (csrc/engine.hip) and the device-side state of the
-// draft-then-verify loop (csrc/spec_loop.hip). The C-ABI view of these is in include/specdec_hip.h.
+// Engine-internal types: the model instance (created and bound in csrc/model.hip, run by csrc/engine.hip, measured and read back
+// by csrc/probe.hip) and the device-side state of the draft-then-verify loop (csrc/spec_loop.hip). The C-ABI view of these is in
+// include/specdec_hip.h.
 #pragma once
 
 #include <vector>
@@ -74,13 +75,31 @@ struct sd_model {
 
 namespace sd {
 
-// csrc/engine.hip: what the step loop (csrc/spec_loop.hip) needs from the model
+// csrc/engine.hip: what the step loop (csrc/spec_loop.hip), the binds (csrc/model.hip) and the probes (csrc/probe.hip) need from
+// the forward
 constexpr int kMaxPartials = 512;
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are indexed from row0
 int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base, int pos_off, int row0, int B, int M,
                   int32_t* ids_out, int ids_stride, void* logits_out, int logits_dtype, int skip_head, hipStream_t st);
 GemvArgs matrix_args(const sd_model* m, int index);
+// What belongs to the call, on top of matrix_args: the pass's tokens, and with pos_base the rows' positions, the head geometry and
+// the cache paging (bt: the pass's first row of the block table, null on dense KV). gated: the launch leaves at entry when the
+// adaptive step's word says so (m->skip_k / skip_i), as every launch of a forward pass does.
+void call_args(GemvArgs& g, const sd_model* m, int T, int M, bool gated, const int32_t* pos_base = nullptr, int pos_off = 0,
+               const int32_t* bt = nullptr);
 bool persist_pass_ok(const sd_model* m, int T, int Bc, int Mc);
+
+// The four row buffers a pass stages, by the `which` of sd_model_debug_rows / sd_model_prefill_rows, and the elements in a row of each
+struct StagedRows {
+  uint16_t* buf[4];   // 0 x, 1 q, 2 attn, 3 act
+  int width[4];       // d_model, Hq * D, Hq * D, d_ff
+};
+inline StagedRows staged_rows(const sd_model_config& c, uint16_t* x, uint16_t* q, uint16_t* attn, uint16_t* act) {
+  return {{x, q, attn, act}, {c.d_model, c.n_heads * c.head_dim, c.n_heads * c.head_dim, c.d_ff}};
+}
+inline StagedRows staged_rows(const sd_model* m) { return staged_rows(m->cfg, m->x, m->q, m->attn, m->act); }
+inline StagedRows staged_rows(const sd_model_config& c, const PrefillRows& r) { return staged_rows(c, r.x, r.q, r.attn, r.act); }
 
 // device-resident loop state (all int32, B rows, K draft tokens per step)
 struct SpecState {

@@ -208,6 +208,7 @@ struct AttnArgs {
 int launch_attention(const AttnArgs& a, hipStream_t st);
 constexpr int kAttnSplitSlots = 1024;   // partial tiles of the split-KV workspace
 size_t attention_split_ws_bytes(int head_dim);   // workspace for kAttnSplitSlots partial tiles (+ counters)
+size_t attention_split_tiles_bytes(int head_dim);   // the partial tiles of it (split_ws); the kAttnSplitSlots counters (split_cnt) follow
 
 // ---- small kernels (misc.hip) -------------------------------------------------------
 struct EmbedArgs {

@@ -1,5 +1,5 @@
 // Persistent decode forward (csrc/persist.hip): ONE launch per forward for passes of <= kPersistMaxT tokens.
-// Internal interface between the engine (engine.hip) and the kernel; not part of the C-ABI.
+// Internal interface between the engine (the forward: engine.hip; the workspace and op table: model.hip) and the kernel; not part of the C-ABI.
 #pragma once
 
 #include "kernels.h"
@@ -72,9 +72,15 @@ struct PersistArgs {
   unsigned long long* debug_ts;   // optional [256][4 * n_ops + n_ops] 100 MHz stamps
 };
 
-// bytes of workspace the persistent path needs for a model of these dimensions (granules + op table + sync words)
-size_t persist_workspace_bytes(const sd_model_config& c);
+// The workspace the persistent path needs for a model of these dimensions: byte offsets of the sync words, the op table and the
+// granule buffers (two parities of gran_parity 8-byte granules each), and the bytes of it all
+struct PersistWorkspace {
+  size_t sync, ops, gran, bytes;
+  unsigned gran_parity;
+};
+PersistWorkspace persist_workspace(const sd_model_config& c);
 constexpr unsigned kGranUnitMax = 528;   // storage granules per 16-granule unit the buffers are sized for
+static_assert(kGranUnitMax % 16 == 0, "a parity is whole 128-byte units: the two parities fill the granule region without padding");
 // static eligibility of a model (architecture, dtype, shapes); T-dependent limits are checked per pass
 bool persist_model_ok(const sd_model_config& c, bool packed, bool w8, int n_cus);
 // cache rows the attention of the persistent launch can walk (16-byte V^T vectors of 8 keys)

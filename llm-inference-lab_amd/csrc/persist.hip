@@ -1408,11 +1408,11 @@ static size_t persist_gran_parity(const sd_model_config& c) {
   return edge_storage(per_tok, kGranUnitMax) + 5 * kGranUnitMax;
 }
 
-size_t persist_workspace_bytes(const sd_model_config& c) {
-  size_t n = 256;                                                           // sync words
-  n += (static_cast<size_t>(4 * c.n_layers + 1) * sizeof(PersistOp) + 255) & ~static_cast<size_t>(255);
-  n += (2 * persist_gran_parity(c) * 8 + 255) & ~static_cast<size_t>(255);
-  return n;
+PersistWorkspace persist_workspace(const sd_model_config& c) {
+  PersistWorkspace w{0, 256, 0, 0, static_cast<unsigned>(persist_gran_parity(c))};   // 256 bytes of sync words, then the op table
+  w.gran = w.ops + ((static_cast<size_t>(4 * c.n_layers + 1) * sizeof(PersistOp) + 255) & ~static_cast<size_t>(255));
+  w.bytes = w.gran + ((2 * persist_gran_parity(c) * 8 + 255) & ~static_cast<size_t>(255));
+  return w;
 }
 
 template <int D, int HC, bool STAMPS, bool SEL, bool TAPS>

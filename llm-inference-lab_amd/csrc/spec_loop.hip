@@ -2,7 +2,7 @@
 //
 // Host-side C++ only. One step proposes K tokens (a draft model, EAGLE-lite rows, the target's own next token, or Medusa
 // heads), verifies them in one target forward and advances the loop state — all enqueued on caller-provided HIP streams
-// through the model forwards of csrc/engine.hip, never synchronising, and graph-capturable: all per-row dynamic quantities
+// through the model forwards of csrc/engine.hip (models made and bound by csrc/model.hip), never synchronising, and graph-capturable: all per-row dynamic quantities
 // (lengths, tokens) live in device memory and are read by the kernels. Which launches a step consists of is decided once per
 // enqueue by plan_step; enqueue_step and its pieces only follow the plan.
 //

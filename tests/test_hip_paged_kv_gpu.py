@@ -90,6 +90,37 @@ def test_paged_long_context_split_kv(monkeypatch):
     assert torch.equal(i_d, i_p) and torch.equal(l_d, l_p)
 
 
+def test_one_model_rebound_dense_paged_dense():
+    """One model instance bound dense, then paged (page_len 32), then dense again: every bind leaves the same fresh state (prompt
+    route AUTO, counts 0, no GEMM-prefill chunk on record, the same persistent-token default) and the same workspace carve, so a
+    3-token forward from empty caches gives bit-identical ids and bf16 logits on the first and third bind, and the paged ids equal
+    the dense ones. The shape is the persist plan tests' toy Llama (the smallest the persistent region is carved for)."""
+    from specdec_hip import weights as W
+    from specdec_hip.engine import HipModel
+
+    cfg = W.ModelConfig(arch=W.ARCH_LLAMA, n_layers=1, d_model=256, n_heads=4, n_kv_heads=2, head_dim=64, d_ff=512, vocab=512,
+                        max_pos=512, rope_theta=500000.0, tie_embeddings=False, name="rebind-toy")
+    m = HipModel(W.synthetic_llama(cfg, seed=11, device="cuda"), batch=1, l_max=64)
+    toks = synthetic_prompts(1, 3, cfg.vocab, seed=3).to(torch.int32).cuda()
+    z = torch.zeros(1, dtype=torch.int32, device="cuda")
+    runs = []
+    for kind in ("dense", "paged", "dense"):
+        if kind == "paged":
+            m._bind_paged(32, None)
+        elif runs:
+            m.page_len = None
+            m._bind_dense()
+        assert (m.page_len is not None) == (kind == "paged")
+        assert m.prefill_backend == "auto" and m.prefill_counts() == {"passes": 0, "rocblas": 0, "native": 0}
+        with pytest.raises(RuntimeError, match="no GEMM-prefill chunk on record"):
+            m.prefill_rows(0, 0, 1)
+        ids, logits = m.forward(toks, z, 0, want_logits=True, logits_dtype=torch.bfloat16)
+        runs.append((ids.cpu(), logits.cpu(), m.persist_tokens))
+    (i0, l0, p0), (i1, _, _), (i2, l2, p2) = runs
+    assert torch.equal(i0, i2) and torch.equal(l0.view(torch.int16), l2.view(torch.int16)) and p0 == p2
+    assert torch.equal(i1, i0)
+
+
 def test_pool_accounting_and_exhaustion():
     _, tgt = tiny_pair()
     _, paged = _engines(tgt, 2, 256, 32, n_pages=5)

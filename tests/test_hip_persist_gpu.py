@@ -281,7 +281,7 @@ def test_a_launch_that_cannot_complete_gives_up_and_reports(monkeypatch):
 
 
 def test_default_follows_model_width_and_cache_length(monkeypatch):
-    """sd_model_bind's default (engine.hip carve_workspace, by measurement): two tokens per persistent pass for d_model <= 2048, off for
+    """sd_model_bind's default (model.hip setup_persist, by measurement): two tokens per persistent pass for d_model <= 2048, off for
     wider models; whether a pass takes the persistent launch then follows the caller's bound on the rows' CURRENT length (1280
     positions: one CU walks a head's whole cache, past that the launch path's split-KV attention wins); SPECDEC_PERSIST_MAX_T
     overrides both."""
