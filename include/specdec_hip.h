@@ -118,6 +118,24 @@ int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_lo
                                  const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
                                  double* ratios_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Lossy acceptance on the verify pass's logits (csrc/typical_accept.hip): a draft token is kept when the target finds it plausible
+ * enough. target_logits: [B][K+1] rows of V elements (f32 / bf16 / f16), row_stride elements apart (>= V), row (b, i) = row
+ * b * (K + 1) + i: the target's distribution after d_1..d_i, where d_{i+1} = draft_ids[b][i] was proposed (row K is not read).
+ * Per row, one pass in fp32 with z = logit / T: H = log S - W / S over S = sum e^{z - m}, W = sum (z - m) e^{z - m} (a -inf element
+ * adds exactly 0 to both), p_d = e^{z_d - m} / S (0 for a -inf logit) and rank_d = #{v : z_v > z_d, or z_v == z_d and v < d}.
+ *   rule SD_ACCEPT_TYPICAL     keep d iff p_d >= min(epsilon, delta * exp(-H)); delta = +inf: the fixed threshold epsilon
+ *   rule SD_ACCEPT_TOPK_AGREE  keep d iff rank_d < agree_k (agree_k = 1: d is the row's argmax, ties to the lower index)
+ * accept_len[b] = the number of leading kept positions. A draft id outside [0, V) and a row holding NaN or +inf are rejected.
+ * stats (nullable, float [B][K][4]): p_d, H, the threshold (rule 2: agree_k), rank_d of every position. Bit-identical run to run.
+ * workspace: sd_typical_accept_workspace(B, K, V) bytes of device scratch, 4-byte aligned. Asynchronous on `stream`, no allocation,
+ * graph-capturable. Refused (nonzero + sd_last_error, before any device work): an unknown rule, temperature not > 0, epsilon outside
+ * (0, 1], delta <= 0 or NaN (rule 1), agree_k outside 1..V (rule 2), K outside 1..63, a NULL pointer, a short workspace. */
+enum sd_accept_rule { SD_ACCEPT_OFF = 0, SD_ACCEPT_TYPICAL = 1, SD_ACCEPT_TOPK_AGREE = 2 };
+size_t sd_typical_accept_workspace(int B, int K, int V);
+int sd_typical_accept(const void* target_logits, int logits_dtype, int64_t row_stride, const int32_t* draft_ids, int B, int K, int V,
+                      int rule, float temperature, float epsilon, float delta, int agree_k, int32_t* accept_len, float* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Draft-target agreement of two logit blocks (csrc/spec_agree.hip): how much of the target's distribution a draft reproduces,
  * position by position, without generating. draft_logits / target_logits: bf16, n rows of V elements, rows ld_q / ld_p
  * elements apart (>= V). Per row t, in float64 over the stored bf16 values, x / T as sd_spec_sample_accept forms it (T the
@@ -852,6 +870,23 @@ int sd_logit_process_rows(void* rows, int64_t row_stride, int B, int R, int V, c
  * without a table is launch for launch what it was. Either call drops the captured graph. Refused: a misaligned table; a
  * table while neither a sampling mode nor the logit-processor stage is on. Additive (SD_ABI_VERSION stays 1). */
 int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling* table);
+
+/* Lossy acceptance inside the step (sd_typical_accept's rules on the verify forward's own rows). With rule SD_ACCEPT_TYPICAL or
+ * SD_ACCEPT_TOPK_AGREE the verify forward stores its [B][K+1][V] logits, the logit-processor stage (if on) processes them in
+ * place — so bans and grammars count — and sd_typical_accept's two launches replace the exact-match accept scan: the step emits
+ * the draft's ids d_1..d_a, then one token of the target's: its (processed) argmax at position a, or, with the sampled-bonus
+ * mode on, the draw sd_specdec_set_sampling configured from row a. The draft loop is unchanged (greedy draft tokens). In the step,
+ * rank_d breaks ties among equal STORED values in favour of the forward's own argmax (computed before the row was rounded to bf16),
+ * then of the lower index: SD_ACCEPT_TOPK_AGREE with agree_k = 1 is exactly the step's exact-match rule.
+ * logits_buf: caller-owned [B][K+1][V] bf16, 16-byte aligned, used while the sampled-bonus mode is off (that mode's own buffer
+ * is used while it is on; logits_buf may then be NULL). rule SD_ACCEPT_OFF (the default): the step is launch for launch what it
+ * is without this call. Switching the rule on or off drops the captured graph. Refused: what sd_typical_accept refuses about
+ * the parameters; a short or misaligned buffer; the draft-emit mode; speculative sampling; per-row adaptive K; EAGLE, Medusa
+ * heads and the tied self-draft (loops without a draft model); a bound row-sampling table. While a rule is on,
+ * sd_specdec_set_spec_sampling, sd_specdec_set_adaptive and a non-NULL sd_specdec_set_row_sampling are refused.
+ * Additive (SD_ABI_VERSION stays 1). */
+int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperature, float epsilon, float delta, int agree_k, void* logits_buf,
+                              size_t logits_bytes);
 
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,

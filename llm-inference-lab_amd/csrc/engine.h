@@ -165,6 +165,13 @@ int launch_spec_step(const SpecState& s, const void* target_logits, const void* 
                      float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st,
                      const sd_row_sampling* table = nullptr);
 
+// csrc/typical_accept.hip: lossy acceptance (typical / top-k agreement) on the stored verify rows. workspace:
+// typical_accept_workspace(B, K) bytes; next_from_ids: s.sampled[b] = target_ids[b][accept_len[b]] (no sampled bonus follows)
+int check_typical_params(const char* who, int rule, float temperature, float epsilon, float delta, int agree_k, int K, int V);
+size_t typical_accept_workspace(int B, int K);
+int launch_typical_step(const SpecState& s, const void* logits, int V, int rule, float temperature, float epsilon, float delta,
+                        int agree_k, bool next_from_ids, void* workspace, hipStream_t st);
+
 // csrc/grammar.hip: token automata (grammar-constrained decoding). next: uint16 [S][V], 0xFFFF = the token is not allowed in the
 // state; allow: the same as one bit per token, uint32 [S][ceil(V / 32)]. A row's state: -1 unconstrained, 0..S-1, else DEAD
 // (only eos is allowed; kept as kFsmDead).

@@ -72,6 +72,12 @@ struct sd_specdec {
   int fsm = 0;
   sd::FsmBind fsm_bind{};          // pos: [B][K+1], the loop's own (allocated at first use)
   int32_t* fsm_pos = nullptr;
+  // lossy acceptance (sd_specdec_set_acceptance): the rule judges the stored verify rows in place of the exact-match scan
+  int acc_rule = 0;                // sd_accept_rule; 0 = off
+  float acc_temperature = 1.0f, acc_epsilon = 1.0f, acc_delta = 1.0f;
+  int acc_agree_k = 1;
+  void* acc_logits = nullptr;      // [B][K+1][V] bf16, caller-owned; used while the sampled-bonus mode does not lend its own
+  void* acc_ws = nullptr;          // flags and records of the two launches (the loop's own, allocated at first use)
   // per-row parameters (sd_specdec_set_row_sampling): device [B], caller-owned, read by the kernels at run time
   const sd_row_sampling* row_table = nullptr;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
@@ -195,7 +201,8 @@ static int enqueue_medusa_heads(sd_specdec* s, hipStream_t st) {
 
 // ---- one plan per enqueue: every decision of a step, made once from the loop's modes (no HIP call, no write)
 enum Proposer { PROPOSE_DRAFT, PROPOSE_EAGLE, PROPOSE_SELF, PROPOSE_HEADS };   // draft model / EAGLE-lite / tied self-draft / Medusa heads alone
-enum Select { SELECT_GREEDY, SELECT_SAMPLED_BONUS, SELECT_SPEC };              // how the emitted tokens are chosen
+// how the emitted tokens are chosen; SELECT_TYPICAL: the draft's ids while the rule keeps them, then the target's argmax or draw
+enum Select { SELECT_GREEDY, SELECT_SAMPLED_BONUS, SELECT_SPEC, SELECT_TYPICAL };
 enum Handover { HAND_FINALIZE, HAND_NEXT, HAND_DRAW };                         // how d_{i+1} leaves draft forward i
 
 struct StepPlan {
@@ -230,7 +237,7 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   StepPlan p{};
   p.proposer = s.draft ? PROPOSE_DRAFT : (s.eagle ? PROPOSE_EAGLE : (s.heads.empty() ? PROPOSE_SELF : PROPOSE_HEADS));
   p.heads = !s.heads.empty();
-  p.select = s.sample ? SELECT_SAMPLED_BONUS : (s.spec ? SELECT_SPEC : SELECT_GREEDY);   // (the setters keep the two apart)
+  p.select = s.acc_rule ? SELECT_TYPICAL : (s.sample ? SELECT_SAMPLED_BONUS : (s.spec ? SELECT_SPEC : SELECT_GREEDY));   // (the setters keep them apart)
   const bool spec = p.select == SELECT_SPEC;
   p.shaped = spec && s.spec_top_k > 0;
   p.rows = s.row_table != nullptr;
@@ -241,6 +248,7 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   p.hand = spec ? HAND_DRAW : ((!p.lp && p.one_pass_d) ? HAND_FINALIZE : HAND_NEXT);
   p.tail = p.select == SELECT_GREEDY && !p.lp && verify_tail_fits(s.st) && s.B * (s.K + 1) <= s.target->max_t;
   if (p.select == SELECT_SAMPLED_BONUS) p.p_buf = s.logits;
+  else if (p.select == SELECT_TYPICAL) p.p_buf = s.sample ? s.logits : s.acc_logits;
   else if (spec) p.p_buf = s.spec_p;
   else if (p.lp) p.p_buf = s.lp_logits;
   p.q_pass = (spec || p.lp) ? static_cast<uint16_t*>(p.p_buf) : nullptr;
@@ -376,13 +384,21 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
       // accept length -> draw the token after the accepted prefix from the stored logits of that position
       if (int rc = launch_accept_len(s->st, st_t)) return rc;
       if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t, table)) return rc;
+    } else if (p.select == SELECT_TYPICAL) {
+      // the rule on every stored (processed) row -> accept length; the token after the accepted prefix is the target's id of that
+      // position, or drawn from its row when the sampled-bonus mode is on
+      if (int rc = launch_typical_step(s->st, p.p_buf, V, s->acc_rule, s->acc_temperature, s->acc_epsilon, s->acc_delta, s->acc_agree_k,
+                                       !s->sample, s->acc_ws, st_t))
+        return rc;
+      if (s->sample)
+        if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t, table)) return rc;
     } else if (p.select == SELECT_SPEC) {
       // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
       if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p, s->seed,
                                     s->draw, s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t, table))
         return rc;
     }
-    const int use_sampled = p.select == SELECT_SPEC ? 2 : (p.select == SELECT_SAMPLED_BONUS ? 1 : 0);
+    const int use_sampled = (p.select == SELECT_SPEC || p.select == SELECT_TYPICAL) ? 2 : (p.select == SELECT_SAMPLED_BONUS ? 1 : 0);
     if (int rc = launch_accept(s->st, s->mode, use_sampled, st_t)) return rc;
     if (p.lp)   // the emitted tokens of every active row enter its counts
       if (int rc = launch_logit_counts_add(s->lp_counts, B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
@@ -403,6 +419,8 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
     SD_HIP_CHECK(hipEventRecord(s->ev_fork, st_t));
     SD_HIP_CHECK(hipStreamWaitEvent(st_d, s->ev_fork, 0));
   }
+  SD_REQUIRE(p.select != SELECT_TYPICAL || (s->draft && p.p_buf && s->acc_ws),
+             "specdec_step: the acceptance rule needs a draft model and a logits buffer (sd_specdec_set_acceptance)");
   SD_REQUIRE(!p.lp || (s->draft && p.p_buf), "specdec_step: logit processors need a draft model and a logits buffer (sd_specdec_set_logit_processors)");
   if (p.proposer == PROPOSE_DRAFT)
     if (int rc = enqueue_draft(s, p, st_d)) return rc;
@@ -516,6 +534,7 @@ extern "C" int sd_specdec_destroy(sd_specdec* s) {
   if (s->head_rows) (void)hipFree(s->head_rows);
   if (s->spec_flags) (void)hipFree(s->spec_flags);
   if (s->fsm_pos) (void)hipFree(s->fsm_pos);
+  if (s->acc_ws) (void)hipFree(s->acc_ws);
   delete s;
   return 0;
 }
@@ -567,6 +586,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(s->heads.empty() && !s->eagle, "specdec_set_adaptive: stateful draft modes keep a fixed K");
   SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
   SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
+  SD_REQUIRE(!s->acc_rule, "specdec_set_adaptive: the acceptance rule keeps a fixed K (disable sd_specdec_set_acceptance first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -648,6 +668,7 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_spec_sampling: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
   SD_REQUIRE(s->draft, "specdec_set_spec_sampling: needs a draft model (self-draft, Medusa heads and EAGLE loops propose without a distribution q)");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_spec_sampling: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->acc_rule, "specdec_set_spec_sampling: an acceptance rule is on (sd_specdec_set_acceptance); speculative sampling has its own");
   SD_REQUIRE(!s->sample, "specdec_set_spec_sampling: the sampled-bonus mode is enabled (sd_specdec_set_sampling); the two modes are mutually exclusive");
   SD_REQUIRE(temperature == temperature && temperature > 0.f, "specdec_set_spec_sampling: temperature %g (must be > 0)", temperature);
   SD_REQUIRE(draft_logits_buf && target_logits_buf && draw_counters, "specdec_set_spec_sampling: NULL logits buffer / draw counters");
@@ -759,11 +780,45 @@ extern "C" int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling*
   SD_REQUIRE(s, "specdec_set_row_sampling: NULL");
   if (table) {
     SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "specdec_set_row_sampling: the row table must be 16-byte aligned");
+    SD_REQUIRE(!s->acc_rule, "specdec_set_row_sampling: an acceptance rule is on (sd_specdec_set_acceptance): its parameters are the loop's, not a row's");
     SD_REQUIRE(s->sample || s->spec || s->lp, "specdec_set_row_sampling: neither a sampling mode nor the logit-processor stage is on "
                "(sd_specdec_set_sampling / sd_specdec_set_spec_sampling / sd_specdec_set_logit_processors first)");
   }
   drop_graph(s);   // unconditional: the captured step holds either the scalar launches or the row launches
   s->row_table = table;
+  return 0;
+}
+
+extern "C" int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperature, float epsilon, float delta, int agree_k,
+                                         void* logits_buf, size_t logits_bytes) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_acceptance: NULL");
+  if (rule == SD_ACCEPT_OFF) {
+    if (s->acc_rule) drop_graph(s);   // only if a rule was on: otherwise the captured step holds none of it
+    s->acc_rule = 0;
+    return 0;
+  }
+  const int V = s->target->cfg.vocab;
+  if (int rc = check_typical_params("specdec_set_acceptance", rule, temperature, epsilon, delta, agree_k, s->K, V)) return rc;
+  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_acceptance: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
+  SD_REQUIRE(!s->eagle, "specdec_set_acceptance: EAGLE loops are not supported (the rule judges a draft model's proposals)");
+  SD_REQUIRE(s->heads.empty(), "specdec_set_acceptance: Medusa heads are not supported (the rule judges a draft model's proposals)");
+  SD_REQUIRE(s->draft, "specdec_set_acceptance: the tied self-draft is not supported (the rule judges a draft model's proposals)");
+  SD_REQUIRE(!s->spec, "specdec_set_acceptance: speculative sampling is enabled (sd_specdec_set_spec_sampling); it has its own acceptance rule");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_acceptance: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->row_table, "specdec_set_acceptance: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
+  SD_REQUIRE(logits_buf || s->sample, "specdec_set_acceptance: NULL logits buffer (the sampled-bonus mode is not on to lend its own)");
+  const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
+  SD_REQUIRE(!logits_buf || logits_bytes >= need, "specdec_set_acceptance: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(logits_buf) & 15) == 0, "specdec_set_acceptance: the logits buffer must be 16-byte aligned");
+  if (!s->acc_ws) SD_HIP_CHECK(hipMalloc(&s->acc_ws, typical_accept_workspace(s->B, s->K)));
+  drop_graph(s);   // the captured step holds the exact-match launches, or this rule's parameters
+  s->acc_rule = rule;
+  s->acc_temperature = temperature;
+  s->acc_epsilon = epsilon;
+  s->acc_delta = delta;
+  s->acc_agree_k = agree_k;
+  s->acc_logits = logits_buf;
   return 0;
 }
 

@@ -26,6 +26,9 @@ SD_F32, SD_F16, SD_BF16, SD_I32, SD_I64, SD_U8, SD_FP8_E4M3 = range(7)
 SD_ABI_VERSION = 1
 # enum sd_prefill_backend
 SD_PREFILL_AUTO, SD_PREFILL_PASSES, SD_PREFILL_ROCBLAS, SD_PREFILL_NATIVE = range(4)
+# enum sd_accept_rule
+SD_ACCEPT_OFF, SD_ACCEPT_TYPICAL, SD_ACCEPT_TOPK_AGREE = range(3)
+ACCEPT_RULES = {"typical": SD_ACCEPT_TYPICAL, "topk_agree": SD_ACCEPT_TOPK_AGREE}
 PREFILL_BACKENDS = {"auto": SD_PREFILL_AUTO, "passes": SD_PREFILL_PASSES, "rocblas": SD_PREFILL_ROCBLAS, "native": SD_PREFILL_NATIVE}
 
 _c_void_p = ctypes.c_void_p
@@ -58,6 +61,12 @@ SIGNATURES = {
         _c_int,
         [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_float, _c_int, ctypes.c_float, ctypes.c_uint64, _c_void_p,
          ctypes.c_uint32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
+    ),
+    "sd_typical_accept_workspace": (_c_size, [_c_int, _c_int, _c_int]),
+    "sd_typical_accept": (
+        _c_int,
+        [_c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int,
+         _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
     ),
     "sd_spec_agreement_workspace": (_c_size, [_c_int, _c_int]),
     "sd_spec_agreement": (
@@ -182,6 +191,7 @@ SIGNATURES = {
          _c_void_p, _c_int, _c_void_p, _c_size, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
     ),
     "sd_specdec_set_row_sampling": (_c_int, [_c_void_p, _c_void_p]),
+    "sd_specdec_set_acceptance": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_void_p, _c_size]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),

@@ -699,6 +699,7 @@ class HipSpecDec:
             self.stream_d = torch.cuda.Stream(self.device)
         # sampling modes (set_sampling / set_spec_sampling): off; their buffers are allocated at first use and kept
         self.sampling = self.spec_sampling = False
+        self.acceptance = None     # the lossy acceptance rule of set_acceptance ("typical" / "topk_agree"), None = exact match
         self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
         # per-row parameters (set_row_sampling): none; the table is allocated at first use and kept (rewritten in place)
@@ -870,6 +871,30 @@ class HipSpecDec:
                 b.numel() * 4 if b is not None else 0, self._logits.data_ptr(), self._logits.numel() * 2, self._lp_ws.data_ptr(),
                 self._lp_ws.numel()), "sd_specdec_set_logit_processors")
             self.logit_processors = True
+
+    def set_acceptance(self, rule: Optional[str], temperature: float = 1.0, epsilon: float = 0.09, delta: Optional[float] = 0.3,
+                       agree_k: int = 1) -> None:
+        """A lossy acceptance rule inside the step (sd_specdec_set_acceptance; None switches it off): "typical" keeps d_{i+1}
+        iff p_i(d) >= min(epsilon, delta * exp(-H(p_i))) at `temperature` (delta None: the fixed threshold), "topk_agree" iff
+        d is among the `agree_k` largest logits of row i — p_i being the target's distribution after d_1..d_i, the rows of the
+        verify forward (`step_logits`, after the logit-processor stage when that is on). The step emits the draft's ids while
+        the rule keeps them, then the target's argmax of the next position, or its draw when set_sampling is on."""
+        with torch.cuda.device(self.device):
+            if rule is None:
+                _abi.check(self.lib.sd_specdec_set_acceptance(self.handle, _abi.SD_ACCEPT_OFF, 1.0, 1.0, 1.0, 1, None, 0),
+                           "sd_specdec_set_acceptance")
+                self.acceptance = None
+                return
+            if rule not in _abi.ACCEPT_RULES:
+                raise ValueError(f"set_acceptance: rule {rule!r} (one of {sorted(_abi.ACCEPT_RULES)})")
+            V = self.target.weights.config.vocab
+            if self._logits is None:
+                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+                torch.cuda.current_stream(self.device).synchronize()
+            _abi.check(self.lib.sd_specdec_set_acceptance(
+                self.handle, _abi.ACCEPT_RULES[rule], float(temperature), float(epsilon), float("inf") if delta is None else float(delta),
+                int(agree_k), self._logits.data_ptr(), self._logits.numel() * 2), "sd_specdec_set_acceptance")
+            self.acceptance = rule
 
     def set_logit_counts_row(self, b: int, prompt_ids: Sequence[int], generated_ids: Sequence[int] = ()) -> None:
         """Row b's counts for a new sequence in its slot: the prompt bit of every prompt id, one count per generated id

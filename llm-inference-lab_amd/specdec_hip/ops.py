@@ -394,6 +394,57 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     return (accept, nxt, ratios) if return_ratios else (accept, nxt)
 
 
+def typical_accept_workspace(B: int, K: int, V: int, device) -> torch.Tensor:
+    """Scratch for typical_accept(..., workspace=): allocate once, reuse for every call of that shape or smaller."""
+    return torch.empty(max(_abi.load().sd_typical_accept_workspace(B, K, V), 4), dtype=torch.uint8, device=device)
+
+
+def typical_accept(target_logits: torch.Tensor, draft_ids: torch.Tensor, rule: str = "typical", temperature: float = 1.0,
+                   epsilon: float = 0.09, delta: Optional[float] = 0.3, agree_k: int = 1, return_stats: bool = False,
+                   out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None):
+    """Accept lengths of a lossy acceptance rule on the verify pass's logits (sd_typical_accept).
+
+    target_logits: [B, K+1, V] f32 / bf16 / f16 on the GPU, unit stride along V, rows at one stride (a view whose rows are
+    further apart than V is taken as it is); draft_ids int32 [B, K]. rule "typical": position i is kept iff
+    p_i(d) >= min(epsilon, delta * exp(-H(p_i))) at `temperature` (delta None: the fixed threshold epsilon); rule "topk_agree":
+    iff d is among the row's `agree_k` largest logits (ties to the lower index). Returns accept_len int32 [B] — the leading
+    kept positions — and with return_stats the float32 [B, K, 4] records (p_d, H, threshold, rank_d). `out`, `stats_out` and
+    `workspace` (typical_accept_workspace) make the call allocation-free, which is what a captured graph needs."""
+    lib = _abi.load()
+    dev = _require_device("typical_accept", target_logits, draft_ids)
+    if rule not in _abi.ACCEPT_RULES:
+        raise ValueError(f"typical_accept: rule {rule!r} (one of {sorted(_abi.ACCEPT_RULES)})")
+    if target_logits.dim() != 3 or draft_ids.dim() != 2:
+        raise ValueError("typical_accept: need target_logits [B,K+1,V] and draft_ids [B,K]")
+    B, K1, V = target_logits.shape
+    K = K1 - 1
+    if tuple(draft_ids.shape) != (B, K):
+        raise ValueError(f"typical_accept: shapes {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
+    if draft_ids.dtype != torch.int32:
+        raise TypeError("typical_accept: draft_ids must be int32")
+    if target_logits.stride(2) != 1 or target_logits.stride(0) != K1 * target_logits.stride(1):
+        target_logits = target_logits.contiguous()
+    draft_ids = draft_ids.contiguous()
+    if out is None:
+        out = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"typical_accept: out must be a contiguous int32 [{B}] tensor on {dev}")
+    stats = stats_out
+    if stats is None and return_stats:
+        stats = torch.full((B, max(K, 0), 4), float("nan"), dtype=torch.float32, device=dev)
+    if stats is not None and (stats.dtype != torch.float32 or tuple(stats.shape) != (B, K, 4) or not stats.is_contiguous() or stats.device != dev):
+        raise ValueError(f"typical_accept: stats_out must be a contiguous float32 [{B}][{K}][4] tensor on {dev}")
+    ws = workspace if workspace is not None else typical_accept_workspace(B, K, V, dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_typical_accept(target_logits.data_ptr(), sd_dtype(target_logits.dtype), target_logits.stride(1),
+                                         draft_ids.data_ptr(), B, K, V, _abi.ACCEPT_RULES[rule], float(temperature), float(epsilon),
+                                         float("inf") if delta is None else float(delta), int(agree_k), out.data_ptr(),
+                                         stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
+                                         _stream_ptr(dev)), "sd_typical_accept")
+    return (out, stats) if (return_stats or stats_out is not None) else out
+
+
 def _row_table(name: str, table, B: int, dev) -> torch.Tensor:
     """The device table of a _rows op: a list of SamplingParams is packed, a tensor (sampling_params.pack: uint8 [B][32]) is
     taken as it is."""

@@ -41,6 +41,7 @@ from ..policies.controllers import FixedKController, create_controller
 from ..policies.policies import create_policy
 from ..utils.deterministic import ensure_deterministic, set_deterministic_mode
 from ..utils.interfaces import LanguageModel
+from .acceptance import device_rule, session_rule
 from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
 PromptLike = Union[str, Sequence[int], torch.Tensor]
@@ -205,7 +206,10 @@ class SpeculativePipeline:
         self.rejection_backend = str((policy_params or {}).get("backend", "host"))
         if self.rejection_backend not in ("host", "device"):
             raise ValueError(f"policy_params['backend']={self.rejection_backend!r} (one of 'host', 'device')")
-        if self.rejection_backend == "device":
+        # policy="typical" / "topk_agree" with backend "device": the rule runs inside the captured step on the verify pass's own rows —
+        # the target's distribution after d_1..d_i, where the host loop scores the draft against the target's own continuation
+        self.accept_device = device_rule(policy, policy_params, self._fake, self.base_lm.vocab_size)
+        if self.rejection_backend == "device" and self.accept_device is None:
             if policy != "rejection":
                 raise ValueError("policy_params['backend']='device' belongs to policy='rejection'")
             if self._fake:
@@ -439,9 +443,11 @@ class SpeculativePipeline:
         sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated."""
         if sampling_params is not None and sampling is not None:
             raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
+        session_rule(self, StepOptions(), emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (its refusals come first)
         options = (StepOptions.from_sampling(sampling) if sampling_params is None else
                    row_options(self, sampling_params, len(prompts), 1, None, processors, self_draft))
         options = with_stage(self, options, processors, grammar, len(prompts))
+        options = session_rule(self, options, emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (a device acceptance rule)
         return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
@@ -909,6 +915,9 @@ class DecodeSession:
         if o.mode != "greedy" and emit_mode != HipSpecDec.EMIT_BONUS:
             raise ValueError("sampling is a generate_batch (bonus-token) feature")
         self._sampled, self._spec = o.mode != "greedy", o.mode == "spec"
+        # a device acceptance rule: the record's emitted tokens are taken as they are (the draft's ids, then the target's token), the way
+        # speculative sampling's are; a sampled token after them costs one draw per step and is never drawn again on the host
+        self._accept = o.accept_rule is not None
         # the processor stage (None: off) has a counts row, and the grammar (None: off) a state, per cache row: both are (re)written wherever
         # the row's device state is. What admit() rewrites — start states, per-request parameters, stream ids — is the session's own
         self.grammar, self.processors, self.self_draft = o.fsm, o.processors, self_draft
@@ -971,7 +980,7 @@ class DecodeSession:
         # state — harmless for the tokens, but the counters would no longer be those of the in-order loop)
         # (speculative sampling advances a row's draw counter on the device by K + 1 per step, void steps included: the host's
         # in-order counters are written back whenever a row is repaired, so its steps can be queued ahead like greedy ones)
-        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and (not self._sampled or self._spec)
+        self._early = ((isinstance(ctl, FixedKController) or self.per_row) and (not self._sampled or self._spec or self._accept)
                        and not self._stateful_draft
                        and os.environ.get("SPECDEC_EARLY_LAUNCH", "1") != "0")
         self._depth = 2 if self._early else 1
@@ -1009,6 +1018,9 @@ class DecodeSession:
         """Loops are cached per (batch, K) and outlive sessions: switch the one in use off what another run left on it and to this
         run's sampling mode, with every row's stream id and draw count. Every set_* call drops the captured step."""
         o, loop, spec = self.options, self.loop, self._spec
+        if getattr(loop, "acceptance", None) is not None and not self._accept:         # (first: the other modes' setters refuse next to a rule)
+            loop.sync()
+            loop.set_acceptance(None)
         if loop.row_table is not None and self.row_params is None:   # a cached loop another run left a table on
             loop.sync()
             loop.set_row_sampling(None)
@@ -1030,6 +1042,9 @@ class DecodeSession:
                                   stream_ids=list(self.row_ids), draw_counts=[r.draws for r in self.rows])
             if self.row_params is not None:   # the mode's launches read table[b]; the scalars above are not in them
                 loop.set_row_sampling(self.row_params)
+        if self._accept:
+            loop.sync()
+            loop.set_acceptance(o.accept_rule, o.accept_temperature, o.accept_epsilon, o.accept_delta, o.accept_k)
 
     def _configure_loop(self) -> None:
         """_configure_sampling, then the processor stage: on or off, its bias rows, every row's counts (forked rows' own too), the grammar."""
@@ -1108,7 +1123,7 @@ class DecodeSession:
             if self.per_row:                       # the device counted steps the host voided: hand it the in-order view
                 m = self.row_ctl[b]
                 loop.set_adaptive_row(b, m.current_k, r.strict_acc, r.strict_prop, m.acceptance_history[-4:])
-        if self._flagged and self._spec and loop.spec_sampling:
+        if self._flagged and ((self._spec and loop.spec_sampling) or (self._accept and self._sampled and loop.sampling)):
             loop.set_draw_counts([r.draws for r in self.rows])   # void steps drew for the flagged rows: back to the in-order view
         self._flagged.clear()
 
@@ -1241,8 +1256,8 @@ class DecodeSession:
                 r.strict_acc += a
                 r.strict_prop += k
                 m.get_k(r.steps + 2, {"step": r.steps + 2, "acceptance_rate": r.strict_acc / max(r.strict_prop, 1)})
-            if self._spec:
-                # speculative sampling: the accepted tokens are the DRAFT's ids, then the redrawn / bonus token. An accepted EOS
+            if self._spec or self._accept:
+                # speculative sampling (and a device acceptance rule alike): the accepted tokens are the DRAFT's ids, then the redrawn / bonus token. An accepted EOS
                 # ends the row by the rule as it stands for greedy steps: the accepted tokens are cut BEFORE the EOS, then the
                 # rule appends t[pos] — a < k: pos = a, the token redrawn after the accepted prefix (the EOS itself is dropped);
                 # a == k: pos = length of the cut, which is the EOS (it stays as the last token)
@@ -1253,7 +1268,8 @@ class DecodeSession:
             if self.emit_mode == HipSpecDec.EMIT_BONUS:
                 constrained = self.grammar is not None and self.grammar_starts[b] >= 0
                 pipe._rules_batch(r, k, a, t, self.max_tokens, self.grammar.eos_id if constrained else self.eos,
-                                  self._resampler(b, r) if (self._sampled and not self._spec) else None, dedup=not constrained)
+                                  self._resampler(b, r) if (self._sampled and not self._spec and not self._accept) else None,
+                                  dedup=not constrained)
                 if self._sampled:
                     r.draws += (k + 1) if self._spec else 1
             else:

@@ -11,6 +11,7 @@ from specdec_hip.grammar import TokenFSM
 from specdec_hip.sampling_params import SamplingParams, check_penalties
 
 from ..policies.controllers import FixedKController
+from .acceptance import refuse_call, with_rule
 
 PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "bad_token_ids", "allowed_token_ids")
 ROW_SAMPLING_CLASH = ("top_k", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty")
@@ -46,6 +47,14 @@ class StepOptions:
     processors: Optional[Processors] = None
     fsm: Any = None
     grammar_starts: Optional[Tuple[int, ...]] = None
+    # the acceptance rule that goes with the mode (keyword fields): None = exact match (speculative sampling's own under "spec"), else
+    # "typical" / "topk_agree" on the device (sd_specdec_set_acceptance); `mode` then says how the token after the accepted prefix is
+    # chosen: "greedy" the target's argmax, "sampled" a draw
+    accept_rule: Optional[str] = None
+    accept_temperature: float = 1.0
+    accept_epsilon: float = 0.09
+    accept_delta: Optional[float] = None
+    accept_k: int = 1
 
     def __post_init__(self):
         # a grammar is a line of the processor stage, and requests with penalties of their own need it: identity scalars will do
@@ -81,6 +90,9 @@ _GATE = {
                         "sampling_params keep a fixed K (controller='fixed'): adaptive K is not supported"),
     "rejection": (None, None, "policy='rejection' (backend='device') keeps a fixed K (controller='fixed'): adaptive K is not supported"),
     "share_prefix": ("share_prefix / n need the captured device step ({what})", None, None),
+    "acceptance": (None, "policy 'typical' / 'topk_agree' with backend='device' needs the draft-model mode (draft_mode='vanilla'): medusa / eagle "
+                   "proposals are not judged by it",
+                   "policy 'typical' / 'topk_agree' with backend='device' keeps a fixed K (controller='fixed'): adaptive K is not supported"),
 }
 
 
@@ -229,6 +241,10 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
     cfg, policy, fake, batch = pipe.config, pipe.policy_name, pipe._fake, policy_routes and not single
     longest, spec = policy == "longest_prefix", policy == "rejection" and pipe.rejection_backend == "device"
     heads, sample_t = batch and pipe.medusa_heads is not None, None      # (persistent heads also serve generate_batch)
+    lossy = getattr(pipe, "accept_device", None)      # "typical" / "topk_agree" with backend="device": a rule of the captured step
+    if lossy is not None:
+        refuse_call(pipe, single, sampling_params)
+        gate(pipe, "acceptance", True)
     if single and sampling_params is not None:
         raise NotImplementedError("sampling_params belong to generate_batch and generate_many (one entry per prompt of a batch): "
                                   "generate() decodes one row")
@@ -240,7 +256,7 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
     rows = None if single else row_options(pipe, sampling_params, len(prompts), n, do_sample, kwargs, heads)
     share_prefix = not single and (bool(share_prefix) or n > 1)
     if share_prefix:
-        gate(pipe, "share_prefix", not fake and (longest or (spec and batch)),
+        gate(pipe, "share_prefix", not fake and (longest or lossy is not None or (spec and batch)),
              "implementation='hip'; policy 'longest_prefix', or 'rejection' with backend='device'" if batch else
              "implementation='hip', policy='longest_prefix'")
     if fake and batch:
@@ -272,7 +288,7 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
     if single and policy == "rejection":
         raise NotImplementedError("policy='rejection' is a generate_batch policy (it emits a correction / bonus token every step)")
     # the route: which runs are the captured step (and one a grammar can run in), and what the others are called in a refusal
-    captured = (longest or spec) if batch else (longest and not fake and sample_t is None)
+    captured = (longest or spec or lossy is not None) if batch else ((longest or lossy is not None) and not fake and sample_t is None)
     grammar_ok = captured and not (pipe._medusa_random() if single else heads)
     what = ("generate(do_sample=True)" if sample_t is not None else f"policy={policy!r} on the host loop" if batch else
             f"policy={policy!r} / implementation={cfg['implementation']!r}")
@@ -284,5 +300,7 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
         options = replace(spec_options(pipe, kwargs), processors=options.processors, fsm=options.fsm, grammar_starts=options.grammar_starts)
     elif route == "host_policy" and sampling is not None:
         raise NotImplementedError(f"policy={policy!r} with do_sample=True is not on the HIP path")
+    if lossy is not None:                     # the rule goes with whatever mode the call's sampling made: greedy or the sampled bonus token
+        options = with_rule(options, lossy)
     self_draft = cfg.get("draft_mode") in ("medusa", "eagle") if single else heads and longest
     return Call(route, prompts, ids, options, max_tokens, float(temperature) if single else temperature, sample_t, share_prefix, self_draft)

@@ -36,6 +36,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--policy-tau", type=float, help="conf_threshold: tau")
     ap.add_argument("--policy-k", type=int, help="topk_agree: k")
     ap.add_argument("--policy-p", type=float, help="typical: p")
+    ap.add_argument("--policy-backend", type=str, choices=["host", "device"], default="host",
+                    help="typical / topk_agree: 'device' runs the rule inside the captured step on the verify pass's rows (the target's "
+                         "distribution after the draft tokens; decodes through generate_batch); 'host' is the reference's loop, which "
+                         "scores the draft against the target's own continuation")
+    ap.add_argument("--typical-epsilon", type=float, help="--policy typical --policy-backend device: the threshold epsilon (same as --policy-p)")
+    ap.add_argument("--typical-delta", type=float, help="--policy typical --policy-backend device: accept p(d) >= min(epsilon, delta * exp(-H)); "
+                                                        "without it the threshold is epsilon alone")
     ap.add_argument("--spec-sampling", action="store_true",
                     help="speculative sampling inside the captured step (policy 'rejection', backend 'device'): the output is "
                          "distributed as the target's own sampling at --temperature; drawn with --seed; fixed K, draft-model mode")
@@ -91,6 +98,27 @@ def cli_sampling_params(args: argparse.Namespace):
         "--policy " + args.policy: args.policy != "longest_prefix"})
 
 
+def device_policy_params(args: argparse.Namespace) -> dict:
+    """The policy_params --policy-backend / --typical-epsilon / --typical-delta add ({} on the host backend); ValueError where they
+    are given without the device backend or with a policy that has none."""
+    device = getattr(args, "policy_backend", "host") == "device"
+    eps, delta = getattr(args, "typical_epsilon", None), getattr(args, "typical_delta", None)
+    if not device:
+        if eps is not None or delta is not None:
+            raise ValueError("--typical-epsilon / --typical-delta belong to --policy typical --policy-backend device")
+        return {}
+    if args.policy not in ("typical", "topk_agree"):
+        raise ValueError(f"--policy-backend device belongs to --policy typical / topk_agree (speculative sampling is --spec-sampling), not {args.policy}")
+    if args.policy != "typical" and (eps is not None or delta is not None):
+        raise ValueError("--typical-epsilon / --typical-delta belong to --policy typical")
+    out = {"backend": "device"}
+    if args.policy == "typical":
+        out.update({k: v for k, v in (("p", eps), ("delta", delta)) if v is not None})
+        if getattr(args, "temperature", None) is not None:
+            out["temperature"] = args.temperature
+    return out
+
+
 def generated_perplexity(lm, tokens):
     """(perplexity, loss) of the generated ids under `lm` (HipLM.score); (inf, inf) for fewer than 2 tokens, as the reference's
     evaluator reports a text it cannot score."""
@@ -137,6 +165,11 @@ def main(argv=None) -> int:
     else:
         controller, cp = "fixed", {"k": args.K}
     policy, pp = args.policy, {k: v for k, v in (("tau", args.policy_tau), ("k", args.policy_k), ("p", args.policy_p)) if v is not None}
+    try:
+        pp.update(device_policy_params(args))
+    except ValueError as e:
+        logging.error("Error: %s", e)
+        return 1
     if args.spec_sampling:
         if args.policy != "longest_prefix":
             logging.error("Cannot specify both --policy and --spec-sampling")
@@ -155,7 +188,7 @@ def main(argv=None) -> int:
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
-        batch = args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None
+        batch = args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:

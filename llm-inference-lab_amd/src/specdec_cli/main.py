@@ -62,6 +62,21 @@ def cmd_run(args: argparse.Namespace) -> int:
         raise SystemExit("--spec-top-k / --spec-top-p belong to --spec-sampling")
     if spec:
         extra["policy_params"].update(shape)
+    lossy = args.policy != "longest_prefix"
+    if lossy:    # typical / topk_agree inside the captured step (the device backend)
+        from specdec.run_specdec import device_policy_params
+
+        if spec:
+            raise SystemExit("--policy and --spec-sampling cannot be given together")
+        try:
+            pp = device_policy_params(args)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if not pp:
+            raise SystemExit(f"--policy {args.policy} needs --policy-backend device here (the host loop is run_specdec's)")
+        if args.policy == "topk_agree" and args.policy_k is not None:
+            pp["k"] = args.policy_k
+        extra = {"policy": args.policy, "policy_params": pp}
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
                                draft_mode="vanilla", **extra)
@@ -71,7 +86,7 @@ def cmd_run(args: argparse.Namespace) -> int:
         proc["grammar"] = pipe.grammar_from_regex(args.regex)
     if row_params is not None:
         proc["sampling_params"] = row_params
-    if spec or args.share_prefix or args.n != 1 or row_params is not None:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    if spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
@@ -111,6 +126,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="speculative sampling on the device (policy 'rejection', backend 'device') at --temperature, drawn with --seed")
     pr.add_argument("--spec-top-k", type=int, help="--spec-sampling: keep the top_k (1..1024) largest logits of both distributions")
     pr.add_argument("--spec-top-p", type=float, help="--spec-sampling: nucleus cut inside --spec-top-k (needs it)")
+    pr.add_argument("--policy", choices=["longest_prefix", "typical", "topk_agree"], default="longest_prefix",
+                    help="acceptance rule of the captured step; typical / topk_agree need --policy-backend device")
+    pr.add_argument("--policy-backend", choices=["host", "device"], default="host",
+                    help="'device': the rule runs inside the captured step on the verify pass's rows (the target after the draft tokens)")
+    pr.add_argument("--policy-k", type=int, help="--policy topk_agree: accept a draft token among the target's k largest logits")
+    pr.add_argument("--typical-epsilon", type=float, help="--policy typical: the threshold epsilon")
+    pr.add_argument("--typical-delta", type=float, help="--policy typical: accept p(d) >= min(epsilon, delta * exp(-H)); without it epsilon alone")
     pr.add_argument("--seed", type=int, default=0)
     pr.add_argument("--repetition-penalty", type=float, help="repetition penalty (> 0) over prompt + generated tokens, inside the captured step")
     pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
