@@ -79,9 +79,21 @@ namespace sd {
 // the forward
 constexpr int kMaxPartials = 512;
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are indexed from row0
-int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base, int pos_off, int row0, int B, int M,
-                  int32_t* ids_out, int ids_stride, void* logits_out, int logits_dtype, int skip_head, hipStream_t st);
+// One forward: rows [row0, row0+B) of the bound batch, M tokens each; tokens / pos_base / ids_out / logits_out are indexed from
+// row0 (element 0 of each array belongs to row row0)
+struct ForwardCall {
+  const int32_t* tokens = nullptr;    // row b's tokens at tokens + b * tok_stride
+  int tok_stride = 0;
+  const int32_t* pos_base = nullptr;  // [B]: row b's first token sits at position pos_base[b] + pos_off
+  int pos_off = 0;
+  int row0 = 0, B = 1, M = 1;
+  int32_t* ids_out = nullptr;         // nullable: argmax id of (b, t) at ids_out[b * ids_stride + t]
+  int ids_stride = 0;
+  void* logits_out = nullptr;         // nullable [B][M][vocab] of logits_dtype (SD_F32 / SD_BF16)
+  int logits_dtype = SD_BF16;
+  int skip_head = 0;                  // 1: the layers only (the residual rows stay in the workspace)
+};
+int model_forward(sd_model* m, const ForwardCall& f, hipStream_t st);
 GemvArgs matrix_args(const sd_model* m, int index);
 // What belongs to the call, on top of matrix_args: the pass's tokens, and with pos_base the rows' positions, the head geometry and
 // the cache paging (bt: the pass's first row of the block table, null on dense KV). gated: the launch leaves at entry when the
@@ -150,27 +162,44 @@ bool verify_tail_fits(const SpecState& s);
 int launch_verify_tail(const SpecState& s, const float* part_val, const int* part_idx, int grid, int mode, int32_t* rec_slots,
                        int rec_ints, int32_t* step_counter, const unsigned* draft_status, const unsigned* target_status, hipStream_t st);
 
-// csrc/sample.hip
-struct SampleArgs;
-int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
-                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st, const sd_row_sampling* table = nullptr);
+// ---- host-side parameter bundles of the sampling stage: the step (csrc/spec_loop.hip) keeps one per mode, the C-ABI ops build
+// them from their arguments, and each launcher unpacks them into the argument structs of its kernels (no kernel receives one).
 
+// How a row is shaped and which Philox values it consumes
+struct DrawSpec {
+  float temperature = 1.0f;
+  int top_k = 0;                           // 0: no top-k cut (speculative sampling: the plain distributions; else 1..1024: both shaped)
+  float top_p = 1.0f;                      // >= 1: no nucleus cut
+  uint64_t seed = 0;
+  uint32_t* draw = nullptr;                // nullable [B]: per-row draw counters, read and advanced on the device
+  uint32_t draw0 = 0;                      // draw index when `draw` is null (the step always has counters)
+  const int32_t* stream_id = nullptr;      // nullable [B]: Philox stream of row b (default b)
+  const sd_row_sampling* table = nullptr;  // device [B] per-row parameters: the _rows kernels read temperature, top_k, top_p and seed
+                                           // from table[b] at run time and the four scalars above are not in the launch
+};
 
-// csrc/spec_sample.hip: speculative sampling inside the step. top_k == 0: the plain distributions; top_k in 1..1024: both
-// distributions shaped by top-k / top-p
-int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                           float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
-                           hipStream_t st, const sd_row_sampling* table = nullptr);
-int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st,
-                     const sd_row_sampling* table = nullptr);
+// The acceptance rule of csrc/typical_accept.hip
+struct AcceptRule {
+  int rule = SD_ACCEPT_OFF;   // sd_accept_rule
+  float temperature = 1.0f, epsilon = 1.0f, delta = 1.0f;
+  int agree_k = 1;
+};
+
+// csrc/sample.hip: the step's draw of the token after the accepted prefix, from row accept_len[b] of the verify logits
+int launch_sample_step(const SpecState& s, const void* logits, int V, const DrawSpec& d, hipStream_t st);
+
+// csrc/spec_sample.hip: speculative sampling inside the step
+int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, const DrawSpec& d,
+                           hipStream_t st);
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, const DrawSpec& d, int32_t* flag,
+                     int32_t* cand, hipStream_t st);
 
 // csrc/typical_accept.hip: lossy acceptance (typical / top-k agreement) on the stored verify rows. workspace:
 // typical_accept_workspace(B, K) bytes; next_from_ids: s.sampled[b] = target_ids[b][accept_len[b]] (no sampled bonus follows)
-int check_typical_params(const char* who, int rule, float temperature, float epsilon, float delta, int agree_k, int K, int V);
+int check_typical_params(const char* who, const AcceptRule& r, int K, int V);
 size_t typical_accept_workspace(int B, int K);
-int launch_typical_step(const SpecState& s, const void* logits, int V, int rule, float temperature, float epsilon, float delta,
-                        int agree_k, bool next_from_ids, void* workspace, hipStream_t st);
+int launch_typical_step(const SpecState& s, const void* logits, int V, const AcceptRule& r, bool next_from_ids, void* workspace,
+                        hipStream_t st);
 
 // csrc/grammar.hip: token automata (grammar-constrained decoding). next: uint16 [S][V], 0xFFFF = the token is not allowed in the
 // state; allow: the same as one bit per token, uint32 [S][ceil(V / 32)]. A row's state: -1 unconstrained, 0..S-1, else DEAD
@@ -199,12 +228,25 @@ int launch_fsm_advance(const uint16_t* next, int S, int V, int32_t* fsm_state, i
                        const int32_t* n_new, int max_new, const int32_t* active, hipStream_t st);
 
 // csrc/logit_proc.hip: logit processors (penalties, bias) on stored bf16 rows, in place; the step and the C-ABI ops run these.
-// fsm (nullable): the grammar line, folded into the same launch
+struct LogitStage {
+  const uint16_t* counts = nullptr;        // [B][V]
+  const float* bias = nullptr;             // [B][V] or null
+  float rp = 1.0f, presence = 0.f, frequency = 0.f;
+  void* workspace = nullptr;               // argmax partials of a launch with ids_out (logit_process_workspace), else unused
+  size_t workspace_bytes = 0;
+  const FsmBind* fsm = nullptr;            // nullable: the grammar line, folded into the same launch
+  const sd_row_sampling* table = nullptr;  // device [B] per-row penalties (the three above are not in the launch), else null
+};
+// row (b, r) of the launch at rows + (b * R + r) * row_stride
+struct LogitRows {
+  void* rows;
+  long long row_stride;
+  int B, R, V;
+};
 size_t logit_process_workspace(int B, int R, int V);
-int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
-                         const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
-                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
-                         const FsmBind* fsm = nullptr, const sd_row_sampling* table = nullptr);
+// n_tokens < 0: row (b, r) is conditioned on the first r in-step tokens of tokens + b * tok_stride, else every row on the first n_tokens
+int launch_logit_process(const LogitRows& rows, const LogitStage& g, const int32_t* tokens, int tok_stride, int n_tokens,
+                         const int32_t* active, int32_t* ids_out, int ids_stride, hipStream_t st);
 int launch_logit_counts_set(uint16_t* counts, int B, int V, int b, const int32_t* prompt, int n_prompt, const int32_t* gen, int n_gen,
                             hipStream_t st);
 int launch_logit_counts_add(uint16_t* counts, int B, int V, const int32_t* tokens, int tok_stride, const int32_t* n_new, int max_new,

@@ -324,57 +324,53 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
   return 0;
 }
 
-// rows [row0, row0+B) of the bound batch; tokens / pos_base / ids_out / logits_out are
-// indexed from row0 (element 0 of each array belongs to row row0)
-int model_forward(sd_model* m, const int32_t* tokens, int tok_stride, const int32_t* pos_base,
-                  int pos_off, int row0, int B, int M, int32_t* ids_out, int ids_stride, void* logits_out,
-                  int logits_dtype, int skip_head, hipStream_t st) {
+int model_forward(sd_model* m, const ForwardCall& f, hipStream_t st) {
   SD_REQUIRE(m && m->k_cache && m->x, "forward: model not bound (sd_model_bind)");
-  SD_REQUIRE(row0 >= 0 && B >= 1 && row0 + B <= m->B, "forward: rows [%d,%d) exceeds bound batch %d", row0, row0 + B, m->B);
-  SD_REQUIRE(M >= 1, "forward: M=%d", M);
-  SD_REQUIRE(tokens && pos_base, "forward: NULL tokens/pos_base");
-  const int esz = (logits_dtype == SD_F32) ? 4 : 2;
-  SD_REQUIRE(!logits_out || logits_dtype == SD_F32 || logits_dtype == SD_BF16, "forward: logits dtype %d", logits_dtype);
+  SD_REQUIRE(f.row0 >= 0 && f.B >= 1 && f.row0 + f.B <= m->B, "forward: rows [%d,%d) exceeds bound batch %d", f.row0, f.row0 + f.B, m->B);
+  SD_REQUIRE(f.M >= 1, "forward: M=%d", f.M);
+  SD_REQUIRE(f.tokens && f.pos_base, "forward: NULL tokens/pos_base");
+  const int esz = (f.logits_dtype == SD_F32) ? 4 : 2;
+  SD_REQUIRE(!f.logits_out || f.logits_dtype == SD_F32 || f.logits_dtype == SD_BF16, "forward: logits dtype %d", f.logits_dtype);
   const int V = m->cfg.vocab;
-  const int cap = (B * M <= m->small_t) ? m->small_t : m->max_t;  // tokens per pass
-  const int backend = prefill_route(m, M, logits_out != nullptr, st);
+  const int cap = (f.B * f.M <= m->small_t) ? m->small_t : m->max_t;  // tokens per pass
+  const int backend = prefill_route(m, f.M, f.logits_out != nullptr, st);
   if (backend == SD_PREFILL_PASSES) {
-    m->prefill_count[SD_PREFILL_PASSES] += B;
+    m->prefill_count[SD_PREFILL_PASSES] += f.B;
   } else if (backend >= 0) {
-    for (int b0 = 0; b0 < B; ++b0) {
+    for (int b0 = 0; b0 < f.B; ++b0) {
       // ids of the prompt positions: the lm_head over the chunk's rows in groups of at most the model's pass size (the decode-shaped
       // head kernel covers no more: 64 rows for some fp8 heads)
       auto head = [&](int m0, int mc, const uint16_t* xr) -> int {
-        if (skip_head || !ids_out) return 0;
+        if (f.skip_head || !f.ids_out) return 0;
         for (int s0 = 0; s0 < mc; s0 += m->max_t) {
           const int n = (mc - s0 < m->max_t) ? mc - s0 : m->max_t;
-          if (int rc = head_pass(m, xr + static_cast<size_t>(s0) * m->cfg.d_model, n, ids_out + static_cast<size_t>(b0) * ids_stride + m0 + s0, st)) return rc;
+          if (int rc = head_pass(m, xr + static_cast<size_t>(s0) * m->cfg.d_model, n, f.ids_out + static_cast<size_t>(b0) * f.ids_stride + m0 + s0, st)) return rc;
         }
         return 0;
       };
-      if (int rc = prefill_row(m, backend, tokens + static_cast<size_t>(b0) * tok_stride, pos_base + b0, pos_off, row0 + b0, M, st, head)) return rc;
+      if (int rc = prefill_row(m, backend, f.tokens + static_cast<size_t>(b0) * f.tok_stride, f.pos_base + b0, f.pos_off, f.row0 + b0, f.M, st, head)) return rc;
     }
-    m->prefill_count[backend] += B;
+    m->prefill_count[backend] += f.B;
     return 0;
   }
-  if (M <= cap) {
-    const int Bc = cap / M;
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-      const int nb = (B - b0 < Bc) ? B - b0 : Bc;
-      void* lo = logits_out ? static_cast<char*>(logits_out) + static_cast<size_t>(b0) * M * V * esz : nullptr;
-      if (int rc = forward_pass(m, tokens, tok_stride, pos_base, pos_off, row0, b0, nb, M, ids_out, ids_stride, lo,
-                                logits_dtype, V, skip_head, st))
+  if (f.M <= cap) {
+    const int Bc = cap / f.M;
+    for (int b0 = 0; b0 < f.B; b0 += Bc) {
+      const int nb = (f.B - b0 < Bc) ? f.B - b0 : Bc;
+      void* lo = f.logits_out ? static_cast<char*>(f.logits_out) + static_cast<size_t>(b0) * f.M * V * esz : nullptr;
+      if (int rc = forward_pass(m, f.tokens, f.tok_stride, f.pos_base, f.pos_off, f.row0, b0, nb, f.M, f.ids_out, f.ids_stride, lo,
+                                f.logits_dtype, V, f.skip_head, st))
         return rc;
     }
     return 0;
   }
   // long M (prefill): chunks of `cap` positions, one row at a time, in position order
-  for (int b0 = 0; b0 < B; ++b0) {
-    for (int m0 = 0; m0 < M; m0 += cap) {
-      const int mc = (M - m0 < cap) ? M - m0 : cap;
-      void* lo = logits_out ? static_cast<char*>(logits_out) + (static_cast<size_t>(b0) * M + m0) * V * esz : nullptr;
-      if (int rc = forward_pass(m, tokens + m0, tok_stride, pos_base, pos_off + m0, row0, b0, 1, mc,
-                                ids_out ? ids_out + m0 : nullptr, ids_stride, lo, logits_dtype, V, skip_head, st))
+  for (int b0 = 0; b0 < f.B; ++b0) {
+    for (int m0 = 0; m0 < f.M; m0 += cap) {
+      const int mc = (f.M - m0 < cap) ? f.M - m0 : cap;
+      void* lo = f.logits_out ? static_cast<char*>(f.logits_out) + (static_cast<size_t>(b0) * f.M + m0) * V * esz : nullptr;
+      if (int rc = forward_pass(m, f.tokens + m0, f.tok_stride, f.pos_base, f.pos_off + m0, f.row0, b0, 1, mc,
+                                f.ids_out ? f.ids_out + m0 : nullptr, f.ids_stride, lo, f.logits_dtype, V, f.skip_head, st))
         return rc;
     }
   }
@@ -465,8 +461,8 @@ extern "C" int sd_model_forward(sd_model* m, const int32_t* tokens, int tok_stri
                                 int pos_off, int row0, int B, int M, int32_t* ids_out, int ids_stride, void* logits_out,
                                 int logits_dtype, int skip_head, void* stream) {
   clear_error();
-  return model_forward(m, tokens, tok_stride, pos_base, pos_off, row0, B, M, ids_out, ids_stride, logits_out,
-                       logits_dtype, skip_head, static_cast<hipStream_t>(stream));
+  const ForwardCall f{tokens, tok_stride, pos_base, pos_off, row0, B, M, ids_out, ids_stride, logits_out, logits_dtype, skip_head};
+  return model_forward(m, f, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_model_score(sd_model* m, const int32_t* tokens, int n, int row, int pos0, float* logprob, int32_t* greedy, void* stream) {

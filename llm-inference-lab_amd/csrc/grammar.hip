@@ -116,7 +116,8 @@ extern "C" int sd_logit_process_fsm(void* rows, int64_t row_stride, int B, int R
   f.S = S;
   f.state = fsm_state;
   f.eos_id = eos_id;
-  return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
-                              repetition_penalty, presence_penalty, frequency_penalty, ids_out, ids_stride, workspace, workspace_bytes,
-                              static_cast<hipStream_t>(stream), &f);
+  const LogitStage g{static_cast<const uint16_t*>(counts), bias, repetition_penalty, presence_penalty, frequency_penalty, workspace,
+                     workspace_bytes, &f};
+  return launch_logit_process({rows, row_stride, B, R, V}, g, tokens, tok_stride, n_tokens, active, ids_out, ids_stride,
+                              static_cast<hipStream_t>(stream));
 }

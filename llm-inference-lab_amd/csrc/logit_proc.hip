@@ -233,45 +233,46 @@ size_t logit_process_workspace(int B, int R, int V) {
   return static_cast<size_t>(B) * R * logit_process_split(V) * (sizeof(float) + sizeof(int));
 }
 
-int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, const uint16_t* counts, const float* bias,
-                         const int32_t* tokens, int tok_stride, int n_tokens, const int32_t* active, float rp, float presence,
-                         float frequency, int32_t* ids_out, int ids_stride, void* workspace, size_t workspace_bytes, hipStream_t st,
-                         const FsmBind* fsm, const sd_row_sampling* table) {
-  SD_REQUIRE(rows && counts, "logit_process: NULL rows / counts");
+int launch_logit_process(const LogitRows& rows, const LogitStage& g, const int32_t* tokens, int tok_stride, int n_tokens,
+                         const int32_t* active, int32_t* ids_out, int ids_stride, hipStream_t st) {
+  const int B = rows.B, R = rows.R, V = rows.V;
+  const FsmBind* const fsm = g.fsm;
+  SD_REQUIRE(rows.rows && g.counts, "logit_process: NULL rows / counts");
   SD_REQUIRE(B >= 1 && R >= 1 && V >= 1 && static_cast<long long>(B) * R <= 65535, "logit_process: B=%d R=%d V=%d out of range", B, R, V);
-  SD_REQUIRE(row_stride >= V, "logit_process: row stride %lld < V=%d", row_stride, V);
+  SD_REQUIRE(rows.row_stride >= V, "logit_process: row stride %lld < V=%d", rows.row_stride, V);
   const int n_max = n_tokens < 0 ? R - 1 : n_tokens;
   SD_REQUIRE(n_max <= kLpMaxTokens, "logit_process: %d in-step tokens (at most %d)", n_max, kLpMaxTokens);
   SD_REQUIRE(n_max == 0 || (tokens && tok_stride >= n_max), "logit_process: %d in-step tokens need a token array with a stride >= %d", n_max, n_max);
-  if (table) {   // the penalties are the rows' own, normalised on the device
-    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "logit_process: the row table must be 16-byte aligned");
+  if (g.table) {   // the penalties are the rows' own, normalised on the device
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(g.table) & 15) == 0, "logit_process: the row table must be 16-byte aligned");
   } else {
-    SD_REQUIRE(rp == rp && rp > 0.f, "logit_process: repetition_penalty %g (must be > 0)", rp);
-    SD_REQUIRE(presence - presence == 0.f && frequency - frequency == 0.f, "logit_process: presence %g / frequency %g must be finite", presence, frequency);
+    SD_REQUIRE(g.rp == g.rp && g.rp > 0.f, "logit_process: repetition_penalty %g (must be > 0)", g.rp);
+    SD_REQUIRE(g.presence - g.presence == 0.f && g.frequency - g.frequency == 0.f, "logit_process: presence %g / frequency %g must be finite",
+               g.presence, g.frequency);
   }
-  SD_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(counts)) & 1) == 0 && (reinterpret_cast<uintptr_t>(bias) & 3) == 0,
+  SD_REQUIRE(((reinterpret_cast<uintptr_t>(rows.rows) | reinterpret_cast<uintptr_t>(g.counts)) & 1) == 0 && (reinterpret_cast<uintptr_t>(g.bias) & 3) == 0,
              "logit_process: misaligned rows / counts / bias");
   const int S = logit_process_split(V);
   LogitProcArgs a{};
-  a.rows = static_cast<uint16_t*>(rows);
-  a.row_stride = row_stride;
+  a.rows = static_cast<uint16_t*>(rows.rows);
+  a.row_stride = rows.row_stride;
   a.R = R;
   a.V = V;
-  a.counts = counts;
-  a.bias = bias;
+  a.counts = g.counts;
+  a.bias = g.bias;
   a.tokens = tokens;
   a.tok_stride = tok_stride;
   a.n_tokens = n_tokens;
   a.active = active;
-  a.rp = rp;
-  a.presence = presence;
-  a.frequency = frequency;
+  a.rp = g.rp;
+  a.presence = g.presence;
+  a.frequency = g.frequency;
   if (ids_out) {
-    SD_REQUIRE(workspace && workspace_bytes >= logit_process_workspace(B, R, V), "logit_process: workspace %zu B < %zu B", workspace_bytes,
+    SD_REQUIRE(g.workspace && g.workspace_bytes >= logit_process_workspace(B, R, V), "logit_process: workspace %zu B < %zu B", g.workspace_bytes,
                logit_process_workspace(B, R, V));
-    SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "logit_process: misaligned workspace");
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(g.workspace) & 3) == 0, "logit_process: misaligned workspace");
     SD_REQUIRE(ids_stride >= R, "logit_process: ids stride %d < R=%d", ids_stride, R);
-    a.part_val = static_cast<float*>(workspace);
+    a.part_val = static_cast<float*>(g.workspace);
     a.part_idx = reinterpret_cast<int*>(a.part_val + static_cast<size_t>(B) * R * S);
   }
   if (fsm) {
@@ -285,10 +286,10 @@ int launch_logit_process(void* rows, long long row_stride, int B, int R, int V, 
     SD_REQUIRE(!fsm->pos || (n_tokens >= 0 ? (R == 1 && fsm->pos_stride > n_tokens) : fsm->pos_stride >= n_max),
                "logit_process: position table of stride %d for R=%d rows of %d tokens", fsm->pos_stride, R, n_tokens);
     a.fsm = *fsm;
-    if (table) hipLaunchKernelGGL(logit_process_rows_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, table);
+    if (g.table) hipLaunchKernelGGL(logit_process_rows_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, g.table);
     else hipLaunchKernelGGL(logit_process_kernel<true>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
   } else {
-    if (table) hipLaunchKernelGGL(logit_process_rows_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, table);
+    if (g.table) hipLaunchKernelGGL(logit_process_rows_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a, g.table);
     else hipLaunchKernelGGL(logit_process_kernel<false>, dim3(S, B * R), dim3(kLpThreads), 0, st, a);
   }
   SD_LAUNCH_CHECK();
@@ -364,9 +365,10 @@ extern "C" int sd_logit_process(void* rows, int64_t row_stride, int B, int R, in
                                 float presence_penalty, float frequency_penalty, int32_t* ids_out, int ids_stride, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   clear_error();
-  return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
-                              repetition_penalty, presence_penalty, frequency_penalty, ids_out, ids_stride, workspace, workspace_bytes,
-                              static_cast<hipStream_t>(stream), nullptr);
+  const LogitStage g{static_cast<const uint16_t*>(counts), bias, repetition_penalty, presence_penalty, frequency_penalty, workspace,
+                     workspace_bytes};
+  return launch_logit_process({rows, row_stride, B, R, V}, g, tokens, tok_stride, n_tokens, active, ids_out, ids_stride,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_logit_process_rows(void* rows, int64_t row_stride, int B, int R, int V, const void* counts, const float* bias,
@@ -384,9 +386,9 @@ extern "C" int sd_logit_process_rows(void* rows, int64_t row_stride, int B, int 
   f.S = S;
   f.state = fsm_state;
   f.eos_id = eos_id;
-  return launch_logit_process(rows, row_stride, B, R, V, static_cast<const uint16_t*>(counts), bias, tokens, tok_stride, n_tokens, active,
-                              1.0f, 0.f, 0.f, ids_out, ids_stride, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                              grammar ? &f : nullptr, table);
+  const LogitStage g{static_cast<const uint16_t*>(counts), bias, 1.0f, 0.f, 0.f, workspace, workspace_bytes, grammar ? &f : nullptr, table};
+  return launch_logit_process({rows, row_stride, B, R, V}, g, tokens, tok_stride, n_tokens, active, ids_out, ids_stride,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t sd_logit_counts_bytes(int B, int V) {

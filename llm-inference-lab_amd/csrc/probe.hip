@@ -145,7 +145,12 @@ extern "C" int sd_model_probe_forward(sd_model* m, int M, int pos0, int iters, i
   const sd_model_config& c = m->cfg;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int32_t* zeros = reinterpret_cast<const int32_t*>(m->attn_cnt);   // kAttnSplitSlots zero words: token ids and the position base
-  auto fwd = [&](int = 0) { return model_forward(m, zeros, M, zeros, pos0, 0, 1, M, nullptr, M, nullptr, SD_BF16, skip_head, st); };
+  ForwardCall f;   // one row of M tokens at positions pos0.., no ids and no logits out
+  f.tokens = f.pos_base = zeros;
+  f.tok_stride = f.M = M;
+  f.pos_off = pos0;
+  f.skip_head = skip_head;
+  auto fwd = [&](int = 0) { return model_forward(m, f, st); };
   if (int rc = timed_launches(fwd, 2, iters, st, avg_usec)) return rc;
   double per_layer = 0;
   for (int i = 0; i < 4; ++i) per_layer += 2.0 * matrix_shape(c, i).N * matrix_shape(c, i).K;

@@ -336,10 +336,9 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const Sampl
 
 // (the fields in declaration order, the seed split into the two Philox key words)
 static SampleArgs sample_args(const void* logits, int dtype, int64_t row_stride, int V, const int32_t* pos, int rows_per_b,
-                              const int32_t* active, float temperature, int top_k, float top_p, uint64_t seed, uint32_t* draw,
-                              uint32_t draw0, const int32_t* stream_id, int32_t* out) {
-  return SampleArgs{logits, dtype, row_stride, V, pos, rows_per_b, active, temperature, top_k, top_p, seed_lo32(seed), seed_hi32(seed),
-                    draw, draw0, stream_id, out};
+                              const int32_t* active, const DrawSpec& d, int32_t* out) {
+  return SampleArgs{logits, dtype, row_stride, V, pos, rows_per_b, active, d.temperature, d.top_k, d.top_p, seed_lo32(d.seed),
+                    seed_hi32(d.seed), d.draw, d.draw0, d.stream_id, out};
 }
 
 // table: per-row parameters (the scalar ones of `a` are ignored), else null
@@ -368,10 +367,8 @@ int launch_sample(const SampleArgs& a, int B, hipStream_t st, const sd_row_sampl
 }
 
 // the step's draw: entry b samples from row b*(K+1) + accept_len[b] of the verify logits
-int launch_sample_step(const SpecState& s, const void* logits, int V, float temperature, int top_k, float top_p,
-                       uint64_t seed, uint32_t* draw, const int32_t* stream_id, hipStream_t st, const sd_row_sampling* table) {
-  return launch_sample(sample_args(logits, SD_BF16, V, V, s.accept_len, s.K + 1, s.active, temperature, top_k, top_p, seed, draw, 0,
-                                   stream_id, s.sampled), s.B, st, table);
+int launch_sample_step(const SpecState& s, const void* logits, int V, const DrawSpec& d, hipStream_t st) {
+  return launch_sample(sample_args(logits, SD_BF16, V, V, s.accept_len, s.K + 1, s.active, d, s.sampled), s.B, st, d.table);
 }
 
 }  // namespace sd
@@ -383,8 +380,9 @@ extern "C" int sd_sample_token(const void* logits, int logits_dtype, int64_t row
                                int top_k, float top_p, uint64_t seed, uint32_t* draw_counters, uint32_t draw0,
                                const int32_t* stream_id, int32_t* out_ids, void* stream) {
   clear_error();
-  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, temperature, top_k, top_p, seed,
-                                   draw_counters, draw0, stream_id, out_ids), B, static_cast<hipStream_t>(stream));
+  const DrawSpec d{temperature, top_k, top_p, seed, draw_counters, draw0, stream_id};
+  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, d, out_ids), B,
+                       static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t sd_row_sampling_bytes(void) { return sizeof(sd_row_sampling); }
@@ -396,6 +394,7 @@ extern "C" int sd_sample_token_rows(const void* logits, int logits_dtype, int64_
   SD_REQUIRE(table, "sample_token_rows: NULL table");
   SD_REQUIRE(B >= 1, "sample_token_rows: B=%d", B);
   SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "sample_token_rows: the row table must be 16-byte aligned");
-  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, 1.0f, 0, 1.0f, 0, draw_counters, draw0,
-                                   stream_id, out_ids), B, static_cast<hipStream_t>(stream), table);
+  const DrawSpec d{1.0f, 0, 1.0f, 0, draw_counters, draw0, stream_id, table};   // the scalars are not in the launch
+  return launch_sample(sample_args(logits, logits_dtype, row_stride, V, pos, rows_per_b, active, d, out_ids), B,
+                       static_cast<hipStream_t>(stream), table);
 }

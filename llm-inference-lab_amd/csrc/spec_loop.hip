@@ -43,43 +43,32 @@ struct sd_specdec {
   hipGraphExec_t exec = nullptr;
   hipStream_t graph_st_t = nullptr, graph_st_d = nullptr;
   long steps = 0;
-  // sampled bonus token (sd_specdec_set_sampling); all buffers are caller-owned
-  int sample = 0;
-  float temperature = 1.0f, top_p = 1.0f;
-  int top_k = 0;
-  uint64_t seed = 0;
-  void* logits = nullptr;          // [B][K+1][V] bf16
-  uint32_t* draw = nullptr;        // [B]
-  const int32_t* stream_id = nullptr;
-  // speculative sampling (sd_specdec_set_spec_sampling): draft tokens drawn from q, accept by p/q, residual redraw. Shares
-  // temperature / seed / draw / stream_id with the sampled-bonus mode (the two are mutually exclusive).
+  // ---- the sampling stage: one bundle (csrc/engine.h) per thing a setter binds, and beside it the [B][K+1][V] bf16 buffer the
+  // mode can lend the verify forward (plan_step picks one). Every buffer is caller-owned unless it says otherwise.
+  // Per-row parameters (sd_specdec_set_row_sampling): ONE device table [B], read by the kernels at run time, kept in every
+  // bundle a launch takes it from (bonus.table == spec_draw.table == stage.table). While it is bound the draws, the statistics
+  // and the process launches are the _rows kernels, and the bundles' scalars are not in those launches.
+  int sample = 0;                  // sampled bonus token (sd_specdec_set_sampling)
+  DrawSpec bonus;
+  void* logits = nullptr;
+  // speculative sampling (sd_specdec_set_spec_sampling): draft tokens drawn from q, accept by p/q, residual redraw. The two
+  // sampling modes are mutually exclusive; each reads the draw description its own setter filled.
   int spec = 0;
-  void* spec_q = nullptr;          // [B][K][V] bf16 draft logits, caller-owned
-  void* spec_p = nullptr;          // [B][K+1][V] bf16 target logits, caller-owned; until the verify forward overwrites it, its first
-                                   // rows are where each draft forward leaves the logits of its pass ([B][M][V])
-  int32_t* spec_flags = nullptr;   // [2][B][K+1] device: accept flags, candidate next tokens
-  int spec_top_k = 0;              // sd_specdec_set_spec_shaping: > 0 = both distributions shaped by top-k / top-p
-  float spec_top_p = 1.0f;
+  DrawSpec spec_draw;              // top_k / top_p: sd_specdec_set_spec_shaping (top_k > 0 = both distributions shaped)
+  void* spec_q = nullptr;          // [B][K][V] bf16 draft logits
+  void* spec_p = nullptr;          // target logits; until the verify forward overwrites it, its first rows are where each draft
+                                   // forward leaves the logits of its pass ([B][M][V])
+  int32_t* spec_flags = nullptr;   // [2][B][K+1] device, the loop's own: accept flags, candidate next tokens
   // logit processors (sd_specdec_set_logit_processors): every logits row is stored, processed in place, then consumed
   int lp = 0;
-  float lp_rp = 1.0f, lp_presence = 0.f, lp_frequency = 0.f;
-  uint16_t* lp_counts = nullptr;   // [B][V], caller-owned
-  const float* lp_bias = nullptr;  // [B][V] or null, caller-owned
-  void* lp_logits = nullptr;       // [B][K+1][V] bf16, caller-owned; used while neither sampling mode owns a buffer
-  void* lp_ws = nullptr;           // argmax partials of the process launches
-  size_t lp_ws_bytes = 0;
-  // grammar (sd_specdec_set_grammar): one more line of the processors' transform; tables and per-row state are caller-owned
-  int fsm = 0;
-  sd::FsmBind fsm_bind{};          // pos: [B][K+1], the loop's own (allocated at first use)
+  LogitStage stage;                // fsm: &fsm_bind while a grammar is bound (sd_specdec_set_grammar: one more line of the transform)
+  void* lp_logits = nullptr;       // used while neither sampling mode owns a buffer
+  FsmBind fsm_bind{};              // tables and per-row state are the caller's; pos: [B][K+1], the loop's own (allocated at first use)
   int32_t* fsm_pos = nullptr;
   // lossy acceptance (sd_specdec_set_acceptance): the rule judges the stored verify rows in place of the exact-match scan
-  int acc_rule = 0;                // sd_accept_rule; 0 = off
-  float acc_temperature = 1.0f, acc_epsilon = 1.0f, acc_delta = 1.0f;
-  int acc_agree_k = 1;
-  void* acc_logits = nullptr;      // [B][K+1][V] bf16, caller-owned; used while the sampled-bonus mode does not lend its own
+  AcceptRule accept;               // rule 0 = off
+  void* acc_logits = nullptr;      // used while the sampled-bonus mode does not lend its own
   void* acc_ws = nullptr;          // flags and records of the two launches (the loop's own, allocated at first use)
-  // per-row parameters (sd_specdec_set_row_sampling): device [B], caller-owned, read by the kernels at run time
-  const sd_row_sampling* row_table = nullptr;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -209,9 +198,6 @@ struct StepPlan {
   Proposer proposer;
   bool heads;         // Medusa heads propose the NEXT step's tokens after the verify (set_medusa on an EAGLE loop keeps both)
   Select select;
-  bool shaped;        // speculative sampling with both distributions shaped by top-k / top-p
-  bool rows;          // a row table is bound: the draws, the statistics and the process launches are the _rows kernels, which read
-                      // their parameters from table[b] at run time (the loop's scalars are not in those launches)
   bool lp;            // logit processors: the forwards store their rows (into the buffer of the sampling mode that is on, else the
                       // mode's own), the rows are processed in place and the argmax of the processed row replaces the fused one
   bool two;           // the draft forwards run on a stream of their own, forked from and joined to the target's
@@ -237,10 +223,8 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   StepPlan p{};
   p.proposer = s.draft ? PROPOSE_DRAFT : (s.eagle ? PROPOSE_EAGLE : (s.heads.empty() ? PROPOSE_SELF : PROPOSE_HEADS));
   p.heads = !s.heads.empty();
-  p.select = s.acc_rule ? SELECT_TYPICAL : (s.sample ? SELECT_SAMPLED_BONUS : (s.spec ? SELECT_SPEC : SELECT_GREEDY));   // (the setters keep them apart)
+  p.select = s.accept.rule ? SELECT_TYPICAL : (s.sample ? SELECT_SAMPLED_BONUS : (s.spec ? SELECT_SPEC : SELECT_GREEDY));   // (the setters keep them apart)
   const bool spec = p.select == SELECT_SPEC;
-  p.shaped = spec && s.spec_top_k > 0;
-  p.rows = s.row_table != nullptr;
   p.lp = s.lp != 0;
   p.two = two_streams && s.draft;
   p.fwd0_select = s.draft && s.st.fwd0_w && s.B == 1 && persist_pass_ok(s.draft, 2, 1, 2);
@@ -256,6 +240,14 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   return p;
 }
 
+// a forward of the step: every row of the loop, positions counted from cur_len; the caller names the tokens and what it wants out
+static ForwardCall step_forward(const SpecState& st) {
+  ForwardCall f;
+  f.pos_base = st.cur_len;
+  f.B = st.B;
+  return f;
+}
+
 // ---- the proposers that are not a draft model, on the target stream (Medusa heads propose after the verify: enqueue_verify)
 static int enqueue_target_proposer(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
   const int B = s->B, K = s->K;
@@ -263,7 +255,11 @@ static int enqueue_target_proposer(sd_specdec* s, const StepPlan& p, hipStream_t
   if (p.proposer == PROPOSE_EAGLE) {
     // EAGLE-lite: residual row of `last` (1-token forward, head skipped) -> K extrapolated rows -> one lm_head launch
     const sd_model_config& c = m->cfg;
-    if (int rc = model_forward(m, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, 1, nullptr, 2, nullptr, SD_BF16, 1, st_t)) return rc;
+    ForwardCall f = step_forward(s->st);
+    f.tokens = s->st.verify_tok;
+    f.tok_stride = K + 1;
+    f.skip_head = 1;
+    if (int rc = model_forward(m, f, st_t)) return rc;
     if (int rc = launch_eagle_extrapolate(m->x, s->eagle_H, s->eagle_prev, s->eagle_has, c.final_norm_w, c.final_norm_b, c.norm_eps,
                                           s->eagle_alpha, c.d_model, B, K, c.arch == SD_ARCH_LLAMA ? 1 : 0, st_t))
       return rc;
@@ -286,7 +282,12 @@ static int enqueue_target_proposer(sd_specdec* s, const StepPlan& p, hipStream_t
   }
   if (p.proposer == PROPOSE_SELF) {
     // self-draft (Medusa-lite, tied heads): the target's own next token, K times
-    if (int rc = model_forward(m, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, 1, s->st.draft_ids, 2, nullptr, SD_BF16, 0, st_t)) return rc;
+    ForwardCall f = step_forward(s->st);
+    f.tokens = s->st.verify_tok;
+    f.tok_stride = K + 1;
+    f.ids_out = s->st.draft_ids;
+    f.ids_stride = 2;
+    if (int rc = model_forward(m, f, st_t)) return rc;
     return launch_medusa_fill(s->st, st_t);
   }
   return 0;
@@ -312,19 +313,15 @@ struct DraftScope {
 static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, int rows, bool more_forms, hipStream_t st_d) {
   const sd_model* d = s->draft;
   const int V = s->target->cfg.vocab;
-  const sd_row_sampling* const table = p.rows ? s->row_table : nullptr;
   if (p.hand == HAND_FINALIZE)
     return launch_draft_finalize(d->part_val, d->part_idx, d->head_grid, M, i, s->st.draft_ids + (rows - M), s->st, d->skip_k, d->skip_i, st_d);
   if (more_forms) return 0;
   if (p.lp)   // the forward left the logits of its positions in q_pass: process row rows - 1 of every batch row with d_1..d_i
-    if (int rc = launch_logit_process(p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V, s->lp_counts,
-                                      s->lp_bias, s->st.draft_tok, s->K, i, s->st.active, s->lp_rp, s->lp_presence, s->lp_frequency,
-                                      p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2, s->lp_ws, s->lp_ws_bytes, st_d,
-                                      s->fsm ? &s->fsm_bind : nullptr, table))
+    if (int rc = launch_logit_process({p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V}, s->stage,
+                                      s->st.draft_tok, s->K, i, s->st.active, p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2,
+                                      st_d))
       return rc;
-  if (p.hand == HAND_DRAW)
-    return launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p,
-                                  s->seed, s->draw, s->stream_id, st_d, table);
+  if (p.hand == HAND_DRAW) return launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->spec_draw, st_d);
   return launch_draft_next(rows, i, s->st, st_d);
 }
 
@@ -332,7 +329,7 @@ static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, i
 static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
   sd_model* d = s->draft;
   const SpecState& st = s->st;
-  const int B = s->B, V = s->target->cfg.vocab;
+  const int V = s->target->cfg.vocab;
   DraftScope scope(d, s->draft_taps);
   int i = 0;
   if (p.fwd0_select) {
@@ -340,12 +337,23 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     // 1-token pass over `last` alone, whose id and logits row land where the 2-token pass leaves its second ones
     d->skip_k = st.fwd0_w;
     d->skip_i = 1;
-    if (int rc = model_forward(d, st.tok2, 2, st.cur_len, -1, 0, B, 2, p.ids_d, 2, p.q_pass, SD_BF16, 0, st_d)) return rc;
+    ForwardCall f2 = step_forward(st);
+    f2.tokens = st.tok2;
+    f2.tok_stride = f2.M = 2;
+    f2.pos_off = -1;
+    f2.ids_out = p.ids_d;
+    f2.ids_stride = 2;
+    f2.logits_out = p.q_pass;
+    if (int rc = model_forward(d, f2, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, 0, 2, 2, true, st_d)) return rc;
     d->skip_k = st.fwd0_w + 1;
-    if (int rc = model_forward(d, st.tok2 + 1, 2, st.cur_len, 0, 0, B, 1, p.ids_d ? p.ids_d + 1 : nullptr, 2, p.q_pass ? p.q_pass + V : nullptr,
-                               SD_BF16, 0, st_d))
-      return rc;
+    ForwardCall f1 = step_forward(st);
+    f1.tokens = st.tok2 + 1;
+    f1.tok_stride = 2;
+    f1.ids_out = p.ids_d ? p.ids_d + 1 : nullptr;
+    f1.ids_stride = 2;
+    f1.logits_out = p.q_pass ? p.q_pass + V : nullptr;
+    if (int rc = model_forward(d, f1, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, 0, 1, 2, false, st_d)) return rc;
     i = 1;
   }
@@ -354,8 +362,14 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     // per-row adaptive K: forward i >= 1 only matters while some row proposes more than i tokens
     d->skip_k = (st.adaptive && i >= 1) ? st.k_active : nullptr;
     d->skip_i = i;
-    if (int rc = model_forward(d, (i == 0) ? st.tok2 : st.next_tok, M, st.cur_len, (i == 0) ? -1 : i, 0, B, M, p.ids_d, 2, p.q_pass, SD_BF16, 0, st_d))
-      return rc;
+    ForwardCall f = step_forward(st);
+    f.tokens = (i == 0) ? st.tok2 : st.next_tok;
+    f.tok_stride = f.M = M;
+    f.pos_off = (i == 0) ? -1 : i;
+    f.ids_out = p.ids_d;
+    f.ids_stride = 2;
+    f.logits_out = p.q_pass;
+    if (int rc = model_forward(d, f, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, i, M, M, false, st_d)) return rc;
   }
   return 0;
@@ -366,14 +380,15 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
   const int B = s->B, K = s->K, V = s->target->cfg.vocab;
   const unsigned* const st_word_d = (s->draft && s->draft->p_sync) ? s->draft->p_sync + 1 : nullptr;
   const unsigned* const st_word_t = s->target->p_sync ? s->target->p_sync + 1 : nullptr;
-  const sd_row_sampling* const table = p.rows ? s->row_table : nullptr;
-  if (int rc = model_forward(s->target, s->st.verify_tok, K + 1, s->st.cur_len, 0, 0, B, K + 1, p.tail ? nullptr : s->st.target_ids,
-                             K + 1, p.p_buf, SD_BF16, 0, st_t))
-    return rc;
+  ForwardCall f = step_forward(s->st);
+  f.tokens = s->st.verify_tok;
+  f.tok_stride = f.M = K + 1;
+  f.ids_out = p.tail ? nullptr : s->st.target_ids;
+  f.ids_stride = K + 1;
+  f.logits_out = p.p_buf;
+  if (int rc = model_forward(s->target, f, st_t)) return rc;
   if (p.lp)   // all B * (K+1) rows in one launch: row (b, i) is conditioned on d_1..d_i; the processed argmax replaces the fused ids
-    if (int rc = launch_logit_process(p.p_buf, V, B, K + 1, V, s->lp_counts, s->lp_bias, s->st.draft_tok, K, -1, s->st.active, s->lp_rp,
-                                      s->lp_presence, s->lp_frequency, s->st.target_ids, K + 1, s->lp_ws, s->lp_ws_bytes, st_t,
-                                      s->fsm ? &s->fsm_bind : nullptr, table))
+    if (int rc = launch_logit_process({p.p_buf, V, B, K + 1, V}, s->stage, s->st.draft_tok, K, -1, s->st.active, s->st.target_ids, K + 1, st_t))
       return rc;
   if (p.tail) {
     if (int rc = launch_verify_tail(s->st, s->target->part_val, s->target->part_idx, s->target->head_grid, s->mode, s->host_record, s->rec,
@@ -383,26 +398,23 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
     if (p.select == SELECT_SAMPLED_BONUS) {
       // accept length -> draw the token after the accepted prefix from the stored logits of that position
       if (int rc = launch_accept_len(s->st, st_t)) return rc;
-      if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t, table)) return rc;
+      if (int rc = launch_sample_step(s->st, s->logits, V, s->bonus, st_t)) return rc;
     } else if (p.select == SELECT_TYPICAL) {
       // the rule on every stored (processed) row -> accept length; the token after the accepted prefix is the target's id of that
       // position, or drawn from its row when the sampled-bonus mode is on
-      if (int rc = launch_typical_step(s->st, p.p_buf, V, s->acc_rule, s->acc_temperature, s->acc_epsilon, s->acc_delta, s->acc_agree_k,
-                                       !s->sample, s->acc_ws, st_t))
-        return rc;
+      if (int rc = launch_typical_step(s->st, p.p_buf, V, s->accept, !s->sample, s->acc_ws, st_t)) return rc;
       if (s->sample)
-        if (int rc = launch_sample_step(s->st, s->logits, V, s->temperature, s->top_k, s->top_p, s->seed, s->draw, s->stream_id, st_t, table)) return rc;
+        if (int rc = launch_sample_step(s->st, s->logits, V, s->bonus, st_t)) return rc;
     } else if (p.select == SELECT_SPEC) {
       // every position's ratio, flag and candidate in parallel -> accept length and the token after the accepted prefix
-      if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->temperature, p.shaped ? s->spec_top_k : 0, s->spec_top_p, s->seed,
-                                    s->draw, s->stream_id, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t, table))
+      if (int rc = launch_spec_step(s->st, s->spec_p, s->spec_q, V, s->spec_draw, s->spec_flags, s->spec_flags + static_cast<size_t>(B) * (K + 1), st_t))
         return rc;
     }
     const int use_sampled = (p.select == SELECT_SPEC || p.select == SELECT_TYPICAL) ? 2 : (p.select == SELECT_SAMPLED_BONUS ? 1 : 0);
     if (int rc = launch_accept(s->st, s->mode, use_sampled, st_t)) return rc;
     if (p.lp)   // the emitted tokens of every active row enter its counts
-      if (int rc = launch_logit_counts_add(s->lp_counts, B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
-    if (p.lp && s->fsm)   // and advance its automaton state
+      if (int rc = launch_logit_counts_add(const_cast<uint16_t*>(s->stage.counts), B, V, s->st.new_tok, K + 1, s->st.n_new, K + 1, s->st.active, st_t)) return rc;
+    if (p.lp && s->stage.fsm)   // and advance its automaton state
       if (int rc = launch_fsm_advance(s->fsm_bind.next, s->fsm_bind.S, V, const_cast<int32_t*>(s->fsm_bind.state), B, s->st.new_tok, K + 1,
                                       s->st.n_new, K + 1, s->st.active, st_t))
         return rc;
@@ -586,7 +598,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(s->heads.empty() && !s->eagle, "specdec_set_adaptive: stateful draft modes keep a fixed K");
   SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
   SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
-  SD_REQUIRE(!s->acc_rule, "specdec_set_adaptive: the acceptance rule keeps a fixed K (disable sd_specdec_set_acceptance first)");
+  SD_REQUIRE(!s->accept.rule, "specdec_set_adaptive: the acceptance rule keeps a fixed K (disable sd_specdec_set_acceptance first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -645,13 +657,8 @@ extern "C" int sd_specdec_set_sampling(sd_specdec* s, int enable, float temperat
   SD_REQUIRE(temperature == temperature && temperature >= 0.f, "specdec_set_sampling: temperature %g", temperature);
   SD_REQUIRE(top_k <= 0 || (top_k < s->target->cfg.vocab ? top_k : s->target->cfg.vocab) <= 1024, "specdec_set_sampling: top_k=%d > 1024", top_k);
   s->sample = 1;
-  s->temperature = temperature;
-  s->top_k = top_k;
-  s->top_p = top_p;
-  s->seed = seed;
+  s->bonus = DrawSpec{temperature, top_k, top_p, seed, draw_counters, 0, stream_ids, s->bonus.table};
   s->logits = logits_buf;
-  s->draw = draw_counters;
-  s->stream_id = stream_ids;
   return 0;
 }
 
@@ -668,7 +675,7 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_spec_sampling: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
   SD_REQUIRE(s->draft, "specdec_set_spec_sampling: needs a draft model (self-draft, Medusa heads and EAGLE loops propose without a distribution q)");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_spec_sampling: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
-  SD_REQUIRE(!s->acc_rule, "specdec_set_spec_sampling: an acceptance rule is on (sd_specdec_set_acceptance); speculative sampling has its own");
+  SD_REQUIRE(!s->accept.rule, "specdec_set_spec_sampling: an acceptance rule is on (sd_specdec_set_acceptance); speculative sampling has its own");
   SD_REQUIRE(!s->sample, "specdec_set_spec_sampling: the sampled-bonus mode is enabled (sd_specdec_set_sampling); the two modes are mutually exclusive");
   SD_REQUIRE(temperature == temperature && temperature > 0.f, "specdec_set_spec_sampling: temperature %g (must be > 0)", temperature);
   SD_REQUIRE(draft_logits_buf && target_logits_buf && draw_counters, "specdec_set_spec_sampling: NULL logits buffer / draw counters");
@@ -681,12 +688,12 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   if (!s->spec_flags) SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->spec_flags), sizeof(int32_t) * 2 * s->B * (s->K + 1)));
   drop_graph(s);   // the captured step holds the other mode's launches, or this mode's parameters
   s->spec = 1;
-  s->temperature = temperature;
-  s->seed = seed;
+  s->spec_draw.temperature = temperature;   // (top_k / top_p are sd_specdec_set_spec_shaping's, the table sd_specdec_set_row_sampling's)
+  s->spec_draw.seed = seed;
+  s->spec_draw.draw = draw_counters;
+  s->spec_draw.stream_id = stream_ids;
   s->spec_q = draft_logits_buf;
   s->spec_p = target_logits_buf;
-  s->draw = draw_counters;
-  s->stream_id = stream_ids;
   return 0;
 }
 
@@ -699,7 +706,7 @@ extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float 
   if (!enable) {
     if (s->lp) drop_graph(s);   // only if the mode was on: otherwise the captured step holds none of it
     s->lp = 0;
-    s->fsm = 0;                 // the grammar is a line of this stage
+    s->stage.fsm = nullptr;     // the grammar is a line of this stage
     return 0;
   }
   SD_REQUIRE(s->draft, "specdec_set_logit_processors: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
@@ -719,14 +726,9 @@ extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float 
                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "specdec_set_logit_processors: buffers must be 16-byte aligned");
   drop_graph(s);   // the captured step holds the unprocessed launches, or this mode's parameters
   s->lp = 1;
-  s->lp_rp = repetition_penalty;
-  s->lp_presence = presence_penalty;
-  s->lp_frequency = frequency_penalty;
-  s->lp_counts = static_cast<uint16_t*>(counts);
-  s->lp_bias = bias;
+  s->stage = LogitStage{static_cast<uint16_t*>(counts), bias, repetition_penalty, presence_penalty, frequency_penalty, workspace, workspace_bytes_,
+                        s->stage.fsm, s->stage.table};
   s->lp_logits = logits_buf;
-  s->lp_ws = workspace;
-  s->lp_ws_bytes = workspace_bytes_;
   return 0;
 }
 
@@ -734,8 +736,8 @@ extern "C" int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* nex
   clear_error();
   SD_REQUIRE(s, "specdec_set_grammar: NULL");
   if (!enable) {
-    if (s->fsm) drop_graph(s);   // only if a grammar was bound: otherwise the captured step holds none of it
-    s->fsm = 0;
+    if (s->stage.fsm) drop_graph(s);   // only if a grammar was bound: otherwise the captured step holds none of it
+    s->stage.fsm = nullptr;
     return 0;
   }
   SD_REQUIRE(s->draft, "specdec_set_grammar: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
@@ -751,14 +753,8 @@ extern "C" int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* nex
     SD_HIP_CHECK(hipMemset(s->fsm_pos, 0xff, sizeof(int32_t) * s->B * (s->K + 1)));   // (-1; every entry is written before it is read)
   }
   drop_graph(s);   // the captured step holds the launches without the mask, or another grammar's tables
-  s->fsm = 1;
-  s->fsm_bind.next = static_cast<const uint16_t*>(next);
-  s->fsm_bind.allow = static_cast<const uint32_t*>(allow);
-  s->fsm_bind.S = S;
-  s->fsm_bind.state = fsm_state;
-  s->fsm_bind.eos_id = eos_id;
-  s->fsm_bind.pos = s->fsm_pos;
-  s->fsm_bind.pos_stride = s->K + 1;
+  s->fsm_bind = FsmBind{static_cast<const uint16_t*>(next), static_cast<const uint32_t*>(allow), S, fsm_state, eos_id, s->fsm_pos, s->K + 1};
+  s->stage.fsm = &s->fsm_bind;
   return 0;
 }
 
@@ -770,8 +766,8 @@ extern "C" int sd_specdec_set_spec_shaping(sd_specdec* s, int top_k, float top_p
   SD_REQUIRE(top_k <= 1024, "specdec_set_spec_shaping: top_k=%d > 1024 is not supported", top_k);
   SD_REQUIRE(s, "specdec_set_spec_shaping: NULL");
   drop_graph(s);   // unconditional, whether or not speculative sampling is on: the captured step holds the launches of the other shape
-  s->spec_top_k = top_k > 0 ? top_k : 0;
-  s->spec_top_p = top_k > 0 ? top_p : 1.0f;
+  s->spec_draw.top_k = top_k > 0 ? top_k : 0;
+  s->spec_draw.top_p = top_k > 0 ? top_p : 1.0f;
   return 0;
 }
 
@@ -780,12 +776,12 @@ extern "C" int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling*
   SD_REQUIRE(s, "specdec_set_row_sampling: NULL");
   if (table) {
     SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "specdec_set_row_sampling: the row table must be 16-byte aligned");
-    SD_REQUIRE(!s->acc_rule, "specdec_set_row_sampling: an acceptance rule is on (sd_specdec_set_acceptance): its parameters are the loop's, not a row's");
+    SD_REQUIRE(!s->accept.rule, "specdec_set_row_sampling: an acceptance rule is on (sd_specdec_set_acceptance): its parameters are the loop's, not a row's");
     SD_REQUIRE(s->sample || s->spec || s->lp, "specdec_set_row_sampling: neither a sampling mode nor the logit-processor stage is on "
                "(sd_specdec_set_sampling / sd_specdec_set_spec_sampling / sd_specdec_set_logit_processors first)");
   }
   drop_graph(s);   // unconditional: the captured step holds either the scalar launches or the row launches
-  s->row_table = table;
+  s->bonus.table = s->spec_draw.table = s->stage.table = table;
   return 0;
 }
 
@@ -794,30 +790,27 @@ extern "C" int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperat
   clear_error();
   SD_REQUIRE(s, "specdec_set_acceptance: NULL");
   if (rule == SD_ACCEPT_OFF) {
-    if (s->acc_rule) drop_graph(s);   // only if a rule was on: otherwise the captured step holds none of it
-    s->acc_rule = 0;
+    if (s->accept.rule) drop_graph(s);   // only if a rule was on: otherwise the captured step holds none of it
+    s->accept.rule = SD_ACCEPT_OFF;
     return 0;
   }
   const int V = s->target->cfg.vocab;
-  if (int rc = check_typical_params("specdec_set_acceptance", rule, temperature, epsilon, delta, agree_k, s->K, V)) return rc;
+  const AcceptRule r{rule, temperature, epsilon, delta, agree_k};
+  if (int rc = check_typical_params("specdec_set_acceptance", r, s->K, V)) return rc;
   SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_acceptance: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
   SD_REQUIRE(!s->eagle, "specdec_set_acceptance: EAGLE loops are not supported (the rule judges a draft model's proposals)");
   SD_REQUIRE(s->heads.empty(), "specdec_set_acceptance: Medusa heads are not supported (the rule judges a draft model's proposals)");
   SD_REQUIRE(s->draft, "specdec_set_acceptance: the tied self-draft is not supported (the rule judges a draft model's proposals)");
   SD_REQUIRE(!s->spec, "specdec_set_acceptance: speculative sampling is enabled (sd_specdec_set_spec_sampling); it has its own acceptance rule");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_acceptance: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
-  SD_REQUIRE(!s->row_table, "specdec_set_acceptance: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
+  SD_REQUIRE(!s->stage.table, "specdec_set_acceptance: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
   SD_REQUIRE(logits_buf || s->sample, "specdec_set_acceptance: NULL logits buffer (the sampled-bonus mode is not on to lend its own)");
   const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
   SD_REQUIRE(!logits_buf || logits_bytes >= need, "specdec_set_acceptance: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need);
   SD_REQUIRE((reinterpret_cast<uintptr_t>(logits_buf) & 15) == 0, "specdec_set_acceptance: the logits buffer must be 16-byte aligned");
   if (!s->acc_ws) SD_HIP_CHECK(hipMalloc(&s->acc_ws, typical_accept_workspace(s->B, s->K)));
   drop_graph(s);   // the captured step holds the exact-match launches, or this rule's parameters
-  s->acc_rule = rule;
-  s->acc_temperature = temperature;
-  s->acc_epsilon = epsilon;
-  s->acc_delta = delta;
-  s->acc_agree_k = agree_k;
+  s->accept = r;
   s->acc_logits = logits_buf;
   return 0;
 }

@@ -145,8 +145,7 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_kernel(const S
   spec_draft_draw_row(G, a, s, blockIdx.x);
 }
 
-static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, float temperature,
-                                   uint64_t seed, const uint32_t* draw, const int32_t* stream_id) {
+static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, const DrawSpec& d) {
   SpecDrawArgs a{};
   a.src = static_cast<const uint16_t*>(src);
   a.src_rows_per_b = src_rows_per_b;
@@ -154,11 +153,11 @@ static SpecDrawArgs spec_draw_args(const void* src, int src_rows_per_b, int src_
   a.q = static_cast<uint16_t*>(q);
   a.i = i;
   a.V = V;
-  a.temperature = temperature;
-  a.seed_lo = seed_lo32(seed);
-  a.seed_hi = seed_hi32(seed);
-  a.draw = draw;
-  a.stream_id = stream_id;
+  a.temperature = d.temperature;
+  a.seed_lo = seed_lo32(d.seed);
+  a.seed_hi = seed_hi32(d.seed);
+  a.draw = d.draw;
+  a.stream_id = d.stream_id;
   return a;
 }
 
@@ -304,20 +303,19 @@ __global__ __launch_bounds__(kWave) void spec_accept_kernel(const SpecAcceptArgs
 
 // flag / cand: [B][K+1] each; the step passes draw0 = 0 and no ratios, the stand-alone ops their caller's
 static SpecStatArgs spec_stat_args(const void* target_logits, const void* draft_logits, const int32_t* draft_ids, int K, int V,
-                                   float temperature, uint64_t seed, const uint32_t* draw, uint32_t draw0, const int32_t* stream_id,
-                                   const int32_t* active, int32_t* flag, int32_t* cand, double* ratios) {
+                                   const DrawSpec& d, const int32_t* active, int32_t* flag, int32_t* cand, double* ratios) {
   SpecStatArgs sa{};
   sa.P = static_cast<const uint16_t*>(target_logits);
   sa.Q = static_cast<const uint16_t*>(draft_logits);
   sa.draft_ids = draft_ids;
   sa.K = K;
   sa.V = V;
-  sa.temperature = temperature;
-  sa.seed_lo = seed_lo32(seed);
-  sa.seed_hi = seed_hi32(seed);
-  sa.draw = draw;
-  sa.draw0 = draw0;
-  sa.stream_id = stream_id;
+  sa.temperature = d.temperature;
+  sa.seed_lo = seed_lo32(d.seed);
+  sa.seed_hi = seed_hi32(d.seed);
+  sa.draw = d.draw;
+  sa.draw0 = d.draw0;
+  sa.stream_id = d.stream_id;
   sa.active = active;
   sa.flag = flag;
   sa.cand = cand;
@@ -388,24 +386,23 @@ __global__ __launch_bounds__(kSampleThreads) void spec_draft_draw_rows_kernel(co
 
 // the draw + hand-over after a draft forward; top_k == 0: spec_draft_draw_kernel, else the shaped kernel; with a table the row
 // kernel, whatever the scalars say
-int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V,
-                           float temperature, int top_k, float top_p, uint64_t seed, const uint32_t* draw, const int32_t* stream_id,
-                           hipStream_t st, const sd_row_sampling* table) {
-  SD_REQUIRE(src && q && draw, "spec_draft_draw: NULL buffer");
-  const SpecDrawArgs a = spec_draw_args(src, src_rows_per_b, src_row, q, i, V, temperature, seed, draw, stream_id);
-  if (table) {
+int launch_spec_draft_draw(const SpecState& s, const void* src, int src_rows_per_b, int src_row, void* q, int i, int V, const DrawSpec& d,
+                           hipStream_t st) {
+  SD_REQUIRE(src && q && d.draw, "spec_draft_draw: NULL buffer");
+  const SpecDrawArgs a = spec_draw_args(src, src_rows_per_b, src_row, q, i, V, d);
+  if (d.table) {
     SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && V <= (1 << kIdxBits) && src_rows_per_b >= 1 && src_row >= 0 && src_row < src_rows_per_b,
                "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
-    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_draft_draw: the row table must be 16-byte aligned");
-    hipLaunchKernelGGL(spec_draft_draw_rows_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, table, s);
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(d.table) & 15) == 0, "spec_draft_draw: the row table must be 16-byte aligned");
+    hipLaunchKernelGGL(spec_draft_draw_rows_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, d.table, s);
     SD_LAUNCH_CHECK();
     return 0;
   }
-  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && (top_k <= 0 || V <= (1 << kIdxBits)) && src_rows_per_b >= 1 && src_row >= 0 &&
+  SD_REQUIRE(i >= 0 && i < s.K && V >= 1 && (d.top_k <= 0 || V <= (1 << kIdxBits)) && src_rows_per_b >= 1 && src_row >= 0 &&
                  src_row < src_rows_per_b, "spec_draft_draw: i=%d V=%d row %d of %d", i, V, src_row, src_rows_per_b);
-  if (top_k > 0) {
-    if (int rc = check_spec_shape("spec_draft_draw", top_k, top_p)) return rc;
-    hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{top_k, top_p}, s);
+  if (d.top_k > 0) {
+    if (int rc = check_spec_shape("spec_draft_draw", d.top_k, d.top_p)) return rc;
+    hipLaunchKernelGGL(spec_draft_draw_shaped_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, SpecShape{d.top_k, d.top_p}, s);
   } else {
     hipLaunchKernelGGL(spec_draft_draw_kernel, dim3(s.B), dim3(kSampleThreads), 0, st, a, s);
   }
@@ -510,22 +507,21 @@ __global__ __launch_bounds__(kSampleThreads) void spec_stats_rows_kernel(const S
 }
 
 // statistics, then accept; top_k == 0: spec_stats_kernel, else the shaped kernel; with a table the row kernel
-static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, int top_k, float top_p, hipStream_t st,
-                               const sd_row_sampling* table = nullptr) {
-  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && ((top_k <= 0 && !table) || sa.V <= (1 << kIdxBits)),
+static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa, int B, const DrawSpec& d, hipStream_t st) {
+  SD_REQUIRE(B >= 1 && B <= 65535 && sa.K >= 1 && sa.K <= 63 && sa.V >= 1 && ((d.top_k <= 0 && !d.table) || sa.V <= (1 << kIdxBits)),
              "spec_sample: B=%d K=%d V=%d out of range", B, sa.K, sa.V);
-  if (table) {
-    SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_sample: the row table must be 16-byte aligned");
-    hipLaunchKernelGGL(spec_stats_rows_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, table);
+  if (d.table) {
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(d.table) & 15) == 0, "spec_sample: the row table must be 16-byte aligned");
+    hipLaunchKernelGGL(spec_stats_rows_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, d.table);
     SD_LAUNCH_CHECK();
     hipLaunchKernelGGL(spec_accept_kernel, dim3(B), dim3(kWave), 0, st, aa);
     SD_LAUNCH_CHECK();
     return 0;
   }
   SD_REQUIRE(sa.temperature == sa.temperature && sa.temperature > 0.f, "spec_sample: temperature %g (must be > 0)", sa.temperature);
-  if (top_k > 0) {
-    if (int rc = check_spec_shape("spec_sample", top_k, top_p)) return rc;
-    hipLaunchKernelGGL(spec_stats_shaped_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, SpecShape{top_k, top_p});
+  if (d.top_k > 0) {
+    if (int rc = check_spec_shape("spec_sample", d.top_k, d.top_p)) return rc;
+    hipLaunchKernelGGL(spec_stats_shaped_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa, SpecShape{d.top_k, d.top_p});
   } else {
     hipLaunchKernelGGL(spec_stats_kernel, dim3(sa.K + 1, B), dim3(kSampleThreads), 0, st, sa);
   }
@@ -536,14 +532,12 @@ static int launch_spec_kernels(const SpecStatArgs& sa, const SpecAcceptArgs& aa,
 }
 
 // the step's statistics + accept: accept length -> s.accept_len, next token -> s.sampled, counters advanced
-int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, uint32_t* draw, const int32_t* stream_id, int32_t* flag, int32_t* cand, hipStream_t st,
-                     const sd_row_sampling* table) {
-  SD_REQUIRE(target_logits && draft_logits && draw && flag && cand, "spec_step: NULL buffer");
-  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, s.draft_tok, s.K, V, temperature, seed, draw, 0, stream_id, s.active,
-                                         flag, cand, nullptr);
-  const SpecAcceptArgs aa{flag, cand, s.K, s.active, draw, s.accept_len, s.sampled};
-  return launch_spec_kernels(sa, aa, s.B, top_k, top_p, st, table);
+int launch_spec_step(const SpecState& s, const void* target_logits, const void* draft_logits, int V, const DrawSpec& d, int32_t* flag,
+                     int32_t* cand, hipStream_t st) {
+  SD_REQUIRE(target_logits && draft_logits && d.draw && flag && cand, "spec_step: NULL buffer");
+  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, s.draft_tok, s.K, V, d, s.active, flag, cand, nullptr);
+  const SpecAcceptArgs aa{flag, cand, s.K, s.active, d.draw, s.accept_len, s.sampled};
+  return launch_spec_kernels(sa, aa, s.B, d, st);
 }
 
 }  // namespace sd
@@ -555,12 +549,10 @@ extern "C" size_t sd_spec_sample_workspace(int B, int K) {
   return static_cast<size_t>(B) * (K + 1) * 2 * sizeof(int32_t);
 }
 
-// the stand-alone op, shaped (top_k > 0) or not; `who` is the op's name in the messages
-static int spec_sample_accept_op(const char* who, int top_k, float top_p, const void* draft_logits, const void* target_logits,
-                                 const int32_t* draft_ids, int B, int K, int V, float temperature, uint64_t seed, uint32_t* draw_counters,
-                                 uint32_t draw0, const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out,
-                                 int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes, void* stream,
-                                 const sd_row_sampling* table = nullptr) {
+// the stand-alone op, shaped (d.top_k > 0), by row (d.table) or neither; `who` is the op's name in the messages
+static int spec_sample_accept_op(const char* who, const DrawSpec& d, const void* draft_logits, const void* target_logits,
+                                 const int32_t* draft_ids, int B, int K, int V, const int32_t* active, int32_t* accept_len_out,
+                                 int32_t* next_tok_out, double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
   SD_REQUIRE(draft_logits && target_logits && draft_ids && accept_len_out && next_tok_out && workspace, "%s: NULL argument", who);
   SD_REQUIRE(B >= 1 && K >= 1, "%s: B=%d K=%d", who, B, K);
   SD_REQUIRE(workspace_bytes >= sd_spec_sample_workspace(B, K), "%s: workspace %zu B < %zu B", who, workspace_bytes,
@@ -569,10 +561,9 @@ static int spec_sample_accept_op(const char* who, int top_k, float top_p, const 
              "%s: misaligned workspace / ratios", who);
   int32_t* flag = static_cast<int32_t*>(workspace);
   int32_t* cand = flag + static_cast<size_t>(B) * (K + 1);
-  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, temperature, seed, draw_counters, draw0, stream_ids,
-                                         active, flag, cand, ratios_out);
-  const SpecAcceptArgs aa{flag, cand, K, active, draw_counters, accept_len_out, next_tok_out};
-  return launch_spec_kernels(sa, aa, B, top_k, top_p, static_cast<hipStream_t>(stream), table);
+  const SpecStatArgs sa = spec_stat_args(target_logits, draft_logits, draft_ids, K, V, d, active, flag, cand, ratios_out);
+  const SpecAcceptArgs aa{flag, cand, K, active, d.draw, accept_len_out, next_tok_out};
+  return launch_spec_kernels(sa, aa, B, d, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
@@ -580,9 +571,9 @@ extern "C" int sd_spec_sample_accept(const void* draft_logits, const void* targe
                                      const int32_t* stream_ids, const int32_t* active, int32_t* accept_len_out, int32_t* next_tok_out,
                                      double* ratios_out, void* workspace, size_t workspace_bytes, void* stream) {
   clear_error();
-  return spec_sample_accept_op("spec_sample_accept", 0, 1.0f, draft_logits, target_logits, draft_ids, B, K, V, temperature, seed,
-                               draw_counters, draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace,
-                               workspace_bytes, stream);
+  const DrawSpec d{temperature, 0, 1.0f, seed, draw_counters, draw0, stream_ids};
+  return spec_sample_accept_op("spec_sample_accept", d, draft_logits, target_logits, draft_ids, B, K, V, active, accept_len_out,
+                               next_tok_out, ratios_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K,
@@ -595,9 +586,9 @@ extern "C" int sd_spec_sample_accept_shaped(const void* draft_logits, const void
   SD_REQUIRE(top_k > 0, "spec_sample_accept_shaped: top_k=%d with top_p=%g: the shaped op needs a top_k in 1..1024 (top_p without top_k, "
              "the full-vocabulary nucleus, is not supported; the unshaped op is sd_spec_sample_accept)", top_k, top_p);
   SD_REQUIRE(top_k <= kSampleMaxK, "spec_sample_accept_shaped: top_k=%d > %d is not supported", top_k, kSampleMaxK);
-  return spec_sample_accept_op("spec_sample_accept_shaped", top_k, top_p, draft_logits, target_logits, draft_ids, B, K, V, temperature,
-                               seed, draw_counters, draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace,
-                               workspace_bytes, stream);
+  const DrawSpec d{temperature, top_k, top_p, seed, draw_counters, draw0, stream_ids};
+  return spec_sample_accept_op("spec_sample_accept_shaped", d, draft_logits, target_logits, draft_ids, B, K, V, active, accept_len_out,
+                               next_tok_out, ratios_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sd_spec_sample_accept_rows(const void* draft_logits, const void* target_logits, const int32_t* draft_ids, int B, int K, int V,
@@ -608,6 +599,7 @@ extern "C" int sd_spec_sample_accept_rows(const void* draft_logits, const void* 
   SD_REQUIRE(table, "spec_sample_accept_rows: NULL table");
   SD_REQUIRE(B >= 1, "spec_sample_accept_rows: B=%d", B);
   SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "spec_sample_accept_rows: the row table must be 16-byte aligned");
-  return spec_sample_accept_op("spec_sample_accept_rows", 0, 1.0f, draft_logits, target_logits, draft_ids, B, K, V, 1.0f, 0, draw_counters,
-                               draw0, stream_ids, active, accept_len_out, next_tok_out, ratios_out, workspace, workspace_bytes, stream, table);
+  const DrawSpec d{1.0f, 0, 1.0f, 0, draw_counters, draw0, stream_ids, table};   // the scalars are not in the launch
+  return spec_sample_accept_op("spec_sample_accept_rows", d, draft_logits, target_logits, draft_ids, B, K, V, active, accept_len_out,
+                               next_tok_out, ratios_out, workspace, workspace_bytes, stream);
 }

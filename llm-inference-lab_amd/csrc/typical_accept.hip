@@ -172,16 +172,17 @@ __global__ __launch_bounds__(kWave) void typical_accept_kernel(const TypicalAcce
 }
 
 // Every check of the two launches in one place: the stand-alone op and the step setter both go through it. 0 = ok.
-int check_typical_params(const char* who, int rule, float temperature, float epsilon, float delta, int agree_k, int K, int V) {
-  SD_REQUIRE(rule == SD_ACCEPT_TYPICAL || rule == SD_ACCEPT_TOPK_AGREE, "%s: unknown rule %d (1 = typical, 2 = top-k agreement)", who, rule);
+int check_typical_params(const char* who, const AcceptRule& r, int K, int V) {
+  SD_REQUIRE(r.rule == SD_ACCEPT_TYPICAL || r.rule == SD_ACCEPT_TOPK_AGREE, "%s: unknown rule %d (1 = typical, 2 = top-k agreement)", who, r.rule);
   SD_REQUIRE(K >= 1 && K <= 63, "%s: K=%d out of range 1..63", who, K);
   SD_REQUIRE(V >= 1, "%s: V=%d", who, V);
-  SD_REQUIRE(temperature == temperature && temperature > 0.f && temperature < INFINITY, "%s: temperature %g (must be > 0)", who, temperature);
-  if (rule == SD_ACCEPT_TYPICAL) {
-    SD_REQUIRE(epsilon > 0.f && epsilon <= 1.0f, "%s: epsilon %g outside (0, 1]", who, epsilon);
-    SD_REQUIRE(delta == delta && delta > 0.f, "%s: delta %g (must be > 0; +inf = the fixed threshold epsilon)", who, delta);
+  SD_REQUIRE(r.temperature == r.temperature && r.temperature > 0.f && r.temperature < INFINITY, "%s: temperature %g (must be > 0)", who,
+             r.temperature);
+  if (r.rule == SD_ACCEPT_TYPICAL) {
+    SD_REQUIRE(r.epsilon > 0.f && r.epsilon <= 1.0f, "%s: epsilon %g outside (0, 1]", who, r.epsilon);
+    SD_REQUIRE(r.delta == r.delta && r.delta > 0.f, "%s: delta %g (must be > 0; +inf = the fixed threshold epsilon)", who, r.delta);
   } else {
-    SD_REQUIRE(agree_k >= 1 && agree_k <= V, "%s: agree_k %d outside 1..V (%d)", who, agree_k, V);
+    SD_REQUIRE(r.agree_k >= 1 && r.agree_k <= V, "%s: agree_k %d outside 1..V (%d)", who, r.agree_k, V);
   }
   return 0;
 }
@@ -192,13 +193,14 @@ size_t typical_accept_workspace(int B, int K) {
 }
 
 // the parameters are checked (check_typical_params) by the caller
-int launch_typical_accept(const void* logits, int dtype, int64_t row_stride, const int32_t* draft_ids, int B, int K, int V, int rule,
-                          float temperature, float epsilon, float delta, int agree_k, const int32_t* active, int32_t* accept_len,
-                          const int32_t* target_ids, int32_t* next_tok, float* stats, void* workspace, hipStream_t st) {
+int launch_typical_accept(const void* logits, int dtype, int64_t row_stride, const int32_t* draft_ids, int B, int K, int V,
+                          const AcceptRule& r, const int32_t* active, int32_t* accept_len, const int32_t* target_ids, int32_t* next_tok,
+                          float* stats, void* workspace, hipStream_t st) {
   SD_REQUIRE(B >= 1 && B <= 65535, "typical_accept: B=%d out of range", B);
   int32_t* flag = static_cast<int32_t*>(workspace);
   float* rec = reinterpret_cast<float*>(flag + static_cast<size_t>(B) * K);
-  const TypicalArgs ta{logits, dtype, row_stride, draft_ids, K, V, rule, temperature, epsilon, delta, agree_k, active, target_ids, flag, rec};
+  const TypicalArgs ta{logits, dtype, row_stride, draft_ids, K, V, r.rule, r.temperature, r.epsilon, r.delta, r.agree_k, active, target_ids,
+                       flag, rec};
   hipLaunchKernelGGL(typical_row_kernel, dim3(K, B), dim3(kSampleThreads), 0, st, ta);
   SD_LAUNCH_CHECK();
   const TypicalAcceptArgs aa{flag, rec, K, active, accept_len, target_ids, next_tok, stats};
@@ -209,12 +211,11 @@ int launch_typical_accept(const void* logits, int dtype, int64_t row_stride, con
 
 // the step's two launches: accept length -> s.accept_len; the target's id after the accepted prefix -> s.sampled unless the
 // sampled-bonus draw follows (next_from_ids == false)
-int launch_typical_step(const SpecState& s, const void* logits, int V, int rule, float temperature, float epsilon, float delta,
-                        int agree_k, bool next_from_ids, void* workspace, hipStream_t st) {
+int launch_typical_step(const SpecState& s, const void* logits, int V, const AcceptRule& r, bool next_from_ids, void* workspace,
+                        hipStream_t st) {
   SD_REQUIRE(logits && workspace, "typical_step: NULL buffer");
-  return launch_typical_accept(logits, SD_BF16, V, s.draft_tok, s.B, s.K, V, rule, temperature, epsilon, delta, agree_k, s.active,
-                               s.accept_len, s.target_ids, next_from_ids ? s.sampled : nullptr, nullptr,
-                               workspace, st);
+  return launch_typical_accept(logits, SD_BF16, V, s.draft_tok, s.B, s.K, V, r, s.active, s.accept_len, s.target_ids,
+                               next_from_ids ? s.sampled : nullptr, nullptr, workspace, st);
 }
 
 }  // namespace sd
@@ -233,12 +234,13 @@ extern "C" int sd_typical_accept(const void* target_logits, int logits_dtype, in
   SD_REQUIRE(target_logits && draft_ids && accept_len && workspace, "typical_accept: NULL argument");
   SD_REQUIRE(logits_dtype == SD_F32 || logits_dtype == SD_BF16 || logits_dtype == SD_F16, "typical_accept: logits dtype %d", logits_dtype);
   SD_REQUIRE(B >= 1, "typical_accept: B=%d", B);
-  if (int rc = check_typical_params("typical_accept", rule, temperature, epsilon, delta, agree_k, K, V)) return rc;
+  const AcceptRule r{rule, temperature, epsilon, delta, agree_k};
+  if (int rc = check_typical_params("typical_accept", r, K, V)) return rc;
   SD_REQUIRE(row_stride >= V, "typical_accept: row_stride %lld below V (%d)", static_cast<long long>(row_stride), V);
   SD_REQUIRE(workspace_bytes >= typical_accept_workspace(B, K), "typical_accept: workspace %zu B < %zu B", workspace_bytes,
              typical_accept_workspace(B, K));
   SD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && (reinterpret_cast<uintptr_t>(stats) & 3) == 0,
              "typical_accept: misaligned workspace / stats");
-  return launch_typical_accept(target_logits, logits_dtype, row_stride, draft_ids, B, K, V, rule, temperature, epsilon, delta, agree_k,
-                               nullptr, accept_len, nullptr, nullptr, stats, workspace, static_cast<hipStream_t>(stream));
+  return launch_typical_accept(target_logits, logits_dtype, row_stride, draft_ids, B, K, V, r, nullptr, accept_len, nullptr, nullptr, stats,
+                               workspace, static_cast<hipStream_t>(stream));
 }

@@ -780,6 +780,23 @@ class HipSpecDec:
         """Forget the extrapolation state of every row (start of new sequences); ordered on the loop's target stream."""
         _abi.check(self.lib.sd_specdec_reset_eagle(self.handle, self.stream_t.cuda_stream), "sd_specdec_reset_eagle")
 
+    @property
+    def _vocab(self) -> int:
+        return self.target.weights.config.vocab
+
+    def _step_logits(self) -> torch.Tensor:
+        """The step's [B][K+1][V] bf16 logits, allocated at first use: every mode that stores the verify rows shares them."""
+        if self._logits is None:
+            self._logits = torch.empty((self.B, self.K + 1, self._vocab), dtype=torch.bfloat16, device=self.device)
+        return self._logits
+
+    def _upload_draws(self, draw_counts: Optional[Sequence[int]], stream_ids: Optional[Sequence[int]]) -> None:
+        """Draw counters (default 0: a new run) and Philox stream ids (default: the row's index), on the current stream."""
+        draws = list(draw_counts) if draw_counts is not None else [0] * self.B
+        sid = list(stream_ids) if stream_ids is not None else list(range(self.B))
+        self._draw = torch.tensor(draws, dtype=torch.int32, device=self.device)
+        self._stream_ids = torch.tensor(sid, dtype=torch.int32, device=self.device)
+
     def set_sampling(self, enable: bool, temperature: float = 1.0, top_k: Optional[int] = None,
                      top_p: Optional[float] = None, seed: int = 0, stream_ids: Optional[Sequence[int]] = None,
                      draw_counts: Optional[Sequence[int]] = None):
@@ -791,17 +808,12 @@ class HipSpecDec:
                            "sd_specdec_set_sampling")
                 self.sampling = False
                 return
-            V = self.target.weights.config.vocab
-            if self._logits is None:
-                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
-            self._draw = torch.tensor(list(draw_counts) if draw_counts is not None else [0] * self.B, dtype=torch.int32,
-                                      device=self.device)
-            sid = list(stream_ids) if stream_ids is not None else list(range(self.B))
-            self._stream_ids = torch.tensor(sid, dtype=torch.int32, device=self.device)
+            logits = self._step_logits()
+            self._upload_draws(draw_counts, stream_ids)
             torch.cuda.current_stream(self.device).synchronize()
             _abi.check(self.lib.sd_specdec_set_sampling(
                 self.handle, 1, float(temperature), int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p),
-                int(seed) & (2 ** 64 - 1), self._logits.data_ptr(), self._logits.numel() * 2, self._draw.data_ptr(),
+                int(seed) & (2 ** 64 - 1), logits.data_ptr(), logits.numel() * 2, self._draw.data_ptr(),
                 self._stream_ids.data_ptr()), "sd_specdec_set_sampling")
             self.sampling = True
 
@@ -823,19 +835,14 @@ class HipSpecDec:
             _abi.check(self.lib.sd_specdec_set_spec_shaping(self.handle, int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p)),
                        "sd_specdec_set_spec_shaping")
             self.spec_shape = (int(top_k), 1.0 if top_p is None else float(top_p)) if top_k else None
-            V = self.target.weights.config.vocab
-            if self._logits is None:
-                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+            logits = self._step_logits()
             if self._draft_logits is None:
-                self._draft_logits = torch.empty((self.B, self.K, V), dtype=torch.bfloat16, device=self.device)
-            self._draw = torch.tensor(list(draw_counts) if draw_counts is not None else [0] * self.B, dtype=torch.int32,
-                                      device=self.device)
-            sid = list(stream_ids) if stream_ids is not None else list(range(self.B))
-            self._stream_ids = torch.tensor(sid, dtype=torch.int32, device=self.device)
+                self._draft_logits = torch.empty((self.B, self.K, self._vocab), dtype=torch.bfloat16, device=self.device)
+            self._upload_draws(draw_counts, stream_ids)
             torch.cuda.current_stream(self.device).synchronize()
             _abi.check(self.lib.sd_specdec_set_spec_sampling(
                 self.handle, 1, float(temperature), int(seed) & (2 ** 64 - 1), self._draft_logits.data_ptr(),
-                self._draft_logits.numel() * 2, self._logits.data_ptr(), self._logits.numel() * 2, self._draw.data_ptr(),
+                self._draft_logits.numel() * 2, logits.data_ptr(), logits.numel() * 2, self._draw.data_ptr(),
                 self._stream_ids.data_ptr()), "sd_specdec_set_spec_sampling")
             self.spec_sampling = True
 
@@ -854,9 +861,8 @@ class HipSpecDec:
                 self.logit_processors = False
                 self.grammar = None        # the grammar is a line of this stage: the library unbinds it too
                 return
-            V = self.target.weights.config.vocab
-            if self._logits is None:
-                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+            V = self._vocab
+            logits = self._step_logits()
             if self.logit_counts is None:
                 self.logit_counts = torch.zeros((self.B, V), dtype=torch.int16, device=self.device)
                 self._lp_ws = torch.empty(max(int(self.lib.sd_logit_process_workspace(self.B, self.K + 1, V)), 16), dtype=torch.uint8,
@@ -868,7 +874,7 @@ class HipSpecDec:
             _abi.check(self.lib.sd_specdec_set_logit_processors(
                 self.handle, 1, float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
                 self.logit_counts.data_ptr(), self.logit_counts.numel() * 2, b.data_ptr() if b is not None else None,
-                b.numel() * 4 if b is not None else 0, self._logits.data_ptr(), self._logits.numel() * 2, self._lp_ws.data_ptr(),
+                b.numel() * 4 if b is not None else 0, logits.data_ptr(), logits.numel() * 2, self._lp_ws.data_ptr(),
                 self._lp_ws.numel()), "sd_specdec_set_logit_processors")
             self.logit_processors = True
 
@@ -887,13 +893,13 @@ class HipSpecDec:
                 return
             if rule not in _abi.ACCEPT_RULES:
                 raise ValueError(f"set_acceptance: rule {rule!r} (one of {sorted(_abi.ACCEPT_RULES)})")
-            V = self.target.weights.config.vocab
-            if self._logits is None:
-                self._logits = torch.empty((self.B, self.K + 1, V), dtype=torch.bfloat16, device=self.device)
+            fresh = self._logits is None
+            logits = self._step_logits()
+            if fresh:
                 torch.cuda.current_stream(self.device).synchronize()
             _abi.check(self.lib.sd_specdec_set_acceptance(
                 self.handle, _abi.ACCEPT_RULES[rule], float(temperature), float(epsilon), float("inf") if delta is None else float(delta),
-                int(agree_k), self._logits.data_ptr(), self._logits.numel() * 2), "sd_specdec_set_acceptance")
+                int(agree_k), logits.data_ptr(), logits.numel() * 2), "sd_specdec_set_acceptance")
             self.acceptance = rule
 
     def set_logit_counts_row(self, b: int, prompt_ids: Sequence[int], generated_ids: Sequence[int] = ()) -> None:
@@ -917,7 +923,7 @@ class HipSpecDec:
                 _abi.check(self.lib.sd_specdec_set_grammar(self.handle, 0, None, None, 0, None, 0), "sd_specdec_set_grammar")
                 self.grammar = None
                 return
-            V = self.target.weights.config.vocab
+            V = self._vocab
             if fsm.V != V:
                 raise ValueError(f"set_grammar: the automaton is over {fsm.V} tokens, the models' vocabulary has {V}")
             if id(fsm) not in self._grammar_tables:

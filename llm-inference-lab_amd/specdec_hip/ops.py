@@ -310,6 +310,50 @@ def kv_append_with_mask_hip(
     return out_k, out_v
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _check_entry_vectors(name: str, B: int, dev, **tensors: Optional[torch.Tensor]) -> None:
+    """The optional per-entry vectors of an op (pos, draw_counters, stream_ids, active, ...), by argument name."""
+    for arg, t in tensors.items():
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"{name}: {arg} must be a contiguous int32 [{B}] tensor on {dev}")
+
+
+def _entry_rows(name: str, logits: torch.Tensor, rows_per_entry: int):
+    """The [rows, V] logits of a draw op, unit stride along V -> (logits, device, entries, V)."""
+    if logits.dim() == 1:
+        logits = logits.unsqueeze(0)
+    if logits.dim() != 2:
+        raise ValueError(f"{name}: logits must be [rows, V], got {tuple(logits.shape)}")
+    dev = _require_device(name, logits)
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    rows, V = logits.shape
+    if rows % rows_per_entry:
+        raise ValueError(f"{name}: {rows} rows is not a multiple of rows_per_entry={rows_per_entry}")
+    return logits, dev, rows // rows_per_entry, V
+
+
+def _sample_token(name: str, logits, draw, pos, rows_per_entry, draw_counters, stream_ids, active, scalars=None, table=None) -> torch.Tensor:
+    """sample_token_hip (`scalars`: temperature, top_k, top_p, seed as the library takes them) / sample_token_rows_hip (`table`)."""
+    lib = _abi.load()
+    logits, dev, B, V = _entry_rows(name, logits, rows_per_entry)
+    _check_entry_vectors(name, B, dev, pos=pos, draw_counters=draw_counters, stream_ids=stream_ids, active=active)
+    if table is not None:
+        table = _row_table(name, table, B, dev)
+    out = torch.empty(B, dtype=torch.int32, device=dev)
+    head = (logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0), B, V, _ptr(pos), int(rows_per_entry), _ptr(active))
+    tail = (_ptr(draw_counters), int(draw) & 0xFFFFFFFF, _ptr(stream_ids), out.data_ptr(), _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        if table is None:
+            _abi.check(lib.sd_sample_token(*head, *scalars, *tail), "sd_sample_token")
+        else:
+            _abi.check(lib.sd_sample_token_rows(*head, table.data_ptr(), *tail), "sd_sample_token_rows")
+    return out
+
+
 def sample_token_hip(logits: torch.Tensor, temperature: float, top_k: Optional[int] = None, top_p: Optional[float] = None,
                      seed: int = 0, draw: int = 0, pos: Optional[torch.Tensor] = None, rows_per_entry: int = 1,
                      draw_counters: Optional[torch.Tensor] = None, stream_ids: Optional[torch.Tensor] = None,
@@ -320,31 +364,42 @@ def sample_token_hip(logits: torch.Tensor, temperature: float, top_k: Optional[i
     logits: [rows, V] (or [V]) f32/bf16/f16 on the GPU, unit stride along V. Entry b reads row
     b*rows_per_entry + pos[b]. Returns int32 [entries]. `draw` (or the int32 `draw_counters`, read
     and incremented on the device) and `stream_ids` select the Philox value; see include/specdec_hip.h."""
+    scalars = (float(temperature), int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p), int(seed) & (2 ** 64 - 1))
+    return _sample_token("sample_token", logits, draw, pos, rows_per_entry, draw_counters, stream_ids, active, scalars=scalars)
+
+
+def _spec_triple(name: str, draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor):
+    """(draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]) of a speculative-sampling op, made contiguous
+    -> (draft_logits, target_logits, draft_ids, device, B, K, V)."""
+    dev = _require_device(name, draft_logits, target_logits, draft_ids)
+    if draft_logits.dim() != 3 or target_logits.dim() != 3 or draft_ids.dim() != 2:
+        raise ValueError(f"{name}: need draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]")
+    B, K, V = draft_logits.shape
+    if tuple(target_logits.shape) != (B, K + 1, V) or tuple(draft_ids.shape) != (B, K):
+        raise ValueError(f"{name}: shapes {tuple(draft_logits.shape)} / {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
+    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16 or draft_ids.dtype != torch.int32:
+        raise TypeError(f"{name}: logits must be bfloat16 and draft_ids int32")
+    return draft_logits.contiguous(), target_logits.contiguous(), draft_ids.contiguous(), dev, B, K, V
+
+
+def _spec_sample_accept(name: str, draft_logits, target_logits, draft_ids, draw, draw_counters, stream_ids, active, return_ratios,
+                        symbol: str = "sd_spec_sample_accept_rows", scalars: tuple = (), table=None):
+    """spec_sample_accept_hip (`symbol`: the shaped or the unshaped entry point, `scalars`: what it takes between V and the draw
+    counters) / spec_sample_accept_rows_hip (`table` in their place)."""
     lib = _abi.load()
-    if logits.dim() == 1:
-        logits = logits.unsqueeze(0)
-    if logits.dim() != 2:
-        raise ValueError(f"sample_token: logits must be [rows, V], got {tuple(logits.shape)}")
-    dev = _require_device("sample_token", logits)
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    rows, V = logits.shape
-    if rows % rows_per_entry:
-        raise ValueError(f"sample_token: {rows} rows is not a multiple of rows_per_entry={rows_per_entry}")
-    B = rows // rows_per_entry
-    for name, t in (("pos", pos), ("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
-        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"sample_token: {name} must be a contiguous int32 [{B}] tensor on {dev}")
-    k = int(top_k) if top_k else 0
-    p = 1.0 if top_p is None else float(top_p)
-    out = torch.empty(B, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    draft_logits, target_logits, draft_ids, dev, B, K, V = _spec_triple(name, draft_logits, target_logits, draft_ids)
+    _check_entry_vectors(name, B, dev, draw_counters=draw_counters, stream_ids=stream_ids, active=active)
+    params = scalars if table is None else (_row_table(name, table, B, dev).data_ptr(),)
+    accept = torch.zeros(B, dtype=torch.int32, device=dev)
+    nxt = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
+    ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _abi.check(lib.sd_sample_token(logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0), B, V, ptr(pos),
-                                       int(rows_per_entry), ptr(active), float(temperature), k, p, int(seed) & (2 ** 64 - 1),
-                                       ptr(draw_counters), int(draw) & 0xFFFFFFFF, ptr(stream_ids), out.data_ptr(),
-                                       _stream_ptr(dev)), "sd_sample_token")
-    return out
+        _abi.check(getattr(lib, symbol)(
+            draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V, *params, _ptr(draw_counters),
+            int(draw) & 0xFFFFFFFF, _ptr(stream_ids), _ptr(active), accept.data_ptr(), nxt.data_ptr(), _ptr(ratios), ws.data_ptr(),
+            ws.numel(), _stream_ptr(dev)), symbol)
+    return (accept, nxt, ratios) if return_ratios else (accept, nxt)
 
 
 def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor, temperature: float,
@@ -360,38 +415,14 @@ def spec_sample_accept_hip(draft_logits: torch.Tensor, target_logits: torch.Tens
     q_i). Returns (accept_len int32 [B], next_tok int32 [B]) and, with return_ratios, the float64 [B, K] ratios
     p_i(d)/q_i(d). Row b's draws use counter `draw` (or the int32 `draw_counters`, advanced by K + 1 on the device) and
     Philox stream stream_ids[b] (default b); see include/specdec_hip.h for the schedule."""
-    lib = _abi.load()
-    dev = _require_device("spec_sample_accept", draft_logits, target_logits, draft_ids)
-    if draft_logits.dim() != 3 or target_logits.dim() != 3 or draft_ids.dim() != 2:
-        raise ValueError("spec_sample_accept: need draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]")
-    B, K, V = draft_logits.shape
-    if tuple(target_logits.shape) != (B, K + 1, V) or tuple(draft_ids.shape) != (B, K):
-        raise ValueError(f"spec_sample_accept: shapes {tuple(draft_logits.shape)} / {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
-    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16 or draft_ids.dtype != torch.int32:
-        raise TypeError("spec_sample_accept: logits must be bfloat16 and draft_ids int32")
-    draft_logits, target_logits, draft_ids = draft_logits.contiguous(), target_logits.contiguous(), draft_ids.contiguous()
-    for name, t in (("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
-        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"spec_sample_accept: {name} must be a contiguous int32 [{B}] tensor on {dev}")
-    accept = torch.zeros(B, dtype=torch.int32, device=dev)
-    nxt = torch.full((B,), -1, dtype=torch.int32, device=dev)
-    ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
-    ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    seed = int(seed) & (2 ** 64 - 1)
     if top_k or (top_p is not None and float(top_p) < 1.0):
-        with torch.cuda.device(dev):
-            _abi.check(lib.sd_spec_sample_accept_shaped(
-                draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V, float(temperature),
-                int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p), int(seed) & (2 ** 64 - 1), ptr(draw_counters),
-                int(draw) & 0xFFFFFFFF, ptr(stream_ids), ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios), ws.data_ptr(),
-                ws.numel(), _stream_ptr(dev)), "sd_spec_sample_accept_shaped")
-        return (accept, nxt, ratios) if return_ratios else (accept, nxt)
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_spec_sample_accept(draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V,
-                                             float(temperature), int(seed) & (2 ** 64 - 1), ptr(draw_counters), int(draw) & 0xFFFFFFFF,
-                                             ptr(stream_ids), ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios),
-                                             ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "sd_spec_sample_accept")
-    return (accept, nxt, ratios) if return_ratios else (accept, nxt)
+        symbol = "sd_spec_sample_accept_shaped"
+        scalars = (float(temperature), int(top_k) if top_k else 0, 1.0 if top_p is None else float(top_p), seed)
+    else:
+        symbol, scalars = "sd_spec_sample_accept", (float(temperature), seed)
+    return _spec_sample_accept("spec_sample_accept", draft_logits, target_logits, draft_ids, draw, draw_counters, stream_ids, active,
+                               return_ratios, symbol, scalars)
 
 
 def typical_accept_workspace(B: int, K: int, V: int, device) -> torch.Tensor:
@@ -463,30 +494,7 @@ def sample_token_rows_hip(logits: torch.Tensor, table, draw: int = 0, pos: Optio
     """sample_token_hip with every entry's own temperature, top_k, top_p and seed (sd_sample_token_rows): `table` is a list of
     SamplingParams, one per entry, or their packed tensor. Entry b's result is that of sample_token_hip on its row alone with
     its normalised parameters, the same draw and the same stream id."""
-    lib = _abi.load()
-    if logits.dim() == 1:
-        logits = logits.unsqueeze(0)
-    if logits.dim() != 2:
-        raise ValueError(f"sample_token_rows: logits must be [rows, V], got {tuple(logits.shape)}")
-    dev = _require_device("sample_token_rows", logits)
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    rows, V = logits.shape
-    if rows % rows_per_entry:
-        raise ValueError(f"sample_token_rows: {rows} rows is not a multiple of rows_per_entry={rows_per_entry}")
-    B = rows // rows_per_entry
-    for name, t in (("pos", pos), ("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
-        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"sample_token_rows: {name} must be a contiguous int32 [{B}] tensor on {dev}")
-    table = _row_table("sample_token_rows", table, B, dev)
-    out = torch.empty(B, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_sample_token_rows(logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0), B, V, ptr(pos),
-                                            int(rows_per_entry), ptr(active), table.data_ptr(), ptr(draw_counters),
-                                            int(draw) & 0xFFFFFFFF, ptr(stream_ids), out.data_ptr(), _stream_ptr(dev)),
-                   "sd_sample_token_rows")
-    return out
+    return _sample_token("sample_token_rows", logits, draw, pos, rows_per_entry, draw_counters, stream_ids, active, table=table)
 
 
 def spec_sample_accept_rows_hip(draft_logits: torch.Tensor, target_logits: torch.Tensor, draft_ids: torch.Tensor, table, draw: int = 0,
@@ -496,31 +504,8 @@ def spec_sample_accept_rows_hip(draft_logits: torch.Tensor, target_logits: torch
     without top_k and top_p runs the unshaped statistics, any other row the shaped ones; a row the speculative-sampling
     kernels cannot honour (temperature 0, top_p without top_k, ...) is a greedy row. Shapes and results as
     spec_sample_accept_hip."""
-    lib = _abi.load()
-    dev = _require_device("spec_sample_accept_rows", draft_logits, target_logits, draft_ids)
-    if draft_logits.dim() != 3 or target_logits.dim() != 3 or draft_ids.dim() != 2:
-        raise ValueError("spec_sample_accept_rows: need draft_logits [B,K,V], target_logits [B,K+1,V], draft_ids [B,K]")
-    B, K, V = draft_logits.shape
-    if tuple(target_logits.shape) != (B, K + 1, V) or tuple(draft_ids.shape) != (B, K):
-        raise ValueError(f"spec_sample_accept_rows: shapes {tuple(draft_logits.shape)} / {tuple(target_logits.shape)} / {tuple(draft_ids.shape)}")
-    if draft_logits.dtype != torch.bfloat16 or target_logits.dtype != torch.bfloat16 or draft_ids.dtype != torch.int32:
-        raise TypeError("spec_sample_accept_rows: logits must be bfloat16 and draft_ids int32")
-    draft_logits, target_logits, draft_ids = draft_logits.contiguous(), target_logits.contiguous(), draft_ids.contiguous()
-    for name, t in (("draw_counters", draw_counters), ("stream_ids", stream_ids), ("active", active)):
-        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"spec_sample_accept_rows: {name} must be a contiguous int32 [{B}] tensor on {dev}")
-    table = _row_table("spec_sample_accept_rows", table, B, dev)
-    accept = torch.zeros(B, dtype=torch.int32, device=dev)
-    nxt = torch.full((B,), -1, dtype=torch.int32, device=dev)
-    ratios = torch.full((B, K), float("nan"), dtype=torch.float64, device=dev) if return_ratios else None
-    ws = torch.empty(max(lib.sd_spec_sample_workspace(B, K), 4), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_spec_sample_accept_rows(draft_logits.data_ptr(), target_logits.data_ptr(), draft_ids.data_ptr(), B, K, V,
-                                                  table.data_ptr(), ptr(draw_counters), int(draw) & 0xFFFFFFFF, ptr(stream_ids),
-                                                  ptr(active), accept.data_ptr(), nxt.data_ptr(), ptr(ratios), ws.data_ptr(), ws.numel(),
-                                                  _stream_ptr(dev)), "sd_spec_sample_accept_rows")
-    return (accept, nxt, ratios) if return_ratios else (accept, nxt)
+    return _spec_sample_accept("spec_sample_accept_rows", draft_logits, target_logits, draft_ids, draw, draw_counters, stream_ids, active,
+                               return_ratios, table=table)
 
 
 def logit_counts(B: int, V: int, device) -> torch.Tensor:
@@ -535,6 +520,59 @@ def _check_counts(name: str, counts: torch.Tensor, dev) -> Tuple[int, int]:
     return int(counts.shape[0]), int(counts.shape[1])
 
 
+def _check_fsm(name: str, nxt: torch.Tensor, allow: torch.Tensor, fsm_state: torch.Tensor, B: int, V: int, dev) -> int:
+    """The automaton tables (fsm_tables) and the rows' states of a grammar over V tokens -> S."""
+    S, Vn = _check_fsm_table(name, nxt, dev)
+    if Vn != V or allow.dtype != torch.int32 or tuple(allow.shape) != (S, (V + 31) // 32) or not allow.is_contiguous():
+        raise ValueError(f"{name}: tables {tuple(nxt.shape)} / {tuple(allow.shape)} for V={V} (fsm_tables)")
+    if fsm_state.dtype != torch.int32 or fsm_state.numel() != B or not fsm_state.is_contiguous():
+        raise ValueError(f"{name}: fsm_state must be a contiguous int32 [{B}] tensor")
+    return S
+
+
+def _logit_process(name: str, rows, counts, bias, tokens, n_tokens, active, return_ids, penalties=None, table=None, fsm=None):
+    """logit_process / logit_process_fsm (`penalties`: the three scalars) and logit_process_rows_hip (`table`); fsm: (nxt, allow,
+    fsm_state, eos_id) or None."""
+    lib = _abi.load()
+    dev = _require_device(name, rows, counts, *(fsm[:3] if fsm else ()))
+    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: rows must be bfloat16 [B][R][V]")
+    B, R, V = (int(x) for x in rows.shape)
+    if _check_counts(name, counts, dev) != (B, V):
+        raise ValueError(f"{name}: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
+    S = _check_fsm(name, *fsm[:3], B, V, dev) if fsm else 0
+    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
+    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
+        raise ValueError(f"{name}: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
+        raise ValueError(f"{name}: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
+    n_tok = -1 if n_tokens is None else int(n_tokens)
+    tok_stride = 0
+    if tokens is not None:
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
+            raise ValueError(f"{name}: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
+        tok_stride = int(tokens.shape[1])
+    _check_entry_vectors(name, B, dev, active=active)
+    if table is not None:
+        table = _row_table(name, table, B, dev)
+    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
+    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
+    head = (rows.data_ptr(), stride, B, R, V, counts.data_ptr(), _ptr(bias), _ptr(tokens), tok_stride, n_tok, _ptr(active))
+    out = (_ptr(ids), R, _ptr(ws), ws.numel() if ws is not None else 0)
+    with torch.cuda.device(dev):
+        if table is not None:
+            nxt, allow, fsm_state, eos_id = fsm or (None, None, None, 0)
+            _abi.check(lib.sd_logit_process_rows(*head, table.data_ptr(), *out, _ptr(nxt), _ptr(allow), S, _ptr(fsm_state), int(eos_id),
+                                                 _stream_ptr(dev)), "sd_logit_process_rows")
+        elif fsm:
+            nxt, allow, fsm_state, eos_id = fsm
+            _abi.check(lib.sd_logit_process_fsm(*head, *penalties, *out, nxt.data_ptr(), allow.data_ptr(), S, fsm_state.data_ptr(),
+                                                int(eos_id), _stream_ptr(dev)), "sd_logit_process_fsm")
+        else:
+            _abi.check(lib.sd_logit_process(*head, *penalties, *out, _stream_ptr(dev)), "sd_logit_process")
+    return ids
+
+
 def logit_process(rows: torch.Tensor, counts: torch.Tensor, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                   frequency_penalty: float = 0.0, bias: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
                   n_tokens: Optional[int] = None, active: Optional[torch.Tensor] = None, return_ids: bool = False):
@@ -545,34 +583,8 @@ def logit_process(rows: torch.Tensor, counts: torch.Tensor, repetition_penalty: 
     logit_counts(B, V); bias: optional float32 [B][V]; tokens: optional int32 [B][n], row b's in-step tokens; n_tokens: None =
     row (b, r) is conditioned on the first r tokens (the verify pass), else every row on the first n_tokens; active: optional
     int32 [B], rows with 0 are not written. Returns None, or with return_ids the int32 [B][R] argmax of each processed row."""
-    lib = _abi.load()
-    dev = _require_device("logit_process", rows, counts)
-    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
-        raise ValueError("logit_process: rows must be bfloat16 [B][R][V]")
-    B, R, V = (int(x) for x in rows.shape)
-    if _check_counts("logit_process", counts, dev) != (B, V):
-        raise ValueError(f"logit_process: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
-    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
-    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
-        raise ValueError("logit_process: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
-        raise ValueError(f"logit_process: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
-    n_tok = -1 if n_tokens is None else int(n_tokens)
-    tok_stride = 0
-    if tokens is not None:
-        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
-            raise ValueError(f"logit_process: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
-        tok_stride = int(tokens.shape[1])
-    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
-        raise ValueError(f"logit_process: active must be a contiguous int32 [{B}] tensor on {dev}")
-    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
-    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_logit_process(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
-                                        ptr(active), float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
-                                        ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr(dev)), "sd_logit_process")
-    return ids
+    return _logit_process("logit_process", rows, counts, bias, tokens, n_tokens, active, return_ids,
+                          penalties=(float(repetition_penalty), float(presence_penalty), float(frequency_penalty)))
 
 
 def logit_counts_set(counts: torch.Tensor, b: int, prompt_ids: Optional[torch.Tensor] = None,
@@ -598,13 +610,11 @@ def logit_counts_add(counts: torch.Tensor, tokens: torch.Tensor, n_new: torch.Te
     B, V = _check_counts("logit_counts_add", counts, dev)
     if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or not tokens.is_contiguous():
         raise ValueError(f"logit_counts_add: tokens must be a contiguous int32 [{B}][n] tensor")
-    for name, t in (("n_new", n_new), ("active", active)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"logit_counts_add: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    _check_entry_vectors("logit_counts_add", B, dev, n_new=n_new, active=active)
     n = int(tokens.shape[1])
     with torch.cuda.device(dev):
         _abi.check(_abi.load().sd_logit_counts_add(counts.data_ptr(), B, V, tokens.data_ptr(), n, n_new.data_ptr(), n,
-                                                   active.data_ptr() if active is not None else None, _stream_ptr(dev)), "sd_logit_counts_add")
+                                                   _ptr(active), _stream_ptr(dev)), "sd_logit_counts_add")
 
 
 def _check_fsm_table(name: str, nxt: torch.Tensor, dev) -> Tuple[int, int]:
@@ -643,40 +653,9 @@ def logit_process_fsm(rows: torch.Tensor, counts: torch.Tensor, nxt: torch.Tenso
     """logit_process with the grammar line (sd_logit_process_fsm): row (b, r) is masked by the state its automaton reaches from
     fsm_state[b] (int32 [B]; -1 = unconstrained) over the row's in-step tokens; a disallowed element is stored as -inf. nxt /
     allow: fsm_tables. Everything else as logit_process."""
-    lib = _abi.load()
-    dev = _require_device("logit_process_fsm", rows, counts, nxt, allow, fsm_state)
-    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
-        raise ValueError("logit_process_fsm: rows must be bfloat16 [B][R][V]")
-    B, R, V = (int(x) for x in rows.shape)
-    if _check_counts("logit_process_fsm", counts, dev) != (B, V):
-        raise ValueError(f"logit_process_fsm: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
-    S, Vn = _check_fsm_table("logit_process_fsm", nxt, dev)
-    if Vn != V or allow.dtype != torch.int32 or tuple(allow.shape) != (S, (V + 31) // 32) or not allow.is_contiguous():
-        raise ValueError(f"logit_process_fsm: tables {tuple(nxt.shape)} / {tuple(allow.shape)} for V={V} (fsm_tables)")
-    if fsm_state.dtype != torch.int32 or fsm_state.numel() != B or not fsm_state.is_contiguous():
-        raise ValueError(f"logit_process_fsm: fsm_state must be a contiguous int32 [{B}] tensor")
-    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
-    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
-        raise ValueError("logit_process_fsm: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
-        raise ValueError(f"logit_process_fsm: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
-    n_tok = -1 if n_tokens is None else int(n_tokens)
-    tok_stride = 0
-    if tokens is not None:
-        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
-            raise ValueError(f"logit_process_fsm: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
-        tok_stride = int(tokens.shape[1])
-    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
-        raise ValueError(f"logit_process_fsm: active must be a contiguous int32 [{B}] tensor on {dev}")
-    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
-    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_logit_process_fsm(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
-                                            ptr(active), float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
-                                            ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0, nxt.data_ptr(), allow.data_ptr(), S,
-                                            fsm_state.data_ptr(), int(eos_id), _stream_ptr(dev)), "sd_logit_process_fsm")
-    return ids
+    return _logit_process("logit_process_fsm", rows, counts, bias, tokens, n_tokens, active, return_ids,
+                          penalties=(float(repetition_penalty), float(presence_penalty), float(frequency_penalty)),
+                          fsm=(nxt, allow, fsm_state, eos_id))
 
 
 def logit_process_rows_hip(rows: torch.Tensor, counts: torch.Tensor, table, bias: Optional[torch.Tensor] = None,
@@ -686,45 +665,11 @@ def logit_process_rows_hip(rows: torch.Tensor, counts: torch.Tensor, table, bias
     """logit_process / logit_process_fsm with every batch row's own penalties (sd_logit_process_rows): `table` is a list of
     SamplingParams, one per batch row, or their packed tensor; a row whose penalties the scalar op would refuse is processed
     with the identity. nxt / allow / fsm_state: the grammar of logit_process_fsm, all None for none."""
-    lib = _abi.load()
     grammar = nxt is not None or allow is not None or fsm_state is not None
     if grammar and (nxt is None or allow is None or fsm_state is None):
         raise ValueError("logit_process_rows: a grammar needs nxt, allow and fsm_state")
-    dev = _require_device("logit_process_rows", rows, counts, *([nxt, allow, fsm_state] if grammar else []))
-    if rows.dim() != 3 or rows.dtype != torch.bfloat16:
-        raise ValueError("logit_process_rows: rows must be bfloat16 [B][R][V]")
-    B, R, V = (int(x) for x in rows.shape)
-    if _check_counts("logit_process_rows", counts, dev) != (B, V):
-        raise ValueError(f"logit_process_rows: counts {tuple(counts.shape)} for rows {tuple(rows.shape)}")
-    S = 0
-    if grammar:
-        S, Vn = _check_fsm_table("logit_process_rows", nxt, dev)
-        if Vn != V or allow.dtype != torch.int32 or tuple(allow.shape) != (S, (V + 31) // 32) or not allow.is_contiguous():
-            raise ValueError(f"logit_process_rows: tables {tuple(nxt.shape)} / {tuple(allow.shape)} for V={V} (fsm_tables)")
-        if fsm_state.dtype != torch.int32 or fsm_state.numel() != B or not fsm_state.is_contiguous():
-            raise ValueError(f"logit_process_rows: fsm_state must be a contiguous int32 [{B}] tensor")
-    stride = int(rows.stride(1)) if R > 1 else (int(rows.stride(0)) if B > 1 else V)
-    if rows.stride(2) != 1 or stride < V or (B > 1 and rows.stride(0) != R * stride):
-        raise ValueError("logit_process_rows: rows must have a unit inner stride and one constant stride >= V between consecutive rows (in place: no copy is made)")
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (B, V) or bias.device != dev or not bias.is_contiguous()):
-        raise ValueError(f"logit_process_rows: bias must be a contiguous float32 [{B}][{V}] tensor on {dev}")
-    n_tok = -1 if n_tokens is None else int(n_tokens)
-    tok_stride = 0
-    if tokens is not None:
-        if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or tokens.device != dev or not tokens.is_contiguous():
-            raise ValueError(f"logit_process_rows: tokens must be a contiguous int32 [{B}][n] tensor on {dev}")
-        tok_stride = int(tokens.shape[1])
-    if active is not None and (active.dtype != torch.int32 or active.numel() != B or active.device != dev or not active.is_contiguous()):
-        raise ValueError(f"logit_process_rows: active must be a contiguous int32 [{B}] tensor on {dev}")
-    table = _row_table("logit_process_rows", table, B, dev)
-    ids = torch.empty((B, R), dtype=torch.int32, device=dev) if return_ids else None
-    ws = torch.empty(max(lib.sd_logit_process_workspace(B, R, V), 16), dtype=torch.uint8, device=dev) if return_ids else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.sd_logit_process_rows(rows.data_ptr(), stride, B, R, V, counts.data_ptr(), ptr(bias), ptr(tokens), tok_stride, n_tok,
-                                             ptr(active), table.data_ptr(), ptr(ids), R, ptr(ws), ws.numel() if ws is not None else 0,
-                                             ptr(nxt), ptr(allow), S, ptr(fsm_state), int(eos_id), _stream_ptr(dev)), "sd_logit_process_rows")
-    return ids
+    return _logit_process("logit_process_rows", rows, counts, bias, tokens, n_tokens, active, return_ids, table=table,
+                          fsm=(nxt, allow, fsm_state, eos_id) if grammar else None)
 
 
 def fsm_advance(nxt: torch.Tensor, fsm_state: torch.Tensor, tokens: torch.Tensor, n_new: torch.Tensor,
@@ -738,13 +683,11 @@ def fsm_advance(nxt: torch.Tensor, fsm_state: torch.Tensor, tokens: torch.Tensor
         raise ValueError("fsm_advance: fsm_state must be a contiguous int32 [B] tensor")
     if tokens.dim() != 2 or tokens.dtype != torch.int32 or tokens.shape[0] != B or not tokens.is_contiguous():
         raise ValueError(f"fsm_advance: tokens must be a contiguous int32 [{B}][n] tensor")
-    for name, t in (("n_new", n_new), ("active", active)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"fsm_advance: {name} must be a contiguous int32 [{B}] tensor on {dev}")
+    _check_entry_vectors("fsm_advance", B, dev, n_new=n_new, active=active)
     n = int(tokens.shape[1])
     with torch.cuda.device(dev):
         _abi.check(_abi.load().sd_fsm_advance(nxt.data_ptr(), S, V, fsm_state.data_ptr(), B, tokens.data_ptr(), n, n_new.data_ptr(), n,
-                                              active.data_ptr() if active is not None else None, _stream_ptr(dev)), "sd_fsm_advance")
+                                              _ptr(active), _stream_ptr(dev)), "sd_fsm_advance")
 
 
 def spec_agreement(draft_logits: torch.Tensor, target_logits: torch.Tensor, temperature: float = 1.0):
