@@ -136,6 +136,17 @@ int sd_typical_accept(const void* target_logits, int logits_dtype, int64_t row_s
                       int rule, float temperature, float epsilon, float delta, int agree_k, int32_t* accept_len, float* stats,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* The confidence of a logits row (csrc/draft_confidence.hip): conf[b] = 1 / sum_v exp(x_v - max_v x_v) over the STORED values of
+ * row b — the softmax probability, at temperature 1, of the row's largest value. logits: B rows of V elements (f32 / f16 /
+ * bf16), row_stride elements apart (>= V); a row need not be 16-byte aligned (aligned rows take 16-byte loads). An element at
+ * -inf adds 0; a row whose maximum is not finite (+inf, or every element -inf) or that holds a NaN gives NaN. fp32, the
+ * running-maximum stream and merge order of sd_typical_accept's row pass (one 1024-thread workgroup per row, the wave xor tree,
+ * then the 16 wave partials in order): bit-identical run to run, no atomics, no waiting. The confidence-gated step
+ * (sd_specdec_set_draft_confidence) runs the same device function on the draft's rows. Asynchronous on `stream`, no allocation,
+ * graph-capturable. Refused: a NULL pointer, an unknown dtype, B outside 1..65535, V < 1, a stride below V, a misaligned conf.
+ * Additive (SD_ABI_VERSION stays 1). */
+int sd_draft_confidence(const void* logits, int logits_dtype, int64_t row_stride, int B, int V, float* conf, void* stream);
+
 /* Draft-target agreement of two logit blocks (csrc/spec_agree.hip): how much of the target's distribution a draft reproduces,
  * position by position, without generating. draft_logits / target_logits: bf16, n rows of V elements, rows ld_q / ld_p
  * elements apart (>= V). Per row t, in float64 over the stored bf16 values, x / T as sd_spec_sample_accept forms it (T the
@@ -908,6 +919,37 @@ int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k, int min_k,
 int sd_specdec_set_adaptive_row(sd_specdec* s, int b, int k, int accepted, int proposed, int hist_n,
                                 const double* hist, void* stream);
 
+/* Confidence-gated draft length inside the captured step (csrc/draft_confidence.hip; the stopping rule of HF assisted generation's
+ * assistant_confidence_threshold, decided on the device between two draft forwards). The loop keeps its SHAPE K. For row b and
+ * draft forward i = 0..K-1, with x the bf16 logits row of the forward's last position as the forward stores it and d_{i+1} its
+ * fused argmax, as without the mode:
+ *   confidence   c_i = sd_draft_confidence(x): the temperature-1 softmax probability of the largest stored value, NaN for a
+ *                row with a NaN or a maximum that is not finite
+ *   stop         k_b = the smallest i + 1 >= min_k with !(c_i >= tau), else K. The token drawn at low confidence is still
+ *                proposed (HF's ConfidenceCriteria); a NaN stops the row
+ *   what counts  only row b's first k_b proposals: accept length = min(longest matching prefix, k_b); emitted tokens, the bonus
+ *                token, the state advance and the form of the next draft forward 0 follow from that length exactly as
+ *                sd_specdec_set_adaptive defines them for k_row[b]
+ *   record       slot [5+3K] is k_b
+ *   gating       draft forward i >= 1 runs iff some active row has k_b > i; otherwise each of its launches returns at entry. Draft
+ *                token slots past the widest row's k_b are unspecified; a row that stopped rides along in later forwards and its
+ *                tokens there do not count
+ *   reset        k_b starts at K in every step: nothing is carried between steps, the host mirrors nothing
+ * One launch per judged forward (i = min_k-1 .. K-2; forward K-1 needs no judgement) follows the forward's hand-over launch on the
+ * draft's stream: one 1024-thread workgroup per row; a row that stops writes k_b, a row that continues stores the constant i + 2 into
+ * the gate word of forward i + 1 (every writer stores the same value: no atomic, no reduction across rows). The step's last
+ * launch on the target stream puts the words back; nothing is added on the target stream. Only judged forwards store a row.
+ * logits_buf: caller-owned bf16, sd_specdec_draft_confidence_bytes(B, V) bytes ([B][2][V]: the two positions of draft forward 0),
+ * 16-byte aligned. conf_out (nullable, device float [B][K], 4-byte aligned): the step's c_i for every judged forward that ran, NaN
+ * elsewhere; the call itself fills it with NaN, so it reads NaN before the first step and where no forward is judged (min_k == K). enable = 0 (the default): the step is launch for launch and bit for bit what it is without this call. Either call
+ * drops the captured graph. Refused: tau outside (0, 1] or NaN; min_k outside 1..K; a NULL, short or misaligned buffer; loops
+ * without a draft model (self-draft, Medusa heads, EAGLE); SD_EMIT_DRAFT; and while on: per-row adaptive K, speculative sampling,
+ * an acceptance rule, logit processors / a grammar, a bound row-sampling table — whose setters in turn refuse while this mode is
+ * on. The sampled-bonus mode stays allowed (it concerns the target's rows). Additive (SD_ABI_VERSION stays 1). */
+size_t sd_specdec_draft_confidence_bytes(int B, int V);
+int sd_specdec_set_draft_confidence(sd_specdec* s, int enable, float tau, int min_k, void* logits_buf, size_t logits_bytes,
+                                    float* conf_out);
+
 /* EAGLE-lite drafting (the reference's _run_eagle_hf, src/specdec/core/pipeline.py:765-889, under greedy decoding), for
  * a loop created with draft = NULL: every step runs a 1-token target forward for the residual row of the last token,
  * h_t = final_norm(row); extrapolates K hidden rows h_1 = h_t + alpha (h_t - E), h_2 = h_1 + alpha (h_1 - h_t), ...
@@ -994,7 +1036,8 @@ int sd_specdec_sync(sd_specdec* s, void* stream);
  *   [3 .. 3+K]            emitted tokens (n_new valid, -1 padded)
  *   [4+K .. 3+2K]         draft tokens d_1..d_K
  *   [4+2K .. 4+3K]        target argmax t_0..t_K
- *   [5+3K]                proposals that counted for the row in this step (K unless sd_specdec_set_adaptive)
+ *   [5+3K]                proposals that counted for the row in this step (K unless sd_specdec_set_adaptive /
+ *                         sd_specdec_set_draft_confidence)
  *   [6+3K]                health word of the models' persistent launches (sd_model_engine_status), 0 = all completed
  * row stride = sd_specdec_record_ints(). */
 const int32_t* sd_specdec_record(const sd_specdec* s);

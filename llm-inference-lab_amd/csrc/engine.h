@@ -137,6 +137,12 @@ struct SpecState {
   int32_t* ctl;         // [B][4] accepted so far, proposed so far, history length (<= 4), k of the step just done
   double* ctl_hist;     // [B][4] the last four reported acceptance rates, oldest first
   int32_t* k_active;    // [1]    max k_row over the active rows
+  // confidence-gated draft length (sd_specdec_set_draft_confidence, csrc/draft_confidence.hip): k_row[b] is rewritten INSIDE every
+  // step by the judgement launches of the draft loop (K at the start of a step, i + 1 once forward i's confidence stops the row) and
+  // read where per-row adaptive K reads it; the step's last launch puts k_row and the gate words back. The two modes exclude each other.
+  int conf;             // 0 = off
+  int32_t* conf_gate;   // [8]    word i gates draft forward i (runs iff word > i): 0 between steps, i + 1 once a row continues past
+                        //        forward i - 1; forwards below min_k are not gated
   // one-sequence loops with a persistent draft: which form of draft forward 0 the NEXT step needs. {2, 1}: the 2-token
   // pass over (prev, last) — prev's K/V are not in the draft cache yet (all k proposals were accepted: d_k was never an
   // input, or the host has just set the row); {1, 2}: prev's K/V are there, the 1-token pass over `last` is enough.
@@ -144,7 +150,7 @@ struct SpecState {
   int32_t* fwd0_w;      // [2]    null: always the 2-token pass
 };
 
-int launch_draft_next(int M, int i, const SpecState& s, hipStream_t st);
+int launch_draft_next(int M, int i, const SpecState& s, const int32_t* skip_k, hipStream_t st);
 int launch_draft_finalize(const float* part_val, const int* part_idx, int grid, int M, int i, int32_t* ids, const SpecState& s,
                           const int32_t* skip_k, int skip_i, hipStream_t st);
 int launch_argmax_value(const float* part_val, const int* part_idx, int T, int grid, int M, int stride, float* vals, hipStream_t st);
@@ -200,6 +206,17 @@ int check_typical_params(const char* who, const AcceptRule& r, int K, int V);
 size_t typical_accept_workspace(int B, int K);
 int launch_typical_step(const SpecState& s, const void* logits, int V, const AcceptRule& r, bool next_from_ids, void* workspace,
                         hipStream_t st);
+
+// csrc/draft_confidence.hip: the judgement after draft forward i of the confidence-gated step. rows: the last position's bf16 row of
+// batch row b at rows + b * row_stride elements. Gated like the forward it follows (skip_k / skip_i); a continuing row opens
+// s.conf_gate[i + 1]. first: the step's first judgement also fills the other slots of conf_out's row with NaN.
+struct ConfRule {
+  float tau = 1.0f;
+  int min_k = 1;
+  float* conf_out = nullptr;   // nullable [B][K]
+};
+int launch_confidence_judge(const SpecState& s, const uint16_t* rows, long long row_stride, int V, int i, const ConfRule& r, bool first,
+                            const int32_t* skip_k, int skip_i, hipStream_t st);
 
 // csrc/grammar.hip: token automata (grammar-constrained decoding). next: uint16 [S][V], 0xFFFF = the token is not allowed in the
 // state; allow: the same as one bit per token, uint32 [S][ceil(V / 32)]. A row's state: -1 unconstrained, 0..S-1, else DEAD

@@ -111,8 +111,8 @@ int launch_argmax_value(const float* part_val, const int* part_idx, int T, int g
 
 // ---- draft: token i of the proposal ------------------------------------------------
 // The draft forward produced M tokens per row; the last one's argmax is d_{i+1}.
-__global__ void draft_next_kernel(int M, int i, SpecState s) {
-  if (s.adaptive && i >= 1) SD_SKIP_IF_INACTIVE(s.k_active, i);   // forward i did not run: d_{i+1} counts for no row
+__global__ void draft_next_kernel(int M, int i, SpecState s, const int32_t* skip_k) {
+  SD_SKIP_IF_INACTIVE(skip_k, i);   // the word forward i was gated on (null: none): it did not run, d_{i+1} counts for no row
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= s.B) return;
   const int d = s.draft_ids[b * 2 + (M - 1)];
@@ -289,8 +289,8 @@ int launch_medusa_fill(const SpecState& s, hipStream_t st) {
   return 0;
 }
 
-int launch_draft_next(int M, int i, const SpecState& s, hipStream_t st) {
-  hipLaunchKernelGGL(draft_next_kernel, dim3((s.B + 63) / 64), dim3(64), 0, st, M, i, s);
+int launch_draft_next(int M, int i, const SpecState& s, const int32_t* skip_k, hipStream_t st) {
+  hipLaunchKernelGGL(draft_next_kernel, dim3((s.B + 63) / 64), dim3(64), 0, st, M, i, s, skip_k);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -310,7 +310,7 @@ __device__ __forceinline__ int accept_scan(const SpecState& s, int b, int lane, 
   const unsigned long long valid = (K >= 64) ? ~0ull : ((1ull << K) - 1ull);
   const unsigned long long miss = (~m64) & valid;
   const int a = miss ? __builtin_ctzll(miss) : K;
-  return s.adaptive ? min(a, s.k_row[b]) : a;   // per-row K: proposals past k_row[b] do not count
+  return (s.adaptive || s.conf) ? min(a, s.k_row[b]) : a;   // per-row K: proposals past k_row[b] do not count
 }
 
 // AdaptiveKController.get_k (controllers.py:100-126) for one row, fed with the row's own cumulative acceptance rate
@@ -378,7 +378,7 @@ __device__ __forceinline__ void accept_row(const SpecState& s, int b, int lane, 
       // Next step's draft forward 0 (spec_loop.hip enqueue_draft). New `prev` sits at old cur_len + n_new - 1. Bonus mode: that is
       // d_a (a >= 1; an input of draft forward a, which ran iff a < k) or the old `last` (a == 0; forward 0's input): its K/V
       // are in the draft cache unless a == k. Draft-emit mode: prev is d_{a-1} or the old `last`: always there.
-      const int k_eff = s.adaptive ? s.k_row[b] : K;   // (before this step's controller update)
+      const int k_eff = (s.adaptive || s.conf) ? s.k_row[b] : K;   // (before this step's controller update / the record's reset)
       const bool two = !s.active[b] || (mode == 0 && a >= k_eff);
       s.fwd0_w[0] = two ? 2 : 1;
       s.fwd0_w[1] = two ? 1 : 2;
@@ -439,7 +439,14 @@ __device__ __forceinline__ void record_rows(const SpecState& s, const RecordArgs
       r[4 + 2 * K + lane] = s.target_ids[b * (K + 1) + lane];
     }
     if (lane < K) r[4 + K + lane] = s.draft_tok[b * K + lane];
-    if (lane == 0) r[5 + 3 * K] = s.adaptive ? s.ctl[4 * b + 3] : K;   // proposals that counted for the row in this step
+    if (lane == 0) {   // proposals that counted for the row in this step
+      int k = s.adaptive ? s.ctl[4 * b + 3] : K;
+      if (s.conf) {    // confidence-gated: what the judgement launches left; the next step starts at K again (same lane: read, then write)
+        k = s.k_row[b];
+        s.k_row[b] = K;
+      }
+      r[5 + 3 * K] = k;
+    }
     // health of the persistent launches (sd_model_engine_status): non-zero = a launch of this or an earlier step gave up
     if (lane == 0) r[6 + 3 * K] = static_cast<int32_t>((draft_status ? *draft_status : 0u) | (target_status ? *target_status : 0u));
   }
@@ -449,6 +456,7 @@ __device__ __forceinline__ void record_rows(const SpecState& s, const RecordArgs
     for (int off = 32; off > 0; off >>= 1) ka = max(ka, __shfl_xor(ka, off, 64));
     if (lane == 0) *s.k_active = ka;
   }
+  if (s.conf && lane < 8) s.conf_gate[lane] = 0;   // every gated draft forward of the next step waits for a row to open it
   if (lane == 0) *step_counter = *step_counter + 1;
 }
 

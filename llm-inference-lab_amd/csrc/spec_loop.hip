@@ -69,6 +69,10 @@ struct sd_specdec {
   AcceptRule accept;               // rule 0 = off
   void* acc_logits = nullptr;      // used while the sampled-bonus mode does not lend its own
   void* acc_ws = nullptr;          // flags and records of the two launches (the loop's own, allocated at first use)
+  // confidence-gated draft length (sd_specdec_set_draft_confidence): on while st.conf; every judged draft forward stores its pass's
+  // rows in conf_logits ([B][2][V] bf16) and a judgement launch follows its hand-over
+  ConfRule conf;
+  uint16_t* conf_logits = nullptr;
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -217,6 +221,10 @@ struct StepPlan {
   void* p_buf;        // [B][K+1][V] bf16 or null: where the verify forward stores its logits
   uint16_t* q_pass;   // p_buf or null: where each draft forward stores the logits of its pass first (the verify overwrites them)
   int32_t* ids_d;     // draft_ids or null: where a draft forward leaves its fused argmax ids (only HAND_NEXT reads them unprocessed)
+  // confidence-gated draft length: forwards conf_first .. K-2 are judged (store their pass's rows in conf_buf, then the judgement
+  // launch), forwards conf_first+1 .. K-1 are gated on their word of SpecState::conf_gate. conf_first = K: the mode is off (or K = 1)
+  int conf_first;
+  uint16_t* conf_buf;
 };
 
 static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
@@ -237,6 +245,8 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   else if (p.lp) p.p_buf = s.lp_logits;
   p.q_pass = (spec || p.lp) ? static_cast<uint16_t*>(p.p_buf) : nullptr;
   p.ids_d = (p.hand == HAND_NEXT && !p.lp) ? s.st.draft_ids : nullptr;
+  p.conf_first = (s.st.conf && s.draft) ? s.conf.min_k - 1 : s.K;   // (the setter keeps the mode apart from spec, lp and the rules)
+  p.conf_buf = s.st.conf ? s.conf_logits : nullptr;
   return p;
 }
 
@@ -310,19 +320,30 @@ struct DraftScope {
 // (rows = M, but for the 1-token form of forward 0: M = 1 in the 2-row layout), gated like the forward by the draft's skip_k /
 // skip_i. more_forms: the other form of forward 0 is still to come; exactly one of the two runs and both leave the last position's
 // row and id in the same place, so whatever is not gated by the form's own word is launched once, after the second.
+// The judgement launch of the confidence-gated step comes last, behind the hand-over, gated on the forward's own word.
 static int after_draft_forward(sd_specdec* s, const StepPlan& p, int i, int M, int rows, bool more_forms, hipStream_t st_d) {
   const sd_model* d = s->draft;
   const int V = s->target->cfg.vocab;
-  if (p.hand == HAND_FINALIZE)
-    return launch_draft_finalize(d->part_val, d->part_idx, d->head_grid, M, i, s->st.draft_ids + (rows - M), s->st, d->skip_k, d->skip_i, st_d);
-  if (more_forms) return 0;
-  if (p.lp)   // the forward left the logits of its positions in q_pass: process row rows - 1 of every batch row with d_1..d_i
-    if (int rc = launch_logit_process({p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V}, s->stage,
-                                      s->st.draft_tok, s->K, i, s->st.active, p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2,
-                                      st_d))
+  const int32_t* const gate = (i == 0) ? nullptr : d->skip_k;   // forward 0 always runs (its skip_k only picks the form)
+  if (p.hand == HAND_FINALIZE) {
+    if (int rc = launch_draft_finalize(d->part_val, d->part_idx, d->head_grid, M, i, s->st.draft_ids + (rows - M), s->st, d->skip_k, d->skip_i, st_d))
       return rc;
-  if (p.hand == HAND_DRAW) return launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->spec_draw, st_d);
-  return launch_draft_next(rows, i, s->st, st_d);
+    if (more_forms) return 0;
+  } else {
+    if (more_forms) return 0;
+    if (p.lp)   // the forward left the logits of its positions in q_pass: process row rows - 1 of every batch row with d_1..d_i
+      if (int rc = launch_logit_process({p.q_pass + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, s->B, 1, V}, s->stage,
+                                        s->st.draft_tok, s->K, i, s->st.active, p.hand == HAND_DRAW ? nullptr : s->st.draft_ids + (rows - 1), 2,
+                                        st_d))
+        return rc;
+    if (int rc = p.hand == HAND_DRAW ? launch_spec_draft_draw(s->st, p.q_pass, rows, rows - 1, s->spec_q, i, V, s->spec_draw, st_d)
+                                     : launch_draft_next(rows, i, s->st, gate, st_d))
+      return rc;
+  }
+  if (i < p.conf_first || i > s->K - 2) return 0;
+  // the confidence of the last position's row decides, row by row, whether forward i + 1 is needed
+  return launch_confidence_judge(s->st, p.conf_buf + static_cast<size_t>(rows - 1) * V, static_cast<long long>(rows) * V, V, i, s->conf,
+                                 i == p.conf_first, gate, i, st_d);
 }
 
 // forward 0 over (prev, last) at positions cur_len-1, cur_len; then one token each
@@ -331,6 +352,8 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
   const SpecState& st = s->st;
   const int V = s->target->cfg.vocab;
   DraftScope scope(d, s->draft_taps);
+  // where forward i stores the rows of its pass: the sampling-side buffer, or the confidence buffer of a judged forward
+  const auto pass_rows = [&](int i) { return (i >= p.conf_first && i <= s->K - 2) ? p.conf_buf : p.q_pass; };
   int i = 0;
   if (p.fwd0_select) {
     // both forms of forward 0, the device picks (SpecState::fwd0_w, written by accept_kernel): the 2-token pass, then the
@@ -343,7 +366,7 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     f2.pos_off = -1;
     f2.ids_out = p.ids_d;
     f2.ids_stride = 2;
-    f2.logits_out = p.q_pass;
+    f2.logits_out = pass_rows(0);
     if (int rc = model_forward(d, f2, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, 0, 2, 2, true, st_d)) return rc;
     d->skip_k = st.fwd0_w + 1;
@@ -352,7 +375,7 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     f1.tok_stride = 2;
     f1.ids_out = p.ids_d ? p.ids_d + 1 : nullptr;
     f1.ids_stride = 2;
-    f1.logits_out = p.q_pass ? p.q_pass + V : nullptr;
+    f1.logits_out = pass_rows(0) ? pass_rows(0) + V : nullptr;
     if (int rc = model_forward(d, f1, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, 0, 1, 2, false, st_d)) return rc;
     i = 1;
@@ -361,6 +384,8 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     const int M = (i == 0) ? 2 : 1;
     // per-row adaptive K: forward i >= 1 only matters while some row proposes more than i tokens
     d->skip_k = (st.adaptive && i >= 1) ? st.k_active : nullptr;
+    // confidence-gated: forward i > conf_first runs only once a row's judgement of forward i - 1 has opened its word
+    if (i > p.conf_first) d->skip_k = st.conf_gate + i;
     d->skip_i = i;
     ForwardCall f = step_forward(st);
     f.tokens = (i == 0) ? st.tok2 : st.next_tok;
@@ -368,7 +393,7 @@ static int enqueue_draft(sd_specdec* s, const StepPlan& p, hipStream_t st_d) {
     f.pos_off = (i == 0) ? -1 : i;
     f.ids_out = p.ids_d;
     f.ids_stride = 2;
-    f.logits_out = p.q_pass;
+    f.logits_out = pass_rows(i);
     if (int rc = model_forward(d, f, st_d)) return rc;
     if (int rc = after_draft_forward(s, p, i, M, M, false, st_d)) return rc;
   }
@@ -480,7 +505,9 @@ static size_t carve_state(sd_specdec* s, int32_t* base, bool fwd0) {
   st.adaptive = 0;
   int32_t* const w = take(2);              // every block has the two words; only a loop that selects forward 0 on the device uses them
   st.fwd0_w = fwd0 ? w : nullptr;
-  return off + 3 - pad;                    // spare words behind the last field: the size depends on B and K alone
+  st.conf = 0;
+  st.conf_gate = take(8);                  // one word per draft forward (K <= 8); zero = shut, as the block starts
+  return off + 3 - pad;                   // spare words behind the last field: the size depends on B and K alone
 }
 
 extern "C" int sd_specdec_create(sd_model* draft, sd_model* target, int B, int K, int emit_mode, sd_specdec** out) {
@@ -599,6 +626,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(!s->spec, "specdec_set_adaptive: speculative sampling keeps a fixed K (disable it first)");
   SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
   SD_REQUIRE(!s->accept.rule, "specdec_set_adaptive: the acceptance rule keeps a fixed K (disable sd_specdec_set_acceptance first)");
+  SD_REQUIRE(!s->st.conf, "specdec_set_adaptive: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -676,6 +704,7 @@ extern "C" int sd_specdec_set_spec_sampling(sd_specdec* s, int enable, float tem
   SD_REQUIRE(s->draft, "specdec_set_spec_sampling: needs a draft model (self-draft, Medusa heads and EAGLE loops propose without a distribution q)");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_spec_sampling: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
   SD_REQUIRE(!s->accept.rule, "specdec_set_spec_sampling: an acceptance rule is on (sd_specdec_set_acceptance); speculative sampling has its own");
+  SD_REQUIRE(!s->st.conf, "specdec_set_spec_sampling: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
   SD_REQUIRE(!s->sample, "specdec_set_spec_sampling: the sampled-bonus mode is enabled (sd_specdec_set_sampling); the two modes are mutually exclusive");
   SD_REQUIRE(temperature == temperature && temperature > 0.f, "specdec_set_spec_sampling: temperature %g (must be > 0)", temperature);
   SD_REQUIRE(draft_logits_buf && target_logits_buf && draw_counters, "specdec_set_spec_sampling: NULL logits buffer / draw counters");
@@ -711,6 +740,7 @@ extern "C" int sd_specdec_set_logit_processors(sd_specdec* s, int enable, float 
   }
   SD_REQUIRE(s->draft, "specdec_set_logit_processors: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_logit_processors: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->st.conf, "specdec_set_logit_processors: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
   SD_REQUIRE(repetition_penalty == repetition_penalty && repetition_penalty > 0.f,
              "specdec_set_logit_processors: repetition_penalty %g (must be > 0)", repetition_penalty);
   SD_REQUIRE(presence_penalty - presence_penalty == 0.f && frequency_penalty - frequency_penalty == 0.f,
@@ -742,6 +772,7 @@ extern "C" int sd_specdec_set_grammar(sd_specdec* s, int enable, const void* nex
   }
   SD_REQUIRE(s->draft, "specdec_set_grammar: needs a draft model (self-draft, Medusa heads and EAGLE loops propose from no logits row)");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_grammar: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->st.conf, "specdec_set_grammar: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
   SD_REQUIRE(s->lp, "specdec_set_grammar: the logit-processor stage is off (sd_specdec_set_logit_processors first; identity penalties will do)");
   SD_REQUIRE(S >= 1 && S <= kFsmMaxStates, "specdec_set_grammar: S=%d states (1..%d)", S, kFsmMaxStates);
   SD_REQUIRE(eos_id >= 0 && eos_id < s->target->cfg.vocab, "specdec_set_grammar: eos_id %d outside [0, %d)", eos_id, s->target->cfg.vocab);
@@ -777,6 +808,7 @@ extern "C" int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling*
   if (table) {
     SD_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, "specdec_set_row_sampling: the row table must be 16-byte aligned");
     SD_REQUIRE(!s->accept.rule, "specdec_set_row_sampling: an acceptance rule is on (sd_specdec_set_acceptance): its parameters are the loop's, not a row's");
+    SD_REQUIRE(!s->st.conf, "specdec_set_row_sampling: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
     SD_REQUIRE(s->sample || s->spec || s->lp, "specdec_set_row_sampling: neither a sampling mode nor the logit-processor stage is on "
                "(sd_specdec_set_sampling / sd_specdec_set_spec_sampling / sd_specdec_set_logit_processors first)");
   }
@@ -803,6 +835,7 @@ extern "C" int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperat
   SD_REQUIRE(s->draft, "specdec_set_acceptance: the tied self-draft is not supported (the rule judges a draft model's proposals)");
   SD_REQUIRE(!s->spec, "specdec_set_acceptance: speculative sampling is enabled (sd_specdec_set_spec_sampling); it has its own acceptance rule");
   SD_REQUIRE(!s->st.adaptive, "specdec_set_acceptance: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->st.conf, "specdec_set_acceptance: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
   SD_REQUIRE(!s->stage.table, "specdec_set_acceptance: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
   SD_REQUIRE(logits_buf || s->sample, "specdec_set_acceptance: NULL logits buffer (the sampled-bonus mode is not on to lend its own)");
   const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
@@ -812,6 +845,47 @@ extern "C" int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperat
   drop_graph(s);   // the captured step holds the exact-match launches, or this rule's parameters
   s->accept = r;
   s->acc_logits = logits_buf;
+  return 0;
+}
+
+// Confidence-gated draft length (the contract is in include/specdec_hip.h). The device decides alone: the judgement launches of the
+// draft loop rewrite k_row inside every step and the step's last launch puts it back, so there is no per-row state to set or repair.
+// The caller has drained the loop's streams (k_row is rewritten here, on no stream).
+extern "C" int sd_specdec_set_draft_confidence(sd_specdec* s, int enable, float tau, int min_k, void* logits_buf, size_t logits_bytes,
+                                               float* conf_out) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_draft_confidence: NULL");
+  drop_graph(s);   // unconditional, on or off: the captured step holds the judgement launches, the gates and the rule by value
+  if (!enable) {
+    s->st.conf = 0;
+    return 0;
+  }
+  SD_REQUIRE(tau > 0.f && tau <= 1.0f, "specdec_set_draft_confidence: tau %g outside (0, 1]", tau);   // (a NaN compares false)
+  SD_REQUIRE(min_k >= 1 && min_k <= s->K, "specdec_set_draft_confidence: min_k %d outside 1..K (%d)", min_k, s->K);
+  SD_REQUIRE(s->draft, "specdec_set_draft_confidence: needs a draft model (self-draft, Medusa heads and EAGLE loops have no draft forward to judge)");
+  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_draft_confidence: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_draft_confidence: per-row adaptive K is on (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->spec, "specdec_set_draft_confidence: speculative sampling is enabled (sd_specdec_set_spec_sampling); it keeps a fixed K");
+  SD_REQUIRE(!s->accept.rule, "specdec_set_draft_confidence: an acceptance rule is on (sd_specdec_set_acceptance); it keeps a fixed K");
+  SD_REQUIRE(!s->lp, "specdec_set_draft_confidence: logit processors / a grammar are on (sd_specdec_set_logit_processors); they keep a fixed K");
+  SD_REQUIRE(!s->stage.table, "specdec_set_draft_confidence: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
+  const size_t need = sd_specdec_draft_confidence_bytes(s->B, s->target->cfg.vocab);
+  SD_REQUIRE(logits_buf, "specdec_set_draft_confidence: NULL logits buffer");
+  SD_REQUIRE(logits_bytes >= need, "specdec_set_draft_confidence: logits buffer %zu B < %zu B ([B][2][V] bf16)", logits_bytes, need);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(logits_buf) & 15) == 0 && (reinterpret_cast<uintptr_t>(conf_out) & 3) == 0,
+             "specdec_set_draft_confidence: the logits buffer must be 16-byte aligned (conf_out 4-byte)");
+  // every row starts a step at K with every gated forward shut (rows that a disabled adaptive K left elsewhere included)
+  std::vector<int32_t> init(static_cast<size_t>(s->B), s->K);
+  SD_HIP_CHECK(hipMemcpy(s->st.k_row, init.data(), sizeof(int32_t) * s->B, hipMemcpyHostToDevice));
+  SD_HIP_CHECK(hipMemset(s->st.conf_gate, 0, sizeof(int32_t) * 8));
+  if (conf_out) {   // NaN until a judgement writes it: with min_k == K (or K == 1) no forward is judged and no launch ever does
+    const uint32_t nan_bits = 0x7fc00000u;
+    std::vector<float> nans(static_cast<size_t>(s->B) * s->K, __builtin_bit_cast(float, nan_bits));
+    SD_HIP_CHECK(hipMemcpy(conf_out, nans.data(), sizeof(float) * nans.size(), hipMemcpyHostToDevice));
+  }
+  s->st.conf = 1;
+  s->conf = ConfRule{tau, min_k, conf_out};
+  s->conf_logits = static_cast<uint16_t*>(logits_buf);
   return 0;
 }
 

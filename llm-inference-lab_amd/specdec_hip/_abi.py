@@ -68,6 +68,7 @@ SIGNATURES = {
         [_c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int,
          _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
     ),
+    "sd_draft_confidence": (_c_int, [_c_void_p, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p]),
     "sd_spec_agreement_workspace": (_c_size, [_c_int, _c_int]),
     "sd_spec_agreement": (
         _c_int,
@@ -194,6 +195,8 @@ SIGNATURES = {
     "sd_specdec_set_acceptance": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_void_p, _c_size]),
     "sd_specdec_set_adaptive": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_void_p]),
     "sd_specdec_set_adaptive_row": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_void_p]),
+    "sd_specdec_draft_confidence_bytes": (_c_size, [_c_int, _c_int]),
+    "sd_specdec_set_draft_confidence": (_c_int, [_c_void_p, _c_int, ctypes.c_float, _c_int, _c_void_p, _c_size, _c_void_p]),
     "sd_specdec_set_medusa": (_c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_int]),
     "sd_specdec_eagle_bytes": (_c_size, [_c_int, _c_int, _c_int]),
     "sd_specdec_set_eagle": (_c_int, [_c_void_p, ctypes.c_float, _c_void_p, _c_size]),

@@ -667,7 +667,7 @@ class StepRecord:
         self.new_tokens = arr[:, 3:4 + K].copy()
         self.draft_tokens = arr[:, 4 + K:4 + 2 * K].copy()
         self.target_ids = arr[:, 4 + 2 * K:5 + 3 * K].copy()
-        self.k_row = arr[:, 5 + 3 * K].copy()      # proposals that counted per row (per-row adaptive K), else K
+        self.k_row = arr[:, 5 + 3 * K].copy()      # proposals that counted per row (per-row adaptive K, confidence gating), else K
         # health word of the models' persistent launches (sd_model_engine_status): a launch that gave up leaves garbage
         self.engine_status = int(arr[0, 6 + 3 * K]) if arr.shape[1] > 6 + 3 * K else 0
         if self.engine_status:
@@ -701,6 +701,8 @@ class HipSpecDec:
         self.sampling = self.spec_sampling = False
         self.acceptance = None     # the lossy acceptance rule of set_acceptance ("typical" / "topk_agree"), None = exact match
         self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
+        self.draft_confidence = None   # (tau, min_k) of set_draft_confidence, None = every row proposes K
+        self._conf_logits = self.draft_conf = None
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
         # per-row parameters (set_row_sampling): none; the table is allocated at first use and kept (rewritten in place)
         self.row_table = None          # uint8 [B][32] on the device: sd_row_sampling[B], or None while the scalars rule
@@ -901,6 +903,28 @@ class HipSpecDec:
                 self.handle, _abi.ACCEPT_RULES[rule], float(temperature), float(epsilon), float("inf") if delta is None else float(delta),
                 int(agree_k), logits.data_ptr(), logits.numel() * 2), "sd_specdec_set_acceptance")
             self.acceptance = rule
+
+    def set_draft_confidence(self, tau: Optional[float], min_k: int = 1) -> None:
+        """Confidence-gated draft length inside the step (sd_specdec_set_draft_confidence; None switches it off): a row stops
+        drafting after the first forward i + 1 >= min_k whose confidence — the softmax probability of the draft's own token,
+        ops.draft_confidence of the row — is below `tau`; only its first k proposals count (StepRecord.k_row), and a draft
+        forward no row needs returns at entry. The device decides alone and starts every step at K: there is no per-row state
+        to set or repair. The loop owns the draft's row buffer and `draft_conf` (float32 [B][K]: the last step's confidences of
+        the judged forwards that ran, NaN elsewhere). The caller has drained the loop."""
+        with torch.cuda.device(self.device):
+            if tau is None:
+                _abi.check(self.lib.sd_specdec_set_draft_confidence(self.handle, 0, 1.0, 1, None, 0, None), "sd_specdec_set_draft_confidence")
+                self.draft_confidence = None
+                return
+            if self._conf_logits is None:
+                n = int(self.lib.sd_specdec_draft_confidence_bytes(self.B, self._vocab))
+                self._conf_logits = torch.empty(n // 2, dtype=torch.bfloat16, device=self.device)
+                self.draft_conf = torch.full((self.B, self.K), float("nan"), dtype=torch.float32, device=self.device)
+                torch.cuda.current_stream(self.device).synchronize()
+            _abi.check(self.lib.sd_specdec_set_draft_confidence(
+                self.handle, 1, float(tau), int(min_k), self._conf_logits.data_ptr(), self._conf_logits.numel() * 2,
+                self.draft_conf.data_ptr()), "sd_specdec_set_draft_confidence")
+            self.draft_confidence = (float(tau), int(min_k))
 
     def set_logit_counts_row(self, b: int, prompt_ids: Sequence[int], generated_ids: Sequence[int] = ()) -> None:
         """Row b's counts for a new sequence in its slot: the prompt bit of every prompt id, one count per generated id

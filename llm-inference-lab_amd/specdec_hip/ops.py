@@ -476,6 +476,33 @@ def typical_accept(target_logits: torch.Tensor, draft_ids: torch.Tensor, rule: s
     return (out, stats) if (return_stats or stats_out is not None) else out
 
 
+def draft_confidence(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The confidence of every row of `logits` (sd_draft_confidence): 1 / sum_v exp(x_v - max x), the temperature-1 softmax
+    probability of the row's largest stored value — what the confidence-gated step (HipSpecDec.set_draft_confidence) judges a
+    draft forward by.
+
+    logits: [B, V] f32 / bf16 / f16 on the GPU, unit stride along V; a view whose rows are further apart than V, or start off a
+    16-byte boundary, is taken as it is. Returns float32 [B]; NaN for a row with a NaN, a +inf, or nothing above -inf. `out`
+    (contiguous float32 [B]) makes the call allocation-free."""
+    lib = _abi.load()
+    dev = _require_device("draft_confidence", logits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("draft_confidence: need logits [B, V]")
+    if logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"draft_confidence: logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    B, V = logits.shape
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"draft_confidence: out must be a contiguous float32 [{B}] tensor on {dev}")
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_draft_confidence(logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0) if B > 1 else V, B, V,
+                                           out.data_ptr(), _stream_ptr(dev)), "sd_draft_confidence")
+    return out
+
+
 def _row_table(name: str, table, B: int, dev) -> torch.Tensor:
     """The device table of a _rows op: a list of SamplingParams is packed, a tensor (sampling_params.pack: uint8 [B][32]) is
     taken as it is."""

@@ -42,6 +42,7 @@ from ..policies.policies import create_policy
 from ..utils.deterministic import ensure_deterministic, set_deterministic_mode
 from ..utils.interfaces import LanguageModel
 from .acceptance import device_rule, session_rule
+from .draft_confidence import check_session, session_confidence
 from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
 PromptLike = Union[str, Sequence[int], torch.Tensor]
@@ -433,14 +434,15 @@ class SpeculativePipeline:
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Union[None, Dict[str, Any], StepOptions] = None, step_limit: Optional[int] = None,
                       self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
-                      **processors) -> "DecodeSession":
+                      draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
         (DecodeSession). sampling: None (greedy), {"temperature", "top_k", "top_p", "seed"} or a StepOptions. processors:
         repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids, allowed_token_ids; identity values
         leave the stage off. grammar: a TokenFSM, or a list with one entry per prompt (None: that row is unconstrained).
-        sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated."""
+        sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated.
+        draft_confidence / draft_min_k: the confidence-gated draft length (generate_batch), the bonus-token emit mode only."""
         if sampling_params is not None and sampling is not None:
             raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
         session_rule(self, StepOptions(), emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (its refusals come first)
@@ -448,6 +450,7 @@ class SpeculativePipeline:
                    row_options(self, sampling_params, len(prompts), 1, None, processors, self_draft))
         options = with_stage(self, options, processors, grammar, len(prompts))
         options = session_rule(self, options, emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (a device acceptance rule)
+        options = session_confidence(self, options, emit_mode, self_draft, draft_confidence, draft_min_k, HipSpecDec.EMIT_BONUS)
         return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
@@ -652,7 +655,7 @@ class SpeculativePipeline:
         t_begin = time.time()
         call = resolve(self, [prompt], max_tokens, temperature, do_sample, kwargs, grammar=kwargs.pop("grammar", None),
                        sampling_params=kwargs.pop("sampling_params", None), share_prefix=kwargs.get("share_prefix"), n=kwargs.get("n", 1),
-                       single=True)
+                       single=True, draft_confidence=kwargs.pop("draft_confidence", None), draft_min_k=kwargs.pop("draft_min_k", None))
         if call.route == "host_policy":
             rows, st = self._decode_host_policy(call.ids, call.max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * call.max_tokens,
                                                 temperature=call.temperature, sample_t=call.sample_t,
@@ -679,7 +682,8 @@ class SpeculativePipeline:
 
     def generate_batch(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None,
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
-                       share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None, **kwargs) -> List[Dict[str, Any]]:
+                       share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None,
+                       draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -703,11 +707,20 @@ class SpeculativePipeline:
         sampling_params (opt-in; not in the reference): one SamplingParams per prompt (expanded with n) — every request its own
         temperature (0: greedy), top_k, top_p, seed and penalties, read by the step's kernels row by row (step_options).
         Under policy="longest_prefix" the step samples the bonus token; under policy="rejection" with backend="device" it is
-        speculative sampling. A request's Philox stream is its index among the call's rows."""
+        speculative sampling. A request's Philox stream is its index among the call's rows.
+
+        draft_confidence (opt-in; config key draft_confidence_threshold; HF assisted generation's assistant_confidence_threshold):
+        a row stops drafting after the first draft forward i + 1 >= draft_min_k (default 1) whose confidence — the draft's
+        softmax probability of its own token — is below the threshold; the token drawn at low confidence is still proposed.
+        Decided on the device between two draft forwards of the captured step (sd_specdec_set_draft_confidence): only the row's
+        first k proposals count, a draft forward no row needs returns at entry, every step starts at K again. Greedy output is
+        the target's own greedy decoding whatever k was. Results carry `k_trace`; `proposed` counts the k of every step;
+        batch_metrics carries mean_k and draft_forwards_skipped. For the draft-model mode with a fixed K, greedy or do_sample;
+        refused next to speculative sampling, the device acceptance rules, logit processors, grammars and sampling_params."""
         if not prompts:
             return []
         call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
-                       sampling_params=sampling_params)
+                       sampling_params=sampling_params, draft_confidence=draft_confidence, draft_min_k=draft_min_k)
         if call.route == "fake":
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
         prompts, max_tokens = call.prompts, call.max_tokens
@@ -728,6 +741,9 @@ class SpeculativePipeline:
             "total_generation_time_ms": total_ms, "total_time_ms": total_ms,
             "tokens_per_sec": tot_acc / (total_ms / 1e3) if total_ms > 0 else 0.0,
             "emitted_tokens": tot_gen, "resyncs": st["resyncs"], "k": st["k"],
+            # proposals that counted per row and step (K unless a row's k moves), and — confidence-gated draft length — the draft
+            # forwards of the consumed steps that no row the host took tokens from needed
+            "mean_k": tot_prop / max(sum(r.steps for r in rows), 1), "draft_forwards_skipped": st.get("draft_forwards_skipped", 0),
             **{key: st.get(key, 0) for key in ("prefilled_rows", "forked_rows", "shared_positions")},
         }
         out = []
@@ -751,7 +767,8 @@ class SpeculativePipeline:
 
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
-                      grammar=None, sampling_params=None, **kwargs) -> List[Dict[str, Any]]:
+                      grammar=None, sampling_params=None, draft_confidence: Optional[float] = None,
+                      draft_min_k: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -763,11 +780,12 @@ class SpeculativePipeline:
         grammar: as generate_batch, one entry per prompt; a prompt admitted to a slot starts in its own automaton's start state.
         sampling_params: as generate_batch, one entry per prompt; a prompt admitted to a slot brings its own entry, its seed and
         its Philox stream (its index among the call's rows) with it — the slot's table entry, stream id and draw counter are
-        rewritten on the loop's stream and the captured step is kept."""
+        rewritten on the loop's stream and the captured step is kept.
+        draft_confidence / draft_min_k: as generate_batch; the device keeps no per-row state for it, so an admission sets nothing."""
         if not prompts:
             return []
         call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
-                       sampling_params=sampling_params, policy_routes=False)
+                       sampling_params=sampling_params, policy_routes=False, draft_confidence=draft_confidence, draft_min_k=draft_min_k)
         prompts, ids, max_tokens, options = call.prompts, call.ids, call.max_tokens, call.options
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
@@ -811,6 +829,8 @@ class SpeculativePipeline:
                         **({"k_trace": list(r.k_trace)} if r.k_trace else {}),
                         "batch_metrics": {"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
                                           "void_row_steps": sess.stats["void_row_steps"], "k": sess.k,
+                                          "mean_k": sess.stats["proposed"] / max(sum(x.steps for x, _ in done.values()), 1),
+                                          "draft_forwards_skipped": sess.stats.get("draft_forwards_skipped", 0),
                                           **{key: sess.stats[key] for key in ("prefilled_rows", "forked_rows", "shared_positions")}}})
         return out
 
@@ -943,6 +963,8 @@ class DecodeSession:
             self.row_ctl = [self._new_row_controller() for _ in self.rows]
         else:
             self.k = pipe._effective_k(ctl.get_k(1, {"step": 1, "generated_tokens": 0, "acceptance_rate": 0.0}), self_draft)
+        # confidence-gated draft length: the device rewrites every row's k inside each step and the record carries it; the host mirrors nothing
+        self._conf = check_session(o, other_step, emit_mode == HipSpecDec.EMIT_BONUS, self.k)
         self.rt, self.loop = pipe._runtime(len(self.rows), self.need, self.k, emit_mode, self.self_draft, adaptive=self.per_row)
         # positions a row may use: the cache rows and both models' position tables
         self.pos_limit = min(self.rt["l_max"], pipe.base_lm.config.max_pos,
@@ -1018,7 +1040,11 @@ class DecodeSession:
         """Loops are cached per (batch, K) and outlive sessions: switch the one in use off what another run left on it and to this
         run's sampling mode, with every row's stream id and draw count. Every set_* call drops the captured step."""
         o, loop, spec = self.options, self.loop, self._spec
-        if getattr(loop, "acceptance", None) is not None and not self._accept:         # (first: the other modes' setters refuse next to a rule)
+        want_conf = (o.draft_confidence, o.draft_min_k) if self._conf else None
+        if getattr(loop, "draft_confidence", None) not in (None, want_conf):    # (first of all: every other mode's setter refuses next to it)
+            loop.sync()
+            loop.set_draft_confidence(None)
+        if getattr(loop, "acceptance", None) is not None and not self._accept:        # (first: the other modes' setters refuse next to a rule)
             loop.sync()
             loop.set_acceptance(None)
         if loop.row_table is not None and self.row_params is None:   # a cached loop another run left a table on
@@ -1050,12 +1076,16 @@ class DecodeSession:
         """_configure_sampling, then the processor stage: on or off, its bias rows, every row's counts (forked rows' own too), the grammar."""
         self._configure_sampling()
         lp, loop = self.processors, self.loop
-        if lp is None and not loop.logit_processors:
+        if lp is None:
+            if loop.logit_processors:
+                loop.sync()
+                loop.set_logit_processors(False)
+            # confidence-gated draft length, last: its setter refuses next to what the lines above have switched off by now
+            if self._conf and loop.draft_confidence != (self.options.draft_confidence, self.options.draft_min_k):
+                loop.drain()
+                loop.set_draft_confidence(self.options.draft_confidence, self.options.draft_min_k)
             return
         loop.sync()
-        if lp is None:
-            loop.set_logit_processors(False)
-            return
         loop.set_logit_processors(True, lp.rp, lp.presence, lp.frequency, bias=lp.bias is not None)
         if lp.bias is not None:
             with torch.cuda.stream(loop.stream_t):
@@ -1237,6 +1267,7 @@ class DecodeSession:
         while self._early and len(self._queue) < self._depth and self._can_launch_ahead():
             self._launch()              # step s+1 (s+2) runs while the rules of step s are applied below
         stats["device_ms"] += (time.time() - t0) * 1e3
+        widest = 0                  # confidence-gated draft length: the widest k among the rows this step counts for
         for b, r in enumerate(rows):
             if not r.active:
                 continue
@@ -1256,6 +1287,12 @@ class DecodeSession:
                 r.strict_acc += a
                 r.strict_prop += k
                 m.get_k(r.steps + 2, {"step": r.steps + 2, "acceptance_rate": r.strict_acc / max(r.strict_prop, 1)})
+            if self._conf:                      # the k the device's judgements left the row in this step: taken from the record, not mirrored
+                k = int(rec.k_row[b])
+                if not 1 <= k <= self.k:
+                    raise RuntimeError(f"row {b}: the step record carries k={k} outside 1..{self.k}")
+                r.k_trace.append(k)
+                widest = max(widest, k)
             if self._spec or self._accept:
                 # speculative sampling (and a device acceptance rule alike): the accepted tokens are the DRAFT's ids, then the redrawn / bonus token. An accepted EOS
                 # ends the row by the rule as it stands for greedy steps: the accepted tokens are cut BEFORE the EOS, then the
@@ -1293,6 +1330,8 @@ class DecodeSession:
             if b in self._flagged:
                 for _, vs in self._queue:      # every step already launched is void for this row
                     vs.add(b)
+        if widest:
+            stats["draft_forwards_skipped"] = stats.get("draft_forwards_skipped", 0) + self.k - widest
         stats["steps"] = max(r.steps for r in rows)
         return True
 

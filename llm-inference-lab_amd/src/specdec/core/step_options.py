@@ -12,6 +12,7 @@ from specdec_hip.sampling_params import SamplingParams, check_penalties
 
 from ..policies.controllers import FixedKController
 from .acceptance import refuse_call, with_rule
+from .draft_confidence import with_confidence
 
 PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "bad_token_ids", "allowed_token_ids")
 ROW_SAMPLING_CLASH = ("top_k", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty")
@@ -55,6 +56,10 @@ class StepOptions:
     accept_epsilon: float = 0.09
     accept_delta: Optional[float] = None
     accept_k: int = 1
+    # confidence-gated draft length (sd_specdec_set_draft_confidence): None = every row proposes K, else a row stops drafting after the
+    # first forward i + 1 >= draft_min_k whose confidence (the draft's softmax probability of its own token) is below the threshold
+    draft_confidence: Optional[float] = None
+    draft_min_k: int = 1
 
     def __post_init__(self):
         # a grammar is a line of the processor stage, and requests with penalties of their own need it: identity scalars will do
@@ -93,6 +98,10 @@ _GATE = {
     "acceptance": (None, "policy 'typical' / 'topk_agree' with backend='device' needs the draft-model mode (draft_mode='vanilla'): medusa / eagle "
                    "proposals are not judged by it",
                    "policy 'typical' / 'topk_agree' with backend='device' keeps a fixed K (controller='fixed'): adaptive K is not supported"),
+    "draft_confidence": ("draft_confidence is decided inside the captured device step: {what} is not supported with it",
+                         "draft_confidence needs the draft-model mode (draft_mode='vanilla'): medusa / eagle drafting has no draft forward to judge",
+                         "draft_confidence moves every row's k inside the step and needs a fixed shape K (controller='fixed'): adaptive K is not "
+                         "supported with it"),
 }
 
 
@@ -233,7 +242,8 @@ Call = namedtuple("Call", "route prompts ids options max_tokens temperature samp
 
 
 def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kwargs: Dict[str, Any], share_prefix=False, n=1,
-            grammar=None, sampling_params=None, single: bool = False, policy_routes: bool = True) -> Call:
+            grammar=None, sampling_params=None, single: bool = False, policy_routes: bool = True, draft_confidence=None,
+            draft_min_k=None) -> Call:
     """A call's arguments -> its route, its prompts expanded with n, their ids and its options, every refusal raised on the way.
     single (generate): one row and no bonus token; the draft modes draft; do_sample=True is the host loop drawing the draft's tokens at
     sample_t. policy_routes (generate, generate_batch): the policy chooses between the captured step and the host loops, persistent heads
@@ -263,6 +273,8 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
         # the double has no tokenizer to pad a batch with: the reference falls back to generate() per prompt (pipeline.py:1680-1700)
         if grammar is not None:
             gate(pipe, "grammar", False, "implementation='fake'")
+        if draft_confidence is not None:
+            gate(pipe, "draft_confidence", False, "implementation='fake'")
         return Call("fake", list(prompts), [], StepOptions(), max_tokens, temperature, None, False, False)
     max_tokens, temperature = max_tokens or cfg["max_new_tokens"], temperature or cfg["temperature"]      # (0 is "not given")
     do_sample, sampling = do_sample if do_sample is not None else cfg["do_sample"], rows
@@ -302,5 +314,10 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
         raise NotImplementedError(f"policy={policy!r} with do_sample=True is not on the HIP path")
     if lossy is not None:                     # the rule goes with whatever mode the call's sampling made: greedy or the sampled bonus token
         options = with_rule(options, lossy)
+    # confidence-gated draft length: the call's threshold over the config's (which generate() and the fake double do not read)
+    if draft_confidence is None and not single and not fake:
+        draft_confidence = cfg.get("draft_confidence_threshold")
+        draft_min_k = cfg.get("draft_min_k") if draft_confidence is not None and draft_min_k is None else draft_min_k
+    options = with_confidence(pipe, options, draft_confidence, draft_min_k, on_step and not fake, what, bool(heads), single)
     self_draft = cfg.get("draft_mode") in ("medusa", "eagle") if single else heads and longest
     return Call(route, prompts, ids, options, max_tokens, float(temperature) if single else temperature, sample_t, share_prefix, self_draft)

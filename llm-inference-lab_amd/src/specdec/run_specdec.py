@@ -56,6 +56,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--target-acceptance", type=float)
     ap.add_argument("--per-row-K", action="store_true",
                     help="adaptive controller: every batch row its own K, moved on the device inside the captured step (not in the reference)")
+    ap.add_argument("--draft-confidence", type=float, metavar="TAU",
+                    help="stop drafting a row once the draft's probability of its own token falls below TAU in (0, 1]: decided on the "
+                         "device between two draft forwards of the captured step; fixed K, draft-model mode; decodes through generate_batch")
+    ap.add_argument("--draft-min-k", type=int, metavar="N", help="--draft-confidence: always draft at least N tokens (default 1)")
     ap.add_argument("--prefill-backend", type=str, choices=["auto", "passes", "rocblas", "native"], default="auto",
                     help="how prompts are absorbed into the KV cache: auto (rocBLAS where it serves the model, else the 128-token passes), "
                          "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
@@ -180,6 +184,9 @@ def main(argv=None) -> int:
     elif args.spec_top_k is not None or args.spec_top_p is not None:
         logging.error("--spec-top-k / --spec-top-p belong to --spec-sampling")
         return 1
+    if args.draft_min_k is not None and args.draft_confidence is None:
+        logging.error("--draft-min-k belongs to --draft-confidence")
+        return 1
     try:
         pipe = SpeculativePipeline(config_path=args.config, base_model=args.base_model, draft_model=args.draft_model,
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,
@@ -188,13 +195,16 @@ def main(argv=None) -> int:
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
-        batch = args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
+        conf = args.draft_confidence is not None
+        batch = conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:
             proc["grammar"] = pipe.grammar_from_regex(args.regex)
         if row_params is not None:
             proc["sampling_params"] = row_params
+        if conf:       # confidence-gated draft length inside the captured step
+            proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
             rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],

@@ -86,7 +86,12 @@ def cmd_run(args: argparse.Namespace) -> int:
         proc["grammar"] = pipe.grammar_from_regex(args.regex)
     if row_params is not None:
         proc["sampling_params"] = row_params
-    if spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:   # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    conf = args.draft_confidence is not None
+    if args.draft_min_k is not None and not conf:
+        raise SystemExit("--draft-min-k belongs to --draft-confidence")
+    if conf:     # confidence-gated draft length inside the captured step (a generate_batch mode)
+        proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
+    if conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
@@ -134,6 +139,10 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--typical-epsilon", type=float, help="--policy typical: the threshold epsilon")
     pr.add_argument("--typical-delta", type=float, help="--policy typical: accept p(d) >= min(epsilon, delta * exp(-H)); without it epsilon alone")
     pr.add_argument("--seed", type=int, default=0)
+    pr.add_argument("--draft-confidence", type=float, metavar="TAU",
+                    help="stop drafting a row once the draft's probability of its own token falls below TAU in (0, 1], decided on the "
+                         "device between two draft forwards of the captured step (generate_batch)")
+    pr.add_argument("--draft-min-k", type=int, metavar="N", help="--draft-confidence: always draft at least N tokens (default 1)")
     pr.add_argument("--repetition-penalty", type=float, help="repetition penalty (> 0) over prompt + generated tokens, inside the captured step")
     pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
     pr.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
