@@ -147,6 +147,23 @@ int sd_typical_accept(const void* target_logits, int logits_dtype, int64_t row_s
  * Additive (SD_ABI_VERSION stays 1). */
 int sd_draft_confidence(const void* logits, int logits_dtype, int64_t row_stride, int B, int V, float* conf, void* stream);
 
+/* Per-token log-probs and top-N alternatives of logits rows (csrc/token_logprobs.hip). logits: R rows of V elements (f32 / f16 /
+ * bf16), row_stride elements apart (>= V); a row need not be 16-byte aligned (aligned rows take 16-byte loads). For row r and its
+ * token t = token_ids[r], over the STORED values x at temperature 1, in fp32, with m = max_v x_v and S = sum_v e^{x_v - m} (an
+ * element at -inf adds exactly 0):
+ *   out_logprob[r]        (x_t - m) - log S; -inf for a token at -inf
+ *   out_rank[r]           #{v : x_v > x_t, or x_v == x_t and v < t}: the ties of the argmax kernels, 0 = t is the row's argmax
+ *   out_top_ids[r][j], out_top_logprob[r][j], j < N = min(top_n, V): the N largest entries, value descending, index ascending;
+ *                         entries at -inf (fewer than N finite ones) follow in that order with log-prob -inf
+ * A row with no finite element, and a token id outside [0, V) (never read), give logprob NaN, rank -1, top ids -1 with log-prob NaN.
+ * One 1024-thread workgroup per row, the running-maximum stream and merge order of sd_typical_accept's row pass: bit-identical run
+ * to run and under graph replay, no global atomics, no waiting. top_n = 0 skips the selection (the top outputs may be NULL).
+ * Asynchronous on `stream`, no allocation, graph-capturable. Refused (nonzero + sd_last_error, before any device work): a NULL
+ * pointer, an unknown dtype, R < 1, V < 1 or above 2^20, top_n outside 0..20, a stride below V, a misaligned output.
+ * Additive (SD_ABI_VERSION stays 1). */
+int sd_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int R, int V, const int32_t* token_ids, int top_n,
+                      float* out_logprob, int32_t* out_rank, int32_t* out_top_ids, float* out_top_logprob, void* stream);
+
 /* Draft-target agreement of two logit blocks (csrc/spec_agree.hip): how much of the target's distribution a draft reproduces,
  * position by position, without generating. draft_logits / target_logits: bf16, n rows of V elements, rows ld_q / ld_p
  * elements apart (>= V). Per row t, in float64 over the stored bf16 values, x / T as sd_spec_sample_accept forms it (T the
@@ -899,6 +916,23 @@ int sd_specdec_set_row_sampling(sd_specdec* s, const sd_row_sampling* table);
 int sd_specdec_set_acceptance(sd_specdec* s, int rule, float temperature, float epsilon, float delta, int agree_k, void* logits_buf,
                               size_t logits_bytes);
 
+/* Per-token log-probs inside the step (sd_token_logprobs' row pass on the verify forward's own rows). While on, the verify forward
+ * stores its [B][K+1][V] logits (in the buffer of whichever mode already stores them, else logits_buf; a plain greedy step then
+ * takes its three launches — ids, accept, record — instead of the fused tail) and ONE launch, after the accept stage and the
+ * logit-processor stage and before the record, describes every emitted token: workgroup (b, i), i = 0..K, handles new_tok[b][i] iff
+ * row b is active and i < n_new[b], from row (b, i) — the target's distribution after d_1..d_i, the (processed) row that token was
+ * checked against or drawn from in every select mode, at temperature 1 and before any top-k / top-p shaping. Every other (b, i)
+ * gets the "no record" value (logprob NaN, rank -1, ids -1). The words go to pinned host memory, sd_specdec_logprobs(): TWO slots
+ * of [B][K+1][W], W = sd_specdec_logprob_words() = 2 + 2 N, N = min(top_n, V); launch i writes slot i & 1, the slot of its step
+ * record. Words of (b, i): [0] logprob (float bits) [1] rank [2 .. 2+N) top ids [2+N .. 2+2N) top log-probs (float bits).
+ * The step record and sd_specdec_record_ints() are unchanged. enable = 0 (the default): the step is launch for launch what it is
+ * without this call. Enabling, changing top_n and disabling (if it was on) drop the captured graph; the caller has drained the loop.
+ * logits_buf: caller-owned [B][K+1][V] bf16, 16-byte aligned — the buffer the other modes were handed, when any is on.
+ * Refused: top_n outside 0..20; a NULL, short or misaligned buffer; loops without a draft model (self-draft, Medusa heads, EAGLE);
+ * SD_EMIT_DRAFT; per-row adaptive K and confidence-gated draft length, whose setters in turn refuse while this mode is on.
+ * Additive (SD_ABI_VERSION stays 1). */
+int sd_specdec_set_logprobs(sd_specdec* s, int enable, int top_n, void* logits_buf, size_t logits_bytes);
+
 /* Per-row adaptive K inside the captured step ("AdaptiveKController driving per-row K inside a
  * captured graph"; the rule is the reference's AdaptiveKController.get_k, src/specdec/policies/controllers.py:100-126,
  * which the reference applies to one K for the whole batch from the host, pipeline.py:1994-2014). The loop keeps the
@@ -1042,6 +1076,10 @@ int sd_specdec_sync(sd_specdec* s, void* stream);
  * row stride = sd_specdec_record_ints(). */
 const int32_t* sd_specdec_record(const sd_specdec* s);
 int sd_specdec_record_ints(const sd_specdec* s);
+/* The log-prob words of sd_specdec_set_logprobs: pinned, two slots of [B][K+1][sd_specdec_logprob_words()], slotted as the
+ * records. NULL until the mode was first enabled; the word count is 0 while it is off. */
+const int32_t* sd_specdec_logprobs(const sd_specdec* s);
+int sd_specdec_logprob_words(const sd_specdec* s);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,13 @@ size_t typical_accept_workspace(int B, int K);
 int launch_typical_step(const SpecState& s, const void* logits, int V, const AcceptRule& r, bool next_from_ids, void* workspace,
                         hipStream_t st);
 
+// csrc/token_logprobs.hip: log-prob, rank and top-N alternatives of every token the step emitted, from the stored verify rows into
+// the pinned block [2][B][K+1][logprob_words(V, top_n)] (slot = the parity of *step_counter, as the step record of the same launch)
+int check_logprob_params(const char* who, int V, int top_n);
+int logprob_words(int V, int top_n);
+int launch_step_logprobs(const SpecState& s, const void* logits, int V, int top_n, const int32_t* step_counter, int32_t* host_words,
+                         hipStream_t st);
+
 // csrc/draft_confidence.hip: the judgement after draft forward i of the confidence-gated step. rows: the last position's bf16 row of
 // batch row b at rows + b * row_stride elements. Gated like the forward it follows (skip_k / skip_i); a continuing row opens
 // s.conf_gate[i + 1]. first: the step's first judgement also fills the other slots of conf_out's row with NaN.

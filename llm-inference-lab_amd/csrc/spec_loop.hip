@@ -73,6 +73,12 @@ struct sd_specdec {
   // rows in conf_logits ([B][2][V] bf16) and a judgement launch follows its hand-over
   ConfRule conf;
   uint16_t* conf_logits = nullptr;
+  // per-token log-probs (sd_specdec_set_logprobs): one launch between the accept stage and the record describes every emitted token
+  // by its stored verify row; the words go to a pinned block of the loop's own, slotted like host_record
+  int logprobs = 0;
+  int logprobs_top = 0;            // top_n, 0..20
+  void* logprobs_logits = nullptr; // used while no other mode stores the verify rows
+  int32_t* host_logprobs = nullptr; // pinned: [2][B][K+1][logprob_words(V, top_n)], allocated at first use for top_n = 20
   // persistent Medusa heads (sd_specdec_set_medusa): K packed [V][d] matrices + their fp32 row scales (fp8)
   std::vector<const void*> heads;
   std::vector<const float*> head_scales;
@@ -225,6 +231,7 @@ struct StepPlan {
   // launch), forwards conf_first+1 .. K-1 are gated on their word of SpecState::conf_gate. conf_first = K: the mode is off (or K = 1)
   int conf_first;
   uint16_t* conf_buf;
+  bool logprobs;      // the log-prob launch between the accept stage and the record (reads p_buf)
 };
 
 static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
@@ -243,6 +250,11 @@ static StepPlan plan_step(const sd_specdec& s, bool two_streams) {
   else if (p.select == SELECT_TYPICAL) p.p_buf = s.sample ? s.logits : s.acc_logits;
   else if (spec) p.p_buf = s.spec_p;
   else if (p.lp) p.p_buf = s.lp_logits;
+  p.logprobs = s.logprobs != 0;
+  if (p.logprobs) {   // the rows must be stored: a greedy step lends the mode's own buffer and takes the three launches, not the fused tail
+    if (!p.p_buf) p.p_buf = s.logprobs_logits;
+    p.tail = false;
+  }
   p.q_pass = (spec || p.lp) ? static_cast<uint16_t*>(p.p_buf) : nullptr;
   p.ids_d = (p.hand == HAND_NEXT && !p.lp) ? s.st.draft_ids : nullptr;
   p.conf_first = (s.st.conf && s.draft) ? s.conf.min_k - 1 : s.K;   // (the setter keeps the mode apart from spec, lp and the rules)
@@ -443,6 +455,8 @@ static int enqueue_verify(sd_specdec* s, const StepPlan& p, hipStream_t st_t) {
       if (int rc = launch_fsm_advance(s->fsm_bind.next, s->fsm_bind.S, V, const_cast<int32_t*>(s->fsm_bind.state), B, s->st.new_tok, K + 1,
                                       s->st.n_new, K + 1, s->st.active, st_t))
         return rc;
+    if (p.logprobs)   // new_tok and n_new are final, the rows are the processed ones; the slot is read before pack_record advances the counter
+      if (int rc = launch_step_logprobs(s->st, p.p_buf, V, s->logprobs_top, s->step_counter, s->host_logprobs, st_t)) return rc;
     if (int rc = launch_pack_record(s->st, s->host_record, s->rec, s->step_counter, st_word_d, st_word_t, st_t)) return rc;
   }
   // persistent Medusa heads: the proposals of the next step, after the record of this one has left
@@ -458,6 +472,7 @@ static int enqueue_step(sd_specdec* s, hipStream_t st_t, hipStream_t st_d) {
   }
   SD_REQUIRE(p.select != SELECT_TYPICAL || (s->draft && p.p_buf && s->acc_ws),
              "specdec_step: the acceptance rule needs a draft model and a logits buffer (sd_specdec_set_acceptance)");
+  SD_REQUIRE(!p.logprobs || (s->draft && p.p_buf && s->host_logprobs), "specdec_step: log-probs need a draft model and a logits buffer (sd_specdec_set_logprobs)");
   SD_REQUIRE(!p.lp || (s->draft && p.p_buf), "specdec_step: logit processors need a draft model and a logits buffer (sd_specdec_set_logit_processors)");
   if (p.proposer == PROPOSE_DRAFT)
     if (int rc = enqueue_draft(s, p, st_d)) return rc;
@@ -574,6 +589,7 @@ extern "C" int sd_specdec_destroy(sd_specdec* s) {
   if (s->spec_flags) (void)hipFree(s->spec_flags);
   if (s->fsm_pos) (void)hipFree(s->fsm_pos);
   if (s->acc_ws) (void)hipFree(s->acc_ws);
+  if (s->host_logprobs) (void)hipHostFree(s->host_logprobs);
   delete s;
   return 0;
 }
@@ -627,6 +643,7 @@ extern "C" int sd_specdec_set_adaptive(sd_specdec* s, int enable, int initial_k,
   SD_REQUIRE(!s->lp, "specdec_set_adaptive: logit processors keep a fixed K (disable sd_specdec_set_logit_processors first)");
   SD_REQUIRE(!s->accept.rule, "specdec_set_adaptive: the acceptance rule keeps a fixed K (disable sd_specdec_set_acceptance first)");
   SD_REQUIRE(!s->st.conf, "specdec_set_adaptive: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
+  SD_REQUIRE(!s->logprobs, "specdec_set_adaptive: per-token log-probs keep a fixed K (disable sd_specdec_set_logprobs first)");
   s->st.adaptive = 1;
   s->st.a_min = min_k;
   s->st.a_max = max_k;
@@ -869,6 +886,7 @@ extern "C" int sd_specdec_set_draft_confidence(sd_specdec* s, int enable, float 
   SD_REQUIRE(!s->accept.rule, "specdec_set_draft_confidence: an acceptance rule is on (sd_specdec_set_acceptance); it keeps a fixed K");
   SD_REQUIRE(!s->lp, "specdec_set_draft_confidence: logit processors / a grammar are on (sd_specdec_set_logit_processors); they keep a fixed K");
   SD_REQUIRE(!s->stage.table, "specdec_set_draft_confidence: a row-sampling table is bound (sd_specdec_set_row_sampling); unbind it first");
+  SD_REQUIRE(!s->logprobs, "specdec_set_draft_confidence: per-token log-probs are on (sd_specdec_set_logprobs); they keep a fixed K");
   const size_t need = sd_specdec_draft_confidence_bytes(s->B, s->target->cfg.vocab);
   SD_REQUIRE(logits_buf, "specdec_set_draft_confidence: NULL logits buffer");
   SD_REQUIRE(logits_bytes >= need, "specdec_set_draft_confidence: logits buffer %zu B < %zu B ([B][2][V] bf16)", logits_bytes, need);
@@ -886,6 +904,36 @@ extern "C" int sd_specdec_set_draft_confidence(sd_specdec* s, int enable, float 
   s->st.conf = 1;
   s->conf = ConfRule{tau, min_k, conf_out};
   s->conf_logits = static_cast<uint16_t*>(logits_buf);
+  return 0;
+}
+
+// Per-token log-probs inside the step (the contract is in include/specdec_hip.h). The caller has drained the loop.
+extern "C" int sd_specdec_set_logprobs(sd_specdec* s, int enable, int top_n, void* logits_buf, size_t logits_bytes) {
+  clear_error();
+  SD_REQUIRE(s, "specdec_set_logprobs: NULL");
+  if (!enable) {
+    if (s->logprobs) drop_graph(s);   // only if the mode was on: otherwise the captured step holds none of it
+    s->logprobs = 0;
+    return 0;
+  }
+  const int V = s->target->cfg.vocab;
+  if (int rc = check_logprob_params("specdec_set_logprobs", V, top_n)) return rc;
+  SD_REQUIRE(s->draft, "specdec_set_logprobs: needs a draft model (self-draft, Medusa heads and EAGLE loops are not supported)");
+  SD_REQUIRE(s->mode == SD_EMIT_BONUS, "specdec_set_logprobs: only the bonus-token emit mode (generate_batch); SD_EMIT_DRAFT is not supported");
+  SD_REQUIRE(!s->st.adaptive, "specdec_set_logprobs: per-row adaptive K is not supported (disable sd_specdec_set_adaptive first)");
+  SD_REQUIRE(!s->st.conf, "specdec_set_logprobs: confidence-gated draft length is on (disable sd_specdec_set_draft_confidence first)");
+  const size_t need = static_cast<size_t>(s->B) * (s->K + 1) * V * 2;
+  SD_REQUIRE(logits_buf, "specdec_set_logprobs: NULL logits buffer");
+  SD_REQUIRE(logits_bytes >= need, "specdec_set_logprobs: logits buffer %zu B < %zu B ([B][K+1][V] bf16)", logits_bytes, need);
+  SD_REQUIRE((reinterpret_cast<uintptr_t>(logits_buf) & 15) == 0, "specdec_set_logprobs: the logits buffer must be 16-byte aligned");
+  if (!s->host_logprobs) {
+    const size_t words = static_cast<size_t>(2) * s->B * (s->K + 1) * logprob_words(V, 20);
+    SD_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s->host_logprobs), sizeof(int32_t) * words, hipHostMallocDefault));
+  }
+  drop_graph(s);   // the captured step holds the launches without the stage, or another top_n
+  s->logprobs = 1;
+  s->logprobs_top = top_n;
+  s->logprobs_logits = logits_buf;
   return 0;
 }
 
@@ -1093,3 +1141,10 @@ extern "C" int sd_specdec_sync(sd_specdec* s, void* stream) {
 extern "C" const int32_t* sd_specdec_record(const sd_specdec* s) { return s ? s->host_record : nullptr; }
 
 extern "C" int sd_specdec_record_ints(const sd_specdec* s) { return s ? s->rec : 0; }
+
+// two slots of [B][K+1][words]: the log-prob words of launch i are in slot i & 1 (null / 0 until sd_specdec_set_logprobs enabled the mode)
+extern "C" const int32_t* sd_specdec_logprobs(const sd_specdec* s) { return s ? s->host_logprobs : nullptr; }
+
+extern "C" int sd_specdec_logprob_words(const sd_specdec* s) {
+  return (s && s->logprobs) ? logprob_words(s->target->cfg.vocab, s->logprobs_top) : 0;
+}

@@ -68,6 +68,10 @@ SIGNATURES = {
         [_c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int,
          _c_void_p, _c_void_p, _c_void_p, _c_size, _c_void_p],
     ),
+    "sd_token_logprobs": (
+        _c_int,
+        [_c_void_p, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    ),
     "sd_draft_confidence": (_c_int, [_c_void_p, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p]),
     "sd_spec_agreement_workspace": (_c_size, [_c_int, _c_int]),
     "sd_spec_agreement": (
@@ -215,6 +219,9 @@ SIGNATURES = {
     "sd_specdec_invalidate": (_c_int, [_c_void_p]),
     "sd_specdec_record": (ctypes.POINTER(ctypes.c_int32), [_c_void_p]),
     "sd_specdec_record_ints": (_c_int, [_c_void_p]),
+    "sd_specdec_set_logprobs": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_size]),
+    "sd_specdec_logprobs": (ctypes.POINTER(ctypes.c_int32), [_c_void_p]),
+    "sd_specdec_logprob_words": (_c_int, [_c_void_p]),
 }
 
 _lock = threading.Lock()

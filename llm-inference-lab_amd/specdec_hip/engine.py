@@ -658,15 +658,27 @@ def pack_heads(heads: torch.Tensor, weight_dtype: str = "bf16", uneven: bool = F
 class StepRecord:
     """Host view of one completed step (pinned memory written by the device)."""
 
-    __slots__ = ("accept_len", "n_new", "cur_len", "new_tokens", "draft_tokens", "target_ids", "k_row", "engine_status")
+    __slots__ = ("accept_len", "n_new", "cur_len", "new_tokens", "draft_tokens", "target_ids", "k_row", "engine_status",
+                 "logprob", "rank", "top_ids", "top_logprobs")
 
-    def __init__(self, arr: np.ndarray, K: int):
+    def __init__(self, arr: np.ndarray, K: int, lp: Optional[np.ndarray] = None):
+        """arr: the record's slot [B][rec_ints]; lp: the same launch's slot of log-prob words [B][K+1][2 + 2N] (set_logprobs), or
+        None while that mode is off."""
         self.accept_len = arr[:, 0].copy()
         self.n_new = arr[:, 1].copy()
         self.cur_len = arr[:, 2].copy()
         self.new_tokens = arr[:, 3:4 + K].copy()
         self.draft_tokens = arr[:, 4 + K:4 + 2 * K].copy()
         self.target_ids = arr[:, 4 + 2 * K:5 + 3 * K].copy()
+        # per-token log-probs (HipSpecDec.set_logprobs): entry (b, i) describes new_tokens[b][i]; NaN / -1 where nothing was emitted
+        self.logprob = self.rank = self.top_ids = self.top_logprobs = None
+        if lp is not None:
+            n = (lp.shape[2] - 2) // 2
+            w = lp.copy()
+            self.logprob = w[:, :, 0].view(np.float32)
+            self.rank = w[:, :, 1]
+            self.top_ids = w[:, :, 2:2 + n]
+            self.top_logprobs = w[:, :, 2 + n:2 + 2 * n].view(np.float32)
         self.k_row = arr[:, 5 + 3 * K].copy()      # proposals that counted per row (per-row adaptive K, confidence gating), else K
         # health word of the models' persistent launches (sd_model_engine_status): a launch that gave up leaves garbage
         self.engine_status = int(arr[0, 6 + 3 * K]) if arr.shape[1] > 6 + 3 * K else 0
@@ -703,6 +715,8 @@ class HipSpecDec:
         self.spec_shape = None     # (top_k, top_p) of the speculative-sampling mode, None = the whole vocabulary
         self.draft_confidence = None   # (tau, min_k) of set_draft_confidence, None = every row proposes K
         self._conf_logits = self.draft_conf = None
+        self.logprobs = None           # top_n of set_logprobs, None = off
+        self._lp_words = None          # the pinned words [2][B][K+1][2 + 2N] while the mode is on
         self._logits = self._draft_logits = self._draw = self._stream_ids = None
         # per-row parameters (set_row_sampling): none; the table is allocated at first use and kept (rewritten in place)
         self.row_table = None          # uint8 [B][32] on the device: sd_row_sampling[B], or None while the scalars rule
@@ -926,6 +940,31 @@ class HipSpecDec:
                 self.draft_conf.data_ptr()), "sd_specdec_set_draft_confidence")
             self.draft_confidence = (float(tau), int(min_k))
 
+    def set_logprobs(self, top_n: Optional[int]) -> None:
+        """Per-token log-probs inside the step (sd_specdec_set_logprobs; None switches it off): every emitted token is described
+        by the verify row it was checked against or drawn from — log-prob and rank at temperature 1 over the stored (processed)
+        values, and the `top_n` (0..20) largest entries of the row. The numbers arrive with the step record (StepRecord.logprob,
+        rank, top_ids, top_logprobs: [B][K+1], entry i for new_tokens[b][i]). The rows are `step_logits`, shared with every mode
+        that stores them; a plain greedy step stores them too while this is on. The caller has drained the loop."""
+        with torch.cuda.device(self.device):
+            if top_n is None:
+                _abi.check(self.lib.sd_specdec_set_logprobs(self.handle, 0, 0, None, 0), "sd_specdec_set_logprobs")
+                self.logprobs = self._lp_words = None
+                return
+            fresh = self._logits is None
+            logits = self._step_logits()
+            if fresh:
+                torch.cuda.current_stream(self.device).synchronize()
+            _abi.check(self.lib.sd_specdec_set_logprobs(self.handle, 1, int(top_n), logits.data_ptr(), logits.numel() * 2),
+                       "sd_specdec_set_logprobs")
+            self.logprobs = int(top_n)
+            words = int(self.lib.sd_specdec_logprob_words(self.handle))
+            self._lp_words = np.ctypeslib.as_array(self.lib.sd_specdec_logprobs(self.handle), shape=(2, self.B, self.K + 1, words))
+
+    def _record_of(self, index: int) -> StepRecord:
+        slot = index & 1   # the record of launch i and its log-prob words share slot i & 1
+        return StepRecord(self._record[slot], self.K, self._lp_words[slot] if self._lp_words is not None else None)
+
     def set_logit_counts_row(self, b: int, prompt_ids: Sequence[int], generated_ids: Sequence[int] = ()) -> None:
         """Row b's counts for a new sequence in its slot: the prompt bit of every prompt id, one count per generated id
         (sd_logit_counts_set on the loop's target stream)."""
@@ -1056,7 +1095,7 @@ class HipSpecDec:
         with torch.cuda.device(self.device):
             _abi.check(self.lib.sd_specdec_sync(self.handle, self.stream_t.cuda_stream), "sd_specdec_sync")
         last = max(int(self.lib.sd_specdec_launches(self.handle)) - 1, 0)
-        return StepRecord(self._record[last & 1], self.K)
+        return self._record_of(last)
 
     @property
     def launches(self) -> int:
@@ -1082,7 +1121,7 @@ class HipSpecDec:
         """Wait for one of the last two launched steps (the other may still be running) and return its record."""
         with torch.cuda.device(self.device):
             _abi.check(self.lib.sd_specdec_wait(self.handle, int(launch_index)), "sd_specdec_wait")
-        return StepRecord(self._record[launch_index & 1], self.K)
+        return self._record_of(launch_index)
 
     def close(self):
         if getattr(self, "handle", None):

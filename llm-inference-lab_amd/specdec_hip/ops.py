@@ -503,6 +503,63 @@ def draft_confidence(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -
     return out
 
 
+class TokenLogprobs(NamedTuple):
+    logprob: torch.Tensor        # float32 [R]
+    rank: torch.Tensor           # int32 [R]
+    top_ids: torch.Tensor        # int32 [R][N]
+    top_logprobs: torch.Tensor   # float32 [R][N]
+
+
+def token_logprobs(logits: torch.Tensor, token_ids, top_n: int = 0, out: Optional[TokenLogprobs] = None) -> TokenLogprobs:
+    """Log-prob, rank and the top-N alternatives of one token per logits row (sd_token_logprobs), at temperature 1 over the
+    stored values: logprob = (x_t - max) - log sum exp(x - max), rank = the entries that beat x_t under the argmax kernels' ties
+    (0: the row's argmax), the N = min(top_n, V) largest entries (value descending, index ascending) as ids and log-probs.
+
+    logits: [R, V] f32 / bf16 / f16 on the GPU, unit stride along V; a view whose rows are further apart than V, or start off a
+    16-byte boundary, is taken as it is. token_ids: R ids, a host sequence (checked against [0, V) here) or an int32 tensor [R]
+    on the device (an id outside the vocabulary then yields the NaN / -1 record). top_n in 0..20. A token at -inf has logprob
+    -inf; a row with nothing above -inf gives logprob NaN, rank -1 and top ids -1. `out` (contiguous tensors of the result's
+    shapes) makes the call allocation-free."""
+    lib = _abi.load()
+    dev = _require_device("token_logprobs", logits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("token_logprobs: need logits [R, V]")
+    if logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"token_logprobs: logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    R, V = logits.shape
+    top_n = int(top_n)
+    if not 0 <= top_n <= 20:
+        raise ValueError(f"token_logprobs: top_n {top_n} outside 0..20")
+    if isinstance(token_ids, torch.Tensor) and token_ids.is_cuda:
+        if token_ids.dtype != torch.int32 or tuple(token_ids.shape) != (R,) or token_ids.device != dev:
+            raise ValueError(f"token_logprobs: token_ids must be int32 [{R}] on {dev}")
+        ids = token_ids.contiguous()
+    else:
+        host = [int(t) for t in (token_ids.tolist() if isinstance(token_ids, torch.Tensor) else token_ids)]
+        if len(host) != R:
+            raise ValueError(f"token_logprobs: {len(host)} token ids for {R} rows")
+        bad = [t for t in host if not 0 <= t < V]
+        if bad:
+            raise ValueError(f"token_logprobs: token id {bad[0]} outside [0, {V})")
+        ids = torch.tensor(host, dtype=torch.int32, device=dev)
+    if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    N = min(top_n, V)
+    if out is None:
+        out = TokenLogprobs(torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+                            torch.empty((R, N), dtype=torch.int32, device=dev), torch.empty((R, N), dtype=torch.float32, device=dev))
+    else:
+        want = ((R,), torch.float32), ((R,), torch.int32), ((R, N), torch.int32), ((R, N), torch.float32)
+        for t, (shape, dt) in zip(out, want):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"token_logprobs: out must hold contiguous tensors {want} on {dev}")
+    with torch.cuda.device(dev):
+        _abi.check(lib.sd_token_logprobs(logits.data_ptr(), sd_dtype(logits.dtype), logits.stride(0) if R > 1 else V, R, V, ids.data_ptr(),
+                                         top_n, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr() if N else None,
+                                         out[3].data_ptr() if N else None, _stream_ptr(dev)), "sd_token_logprobs")
+    return out
+
+
 def _row_table(name: str, table, B: int, dev) -> torch.Tensor:
     """The device table of a _rows op: a list of SamplingParams is packed, a tensor (sampling_params.pack: uint8 [B][32]) is
     taken as it is."""

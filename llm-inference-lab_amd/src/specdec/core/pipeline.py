@@ -43,6 +43,7 @@ from ..utils.deterministic import ensure_deterministic, set_deterministic_mode
 from ..utils.interfaces import LanguageModel
 from .acceptance import device_rule, session_rule
 from .draft_confidence import check_session, session_confidence
+from . import logprobs as lpmod
 from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
 PromptLike = Union[str, Sequence[int], torch.Tensor]
@@ -99,7 +100,7 @@ def expected_tokens_per_step(alpha: Sequence[float], k_max: int = 8) -> Dict[int
 
 class _Row:
     __slots__ = ("seq", "generated", "active", "proposed", "accepted", "draws", "steps", "strict_acc", "strict_prop", "k_trace", "counters",
-                 "n_prompt")
+                 "n_prompt", "token_info")
 
     def __init__(self, seq: List[int]):
         self.seq, self.generated, self.active = seq, [], True
@@ -108,6 +109,7 @@ class _Row:
         self.counters: List[tuple] = []            # after each of the row's own steps: (proposed, accepted, tokens generated, accept length)
         self.strict_acc = self.strict_prop = 0     # per-row adaptive K: what the row's controller is fed with
         self.k_trace: List[int] = []               # ... and the k that counted in each of its steps
+        self.token_info: List[Any] = []            # logprobs: entry j is the TokenInfo of generated[j] (empty while the mode is off)
 
 
 class SpeculativePipeline:
@@ -365,39 +367,52 @@ class SpeculativePipeline:
 
     # ------------------------------------------------------------------ host-side rules
     def _rules_batch(self, row: _Row, k: int, a: int, t: List[int], max_tokens: int, eos: Optional[int],
-                     resample=None, dedup: bool = True) -> None:
+                     resample=None, dedup: bool = True, info=None, resample_info=None) -> None:
         """One row of one generate_batch step (pipeline.py:3018-3590), from the step record:
         a = accepted length, t[i] = target argmax after the row's sequence + d_1..d_i (sampling mode:
         t[a] is the token the device sampled at position a; `resample(pos)` draws at another position
         with the same Philox draw — only an EOS-cut full acceptance needs it). dedup=False (a row under a grammar): the
-        overlap / de-duplication rules are not applied — they delete tokens the row's automaton has consumed."""
+        overlap / de-duplication rules are not applied — they delete tokens the row's automaton has consumed.
+        info (logprobs; None: nothing is tracked): a payload parallel to t, entry i describing t[i]; every slice, append and delete
+        applied to the tokens is applied to it too, into row.token_info, which stays parallel to row.generated.
+        resample_info(pos, token): the payload of a token `resample` drew at another position."""
         V = self.base_lm.vocab_size
-        gen = row.generated
+        gen, ginfo = row.generated, row.token_info
         if a > 0:
             acc = [_clamp(x, V) for x in t[:a]]
+            acc_i = list(info[:a]) if info is not None else None
             if eos is not None and eos in acc:           # accepted EOS: cut there, row stops (:3120-3131)
                 acc = acc[: acc.index(eos)]
                 row.active = False
             pos = a if a < k else len(acc)                # (:3140-3231) the extra forward runs over seq + cut acc
-            bonus = _clamp(t[pos] if (resample is None or pos == a) else resample(pos), V)
+            redrawn = not (resample is None or pos == a)
+            bonus = _clamp(resample(pos) if redrawn else t[pos], V)
             if eos is not None and bonus == eos:         # bonus EOS stays in the output (:3274-3280)
                 row.active = False
             acc.append(bonus)
+            if info is not None:
+                acc_i = acc_i[: len(acc) - 1] + [resample_info(pos, bonus) if redrawn else info[pos]]
             if gen and dedup:                            # overlap with the generated tail (:3295-3318)
                 for c in range(min(5, len(gen), len(acc)), 0, -1):
                     if gen[-c:] == acc[:c]:
                         acc = acc[c:]
+                        acc_i = acc_i[c:] if info is not None else None
                         break
             gen.extend(acc)
             emitted = acc
         else:
             emitted = [_clamp(t[0], V)]
+            acc_i = [info[0]] if info is not None else None
             if eos is not None and emitted[0] == eos:    # (:3360-3365)
                 row.active = False
                 emitted = []
             if dedup and emitted and gen and gen[-1] == emitted[0]:  # (:3367-3376)
                 emitted = []
             gen.extend(emitted)
+            if not emitted:
+                acc_i = [] if info is not None else None
+        if info is not None:
+            ginfo.extend(acc_i)
         row.proposed += k
         row.accepted += len(emitted)
         if emitted:                                      # sequence update with its own overlap rule (:3470-3572)
@@ -408,6 +423,8 @@ class SpeculativePipeline:
                     acc = acc[c:]
                     if len(gen) >= c:
                         del gen[-c:]
+                        if info is not None:
+                            del ginfo[-c:]
                 else:
                     acc = []
             row.seq = cur + acc
@@ -434,7 +451,8 @@ class SpeculativePipeline:
     def start_session(self, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                       sampling: Union[None, Dict[str, Any], StepOptions] = None, step_limit: Optional[int] = None,
                       self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
-                      draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, **processors) -> "DecodeSession":
+                      draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
+                      **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
@@ -442,7 +460,9 @@ class SpeculativePipeline:
         repetition_penalty, presence_penalty, frequency_penalty, logit_bias, bad_token_ids, allowed_token_ids; identity values
         leave the stage off. grammar: a TokenFSM, or a list with one entry per prompt (None: that row is unconstrained).
         sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated.
-        draft_confidence / draft_min_k: the confidence-gated draft length (generate_batch), the bonus-token emit mode only."""
+        draft_confidence / draft_min_k: the confidence-gated draft length (generate_batch), the bonus-token emit mode only.
+        logprobs: per-token log-probs (True / 0: the chosen token's; 1..20: that many alternatives too), the bonus-token emit mode
+        only; every row's token_info then stays parallel to its generated tokens."""
         if sampling_params is not None and sampling is not None:
             raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
         session_rule(self, StepOptions(), emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (its refusals come first)
@@ -451,6 +471,7 @@ class SpeculativePipeline:
         options = with_stage(self, options, processors, grammar, len(prompts))
         options = session_rule(self, options, emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (a device acceptance rule)
         options = session_confidence(self, options, emit_mode, self_draft, draft_confidence, draft_min_k, HipSpecDec.EMIT_BONUS)
+        options = lpmod.session_logprobs(self, options, emit_mode, self_draft, logprobs, HipSpecDec.EMIT_BONUS)
         return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
@@ -655,7 +676,8 @@ class SpeculativePipeline:
         t_begin = time.time()
         call = resolve(self, [prompt], max_tokens, temperature, do_sample, kwargs, grammar=kwargs.pop("grammar", None),
                        sampling_params=kwargs.pop("sampling_params", None), share_prefix=kwargs.get("share_prefix"), n=kwargs.get("n", 1),
-                       single=True, draft_confidence=kwargs.pop("draft_confidence", None), draft_min_k=kwargs.pop("draft_min_k", None))
+                       single=True, draft_confidence=kwargs.pop("draft_confidence", None), draft_min_k=kwargs.pop("draft_min_k", None),
+                       logprobs=kwargs.pop("logprobs", None))
         if call.route == "host_policy":
             rows, st = self._decode_host_policy(call.ids, call.max_tokens, HipSpecDec.EMIT_DRAFT, step_limit=2 * call.max_tokens,
                                                 temperature=call.temperature, sample_t=call.sample_t,
@@ -683,7 +705,8 @@ class SpeculativePipeline:
     def generate_batch(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None,
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
                        share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None,
-                       draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
+                       draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
+                       best_of: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -716,11 +739,28 @@ class SpeculativePipeline:
         first k proposals count, a draft forward no row needs returns at entry, every step starts at K again. Greedy output is
         the target's own greedy decoding whatever k was. Results carry `k_trace`; `proposed` counts the k of every step;
         batch_metrics carries mean_k and draft_forwards_skipped. For the draft-model mode with a fixed K, greedy or do_sample;
-        refused next to speculative sampling, the device acceptance rules, logit processors, grammars and sampling_params."""
+        refused next to speculative sampling, the device acceptance rules, logit processors, grammars and sampling_params.
+
+        logprobs (opt-in; not in the reference): True or 0 — every result gains `logprobs` (one float per generated token),
+        `token_ranks` and `cumulative_logprob` (their Python float sum, in emission order); 1..20 — also `top_logprobs`, that
+        many (id, logprob) alternatives per token. Computed on the device inside the step that emits the token
+        (sd_specdec_set_logprobs), from the verify row the token was checked against or drawn from: the target's distribution at
+        temperature 1 after the logit processors and the grammar, before top-k / top-p shaping. For the captured step with a
+        draft model and a fixed K, in every select mode; refused on the host loops, with implementation='fake', medusa / eagle /
+        self-draft, adaptive K, draft_confidence and generate().
+
+        best_of=m >= n (opt-in): every prompt decodes m rows (the `n` machinery: one shared prompt, a Philox stream per row) and
+        the n with the highest cumulative_logprob come back, best first, ties to the lower row. Implies logprobs; needs a
+        sampling mode (greedy rows are all equal). batch_metrics carries best_of."""
         if not prompts:
             return []
+        m_best = lpmod.check_best_of(best_of, n)
+        if m_best is not None:
+            n_keep, n, logprobs = int(n), m_best, (0 if lpmod.check_logprobs(logprobs) is None else logprobs)
         call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
-                       sampling_params=sampling_params, draft_confidence=draft_confidence, draft_min_k=draft_min_k)
+                       sampling_params=sampling_params, draft_confidence=draft_confidence, draft_min_k=draft_min_k, logprobs=logprobs)
+        if m_best is not None:
+            lpmod.check_best_of_mode(call.options)
         if call.route == "fake":
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
         prompts, max_tokens = call.prompts, call.max_tokens
@@ -762,13 +802,17 @@ class SpeculativePipeline:
                 "batch_metrics": batch_metrics, "kv_append_enabled": True, "kv_append_backend": "hip",
                 "kv_appended_tokens": n, "kv_append_time_ms": 0.0, "sequence": list(r.seq),
                 **({"k_trace": list(r.k_trace)} if r.k_trace else {}),     # per-row adaptive K: the k of each of the row's steps
+                **lpmod.result_fields(r, call.options.logprobs),
             })
+        if m_best is not None:
+            batch_metrics["best_of"] = m_best
+            out = lpmod.pick_best(out, m_best, n_keep)
         return out
 
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
                       grammar=None, sampling_params=None, draft_confidence: Optional[float] = None,
-                      draft_min_k: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
+                      draft_min_k: Optional[int] = None, logprobs=None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -781,11 +825,14 @@ class SpeculativePipeline:
         sampling_params: as generate_batch, one entry per prompt; a prompt admitted to a slot brings its own entry, its seed and
         its Philox stream (its index among the call's rows) with it — the slot's table entry, stream id and draw counter are
         rewritten on the loop's stream and the captured step is kept.
-        draft_confidence / draft_min_k: as generate_batch; the device keeps no per-row state for it, so an admission sets nothing."""
+        draft_confidence / draft_min_k: as generate_batch; the device keeps no per-row state for it, so an admission sets nothing.
+        logprobs: as generate_batch (best_of is a generate_batch argument and is refused here)."""
         if not prompts:
             return []
+        lpmod.refuse_best_of(kwargs)
         call = resolve(self, prompts, max_tokens, temperature, do_sample, kwargs, share_prefix=share_prefix, n=n, grammar=grammar,
-                       sampling_params=sampling_params, policy_routes=False, draft_confidence=draft_confidence, draft_min_k=draft_min_k)
+                       sampling_params=sampling_params, policy_routes=False, draft_confidence=draft_confidence, draft_min_k=draft_min_k,
+                       logprobs=logprobs)
         prompts, ids, max_tokens, options = call.prompts, call.ids, call.max_tokens, call.options
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
@@ -826,7 +873,7 @@ class SpeculativePipeline:
                         "throughput_tokens_per_sec": tot_tok / (total_ms / 1e3) if total_ms > 0 else 0.0,
                         "acceptance_rate": r.accepted / max(r.proposed, 1), "proposed": r.proposed, "accepted": r.accepted,
                         "steps": r.steps, "sequence": list(r.seq), "kv_append_enabled": True, "kv_append_backend": "hip",
-                        **({"k_trace": list(r.k_trace)} if r.k_trace else {}),
+                        **({"k_trace": list(r.k_trace)} if r.k_trace else {}), **lpmod.result_fields(r, options.logprobs),
                         "batch_metrics": {"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
                                           "void_row_steps": sess.stats["void_row_steps"], "k": sess.k,
                                           "mean_k": sess.stats["proposed"] / max(sum(x.steps for x, _ in done.values()), 1),
@@ -965,6 +1012,8 @@ class DecodeSession:
             self.k = pipe._effective_k(ctl.get_k(1, {"step": 1, "generated_tokens": 0, "acceptance_rate": 0.0}), self_draft)
         # confidence-gated draft length: the device rewrites every row's k inside each step and the record carries it; the host mirrors nothing
         self._conf = check_session(o, other_step, emit_mode == HipSpecDec.EMIT_BONUS, self.k)
+        # per-token log-probs: the step describes every emitted token and the record carries it (None: off, else top_n)
+        self._logprobs = lpmod.check_session(o, other_step, emit_mode == HipSpecDec.EMIT_BONUS)
         self.rt, self.loop = pipe._runtime(len(self.rows), self.need, self.k, emit_mode, self.self_draft, adaptive=self.per_row)
         # positions a row may use: the cache rows and both models' position tables
         self.pos_limit = min(self.rt["l_max"], pipe.base_lm.config.max_pos,
@@ -994,6 +1043,7 @@ class DecodeSession:
                 for b in range(len(self.rows)):
                     self.loop.set_adaptive_row(b, ctl.initial_k)
         self._configure_loop()
+        self._configure_logprobs()
         self._stateful_draft = self_draft and (pipe.medusa_heads is not None or pipe._eagle())
         if self_draft and pipe._eagle():
             self.loop.reset_eagle()   # the reference keeps the state on the pipeline object, across generate() calls even; here a run starts clean
@@ -1040,6 +1090,9 @@ class DecodeSession:
         """Loops are cached per (batch, K) and outlive sessions: switch the one in use off what another run left on it and to this
         run's sampling mode, with every row's stream id and draw count. Every set_* call drops the captured step."""
         o, loop, spec = self.options, self.loop, self._spec
+        if getattr(loop, "logprobs", None) not in (None, self._logprobs):    # (first of all: confidence gating's setter refuses next to it)
+            loop.drain()
+            loop.set_logprobs(None)
         want_conf = (o.draft_confidence, o.draft_min_k) if self._conf else None
         if getattr(loop, "draft_confidence", None) not in (None, want_conf):    # (first of all: every other mode's setter refuses next to it)
             loop.sync()
@@ -1098,6 +1151,22 @@ class DecodeSession:
                 self._set_grammar_state(b)
         elif loop.grammar is not None:
             loop.set_grammar(None)
+
+    def _configure_logprobs(self) -> None:
+        """The log-prob stage of this run, after every other mode is what the run wants (what _configure_sampling left on from an
+        earlier run with the same top_n stays on)."""
+        if self._logprobs is not None and self.loop.logprobs != self._logprobs:
+            self.loop.drain()
+            self.loop.set_logprobs(self._logprobs)
+
+    def _resample_info(self, b: int):
+        """The payload of a token the host redrew at another row of the step's logits (next to _resampler's draw)."""
+        loop, top_n = self.loop, self._logprobs
+
+        def resample_info(pos: int, tok: int):
+            with torch.cuda.stream(loop.stream_t):
+                return lpmod.redraw_payload(loop.step_logits[b, pos], tok, top_n)
+        return resample_info
 
     def _set_grammar_state(self, b: int) -> None:
         """Row b's automaton state as the host sees the row: its own start state walked over what it has generated so far."""
@@ -1251,6 +1320,7 @@ class DecodeSession:
                 for b, r in enumerate(rows):
                     pipe._set_row(self.loop, b, r)
                 self._configure_loop()
+                self._configure_logprobs()
         k, loop, rt = self.k, self.loop, self.rt
         t0 = time.time()
         if not self._queue:
@@ -1304,9 +1374,11 @@ class DecodeSession:
             assumed = before + t[: int(rec.n_new[b])]  # what the device advanced to
             if self.emit_mode == HipSpecDec.EMIT_BONUS:
                 constrained = self.grammar is not None and self.grammar_starts[b] >= 0
+                # logprobs: t[i] is new_tokens[b][i] for every i < n_new, and the rules read no other position
+                info = lpmod.step_payload(rec, b, len(t)) if self._logprobs is not None else None
                 pipe._rules_batch(r, k, a, t, self.max_tokens, self.grammar.eos_id if constrained else self.eos,
                                   self._resampler(b, r) if (self._sampled and not self._spec and not self._accept) else None,
-                                  dedup=not constrained)
+                                  dedup=not constrained, info=info, resample_info=self._resample_info(b) if info is not None else None)
                 if self._sampled:
                     r.draws += (k + 1) if self._spec else 1
             else:

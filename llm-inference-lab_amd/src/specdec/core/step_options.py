@@ -13,6 +13,7 @@ from specdec_hip.sampling_params import SamplingParams, check_penalties
 from ..policies.controllers import FixedKController
 from .acceptance import refuse_call, with_rule
 from .draft_confidence import with_confidence
+from .logprobs import with_logprobs
 
 PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "bad_token_ids", "allowed_token_ids")
 ROW_SAMPLING_CLASH = ("top_k", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty")
@@ -60,6 +61,8 @@ class StepOptions:
     # first forward i + 1 >= draft_min_k whose confidence (the draft's softmax probability of its own token) is below the threshold
     draft_confidence: Optional[float] = None
     draft_min_k: int = 1
+    # per-token log-probs (sd_specdec_set_logprobs): None = off, else the alternatives listed per emitted token (0: its own log-prob only)
+    logprobs: Optional[int] = None
 
     def __post_init__(self):
         # a grammar is a line of the processor stage, and requests with penalties of their own need it: identity scalars will do
@@ -102,6 +105,9 @@ _GATE = {
                          "draft_confidence needs the draft-model mode (draft_mode='vanilla'): medusa / eagle drafting has no draft forward to judge",
                          "draft_confidence moves every row's k inside the step and needs a fixed shape K (controller='fixed'): adaptive K is not "
                          "supported with it"),
+    "logprobs": ("logprobs are computed inside the captured device step: {what} is not supported with them",
+                 "logprobs need the draft-model mode (draft_mode='vanilla'): medusa / eagle / self-draft steps store no verify rows",
+                 "logprobs keep a fixed K (controller='fixed'): adaptive K is not supported"),
 }
 
 
@@ -243,7 +249,7 @@ Call = namedtuple("Call", "route prompts ids options max_tokens temperature samp
 
 def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kwargs: Dict[str, Any], share_prefix=False, n=1,
             grammar=None, sampling_params=None, single: bool = False, policy_routes: bool = True, draft_confidence=None,
-            draft_min_k=None) -> Call:
+            draft_min_k=None, logprobs=None) -> Call:
     """A call's arguments -> its route, its prompts expanded with n, their ids and its options, every refusal raised on the way.
     single (generate): one row and no bonus token; the draft modes draft; do_sample=True is the host loop drawing the draft's tokens at
     sample_t. policy_routes (generate, generate_batch): the policy chooses between the captured step and the host loops, persistent heads
@@ -275,6 +281,7 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
             gate(pipe, "grammar", False, "implementation='fake'")
         if draft_confidence is not None:
             gate(pipe, "draft_confidence", False, "implementation='fake'")
+        with_logprobs(pipe, StepOptions(), logprobs, False, "implementation='fake'")
         return Call("fake", list(prompts), [], StepOptions(), max_tokens, temperature, None, False, False)
     max_tokens, temperature = max_tokens or cfg["max_new_tokens"], temperature or cfg["temperature"]      # (0 is "not given")
     do_sample, sampling = do_sample if do_sample is not None else cfg["do_sample"], rows
@@ -319,5 +326,6 @@ def resolve(pipe, prompts: Sequence[Any], max_tokens, temperature, do_sample, kw
         draft_confidence = cfg.get("draft_confidence_threshold")
         draft_min_k = cfg.get("draft_min_k") if draft_confidence is not None and draft_min_k is None else draft_min_k
     options = with_confidence(pipe, options, draft_confidence, draft_min_k, on_step and not fake, what, bool(heads), single)
+    options = with_logprobs(pipe, options, logprobs, on_step and not fake, "implementation='fake'" if fake else what, bool(heads), single)
     self_draft = cfg.get("draft_mode") in ("medusa", "eagle") if single else heads and longest
     return Call(route, prompts, ids, options, max_tokens, float(temperature) if single else temperature, sample_t, share_prefix, self_draft)

@@ -81,6 +81,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "frequency_penalty): per-request parameters read row by row inside the captured step; temperature 0 is a "
                          "greedy request; with --n every completion shares its prompt's entry; decodes through generate_batch "
                          "(sampled bonus token, or speculative sampling with --spec-sampling)")
+    ap.add_argument("--logprobs", type=int, metavar="N",
+                    help="per-token log-probs of the generated tokens under the target, computed inside the captured step from the row "
+                         "each token was checked against or drawn from: 0 = the chosen token's log-prob and rank, 1..20 = that many "
+                         "alternatives as well; adds logprobs, token_ranks, top_logprobs, cumulative_logprob; decodes through generate_batch")
+    ap.add_argument("--best-of", type=int, metavar="M",
+                    help="decode M >= --n rows of the prompt and return the --n with the highest cumulative log-prob, best first "
+                         "(implies --logprobs 0; needs a sampling mode: --spec-sampling or --sampling-params)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
@@ -196,7 +203,8 @@ def main(argv=None) -> int:
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         conf = args.draft_confidence is not None
-        batch = conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
+        lp = args.logprobs is not None or args.best_of is not None
+        batch = lp or conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:
@@ -205,11 +213,14 @@ def main(argv=None) -> int:
             proc["sampling_params"] = row_params
         if conf:       # confidence-gated draft length inside the captured step
             proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
+        if lp:         # per-token log-probs inside the captured step; best_of ranks the rows by their sum
+            proc.update(logprobs=args.logprobs, best_of=args.best_of)
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
             rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],
                  "acceptance_rate": rs[0]["accepted"] / max(rs[0]["proposed"], 1), "n": len(rs), "texts": [x["text"] for x in rs],
-                 "forked_rows": rs[0]["batch_metrics"]["forked_rows"], "shared_positions": rs[0]["batch_metrics"]["shared_positions"]}
+                 "forked_rows": rs[0]["batch_metrics"]["forked_rows"], "shared_positions": rs[0]["batch_metrics"]["shared_positions"],
+                 "cumulative_logprobs": [x.get("cumulative_logprob") for x in rs]}
         else:
             r = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=False, **proc)
         if args.eval_perplexity:
@@ -223,6 +234,9 @@ def main(argv=None) -> int:
             "base_model", "draft_model", "draft_mode", "dtype")
     if args.share_prefix or args.n != 1:
         keys += ("n", "texts", "forked_rows", "shared_positions")
+    if args.logprobs is not None or args.best_of is not None:
+        keys += ("generated_tokens", "logprobs", "token_ranks", "cumulative_logprob", "cumulative_logprobs")
+        keys += ("top_logprobs",) if (args.logprobs or 0) > 0 else ()
     if args.eval_perplexity:
         keys += ("perplexity", "perplexity_loss")
     if args.eval_agreement:

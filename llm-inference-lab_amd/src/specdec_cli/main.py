@@ -91,11 +91,21 @@ def cmd_run(args: argparse.Namespace) -> int:
         raise SystemExit("--draft-min-k belongs to --draft-confidence")
     if conf:     # confidence-gated draft length inside the captured step (a generate_batch mode)
         proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
-    if conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    lp = args.logprobs is not None or args.best_of is not None
+    if lp:       # per-token log-probs inside the captured step; best_of ranks the rows by their sum (generate_batch)
+        proc.update(logprobs=args.logprobs, best_of=args.best_of)
+        if args.do_sample:
+            proc.update(do_sample=True, temperature=args.temperature, seed=args.seed)
+    if lp or conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
             print(f"Text {i}: {x.get('text', '')}")
+        if lp:
+            import json
+
+            fields = ("generated_tokens", "logprobs", "token_ranks", "top_logprobs", "cumulative_logprob")
+            print("Logprobs: " + json.dumps([{k: x[k] for k in fields if k in x} for x in rs]))
     else:
         res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample, **proc)
     kinfo = get_kernel_info()
@@ -143,6 +153,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="stop drafting a row once the draft's probability of its own token falls below TAU in (0, 1], decided on the "
                          "device between two draft forwards of the captured step (generate_batch)")
     pr.add_argument("--draft-min-k", type=int, metavar="N", help="--draft-confidence: always draft at least N tokens (default 1)")
+    pr.add_argument("--logprobs", type=int, metavar="N",
+                    help="per-token log-probs of the generated tokens, computed inside the captured step: 0 = the chosen token's, "
+                         "1..20 = that many alternatives as well; printed as one JSON line (generate_batch)")
+    pr.add_argument("--best-of", type=int, metavar="M",
+                    help="decode M >= --n rows and keep the --n with the highest cumulative log-prob, best first (implies --logprobs 0; "
+                         "needs --do-sample, --spec-sampling or --sampling-params)")
     pr.add_argument("--repetition-penalty", type=float, help="repetition penalty (> 0) over prompt + generated tokens, inside the captured step")
     pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
     pr.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
