@@ -591,6 +591,20 @@ int sd_model_matrix_shape(const sd_model* m, int which, int* N, int* K, int* n_p
 int sd_gemv_variant(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap);
 int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue, int epi, char* out, size_t cap);
 
+/* Diagnostics of the K-token attention launch (csrc/attention.hip); host-only, additive (SD_ABI_VERSION stays 1).
+ *
+ * sd_attention_plan answers, from dimensions alone (no device call), the geometry launch_attention decides from the same
+ * function for B rows x M tokens over a cache of l_max positions per row: *tiles = 16-row query tiles per (row, kv head),
+ * ceil(Hq / Hkv * M / 16); *n_split = workgroups per tile (split-KV): l_max / 512, at most 32, at most the workspace's
+ * 1024 partial tiles / (Hkv * B * tiles) and at most 512 / (Hkv * B * tiles), at least 1 (a row uses
+ * min(n_split, ceil(key blocks / 16)) of them); the grid is (*grid_x, *grid_y, *grid_z) = (Hkv, B, tiles * n_split).
+ * paged: 0 = dense cache rows, else the positions per page. The engine's launches always have the split workspace, so
+ * the query assumes it; SPECDEC_NO_ATTN_SPLIT in the environment gives n_split 1, as at a launch. Refused (nonzero): a
+ * NULL output, heads or M above 255, and what the launch refuses, in its words (head_dim not 32 / 64 / 128, Hq % Hkv,
+ * B or M below 1, l_max not a multiple of 8, pages not 32 * 2^n positions or l_max not whole pages). */
+int sd_attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles, int* n_split,
+                      int* grid_x, int* grid_y, int* grid_z);
+
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *
  * sd_persist_plan answers, from a model's dimensions and facts alone (no weights, no device call; a GPU of 256 CUs is

@@ -69,37 +69,47 @@ static void launch_attention_d(const AttnArgs& a, int waves, dim3 grid, hipStrea
 size_t attention_split_tiles_bytes(int head_dim) { return static_cast<size_t>(kAttnSplitSlots) * kAttnRows * (head_dim + 2) * sizeof(float); }
 size_t attention_split_ws_bytes(int head_dim) { return attention_split_tiles_bytes(head_dim) + static_cast<size_t>(kAttnSplitSlots) * sizeof(unsigned); }
 
+int attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int page_shift, bool has_split_ws,
+                   int split_slots, AttnPlan& plan) {
+  SD_REQUIRE(head_dim == 32 || head_dim == 64 || head_dim == 128,
+             "attention: head_dim %d not in {32,64,128}", head_dim);
+  SD_REQUIRE(n_kv_heads > 0 && n_q_heads % n_kv_heads == 0, "attention: Hq %% Hkv != 0");
+  SD_REQUIRE(B >= 1 && M >= 1, "attention: empty batch");
+  SD_REQUIRE(l_max % 8 == 0 && l_max >= 8, "attention: l_max=%d must be a multiple of 8", l_max);
+  SD_REQUIRE(page_shift < 0 || (page_shift >= 5 && page_shift <= 16 && l_max >= (1 << page_shift) && l_max % (1 << page_shift) == 0),
+             "attention: paged cache needs pages of 32 * 2^n positions and l_max = max_pages * page_len");
+  const int G = n_q_heads / n_kv_heads;
+  const int R = G * M;
+  const int tiles = (R + kAttnRows - 1) / kAttnRows;
+  // split-KV: as many workgroups per tile as the cache could keep busy (one per 512 keys of l_max: kAttnSplitBlocks blocks
+  // of kAttnBlock keys), within the partial-tile workspace and ~one wave of workgroups over the chip; the kernel uses
+  // fewer while the row is short. Fixed per launch site, so a captured step stays valid as rows grow.
+  const int base = n_kv_heads * B * tiles;
+  int ns = 1;
+  if (has_split_ws && !getenv(debug_env::kNoAttnSplit)) {
+    ns = l_max / (kAttnBlock * kAttnSplitBlocks);
+    if (ns > kAttnMaxSplit) ns = kAttnMaxSplit;
+    if (ns > split_slots / base) ns = split_slots / base;
+    if (ns > 512 / base) ns = 512 / base;
+    if (ns < 1) ns = 1;
+  }
+  plan = AttnPlan{tiles, ns, n_kv_heads, B, tiles * ns};
+  return 0;
+}
+
 int launch_attention(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;
-  SD_REQUIRE(a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128,
-             "attention: head_dim %d not in {32,64,128}", a.head_dim);
-  SD_REQUIRE(a.n_kv_heads > 0 && a.n_q_heads % a.n_kv_heads == 0, "attention: Hq %% Hkv != 0");
-  SD_REQUIRE(a.B >= 1 && a.M >= 1, "attention: empty batch");
-  SD_REQUIRE(a.l_max % 8 == 0 && a.l_max >= 8, "attention: l_max=%d must be a multiple of 8", a.l_max);
-  SD_REQUIRE(!a.block_table || (a.page_shift >= 5 && a.page_shift <= 16 && a.l_max >= (1 << a.page_shift) && a.l_max % (1 << a.page_shift) == 0),
-             "attention: paged cache needs pages of 32 * 2^n positions and l_max = max_pages * page_len");
-  const int G = a.n_q_heads / a.n_kv_heads;
-  const int R = G * a.M;
-  const int tiles = (R + kAttnRows - 1) / kAttnRows;
+  AttnPlan pl{};
+  if (int rc = attention_plan(a.n_q_heads, a.n_kv_heads, a.head_dim, a.B, a.M, a.l_max, a.block_table ? static_cast<int>(a.page_shift) : -1,
+                              a.split_ws && a.split_cnt, a.split_slots, pl))
+    return rc;
   const int D = a.head_dim;
   // 4 waves per workgroup. 8 and 16 were measured and lose at every context length: the LDS merge grows with the wave
   // count and a 16-wave workgroup holds a CU's LDS alone (3B + 1B, K=4: 8 K context 6.8 ms/step with 4 waves, 9.3 with
   // 16; short contexts equal within noise).
   const int waves = 4;
-  // split-KV: as many workgroups per tile as the cache could keep busy (one per 256 keys of l_max),
-  // within the partial-tile workspace and ~one wave of workgroups over the chip; the kernel uses
-  // fewer while the row is short. Fixed per launch site, so a captured step stays valid as rows grow.
-  const int base = a.n_kv_heads * a.B * tiles;
-  int ns = 1;
-  if (a.split_ws && a.split_cnt && !getenv(debug_env::kNoAttnSplit)) {
-    ns = a.l_max / (kAttnBlock * kAttnSplitBlocks);
-    if (ns > kAttnMaxSplit) ns = kAttnMaxSplit;
-    if (ns > a.split_slots / base) ns = a.split_slots / base;
-    if (ns > 512 / base) ns = 512 / base;
-    if (ns < 1) ns = 1;
-  }
-  a.n_split = ns;
-  const dim3 grid(a.n_kv_heads, a.B, tiles * ns);
+  a.n_split = pl.n_split;
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);
   switch (D) {
     case 32: launch_attention_d<32>(a, waves, grid, st); break;
     case 64: launch_attention_d<64>(a, waves, grid, st); break;

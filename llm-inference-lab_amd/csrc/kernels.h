@@ -207,6 +207,13 @@ struct AttnArgs {
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);
 constexpr int kAttnSplitSlots = 1024;   // partial tiles of the split-KV workspace
+// The geometry of one attention launch, decided on the host from dimensions alone: launch_attention consults it and
+// sd_attention_plan (plan_query.hip) reports it. tiles: 16-row query tiles per (row, kv head); n_split: workgroups per tile
+// (1 = no split-KV); grid = (n_kv_heads, B, tiles * n_split). page_shift < 0: a dense cache. has_split_ws: the launch has a
+// partial-tile workspace of split_slots tiles and its arrival counters. Refuses what launch_attention refuses, in its words.
+struct AttnPlan { int tiles, n_split, grid_x, grid_y, grid_z; };
+int attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int page_shift, bool has_split_ws,
+                   int split_slots, AttnPlan& plan);
 size_t attention_split_ws_bytes(int head_dim);   // workspace for kAttnSplitSlots partial tiles (+ counters)
 size_t attention_split_tiles_bytes(int head_dim);   // the partial tiles of it (split_ws); the kAttnSplitSlots counters (split_cnt) follow
 

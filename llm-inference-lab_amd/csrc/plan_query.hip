@@ -1,5 +1,5 @@
 // Plan queries that need no GPU: which kernel instance, work split or refusal a shape gets, asked from dimensions alone
-// (sd_prefill_plan, sd_prefill_plan_tables, sd_gemm_plan, sd_gemv_variant, sd_gemv_instance, sd_persist_plan) or from a model's
+// (sd_prefill_plan, sd_prefill_plan_tables, sd_gemm_plan, sd_gemv_variant, sd_gemv_instance, sd_attention_plan, sd_persist_plan) or from a model's
 // (sd_model_matrix_shape). Each asks the function the launch itself consults; nothing is enqueued. Host-side C++ behind the C-ABI.
 
 #include <stdarg.h>
@@ -163,6 +163,29 @@ extern "C" int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue,
   int n = 0;
   if (int rc = gemv_instance_name(T, n_pairs, K, w8 == 1, prologue, epi, name, sizeof(name), &n, w12_form_of(w8))) return rc;   // a launch launch_gemv refuses, in its words
   return return_text({"gemv_instance", "cap", "name", 1, out, cap}, name, n, sizeof(name));
+}
+
+extern "C" int sd_attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles, int* n_split,
+                                 int* grid_x, int* grid_y, int* grid_z) {
+  clear_error();
+  SD_REQUIRE(tiles && n_split && grid_x && grid_y && grid_z, "attention_plan: NULL argument");
+  // (AttnArgs holds M and the head counts in 8 bits each)
+  SD_REQUIRE(n_q_heads >= 1 && n_q_heads <= 255 && n_kv_heads >= 0 && n_kv_heads <= 255 && M <= 255 && B <= (1 << 16),
+             "attention_plan: Hq=%d Hkv=%d M=%d B=%d beyond what a launch holds (heads and M <= 255)", n_q_heads, n_kv_heads, M, B);
+  int page_shift = -1;   // paged: 0 = dense rows, else positions per page (a power of two; any other length is refused as the launch would)
+  if (paged != 0) {
+    page_shift = 0;
+    while (page_shift < 30 && (1 << page_shift) < paged) ++page_shift;
+    if (paged < 0 || (1 << page_shift) != paged) page_shift = 0;
+  }
+  AttnPlan pl{};
+  if (int rc = attention_plan(n_q_heads, n_kv_heads, head_dim, B, M, l_max, page_shift, true, kAttnSplitSlots, pl)) return rc;
+  *tiles = pl.tiles;
+  *n_split = pl.n_split;
+  *grid_x = pl.grid_x;
+  *grid_y = pl.grid_y;
+  *grid_z = pl.grid_z;
+  return 0;
 }
 
 extern "C" int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,

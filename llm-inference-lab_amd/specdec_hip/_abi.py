@@ -147,6 +147,7 @@ SIGNATURES = {
     "sd_gemv_variant": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_char_p, _c_size]),
     "sd_gemv_instance": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_char_p, _c_size]),
     "sd_model_matrix_shape": (_c_int, [_c_void_p] + [_c_int] + [ctypes.POINTER(_c_int)] * 5),
+    "sd_attention_plan": (_c_int, [_c_int] * 7 + [ctypes.POINTER(_c_int)] * 5),
     "sd_persist_plan": (_c_int, [_c_int] * 12 + [ctypes.POINTER(_c_int)] * 3 + [ctypes.c_char_p, _c_size, ctypes.c_char_p, _c_size]),
     "sd_model_set_persist_taps": (_c_int, [_c_void_p, _c_int]),
     "sd_model_probe_forward": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, ctypes.POINTER(ctypes.c_float),

@@ -892,6 +892,23 @@ def gemv_instance(T: int, n_pairs: int, K: int, w8: bool = False, prologue: int 
     return buf.value.decode()
 
 
+class AttentionPlan(NamedTuple):
+    tiles: int                    # 16-row query tiles per (row, kv head)
+    n_split: int                  # workgroups per tile (1: no split-KV); a row uses min(n_split, ceil(key blocks / 16)) of them
+    grid: Tuple[int, int, int]    # (Hkv, B, tiles * n_split)
+
+
+def attention_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: int, M: int, l_max: int, paged: int = 0) -> AttentionPlan:
+    """The geometry of one K-token attention launch (csrc/attention.hip) of B rows x M tokens over a cache of l_max positions
+    per row (sd_attention_plan), from the function the launch itself consults. paged: 0 = dense rows, else the page length.
+    Follows SPECDEC_NO_ATTN_SPLIT in the environment, as a launch does; raises where the launch would refuse. Host-only."""
+    out = [ctypes.c_int(0) for _ in range(5)]
+    _abi.check(_abi.load().sd_attention_plan(int(n_q_heads), int(n_kv_heads), int(head_dim), int(B), int(M), int(l_max), int(paged or 0),
+                                             *(ctypes.byref(o) for o in out)), "sd_attention_plan")
+    t, ns, gx, gy, gz = (int(o.value) for o in out)
+    return AttentionPlan(t, ns, (gx, gy, gz))
+
+
 class PersistPlan(NamedTuple):
     eligible: bool       # the model passes every static rule of the persistent forward
     max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)

@@ -170,7 +170,7 @@ def test_batched_verify_shapes_on_synthetic_pair(B, M, monkeypatch):
 @pytest.mark.parametrize("lens,M", [([300, 1500, 40], 5), ([2100], 1), ([900, 901], 9), ([700], 33)])
 def test_long_context_split_kv_attention(lens, M, monkeypatch):
     """Contexts of hundreds to thousands of keys: the keys of a (row, kv head, query tile) are shared by
-    several workgroups (one per 256 keys of the row's CURRENT length, merged by the last arrival). Logits
+    several workgroups (one per 512 keys of the row's CURRENT length, merged by the last arrival). Logits
     against the oracle, and against the one-workgroup-per-tile path (SPECDEC_NO_ATTN_SPLIT)."""
     import dataclasses
 
