@@ -406,6 +406,17 @@ int sd_model_kv_fork(sd_model* m, int src_row, const int32_t* dst_rows, int n_ds
  * (n_pos == page_len: whole pages). Block tables and page ownership stay the caller's. */
 int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, const int32_t* dst_pages, int n_pairs, int n_pos, void* stream);
 
+/* KV eviction inside one cache row (csrc/kv_evict.hip): the rolling context window. In row `row` of a dense cache of a
+ * Llama model, positions [keep + drop, n_pos) become positions [keep, n_pos - drop): all layers, all KV heads, K and V,
+ * in place, in one launch, asynchronous on `stream`, no allocation, capturable. V moves bit for bit. K is stored after
+ * RoPE, so it is rotated by -drop positions: rotate-half pairs (i, i + D/2), c = rope_cos[drop][i], s = rope_sin[drop][i]
+ * of the model's own tables, a' = a c + b s, b' = b c - a s in fp32 from the stored bf16 values, rounded once to bf16.
+ * Positions [0, keep), positions >= n_pos - drop of the row (the stale [n_pos - drop, n_pos) included) and every other row
+ * keep their bits. n_pos == keep + drop succeeds and launches nothing. Refused before any device work (return code +
+ * sd_last_error): an unbound model, a paged model, a GPT-2 model, row out of range, keep < 0, drop < 1 or not a multiple of 8
+ * (source and destination of a V row stay in one 16-byte phase), drop >= max_pos, keep + drop > n_pos, n_pos > Lmax. */
+int sd_model_kv_evict(sd_model* m, int row, int keep, int drop, int n_pos, void* stream);
+
 /* One forward over M new tokens per batch row, appended to the KV cache in place.
  *   tokens   : device int32, token (b,m) at tokens[b*tok_stride + m]
  *   pos_base : device int32[B]; token (b,m) sits at position pos_base[b] + pos_off + m

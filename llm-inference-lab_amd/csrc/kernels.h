@@ -243,4 +243,10 @@ constexpr int kForkMaxList = 64;
 int launch_kv_fork(uint16_t* k, uint16_t* v, int n_layers, int n_slots, int Hkv, int Lslot, int D, const int32_t* src,
                    const int32_t* dst, int n_groups, int fan, int n_pos, hipStream_t st);
 
+// ---- KV eviction (kv_evict.hip) ---------------------------------------------------------
+// Row `row` of a dense cache, in place: positions [keep + drop, n_pos) -> [keep, n_pos - drop), all layers / heads; V bit
+// for bit, K rotated by -drop with row `drop` of the fp32 tables rope_cos / rope_sin ([max_pos][D / 2]). drop % 8 == 0.
+int launch_kv_evict(uint16_t* k, uint16_t* v, const float* rope_cos, const float* rope_sin, int n_layers, int B, int Hkv, int Lmax, int D,
+                    int row, int keep, int drop, int n_pos, hipStream_t st);
+
 }  // namespace sd

@@ -360,6 +360,26 @@ extern "C" int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, con
                         1, n_pos, static_cast<hipStream_t>(stream));
 }
 
+// ---- KV eviction inside one cache row (csrc/kv_evict.hip): the arguments that need no model, then the model, then its geometry
+extern "C" int sd_model_kv_evict(sd_model* m, int row, int keep, int drop, int n_pos, void* stream) {
+  clear_error();
+  SD_REQUIRE(row >= 0, "kv_evict: row %d is negative", row);
+  SD_REQUIRE(keep >= 0, "kv_evict: keep=%d is negative", keep);
+  SD_REQUIRE(drop >= 1 && drop % 8 == 0, "kv_evict: drop=%d must be a positive multiple of 8", drop);
+  SD_REQUIRE(static_cast<int64_t>(keep) + drop <= n_pos, "kv_evict: keep=%d + drop=%d exceed n_pos=%d", keep, drop, n_pos);
+  SD_REQUIRE(m, "kv_evict: NULL model");
+  SD_REQUIRE(m->k_cache && m->x, "kv_evict: model not bound (sd_model_bind)");
+  SD_REQUIRE(!m->block_table, "kv_evict: this model is bound to a paged cache (eviction covers dense caches)");
+  const sd_model_config& c = m->cfg;
+  SD_REQUIRE(c.arch == SD_ARCH_LLAMA, "kv_evict: a GPT-2 model has learned positions in its hidden states: nothing to re-rotate");
+  SD_REQUIRE(row < m->B, "kv_evict: row %d outside the bound batch of %d", row, m->B);
+  SD_REQUIRE(drop < c.max_pos, "kv_evict: drop=%d is outside the model's %d rope positions", drop, c.max_pos);
+  SD_REQUIRE(n_pos <= m->Lmax, "kv_evict: n_pos=%d exceeds Lmax=%d", n_pos, m->Lmax);
+  if (n_pos == keep + drop) return 0;
+  return launch_kv_evict(m->k_cache, m->v_cache, c.rope_cos, c.rope_sin, c.n_layers, m->B, c.n_kv_heads, m->Lmax, c.head_dim, row, keep,
+                         drop, n_pos, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int sd_model_set_persist_tokens(sd_model* m, int max_tokens) {
   clear_error();
   SD_REQUIRE(m && m->x, "set_persist_tokens: NULL argument / model not bound");

@@ -119,6 +119,7 @@ SIGNATURES = {
     "sd_model_bind_paged": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size]),
     "sd_model_kv_fork": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p]),
     "sd_model_kv_copy_pages": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "sd_model_kv_evict": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "sd_model_forward": (
         _c_int,
         [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,

@@ -314,6 +314,16 @@ class HipModel:
                 dp = (ctypes.c_int32 * len(pairs))(*[p[1] for p in pairs])
                 _abi.check(self.lib.sd_model_kv_copy_pages(self.handle, sp, dp, len(pairs), n, st), "sd_model_kv_copy_pages")
 
+    def evict_row(self, row: int, keep: int, drop: int, n_pos: int, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """The rolling context window's device step (csrc/kv_evict.hip), asynchronously on `stream`: in cache row `row`, positions
+        [keep + drop, n_pos) become positions [keep, n_pos - drop) in every layer and KV head — V bit for bit, K rotated by
+        -drop positions with the model's own RoPE tables (one more bf16 rounding of the moved keys). The first `keep` positions,
+        positions >= n_pos - drop and the other rows keep their bits; the row's length afterwards is the caller's to lower by
+        `drop`. Dense Llama caches only, drop a positive multiple of 8 below max_pos: anything else raises before device work."""
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.sd_model_kv_evict(self.handle, int(row), int(keep), int(drop), int(n_pos), _stream(stream, self.device)),
+                       "sd_model_kv_evict")
+
     def kv_view(self):
         c = self.cfg
         if self.page_len is not None:

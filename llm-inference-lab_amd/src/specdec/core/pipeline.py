@@ -44,6 +44,7 @@ from ..utils.interfaces import LanguageModel
 from .acceptance import device_rule, session_rule
 from .draft_confidence import check_session, session_confidence
 from . import logprobs as lpmod
+from . import rolling
 from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
 PromptLike = Union[str, Sequence[int], torch.Tensor]
@@ -69,6 +70,10 @@ _DEFAULTS: Dict[str, Any] = {
     # share_prefix: a row is forked over a prefix it has in common with a row already in the cache from this many tokens on
     # (rows whose whole prompts are equal are always forked)
     "min_shared_prefix": 32,
+    # the rolling context window (core/rolling.py): None = a row lives within prompt + max_tokens cache positions; W = its cache keeps
+    # attention_sinks first positions and the most recent ones, never more than W, and generation length is no longer bound by the cache
+    "context_window": None,
+    "attention_sinks": 4,
 }
 
 
@@ -100,7 +105,7 @@ def expected_tokens_per_step(alpha: Sequence[float], k_max: int = 8) -> Dict[int
 
 class _Row:
     __slots__ = ("seq", "generated", "active", "proposed", "accepted", "draws", "steps", "strict_acc", "strict_prop", "k_trace", "counters",
-                 "n_prompt", "token_info")
+                 "n_prompt", "token_info", "evicted", "evictions", "rebuilds")
 
     def __init__(self, seq: List[int]):
         self.seq, self.generated, self.active = seq, [], True
@@ -110,6 +115,11 @@ class _Row:
         self.strict_acc = self.strict_prop = 0     # per-row adaptive K: what the row's controller is fed with
         self.k_trace: List[int] = []               # ... and the k that counted in each of its steps
         self.token_info: List[Any] = []            # logprobs: entry j is the TokenInfo of generated[j] (empty while the mode is off)
+        # context_window: positions evicted from the row's caches so far (its cache length is len(seq) - evicted), the rolls as
+        # (tokens generated before the roll, drop), and the tokens generated before each rebuild of a rolled row's caches (a resync)
+        self.evicted = 0
+        self.evictions: List[tuple] = []
+        self.rebuilds: List[int] = []
 
 
 class SpeculativePipeline:
@@ -255,13 +265,15 @@ class SpeculativePipeline:
         return cfg
 
     # ------------------------------------------------------------------ runtime pieces
-    def _runtime(self, batch: int, need_len: int, k: int, emit_mode: int, self_draft: bool = False, adaptive: bool = False):
+    def _runtime(self, batch: int, need_len: int, k: int, emit_mode: int, self_draft: bool = False, adaptive: bool = False,
+                 windowed: bool = False):
         """Engine instances (own KV caches over the shared weights) + the step loop object (`adaptive`: the loop whose
-        rows carry their own K, a different captured step from the fixed-K loop of the same shape)."""
-        key = (batch, emit_mode, self_draft)
+        rows carry their own K, a different captured step from the fixed-K loop of the same shape). windowed (context_window): the
+        caches are sized by need_len itself, the window and its slack, and kept apart from those sized by prompt + budget."""
+        key = (batch, emit_mode, self_draft, "window") if windowed else (batch, emit_mode, self_draft)
         rt = self._runtimes.get(key)
         if rt is None or rt["l_max"] < need_len:
-            l_max = (max(need_len, 256) + 63) // 64 * 64
+            l_max = ((need_len if windowed else max(need_len, 256)) + 63) // 64 * 64
             rt = {"l_max": l_max, "target": self.base_lm.new_engine(batch, l_max),
                   "draft": None if self_draft else self.draft_lm.new_engine(batch, l_max), "loops": {}}
             self._runtimes[key] = rt
@@ -362,8 +374,8 @@ class SpeculativePipeline:
 
     @staticmethod
     def _set_row(loop: HipSpecDec, b: int, row: _Row) -> None:
-        seq = row.seq
-        loop.set_row(b, len(seq), seq[-2] if len(seq) >= 2 else 0, seq[-1], row.active)
+        seq = row.seq       # (a rolled row sits at its cache length: what was evicted no longer counts)
+        loop.set_row(b, len(seq) - row.evicted, seq[-2] if len(seq) >= 2 else 0, seq[-1], row.active)
 
     # ------------------------------------------------------------------ host-side rules
     def _rules_batch(self, row: _Row, k: int, a: int, t: List[int], max_tokens: int, eos: Optional[int],
@@ -452,7 +464,7 @@ class SpeculativePipeline:
                       sampling: Union[None, Dict[str, Any], StepOptions] = None, step_limit: Optional[int] = None,
                       self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
                       draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
-                      **processors) -> "DecodeSession":
+                      context_window: Optional[int] = None, attention_sinks: Optional[int] = None, **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
@@ -462,7 +474,9 @@ class SpeculativePipeline:
         sampling_params: one SamplingParams per prompt (in place of `sampling` and of penalty arguments); only they are gated.
         draft_confidence / draft_min_k: the confidence-gated draft length (generate_batch), the bonus-token emit mode only.
         logprobs: per-token log-probs (True / 0: the chosen token's; 1..20: that many alternatives too), the bonus-token emit mode
-        only; every row's token_info then stays parallel to its generated tokens."""
+        only; every row's token_info then stays parallel to its generated tokens.
+        context_window / attention_sinks: the rolling context window (core/rolling.py), the bonus-token emit mode only: the caches
+        are sized by the window, not by max_tokens, and a row rolls whenever its next launches would not fit."""
         if sampling_params is not None and sampling is not None:
             raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
         session_rule(self, StepOptions(), emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (its refusals come first)
@@ -472,12 +486,13 @@ class SpeculativePipeline:
         options = session_rule(self, options, emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (a device acceptance rule)
         options = session_confidence(self, options, emit_mode, self_draft, draft_confidence, draft_min_k, HipSpecDec.EMIT_BONUS)
         options = lpmod.session_logprobs(self, options, emit_mode, self_draft, logprobs, HipSpecDec.EMIT_BONUS)
-        return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
+        window = rolling.session_window(self, context_window, attention_sinks, emit_mode, self_draft, share_prefix, HipSpecDec.EMIT_BONUS, prompts)
+        return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window)
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
-                options: Optional[StepOptions] = None, self_draft: bool = False, share_prefix: bool = False):
+                options: Optional[StepOptions] = None, self_draft: bool = False, share_prefix: bool = False, window=None):
         t_start = time.time()
-        sess = DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix)
+        sess = DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -674,6 +689,7 @@ class SpeculativePipeline:
         """Single-prompt speculative decoding (reference :893-1413): accepted tokens are the
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
+        rolling.refuse_single(self, kwargs)
         call = resolve(self, [prompt], max_tokens, temperature, do_sample, kwargs, grammar=kwargs.pop("grammar", None),
                        sampling_params=kwargs.pop("sampling_params", None), share_prefix=kwargs.get("share_prefix"), n=kwargs.get("n", 1),
                        single=True, draft_confidence=kwargs.pop("draft_confidence", None), draft_min_k=kwargs.pop("draft_min_k", None),
@@ -706,7 +722,8 @@ class SpeculativePipeline:
                        temperature: Optional[float] = None, do_sample: Optional[bool] = None,
                        share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None,
                        draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
-                       best_of: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
+                       best_of: Optional[int] = None, context_window: Optional[int] = None, attention_sinks: Optional[int] = None,
+                       **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -751,7 +768,19 @@ class SpeculativePipeline:
 
         best_of=m >= n (opt-in): every prompt decodes m rows (the `n` machinery: one shared prompt, a Philox stream per row) and
         the n with the highest cumulative_logprob come back, best first, ties to the lower row. Implies logprobs; needs a
-        sampling mode (greedy rows are all equal). batch_metrics carries best_of."""
+        sampling mode (greedy rows are all equal). batch_metrics carries best_of.
+
+        context_window=W / attention_sinks=S (opt-in; config keys of the same names, S defaults to 4; not in the reference): the rolling
+        context window. The caches are sized by W (plus the slack the launches in flight need), not by prompt + max_tokens, and
+        generation length is no longer bound by the cache or by the models' max_pos. A row's cache keeps its first S positions and
+        the most recent ones: when its next launches would not fit within W, the `drop` positions after the sinks are evicted in
+        both engines (csrc/kv_evict.hip: the survivors move down and their keys are re-rotated to their new positions), at the
+        session's repair point, and the row goes on. Results carry `evictions`, a list of (tokens generated before the roll, drop):
+        the output is the target's own greedy decoding over the rolled cache GIVEN that schedule, and the schedule depends on where
+        the step boundaries fall, hence on acceptance. batch_metrics carries evictions / evicted_positions. For the captured step
+        with a draft model and a fixed K, in every select mode, with processors, grammars, sampling_params, logprobs and
+        draft_confidence; refused with paged KV, GPT-2 models, the host loops, implementation='fake', medusa / eagle / self-draft,
+        adaptive K, share_prefix / n, generate(), and a prompt the window has no room for (prompts are not truncated)."""
         if not prompts:
             return []
         m_best = lpmod.check_best_of(best_of, n)
@@ -761,6 +790,7 @@ class SpeculativePipeline:
                        sampling_params=sampling_params, draft_confidence=draft_confidence, draft_min_k=draft_min_k, logprobs=logprobs)
         if m_best is not None:
             lpmod.check_best_of_mode(call.options)
+        window = rolling.call_window(self, context_window, attention_sinks, call)
         if call.route == "fake":
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
         prompts, max_tokens = call.prompts, call.max_tokens
@@ -770,7 +800,7 @@ class SpeculativePipeline:
             rows, st = self._decode_host_policy(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
             rows, st = self._decode(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, options=call.options,
-                                    self_draft=call.self_draft, share_prefix=call.share_prefix)
+                                    self_draft=call.self_draft, share_prefix=call.share_prefix, **({} if window is None else {"window": window}))
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -785,6 +815,7 @@ class SpeculativePipeline:
             # forwards of the consumed steps that no row the host took tokens from needed
             "mean_k": tot_prop / max(sum(r.steps for r in rows), 1), "draft_forwards_skipped": st.get("draft_forwards_skipped", 0),
             **{key: st.get(key, 0) for key in ("prefilled_rows", "forked_rows", "shared_positions")},
+            **({} if window is None else {key: st.get(key, 0) for key in ("evictions", "evicted_positions")}),
         }
         out = []
         for i, (p, r) in enumerate(zip(prompts, rows)):
@@ -803,6 +834,7 @@ class SpeculativePipeline:
                 "kv_appended_tokens": n, "kv_append_time_ms": 0.0, "sequence": list(r.seq),
                 **({"k_trace": list(r.k_trace)} if r.k_trace else {}),     # per-row adaptive K: the k of each of the row's steps
                 **lpmod.result_fields(r, call.options.logprobs),
+                **({} if window is None else {"evictions": list(r.evictions), "window_rebuilds": list(r.rebuilds)}),
             })
         if m_best is not None:
             batch_metrics["best_of"] = m_best
@@ -812,7 +844,8 @@ class SpeculativePipeline:
     def generate_many(self, prompts: Sequence[PromptLike], max_tokens: Optional[int] = None, batch_size: int = 8,
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
                       grammar=None, sampling_params=None, draft_confidence: Optional[float] = None,
-                      draft_min_k: Optional[int] = None, logprobs=None, **kwargs) -> List[Dict[str, Any]]:
+                      draft_min_k: Optional[int] = None, logprobs=None, context_window: Optional[int] = None,
+                      attention_sinks: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -826,7 +859,9 @@ class SpeculativePipeline:
         its Philox stream (its index among the call's rows) with it — the slot's table entry, stream id and draw counter are
         rewritten on the loop's stream and the captured step is kept.
         draft_confidence / draft_min_k: as generate_batch; the device keeps no per-row state for it, so an admission sets nothing.
-        logprobs: as generate_batch (best_of is a generate_batch argument and is refused here)."""
+        logprobs: as generate_batch (best_of is a generate_batch argument and is refused here).
+        context_window / attention_sinks: as generate_batch; a prompt admitted to a slot starts with nothing evicted, and must fit the
+        window as the first ones must."""
         if not prompts:
             return []
         lpmod.refuse_best_of(kwargs)
@@ -834,13 +869,14 @@ class SpeculativePipeline:
                        sampling_params=sampling_params, policy_routes=False, draft_confidence=draft_confidence, draft_min_k=draft_min_k,
                        logprobs=logprobs)
         prompts, ids, max_tokens, options = call.prompts, call.ids, call.max_tokens, call.options
+        window = rolling.call_window(self, context_window, attention_sinks, call)
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
         sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, options.rows(first), max_tokens,
-                             share_prefix=call.share_prefix)
+                             share_prefix=call.share_prefix, **({} if window is None else {"window": window}))
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -874,7 +910,8 @@ class SpeculativePipeline:
                         "acceptance_rate": r.accepted / max(r.proposed, 1), "proposed": r.proposed, "accepted": r.accepted,
                         "steps": r.steps, "sequence": list(r.seq), "kv_append_enabled": True, "kv_append_backend": "hip",
                         **({"k_trace": list(r.k_trace)} if r.k_trace else {}), **lpmod.result_fields(r, options.logprobs),
-                        "batch_metrics": {"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
+                        **({} if window is None else {"evictions": list(r.evictions), "window_rebuilds": list(r.rebuilds)}),
+                        "batch_metrics": {**({} if window is None else {key: sess.stats[key] for key in ("evictions", "evicted_positions")}),"total_steps": sess.stats["steps"], "device_steps": sess.step, "resyncs": sess.stats["resyncs"],
                                           "void_row_steps": sess.stats["void_row_steps"], "k": sess.k,
                                           "mean_k": sess.stats["proposed"] / max(sum(x.steps for x, _ in done.values()), 1),
                                           "draft_forwards_skipped": sess.stats.get("draft_forwards_skipped", 0),
@@ -967,7 +1004,8 @@ class DecodeSession:
     prefilled (SpeculativePipeline._absorb_row); stats counts prefilled_rows / forked_rows / shared_positions."""
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
-                 options: Optional[StepOptions] = None, step_limit: Optional[int] = None, self_draft: bool = False, share_prefix: bool = False):
+                 options: Optional[StepOptions] = None, step_limit: Optional[int] = None, self_draft: bool = False, share_prefix: bool = False,
+                 window: Optional[rolling.Window] = None):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
         self.options = o = options if options is not None else StepOptions()      # what the step does: greedy, sampled bonus token, spec
         other_step = self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))     # no draft model, or no fixed K
@@ -1014,10 +1052,19 @@ class DecodeSession:
         self._conf = check_session(o, other_step, emit_mode == HipSpecDec.EMIT_BONUS, self.k)
         # per-token log-probs: the step describes every emitted token and the record carries it (None: off, else top_n)
         self._logprobs = lpmod.check_session(o, other_step, emit_mode == HipSpecDec.EMIT_BONUS)
-        self.rt, self.loop = pipe._runtime(len(self.rows), self.need, self.k, emit_mode, self.self_draft, adaptive=self.per_row)
-        # positions a row may use: the cache rows and both models' position tables
+        # the rolling context window (None: off): the caches are sized by the window and its slack, not by prompt + max_tokens
+        self.window = rolling.check_session(window, other_step, emit_mode == HipSpecDec.EMIT_BONUS, share_prefix, self.k)
+        if self.window is not None:
+            self.need = self.window.l_max
+        self.rt, self.loop = pipe._runtime(len(self.rows), self.need, self.k, emit_mode, self.self_draft, adaptive=self.per_row,
+                                           **({} if self.window is None else {"windowed": True}))
+        # positions a row may use: the cache rows and both models' position tables (a windowed row's positions are its cache's:
+        # they stay below the window, which is within both tables, and nothing here stops it)
         self.pos_limit = min(self.rt["l_max"], pipe.base_lm.config.max_pos,
                              pipe.draft_lm.config.max_pos if not self_draft else pipe.base_lm.config.max_pos)
+        if self.window is not None:
+            rolling.refuse_paged([e for e in (self.rt["target"], self.rt["draft"]) if e is not None])
+            assert self.rt["l_max"] >= self.window.l_max and all(self.window.fits(len(r.seq)) for r in self.rows)
         for r in self.rows:
             if len(r.seq) + 2 * self.k + 4 > self.pos_limit:
                 raise ValueError(f"prompt of {len(r.seq)} tokens leaves no room for a step within {self.pos_limit} positions")
@@ -1028,6 +1075,8 @@ class DecodeSession:
         self._fresh: set = set()                # rows whose slot was handed to a new sequence (admit)
         self.stats = {"steps": 0, "resyncs": 0, "proposed": 0, "accepted": 0, "device_ms": 0.0, "void_row_steps": 0,
                       "prefilled_rows": 0, "forked_rows": 0, "shared_positions": 0}
+        if self.window is not None:
+            self.stats.update(evictions=0, evicted_positions=0)
         # share_prefix: per row, the tokens whose KV both caches hold at positions [0, len) — None: not to be relied on
         self._held: Optional[List[Optional[List[int]]]] = [None] * len(self.rows) if share_prefix else None
         pipe._prefill(self.rt, self.rows, self._held, self.stats)
@@ -1067,8 +1116,8 @@ class DecodeSession:
         self._hint()
 
     def _reach(self) -> int:
-        """Positions the steps in flight plus one more can have reached on the longest row."""
-        return max(len(r.seq) for r in self.rows) + (len(self._queue) + 2) * (self.k + 1) + 2
+        """Cache positions the steps in flight plus one more can have reached on the longest row."""
+        return max(len(r.seq) - r.evicted for r in self.rows) + (len(self._queue) + 2) * (self.k + 1) + 2
 
     def _hint(self) -> tuple:
         reach = self._reach()
@@ -1212,9 +1261,15 @@ class DecodeSession:
                 else:
                     for e in self._engines:
                         e.unshare(b)               # (pages shared with other rows are never written: the rebuild gets fresh ones)
-                    pipe._prefill_row(rt, b, r.seq)
+                    if r.evicted:                  # a rolled row is rebuilt from the tokens its cache still holds, at their cache positions
+                        pipe._prefill_row(rt, b, rolling.kept_tokens(r.seq, self.window.sinks, r.evicted))
+                        r.rebuilds.append(len(r.seq) - r.n_prompt)
+                    else:
+                        pipe._prefill_row(rt, b, r.seq)
                     self.stats["prefilled_rows"] += 1 if fresh else 0
                 loop.join_current_stream()
+            if self.window is not None and r.active:
+                self._roll(b, r)                   # (whatever flagged the row: its next launches must fit the window)
             pipe._set_row(loop, b, r)              # (re)position, or freeze a finished row
             if r.active:
                 self._set_counts(b)                # (void steps counted tokens the row never kept: back to the in-order view)
@@ -1225,6 +1280,29 @@ class DecodeSession:
         if self._flagged and ((self._spec and loop.spec_sampling) or (self._accept and self._sampled and loop.sampling)):
             loop.set_draw_counts([r.draws for r in self.rows])   # void steps drew for the flagged rows: back to the in-order view
         self._flagged.clear()
+
+    def _roll(self, b: int, r: _Row) -> None:
+        """The rolling context window, at the repair point (idle stream): when row b's next launches would not fit the window, the
+        `drop` positions after the sinks leave both caches — evict_row on the loop's stream moves the survivors down and re-rotates
+        their keys — and the row's cache length drops by as much. The caches hold the positions of seq[:-1] (the draft's `prev`
+        hole among them: it moves with the rest and the next forward 0 refills it at its new position); what void steps wrote
+        above them is stale and is overwritten. Token-counting state (processor counts, grammar state, log-prob payloads, draw
+        counters) counts tokens, not positions: nothing to do."""
+        w = self.window
+        length = len(r.seq) - r.evicted
+        drop = w.roll(length)
+        if drop is None:
+            return
+        assert w.sinks + drop <= length - 1 <= w.size, (w, length)
+        for e in self._engines:
+            e.evict_row(b, w.sinks, drop, length - 1, stream=self.loop.stream_t)
+        r.evicted += drop
+        r.evictions.append((len(r.seq) - r.n_prompt, drop))
+        self.stats["evictions"] += 1
+        self.stats["evicted_positions"] += drop
+        if self._held is not None:
+            self._held[b] = None                   # a rolled row is no longer a source to fork from
+        assert w.roll(len(r.seq) - r.evicted) is None
 
     def _recover(self, err: Exception) -> None:
         """A persistent launch of one of the models gave up (its bounded waits expired: the CUs were shared with another
@@ -1267,6 +1345,10 @@ class DecodeSession:
                 self.stats["path_switches"] = self.stats.get("path_switches", 0) + 1
             self.loop.captured_paths = paths
         idx = self.loop.launches
+        if self.window is not None:
+            # the device advances every row in every launched step, void or not: what this launch and the ones in flight can address
+            # on the longest row stays inside the cache rows (the window's slack: rolling.Window.room)
+            assert self._reach() <= self.rt["l_max"], (self._reach(), self.rt["l_max"], self.window)
         if self._engines[0].page_len is not None:
             # paged KV: the device advances by itself, so every row gets the pages of all the steps in flight plus this one
             # before it is launched (table writes go to the loop's stream, ahead of the step). Frozen rows keep writing their
@@ -1293,8 +1375,8 @@ class DecodeSession:
                 continue
             if self.step_limit is not None and r.steps + ahead + 1 > self.step_limit:
                 continue
-            if len(r.seq) + (ahead + 2) * self.k + 6 > self.pos_limit:
-                continue
+            if self.window is None and len(r.seq) + (ahead + 2) * self.k + 6 > self.pos_limit:
+                continue                   # (a windowed row is flagged "roll" before it gets there, and no flagged row is launched ahead)
             return True
         return False
 
@@ -1392,13 +1474,15 @@ class DecodeSession:
             stats["accepted"] += r.accepted - acc0
             if r.active and self.step_limit is not None and r.steps >= self.step_limit:
                 r.active = False                # the reference's loop bound counts steps (pipeline.py:1984, :984)
-            if r.active and len(r.seq) + 2 * self.k + 4 > self.pos_limit:
+            if self.window is None and r.active and len(r.seq) + 2 * self.k + 4 > self.pos_limit:
                 r.active = False                # out of cache rows / model positions
             if not r.active:
                 self._flagged[b] = "freeze"     # stop the row on the device
             elif r.seq != assumed:
                 stats["resyncs"] += 1
                 self._flagged[b] = "resync"
+            elif self.window is not None and self.window.roll(len(r.seq) - r.evicted) is not None:
+                self._flagged[b] = "roll"       # its next launches would not fit the window: evicted at the repair point (_roll)
             if b in self._flagged:
                 for _, vs in self._queue:      # every step already launched is void for this row
                     vs.add(b)
@@ -1418,7 +1502,11 @@ class DecodeSession:
             raise ValueError(f"row {b} is still decoding")
         if not prompt:
             raise ValueError("empty prompt")
-        if len(prompt) + self.max_tokens + 2 * self.k + 8 > self.rt["l_max"] or len(prompt) + 2 * self.k + 4 > self.pos_limit:
+        if self.window is not None:         # the cache is sized by the window: the prompt must start without a roll, the budget does not count
+            fits = self.window.fits(len(prompt))
+        else:
+            fits = not (len(prompt) + self.max_tokens + 2 * self.k + 8 > self.rt["l_max"] or len(prompt) + 2 * self.k + 4 > self.pos_limit)
+        if not fits:
             raise ValueError(f"prompt of {len(prompt)} tokens does not fit this session (l_max {self.rt['l_max']}, positions {self.pos_limit})")
         if grammar_start >= 0 and self.grammar is None:
             raise ValueError("admit: the session was started without a grammar")

@@ -108,6 +108,10 @@ _GATE = {
     "logprobs": ("logprobs are computed inside the captured device step: {what} is not supported with them",
                  "logprobs need the draft-model mode (draft_mode='vanilla'): medusa / eagle / self-draft steps store no verify rows",
                  "logprobs keep a fixed K (controller='fixed'): adaptive K is not supported"),
+    "context_window": ("context_window rolls the caches of the captured device step: {what} is not supported with it",
+                       "context_window needs the draft-model mode (draft_mode='vanilla'): medusa / eagle / self-draft steps keep state that "
+                       "a roll does not move",
+                       "context_window keeps a fixed K (controller='fixed'): adaptive K is not supported"),
 }
 
 

@@ -88,6 +88,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--best-of", type=int, metavar="M",
                     help="decode M >= --n rows of the prompt and return the --n with the highest cumulative log-prob, best first "
                          "(implies --logprobs 0; needs a sampling mode: --spec-sampling or --sampling-params)")
+    ap.add_argument("--context-window", type=int, metavar="W",
+                    help="rolling context window: a row's cache keeps --attention-sinks first positions and the most recent ones, never "
+                         "more than W; the caches are sized by W, not by --max-tokens, and the middle is evicted (keys re-rotated on the "
+                         "device) whenever the next steps would not fit; adds evictions; decodes through generate_batch")
+    ap.add_argument("--attention-sinks", type=int, metavar="S", help="--context-window: positions kept at the start of the cache (default 4)")
     ap.add_argument("--eval-perplexity", action="store_true",
                     help="add perplexity / perplexity_loss of the generated tokens under the target model (scored on the device)")
     ap.add_argument("--eval-agreement", action="store_true",
@@ -194,6 +199,9 @@ def main(argv=None) -> int:
     if args.draft_min_k is not None and args.draft_confidence is None:
         logging.error("--draft-min-k belongs to --draft-confidence")
         return 1
+    if args.attention_sinks is not None and args.context_window is None:
+        logging.error("--attention-sinks belongs to --context-window")
+        return 1
     try:
         pipe = SpeculativePipeline(config_path=args.config, base_model=args.base_model, draft_model=args.draft_model,
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,
@@ -204,7 +212,9 @@ def main(argv=None) -> int:
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         conf = args.draft_confidence is not None
         lp = args.logprobs is not None or args.best_of is not None
-        batch = lp or conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None or pp.get("backend") == "device"
+        roll = args.context_window is not None
+        batch = (roll or lp or conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None
+                 or pp.get("backend") == "device")
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:
@@ -215,6 +225,8 @@ def main(argv=None) -> int:
             proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
         if lp:         # per-token log-probs inside the captured step; best_of ranks the rows by their sum
             proc.update(logprobs=args.logprobs, best_of=args.best_of)
+        if roll:       # the rolling context window: the caches are sized by it, rows roll at the session's repair point
+            proc.update(context_window=args.context_window, attention_sinks=args.attention_sinks)
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows
             rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
             r = {**pipe._sysinfo(), **rs[0], "latency_ms": rs[0]["total_time_ms"],
@@ -237,6 +249,8 @@ def main(argv=None) -> int:
     if args.logprobs is not None or args.best_of is not None:
         keys += ("generated_tokens", "logprobs", "token_ranks", "cumulative_logprob", "cumulative_logprobs")
         keys += ("top_logprobs",) if (args.logprobs or 0) > 0 else ()
+    if args.context_window is not None:
+        keys += ("evictions",)
     if args.eval_perplexity:
         keys += ("perplexity", "perplexity_loss")
     if args.eval_agreement:

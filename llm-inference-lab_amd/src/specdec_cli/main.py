@@ -96,7 +96,12 @@ def cmd_run(args: argparse.Namespace) -> int:
         proc.update(logprobs=args.logprobs, best_of=args.best_of)
         if args.do_sample:
             proc.update(do_sample=True, temperature=args.temperature, seed=args.seed)
-    if lp or conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    roll = args.context_window is not None
+    if args.attention_sinks is not None and not roll:
+        raise SystemExit("--attention-sinks belongs to --context-window")
+    if roll:     # the rolling context window (a generate_batch mode): caches sized by the window, rows roll at the repair point
+        proc.update(context_window=args.context_window, attention_sinks=args.attention_sinks)
+    if roll or lp or conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
@@ -106,6 +111,8 @@ def cmd_run(args: argparse.Namespace) -> int:
 
             fields = ("generated_tokens", "logprobs", "token_ranks", "top_logprobs", "cumulative_logprob")
             print("Logprobs: " + json.dumps([{k: x[k] for k in fields if k in x} for x in rs]))
+        if roll:
+            print(f"Evictions (tokens generated before the roll, positions dropped): {[list(e) for e in rs[0]['evictions']]}")
     else:
         res = pipe.generate(prompt=args.prompt, max_tokens=args.max_tokens, temperature=args.temperature, do_sample=args.do_sample, **proc)
     kinfo = get_kernel_info()
@@ -159,6 +166,10 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--best-of", type=int, metavar="M",
                     help="decode M >= --n rows and keep the --n with the highest cumulative log-prob, best first (implies --logprobs 0; "
                          "needs --do-sample, --spec-sampling or --sampling-params)")
+    pr.add_argument("--context-window", type=int, metavar="W",
+                    help="rolling context window: a row's cache keeps --attention-sinks first positions and the most recent ones, never "
+                         "more than W; the caches are sized by W, not by --max-tokens (generate_batch)")
+    pr.add_argument("--attention-sinks", type=int, metavar="S", help="--context-window: positions kept at the start of the cache (default 4)")
     pr.add_argument("--repetition-penalty", type=float, help="repetition penalty (> 0) over prompt + generated tokens, inside the captured step")
     pr.add_argument("--presence-penalty", type=float, help="subtracted from the logit of every token generated so far")
     pr.add_argument("--frequency-penalty", type=float, help="subtracted from the logit of a token once per time it was generated")
