@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdlib.h>
+#include <string.h>
 
 #include <new>
 #include <vector>
@@ -570,6 +571,10 @@ extern "C" int sd_specdec_create(sd_model* draft, sd_model* target, int B, int K
     sd_specdec_destroy(s);
     SD_REQUIRE(false, "specdec_create: pinned memory / event creation failed");
   }
+  // a loop that is synchronised before its first step hands out slot 0 as it is: pinned memory comes back from the allocator
+  // with what its last owner left in it (another loop's record, whose words would be read as this loop's health word)
+  memset(s->host_record, 0, sizeof(int32_t) * 2 * B * s->rec);
+  memset(s->host_stage, 0, sizeof(int32_t) * (B * kStageInts + 4));
   *out = s;
   return 0;
 }
@@ -929,6 +934,7 @@ extern "C" int sd_specdec_set_logprobs(sd_specdec* s, int enable, int top_n, voi
   if (!s->host_logprobs) {
     const size_t words = static_cast<size_t>(2) * s->B * (s->K + 1) * logprob_words(V, 20);
     SD_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s->host_logprobs), sizeof(int32_t) * words, hipHostMallocDefault));
+    memset(s->host_logprobs, 0, sizeof(int32_t) * words);   // (as host_record: slot 0 can be read before the first step)
   }
   drop_graph(s);   // the captured step holds the launches without the stage, or another top_n
   s->logprobs = 1;

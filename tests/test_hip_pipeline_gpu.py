@@ -621,3 +621,21 @@ def test_rejection_sampling_policy_in_the_pipeline():
                                controller="fixed", controller_params={"k": k}, seed=1234).generate_batch([prompt], max_tokens=mt, do_sample=True)[0]
     steps = same["batch_metrics"]["total_steps"]
     assert same["accepted"] == (k + 1) * steps or 2 in same["generated_tokens"]
+
+
+def test_record_of_a_loop_before_its_first_step_is_empty():
+    """A loop that is synchronised before its first step (every session does: DecodeSession._configure_sampling) returns slot 0
+    of its pinned record block untouched. The block must come zeroed from sd_specdec_create, whatever its last owner left in
+    the pages: here an earlier loop of the same size whose record was filled with words that read as a health word."""
+    from specdec_hip.engine import HipModel, HipSpecDec
+
+    drf, tgt = tiny_pair(flip_fraction=0.25)
+    t, d = HipModel(tgt.to("cuda"), batch=2, l_max=128), HipModel(drf.to("cuda"), batch=2, l_max=128)
+    for _ in range(3):
+        loop = HipSpecDec(d, t, 2, 4, HipSpecDec.EMIT_BONUS)
+        assert loop.launches == 0
+        assert not loop._record.any()
+        rec = loop.sync()                       # raises EngineGaveUp on a non-zero health word
+        assert rec.engine_status == 0 and not rec.n_new.any() and not rec.new_tokens.any()
+        loop._record[...] = 0x230               # what the next owner of the pages finds
+        loop.close()
