@@ -369,10 +369,22 @@ int sd_model_pass_tokens(const sd_model* m);
 
 /* Scratch the forward needs (activations of one pass + argmax partials). */
 size_t sd_model_workspace_bytes(const sd_model* m);
-/* Bytes of ONE of the two cache tensors, bf16:
+/* Bytes of ONE of the two cache tensors, bf16 (an fp8-KV model, below: one byte per element, the same layouts):
  *   K: [n_layers][B][Hkv][Lmax][D]      V: [n_layers][B][Hkv][D][Lmax] (transposed)
- * Lmax must be a multiple of 8. */
+ * Lmax must be a multiple of 8 (fp8 KV: of 16). */
 size_t sd_model_kv_bytes(const sd_model* m, int B, int Lmax);
+/* The element type of the KV cache, set between sd_model_create and sd_model_bind: SD_BF16 (the default) or SD_FP8_E4M3 with
+ * the scales of K and V (positive and finite; 1 for SD_BF16). A stored element is OCP e4m3, round to nearest even, of
+ * clamp(x / scale, -448, 448), where x is the bf16-rounded value the bf16 cache would hold: the clamp is explicit, in fp32,
+ * before the convert, and NaN stays NaN. The attention kernel widens e4m3 to bf16 exactly, folds k_scale into the softmax
+ * scale and v_scale into the final 1 / sum, both in fp32 (csrc/attention_kv8.hip): it computes what the bf16 kernel computes
+ * over the dequantised cache. An fp8-KV model binds dense caches with Lmax % 16 == 0 and head_dim 64 or 128, runs every pass
+ * on the launch path (the persistent forward is ineligible at bind: sd_model_persist_active reports 0, sd_model_persist_tokens
+ * 0) and its QKV launches of <= 9 tokens take the generic GEMV kernel. Refused for it, with a return code and sd_last_error
+ * before any device work: this call after a bind, sd_model_bind_paged, sd_model_kv_fork, sd_model_kv_copy_pages and
+ * sd_model_kv_evict (re-rotating an e4m3 key is lossy). Not built yet: paged fp8 KV, fork / evict on fp8 caches, the
+ * persistent forward over an fp8 cache, per-head or per-token scales. sd_model_config is unchanged. */
+int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, float v_scale);
 /* Attach caller-owned KV caches and workspace. */
 int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, int Lmax,
                   void* workspace, size_t workspace_bytes);

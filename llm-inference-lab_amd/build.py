@@ -66,6 +66,8 @@ FILE_FLAGS = {
     "logit_proc.hip": ["-O3", "-ffp-contract=off"],
     # csrc/grammar.hip extends that transform (its mask line sits in logit_proc.hip's kernel): built the same way
     "grammar.hip": ["-O3", "-ffp-contract=off"],
+    # csrc/attention_kv8.hip: no packed fp32 VALU operations (v_pk_mul_f32 and kin) in the e4m3 attention kernels
+    "attention_kv8.hip": ["-O3", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -26,6 +26,9 @@
 //   O[q][d] += P[q][key] . V[key][d]       D/16 MFMAs, B = V^T rows (16 B per lane)
 // All K and V loads of a block are issued before any arithmetic: one memory round
 // trip per block, and at decode lengths (<= 128 keys per wave) one per kernel.
+//
+// An e4m3 cache (sd_model_set_kv_dtype) is read by instantiations of the same tile with a key loop of its own over 64-key
+// blocks: csrc/attention_kv8.hip. The plan, the masking, the wave merge and the split-KV hand-over are shared.
 
 #include <stdlib.h>
 
@@ -104,12 +107,15 @@ int launch_attention(const AttnArgs& a_in, hipStream_t st) {
                               a.split_ws && a.split_cnt, a.split_slots, pl))
     return rc;
   const int D = a.head_dim;
+  SD_REQUIRE(!a.kv8 || (!a.block_table && (D == 64 || D == 128) && a.l_max % 16 == 0),
+             "attention: an e4m3 KV cache is dense, of head_dim 64 or 128 (got %d), with l_max %% 16 == 0 (got %d)", D, a.l_max);
   // 4 waves per workgroup. 8 and 16 were measured and lose at every context length: the LDS merge grows with the wave
   // count and a 16-wave workgroup holds a CU's LDS alone (3B + 1B, K=4: 8 K context 6.8 ms/step with 4 waves, 9.3 with
   // 16; short contexts equal within noise).
   const int waves = 4;
   a.n_split = pl.n_split;
   const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);
+  if (a.kv8) return launch_attention_kv8(a, grid, st);   // the e4m3 instantiations: csrc/attention_kv8.hip
   switch (D) {
     case 32: launch_attention_d<32>(a, waves, grid, st); break;
     case 64: launch_attention_d<64>(a, waves, grid, st); break;

@@ -15,6 +15,12 @@ struct sd_model {
   // bound storage
   uint16_t* k_cache = nullptr;
   uint16_t* v_cache = nullptr;
+  // sd_model_set_kv_dtype: the caches hold OCP e4m3 bytes, element x stored as e4m3(clamp(x / kv_scale, +-448)) (0: K, 1: V)
+  int kv8 = 0;
+  float kv_scale[2] = {1.0f, 1.0f};
+  uint16_t* kv_at(uint16_t* cache, size_t elems) const {   // element `elems` of a cache (bf16: 2 bytes, e4m3: 1)
+    return kv8 ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(cache) + elems) : cache + elems;
+  }
   int B = 0, Lmax = 0;
   // paged KV (sd_model_bind_paged): k_cache / v_cache are page pools of n_pages pages per layer, Lmax = max_pages * page_len
   const int32_t* block_table = nullptr;   // device [B][max_pages], caller-owned and caller-maintained

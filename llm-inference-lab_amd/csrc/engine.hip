@@ -76,6 +76,9 @@ void call_args(GemvArgs& g, const sd_model* m, int T, int M, bool gated, const i
   g.l_max = m->Lmax;
   g.block_table = bt;
   g.page_shift = m->page_shift;
+  g.kv8 = m->kv8;
+  g.kv_rscale[0] = 1.0f / m->kv_scale[0];
+  g.kv_rscale[1] = 1.0f / m->kv_scale[1];
 }
 
 // one pass of forward_pass: the caller's arrays moved to the pass's first row
@@ -162,8 +165,8 @@ static int launch_pass(sd_model* m, const Pass& p, hipStream_t st) {
     }
   };
   for (int l = 0; l < c.n_layers; ++l) {
-    uint16_t* kc = m->k_cache + l * layer_kv + row_kv;
-    uint16_t* vc = m->v_cache + l * layer_kv + row_kv;
+    uint16_t* kc = m->kv_at(m->k_cache, l * layer_kv + row_kv);
+    uint16_t* vc = m->kv_at(m->v_cache, l * layer_kv + row_kv);
     auto layer_args = [&](int which) {
       GemvArgs g = matrix_args(m, 4 * l + which);
       call_args(g, m, T, p.Mc, true, p.pos_base, p.pos_off, bt);
@@ -195,6 +198,7 @@ static int launch_pass(sd_model* m, const Pass& p, hipStream_t st) {
     at.head_dim = D;
     at.l_max = m->Lmax;
     at.scale = 1.0f / sqrtf(static_cast<float>(D));
+    if (m->kv8) { at.kv8 = 1; at.scale *= m->kv_scale[0]; at.v_scale = m->kv_scale[1]; }
     at.split_ws = m->attn_ws;
     at.split_cnt = m->attn_cnt;
     at.split_slots = kAttnSplitSlots;
@@ -296,6 +300,9 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
   pm.page_shift = m->page_shift;
   pm.max_pages = m->max_pages;
   pm.n_pages = m->n_pages;
+  pm.kv8 = m->kv8;
+  pm.kv_scale[0] = m->kv_scale[0];
+  pm.kv_scale[1] = m->kv_scale[1];
   if (backend == SD_PREFILL_NATIVE) {
     if (!m->native_plan.buf)
       if (int rc = native_plan_build(c, m->native_plan)) return rc;

@@ -603,7 +603,8 @@ static int gemv_tt(int T) { return T <= 1 ? 1 : T <= 2 ? 2 : T <= 3 ? 3 : T <= 5
 // ------------------------------------------------------------------------------
 // fixed-geometry instances: the (epilogue, K slices, pairs per tile, prologue) classes of the bf16 Llama layer matrices at
 // 1B / 3B / 8B dimensions, each at the five token bounds and both batch depths. Everything else — the lm_head (multi-round),
-// fp8, MASK shapes (8B down: K = 14336), GPT-2, gathered rows, biases, batched heads — runs the generic kernel. Every class has
+// fp8, MASK shapes (8B down: K = 14336), GPT-2, gathered rows, biases, batched heads, the QKV launches of an fp8-KV model (the e4m3
+// branch of the KV append lives in the generic epilogue only; sd_gemv_variant names what a bf16-KV model runs) — runs the generic kernel. Every class has
 // a W12 twin at token bound 5 (kW12FixedTT), taken when the matrix streams its W12 copy.
 // ------------------------------------------------------------------------------
 #define SD_GEMV_FIXED_TABLE(X)                                                          \
@@ -796,7 +797,7 @@ int launch_gemv(const GemvArgs& a_in, int epi, hipStream_t st) {
   SD_REQUIRE(!a.w8 || (a.packed && a.w_scale), "gemv: fp8 weights need the packed layout and row scales");
   // one workgroup (16 waves) per CU with an equal, contiguous share of the row pairs, cut into
   // a power-of-two count of <= 8-pair tiles; the 16 waves take (tile, K-slice) units
-  const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes, !a.x_row && !a.batch_bytes,
+  const GemvChoice c = gemv_choose(a.T, a.n_pairs, a.K, a.w8 != 0, a.prologue, epi, a.packed && !a.x_row && !a.bias && !a.batch_bytes && !(a.kv8 && epi == EPI_QKV_ROPE), !a.x_row && !a.batch_bytes,
                                    (a.w12_main && a.w12_table && a.packed && !a.batch_bytes) ? (a.w12_form == W12_SPLIT ? W12_SPLIT : W12_CODES) : W12_NONE);
   if (int rc = gemv_choice_refused(c, a.T, a.K)) return rc;
   if (c.route == GEMV_SKINNY) return launch_gemm_skinny(a_in, epi, st);

@@ -124,6 +124,8 @@ __device__ __forceinline__ void pin_gemv_args(const GemvArgs& a) {
     SD_PIN("s"(static_cast<int>(a.head_dim)), "s"(static_cast<int>(a.n_q_heads)), "s"(static_cast<int>(a.n_kv_heads)), "s"(a.pos_base), "s"(a.pos_off), "s"(a.rope_cos),
            "s"(a.rope_sin), "s"(a.max_pos), "s"(a.k_cache), "s"(a.v_cache), "s"(a.l_max), "s"(static_cast<int>(a.half_shift)),
            "s"(a.block_table), "s"(static_cast<int>(a.page_shift)));   // (left out, the epilogue waited for a scalar load of its own: 0.5 % of the step)
+  // (a.kv8 is a bit of page_shift's dword, which is handed over above; kv_rscale is left to the e4m3 branch of the epilogue, which
+  // alone reads it: listed here, every bf16-KV launch would fetch a further line of the argument block)
   if constexpr (EPI == EPI_ARGMAX) SD_PIN("s"(static_cast<int>(a.out_dtype)), "s"(a.part_val), "s"(a.part_idx), "s"(a.batch_bytes));
 }
 
@@ -144,13 +146,25 @@ __device__ __forceinline__ void pair_rows(const GemvArgs& a, int p, int& r0, int
   }
 }
 
+// One element of an e4m3 KV cache (sd_model_set_kv_dtype): the bf16 bits the bf16 cache would hold, times 1 / scale, clamped to
+// +-448 in fp32 (comparisons: NaN stays NaN), converted to OCP e4m3 with round to nearest even. The product is one v_mul_f32
+// spelled out: left to the compiler, the two elements of a lane are fused into a packed fp32 multiply.
+__device__ __forceinline__ uint8_t kv_e4m3(uint16_t bits, float rscale) {
+  float x;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(x) : "v"(bf16_bits_to_float(bits)), "v"(rscale));
+  x = (x > 448.f) ? 448.f : x;
+  x = (x < -448.f) ? -448.f : x;
+  return static_cast<uint8_t>(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xffu);
+}
+
 // ------------------------------------------------------------------------------
 // epilogues: one lane finishes token t of pair p (y0 = row r0, y1 = row r1)
 // ------------------------------------------------------------------------------
 //   COH (EPI_RESID only): the new residual row is stored with an agent-scope relaxed atomic store (write-through to
 //   memory), for a consumer on another XCD inside the same launch.
 //   FIXED: called by a fixed-geometry instance of gemv.hip, whose outputs must equal the generic kernel's bit for bit: a.bias is
-//   known to be null, and the RoPE rotation has its roundings spelled out (see there).
+//   known to be null, and the RoPE rotation has its roundings spelled out (see there). The fixed instances do not carry the e4m3
+//   branch of the KV append: launch_gemv does not select them for an fp8-KV model.
 template <int EPI, bool COH = false, bool FIXED = false>
 __device__ __forceinline__ void epilogue(const GemvArgs& a, int p, int r0, int r1, int t, float y0,
                                          float y1, float& best_v, int& best_i, bool have_old = false,
@@ -202,6 +216,22 @@ __device__ __forceinline__ void epilogue(const GemvArgs& a, int p, int r0, int r
         slab = static_cast<size_t>(a.block_table[b * (a.l_max >> a.page_shift) + (pos >> a.page_shift)]);
         plen = 1 << a.page_shift;
         off = pos & (plen - 1);
+      }
+      if constexpr (!FIXED) {
+        if (a.kv8) {   // uniform: the same two elements (i, i + D/2), one byte each (dense rows: bind refuses paged e4m3 caches)
+          const float rs = a.kv_rscale[is_k ? 0 : 1];
+          const uint8_t e0 = kv_e4m3(u0, rs), e1 = kv_e4m3(u1, rs);
+          if (is_k) {
+            uint8_t* dst = static_cast<uint8_t*>(a.k_cache) + ((slab * a.n_kv_heads + (h - a.n_q_heads)) * plen + off) * D + i;
+            dst[0] = e0;
+            dst[half] = e1;
+          } else {
+            uint8_t* dst = static_cast<uint8_t*>(a.v_cache) + ((slab * a.n_kv_heads + (h - a.n_q_heads - a.n_kv_heads)) * D + i) * plen + off;
+            dst[0] = e0;
+            dst[static_cast<size_t>(half) * plen] = e1;
+          }
+          return;
+        }
       }
       if (is_k) {
         const int kvh = h - a.n_q_heads;

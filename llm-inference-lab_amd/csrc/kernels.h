@@ -63,7 +63,7 @@ struct GemvArgs {
   const int32_t* pos_base;  // device [B]
   const float* rope_cos;    // [max_pos][head_dim/2] or null (no RoPE)
   const float* rope_sin;
-  void* k_cache;            // [B][n_kv_heads][l_max][head_dim] bf16
+  void* k_cache;            // [B][n_kv_heads][l_max][head_dim] bf16 (kv8: e4m3, one byte per element)
   void* v_cache;
   // paged KV (sd_model_bind_paged): k_cache / v_cache are page POOLS ([pages][Hkv][P][D] / [pages][Hkv][D][P]) and row b's
   // position pos lives in page block_table[b * (l_max >> page_shift) + (pos >> page_shift)] at offset pos & (P - 1).
@@ -72,7 +72,8 @@ struct GemvArgs {
   int pos_off;
   int max_pos;
   int l_max;
-  unsigned head_dim : 8, n_q_heads : 8, n_kv_heads : 8, page_shift : 8;
+  unsigned head_dim : 8, n_q_heads : 8, n_kv_heads : 8, page_shift : 7;   // (page_shift <= 16)
+  unsigned kv8 : 1;         // the caches hold OCP e4m3 bytes (sd_model_set_kv_dtype), see kv_rscale; the last bit of page_shift's dword
   // ARGMAX epilogue: per-workgroup partials [T][grid]
   float* part_val;
   int* part_idx;
@@ -94,6 +95,9 @@ struct GemvArgs {
   const uint32_t* w12_table;
   const void* w12_ovf;           // fourth dwords of the wide blocks, 256 bytes each (read by the kernel, late and rarely)
   int w12_form;                  // W12Form of that copy (0 with a copy: W12_CODES); read by launch_gemv, not by the kernels
+  // kv8: 1 / k_scale and 1 / v_scale; a stored byte is e4m3(clamp(bf16(x) * kv_rscale, -448, 448)). Last in the block (no other
+  // field moves) and not in the hand-over of pin_gemv_args: only the e4m3 branch of the QKV epilogue loads them.
+  float kv_rscale[2];
 };
 constexpr int kStatStride = 256;                    // partials per token (>= workgroups of the producing launch)
 constexpr int kStatPlane = kSkinnyMaxT * kStatStride;   // floats per plane (plane 0: sum of squares, plane 1: sum)
@@ -186,17 +190,17 @@ int launch_gemm_pipe(const GemvArgs& a, const GemvGeom& q, const GemmPlan& pl, i
 struct AttnArgs {
   // line 0 (64 bytes): everything a short-context launch reads (see GemvArgs on why the order matters)
   const void* q;        // bf16 [T][n_q_heads*head_dim]
-  const void* k_cache;  // bf16 [B][n_kv_heads][l_max][head_dim]
+  const void* k_cache;  // bf16 [B][n_kv_heads][l_max][head_dim] (kv8: e4m3 bytes, dense only)
   const void* v_cache;
   void* out;            // bf16 [T][n_q_heads*head_dim]
   const int32_t* pos_base;
   const int32_t* skip_k;   // per-row adaptive K, as GemvArgs
   int pos_off;
   int l_max;
-  float scale;
+  float scale;          // of the scores; kv8: the caller has folded k_scale in
   unsigned M : 8, n_q_heads : 8, n_kv_heads : 8, n_split : 8;   // n_split: set by launch_attention
   // line 1
-  unsigned head_dim : 8, page_shift : 8, skip_i : 4;
+  unsigned head_dim : 8, page_shift : 8, skip_i : 4, kv8 : 1;
   int B;
   // split-KV over workgroups for long contexts (attention.hip): partial (max, sum, O) tiles and one
   // arrival counter per (row, kv head, query tile); null / 0 = every tile is one workgroup
@@ -204,8 +208,10 @@ struct AttnArgs {
   unsigned* split_cnt;
   int split_slots;      // partial tiles the workspace holds
   const int32_t* block_table;   // paged KV, as GemvArgs (null = dense rows of l_max positions)
+  float v_scale;        // kv8: multiplies the final 1 / den (read by the e4m3 instantiations only)
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);
+int launch_attention_kv8(const AttnArgs& a, dim3 grid, hipStream_t st);   // attention_kv8.hip; a.n_split and grid from launch_attention
 constexpr int kAttnSplitSlots = 1024;   // partial tiles of the split-KV workspace
 // The geometry of one attention launch, decided on the host from dimensions alone: launch_attention consults it and
 // sd_attention_plan (plan_query.hip) reports it. tiles: 16-row query tiles per (row, kv head); n_split: workgroups per tile

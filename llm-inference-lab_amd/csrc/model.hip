@@ -96,7 +96,8 @@ static int setup_persist(sd_model* m) {
   }
   SD_HIP_CHECK(hipMemcpy(m->p_ops, ops.data(), ops.size() * sizeof(PersistOp), hipMemcpyHostToDevice));
   // (a cache whose rows are not whole 8-key vectors cannot be walked by the launch's attention: launch path)
-  m->persist_cap = persist_cache_ok(m->Lmax) ? persist_max_tokens(c) : 0;
+  // (nor does the launch read an e4m3 cache: an fp8-KV model runs every pass on the launch path)
+  m->persist_cap = (persist_cache_ok(m->Lmax) && !m->kv8) ? persist_max_tokens(c) : 0;
   // tokens per pass the persistent launch takes (0 = off), by measurement (same box, 128 cached positions, us per forward,
   // persistent / launches; profiles/round3_persist_ab.md): Llama-3.2-1B dimensions 1 token 596 / 698, 2 tokens 677 / 718,
   // 3 tokens 838 / 741; Llama-3.2-3B dimensions 1 token 1506 / 1495, 2 tokens 1640 / 1540. So: 2 tokens up to
@@ -260,7 +261,20 @@ extern "C" size_t sd_model_workspace_bytes(const sd_model* m) { return m ? works
 
 extern "C" size_t sd_model_kv_bytes(const sd_model* m, int B, int Lmax) {
   if (!m || B <= 0 || Lmax <= 0) return 0;
-  return static_cast<size_t>(m->cfg.n_layers) * B * m->cfg.n_kv_heads * Lmax * m->cfg.head_dim * 2;
+  return static_cast<size_t>(m->cfg.n_layers) * B * m->cfg.n_kv_heads * Lmax * m->cfg.head_dim * (m->kv8 ? 1 : 2);
+}
+
+extern "C" int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, float v_scale) {
+  clear_error();
+  SD_REQUIRE(m, "model_set_kv_dtype: NULL model");
+  SD_REQUIRE(!m->k_cache, "model_set_kv_dtype: the kv dtype is set between sd_model_create and sd_model_bind (this model is bound)");
+  SD_REQUIRE(dtype == SD_BF16 || dtype == SD_FP8_E4M3, "model_set_kv_dtype: kv dtype %d (SD_BF16 or SD_FP8_E4M3)", dtype);
+  SD_REQUIRE(k_scale > 0.f && v_scale > 0.f && k_scale - k_scale == 0.f && v_scale - v_scale == 0.f,
+             "model_set_kv_dtype: kv scales must be positive and finite (got %g, %g)", static_cast<double>(k_scale), static_cast<double>(v_scale));
+  m->kv8 = dtype == SD_FP8_E4M3;
+  m->kv_scale[0] = m->kv8 ? k_scale : 1.0f;
+  m->kv_scale[1] = m->kv8 ? v_scale : 1.0f;
+  return 0;
 }
 
 extern "C" int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, int Lmax, void* workspace,
@@ -271,6 +285,8 @@ extern "C" int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, i
   SD_REQUIRE(workspace_bytes_ >= workspace_layout(m->cfg).bytes, "model_bind: workspace too small");
   SD_REQUIRE((reinterpret_cast<uintptr_t>(k_cache) & 15) == 0 && (reinterpret_cast<uintptr_t>(v_cache) & 15) == 0,
              "model_bind: caches must be 16-byte aligned");
+  SD_REQUIRE(!m->kv8 || (Lmax % 16 == 0 && (m->cfg.head_dim == 64 || m->cfg.head_dim == 128)),
+             "model_bind: an fp8 (e4m3) kv dtype needs Lmax %% 16 == 0 (got %d) and head_dim 64 or 128 (got %d)", Lmax, m->cfg.head_dim);
   return bind_caches(m, k_cache, v_cache, B, Lmax, nullptr, 0, 0, 0, workspace);
 }
 
@@ -286,6 +302,7 @@ extern "C" int sd_model_bind_paged(sd_model* m, void* k_pool, void* v_pool, int 
                                    int max_pages_per_row, int B, void* workspace, size_t workspace_bytes_) {
   clear_error();
   SD_REQUIRE(m && k_pool && v_pool && block_table && workspace, "model_bind_paged: NULL argument");
+  SD_REQUIRE(!m->kv8, "model_bind_paged: an fp8 (e4m3) kv dtype serves dense caches only (sd_model_bind)");
   SD_REQUIRE(B >= 1 && n_pages >= 1 && max_pages_per_row >= 1, "model_bind_paged: B=%d pages=%d max_pages=%d", B, n_pages, max_pages_per_row);
   int shift = 0;
   while ((1 << shift) < page_len) ++shift;
@@ -310,6 +327,7 @@ extern "C" int sd_model_kv_fork(sd_model* m, int src_row, const int32_t* dst_row
     SD_REQUIRE(dst_rows[i] != src_row, "kv_fork: destination row %d is the source row", dst_rows[i]);
   }
   SD_REQUIRE(m, "kv_fork: NULL model");
+  SD_REQUIRE(!m->kv8, "kv_fork: not available with an fp8 (e4m3) kv dtype");
   SD_REQUIRE(m->k_cache && m->x, "kv_fork: model not bound (sd_model_bind)");
   SD_REQUIRE(!m->block_table, "kv_fork: this model is bound to a paged cache (rows share pages: sd_model_kv_copy_pages)");
   SD_REQUIRE(src_row < m->B, "kv_fork: src_row %d outside the bound batch of %d", src_row, m->B);
@@ -338,6 +356,7 @@ extern "C" int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, con
     SD_REQUIRE(src_pages[i] != dst_pages[i], "kv_copy_pages: pair %d copies page %d onto itself", i, src_pages[i]);
   }
   SD_REQUIRE(m, "kv_copy_pages: NULL model");
+  SD_REQUIRE(!m->kv8, "kv_copy_pages: not available with an fp8 (e4m3) kv dtype");
   SD_REQUIRE(m->k_cache && m->x, "kv_copy_pages: model not bound (sd_model_bind_paged)");
   SD_REQUIRE(m->block_table, "kv_copy_pages: this model is bound to a dense cache (sd_model_kv_fork)");
   const int page_len = 1 << m->page_shift;
@@ -368,6 +387,7 @@ extern "C" int sd_model_kv_evict(sd_model* m, int row, int keep, int drop, int n
   SD_REQUIRE(drop >= 1 && drop % 8 == 0, "kv_evict: drop=%d must be a positive multiple of 8", drop);
   SD_REQUIRE(static_cast<int64_t>(keep) + drop <= n_pos, "kv_evict: keep=%d + drop=%d exceed n_pos=%d", keep, drop, n_pos);
   SD_REQUIRE(m, "kv_evict: NULL model");
+  SD_REQUIRE(!m->kv8, "kv_evict: not available with an fp8 (e4m3) kv dtype (re-rotating an e4m3 key is lossy)");
   SD_REQUIRE(m->k_cache && m->x, "kv_evict: model not bound (sd_model_bind)");
   SD_REQUIRE(!m->block_table, "kv_evict: this model is bound to a paged cache (eviction covers dense caches)");
   const sd_model_config& c = m->cfg;

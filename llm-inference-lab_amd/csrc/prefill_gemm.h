@@ -86,6 +86,9 @@ struct PrefillModel {
   // paged KV (sd_model_bind_paged): null = dense rows
   const int32_t* block_table = nullptr;   // [B][max_pages]
   int page_shift = 0, max_pages = 0, n_pages = 0;
+  // e4m3 caches (sd_model_set_kv_dtype): one byte per element, the scales of K and V
+  int kv8 = 0;
+  float kv_scale[2] = {1.0f, 1.0f};
   // matrix product: rocBLAS over the HF-layout bf16 weights, or the native GEMM over the packed streams
   int gemm = PREFILL_GEMM_ROCBLAS;
   const void* const* packed = nullptr;    // native: per matrix (4 per layer + lm_head, packing order)

@@ -254,8 +254,9 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
   };
   for (int l = 0; l < c.n_layers; ++l) {
     const sd_layer_weights& w = c.layers[l];
-    uint16_t* kc = m.k_cache + l * layer_kv + row_kv;
-    uint16_t* vc = m.v_cache + l * layer_kv + row_kv;
+    const size_t kv_off = (l * layer_kv + row_kv) * (m.kv8 ? 1 : 2);   // bytes
+    uint16_t* kc = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(m.k_cache) + kv_off);
+    uint16_t* vc = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(m.v_cache) + kv_off);
     GemvArgs g{};
     g.T = 128;                 // (per 128-token group: see epilogue_rows_kernel)
     g.M = 128;
@@ -269,6 +270,9 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     g.out_dtype = SD_BF16;
     g.block_table = bt;
     g.page_shift = m.page_shift;
+    g.kv8 = m.kv8;
+    g.kv_rscale[0] = 1.0f / m.kv_scale[0];
+    g.kv_rscale[1] = 1.0f / m.kv_scale[1];
     // the epilogue of product `which`: its shape and bias, the rows it writes
     auto epilogue_args = [&](int which, void* out, int out_stride) {
       const MatShape sh = matrix_shape(c, which);
@@ -309,6 +313,7 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
       at.head_dim = D;
       at.l_max = m.Lmax;
       at.scale = 1.0f / sqrtf(static_cast<float>(D));
+      if (m.kv8) { at.kv8 = 1; at.scale *= m.kv_scale[0]; at.v_scale = m.kv_scale[1]; }
       at.split_ws = m.attn_ws;
       at.split_cnt = m.attn_cnt;
       at.split_slots = kAttnSplitSlots;

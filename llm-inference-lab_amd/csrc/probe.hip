@@ -123,7 +123,7 @@ extern "C" int sd_model_probe_gemv(sd_model* m, int which, int T, int iters, voi
     if (which == 0) {  // QKV: + RoPE + in-place KV append (row 0 of the cache, positions 0..T-1)
       g.rope_cos = c.arch == SD_ARCH_LLAMA ? c.rope_cos : nullptr; g.rope_sin = c.arch == SD_ARCH_LLAMA ? c.rope_sin : nullptr;
       const size_t layer_kv = static_cast<size_t>(m->B) * c.n_kv_heads * m->Lmax * c.head_dim;
-      g.k_cache = m->k_cache + li * layer_kv; g.v_cache = m->v_cache + li * layer_kv;
+      g.k_cache = m->kv_at(m->k_cache, li * layer_kv); g.v_cache = m->kv_at(m->v_cache, li * layer_kv);
     }
     if (use_xstat && sh.epi == EPI_RESID && gemm_resid_publishes_stats(g)) g.xstat_out = m->xstat;
     return launch_gemv(g, sh.epi, st);

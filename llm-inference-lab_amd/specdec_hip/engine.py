@@ -126,9 +126,12 @@ class HipModel:
 
     def __init__(self, weights: ModelWeights, batch: int, l_max: int, device: Optional[torch.device] = None,
                  weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None,
-                 prefill_backend: str = "auto"):
+                 prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0)):
         """weight_dtype "fp8": the engine streams an OCP e4m3 copy of the Linear weights (per-output-row
-        scales, quantised on the device at load); activations and the KV cache stay bf16.
+        scales, quantised on the device at load); activations stay bf16.
+        kv_dtype "fp8" (kv_cache_dtype): the KV cache holds OCP e4m3 bytes, element x stored as e4m3(clamp(x / scale, +-448)) with
+        kv_scales = (k_scale, v_scale); half the bytes of the bf16 cache. Dense caches of head_dim 64 or 128; every pass runs on
+        the launch path; fork_row / evict_row and page_len are refused (sd_model_set_kv_dtype).
         page_len (a power of two >= 32): paged KV — the rows share a pool of `n_pages` pages (default: enough for every
         row to reach l_max) through a block table; `reserve(row, length)` / `release(row)` manage a row's pages.
         prefill_backend: how prompts (>= 96 positions per row) are absorbed — "auto" (rocBLAS where it serves the model, else
@@ -136,7 +139,13 @@ class HipModel:
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype={weight_dtype!r} (bf16 or fp8)")
         _prefill_backend_id(prefill_backend)
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype={kv_dtype!r} (kv_cache_dtype: bf16 or fp8)")
+        if kv_dtype == "fp8" and (page_len is not None or os.environ.get("SPECDEC_PAGED_KV")):
+            raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with page_len / SPECDEC_PAGED_KV")
         self.weight_dtype = weight_dtype
+        self.kv_dtype = kv_dtype
+        self.kv_scales = (float(kv_scales[0]), float(kv_scales[1]))
         self.lib = _abi.load()
         self.cfg: ModelConfig = weights.config
         dev = torch.device(device) if device is not None else weights.tok_emb.device
@@ -204,6 +213,8 @@ class HipModel:
                     copy = weights.meta[key] = build_w12(self.lib, mc, dev, classes, form)
                 setattr(self, attr, copy)
                 _abi.check(self.lib.sd_model_set_w12_form(self.handle, _ptr(copy[0]), copy[1].ctypes.data, classes, form), "sd_model_set_w12_form")
+        if kv_dtype == "fp8":
+            self.set_kv_dtype(kv_dtype, self.kv_scales)
         self.batch, self.l_max = int(batch), (int(l_max) + 31) // 32 * 32  # whole 32-key blocks
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):
@@ -213,13 +224,22 @@ class HipModel:
         if prefill_backend != "auto":
             self.set_prefill_backend(prefill_backend)
 
+    def set_kv_dtype(self, kv_dtype: str, kv_scales: Sequence[float] = (1.0, 1.0)) -> None:
+        """sd_model_set_kv_dtype: between create and bind only (the constructor calls it; afterwards the library refuses)"""
+        _abi.check(self.lib.sd_model_set_kv_dtype(self.handle, _abi.SD_FP8_E4M3 if kv_dtype == "fp8" else _abi.SD_BF16,
+                                                  float(kv_scales[0]), float(kv_scales[1])), "sd_model_set_kv_dtype")
+
     def _bind_dense(self) -> None:
         dev = self.device
         kv_bytes = self.lib.sd_model_kv_bytes(self.handle, self.batch, self.l_max)
         with torch.cuda.device(dev):
-            # [n_layers][B][Hkv][Lmax][D] bf16 — sized for 288 GB of HBM: no paging, no realign copies
-            self.k_cache = torch.zeros(kv_bytes // 2, dtype=torch.bfloat16, device=dev)
-            self.v_cache = torch.zeros(kv_bytes // 2, dtype=torch.bfloat16, device=dev)
+            # [n_layers][B][Hkv][Lmax][D] bf16 — sized for 288 GB of HBM: no paging, no realign copies (fp8: e4m3 bytes)
+            if self.kv_dtype == "fp8":
+                self.k_cache = torch.zeros(kv_bytes, dtype=torch.uint8, device=dev)
+                self.v_cache = torch.zeros(kv_bytes, dtype=torch.uint8, device=dev)
+            else:
+                self.k_cache = torch.zeros(kv_bytes // 2, dtype=torch.bfloat16, device=dev)
+                self.v_cache = torch.zeros(kv_bytes // 2, dtype=torch.bfloat16, device=dev)
             self.workspace = torch.empty(self.lib.sd_model_workspace_bytes(self.handle), dtype=torch.uint8, device=dev)
             _abi.check(self.lib.sd_model_bind(self.handle, self.k_cache.data_ptr(), self.v_cache.data_ptr(),
                                               self.batch, self.l_max, self.workspace.data_ptr(),
@@ -291,6 +311,7 @@ class HipModel:
         partial last one); the table entries are written on `stream`, as reserve() does. Shared pages are immutable — rows
         only append or roll back to >= their accepted length — so there is no copy-on-write. A pool that cannot serve the
         fork raises before any table entry or ownership list has changed."""
+        self._no_fp8_kv("fork_row (share_prefix, n / best_of)")
         dsts = [int(d) for d in dsts]
         length = int(length)
         st = _stream(stream, self.device)
@@ -320,17 +341,26 @@ class HipModel:
         -drop positions with the model's own RoPE tables (one more bf16 rounding of the moved keys). The first `keep` positions,
         positions >= n_pos - drop and the other rows keep their bits; the row's length afterwards is the caller's to lower by
         `drop`. Dense Llama caches only, drop a positive multiple of 8 below max_pos: anything else raises before device work."""
+        self._no_fp8_kv("evict_row (context_window)")
         with torch.cuda.device(self.device):
             _abi.check(self.lib.sd_model_kv_evict(self.handle, int(row), int(keep), int(drop), int(n_pos), _stream(stream, self.device)),
                        "sd_model_kv_evict")
 
+    def _no_fp8_kv(self, what: str) -> None:
+        if self.kv_dtype == "fp8":
+            raise RuntimeError(f"{what} is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked or re-rotated)")
+
     def kv_view(self):
+        """(K [layers][B][Hkv][Lmax][D], V [layers][B][Hkv][D][Lmax]) views of the caches (paged: of the pools); bf16, or
+        torch.float8_e4m3fn on an fp8-KV engine (multiply by kv_scales to dequantise)"""
         c = self.cfg
         if self.page_len is not None:
             return (self.k_cache.view(c.n_layers, self.n_pages, c.n_kv_heads, self.page_len, c.head_dim),
                     self.v_cache.view(c.n_layers, self.n_pages, c.n_kv_heads, c.head_dim, self.page_len))
         k_shape = (c.n_layers, self.batch, c.n_kv_heads, self.l_max, c.head_dim)
         v_shape = (c.n_layers, self.batch, c.n_kv_heads, c.head_dim, self.l_max)  # V is kept transposed
+        if self.kv_dtype == "fp8":
+            return self.k_cache.view(torch.float8_e4m3fn).view(k_shape), self.v_cache.view(torch.float8_e4m3fn).view(v_shape)
         return self.k_cache.view(k_shape), self.v_cache.view(v_shape)
 
     def forward(self, tokens: torch.Tensor, pos_base: torch.Tensor, pos_off: int = 0,

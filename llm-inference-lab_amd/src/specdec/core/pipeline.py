@@ -131,11 +131,12 @@ class SpeculativePipeline:
                  policy_params: Optional[Dict[str, Any]] = None, controller: str = "fixed",
                  controller_params: Optional[Dict[str, Any]] = None, draft_mode: str = "vanilla",
                  enable_optimization: bool = True, enable_profiling: bool = False,
-                 profile_dir: Optional[str] = None, medusa_heads: Optional[Any] = None):
+                 profile_dir: Optional[str] = None, medusa_heads: Optional[Any] = None, kv_cache_dtype: Optional[str] = None):
         self.logger = logging.getLogger(__name__)
         self.config = self._load_config(config_path)
         for key, val in (("base_model", base_model), ("draft_model", draft_model), ("max_draft", max_draft),
-                         ("seed", seed), ("implementation", implementation), ("draft_mode", draft_mode)):
+                         ("seed", seed), ("implementation", implementation), ("draft_mode", draft_mode),
+                         ("kv_cache_dtype", kv_cache_dtype)):
             if val is not None:
                 self.config[key] = val
         impl = self.config["implementation"]
@@ -205,6 +206,10 @@ class SpeculativePipeline:
             if not isinstance(lm, HipLM):
                 raise TypeError(f"{who}_lm must be a HipLM (got {type(lm).__name__}): the step loop drives the "
                                 "models through the C-ABI engine, not through generate_tokens")
+        if not self._fake and self.config.get("kv_cache_dtype") is not None:   # both engines of the pipeline: "bf16" or "fp8"
+            for lm in (self.base_lm, self.draft_lm):
+                if lm is not None:
+                    lm.set_kv_dtype(str(self.config["kv_cache_dtype"]), lm.kv_scales)
         if self.draft_lm is not None and self.base_lm.vocab_size != self.draft_lm.vocab_size:
             raise ValueError(f"draft/base vocabularies differ: {self.draft_lm.vocab_size} vs {self.base_lm.vocab_size}")
         self.speculative_enabled = True

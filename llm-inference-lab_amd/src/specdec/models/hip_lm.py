@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -82,7 +82,8 @@ def _draw(last: torch.Tensor, temperature: float, kwargs) -> torch.Tensor:
 class HipLM(LanguageModel):
     def __init__(self, weights: W.ModelWeights, tokenizer: Any = None, name: Optional[str] = None,
                  max_len: int = 1024, batch: int = 1, device: str = "cuda", weight_dtype: str = "bf16",
-                 kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto"):
+                 kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto",
+                 kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0)):
         if prefill_backend not in _abi.PREFILL_BACKENDS:
             raise ValueError(f"prefill_backend={prefill_backend!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
         if not torch.cuda.is_available():
@@ -102,14 +103,26 @@ class HipLM(LanguageModel):
         # how the engines absorb prompts (HipModel.set_prefill_backend): "auto", "passes", "rocblas" or "native"
         self.prefill_backend = prefill_backend
         self._model: Optional[HipModel] = None
+        # element type of the engines' KV caches (HipModel kv_dtype): "bf16", or "fp8" = e4m3 bytes with the scales (k, v)
+        self.set_kv_dtype(kv_dtype, kv_scales)
         self._cached: List[List[int]] = []
         self._last_generated_kv: Optional[KVCache] = None
 
     # ---- engine instances ----------------------------------------------------------
+    def set_kv_dtype(self, kv_dtype: str, kv_scales: Sequence[float] = (1.0, 1.0)) -> None:
+        """kv_cache_dtype of the engines created from now on ("bf16" or "fp8"); an engine this model holds is dropped"""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype={kv_dtype!r} (bf16 or fp8)")
+        if kv_dtype == "fp8" and self.kv_page_len is not None:
+            raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with kv_page_len")
+        self.kv_cache_dtype, self.kv_scales = kv_dtype, (float(kv_scales[0]), float(kv_scales[1]))
+        self._model, self._cached = None, []
+
     def new_engine(self, batch: int, l_max: int) -> HipModel:
         """A forward instance with its own KV cache over the shared weights."""
         return HipModel(self.weights, batch=batch, l_max=l_max, device=self._device, weight_dtype=self.weight_dtype,
-                        page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend)
+                        page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend,
+                        kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales)
 
     def _engine(self, batch: int, need_len: int) -> HipModel:
         m = self._model
@@ -367,6 +380,8 @@ class HipLM(LanguageModel):
             return None
         n = len(self._cached[0])
         k, v = m.kv_view()
+        if m.kv_dtype == "fp8":   # dequantised bf16 copies (exact for power-of-two scales)
+            k, v = k.to(torch.bfloat16) * m.kv_scales[0], v.to(torch.bfloat16) * m.kv_scales[1]
         if m.page_len is None:   # dense rows: k [L,B,H,Lmax,D], v [L,B,H,D,Lmax] -> views
             kv = tuple((k[l, :, :, :n, :], v[l, :, :, :, :n].transpose(-1, -2)) for l in range(self.config.n_layers))
             return KVCache(past_key_values=kv, seq_len=n, dtype=torch.bfloat16, device=self._device)

@@ -63,6 +63,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--prefill-backend", type=str, choices=["auto", "passes", "rocblas", "native"], default="auto",
                     help="how prompts are absorbed into the KV cache: auto (rocBLAS where it serves the model, else the 128-token passes), "
                          "passes, rocblas, or native (this library's MFMA GEMM over the packed weights; bf16 and fp8, dense and paged KV)")
+    ap.add_argument("--kv-cache-dtype", type=str, choices=["bf16", "fp8"], default=None,
+                    help="element type of both engines' KV caches: bf16, or fp8 (OCP e4m3, half the bytes; dense caches, no "
+                         "--share-prefix / --n / --context-window)")
     ap.add_argument("--n", type=int, default=1,
                     help="n completions of the prompt as n rows of one generate_batch call: the prompt is prefilled once and the other "
                          "rows are forked from it (implies --share-prefix); they differ under --spec-sampling (a Philox stream per row)")
@@ -206,7 +209,7 @@ def main(argv=None) -> int:
         pipe = SpeculativePipeline(config_path=args.config, base_model=args.base_model, draft_model=args.draft_model,
                                    max_draft=args.max_draft, device=args.device, seed=args.seed, implementation=args.impl,
                                    policy=policy, controller=controller, controller_params=cp, draft_mode=args.draft_mode,
-                                   policy_params=pp)
+                                   policy_params=pp, kv_cache_dtype=args.kv_cache_dtype)
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)

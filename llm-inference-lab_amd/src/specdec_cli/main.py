@@ -79,7 +79,7 @@ def cmd_run(args: argparse.Namespace) -> int:
         extra = {"policy": args.policy, "policy_params": pp}
     pipe = SpeculativePipeline(base_model=args.base_model, draft_model=args.draft_model, max_draft=args.k, implementation="hip",
                                device=args.device, controller="fixed", controller_params={"k": args.k}, enable_optimization=True,
-                               draft_mode="vanilla", **extra)
+                               draft_mode="vanilla", kv_cache_dtype=args.kv_cache_dtype, **extra)
     proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                               ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
     if args.regex is not None:
@@ -179,6 +179,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--sampling-params", type=str, metavar="FILE",
                     help="JSON list with one object per prompt (temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, "
                          "frequency_penalty): per-request parameters read row by row inside the captured step (generate_batch)")
+    pr.add_argument("--kv-cache-dtype", choices=["bf16", "fp8"], default=None,
+                    help="element type of both engines' KV caches: bf16, or fp8 (OCP e4m3, half the bytes; dense caches, no --share-prefix / --n / --context-window)")
     pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
                                                      "once and forked into the others (implies --share-prefix)")
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
