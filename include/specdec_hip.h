@@ -418,6 +418,28 @@ int sd_model_kv_fork(sd_model* m, int src_row, const int32_t* dst_rows, int n_ds
  * (n_pos == page_len: whole pages). Block tables and page ownership stay the caller's. */
 int sd_model_kv_copy_pages(sd_model* m, const int32_t* src_pages, const int32_t* dst_pages, int n_pairs, int n_pos, void* stream);
 
+/* Cascade attention (csrc/attention_cascade.hip): rows forked from one prompt read the shared keys once per group instead of once
+ * per row. Additive (SD_ABI_VERSION stays 1).
+ *
+ * sd_model_set_cascade(enable != 0), between sd_model_create and a bind: every attention launch of the launch path (the 1-9
+ * token forwards and the multi-token passes alike) becomes the cascade launch; the GEMM prompt route keeps its attention and the
+ * model never runs a pass as the persistent launch. The next bind allocates the mode's own storage (the table below, the
+ * partial-tile workspace and its arrival counters, sized from B and Lmax) and needs Lmax % 32 == 0. bf16 caches, dense or paged.
+ * Refused: a bound model, an fp8 (e4m3) kv dtype (and sd_model_set_kv_dtype to fp8 afterwards), sd_model_kv_evict on such a
+ * model, and a forward under per-row adaptive K.
+ *
+ * sd_model_set_shared_prefix writes one entry of the per-row table {leader, shared_len}, asynchronously on `stream` (order it
+ * before the forward that should see it): positions [0, shared_len) of `row` are BIT-IDENTICAL to the same positions of row
+ * `leader` (dense: sd_model_kv_fork made them so; paged: the rows' block tables name the same pages or equal copies) and
+ * shared_len <= the position of the row's next token; attention then reads them from the leader's cache. A group's root names
+ * itself with the longest length of its members; (row, row, 0) takes a row out of every group, which is how a bind leaves all
+ * rows. With no entries set a launch computes what the plain kernel computes. Refused before any device work: a model without
+ * the mode or unbound, row or leader outside the bound batch, shared_len negative, beyond Lmax or not a multiple of 32,
+ * shared_len 0 with leader != row, a leader whose own entry names another row (not a root), and making `row` a member or taking it
+ * out of its group while another row's entry still names it (groups stay one level deep: move the members first). */
+int sd_model_set_cascade(sd_model* m, int enable);
+int sd_model_set_shared_prefix(sd_model* m, int row, int leader, int shared_len, void* stream);
+
 /* KV eviction inside one cache row (csrc/kv_evict.hip): the rolling context window. In row `row` of a dense cache of a
  * Llama model, positions [keep + drop, n_pos) become positions [keep, n_pos - drop): all layers, all KV heads, K and V,
  * in place, in one launch, asynchronous on `stream`, no allocation, capturable. V moves bit for bit. K is stored after
@@ -627,6 +649,14 @@ int sd_gemv_instance(int T, int n_pairs, int K, int w8, int prologue, int epi, c
  * B or M below 1, l_max not a multiple of 8, pages not 32 * 2^n positions or l_max not whole pages). */
 int sd_attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles, int* n_split,
                       int* grid_x, int* grid_y, int* grid_z);
+/* The same for a cascade launch (sd_model_set_cascade): *tiles and *n_split as above (they shape its suffix workgroups: a row in no
+ * group is computed as the plain launch computes it); *sets = groups of up to 4 stacked 16-row query tiles that B rows can form,
+ * ceil(ceil(B * Hq / Hkv * M / 16) / 4); *p_split = workgroups per set over a group's shared keys: l_max / 512, at most 32, at
+ * most 512 / (Hkv * sets), at least 1 (1 under SPECDEC_NO_ATTN_SPLIT); *slots = partial tiles of the mode's workspace the launch
+ * addresses, Hkv * B * tiles * (n_split + p_split); the grid is (Hkv, B, tiles * n_split + sets * p_split). Refused as above, and
+ * l_max not a multiple of 32 or B above 128. */
+int sd_attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles,
+                              int* n_split, int* sets, int* p_split, int* slots, int* grid_x, int* grid_y, int* grid_z);
 
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *

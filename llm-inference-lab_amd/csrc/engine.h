@@ -71,7 +71,18 @@ struct sd_model {
   int persist_cap = 0;                     // tokens per persistent pass this model / device / cache can take (0: none)
   int len_hint = 0;                        // caller's bound on the rows' current lengths (sd_model_set_length_hint; default Lmax)
   int ctx_limit = 0;                       // longest rows the persistent launch serves (kPersistMaxCtx; lifted by SPECDEC_PERSIST_MAX_T)
+  // cascade attention (sd_model_set_cascade; csrc/attention_cascade.hip): the launch path's attention reads a group's shared keys
+  // once. One allocation of the model's own, made at the bind (its size follows B and Lmax): the shared-prefix table {leader,
+  // shared_len} x B, the arrival counters, the partial tiles. share_host mirrors the table (sd_model_set_shared_prefix validates on it).
+  int cascade = 0;
+  void* cascade_buf = nullptr;
+  int32_t* share = nullptr;
+  unsigned* cascade_cnt = nullptr;
+  float* cascade_ws = nullptr;
+  int cascade_slots = 0;
+  std::vector<int32_t> share_host;
   ~sd_model() {
+    if (cascade_buf) (void)hipFree(cascade_buf);
     if (host_status) (void)hipHostFree(host_status);
     if (prefill_ws) (void)hipFree(prefill_ws);
     if (score_ws) (void)hipFree(score_ws);

@@ -206,7 +206,19 @@ static int launch_pass(sd_model* m, const Pass& p, hipStream_t st) {
     at.page_shift = m->page_shift;
     at.skip_k = m->skip_k;
     at.skip_i = m->skip_i;
-    if (int rc = launch_attention(at, st)) return rc;
+    if (m->cascade) {
+      // the cascade launch (csrc/attention_cascade.hip): the layer's whole caches and table (a group's leader may sit outside this
+      // pass's rows), the mode's own workspace
+      at.k_cache = m->k_cache + l * layer_kv;
+      at.v_cache = m->v_cache + l * layer_kv;
+      at.block_table = m->block_table;
+      at.row0 = p.row;
+      at.share = m->share;
+      at.split_ws = m->cascade_ws;
+      at.split_cnt = m->cascade_cnt;
+      at.split_slots = m->cascade_slots;
+      if (int rc = launch_attention_cascade(at, st)) return rc;
+    } else if (int rc = launch_attention(at, st)) return rc;
 
     // 3. output projection + residual, 4. norm + up projection (+ gate) + activation
     GemvArgs a3 = layer_args(1);

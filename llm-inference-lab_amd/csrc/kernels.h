@@ -209,6 +209,13 @@ struct AttnArgs {
   int split_slots;      // partial tiles the workspace holds
   const int32_t* block_table;   // paged KV, as GemvArgs (null = dense rows of l_max positions)
   float v_scale;        // kv8: multiplies the final 1 / den (read by the e4m3 instantiations only)
+  // cascade attention (attention_cascade.hip; read by its kernels only): the shared-prefix table of the BOUND batch, {leader,
+  // shared_len} per row — keys [0, shared_len[b]) of row b are bit-identical to the same positions of row leader[b]; (b, 0) = in no
+  // group. Such a launch indexes q / out / pos_base from the pass's first row as every launch does, but k_cache / v_cache /
+  // block_table are the layer's whole caches and row0 is the pass's first row in them (a leader may sit outside the pass).
+  const int32_t* share;
+  int row0;
+  unsigned c_split : 8;   // workgroups per prefix tile set (set by launch_attention_cascade)
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);
 int launch_attention_kv8(const AttnArgs& a, dim3 grid, hipStream_t st);   // attention_kv8.hip; a.n_split and grid from launch_attention
@@ -222,6 +229,17 @@ int attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, in
                    int split_slots, AttnPlan& plan);
 size_t attention_split_ws_bytes(int head_dim);   // workspace for kAttnSplitSlots partial tiles (+ counters)
 size_t attention_split_tiles_bytes(int head_dim);   // the partial tiles of it (split_ws); the kAttnSplitSlots counters (split_cnt) follow
+// Cascade attention (attention_cascade.hip): one launch whose prefix workgroups read a group's shared keys once for all its member
+// rows and whose suffix workgroups read each row's own keys; a.share is the table, a.split_ws / split_cnt / split_slots the mode's
+// own workspace. Its geometry, from dimensions alone (sd_attention_cascade_plan reports it): tiles and n_split are attention_plan's
+// (the suffix of an ungrouped row is the plain computation); sets: groups of up to 4 stacked 16-row query tiles a launch of B rows
+// can hold; p_split: workgroups per set; slots: partial tiles of the workspace (n_kv_heads * B * tiles * (n_split + p_split)),
+// one arrival counter per (row, kv head, tile); grid = (n_kv_heads, B, tiles * n_split + sets * p_split).
+struct CascadePlan { int tiles, n_split, sets, p_split, slots, grid_x, grid_y, grid_z; };
+int attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int page_shift, CascadePlan& plan);
+size_t attention_cascade_ws_bytes(int head_dim, int slots);   // the partial tiles (the counters are the caller's to add)
+int launch_attention_cascade(const AttnArgs& a, hipStream_t st);
+int launch_cascade_set_entry(int32_t* share, int row, int leader, int shared_len, hipStream_t st);
 
 // ---- small kernels (misc.hip) -------------------------------------------------------
 struct EmbedArgs {

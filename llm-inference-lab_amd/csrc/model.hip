@@ -97,7 +97,8 @@ static int setup_persist(sd_model* m) {
   SD_HIP_CHECK(hipMemcpy(m->p_ops, ops.data(), ops.size() * sizeof(PersistOp), hipMemcpyHostToDevice));
   // (a cache whose rows are not whole 8-key vectors cannot be walked by the launch's attention: launch path)
   // (nor does the launch read an e4m3 cache: an fp8-KV model runs every pass on the launch path)
-  m->persist_cap = (persist_cache_ok(m->Lmax) && !m->kv8) ? persist_max_tokens(c) : 0;
+  // (nor does it know the shared-prefix table: a cascade model runs every pass on the launch path, as a session past its length hint)
+  m->persist_cap = (persist_cache_ok(m->Lmax) && !m->kv8 && !m->cascade) ? persist_max_tokens(c) : 0;
   // tokens per pass the persistent launch takes (0 = off), by measurement (same box, 128 cached positions, us per forward,
   // persistent / launches; profiles/round3_persist_ab.md): Llama-3.2-1B dimensions 1 token 596 / 698, 2 tokens 677 / 718,
   // 3 tokens 838 / 741; Llama-3.2-3B dimensions 1 token 1506 / 1495, 2 tokens 1640 / 1540. So: 2 tokens up to
@@ -136,6 +137,35 @@ static int carve_workspace(sd_model* m, void* workspace) {
   return setup_persist(m);
 }
 
+// Cascade attention's own storage (sd_model_set_cascade), sized for the largest launch a pass of this batch can be: every
+// (rows, tokens per row) with rows <= B and rows * tokens <= kSkinnyMaxT. The table starts with every row in no group.
+static int setup_cascade(sd_model* m) {
+  const sd_model_config& c = m->cfg;
+  SD_REQUIRE(m->Lmax % 32 == 0, "model_bind: cascade attention needs Lmax %% 32 == 0 (got %d)", m->Lmax);
+  int slots = 0, counters = 0;
+  for (int M = 1; M <= kSkinnyMaxT; ++M)
+    for (int B = 1; B <= m->B && B * M <= kSkinnyMaxT; ++B) {
+      CascadePlan pl{};
+      if (int rc = attention_cascade_plan(c.n_heads, c.n_kv_heads, c.head_dim, B, M, m->Lmax, m->block_table ? m->page_shift : -1, pl)) return rc;
+      if (pl.slots > slots) slots = pl.slots;
+      if (c.n_kv_heads * B * pl.tiles > counters) counters = c.n_kv_heads * B * pl.tiles;
+    }
+  const size_t tb = align_up(sizeof(int32_t) * 2 * m->B, 256), cb = align_up(sizeof(unsigned) * counters, 256);
+  if (m->cascade_buf) SD_HIP_CHECK(hipFree(m->cascade_buf));
+  m->cascade_buf = nullptr;
+  SD_HIP_CHECK(hipMalloc(&m->cascade_buf, tb + cb + attention_cascade_ws_bytes(c.head_dim, slots)));
+  char* p = static_cast<char*>(m->cascade_buf);
+  m->share = reinterpret_cast<int32_t*>(p);
+  m->cascade_cnt = reinterpret_cast<unsigned*>(p + tb);
+  m->cascade_ws = reinterpret_cast<float*>(p + tb + cb);
+  m->cascade_slots = slots;
+  m->share_host.assign(2 * static_cast<size_t>(m->B), 0);
+  for (int b = 0; b < m->B; ++b) m->share_host[2 * b] = b;
+  SD_HIP_CHECK(hipMemcpy(m->share, m->share_host.data(), sizeof(int32_t) * 2 * m->B, hipMemcpyHostToDevice));
+  SD_HIP_CHECK(hipMemset(m->cascade_cnt, 0, cb));
+  return 0;
+}
+
 // What both binds do once their own arguments have passed: the cache description (block_table null: dense rows of Lmax positions),
 // a fresh prompt route, count and record, and the carve.
 static int bind_caches(sd_model* m, void* k, void* v, int B, int Lmax, const int32_t* block_table, int page_shift, int max_pages,
@@ -148,7 +178,8 @@ static int bind_caches(sd_model* m, void* k, void* v, int B, int Lmax, const int
   m->prefill_backend = SD_PREFILL_AUTO;
   m->prefill_mc = 0;
   for (int64_t& n : m->prefill_count) n = 0;
-  return carve_workspace(m, workspace);
+  if (int rc = carve_workspace(m, workspace)) return rc;
+  return m->cascade ? setup_cascade(m) : 0;
 }
 
 }  // namespace sd
@@ -271,10 +302,41 @@ extern "C" int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, floa
   SD_REQUIRE(dtype == SD_BF16 || dtype == SD_FP8_E4M3, "model_set_kv_dtype: kv dtype %d (SD_BF16 or SD_FP8_E4M3)", dtype);
   SD_REQUIRE(k_scale > 0.f && v_scale > 0.f && k_scale - k_scale == 0.f && v_scale - v_scale == 0.f,
              "model_set_kv_dtype: kv scales must be positive and finite (got %g, %g)", static_cast<double>(k_scale), static_cast<double>(v_scale));
+  SD_REQUIRE(dtype != SD_FP8_E4M3 || !m->cascade, "model_set_kv_dtype: an fp8 (e4m3) kv dtype is not available with cascade attention (an e4m3 cache is not forked)");
   m->kv8 = dtype == SD_FP8_E4M3;
   m->kv_scale[0] = m->kv8 ? k_scale : 1.0f;
   m->kv_scale[1] = m->kv8 ? v_scale : 1.0f;
   return 0;
+}
+
+extern "C" int sd_model_set_cascade(sd_model* m, int enable) {
+  clear_error();
+  SD_REQUIRE(m, "model_set_cascade: NULL model");
+  SD_REQUIRE(!m->k_cache, "model_set_cascade: cascade attention is set between sd_model_create and sd_model_bind (this model is bound)");
+  SD_REQUIRE(!enable || !m->kv8, "model_set_cascade: not available with an fp8 (e4m3) kv dtype (an e4m3 cache is not forked)");
+  m->cascade = enable ? 1 : 0;
+  return 0;
+}
+
+extern "C" int sd_model_set_shared_prefix(sd_model* m, int row, int leader, int shared_len, void* stream) {
+  clear_error();
+  SD_REQUIRE(m, "set_shared_prefix: NULL model");
+  SD_REQUIRE(m->cascade, "set_shared_prefix: this model has no cascade attention (sd_model_set_cascade)");
+  SD_REQUIRE(m->k_cache && m->share, "set_shared_prefix: model not bound (sd_model_bind)");
+  SD_REQUIRE(row >= 0 && row < m->B, "set_shared_prefix: row %d outside the bound batch of %d", row, m->B);
+  SD_REQUIRE(leader >= 0 && leader < m->B, "set_shared_prefix: leader %d outside the bound batch of %d", leader, m->B);
+  SD_REQUIRE(shared_len >= 0 && shared_len <= m->Lmax && shared_len % 32 == 0,
+             "set_shared_prefix: shared_len=%d must be a multiple of 32 in [0, Lmax=%d]", shared_len, m->Lmax);
+  SD_REQUIRE(shared_len > 0 || leader == row, "set_shared_prefix: a row that shares nothing is its own leader (row %d, leader %d)", row, leader);
+  SD_REQUIRE(leader == row || m->share_host[2 * leader] == leader, "set_shared_prefix: leader %d is itself a member of row %d's group, not a root",
+             leader, m->share_host[2 * leader]);
+  if (leader != row || shared_len == 0)   // groups stay one level deep: a row that members name stays a root until they have moved
+    for (int b = 0; b < m->B; ++b)
+      SD_REQUIRE(b == row || m->share_host[2 * b] != row || m->share_host[2 * b + 1] == 0,
+                 "set_shared_prefix: row %d still names row %d as its leader (move the members first)", b, row);
+  m->share_host[2 * row] = leader;
+  m->share_host[2 * row + 1] = shared_len;
+  return launch_cascade_set_entry(m->share, row, leader, shared_len, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, int Lmax, void* workspace,
@@ -388,6 +450,7 @@ extern "C" int sd_model_kv_evict(sd_model* m, int row, int keep, int drop, int n
   SD_REQUIRE(static_cast<int64_t>(keep) + drop <= n_pos, "kv_evict: keep=%d + drop=%d exceed n_pos=%d", keep, drop, n_pos);
   SD_REQUIRE(m, "kv_evict: NULL model");
   SD_REQUIRE(!m->kv8, "kv_evict: not available with an fp8 (e4m3) kv dtype (re-rotating an e4m3 key is lossy)");
+  SD_REQUIRE(!m->cascade, "kv_evict: not available with cascade attention (a shared prefix does not move)");
   SD_REQUIRE(m->k_cache && m->x, "kv_evict: model not bound (sd_model_bind)");
   SD_REQUIRE(!m->block_table, "kv_evict: this model is bound to a paged cache (eviction covers dense caches)");
   const sd_model_config& c = m->cfg;

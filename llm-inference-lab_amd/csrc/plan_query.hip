@@ -188,6 +188,25 @@ extern "C" int sd_attention_plan(int n_q_heads, int n_kv_heads, int head_dim, in
   return 0;
 }
 
+extern "C" int sd_attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles,
+                                         int* n_split, int* sets, int* p_split, int* slots, int* grid_x, int* grid_y, int* grid_z) {
+  clear_error();
+  SD_REQUIRE(tiles && n_split && sets && p_split && slots && grid_x && grid_y && grid_z, "attention_cascade_plan: NULL argument");
+  SD_REQUIRE(n_q_heads >= 1 && n_q_heads <= 255 && n_kv_heads >= 0 && n_kv_heads <= 255 && M <= 255 && B <= (1 << 16),
+             "attention_cascade_plan: Hq=%d Hkv=%d M=%d B=%d beyond what a launch holds (heads and M <= 255)", n_q_heads, n_kv_heads, M, B);
+  int page_shift = -1;   // as sd_attention_plan
+  if (paged != 0) {
+    page_shift = 0;
+    while (page_shift < 30 && (1 << page_shift) < paged) ++page_shift;
+    if (paged < 0 || (1 << page_shift) != paged) page_shift = 0;
+  }
+  CascadePlan pl{};
+  if (int rc = attention_cascade_plan(n_q_heads, n_kv_heads, head_dim, B, M, l_max, page_shift, pl)) return rc;
+  *tiles = pl.tiles; *n_split = pl.n_split; *sets = pl.sets; *p_split = pl.p_split; *slots = pl.slots;
+  *grid_x = pl.grid_x; *grid_y = pl.grid_y; *grid_z = pl.grid_z;
+  return 0;
+}
+
 extern "C" int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
                                int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
                                char* name, size_t name_cap, char* reason, size_t reason_cap) {

@@ -121,6 +121,9 @@ SIGNATURES = {
     "sd_model_kv_fork": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p]),
     "sd_model_kv_copy_pages": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
     "sd_model_kv_evict": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
+    "sd_model_set_cascade": (_c_int, [_c_void_p, _c_int]),
+    "sd_model_set_shared_prefix": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
+    "sd_attention_cascade_plan": (_c_int, [_c_int] * 7 + [ctypes.POINTER(_c_int)] * 8),
     "sd_model_forward": (
         _c_int,
         [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,

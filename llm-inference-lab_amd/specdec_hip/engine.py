@@ -126,7 +126,7 @@ class HipModel:
 
     def __init__(self, weights: ModelWeights, batch: int, l_max: int, device: Optional[torch.device] = None,
                  weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None,
-                 prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0)):
+                 prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade: bool = False):
         """weight_dtype "fp8": the engine streams an OCP e4m3 copy of the Linear weights (per-output-row
         scales, quantised on the device at load); activations stay bf16.
         kv_dtype "fp8" (kv_cache_dtype): the KV cache holds OCP e4m3 bytes, element x stored as e4m3(clamp(x / scale, +-448)) with
@@ -134,6 +134,9 @@ class HipModel:
         the launch path; fork_row / evict_row and page_len are refused (sd_model_set_kv_dtype).
         page_len (a power of two >= 32): paged KV — the rows share a pool of `n_pages` pages (default: enough for every
         row to reach l_max) through a block table; `reserve(row, length)` / `release(row)` manage a row's pages.
+        cascade (cascade_attention): the launch path's attention reads keys that rows share (set_shared_prefix) once per group of
+        rows instead of once per row (sd_model_set_cascade); bf16 caches, dense or paged; every pass runs on the launch path;
+        kv_dtype fp8 and evict_row are refused.
         prefill_backend: how prompts (>= 96 positions per row) are absorbed — "auto" (rocBLAS where it serves the model, else
         the passes), "passes", "rocblas" or "native" (this library's GEMM over the packed weights); see set_prefill_backend."""
         if weight_dtype not in ("bf16", "fp8"):
@@ -143,8 +146,12 @@ class HipModel:
             raise ValueError(f"kv_dtype={kv_dtype!r} (kv_cache_dtype: bf16 or fp8)")
         if kv_dtype == "fp8" and (page_len is not None or os.environ.get("SPECDEC_PAGED_KV")):
             raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with page_len / SPECDEC_PAGED_KV")
+        if cascade and kv_dtype == "fp8":
+            raise ValueError("cascade_attention is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked)")
         self.weight_dtype = weight_dtype
         self.kv_dtype = kv_dtype
+        self.cascade = bool(cascade)
+        self._shared: dict = {}      # cascade: the table entries this object has written, row -> (leader, shared_len)
         self.kv_scales = (float(kv_scales[0]), float(kv_scales[1]))
         self.lib = _abi.load()
         self.cfg: ModelConfig = weights.config
@@ -215,6 +222,8 @@ class HipModel:
                 _abi.check(self.lib.sd_model_set_w12_form(self.handle, _ptr(copy[0]), copy[1].ctypes.data, classes, form), "sd_model_set_w12_form")
         if kv_dtype == "fp8":
             self.set_kv_dtype(kv_dtype, self.kv_scales)
+        if self.cascade:
+            _abi.check(self.lib.sd_model_set_cascade(self.handle, 1), "sd_model_set_cascade")
         self.batch, self.l_max = int(batch), (int(l_max) + 31) // 32 * 32  # whole 32-key blocks
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):
@@ -228,6 +237,25 @@ class HipModel:
         """sd_model_set_kv_dtype: between create and bind only (the constructor calls it; afterwards the library refuses)"""
         _abi.check(self.lib.sd_model_set_kv_dtype(self.handle, _abi.SD_FP8_E4M3 if kv_dtype == "fp8" else _abi.SD_BF16,
                                                   float(kv_scales[0]), float(kv_scales[1])), "sd_model_set_kv_dtype")
+
+    def set_shared_prefix(self, row: int, leader: int, shared_len: int, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """One entry of the cascade table, asynchronously on `stream` (sd_model_set_shared_prefix): positions [0, shared_len) of
+        `row` are bit-identical to row `leader`'s (fork_row made them so) and attention reads them from the leader's cache.
+        shared_len: a multiple of 32, at most the position of the row's next token; (row, row, 0) takes the row out of every group.
+        The leader's own entry must name itself. Raises before device work where the library refuses."""
+        if not self.cascade:
+            raise RuntimeError("set_shared_prefix needs an engine built with cascade=True (cascade_attention)")
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.sd_model_set_shared_prefix(self.handle, int(row), int(leader), int(shared_len), _stream(stream, self.device)),
+                       "sd_model_set_shared_prefix")
+        self._shared[int(row)] = (int(leader), int(shared_len))
+
+    def clear_shared_prefixes(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Every row out of every group, members before their roots (a row that members name cannot leave first)."""
+        for members in (True, False):
+            for row, (leader, n) in sorted(self._shared.items()):
+                if n and (leader != row) == members:
+                    self.set_shared_prefix(row, row, 0, stream)
 
     def _bind_dense(self) -> None:
         dev = self.device
@@ -342,6 +370,8 @@ class HipModel:
         positions >= n_pos - drop and the other rows keep their bits; the row's length afterwards is the caller's to lower by
         `drop`. Dense Llama caches only, drop a positive multiple of 8 below max_pos: anything else raises before device work."""
         self._no_fp8_kv("evict_row (context_window)")
+        if self.cascade:
+            raise RuntimeError("evict_row (context_window) is not available with cascade_attention (a shared prefix does not move)")
         with torch.cuda.device(self.device):
             _abi.check(self.lib.sd_model_kv_evict(self.handle, int(row), int(keep), int(drop), int(n_pos), _stream(stream, self.device)),
                        "sd_model_kv_evict")

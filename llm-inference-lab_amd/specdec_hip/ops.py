@@ -909,6 +909,25 @@ def attention_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: int, M: in
     return AttentionPlan(t, ns, (gx, gy, gz))
 
 
+class CascadePlan(NamedTuple):
+    tiles: int                    # as AttentionPlan: they shape the suffix workgroups
+    n_split: int
+    sets: int                     # groups of up to 4 stacked query tiles that B rows can form
+    p_split: int                  # workgroups per set over a group's shared keys
+    slots: int                    # partial tiles of the mode's workspace the launch addresses
+    grid: Tuple[int, int, int]    # (Hkv, B, tiles * n_split + sets * p_split)
+
+
+def attention_cascade_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: int, M: int, l_max: int, paged: int = 0) -> CascadePlan:
+    """The geometry of one cascade attention launch (csrc/attention_cascade.hip; sd_attention_cascade_plan), from the function the
+    launch itself consults. Arguments and environment as attention_plan. Host-only."""
+    out = [ctypes.c_int(0) for _ in range(8)]
+    _abi.check(_abi.load().sd_attention_cascade_plan(int(n_q_heads), int(n_kv_heads), int(head_dim), int(B), int(M), int(l_max), int(paged or 0),
+                                                     *(ctypes.byref(o) for o in out)), "sd_attention_cascade_plan")
+    t, ns, sets, ps, slots, gx, gy, gz = (int(o.value) for o in out)
+    return CascadePlan(t, ns, sets, ps, slots, (gx, gy, gz))
+
+
 class PersistPlan(NamedTuple):
     eligible: bool       # the model passes every static rule of the persistent forward
     max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)

@@ -44,6 +44,7 @@ from ..utils.interfaces import LanguageModel
 from .acceptance import device_rule, session_rule
 from .draft_confidence import check_session, session_confidence
 from . import logprobs as lpmod
+from . import cascade as cascmod
 from . import rolling
 from .step_options import StepOptions, resolve, row_options, spec_options, with_stage
 
@@ -70,6 +71,11 @@ _DEFAULTS: Dict[str, Any] = {
     # share_prefix: a row is forked over a prefix it has in common with a row already in the cache from this many tokens on
     # (rows whose whole prompts are equal are always forked)
     "min_shared_prefix": 32,
+    # cascade attention (core/cascade.py, csrc/attention_cascade.hip): off = the target re-reads a shared prompt per forked row. On
+    # (needs share_prefix / n): groups of rows that share at least cascade_min_shared positions read them once. The default threshold
+    # is the longest length profiles/cascade_attention.md measured, at which the mode had not stopped losing: lower it to try the mode
+    "cascade_attention": False,
+    "cascade_min_shared": cascmod.MIN_SHARED_DEFAULT,
     # the rolling context window (core/rolling.py): None = a row lives within prompt + max_tokens cache positions; W = its cache keeps
     # attention_sinks first positions and the most recent ones, never more than W, and generation length is no longer bound by the cache
     "context_window": None,
@@ -271,15 +277,17 @@ class SpeculativePipeline:
 
     # ------------------------------------------------------------------ runtime pieces
     def _runtime(self, batch: int, need_len: int, k: int, emit_mode: int, self_draft: bool = False, adaptive: bool = False,
-                 windowed: bool = False):
+                 windowed: bool = False, cascade: bool = False):
         """Engine instances (own KV caches over the shared weights) + the step loop object (`adaptive`: the loop whose
         rows carry their own K, a different captured step from the fixed-K loop of the same shape). windowed (context_window): the
         caches are sized by need_len itself, the window and its slack, and kept apart from those sized by prompt + budget."""
         key = (batch, emit_mode, self_draft, "window") if windowed else (batch, emit_mode, self_draft)
+        if cascade:     # cascade_attention: a target engine of its own (sd_model_set_cascade is decided before the bind); the draft's is plain
+            key += ("cascade",)
         rt = self._runtimes.get(key)
         if rt is None or rt["l_max"] < need_len:
             l_max = ((need_len if windowed else max(need_len, 256)) + 63) // 64 * 64
-            rt = {"l_max": l_max, "target": self.base_lm.new_engine(batch, l_max),
+            rt = {"l_max": l_max, "target": self.base_lm.new_engine(batch, l_max, cascade=True) if cascade else self.base_lm.new_engine(batch, l_max),
                   "draft": None if self_draft else self.draft_lm.new_engine(batch, l_max), "loops": {}}
             self._runtimes[key] = rt
         lkey = ("adaptive", k) if adaptive else k
@@ -321,7 +329,20 @@ class SpeculativePipeline:
         if rt["draft"] is not None:
             rt["draft"].forward(toks, zero, 0, skip_head=True, row0=b)
 
-    def _absorb_row(self, rt, b: int, seq: List[int], held: List[Optional[List[int]]], stats: Dict[str, Any]) -> None:
+    @staticmethod
+    def _cascade_push(rt, groups) -> None:
+        """cascade_attention: the table entries that changed, onto the target engine on the current stream — the stream of the fork
+        or prefill work around it, which the session orders before its next step"""
+        for row, leader, shared in groups.flush():
+            rt["target"].set_shared_prefix(row, leader, shared)
+
+    def _cascade_leave(self, rt, groups, b: int) -> None:
+        """before row b's slot is written: it leaves its group (a root hands the group to its lowest member)"""
+        if groups is not None:
+            groups.rewrite(b)
+            self._cascade_push(rt, groups)
+
+    def _absorb_row(self, rt, b: int, seq: List[int], held: List[Optional[List[int]]], stats: Dict[str, Any], groups=None) -> None:
         """share_prefix: KV of seq[:-1] into row b of both caches, computing as little of it as the other rows allow.
         held[j] is the token prefix whose KV row j's caches hold (None: nothing to rely on). The row with the longest common
         prefix c is the source: c == len(seq) - 1 (the same prompt) -> the row is forked from it (HipModel.fork_row, both
@@ -341,9 +362,15 @@ class SpeculativePipeline:
             if n > c:
                 best, c = j, n
         engines = [e for e in (rt["target"], rt["draft"]) if e is not None]
+        self._cascade_leave(rt, groups, b)
         if want and c == len(want) or c >= max(int(self.config.get("min_shared_prefix", 32)), 1):
             for e in engines:
                 e.fork_row(best, [b], c)
+            if groups is not None:      # cascade_attention: the target reads the forked positions through the source's root from now on
+                shared = groups.fork(b, best, c)
+                self._cascade_push(rt, groups)
+                stats["cascade_rows"] += 1 if shared else 0
+                stats["cascade_positions"] += shared
             if c < len(want):
                 toks = torch.tensor([want[c:]], dtype=torch.int32, device="cuda")
                 base = torch.tensor([c], dtype=torch.int32, device="cuda")
@@ -357,12 +384,12 @@ class SpeculativePipeline:
         held[b] = list(want)
 
     def _prefill(self, rt, rows: List[_Row], held: Optional[List[Optional[List[int]]]] = None,
-                 stats: Optional[Dict[str, Any]] = None) -> None:
+                 stats: Optional[Dict[str, Any]] = None, groups=None) -> None:
         """held (share_prefix): the session's record of what each row's caches hold; rows are then absorbed one by one, each
-        forked from an earlier one where their prompts allow (_absorb_row)."""
+        forked from an earlier one where their prompts allow (_absorb_row). groups (cascade_attention): the session's CascadeGroups."""
         if held is not None:
             for b, r in enumerate(rows):
-                self._absorb_row(rt, b, r.seq, held, stats)
+                self._absorb_row(rt, b, r.seq, held, stats, groups)
             return
         if stats is not None:
             stats["prefilled_rows"] += sum(1 for r in rows if len(r.seq) >= 2)
@@ -469,7 +496,8 @@ class SpeculativePipeline:
                       sampling: Union[None, Dict[str, Any], StepOptions] = None, step_limit: Optional[int] = None,
                       self_draft: bool = False, share_prefix: bool = False, grammar=None, sampling_params=None,
                       draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
-                      context_window: Optional[int] = None, attention_sinks: Optional[int] = None, **processors) -> "DecodeSession":
+                      context_window: Optional[int] = None, attention_sinks: Optional[int] = None,
+                      cascade_attention: Optional[bool] = None, **processors) -> "DecodeSession":
         """Prefill + device state for a batch of rows; `advance()` then runs one step at a time
         (generate / generate_batch drive it to completion, bench.py times exact step counts).
         share_prefix: rows that hold the same prompt, or a common prefix of >= min_shared_prefix tokens, pay for it once
@@ -481,7 +509,9 @@ class SpeculativePipeline:
         logprobs: per-token log-probs (True / 0: the chosen token's; 1..20: that many alternatives too), the bonus-token emit mode
         only; every row's token_info then stays parallel to its generated tokens.
         context_window / attention_sinks: the rolling context window (core/rolling.py), the bonus-token emit mode only: the caches
-        are sized by the window, not by max_tokens, and a row rolls whenever its next launches would not fit."""
+        are sized by the window, not by max_tokens, and a row rolls whenever its next launches would not fit.
+        cascade_attention (config key of the same name; needs share_prefix): the target's attention reads what forked rows share once
+        per group (core/cascade.py); groups of at least cascade_min_shared positions only."""
         if sampling_params is not None and sampling is not None:
             raise ValueError("sampling_params carries every request's own parameters: a `sampling` description cannot be given with it")
         session_rule(self, StepOptions(), emit_mode, self_draft, sampling_params, HipSpecDec.EMIT_BONUS)   # (its refusals come first)
@@ -492,12 +522,13 @@ class SpeculativePipeline:
         options = session_confidence(self, options, emit_mode, self_draft, draft_confidence, draft_min_k, HipSpecDec.EMIT_BONUS)
         options = lpmod.session_logprobs(self, options, emit_mode, self_draft, logprobs, HipSpecDec.EMIT_BONUS)
         window = rolling.session_window(self, context_window, attention_sinks, emit_mode, self_draft, share_prefix, HipSpecDec.EMIT_BONUS, prompts)
-        return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window)
+        return DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window,
+                             cascade=cascmod.asked(self, cascade_attention))
 
     def _decode(self, prompts: List[List[int]], max_tokens: int, emit_mode: int, step_limit: int,
-                options: Optional[StepOptions] = None, self_draft: bool = False, share_prefix: bool = False, window=None):
+                options: Optional[StepOptions] = None, self_draft: bool = False, share_prefix: bool = False, window=None, cascade: bool = False):
         t_start = time.time()
-        sess = DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window)
+        sess = DecodeSession(self, prompts, max_tokens, emit_mode, options, step_limit, self_draft, share_prefix, window=window, cascade=cascade)
         while sess.any_active():    # every row stops after `step_limit` steps of its own
             if not sess.advance():
                 break
@@ -695,6 +726,7 @@ class SpeculativePipeline:
         draft's, no bonus token, a zero-accept step emits one base token."""
         t_begin = time.time()
         rolling.refuse_single(self, kwargs)
+        cascmod.refuse_single(self, kwargs)
         call = resolve(self, [prompt], max_tokens, temperature, do_sample, kwargs, grammar=kwargs.pop("grammar", None),
                        sampling_params=kwargs.pop("sampling_params", None), share_prefix=kwargs.get("share_prefix"), n=kwargs.get("n", 1),
                        single=True, draft_confidence=kwargs.pop("draft_confidence", None), draft_min_k=kwargs.pop("draft_min_k", None),
@@ -728,7 +760,7 @@ class SpeculativePipeline:
                        share_prefix: bool = False, n: int = 1, grammar=None, sampling_params=None,
                        draft_confidence: Optional[float] = None, draft_min_k: Optional[int] = None, logprobs=None,
                        best_of: Optional[int] = None, context_window: Optional[int] = None, attention_sinks: Optional[int] = None,
-                       **kwargs) -> List[Dict[str, Any]]:
+                       cascade_attention: Optional[bool] = None, **kwargs) -> List[Dict[str, Any]]:
         """Batched speculative decoding (reference :1605-3931): base tokens + bonus token per
         step, step-count bound, no truncation to max_tokens. Rows are independent sequences.
 
@@ -785,7 +817,14 @@ class SpeculativePipeline:
         the step boundaries fall, hence on acceptance. batch_metrics carries evictions / evicted_positions. For the captured step
         with a draft model and a fixed K, in every select mode, with processors, grammars, sampling_params, logprobs and
         draft_confidence; refused with paged KV, GPT-2 models, the host loops, implementation='fake', medusa / eagle / self-draft,
-        adaptive K, share_prefix / n, generate(), and a prompt the window has no room for (prompts are not truncated)."""
+        adaptive K, share_prefix / n, generate(), and a prompt the window has no room for (prompts are not truncated).
+
+        cascade_attention=True (opt-in; config key cascade_attention; needs share_prefix or n > 1): the target's attention reads the
+        positions forked rows share once per group instead of once per row (csrc/attention_cascade.hip). Groups follow the forks of
+        share_prefix and hold rows that share at least cascade_min_shared positions (config key). Off by default: the merge order
+        differs from the plain kernel's, so results can differ at fp32-rounding level, and profiles/cascade_attention.md measured no
+        gain. batch_metrics carries cascade_rows / cascade_positions. Refused: what share_prefix refuses, kv_cache_dtype fp8,
+        context_window, adaptive K, medusa / eagle drafting and generate()."""
         if not prompts:
             return []
         m_best = lpmod.check_best_of(best_of, n)
@@ -796,6 +835,9 @@ class SpeculativePipeline:
         if m_best is not None:
             lpmod.check_best_of_mode(call.options)
         window = rolling.call_window(self, context_window, attention_sinks, call)
+        cascade = cascmod.asked(self, cascade_attention)
+        if cascade:
+            cascmod.check_session(self, call.share_prefix, call.self_draft, window is not None or context_window is not None, call.route == "step")
         if call.route == "fake":
             return [self.generate(p, max_tokens=max_tokens, temperature=temperature, do_sample=do_sample, **kwargs) for p in prompts]
         prompts, max_tokens = call.prompts, call.max_tokens
@@ -805,7 +847,8 @@ class SpeculativePipeline:
             rows, st = self._decode_host_policy(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens)
         else:
             rows, st = self._decode(call.ids, max_tokens, HipSpecDec.EMIT_BONUS, step_limit=max_tokens, options=call.options,
-                                    self_draft=call.self_draft, share_prefix=call.share_prefix, **({} if window is None else {"window": window}))
+                                    self_draft=call.self_draft, share_prefix=call.share_prefix, cascade=cascade,
+                                    **({} if window is None else {"window": window}))
         total_ms = st["total_ms"]
         tot_prop = sum(r.proposed for r in rows)
         tot_acc = sum(r.accepted for r in rows)
@@ -819,7 +862,7 @@ class SpeculativePipeline:
             # proposals that counted per row and step (K unless a row's k moves), and — confidence-gated draft length — the draft
             # forwards of the consumed steps that no row the host took tokens from needed
             "mean_k": tot_prop / max(sum(r.steps for r in rows), 1), "draft_forwards_skipped": st.get("draft_forwards_skipped", 0),
-            **{key: st.get(key, 0) for key in ("prefilled_rows", "forked_rows", "shared_positions")},
+            **{key: st.get(key, 0) for key in ("prefilled_rows", "forked_rows", "shared_positions", "cascade_rows", "cascade_positions")},
             **({} if window is None else {key: st.get(key, 0) for key in ("evictions", "evicted_positions")}),
         }
         out = []
@@ -850,7 +893,7 @@ class SpeculativePipeline:
                       temperature: Optional[float] = None, do_sample: Optional[bool] = None, share_prefix: bool = False, n: int = 1,
                       grammar=None, sampling_params=None, draft_confidence: Optional[float] = None,
                       draft_min_k: Optional[int] = None, logprobs=None, context_window: Optional[int] = None,
-                      attention_sinks: Optional[int] = None, **kwargs) -> List[Dict[str, Any]]:
+                      attention_sinks: Optional[int] = None, cascade_attention: Optional[bool] = None, **kwargs) -> List[Dict[str, Any]]:
         """Continuous batching over a list of prompts: `batch_size` rows decode together (generate_batch
         semantics per row) and a finished row's slot is handed to the next waiting prompt at once, instead of
         the reference harness' fixed batches that idle until their slowest row ends
@@ -866,7 +909,9 @@ class SpeculativePipeline:
         draft_confidence / draft_min_k: as generate_batch; the device keeps no per-row state for it, so an admission sets nothing.
         logprobs: as generate_batch (best_of is a generate_batch argument and is refused here).
         context_window / attention_sinks: as generate_batch; a prompt admitted to a slot starts with nothing evicted, and must fit the
-        window as the first ones must."""
+        window as the first ones must.
+        cascade_attention: as generate_batch; when a slot that leads a group is handed to a new prompt, the group's lowest remaining
+        row leads it from then on."""
         if not prompts:
             return []
         lpmod.refuse_best_of(kwargs)
@@ -875,13 +920,16 @@ class SpeculativePipeline:
                        logprobs=logprobs)
         prompts, ids, max_tokens, options = call.prompts, call.ids, call.max_tokens, call.options
         window = rolling.call_window(self, context_window, attention_sinks, call)
+        cascade = cascmod.asked(self, cascade_attention)
+        if cascade:
+            cascmod.check_session(self, call.share_prefix, call.self_draft, window is not None or context_window is not None)
         n_slots = max(1, min(int(batch_size), len(ids)))
         order = sorted(range(len(ids)), key=lambda i: -len(ids[i]))   # the longest prompts size the session
         first = order[:n_slots]
         waiting = [i for i in range(len(ids)) if i not in set(first)]
         t_start = time.time()
         sess = DecodeSession(self, [ids[i] for i in first], max_tokens, HipSpecDec.EMIT_BONUS, options.rows(first), max_tokens,
-                             share_prefix=call.share_prefix, **({} if window is None else {"window": window}))
+                             share_prefix=call.share_prefix, cascade=cascade, **({} if window is None else {"window": window}))
         owner: List[Optional[int]] = list(first)
         done: Dict[int, Any] = {}
         while len(done) < len(ids):
@@ -920,7 +968,8 @@ class SpeculativePipeline:
                                           "void_row_steps": sess.stats["void_row_steps"], "k": sess.k,
                                           "mean_k": sess.stats["proposed"] / max(sum(x.steps for x, _ in done.values()), 1),
                                           "draft_forwards_skipped": sess.stats.get("draft_forwards_skipped", 0),
-                                          **{key: sess.stats[key] for key in ("prefilled_rows", "forked_rows", "shared_positions")}}})
+                                          **{key: sess.stats[key] for key in ("prefilled_rows", "forked_rows", "shared_positions", "cascade_rows",
+                                                                              "cascade_positions")}}})
         return out
 
     def draft_agreement(self, text_or_ids: PromptLike, temperature: float = 1.0, chunk: int = 256) -> Dict[str, Any]:
@@ -1010,7 +1059,7 @@ class DecodeSession:
 
     def __init__(self, pipe: SpeculativePipeline, prompts: List[List[int]], max_tokens: int, emit_mode: int,
                  options: Optional[StepOptions] = None, step_limit: Optional[int] = None, self_draft: bool = False, share_prefix: bool = False,
-                 window: Optional[rolling.Window] = None):
+                 window: Optional[rolling.Window] = None, cascade: bool = False):
         self.pipe, self.max_tokens, self.emit_mode = pipe, max_tokens, emit_mode
         self.options = o = options if options is not None else StepOptions()      # what the step does: greedy, sampled bonus token, spec
         other_step = self_draft or pipe._fake or bool(getattr(pipe.controller, "per_row", False))     # no draft model, or no fixed K
@@ -1061,8 +1110,10 @@ class DecodeSession:
         self.window = rolling.check_session(window, other_step, emit_mode == HipSpecDec.EMIT_BONUS, share_prefix, self.k)
         if self.window is not None:
             self.need = self.window.l_max
+        if cascade:     # cascade_attention: refused before any device work where the target cannot take the cascade launch
+            cascmod.check_session(pipe, share_prefix, self_draft, self.window is not None)
         self.rt, self.loop = pipe._runtime(len(self.rows), self.need, self.k, emit_mode, self.self_draft, adaptive=self.per_row,
-                                           **({} if self.window is None else {"windowed": True}))
+                                           **({} if self.window is None else {"windowed": True}), **({"cascade": True} if cascade else {}))
         # positions a row may use: the cache rows and both models' position tables (a windowed row's positions are its cache's:
         # they stay below the window, which is within both tables, and nothing here stops it)
         self.pos_limit = min(self.rt["l_max"], pipe.base_lm.config.max_pos,
@@ -1079,12 +1130,18 @@ class DecodeSession:
                 e.release(b)
         self._fresh: set = set()                # rows whose slot was handed to a new sequence (admit)
         self.stats = {"steps": 0, "resyncs": 0, "proposed": 0, "accepted": 0, "device_ms": 0.0, "void_row_steps": 0,
-                      "prefilled_rows": 0, "forked_rows": 0, "shared_positions": 0}
+                      "prefilled_rows": 0, "forked_rows": 0, "shared_positions": 0, "cascade_rows": 0, "cascade_positions": 0}
         if self.window is not None:
             self.stats.update(evictions=0, evicted_positions=0)
         # share_prefix: per row, the tokens whose KV both caches hold at positions [0, len) — None: not to be relied on
         self._held: Optional[List[Optional[List[int]]]] = [None] * len(self.rows) if share_prefix else None
-        pipe._prefill(self.rt, self.rows, self._held, self.stats)
+        # cascade_attention: which rows read which row's prefix (None: off). The engine may come from an earlier session: every entry is
+        # cleared first, on the stream of the prefill that follows
+        self._groups = None
+        if cascade:
+            self._groups = cascmod.CascadeGroups(len(self.rows), int(pipe.config.get("cascade_min_shared", cascmod.MIN_SHARED_DEFAULT)))
+            self.rt["target"].clear_shared_prefixes()
+        pipe._prefill(self.rt, self.rows, self._held, self.stats, self._groups)
         self.loop.join_current_stream()
         for b, r in enumerate(self.rows):
             pipe._set_row(self.loop, b, r)
@@ -1262,8 +1319,9 @@ class DecodeSession:
                 self._fresh.discard(b)
             if what == "resync" and r.active:      # a new sequence, or the host rules rewrote the row: rebuild its caches
                 if fresh and self._held is not None:
-                    pipe._absorb_row(rt, b, r.seq, self._held, self.stats)    # forked from a row the session holds, if one fits
+                    pipe._absorb_row(rt, b, r.seq, self._held, self.stats, self._groups)    # forked from a row the session holds, if one fits
                 else:
+                    pipe._cascade_leave(rt, self._groups, b)
                     for e in self._engines:
                         e.unshare(b)               # (pages shared with other rows are never written: the rebuild gets fresh ones)
                     if r.evicted:                  # a rolled row is rebuilt from the tokens its cache still holds, at their cache positions

@@ -83,9 +83,13 @@ class HipLM(LanguageModel):
     def __init__(self, weights: W.ModelWeights, tokenizer: Any = None, name: Optional[str] = None,
                  max_len: int = 1024, batch: int = 1, device: str = "cuda", weight_dtype: str = "bf16",
                  kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto",
-                 kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0)):
+                 kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade_attention: bool = False):
         if prefill_backend not in _abi.PREFILL_BACKENDS:
             raise ValueError(f"prefill_backend={prefill_backend!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
+        if cascade_attention and kv_dtype == "fp8":
+            raise ValueError("cascade_attention is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked)")
+        # engines created by this model read keys that rows share once per group (HipModel cascade / set_shared_prefix)
+        self.cascade_attention = bool(cascade_attention)
         if not torch.cuda.is_available():
             raise RuntimeError("HipLM needs a GPU: this build has no CPU compute path")
         self._device = torch.device(device if device != "auto" else "cuda")
@@ -115,14 +119,17 @@ class HipLM(LanguageModel):
             raise ValueError(f"kv_cache_dtype={kv_dtype!r} (bf16 or fp8)")
         if kv_dtype == "fp8" and self.kv_page_len is not None:
             raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with kv_page_len")
+        if kv_dtype == "fp8" and self.cascade_attention:
+            raise ValueError("kv_cache_dtype fp8 is not available with cascade_attention (an e4m3 cache is not forked)")
         self.kv_cache_dtype, self.kv_scales = kv_dtype, (float(kv_scales[0]), float(kv_scales[1]))
         self._model, self._cached = None, []
 
-    def new_engine(self, batch: int, l_max: int) -> HipModel:
-        """A forward instance with its own KV cache over the shared weights."""
+    def new_engine(self, batch: int, l_max: int, cascade: Optional[bool] = None) -> HipModel:
+        """A forward instance with its own KV cache over the shared weights. cascade: None = this model's cascade_attention."""
         return HipModel(self.weights, batch=batch, l_max=l_max, device=self._device, weight_dtype=self.weight_dtype,
                         page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend,
-                        kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales)
+                        kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales,
+                        cascade=self.cascade_attention if cascade is None else bool(cascade))
 
     def _engine(self, batch: int, need_len: int) -> HipModel:
         m = self._model

@@ -69,6 +69,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--n", type=int, default=1,
                     help="n completions of the prompt as n rows of one generate_batch call: the prompt is prefilled once and the other "
                          "rows are forked from it (implies --share-prefix); they differ under --spec-sampling (a Philox stream per row)")
+    ap.add_argument("--cascade-attention", action="store_true",
+                    help="with --share-prefix / --n: the target's attention reads what the forked rows share once per group "
+                         "(cascade_attention=True; groups of at least the config key cascade_min_shared positions)")
     ap.add_argument("--share-prefix", action="store_true",
                     help="decode through generate_batch with share_prefix=True (rows pay for an equal prompt or a common prefix once)")
     ap.add_argument("--repetition-penalty", type=float, help="divide (multiply, when negative) the logits of tokens in the prompt or "
@@ -217,7 +220,7 @@ def main(argv=None) -> int:
         lp = args.logprobs is not None or args.best_of is not None
         roll = args.context_window is not None
         batch = (roll or lp or conf or args.spec_sampling or args.share_prefix or args.n != 1 or row_params is not None
-                 or pp.get("backend") == "device")
+                 or pp.get("backend") == "device" or args.cascade_attention)
         proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                                   ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
         if args.regex is not None:
@@ -228,6 +231,8 @@ def main(argv=None) -> int:
             proc.update(draft_confidence=args.draft_confidence, draft_min_k=args.draft_min_k)
         if lp:         # per-token log-probs inside the captured step; best_of ranks the rows by their sum
             proc.update(logprobs=args.logprobs, best_of=args.best_of)
+        if args.cascade_attention:
+            proc["cascade_attention"] = True
         if roll:       # the rolling context window: the caches are sized by it, rows roll at the session's repair point
             proc.update(context_window=args.context_window, attention_sinks=args.attention_sinks)
         if batch:      # generate_batch modes (a correction / bonus token every step): a batch of the prompt's --n rows

@@ -101,7 +101,9 @@ def cmd_run(args: argparse.Namespace) -> int:
         raise SystemExit("--attention-sinks belongs to --context-window")
     if roll:     # the rolling context window (a generate_batch mode): caches sized by the window, rows roll at the repair point
         proc.update(context_window=args.context_window, attention_sinks=args.attention_sinks)
-    if roll or lp or conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
+    if args.cascade_attention:
+        proc["cascade_attention"] = True
+    if roll or lp or conf or spec or lossy or args.share_prefix or args.n != 1 or row_params is not None or args.cascade_attention:  # generate_batch modes (speculative sampling inside the captured step; --n rows of the prompt)
         rs = pipe.generate_batch([args.prompt], max_tokens=args.max_tokens, share_prefix=args.share_prefix, n=args.n, **proc)
         res = {**pipe._sysinfo(), **rs[0]}
         for i, x in enumerate(rs[1:], 1):
@@ -184,6 +186,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--n", type=int, default=1, help="n completions of the prompt: n rows of one generate_batch call, the prompt prefilled "
                                                      "once and forked into the others (implies --share-prefix)")
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
+    pr.add_argument("--cascade-attention", action="store_true",
+                    help="with --share-prefix / --n: the target's attention reads what the forked rows share once per group")
     pr.add_argument("prompt", type=str)
     pr.set_defaults(func=cmd_run)
     return p
