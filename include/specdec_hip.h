@@ -573,6 +573,22 @@ int sd_model_prefill_backend(const sd_model* m);
  * positions per row. -1 for another value. */
 int64_t sd_model_prefill_count(const sd_model* m, int backend);
 
+/* The attention of a prompt absorbed by a GEMM prefill backend (rocBLAS or native), per chunk of <= 512 positions and layer:
+ *   SD_PREFILL_ATTN_PASSES  the default: sub-passes of 128 query positions through the decode / verify attention kernel
+ *   SD_PREFILL_ATTN_TILED   one launch of the tiled prompt kernel (csrc/attention_prefill.hip): a workgroup is a kv head and a tile
+ *                           of 16 or 32 query positions x all of its query heads; the key blocks are staged through LDS once per
+ *                           workgroup and only the blocks up to the tile's last position are walked
+ * Prompts that take the 128-token passes (under 96 positions, logits asked for, stream capture, adaptive K) are not affected.
+ * The mode is kept over binds. Refused (nonzero, with sd_last_error): an unknown value; TILED for an fp8 (e4m3) kv dtype, a
+ * head_dim other than 64 or 128, a non-Llama model, or more than 8 query heads per kv head. sd_model_set_kv_dtype(SD_FP8_E4M3)
+ * on a model in the tiled mode is refused likewise. Additive (SD_ABI_VERSION stays 1). */
+enum sd_prefill_attention { SD_PREFILL_ATTN_PASSES = 0, SD_PREFILL_ATTN_TILED = 1 };
+int sd_model_set_prefill_attention(sd_model* m, int mode);
+/* The configured mode (enum sd_prefill_attention); -1 for a NULL model. */
+int sd_model_prefill_attention(const sd_model* m);
+/* Launches of the tiled prompt kernel since the bind: one per chunk and layer. -1 for a NULL model. */
+int64_t sd_model_prefill_tiled_launches(const sd_model* m);
+
 /* Rows [row0, row0+n) of one of the workspace buffers the last pass left behind (bf16, asynchronous copy on `stream`):
  * which = 0 residual stream [d_model] (= sd_model_hidden_rows), 1 q after RoPE [Hq*D], 2 attention rows [Hq*D],
  * 3 MLP activation [d_ff]; all of the LAST layer. After a prompt absorbed by a GEMM prefill backend (rocBLAS or native) the
@@ -657,6 +673,17 @@ int sd_attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M,
  * l_max not a multiple of 32 or B above 128. */
 int sd_attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int* tiles,
                               int* n_split, int* sets, int* p_split, int* slots, int* grid_x, int* grid_y, int* grid_z);
+
+/* The same for the tiled prompt kernel (sd_model_set_prefill_attention) over one chunk of Mc <= 512 positions of one cache row:
+ * *pt = query positions per tile, 32 where 32 * Hq / Hkv <= 128 and ceil(Mc / 32) * Hkv >= 256 workgroups, else 16;
+ * *rows_per_wg = pt * Hq / Hkv rounded up to 16, the stacked query rows of a workgroup; *waves = rows_per_wg / 16, the waves that own
+ * rows (the launch has 4 waves, 8 when more than 4 own rows: the others only stage); *tiles = ceil(Mc / pt); *n_split = workgroups
+ * per tile, always 1 (a tile's keys are walked by one workgroup and nothing is merged); *lds_bytes = dynamic LDS of a workgroup
+ * (two buffers of K [64][D + 8] and V^T [D][72] bf16). The grid is (Hkv, *tiles). Host-only, additive (SD_ABI_VERSION stays 1).
+ * Refused (nonzero): a NULL output, head_dim not 64 / 128, Hq % Hkv, more than 8 query heads per kv head, Mc outside 1 .. 512,
+ * l_max not a multiple of 8, pages not 32 * 2^n positions or l_max not whole pages. */
+int sd_attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int paged, int* pt, int* rows_per_wg,
+                              int* waves, int* tiles, int* n_split, int* lds_bytes);
 
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *

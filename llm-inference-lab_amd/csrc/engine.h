@@ -63,6 +63,8 @@ struct sd_model {
   void* prefill_ws = nullptr;              // lazily allocated workspace of the GEMM prefill path (csrc/prefill_gemm.hip)
   int prefill_backend = SD_PREFILL_AUTO;   // sd_model_set_prefill_backend (a bind resets it)
   int64_t prefill_count[4] = {0, 0, 0, 0}; // prompt rows absorbed per backend since the bind (index: enum sd_prefill_backend)
+  int prefill_attention = SD_PREFILL_ATTN_PASSES;   // sd_model_set_prefill_attention: the attention of a GEMM-prefill chunk (kept over binds)
+  int64_t prefill_tiled_launches = 0;      // launches of the tiled prompt-attention kernel since the bind (one per layer and chunk)
   sd::NativePlan native_plan;              // row-block tables of the native prefill GEMM (built at its first use)
   sd::PrefillRows prefill_rows;            // the last GEMM-prefill chunk's rows in prefill_ws (sd_model_prefill_rows), valid while
   int prefill_mc = 0;                      // prefill_mc > 0: cleared by a bind and by every pass that is not such a chunk

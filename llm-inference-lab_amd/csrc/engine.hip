@@ -323,10 +323,12 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
     pm.scales = m->w8() ? m->scales.data() : nullptr;
     pm.plan = &m->native_plan;
   }
+  pm.attn_tiled = m->prefill_attention == SD_PREFILL_ATTN_TILED;
   for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
     const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
     PrefillRows rows;
     if (int rc = prefill_gemm_chunk(pm, tokens + m0, pos_base_row, pos_off + m0, row, mc, m->prefill_ws, &rows, st)) return rc;
+    if (pm.attn_tiled) m->prefill_tiled_launches += c.n_layers;
     // the chunk's last <= 128 positions go where every other pass leaves them: the residual rows (hidden rows, the head) and
     // the last layer's q, attention and activation rows (sd_model_debug_rows)
     const int keep = mc < 128 ? mc : 128;

@@ -240,6 +240,30 @@ int attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, i
 size_t attention_cascade_ws_bytes(int head_dim, int slots);   // the partial tiles (the counters are the caller's to add)
 int launch_attention_cascade(const AttnArgs& a, hipStream_t st);
 int launch_cascade_set_entry(int32_t* share, int row, int leader, int shared_len, hipStream_t st);
+// Prompt attention (attention_prefill.hip): the attention of one GEMM-prefill chunk of Mc <= 512 positions of ONE cache row as one
+// launch, K / V staged through LDS once per tile of query rows (sd_model_set_prefill_attention). A kernel of its own with its own
+// arguments: Mc does not fit AttnArgs' 8 bits.
+struct PrefillAttnArgs {
+  const void* q;                // bf16 [Mc][n_q_heads * head_dim]
+  const void* k_cache;          // dense: the row's slab [n_kv_heads][l_max][head_dim]; paged: the layer's page pool
+  const void* v_cache;          // dense: [n_kv_heads][head_dim][l_max]; paged: the pool
+  void* out;                    // bf16 [Mc][n_q_heads * head_dim]
+  const int32_t* pos_base;      // the row's entry: query 0 sits at position pos_base[0] + pos_off
+  const int32_t* block_table;   // paged: the row's table (null = dense)
+  int pos_off, l_max, Mc;
+  int n_q_heads, n_kv_heads, head_dim, page_shift;
+  int pt;                       // set by launch_attention_prefill
+  float scale;
+};
+// Its geometry, from dimensions alone (launch_attention_prefill consults it, sd_attention_prefill_plan reports it): pt = query
+// positions per tile (16 or 32), rows_per_wg = 16 * waves >= pt * G stacked query rows, waves = waves that own rows (the launch has
+// threads / 64 = 4 or 8: the others only stage), tiles = ceil(Mc / pt), n_split = workgroups per tile (always 1), lds_bytes = dynamic
+// LDS of a workgroup; grid = (n_kv_heads, tiles). page_shift < 0: a dense cache.
+struct PrefillAttnPlan { int pt, rows_per_wg, waves, threads, tiles, n_split, lds_bytes; };
+int attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int page_shift, PrefillAttnPlan& plan);
+// The one rule that admits a model to the mode: null, or why not
+const char* attention_prefill_refusal(int arch, int head_dim, int n_q_heads, int n_kv_heads, bool kv8);
+int launch_attention_prefill(const PrefillAttnArgs& a, hipStream_t st);
 
 // ---- small kernels (misc.hip) -------------------------------------------------------
 struct EmbedArgs {

@@ -178,6 +178,7 @@ static int bind_caches(sd_model* m, void* k, void* v, int B, int Lmax, const int
   m->prefill_backend = SD_PREFILL_AUTO;
   m->prefill_mc = 0;
   for (int64_t& n : m->prefill_count) n = 0;
+  m->prefill_tiled_launches = 0;
   if (int rc = carve_workspace(m, workspace)) return rc;
   return m->cascade ? setup_cascade(m) : 0;
 }
@@ -303,6 +304,8 @@ extern "C" int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, floa
   SD_REQUIRE(k_scale > 0.f && v_scale > 0.f && k_scale - k_scale == 0.f && v_scale - v_scale == 0.f,
              "model_set_kv_dtype: kv scales must be positive and finite (got %g, %g)", static_cast<double>(k_scale), static_cast<double>(v_scale));
   SD_REQUIRE(dtype != SD_FP8_E4M3 || !m->cascade, "model_set_kv_dtype: an fp8 (e4m3) kv dtype is not available with cascade attention (an e4m3 cache is not forked)");
+  SD_REQUIRE(dtype != SD_FP8_E4M3 || m->prefill_attention != SD_PREFILL_ATTN_TILED, "model_set_kv_dtype: %s",
+             attention_prefill_refusal(m->cfg.arch, m->cfg.head_dim, m->cfg.n_heads, m->cfg.n_kv_heads, true));
   m->kv8 = dtype == SD_FP8_E4M3;
   m->kv_scale[0] = m->kv8 ? k_scale : 1.0f;
   m->kv_scale[1] = m->kv8 ? v_scale : 1.0f;
@@ -517,6 +520,22 @@ extern "C" int sd_model_set_prefill_backend(sd_model* m, int backend) {
 }
 
 extern "C" int sd_model_prefill_backend(const sd_model* m) { return m ? m->prefill_backend : -1; }
+
+extern "C" int sd_model_set_prefill_attention(sd_model* m, int mode) {
+  clear_error();
+  SD_REQUIRE(m, "set_prefill_attention: NULL model");
+  SD_REQUIRE(mode == SD_PREFILL_ATTN_PASSES || mode == SD_PREFILL_ATTN_TILED, "set_prefill_attention: unknown mode %d", mode);
+  if (mode == SD_PREFILL_ATTN_TILED) {
+    const char* why = attention_prefill_refusal(m->cfg.arch, m->cfg.head_dim, m->cfg.n_heads, m->cfg.n_kv_heads, m->kv8 != 0);
+    SD_REQUIRE(!why, "set_prefill_attention: %s", why);
+  }
+  m->prefill_attention = mode;
+  return 0;
+}
+
+extern "C" int sd_model_prefill_attention(const sd_model* m) { return m ? m->prefill_attention : -1; }
+
+extern "C" int64_t sd_model_prefill_tiled_launches(const sd_model* m) { return m ? m->prefill_tiled_launches : -1; }
 
 extern "C" int64_t sd_model_prefill_count(const sd_model* m, int backend) {
   if (!m || backend < SD_PREFILL_PASSES || backend > SD_PREFILL_NATIVE) return -1;

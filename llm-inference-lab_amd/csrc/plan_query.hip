@@ -1,5 +1,5 @@
 // Plan queries that need no GPU: which kernel instance, work split or refusal a shape gets, asked from dimensions alone
-// (sd_prefill_plan, sd_prefill_plan_tables, sd_gemm_plan, sd_gemv_variant, sd_gemv_instance, sd_attention_plan, sd_persist_plan) or from a model's
+// (sd_prefill_plan, sd_prefill_plan_tables, sd_gemm_plan, sd_gemv_variant, sd_gemv_instance, sd_attention_plan, sd_attention_prefill_plan, sd_persist_plan) or from a model's
 // (sd_model_matrix_shape). Each asks the function the launch itself consults; nothing is enqueued. Host-side C++ behind the C-ABI.
 
 #include <stdarg.h>
@@ -204,6 +204,22 @@ extern "C" int sd_attention_cascade_plan(int n_q_heads, int n_kv_heads, int head
   if (int rc = attention_cascade_plan(n_q_heads, n_kv_heads, head_dim, B, M, l_max, page_shift, pl)) return rc;
   *tiles = pl.tiles; *n_split = pl.n_split; *sets = pl.sets; *p_split = pl.p_split; *slots = pl.slots;
   *grid_x = pl.grid_x; *grid_y = pl.grid_y; *grid_z = pl.grid_z;
+  return 0;
+}
+
+extern "C" int sd_attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int paged, int* pt, int* rows_per_wg,
+                                         int* waves, int* tiles, int* n_split, int* lds_bytes) {
+  clear_error();
+  SD_REQUIRE(pt && rows_per_wg && waves && tiles && n_split && lds_bytes, "attention_prefill_plan: NULL argument");
+  int page_shift = -1;   // as sd_attention_plan
+  if (paged != 0) {
+    page_shift = 0;
+    while (page_shift < 30 && (1 << page_shift) < paged) ++page_shift;
+    if (paged < 0 || (1 << page_shift) != paged) page_shift = 0;
+  }
+  PrefillAttnPlan pl{};
+  if (int rc = attention_prefill_plan(n_q_heads, n_kv_heads, head_dim, Mc, l_max, page_shift, pl)) return rc;
+  *pt = pl.pt; *rows_per_wg = pl.rows_per_wg; *waves = pl.waves; *tiles = pl.tiles; *n_split = pl.n_split; *lds_bytes = pl.lds_bytes;
   return 0;
 }
 

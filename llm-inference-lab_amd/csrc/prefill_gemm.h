@@ -94,6 +94,9 @@ struct PrefillModel {
   const void* const* packed = nullptr;    // native: per matrix (4 per layer + lm_head, packing order)
   const float* const* scales = nullptr;   // native, fp8 storage: fp32 row scales per matrix (else null)
   const NativePlan* plan = nullptr;
+  // step 2 of the layer loop: 0 = sub-passes of 128 query positions through launch_attention, 1 = one launch of the tiled prompt
+  // kernel per chunk (csrc/attention_prefill.hip; sd_model_set_prefill_attention)
+  int attn_tiled = 0;
 };
 
 bool prefill_gemm_available();                               // rocBLAS could be opened (dlopen at first use) and a handle created

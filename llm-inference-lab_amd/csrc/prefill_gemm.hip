@@ -12,7 +12,8 @@
 //                                 to the fp32 products: RoPE + q store + in-place K / V^T append, residual add, SwiGLU — so the
 //                                 bf16 rounding points are those of every other path (RoPE on the fp32 sum, rounded once)
 //   * attention                 — the existing MFMA attention kernel, in sub-passes of 128 query positions over the cache the QKV
-//                                 epilogue has just appended to (causal by position)
+//                                 epilogue has just appended to (causal by position); or, by sd_model_set_prefill_attention, the
+//                                 tiled prompt kernel of csrc/attention_prefill.hip, one launch per chunk
 // Sums differ from the GEMV path in fp32 summation order only; tests/test_hip_prefill_gemm_gpu.py holds the chunked path against the
 // 128-token passes (next tokens, logits, K / V rows).
 //
@@ -297,29 +298,49 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
     a1.v_cache = vc;
     if (int rc = launch_epilogue_rows<EPI_QKV_ROPE>(a1, Y, Mc, HqD * 2, st)) return rc;
 
-    // 2. attention of the chunk's positions over the cache they have just been appended to, 128 query positions per launch
-    for (int s0 = 0; s0 < Mc; s0 += 128) {
-      AttnArgs at{};
-      at.q = q + static_cast<size_t>(s0) * HqD;
+    // 2. attention of the chunk's positions over the cache they have just been appended to: the tiled prompt kernel in one launch,
+    // or 128 query positions per launch of the decode-shaped one
+    if (m.attn_tiled) {
+      PrefillAttnArgs at{};
+      at.q = q;
       at.k_cache = kc;
       at.v_cache = vc;
-      at.out = attn + static_cast<size_t>(s0) * HqD;
+      at.out = attn;
       at.pos_base = pos_base_row;
-      at.pos_off = pos_off + s0;
-      at.B = 1;
-      at.M = (Mc - s0 < 128) ? Mc - s0 : 128;
+      at.block_table = bt;
+      at.pos_off = pos_off;
+      at.l_max = m.Lmax;
+      at.Mc = Mc;
       at.n_q_heads = Hq;
       at.n_kv_heads = Hkv;
       at.head_dim = D;
-      at.l_max = m.Lmax;
-      at.scale = 1.0f / sqrtf(static_cast<float>(D));
-      if (m.kv8) { at.kv8 = 1; at.scale *= m.kv_scale[0]; at.v_scale = m.kv_scale[1]; }
-      at.split_ws = m.attn_ws;
-      at.split_cnt = m.attn_cnt;
-      at.split_slots = kAttnSplitSlots;
-      at.block_table = bt;
       at.page_shift = m.page_shift;
-      if (int rc = launch_attention(at, st)) return rc;
+      at.scale = 1.0f / sqrtf(static_cast<float>(D));
+      if (int rc = launch_attention_prefill(at, st)) return rc;
+    } else {
+      for (int s0 = 0; s0 < Mc; s0 += 128) {
+        AttnArgs at{};
+        at.q = q + static_cast<size_t>(s0) * HqD;
+        at.k_cache = kc;
+        at.v_cache = vc;
+        at.out = attn + static_cast<size_t>(s0) * HqD;
+        at.pos_base = pos_base_row;
+        at.pos_off = pos_off + s0;
+        at.B = 1;
+        at.M = (Mc - s0 < 128) ? Mc - s0 : 128;
+        at.n_q_heads = Hq;
+        at.n_kv_heads = Hkv;
+        at.head_dim = D;
+        at.l_max = m.Lmax;
+        at.scale = 1.0f / sqrtf(static_cast<float>(D));
+        if (m.kv8) { at.kv8 = 1; at.scale *= m.kv_scale[0]; at.v_scale = m.kv_scale[1]; }
+        at.split_ws = m.attn_ws;
+        at.split_cnt = m.attn_cnt;
+        at.split_slots = kAttnSplitSlots;
+        at.block_table = bt;
+        at.page_shift = m.page_shift;
+        if (int rc = launch_attention(at, st)) return rc;
+      }
     }
 
     // 3. output projection + residual

@@ -29,6 +29,9 @@ SD_PREFILL_AUTO, SD_PREFILL_PASSES, SD_PREFILL_ROCBLAS, SD_PREFILL_NATIVE = rang
 # enum sd_accept_rule
 SD_ACCEPT_OFF, SD_ACCEPT_TYPICAL, SD_ACCEPT_TOPK_AGREE = range(3)
 ACCEPT_RULES = {"typical": SD_ACCEPT_TYPICAL, "topk_agree": SD_ACCEPT_TOPK_AGREE}
+# enum sd_prefill_attention
+SD_PREFILL_ATTN_PASSES, SD_PREFILL_ATTN_TILED = range(2)
+PREFILL_ATTENTION = {"passes": SD_PREFILL_ATTN_PASSES, "tiled": SD_PREFILL_ATTN_TILED}
 PREFILL_BACKENDS = {"auto": SD_PREFILL_AUTO, "passes": SD_PREFILL_PASSES, "rocblas": SD_PREFILL_ROCBLAS, "native": SD_PREFILL_NATIVE}
 
 _c_void_p = ctypes.c_void_p
@@ -144,6 +147,10 @@ SIGNATURES = {
     "sd_model_set_prefill_backend": (_c_int, [_c_void_p, _c_int]),
     "sd_model_prefill_backend": (_c_int, [_c_void_p]),
     "sd_model_prefill_count": (_c_i64, [_c_void_p, _c_int]),
+    "sd_model_set_prefill_attention": (_c_int, [_c_void_p, _c_int]),
+    "sd_model_prefill_attention": (_c_int, [_c_void_p]),
+    "sd_model_prefill_tiled_launches": (_c_i64, [_c_void_p]),
+    "sd_attention_prefill_plan": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_int)] * 6),
     "sd_model_debug_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "sd_model_prefill_rows": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "sd_prefill_plan": (_c_int, [_c_int] * 10 + [ctypes.POINTER(_c_int)] * 8 + [ctypes.c_char_p, _c_size, ctypes.c_char_p, _c_size]),

@@ -115,6 +115,16 @@ def _prefill_backend_id(name: str) -> int:
     return _abi.PREFILL_BACKENDS[name]
 
 
+_PREFILL_ATTN_NAMES = {v: k for k, v in _abi.PREFILL_ATTENTION.items()}
+
+
+def _prefill_attention_id(name: str) -> int:
+    """enum sd_prefill_attention of a mode name; raises before any device work"""
+    if name not in _abi.PREFILL_ATTENTION:
+        raise ValueError(f"prefill_attention={name!r} (one of {', '.join(_abi.PREFILL_ATTENTION)})")
+    return _abi.PREFILL_ATTENTION[name]
+
+
 def prefill_backends_available() -> List[str]:
     """names of the prefill backends this process can use"""
     lib = _abi.load()
@@ -126,7 +136,8 @@ class HipModel:
 
     def __init__(self, weights: ModelWeights, batch: int, l_max: int, device: Optional[torch.device] = None,
                  weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None,
-                 prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade: bool = False):
+                 prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade: bool = False,
+                 prefill_attention: str = "passes"):
         """weight_dtype "fp8": the engine streams an OCP e4m3 copy of the Linear weights (per-output-row
         scales, quantised on the device at load); activations stay bf16.
         kv_dtype "fp8" (kv_cache_dtype): the KV cache holds OCP e4m3 bytes, element x stored as e4m3(clamp(x / scale, +-448)) with
@@ -138,10 +149,13 @@ class HipModel:
         rows instead of once per row (sd_model_set_cascade); bf16 caches, dense or paged; every pass runs on the launch path;
         kv_dtype fp8 and evict_row are refused.
         prefill_backend: how prompts (>= 96 positions per row) are absorbed — "auto" (rocBLAS where it serves the model, else
-        the passes), "passes", "rocblas" or "native" (this library's GEMM over the packed weights); see set_prefill_backend."""
+        the passes), "passes", "rocblas" or "native" (this library's GEMM over the packed weights); see set_prefill_backend.
+        prefill_attention: the attention of a GEMM-prefilled chunk — "passes" (128 query positions per launch of the decode-shaped
+        kernel) or "tiled" (one launch of the prompt kernel per chunk, csrc/attention_prefill.hip); see set_prefill_attention."""
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype={weight_dtype!r} (bf16 or fp8)")
         _prefill_backend_id(prefill_backend)
+        _prefill_attention_id(prefill_attention)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype={kv_dtype!r} (kv_cache_dtype: bf16 or fp8)")
         if kv_dtype == "fp8" and (page_len is not None or os.environ.get("SPECDEC_PAGED_KV")):
@@ -232,6 +246,8 @@ class HipModel:
             self._bind_dense()
         if prefill_backend != "auto":
             self.set_prefill_backend(prefill_backend)
+        if prefill_attention != "passes":
+            self.set_prefill_attention(prefill_attention)
 
     def set_kv_dtype(self, kv_dtype: str, kv_scales: Sequence[float] = (1.0, 1.0)) -> None:
         """sd_model_set_kv_dtype: between create and bind only (the constructor calls it; afterwards the library refuses)"""
@@ -507,6 +523,19 @@ class HipModel:
     @property
     def prefill_backend(self) -> str:
         return _PREFILL_NAMES[self.lib.sd_model_prefill_backend(self.handle)]
+
+    def set_prefill_attention(self, name: str) -> None:
+        """How the attention of a GEMM-prefilled chunk runs (sd_model_set_prefill_attention): "passes" or "tiled". Kept over binds.
+        "tiled" is refused for kv_dtype fp8, head_dim 32, GPT-2 models and more than 8 query heads per kv head."""
+        _abi.check(self.lib.sd_model_set_prefill_attention(self.handle, _prefill_attention_id(name)), "sd_model_set_prefill_attention")
+
+    @property
+    def prefill_attention(self) -> str:
+        return _PREFILL_ATTN_NAMES[self.lib.sd_model_prefill_attention(self.handle)]
+
+    def prefill_tiled_launches(self) -> int:
+        """Launches of the tiled prompt-attention kernel since the bind: one per chunk and layer."""
+        return int(self.lib.sd_model_prefill_tiled_launches(self.handle))
 
     def prefill_counts(self) -> dict:
         """Prompt rows absorbed per backend since the bind (one per row of a forward of >= 96 positions per row)."""

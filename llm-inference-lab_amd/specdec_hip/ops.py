@@ -928,6 +928,24 @@ def attention_cascade_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: in
     return CascadePlan(t, ns, sets, ps, slots, (gx, gy, gz))
 
 
+class PrefillAttentionPlan(NamedTuple):
+    pt: int                       # query positions per tile (16 or 32)
+    rows_per_wg: int              # stacked query rows of a workgroup: pt * Hq / Hkv rounded up to 16
+    waves: int                    # waves that own 16 rows each
+    tiles: int                    # ceil(Mc / pt); the grid is (Hkv, tiles)
+    n_split: int                  # workgroups per tile (always 1)
+    lds_bytes: int                # dynamic LDS of a workgroup
+
+
+def attention_prefill_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, Mc: int, l_max: int, paged: int = 0) -> PrefillAttentionPlan:
+    """The geometry of the tiled prompt-attention launch over one chunk of Mc <= 512 positions (csrc/attention_prefill.hip;
+    sd_attention_prefill_plan), from the function the launch itself consults. paged: 0 dense, else the page length. Host-only."""
+    out = [ctypes.c_int(0) for _ in range(6)]
+    _abi.check(_abi.load().sd_attention_prefill_plan(int(n_q_heads), int(n_kv_heads), int(head_dim), int(Mc), int(l_max), int(paged or 0),
+                                                     *(ctypes.byref(o) for o in out)), "sd_attention_prefill_plan")
+    return PrefillAttentionPlan(*(int(o.value) for o in out))
+
+
 class PersistPlan(NamedTuple):
     eligible: bool       # the model passes every static rule of the persistent forward
     max_tokens: int      # tokens one persistent pass can hold (0 when not eligible)

@@ -138,6 +138,8 @@ def get_kernel_info(model=None):
         "library": str(_abi.lib_path()),
         "library_loaded": lib_ok,
         "prefill_backends": _prefill_backends() if lib_ok else [],
+        # the attention of a GEMM-prefilled chunk (sd_model_set_prefill_attention): the 128-position passes or csrc/attention_prefill.hip
+        "prefill_attention": list(_abi.PREFILL_ATTENTION) if lib_ok else [],
         # sequence log-likelihood on the device (sd_model_score: lm_head GEMM with a log-softmax epilogue, csrc/score_head.hip)
         "score_head": "hip" if lib_ok else "unavailable",
         # draft-target agreement of two logit blocks (sd_spec_agreement, csrc/spec_agree.hip)

@@ -216,6 +216,8 @@ class SpeculativePipeline:
             for lm in (self.base_lm, self.draft_lm):
                 if lm is not None:
                     lm.set_kv_dtype(str(self.config["kv_cache_dtype"]), lm.kv_scales)
+        if not self._fake and self.config.get("prefill_attention") is not None:   # both engines of the pipeline: "passes" or "tiled"
+            self.set_prefill_attention(str(self.config["prefill_attention"]))
         if self.draft_lm is not None and self.base_lm.vocab_size != self.draft_lm.vocab_size:
             raise ValueError(f"draft/base vocabularies differ: {self.draft_lm.vocab_size} vs {self.base_lm.vocab_size}")
         self.speculative_enabled = True
@@ -264,6 +266,18 @@ class SpeculativePipeline:
         self._grammar_unions, self._grammar_regexes = {}, {}
 
     # ------------------------------------------------------------------ configuration
+    def set_prefill_attention(self, name: str) -> None:
+        """The attention of a GEMM-prefilled prompt chunk on both models ("passes" or "tiled"; HipModel.set_prefill_attention): read
+        when an engine is created, so engines the models hold are dropped."""
+        from specdec_hip import _abi
+
+        if name not in _abi.PREFILL_ATTENTION:
+            raise ValueError(f"prefill_attention={name!r} (one of {', '.join(_abi.PREFILL_ATTENTION)})")
+        for lm in (self.base_lm, self.draft_lm):
+            if lm is not None and hasattr(lm, "prefill_attention"):
+                lm.prefill_attention = name
+                lm._model, lm._cached = None, []
+
     def _load_config(self, config_path: Optional[str]) -> Dict[str, Any]:
         """Flat YAML merged over the defaults (pipeline.py:398-438)."""
         cfg = dict(_DEFAULTS)

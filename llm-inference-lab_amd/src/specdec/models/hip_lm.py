@@ -83,9 +83,12 @@ class HipLM(LanguageModel):
     def __init__(self, weights: W.ModelWeights, tokenizer: Any = None, name: Optional[str] = None,
                  max_len: int = 1024, batch: int = 1, device: str = "cuda", weight_dtype: str = "bf16",
                  kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto",
-                 kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade_attention: bool = False):
+                 kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade_attention: bool = False,
+                 prefill_attention: str = "passes"):
         if prefill_backend not in _abi.PREFILL_BACKENDS:
             raise ValueError(f"prefill_backend={prefill_backend!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
+        if prefill_attention not in _abi.PREFILL_ATTENTION:
+            raise ValueError(f"prefill_attention={prefill_attention!r} (one of {', '.join(_abi.PREFILL_ATTENTION)})")
         if cascade_attention and kv_dtype == "fp8":
             raise ValueError("cascade_attention is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked)")
         # engines created by this model read keys that rows share once per group (HipModel cascade / set_shared_prefix)
@@ -106,6 +109,8 @@ class HipLM(LanguageModel):
         self.kv_page_len, self.kv_pages = kv_page_len, kv_pages
         # how the engines absorb prompts (HipModel.set_prefill_backend): "auto", "passes", "rocblas" or "native"
         self.prefill_backend = prefill_backend
+        # the attention of a GEMM-prefilled chunk (HipModel.set_prefill_attention): "passes" or "tiled"; both engines of a pipeline
+        self.prefill_attention = prefill_attention
         self._model: Optional[HipModel] = None
         # element type of the engines' KV caches (HipModel kv_dtype): "bf16", or "fp8" = e4m3 bytes with the scales (k, v)
         self.set_kv_dtype(kv_dtype, kv_scales)
@@ -128,7 +133,7 @@ class HipLM(LanguageModel):
         """A forward instance with its own KV cache over the shared weights. cascade: None = this model's cascade_attention."""
         return HipModel(self.weights, batch=batch, l_max=l_max, device=self._device, weight_dtype=self.weight_dtype,
                         page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend,
-                        kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales,
+                        prefill_attention=self.prefill_attention, kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales,
                         cascade=self.cascade_attention if cascade is None else bool(cascade))
 
     def _engine(self, batch: int, need_len: int) -> HipModel:

@@ -69,6 +69,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--n", type=int, default=1,
                     help="n completions of the prompt as n rows of one generate_batch call: the prompt is prefilled once and the other "
                          "rows are forked from it (implies --share-prefix); they differ under --spec-sampling (a Philox stream per row)")
+    ap.add_argument("--prefill-attention", type=str, choices=["passes", "tiled"], default=None,
+                    help="the attention of a GEMM-prefilled prompt chunk: passes (128 query positions per launch of the decode-shaped "
+                         "kernel; the default) or tiled (one launch of the prompt kernel per chunk: K / V staged through LDS once per "
+                         "tile of query rows); the config key prefill_attention")
     ap.add_argument("--cascade-attention", action="store_true",
                     help="with --share-prefix / --n: the target's attention reads what the forked rows share once per group "
                          "(cascade_attention=True; groups of at least the config key cascade_min_shared positions)")
@@ -216,6 +220,8 @@ def main(argv=None) -> int:
         for lm in (pipe.base_lm, pipe.draft_lm):
             if lm is not None and hasattr(lm, "prefill_backend"):
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
+        if args.prefill_attention is not None:
+            pipe.set_prefill_attention(args.prefill_attention)
         conf = args.draft_confidence is not None
         lp = args.logprobs is not None or args.best_of is not None
         roll = args.context_window is not None
