@@ -385,6 +385,19 @@ size_t sd_model_kv_bytes(const sd_model* m, int B, int Lmax);
  * sd_model_kv_evict (re-rotating an e4m3 key is lossy). Not built yet: paged fp8 KV, fork / evict on fp8 caches, the
  * persistent forward over an fp8 cache, per-head or per-token scales. sd_model_config is unchanged. */
 int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, float v_scale);
+/* Sliding-window attention (csrc/attention_window.hip), set between sd_model_create and a bind like the kv dtype. Additive
+ * (SD_ABI_VERSION stays 1). With W >= 1 the query at absolute position p attends to exactly the keys max(0, p - W + 1) .. p: W
+ * keys including its own, the rule of models trained with a local window (Mistral-7B-v0.1: sliding_window 4096). W = 0 (the
+ * default) is off and leaves every launch what it is. Only what attention READS changes: the cache is sized and appended as ever
+ * (no rolling W-slot buffer), dense or paged, and sd_model_kv_fork / sd_model_kv_copy_pages work unchanged. Every attention launch
+ * of the model — the 1-9 token forwards, the multi-token passes, both attentions of the GEMM prompt route — walks the window's key
+ * blocks only, so its cost follows W, not the row's length. Such a model runs every pass on the launch path (the persistent
+ * forward is ineligible at bind). Refused before any device work, with a message that names sliding_window: W < 0, a bound model,
+ * a GPT-2 model, head_dim other than 64 or 128, an fp8 (e4m3) kv dtype (and sd_model_set_kv_dtype to fp8 afterwards), cascade
+ * attention (and sd_model_set_cascade afterwards), and sd_model_kv_evict on such a model. sd_model_sliding_window: the configured
+ * W; -1 for a NULL model. */
+int sd_model_set_sliding_window(sd_model* m, int W);
+int sd_model_sliding_window(const sd_model* m);
 /* Attach caller-owned KV caches and workspace. */
 int sd_model_bind(sd_model* m, void* k_cache, void* v_cache, int B, int Lmax,
                   void* workspace, size_t workspace_bytes);
@@ -684,6 +697,17 @@ int sd_attention_cascade_plan(int n_q_heads, int n_kv_heads, int head_dim, int B
  * l_max not a multiple of 8, pages not 32 * 2^n positions or l_max not whole pages. */
 int sd_attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int paged, int* pt, int* rows_per_wg,
                               int* waves, int* tiles, int* n_split, int* lds_bytes);
+
+/* The same for a sliding-window launch (sd_model_set_sliding_window; csrc/attention_window.hip) of window W >= 1: *tiles and the grid
+ * as sd_attention_plan; *n_split is sized from min(l_max, W + M) — the keys a tile can walk — in place of l_max, under the same
+ * caps (a row uses min(n_split, ceil(blocks of its span / 16)) of them); *max_blocks = the most 32-key blocks any tile of the
+ * launch walks, <= (W + M) / 32 + 2. Refused as sd_attention_plan, and W < 1, head_dim not 64 / 128, M above 128.
+ * sd_attention_prefill_window_blocks: the most 64-key blocks a tile of the tiled prompt kernel walks under W, <= (W + pt) / 64 + 2,
+ * with the geometry sd_attention_prefill_plan reports for the same arguments; < 0 where that query refuses or W < 1 (sd_last_error).
+ * Host-only, additive (SD_ABI_VERSION stays 1). */
+int sd_attention_window_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int W, int* tiles,
+                             int* n_split, int* grid_x, int* grid_y, int* grid_z, int* max_blocks);
+int sd_attention_prefill_window_blocks(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int paged, int W);
 
 /* Diagnostics of the persistent forward (csrc/persist.hip); host-only, additive (SD_ABI_VERSION stays 1).
  *

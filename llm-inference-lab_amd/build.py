@@ -74,6 +74,8 @@ FILE_FLAGS = {
     "attention_cascade.hip": ["-O3", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # csrc/attention_prefill.hip: the same softmax rescaling of accumulator pairs, built the same way
     "attention_prefill.hip": ["-O3", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # csrc/attention_window.hip: the same
+    "attention_window.hip": ["-O3", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

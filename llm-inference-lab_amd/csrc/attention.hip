@@ -101,6 +101,7 @@ int attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, in
 }
 
 int launch_attention(const AttnArgs& a_in, hipStream_t st) {
+  if (a_in.window > 0) return launch_attention_window(a_in, st);   // sliding-window attention: csrc/attention_window.hip, with a plan of its own
   AttnArgs a = a_in;
   AttnPlan pl{};
   if (int rc = attention_plan(a.n_q_heads, a.n_kv_heads, a.head_dim, a.B, a.M, a.l_max, a.block_table ? static_cast<int>(a.page_shift) : -1,

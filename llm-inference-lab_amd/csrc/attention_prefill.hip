@@ -30,6 +30,14 @@
 //               dense rows and V^T pieces are clamped inside l_max as in attention_tile. What such a load returns stands for a key
 //               beyond the tile's last: its score is masked, and its V^T elements are zeroed while staging (0 x NaN is NaN).
 // Launched with 4 or 8 waves; waves beyond the tile's row count only stage. bf16 caches, dense or paged; head_dim 64 and 128.
+//
+// Sliding window (WIN instances; sd_model_set_sliding_window, see attention_window.hip for the decode-shaped kernel): position p sees
+// keys max(0, p - W + 1) .. p. The block walk starts at max(0, first - W + 1) / 64 — blocks below it are never staged — and a block
+// that holds some row's window start (key0 < last - W + 1) takes a lower-edge instantiation of the block body, which adds the compare
+// key >= my_limit - W + 1; a tile of 16 positions under W >= 64 meets at most two of them. A block can be lower edge and diagonal at
+// once (W < 64 or a window not yet full): the doubly masked instantiation. Keys of a staged block below a row's window are real,
+// finite, stale: P = 0 there and nothing is zeroed. Resources of the D = 128 WIN instances (hipcc --save-temps, gfx950): see the
+// header of attention_window.hip.
 
 #include "attention_device.h"
 #include "prefill_gemm.h"
@@ -52,9 +60,10 @@ struct PfLds {
 };
 
 // One 64-key block for one wave: S^T, softmax update, P V. kb / vb: the block's LDS buffers. MASK: compare keys with positions.
-template <int D, bool MASK>
+// LOW: a lower edge of a windowed tile, compare keys with the row's window start my_lo as well.
+template <int D, bool MASK, bool LOW = false>
 __device__ __forceinline__ void pf_block(const uint16_t* kb, const uint16_t* vb, const u32x4 (&qf)[D / 32], int key0, int my_limit, float scale,
-                                         int g, int n, f32x4_t (&oacc)[D / 16], float& m_run, float& l_run) {
+                                         int g, int n, f32x4_t (&oacc)[D / 16], float& m_run, float& l_run, int my_lo = 0) {
   constexpr int NKS = D / 32, NDT = D / 16;
   constexpr int KS = PfLds<D>::KS, VS = PfLds<D>::VS;
   f32x4_t st[4];
@@ -80,6 +89,10 @@ __device__ __forceinline__ void pf_block(const uint16_t* kb, const uint16_t* vb,
         const int key = key0 + 32 * (t >> 1) + 8 * g + 4 * (t & 1) + r;
         v = (key <= my_limit) ? v : -INFINITY;
       }
+      if constexpr (LOW) {
+        const int key = key0 + 32 * (t >> 1) + 8 * g + 4 * (t & 1) + r;
+        v = (key >= my_lo) ? v : -INFINITY;
+      }
       sc[4 * t + r] = v;
       mx = fmaxf(mx, v);
     }
@@ -88,8 +101,8 @@ __device__ __forceinline__ void pf_block(const uint16_t* kb, const uint16_t* vb,
   const float m_new = fmaxf(m_run, mx);
   float alpha, psum = 0.f;
   float p[16];
-  if constexpr (MASK) {
-    // a row may see nothing of a diagonal block (never of block 0: key 0 is visible to every position)
+  if constexpr (MASK || LOW) {
+    // a row may see nothing of a diagonal block (never of block 0: key 0 is visible to every position), nor of a lower-edge one
     alpha = (m_run > -INFINITY) ? __expf(m_run - m_new) : 0.f;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
@@ -130,8 +143,8 @@ __device__ __forceinline__ void pf_block(const uint16_t* kb, const uint16_t* vb,
   }
 }
 
-// NWT: waves launched (4 or 8). grid = (n_kv_heads, tiles); block = NWT * 64; dynamic LDS = PfLds<D>::BYTES.
-template <int D, bool PAGED, int NWT>
+// NWT: waves launched (4 or 8). grid = (n_kv_heads, tiles); block = NWT * 64; dynamic LDS = PfLds<D>::BYTES. WIN: a.window >= 1.
+template <int D, bool PAGED, int NWT, bool WIN = false>
 __global__ __launch_bounds__(NWT * 64) void attention_prefill_kernel(const PrefillAttnArgs a) {
   constexpr int NT = NWT * 64, NKS = D / 32, NDT = D / 16;
   using L = PfLds<D>;
@@ -153,6 +166,8 @@ __global__ __launch_bounds__(NWT * 64) void attention_prefill_kernel(const Prefi
   const int last = min(first + pn, a.l_max) - 1;           // the tile's last key
   if (last < 0) return;
   const int n_blocks = last / kPfBlock + 1;
+  const int blk_lo = WIN ? max(0, first - a.window + 1) / kPfBlock : 0;   // first block any row of the tile sees
+  const int lo_max = WIN ? last - a.window + 1 : 0;                       // the latest window start among the tile's rows
   const int HqD = a.n_q_heads * D;
 
   // ---- this wave's rows: Q fragments, lane (g, n) holds Q[row n][32 s + 8 g .. +8]
@@ -234,17 +249,24 @@ __global__ __launch_bounds__(NWT * 64) void attention_prefill_kernel(const Prefi
     }
   };
 
-  fetch(0);
+  fetch(blk_lo);
   stage(0);
   __syncthreads();
-  for (int blk = 0; blk < n_blocks; ++blk) {
-    const int buf = blk & 1;
+  for (int blk = blk_lo; blk < n_blocks; ++blk) {
+    const int buf = (blk - blk_lo) & 1;
     if (blk + 1 < n_blocks) fetch(blk + 1);               // in flight during the MFMAs below
     if (computes) {
       const uint16_t* kb = lds + buf * L::BUF;
       const uint16_t* vb = kb + L::K_ELEMS;
       const int key0 = blk * kPfBlock;
-      if (key0 + kPfBlock - 1 <= first) pf_block<D, false>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run);
+      if constexpr (WIN) {
+        const bool low = key0 < lo_max, diag = key0 + kPfBlock - 1 > first;   // workgroup-uniform
+        const int my_lo = my_limit - a.window + 1;
+        if (low && diag) pf_block<D, true, true>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run, my_lo);
+        else if (low) pf_block<D, false, true>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run, my_lo);
+        else if (diag) pf_block<D, true>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run);
+        else pf_block<D, false>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run);
+      } else if (key0 + kPfBlock - 1 <= first) pf_block<D, false>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run);
       else pf_block<D, true>(kb, vb, qf, key0, my_limit, a.scale, g, n, oacc, m_run, l_run);
     }
     if (blk + 1 < n_blocks) stage(buf ^ 1);               // last read before the previous barrier
@@ -265,12 +287,12 @@ __global__ __launch_bounds__(NWT * 64) void attention_prefill_kernel(const Prefi
   }
 }
 
-template <int D, bool PAGED, int NWT>
+template <int D, bool PAGED, int NWT, bool WIN = false>
 int launch_instance(const PrefillAttnArgs& a, const PrefillAttnPlan& pl, hipStream_t st) {
   static unsigned long long seen = 0;
-  const void* fn = reinterpret_cast<const void*>(&attention_prefill_kernel<D, PAGED, NWT>);
+  const void* fn = reinterpret_cast<const void*>(&attention_prefill_kernel<D, PAGED, NWT, WIN>);
   if (int rc = opt_in_dynamic_lds(fn, PfLds<D>::BYTES, seen)) return rc;
-  hipLaunchKernelGGL((attention_prefill_kernel<D, PAGED, NWT>), dim3(a.n_kv_heads, pl.tiles), dim3(NWT * 64), PfLds<D>::BYTES, st, a);
+  hipLaunchKernelGGL((attention_prefill_kernel<D, PAGED, NWT, WIN>), dim3(a.n_kv_heads, pl.tiles), dim3(NWT * 64), PfLds<D>::BYTES, st, a);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -278,6 +300,10 @@ int launch_instance(const PrefillAttnArgs& a, const PrefillAttnPlan& pl, hipStre
 template <int D>
 int launch_d(const PrefillAttnArgs& a, const PrefillAttnPlan& pl, hipStream_t st) {
   const bool paged = a.block_table != nullptr;
+  if (a.window > 0) {
+    if (pl.threads == 256) return paged ? launch_instance<D, true, 4, true>(a, pl, st) : launch_instance<D, false, 4, true>(a, pl, st);
+    return paged ? launch_instance<D, true, 8, true>(a, pl, st) : launch_instance<D, false, 8, true>(a, pl, st);
+  }
   if (pl.threads == 256) return paged ? launch_instance<D, true, 4>(a, pl, st) : launch_instance<D, false, 4>(a, pl, st);
   return paged ? launch_instance<D, true, 8>(a, pl, st) : launch_instance<D, false, 8>(a, pl, st);
 }
@@ -315,11 +341,20 @@ int attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, 
   return 0;
 }
 
+int attention_prefill_window_blocks(const PrefillAttnPlan& plan, int l_max, int W) {
+  // W + pt - 1 consecutive keys at most (the first row's window start .. the tile's last key), and never more than the row has
+  const long long reach = static_cast<long long>(W) + plan.pt - 1;
+  const int keys = reach < l_max ? static_cast<int>(reach) : l_max;
+  const int row_blocks = (l_max + kPfBlock - 1) / kPfBlock, walk = (keys + kPfBlock - 2) / kPfBlock + 1;
+  return walk < row_blocks ? walk : row_blocks;
+}
+
 int launch_attention_prefill(const PrefillAttnArgs& a_in, hipStream_t st) {
   PrefillAttnArgs a = a_in;
   PrefillAttnPlan pl{};
   if (int rc = attention_prefill_plan(a.n_q_heads, a.n_kv_heads, a.head_dim, a.Mc, a.l_max, a.block_table ? a.page_shift : -1, pl)) return rc;
   SD_REQUIRE(a.q && a.k_cache && a.v_cache && a.out && a.pos_base, "attention_prefill: NULL argument");
+  SD_REQUIRE(a.window >= 0, "attention_prefill: sliding_window W=%d is negative", a.window);
   a.pt = pl.pt;
   return a.head_dim == 64 ? launch_d<64>(a, pl, st) : launch_d<128>(a, pl, st);
 }

@@ -18,6 +18,8 @@ struct sd_model {
   // sd_model_set_kv_dtype: the caches hold OCP e4m3 bytes, element x stored as e4m3(clamp(x / kv_scale, +-448)) (0: K, 1: V)
   int kv8 = 0;
   float kv_scale[2] = {1.0f, 1.0f};
+  // sd_model_set_sliding_window: every attention launch reads the keys max(0, p - window + 1) .. p of query position p (0: off)
+  int window = 0;
   uint16_t* kv_at(uint16_t* cache, size_t elems) const {   // element `elems` of a cache (bf16: 2 bytes, e4m3: 1)
     return kv8 ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(cache) + elems) : cache + elems;
   }

@@ -206,6 +206,7 @@ static int launch_pass(sd_model* m, const Pass& p, hipStream_t st) {
     at.page_shift = m->page_shift;
     at.skip_k = m->skip_k;
     at.skip_i = m->skip_i;
+    at.window = m->window;
     if (m->cascade) {
       // the cascade launch (csrc/attention_cascade.hip): the layer's whole caches and table (a group's leader may sit outside this
       // pass's rows), the mode's own workspace
@@ -324,6 +325,7 @@ static int prefill_row(sd_model* m, int backend, const int32_t* tokens, const in
     pm.plan = &m->native_plan;
   }
   pm.attn_tiled = m->prefill_attention == SD_PREFILL_ATTN_TILED;
+  pm.window = m->window;
   for (int m0 = 0; m0 < M; m0 += kPrefillChunk) {
     const int mc = (M - m0 < kPrefillChunk) ? M - m0 : kPrefillChunk;
     PrefillRows rows;

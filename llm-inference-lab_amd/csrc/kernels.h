@@ -216,8 +216,11 @@ struct AttnArgs {
   const int32_t* share;
   int row0;
   unsigned c_split : 8;   // workgroups per prefix tile set (set by launch_attention_cascade)
+  // sliding-window attention (attention_window.hip; read by its kernel only): query position p sees keys max(0, p - window + 1) .. p.
+  // 0 = off: launch_attention is what it was. Last in the block (no other field moves).
+  int window;
 };
-int launch_attention(const AttnArgs& a, hipStream_t st);
+int launch_attention(const AttnArgs& a, hipStream_t st);   // a.window > 0: launch_attention_window
 int launch_attention_kv8(const AttnArgs& a, dim3 grid, hipStream_t st);   // attention_kv8.hip; a.n_split and grid from launch_attention
 constexpr int kAttnSplitSlots = 1024;   // partial tiles of the split-KV workspace
 // The geometry of one attention launch, decided on the host from dimensions alone: launch_attention consults it and
@@ -227,6 +230,13 @@ constexpr int kAttnSplitSlots = 1024;   // partial tiles of the split-KV workspa
 struct AttnPlan { int tiles, n_split, grid_x, grid_y, grid_z; };
 int attention_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int page_shift, bool has_split_ws,
                    int split_slots, AttnPlan& plan);
+// Sliding-window attention (attention_window.hip): the launch of a.window = W >= 1 over bf16 caches, dense or paged, head_dim 64 / 128,
+// M <= 128. Its plan (sd_attention_window_plan reports it): attn as attention_plan's, with n_split sized from min(l_max, W + M) — the
+// keys a tile can walk — in place of l_max; max_blocks: the most 32-key blocks any tile of the launch walks, <= (W + M) / 32 + 2.
+struct AttnWindowPlan { AttnPlan attn; int max_blocks; };
+int attention_window_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int page_shift, bool has_split_ws,
+                          int split_slots, int W, AttnWindowPlan& plan);
+int launch_attention_window(const AttnArgs& a, hipStream_t st);
 size_t attention_split_ws_bytes(int head_dim);   // workspace for kAttnSplitSlots partial tiles (+ counters)
 size_t attention_split_tiles_bytes(int head_dim);   // the partial tiles of it (split_ws); the kAttnSplitSlots counters (split_cnt) follow
 // Cascade attention (attention_cascade.hip): one launch whose prefix workgroups read a group's shared keys once for all its member
@@ -254,6 +264,7 @@ struct PrefillAttnArgs {
   int n_q_heads, n_kv_heads, head_dim, page_shift;
   int pt;                       // set by launch_attention_prefill
   float scale;
+  int window;                   // sliding-window attention: position p sees keys max(0, p - window + 1) .. p; 0 = off (the plain instances)
 };
 // Its geometry, from dimensions alone (launch_attention_prefill consults it, sd_attention_prefill_plan reports it): pt = query
 // positions per tile (16 or 32), rows_per_wg = 16 * waves >= pt * G stacked query rows, waves = waves that own rows (the launch has
@@ -261,6 +272,9 @@ struct PrefillAttnArgs {
 // LDS of a workgroup; grid = (n_kv_heads, tiles). page_shift < 0: a dense cache.
 struct PrefillAttnPlan { int pt, rows_per_wg, waves, threads, tiles, n_split, lds_bytes; };
 int attention_prefill_plan(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int page_shift, PrefillAttnPlan& plan);
+// Under a window W >= 1 the geometry is the same and a tile walks the 64-key blocks from max(0, first - W + 1) / 64 on: the most any
+// tile of a launch with this plan walks, <= (W + pt) / 64 + 2 (sd_attention_prefill_window_blocks reports it).
+int attention_prefill_window_blocks(const PrefillAttnPlan& plan, int l_max, int W);
 // The one rule that admits a model to the mode: null, or why not
 const char* attention_prefill_refusal(int arch, int head_dim, int n_q_heads, int n_kv_heads, bool kv8);
 int launch_attention_prefill(const PrefillAttnArgs& a, hipStream_t st);

@@ -98,7 +98,8 @@ static int setup_persist(sd_model* m) {
   // (a cache whose rows are not whole 8-key vectors cannot be walked by the launch's attention: launch path)
   // (nor does the launch read an e4m3 cache: an fp8-KV model runs every pass on the launch path)
   // (nor does it know the shared-prefix table: a cascade model runs every pass on the launch path, as a session past its length hint)
-  m->persist_cap = (persist_cache_ok(m->Lmax) && !m->kv8 && !m->cascade) ? persist_max_tokens(c) : 0;
+  // (nor a window: the launch's attention walks the whole row, so a sliding-window model runs every pass on the launch path)
+  m->persist_cap = (persist_cache_ok(m->Lmax) && !m->kv8 && !m->cascade && !m->window) ? persist_max_tokens(c) : 0;
   // tokens per pass the persistent launch takes (0 = off), by measurement (same box, 128 cached positions, us per forward,
   // persistent / launches; profiles/round3_persist_ab.md): Llama-3.2-1B dimensions 1 token 596 / 698, 2 tokens 677 / 718,
   // 3 tokens 838 / 741; Llama-3.2-3B dimensions 1 token 1506 / 1495, 2 tokens 1640 / 1540. So: 2 tokens up to
@@ -304,6 +305,7 @@ extern "C" int sd_model_set_kv_dtype(sd_model* m, int dtype, float k_scale, floa
   SD_REQUIRE(k_scale > 0.f && v_scale > 0.f && k_scale - k_scale == 0.f && v_scale - v_scale == 0.f,
              "model_set_kv_dtype: kv scales must be positive and finite (got %g, %g)", static_cast<double>(k_scale), static_cast<double>(v_scale));
   SD_REQUIRE(dtype != SD_FP8_E4M3 || !m->cascade, "model_set_kv_dtype: an fp8 (e4m3) kv dtype is not available with cascade attention (an e4m3 cache is not forked)");
+  SD_REQUIRE(dtype != SD_FP8_E4M3 || !m->window, "model_set_kv_dtype: an fp8 (e4m3) kv dtype is not available with sliding_window (the window kernels read bf16 caches)");
   SD_REQUIRE(dtype != SD_FP8_E4M3 || m->prefill_attention != SD_PREFILL_ATTN_TILED, "model_set_kv_dtype: %s",
              attention_prefill_refusal(m->cfg.arch, m->cfg.head_dim, m->cfg.n_heads, m->cfg.n_kv_heads, true));
   m->kv8 = dtype == SD_FP8_E4M3;
@@ -317,9 +319,28 @@ extern "C" int sd_model_set_cascade(sd_model* m, int enable) {
   SD_REQUIRE(m, "model_set_cascade: NULL model");
   SD_REQUIRE(!m->k_cache, "model_set_cascade: cascade attention is set between sd_model_create and sd_model_bind (this model is bound)");
   SD_REQUIRE(!enable || !m->kv8, "model_set_cascade: not available with an fp8 (e4m3) kv dtype (an e4m3 cache is not forked)");
+  SD_REQUIRE(!enable || !m->window, "model_set_cascade: not available with sliding_window (the cascade launch reads whole rows)");
   m->cascade = enable ? 1 : 0;
   return 0;
 }
+
+extern "C" int sd_model_set_sliding_window(sd_model* m, int W) {
+  clear_error();
+  SD_REQUIRE(m, "model_set_sliding_window: NULL model");
+  SD_REQUIRE(!m->k_cache, "model_set_sliding_window: sliding_window is set between sd_model_create and sd_model_bind (this model is bound)");
+  SD_REQUIRE(W >= 0, "model_set_sliding_window: sliding_window W=%d is negative (0 = off)", W);
+  if (W > 0) {
+    SD_REQUIRE(m->cfg.arch == SD_ARCH_LLAMA, "model_set_sliding_window: sliding_window serves Llama-architecture models only (this model is GPT-2)");
+    SD_REQUIRE(m->cfg.head_dim == 64 || m->cfg.head_dim == 128, "model_set_sliding_window: sliding_window covers head_dim 64 and 128 only (got %d)",
+               m->cfg.head_dim);
+    SD_REQUIRE(!m->kv8, "model_set_sliding_window: sliding_window is not available with an fp8 (e4m3) kv dtype (the window kernels read bf16 caches)");
+    SD_REQUIRE(!m->cascade, "model_set_sliding_window: sliding_window is not available with cascade attention (the cascade launch reads whole rows)");
+  }
+  m->window = W;
+  return 0;
+}
+
+extern "C" int sd_model_sliding_window(const sd_model* m) { return m ? m->window : -1; }
 
 extern "C" int sd_model_set_shared_prefix(sd_model* m, int row, int leader, int shared_len, void* stream) {
   clear_error();
@@ -454,6 +475,7 @@ extern "C" int sd_model_kv_evict(sd_model* m, int row, int keep, int drop, int n
   SD_REQUIRE(m, "kv_evict: NULL model");
   SD_REQUIRE(!m->kv8, "kv_evict: not available with an fp8 (e4m3) kv dtype (re-rotating an e4m3 key is lossy)");
   SD_REQUIRE(!m->cascade, "kv_evict: not available with cascade attention (a shared prefix does not move)");
+  SD_REQUIRE(!m->window, "kv_evict: not available with sliding_window (context_window moves keys; a window only masks them)");
   SD_REQUIRE(m->k_cache && m->x, "kv_evict: model not bound (sd_model_bind)");
   SD_REQUIRE(!m->block_table, "kv_evict: this model is bound to a paged cache (eviction covers dense caches)");
   const sd_model_config& c = m->cfg;

@@ -223,6 +223,42 @@ extern "C" int sd_attention_prefill_plan(int n_q_heads, int n_kv_heads, int head
   return 0;
 }
 
+extern "C" int sd_attention_window_plan(int n_q_heads, int n_kv_heads, int head_dim, int B, int M, int l_max, int paged, int W, int* tiles,
+                                        int* n_split, int* grid_x, int* grid_y, int* grid_z, int* max_blocks) {
+  clear_error();
+  SD_REQUIRE(tiles && n_split && grid_x && grid_y && grid_z && max_blocks, "attention_window_plan: NULL argument");
+  SD_REQUIRE(n_q_heads >= 1 && n_q_heads <= 255 && n_kv_heads >= 0 && n_kv_heads <= 255 && M <= 255 && B <= (1 << 16),
+             "attention_window_plan: Hq=%d Hkv=%d M=%d B=%d beyond what a launch holds (heads and M <= 255)", n_q_heads, n_kv_heads, M, B);
+  int page_shift = -1;   // as sd_attention_plan
+  if (paged != 0) {
+    page_shift = 0;
+    while (page_shift < 30 && (1 << page_shift) < paged) ++page_shift;
+    if (paged < 0 || (1 << page_shift) != paged) page_shift = 0;
+  }
+  AttnWindowPlan pl{};
+  if (int rc = attention_window_plan(n_q_heads, n_kv_heads, head_dim, B, M, l_max, page_shift, true, kAttnSplitSlots, W, pl)) return rc;
+  *tiles = pl.attn.tiles; *n_split = pl.attn.n_split; *max_blocks = pl.max_blocks;
+  *grid_x = pl.attn.grid_x; *grid_y = pl.attn.grid_y; *grid_z = pl.attn.grid_z;
+  return 0;
+}
+
+extern "C" int sd_attention_prefill_window_blocks(int n_q_heads, int n_kv_heads, int head_dim, int Mc, int l_max, int paged, int W) {
+  clear_error();
+  int page_shift = -1;   // as sd_attention_plan
+  if (paged != 0) {
+    page_shift = 0;
+    while (page_shift < 30 && (1 << page_shift) < paged) ++page_shift;
+    if (paged < 0 || (1 << page_shift) != paged) page_shift = 0;
+  }
+  PrefillAttnPlan pl{};
+  if (attention_prefill_plan(n_q_heads, n_kv_heads, head_dim, Mc, l_max, page_shift, pl)) return -1;
+  if (W < 1) {
+    set_error("attention_prefill_window_blocks: sliding_window W=%d (>= 1)", W);
+    return -1;
+  }
+  return attention_prefill_window_blocks(pl, l_max, W);
+}
+
 extern "C" int sd_persist_plan(int arch, int n_layers, int d_model, int n_heads, int n_kv_heads, int head_dim, int d_ff, int vocab,
                                int packed, int weight_dtype, int has_bias, int T, int* eligible, int* max_tokens, int* ring_bytes,
                                char* name, size_t name_cap, char* reason, size_t reason_cap) {

@@ -97,6 +97,7 @@ struct PrefillModel {
   // step 2 of the layer loop: 0 = sub-passes of 128 query positions through launch_attention, 1 = one launch of the tiled prompt
   // kernel per chunk (csrc/attention_prefill.hip; sd_model_set_prefill_attention)
   int attn_tiled = 0;
+  int window = 0;       // sd_model_set_sliding_window: passed to either attention (0: off)
 };
 
 bool prefill_gemm_available();                               // rocBLAS could be opened (dlopen at first use) and a handle created

@@ -316,6 +316,7 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
       at.head_dim = D;
       at.page_shift = m.page_shift;
       at.scale = 1.0f / sqrtf(static_cast<float>(D));
+      at.window = m.window;
       if (int rc = launch_attention_prefill(at, st)) return rc;
     } else {
       for (int s0 = 0; s0 < Mc; s0 += 128) {
@@ -339,6 +340,7 @@ int prefill_gemm_chunk(const PrefillModel& m, const int32_t* tokens, const int32
         at.split_slots = kAttnSplitSlots;
         at.block_table = bt;
         at.page_shift = m.page_shift;
+        at.window = m.window;
         if (int rc = launch_attention(at, st)) return rc;
       }
     }

@@ -118,6 +118,10 @@ SIGNATURES = {
     "sd_model_workspace_bytes": (_c_size, [_c_void_p]),
     "sd_model_kv_bytes": (_c_size, [_c_void_p, _c_int, _c_int]),
     "sd_model_set_kv_dtype": (_c_int, [_c_void_p, _c_int, ctypes.c_float, ctypes.c_float]),
+    "sd_model_set_sliding_window": (_c_int, [_c_void_p, _c_int]),
+    "sd_model_sliding_window": (_c_int, [_c_void_p]),
+    "sd_attention_window_plan": (_c_int, [_c_int] * 8 + [ctypes.POINTER(_c_int)] * 6),
+    "sd_attention_prefill_window_blocks": (_c_int, [_c_int] * 7),
     "sd_model_bind": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_size]),
     "sd_model_kv_pool_bytes": (_c_size, [_c_void_p, _c_int, _c_int]),
     "sd_model_bind_paged": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size]),

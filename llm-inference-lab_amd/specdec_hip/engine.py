@@ -131,13 +131,24 @@ def prefill_backends_available() -> List[str]:
     return [name for name, v in _abi.PREFILL_BACKENDS.items() if lib.sd_prefill_backend_available(v)]
 
 
+def check_sliding_window(sliding_window, kv_dtype: str = "bf16", cascade: bool = False) -> None:
+    """What the library refuses of a sliding_window setting (sd_model_set_sliding_window), before any device work"""
+    w = int(sliding_window or 0)
+    if w < 0:
+        raise ValueError(f"sliding_window={sliding_window} is negative (0 = off)")
+    if w and kv_dtype == "fp8":
+        raise ValueError("sliding_window is not available with kv_cache_dtype fp8 (the window kernels read bf16 caches)")
+    if w and cascade:
+        raise ValueError("sliding_window is not available with cascade_attention (the cascade launch reads whole rows)")
+
+
 class HipModel:
     """A decoder (Llama or GPT-2 shaped) bound to its KV cache on one GPU."""
 
     def __init__(self, weights: ModelWeights, batch: int, l_max: int, device: Optional[torch.device] = None,
                  weight_dtype: str = "bf16", page_len: Optional[int] = None, n_pages: Optional[int] = None,
                  prefill_backend: str = "auto", kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade: bool = False,
-                 prefill_attention: str = "passes"):
+                 prefill_attention: str = "passes", sliding_window: int = 0):
         """weight_dtype "fp8": the engine streams an OCP e4m3 copy of the Linear weights (per-output-row
         scales, quantised on the device at load); activations stay bf16.
         kv_dtype "fp8" (kv_cache_dtype): the KV cache holds OCP e4m3 bytes, element x stored as e4m3(clamp(x / scale, +-448)) with
@@ -151,7 +162,11 @@ class HipModel:
         prefill_backend: how prompts (>= 96 positions per row) are absorbed — "auto" (rocBLAS where it serves the model, else
         the passes), "passes", "rocblas" or "native" (this library's GEMM over the packed weights); see set_prefill_backend.
         prefill_attention: the attention of a GEMM-prefilled chunk — "passes" (128 query positions per launch of the decode-shaped
-        kernel) or "tiled" (one launch of the prompt kernel per chunk, csrc/attention_prefill.hip); see set_prefill_attention."""
+        kernel) or "tiled" (one launch of the prompt kernel per chunk, csrc/attention_prefill.hip); see set_prefill_attention.
+        sliding_window W >= 1 (sd_model_set_sliding_window; csrc/attention_window.hip): the query at position p attends to the keys
+        max(0, p - W + 1) .. p only, as models trained with a local window expect (Mistral: 4096); 0 = off. The cache is sized and
+        appended as ever, dense or paged; every pass runs on the launch path; Llama models of head_dim 64 or 128; kv_dtype fp8,
+        cascade and evict_row are refused."""
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype={weight_dtype!r} (bf16 or fp8)")
         _prefill_backend_id(prefill_backend)
@@ -162,6 +177,8 @@ class HipModel:
             raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with page_len / SPECDEC_PAGED_KV")
         if cascade and kv_dtype == "fp8":
             raise ValueError("cascade_attention is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked)")
+        check_sliding_window(sliding_window, kv_dtype, cascade)
+        self.sliding_window = int(sliding_window or 0)
         self.weight_dtype = weight_dtype
         self.kv_dtype = kv_dtype
         self.cascade = bool(cascade)
@@ -238,6 +255,8 @@ class HipModel:
             self.set_kv_dtype(kv_dtype, self.kv_scales)
         if self.cascade:
             _abi.check(self.lib.sd_model_set_cascade(self.handle, 1), "sd_model_set_cascade")
+        if self.sliding_window:
+            _abi.check(self.lib.sd_model_set_sliding_window(self.handle, self.sliding_window), "sd_model_set_sliding_window")
         self.batch, self.l_max = int(batch), (int(l_max) + 31) // 32 * 32  # whole 32-key blocks
         self.page_len = None
         if page_len is not None or os.environ.get("SPECDEC_PAGED_KV"):
@@ -388,6 +407,8 @@ class HipModel:
         self._no_fp8_kv("evict_row (context_window)")
         if self.cascade:
             raise RuntimeError("evict_row (context_window) is not available with cascade_attention (a shared prefix does not move)")
+        if self.sliding_window:
+            raise RuntimeError("evict_row (context_window) is not available with sliding_window (eviction moves keys; a window only masks them)")
         with torch.cuda.device(self.device):
             _abi.check(self.lib.sd_model_kv_evict(self.handle, int(row), int(keep), int(drop), int(n_pos), _stream(stream, self.device)),
                        "sd_model_kv_evict")

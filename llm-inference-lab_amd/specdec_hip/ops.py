@@ -909,6 +909,23 @@ def attention_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: int, M: in
     return AttentionPlan(t, ns, (gx, gy, gz))
 
 
+class AttentionWindowPlan(NamedTuple):
+    tiles: int                    # as AttentionPlan
+    n_split: int                  # workgroups per tile, sized from min(l_max, W + M); a row uses min(n_split, ceil(blocks of its span / 16))
+    grid: Tuple[int, int, int]    # (Hkv, B, tiles * n_split)
+    max_blocks: int               # the most 32-key blocks any tile of the launch walks, <= (W + M) / 32 + 2
+
+
+def attention_window_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, B: int, M: int, l_max: int, W: int, paged: int = 0) -> AttentionWindowPlan:
+    """The geometry of one sliding-window attention launch of window W (csrc/attention_window.hip; sd_attention_window_plan), from the
+    function the launch itself consults. Arguments and environment as attention_plan. Host-only."""
+    out = [ctypes.c_int(0) for _ in range(6)]
+    _abi.check(_abi.load().sd_attention_window_plan(int(n_q_heads), int(n_kv_heads), int(head_dim), int(B), int(M), int(l_max), int(paged or 0),
+                                                    int(W), *(ctypes.byref(o) for o in out)), "sd_attention_window_plan")
+    t, ns, gx, gy, gz, mb = (int(o.value) for o in out)
+    return AttentionWindowPlan(t, ns, (gx, gy, gz), mb)
+
+
 class CascadePlan(NamedTuple):
     tiles: int                    # as AttentionPlan: they shape the suffix workgroups
     n_split: int
@@ -935,15 +952,22 @@ class PrefillAttentionPlan(NamedTuple):
     tiles: int                    # ceil(Mc / pt); the grid is (Hkv, tiles)
     n_split: int                  # workgroups per tile (always 1)
     lds_bytes: int                # dynamic LDS of a workgroup
+    max_blocks: int = 0           # window > 0: the most 64-key blocks a tile walks, <= (window + pt) / 64 + 2 (else 0: a tile walks its row)
 
 
-def attention_prefill_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, Mc: int, l_max: int, paged: int = 0) -> PrefillAttentionPlan:
+def attention_prefill_plan(n_q_heads: int, n_kv_heads: int, head_dim: int, Mc: int, l_max: int, paged: int = 0, window: int = 0) -> PrefillAttentionPlan:
     """The geometry of the tiled prompt-attention launch over one chunk of Mc <= 512 positions (csrc/attention_prefill.hip;
-    sd_attention_prefill_plan), from the function the launch itself consults. paged: 0 dense, else the page length. Host-only."""
+    sd_attention_prefill_plan), from the function the launch itself consults. paged: 0 dense, else the page length. window > 0: the
+    sliding-window instances (sd_attention_prefill_window_blocks), the same geometry with max_blocks filled in. Host-only."""
     out = [ctypes.c_int(0) for _ in range(6)]
     _abi.check(_abi.load().sd_attention_prefill_plan(int(n_q_heads), int(n_kv_heads), int(head_dim), int(Mc), int(l_max), int(paged or 0),
                                                      *(ctypes.byref(o) for o in out)), "sd_attention_prefill_plan")
-    return PrefillAttentionPlan(*(int(o.value) for o in out))
+    plan = PrefillAttentionPlan(*(int(o.value) for o in out))
+    if not window:
+        return plan
+    blocks = _abi.load().sd_attention_prefill_window_blocks(int(n_q_heads), int(n_kv_heads), int(head_dim), int(Mc), int(l_max), int(paged or 0), int(window))
+    _abi.check(1 if blocks < 0 else 0, "sd_attention_prefill_window_blocks")
+    return plan._replace(max_blocks=blocks)
 
 
 class PersistPlan(NamedTuple):

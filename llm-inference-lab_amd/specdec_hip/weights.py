@@ -43,6 +43,7 @@ class ModelConfig:
     tie_embeddings: bool = True
     eos_token_id: Optional[int] = None
     name: str = "tiny"
+    sliding_window: int = 0  # attention window of a Llama-architecture model trained with one (HF Mistral "sliding_window"); 0 = none
 
     @property
     def n_params_matmul(self) -> int:
@@ -216,6 +217,7 @@ def config_from_hf(hf_cfg) -> ModelConfig:
         max_pos=min(int(hf_cfg.max_position_embeddings), 8192), norm_eps=hf_cfg.rms_norm_eps,
         rope_theta=float(theta or 10000.0), rope_scaling=rs,
         tie_embeddings=bool(getattr(hf_cfg, "tie_word_embeddings", False)), eos_token_id=eos, name="llama-like",
+        sliding_window=int(getattr(hf_cfg, "sliding_window", None) or 0),   # Mistral-style checkpoints; null or absent: none
     )
 
 

@@ -218,6 +218,8 @@ class SpeculativePipeline:
                     lm.set_kv_dtype(str(self.config["kv_cache_dtype"]), lm.kv_scales)
         if not self._fake and self.config.get("prefill_attention") is not None:   # both engines of the pipeline: "passes" or "tiled"
             self.set_prefill_attention(str(self.config["prefill_attention"]))
+        if not self._fake and self.config.get("sliding_window") is not None:      # both engines of the pipeline: W, 0 = off
+            self.set_sliding_window(int(self.config["sliding_window"]))
         if self.draft_lm is not None and self.base_lm.vocab_size != self.draft_lm.vocab_size:
             raise ValueError(f"draft/base vocabularies differ: {self.draft_lm.vocab_size} vs {self.base_lm.vocab_size}")
         self.speculative_enabled = True
@@ -276,6 +278,20 @@ class SpeculativePipeline:
         for lm in (self.base_lm, self.draft_lm):
             if lm is not None and hasattr(lm, "prefill_attention"):
                 lm.prefill_attention = name
+                lm._model, lm._cached = None, []
+
+    def set_sliding_window(self, window: int) -> None:
+        """Sliding-window attention on both models (HipModel sliding_window; csrc/attention_window.hip): a query attends to the last
+        `window` keys only, 0 = off. A model whose own config carries a window (a Mistral-style checkpoint) keeps it. Read when an
+        engine is created, so engines the models hold are dropped. Refused: a negative window, kv_cache_dtype fp8, cascade_attention."""
+        from specdec_hip.engine import check_sliding_window
+
+        lms = [lm for lm in (self.base_lm, self.draft_lm) if lm is not None and hasattr(lm, "sliding_window")]
+        for lm in lms:
+            check_sliding_window(window, getattr(lm, "kv_cache_dtype", "bf16"), getattr(lm, "cascade_attention", False))
+        for lm in lms:
+            if not getattr(getattr(lm, "config", None), "sliding_window", 0):
+                lm.sliding_window = int(window)
                 lm._model, lm._cached = None, []
 
     def _load_config(self, config_path: Optional[str]) -> Dict[str, Any]:

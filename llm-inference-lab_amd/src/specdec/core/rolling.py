@@ -95,6 +95,9 @@ def _window(pipe, size, sinks, k: int, captured: bool, what: str, self_draft: bo
         if getattr(lm, "kv_cache_dtype", "bf16") != "bf16":
             raise NotImplementedError(f"context_window is not supported with kv_cache_dtype {lm.kv_cache_dtype}: eviction re-rotates the "
                                       "cached keys, which is lossy on an e4m3 cache")
+        if getattr(lm, "sliding_window", 0):
+            raise NotImplementedError(f"context_window is not supported with sliding_window={lm.sliding_window}: eviction moves the cached "
+                                      "keys, a sliding window only masks them")
     if share_prefix:
         raise NotImplementedError("share_prefix / n are not supported with context_window: forked rows would need their own eviction events")
     w = plan(size, 4 if sinks is None else sinks, k, LAUNCH_DEPTH, min(int(lm.config.max_pos) for lm in _models(pipe)))

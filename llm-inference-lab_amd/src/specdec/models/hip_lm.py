@@ -21,7 +21,7 @@ import torch
 
 from specdec_hip import _abi
 from specdec_hip import weights as W
-from specdec_hip.engine import EngineGaveUp, HipModel
+from specdec_hip.engine import EngineGaveUp, HipModel, check_sliding_window
 
 from ..cache.kv_types import KVCache
 from ..utils.interfaces import LanguageModel
@@ -84,7 +84,7 @@ class HipLM(LanguageModel):
                  max_len: int = 1024, batch: int = 1, device: str = "cuda", weight_dtype: str = "bf16",
                  kv_page_len: Optional[int] = None, kv_pages: Optional[int] = None, prefill_backend: str = "auto",
                  kv_dtype: str = "bf16", kv_scales: Sequence[float] = (1.0, 1.0), cascade_attention: bool = False,
-                 prefill_attention: str = "passes"):
+                 prefill_attention: str = "passes", sliding_window: Optional[int] = None):
         if prefill_backend not in _abi.PREFILL_BACKENDS:
             raise ValueError(f"prefill_backend={prefill_backend!r} (one of {', '.join(_abi.PREFILL_BACKENDS)})")
         if prefill_attention not in _abi.PREFILL_ATTENTION:
@@ -93,6 +93,10 @@ class HipLM(LanguageModel):
             raise ValueError("cascade_attention is not available with kv_cache_dtype fp8 (an e4m3 cache is not forked)")
         # engines created by this model read keys that rows share once per group (HipModel cascade / set_shared_prefix)
         self.cascade_attention = bool(cascade_attention)
+        # the attention window of the engines (HipModel sliding_window): None = what the weights' config carries (a Mistral-style
+        # checkpoint: 4096), 0 = off
+        self.sliding_window = int(getattr(weights.config, "sliding_window", 0) or 0) if sliding_window is None else int(sliding_window)
+        check_sliding_window(self.sliding_window, kv_dtype, self.cascade_attention)
         if not torch.cuda.is_available():
             raise RuntimeError("HipLM needs a GPU: this build has no CPU compute path")
         self._device = torch.device(device if device != "auto" else "cuda")
@@ -126,6 +130,7 @@ class HipLM(LanguageModel):
             raise ValueError("kv_cache_dtype fp8 serves dense caches only: not together with kv_page_len")
         if kv_dtype == "fp8" and self.cascade_attention:
             raise ValueError("kv_cache_dtype fp8 is not available with cascade_attention (an e4m3 cache is not forked)")
+        check_sliding_window(self.sliding_window, kv_dtype)
         self.kv_cache_dtype, self.kv_scales = kv_dtype, (float(kv_scales[0]), float(kv_scales[1]))
         self._model, self._cached = None, []
 
@@ -134,7 +139,7 @@ class HipLM(LanguageModel):
         return HipModel(self.weights, batch=batch, l_max=l_max, device=self._device, weight_dtype=self.weight_dtype,
                         page_len=self.kv_page_len, n_pages=self.kv_pages, prefill_backend=self.prefill_backend,
                         prefill_attention=self.prefill_attention, kv_dtype=self.kv_cache_dtype, kv_scales=self.kv_scales,
-                        cascade=self.cascade_attention if cascade is None else bool(cascade))
+                        cascade=self.cascade_attention if cascade is None else bool(cascade), sliding_window=self.sliding_window)
 
     def _engine(self, batch: int, need_len: int) -> HipModel:
         m = self._model

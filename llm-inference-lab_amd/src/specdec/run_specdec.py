@@ -73,6 +73,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="the attention of a GEMM-prefilled prompt chunk: passes (128 query positions per launch of the decode-shaped "
                          "kernel; the default) or tiled (one launch of the prompt kernel per chunk: K / V staged through LDS once per "
                          "tile of query rows); the config key prefill_attention")
+    ap.add_argument("--sliding-window", type=int, metavar="W", default=None,
+                    help="sliding-window attention on both models: a query attends to the last W keys only (models trained with a "
+                         "local window, e.g. Mistral-7B-v0.1: 4096; read from a checkpoint's config.json when it carries one); "
+                         "0 = off; the config key sliding_window. Not with --kv-cache-dtype fp8, --cascade-attention, --context-window")
     ap.add_argument("--cascade-attention", action="store_true",
                     help="with --share-prefix / --n: the target's attention reads what the forked rows share once per group "
                          "(cascade_attention=True; groups of at least the config key cascade_min_shared positions)")
@@ -222,6 +226,8 @@ def main(argv=None) -> int:
                 lm.prefill_backend = args.prefill_backend    # read when the pipeline creates its engines (first generate)
         if args.prefill_attention is not None:
             pipe.set_prefill_attention(args.prefill_attention)
+        if args.sliding_window is not None:
+            pipe.set_sliding_window(args.sliding_window)
         conf = args.draft_confidence is not None
         lp = args.logprobs is not None or args.best_of is not None
         roll = args.context_window is not None

@@ -82,6 +82,8 @@ def cmd_run(args: argparse.Namespace) -> int:
                                draft_mode="vanilla", kv_cache_dtype=args.kv_cache_dtype, **extra)
     if args.prefill_attention is not None:
         pipe.set_prefill_attention(args.prefill_attention)
+    if args.sliding_window is not None:
+        pipe.set_sliding_window(args.sliding_window)
     proc = {k: v for k, v in (("repetition_penalty", args.repetition_penalty), ("presence_penalty", args.presence_penalty),
                               ("frequency_penalty", args.frequency_penalty), ("bad_token_ids", args.ban_token)) if v is not None}
     if args.regex is not None:
@@ -190,6 +192,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--share-prefix", action="store_true", help="decode through generate_batch with share_prefix=True")
     pr.add_argument("--prefill-attention", type=str, choices=["passes", "tiled"], default=None,
                     help="the attention of a GEMM-prefilled prompt chunk: passes (the default) or tiled (one launch of the prompt kernel per chunk)")
+    pr.add_argument("--sliding-window", type=int, metavar="W", default=None,
+                    help="sliding-window attention on both models: a query attends to the last W keys only (0 = off)")
     pr.add_argument("--cascade-attention", action="store_true",
                     help="with --share-prefix / --n: the target's attention reads what the forked rows share once per group")
     pr.add_argument("prompt", type=str)
